@@ -70,6 +70,23 @@ def host_cores():
     return n
 
 
+DUMP_BYTES = 64 * 10**6
+DUMP_SAMPLE_PIXELS = 1 << 22  # 48 MiB of float32 RGB
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame whole if it fits in DUMP_BYTES, else the same seeded sample of its pixels on every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), frame)
+        return
+    pixels = frame.reshape(-1, 3)
+    pick = np.sort(np.random.default_rng(SEED).choice(len(pixels), DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), pixels[pick])
+
+
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -110,7 +127,14 @@ def parse_args():
                     help="N>1 dry run on a box with ONE GPU: every rank uses cuda:0 and goes through the same sol_comm_init / "
                          "sol_gather calls as a real run, over the test-only transport stub tests/stub_rccl (RCCL refuses two "
                          "ranks on one device); its throughput means nothing and the JSON line says so")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the frame the last timed step gave rank 0 (per-pixel sample sums, float32) to "
+                         "DIR/image.npy, shape (H, W, 3); a frame over 64 MB goes to DIR/image_sample.npy instead, shape (n, 3): the "
+                         "pixels of a fixed seeded sample, in row-major order")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---- rendezvous of the ranks: a tiny key-value store (set / blocking get / add) ------------------------------------------------
@@ -473,6 +497,9 @@ def worker(args):
         step()
     fence()
     dt = coord.max(time.perf_counter() - t0)
+    dump_frame = None
+    if args.dump_outputs and rank == 0:  # (copied now: the steps below render into the same buffers)
+        dump_frame = image.view(h, w, 3).cpu().numpy() if image is not None else ds.read_image()
     k_ms, grid = ds.last_kernel_ms()  # duration of the last step's (last) render kernel (HIP events on its stream)
     # what a scaling curve needs to explain itself: every rank's kernel time, and the gather timed on its own (one more, untimed,
     # gather of the accumulators the last step left: host clock around sol_gather + synchronise, maximum over the ranks)
@@ -669,6 +696,8 @@ def worker(args):
                                    "sample": f"full {w}x{h} frame, {n_spp} spp ({w * h * n_spp} samples, {tc:.1f} s), f64 restatement of the "
                                              f"reference algorithm (reference-order BVH search, no culling), row-parallel std::thread",
                                    "mrays_per_s": round(ost["rays"] / tc / 1e6, 3), "gpu_over_cpu": round(value / cpu_v, 1)}
+        if dump_frame is not None:
+            dump_outputs(args.dump_outputs, dump_frame)
         print(json.dumps(out), flush=True)
     coord.barrier()
 

@@ -42,6 +42,21 @@ def test_single_gpu_line_has_the_contract_fields():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and "spp" in cb["sample"]
 
 
+def test_dump_outputs_is_the_last_timed_frame(tmp_path):
+    """--dump-outputs DIR: the frame of the last timed step, as rank 0 received it, equals a plain render of the same scene and seed."""
+    import bench
+    from solstrale_amd import DeviceScene, RenderConfig, scenes
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--spp", "16", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--no-pmc", "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert _line(r.stdout)["steps"] == 2 and sorted(os.listdir(tmp_path)) == ["image.npy"]
+    img = np.load(tmp_path / "image.npy")
+    with DeviceScene(scenes.cornell_box(RenderConfig(400, 400, 16))) as ds:
+        ds.render(0, 16, bench.SEED)
+        ref = ds.read()
+    assert img.dtype == np.float32 and img.shape == (400, 400, 3) and np.array_equal(img, ref)
+
+
 @pytest.mark.parametrize("ranks,scaling,spp_total", [(2, "strong", 16), (2, "weak", 32), (3, "strong", 16)])
 def test_rehearsal_without_a_launcher_goes_through_sol_gather(ranks, scaling, spp_total):
     """`python bench.py --gpus N --rehearse` starts its own ranks; the data path is the real one (sol_comm_init, sol_render, sol_gather
