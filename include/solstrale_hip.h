@@ -446,6 +446,30 @@ int sol_bloom_rgb8(SolScene* scene, const void* image_dev, uint32_t num_samples,
 /* create_gaussian_blur_weights (src/util/gaussian.rs:11-25), the weights sol_bloom uses; host-only, for known-answer tests. */
 int sol_gaussian_blur_weights(uint32_t kernel_size, double std_dev, double* out);
 
+/* ---- adaptive sampling (EXTENSION, not in the reference; opt-in) ------------------------------------------------
+ * Rounds of `round_samples` samples over the 8x8 blocks still active; a block stops once every real pixel in it has converged by
+ * the batch-means rule of DESIGN.md 11, or when it holds max_samples. Every pixel of a block holds the same count n_b, and its
+ * sums are bit-identical to sol_clear + sol_render(scene, 0, n_b, seed). One rank, one device: world > 1 is SOL_EINVAL.
+ * sol_clear, sol_render, sol_render_counted and sol_scene_set_partition end the session. */
+typedef struct SolAdaptive {
+  uint32_t size;           /* in: sizeof(SolAdaptive): lets the struct grow                                              */
+  uint32_t round;          /* samples per round, a positive multiple of 16                                              */
+  uint32_t min_samples;    /* no block stops before it holds this many (nor before its second round): a multiple of 16  */
+  uint32_t max_samples;    /* samples_per_pixel: >= min_samples, >= 1                                                  */
+  float threshold;         /* relative standard error of the mean luminance that counts as converged; 0 = never          */
+} SolAdaptive;
+/* Checks the configuration (before the device is touched), clears the accumulator and the per-pixel state, activates every block. */
+int sol_adaptive_begin(SolScene* scene, const SolAdaptive* config);
+/* Renders and evaluates one round; *active_blocks = the blocks the next round samples (0: the session is done). Blocks. */
+int sol_adaptive_round(SolScene* scene, uint64_t seed, uint32_t* active_blocks);
+/* Samples per pixel of every image block, row-major over blocks of 8x8 ((width + 7) / 8 per row); n = the entries of per_block. */
+int sol_adaptive_counts(SolScene* scene, uint32_t* per_block, size_t n);
+/* The Nop post-processor (sol_tonemap_rgb8) with every pixel scaled by its own block's sample count. */
+int sol_tonemap_rgb8_adaptive(SolScene* scene, const void* image_dev, uint8_t* rgb8_host);
+/* Rescales image_dev (W*H*3 floats, device) in place to sum * max_samples / n_b, so that sol_bloom / sol_bloom_rgb8 with
+ * max_samples see sums of a uniform count. */
+int sol_adaptive_rescale(SolScene* scene, void* image_dev);
+
 int sol_stats(const SolScene* scene, SolStats* out);
 /* What the paths of the last instrumented render (sol_render_counted, one-path-per-lane kernel) looked like - how hard a workload
  * is: the share of camera rays that hit something and the samples by the number of rays of their path (a path of n rays was

@@ -92,6 +92,11 @@ int solh_load_obj(SolhBuilder* b, const char* path, const char* filename, int tr
  * ("kernel_size_fraction must be between 0 and 0.5"). */
 int solh_set_post_processors(SolhBuilder* b, int n, const int* kinds, const double* params);
 
+/* EXTENSION, not in the reference: adaptive sampling (solstrale_hip.h SolAdaptive) for the following
+ * solh_ray_trace calls, with samples_per_pixel as max_samples; round = 0 turns it off. Every round is one progress event (progress
+ * = samples spent / (blocks * samples_per_pixel), the last event 1.0); images are tone-mapped with each block's own count (Nop) or
+ * rescaled to samples_per_pixel before bloom. One device: solh_ray_trace_devices with more than one device fails. */
+int solh_set_adaptive(SolhBuilder* b, uint32_t round, uint32_t min_samples, double threshold);
 typedef void (*solh_progress_fn)(void* user, double progress, double fps, double eta_seconds,
                                  const uint8_t* image_rgb8, uint32_t width, uint32_t height);
 typedef int (*solh_abort_fn)(void* user);

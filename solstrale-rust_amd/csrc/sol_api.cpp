@@ -134,6 +134,7 @@ int sol_rebuild_order(SolScene* s) {
 int sol_set_partition(SolScene* s, int rank, int world) {
   if (world < 1 || rank < 0 || rank >= world) return sol_fail(SOL_EINVAL, "bad partition %d/%d", rank, world);
   const int rank_before = s->rank, world_before = s->world;
+  s->adaptive.open = false;  // (the active list and the per-pixel state describe the old partition)
   s->rank = rank; s->world = world;
   const uint32_t nb = s->blocks_x * s->blocks_y;
   s->n_local_blocks = (nb + (uint32_t)world - 1u - (uint32_t)rank) / (uint32_t)world;  // blocks b with b % world == rank
@@ -226,6 +227,7 @@ void sol_scene_destroy(SolScene* s) {
   void* ptrs[] = {s->leaf_refs, s->nodes, s->wides, s->tris, s->tri_shade, s->quads, s->spheres, s->mediums, s->mats, s->texs, s->texels, s->env, s->lights, s->light_tri,
                   s->acc_own, s->partial, s->image, s->rgb8, s->work, s->spill, s->counters, s->pool, s->queue, s->wf_ctr,
                   s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block};
+  s->adaptive.release();
   if (s->wf_ctr_host) hipHostFree(s->wf_ctr_host);
   for (void* p : ptrs)
     if (p) hipFree(p);
@@ -315,6 +317,7 @@ int sol_scene_set_option(SolScene* s, int option, int64_t value) {
 
 int sol_scene_set_partition(SolScene* s, int rank, int world) {
   if (!s) return sol_fail(SOL_EINVAL, "null scene");
+  s->adaptive.open = false;  // (ends an adaptive sampling session)
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipStreamSynchronize(s->stream));
   if (world >= 1 && s->acc != s->acc_own) {
@@ -347,6 +350,7 @@ int sol_scene_set_stream(SolScene* s, void* stream) {
 
 int sol_clear(SolScene* s) {
   if (!s) return sol_fail(SOL_EINVAL, "null scene");
+  s->adaptive.open = false;  // (ends an adaptive sampling session)
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipMemsetAsync(s->acc, 0, s->acc_floats * sizeof(float), s->stream));
   return SOL_OK;

@@ -17,7 +17,10 @@
 
 #include "sol_scene.h"
 
-int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count) {
+// ad != null: one round of adaptive sampling (sol_adaptive.hip). The launch traces the active list `ad->order` - a DevScene copy
+// with that work order, uploaded to its own device copy - and leaves the chunk sums in `partial` for sol_adaptive_round, which
+// adds them to the accumulator; the product kernel itself is the one a plain render runs.
+int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count, const SolAdaptiveLaunch* ad) {
   if (!s) return sol_fail(SOL_EINVAL, "null scene");
   if (n == 0) return SOL_OK;
   if ((uint64_t)first + n > 0xFFFFFFFFull) return sol_fail(SOL_EINVAL, "sample range overflows 32 bits");
@@ -29,6 +32,7 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   P.n_local_blocks = s->n_local_blocks; P.blocks_x = s->blocks_x;
   P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
   int version = s->kernel_version ? s->kernel_version : 1;
+  if (ad) version = 1;  // (the count map must not depend on the kernel variant: rounds always run the product kernel)
   // version 4, the pool kernel (sol_pool.hip): plain renders of the path-tracing... any shader; counted renders (probes, statistics) and trees
   // of 2^17 wide nodes or more (its one-dword node groups carry a 17-bit base) stay with the one-path-per-lane kernel
   if (version == 4 && ((count && !std::getenv("SOL_POOL_COUNT")) || s->n_wide >= SOL_PACK_MAX_NODES)) version = 1;  // (SOL_POOL_COUNT: phase statistics of the pool kernel)
@@ -52,9 +56,12 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   // Background blocks - the tail of the work order - are not traced: their sums are written by sol_fill_background_kernel. Counted
   // renders trace everything (their counters describe the whole algorithm; the creation probes are counted renders).
   P.n_traced_blocks = P.n_local_blocks;
-  if (version == 1 && (!count || s->background_in_counted) && s->background_enabled && s->S.block_order && s->n_background_local <= P.n_local_blocks)
+  if (ad) P.n_traced_blocks = ad->n_traced;
+  else if (version == 1 && (!count || s->background_in_counted) && s->background_enabled && s->S.block_order && s->n_background_local <= P.n_local_blocks)
     P.n_traced_blocks = P.n_local_blocks - s->n_background_local;
   const uint64_t items = (uint64_t)P.n_chunks * P.n_traced_blocks * 64u;
+  DevScene Sv = s->S;  // the scene this launch renders: the work order is the active list in a round of adaptive sampling
+  if (ad) { Sv.block_order = ad->order; Sv.n_first = ad->n_first; }
   // the 32-bit work counter keeps counting after the items run out (every wave adds 64 per refused fetch until all its
   // lanes have left): 16 M of headroom is > 100 times what 5120 resident waves can add
   if ((uint64_t)P.n_chunks * P.n_local_blocks * 64u > SOL_MAX_ITEMS) return sol_fail(SOL_EINVAL, "too many work items in one call (%llu): split the sample range", (unsigned long long)items);
@@ -156,7 +163,7 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
     // items per reservation of a wave's reservoir: a whole pair (1024 samples) when every resident wave gets at least 16 of them, else 64
     P.pool_slots = total >= (uint64_t)(P.total_threads / 64u) * 1024u * 16u ? 1024u : 64u;
   } else if (version == 1 && !count && fine_tail > 0) {
-    const uint32_t rest = P.n_traced_blocks - std::min(P.n_traced_blocks, s->S.n_first);
+    const uint32_t rest = P.n_traced_blocks - std::min(P.n_traced_blocks, Sv.n_first);
     const uint32_t pairs = std::min<uint32_t>(rest, (uint32_t)(((uint64_t)fine_tail * (P.total_threads / 64u) + 3u) / 4u));
     const uint64_t total = items - (uint64_t)pairs * 64u + (uint64_t)pairs * 64u * SOL_CHUNK;
     if (pairs > 0 && total <= SOL_MAX_ITEMS && (uint64_t)P.stage_at + (uint64_t)pairs * 64u * SOL_CHUNK <= 0xFFFFFFFFull) {
@@ -210,23 +217,37 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
 #endif
   {
     if (!s->dscene) HIP_TRY(hipMalloc((void**)&s->dscene, sizeof(DevScene)));
-    if (!s->dscene_valid || std::memcmp(&s->S, &s->S_uploaded, sizeof(DevScene)) != 0) {
-      // rare (scene creation, tree probe, auxiliary renders): launches already queued may still read the old copy
+    DevScene* dS = ad ? ad->dscene : s->dscene;
+    DevScene* up = ad ? ad->uploaded : &s->S_uploaded;
+    bool* valid = ad ? ad->valid : &s->dscene_valid;
+    if (!*valid || std::memcmp(&Sv, up, sizeof(DevScene)) != 0) {
+      // rare (scene creation, tree probe, auxiliary renders; a round whose active list has a new heavy prefix): launches already
+      // queued may still read the old copy
       HIP_TRY(hipStreamSynchronize(s->stream));
-      HIP_TRY(hipMemcpy(s->dscene, &s->S, sizeof(DevScene), hipMemcpyHostToDevice));
-      std::memcpy(&s->S_uploaded, &s->S, sizeof(DevScene));
-      s->dscene_valid = true;
+      HIP_TRY(hipMemcpy(dS, &Sv, sizeof(DevScene), hipMemcpyHostToDevice));
+      std::memcpy(up, &Sv, sizeof(DevScene));
+      *valid = true;
     }
     if (P.n_items > 0)
-      HIP_TRY(sol_launch_render(version, s->S, s->dscene, P, s->acc, s->partial, s->work, s->spill, s->pool, s->counters, grid, count,
+      HIP_TRY(sol_launch_render(version, Sv, dS, P, s->acc, s->partial, s->work, s->spill, s->pool, s->counters, grid, count,
                                 s->has_medium, stack_need > lds_depth, s->stream));
-    if (P.n_traced_blocks != P.n_local_blocks) HIP_TRY(sol_launch_fill_background(s->dscene, P, s->partial, s->stream));
+    if (ad) {
+      // the active background blocks are the last ad->n_background entries of the active list: the fill kernel writes the blocks
+      // behind its n_traced_blocks
+      if (ad->n_background) {
+        RenderParams Q = P;
+        Q.n_traced_blocks = P.n_local_blocks - ad->n_background;
+        HIP_TRY(sol_launch_fill_background(dS, Q, s->partial, s->stream));
+      }
+    } else if (P.n_traced_blocks != P.n_local_blocks) {
+      HIP_TRY(sol_launch_fill_background(dS, P, s->partial, s->stream));
+    }
   }
   if (s->timing) { HIP_TRY(hipEventRecord(s->ev_stop, s->stream)); s->timed_launches++; }
   s->last_grid = grid;
   s->last_version = version;
-  if (P.n_coarse != P.n_items) HIP_TRY(sol_launch_stage_resolve(s->dscene, P, s->partial, s->stream));
-  if (via_partial) HIP_TRY(sol_launch_resolve(s->acc, s->partial, (uint32_t)slots3, P.n_chunks, s->stream));
+  if (P.n_coarse != P.n_items) HIP_TRY(sol_launch_stage_resolve(ad ? ad->dscene : s->dscene, P, s->partial, s->stream));
+  if (via_partial && !ad) HIP_TRY(sol_launch_resolve(s->acc, s->partial, (uint32_t)slots3, P.n_chunks, s->stream));
   if (count) {
     DevCounters c;
     HIP_TRY(hipMemcpyAsync(&c, s->counters, sizeof c, hipMemcpyDeviceToHost, s->stream));
@@ -244,8 +265,14 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
 
 extern "C" {
 
-int sol_render(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) { return sol_render_impl(s, first, n, seed, false); }
-int sol_render_counted(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) { return sol_render_impl(s, first, n, seed, true); }
+int sol_render(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
+  if (s) s->adaptive.open = false;  // (ends an adaptive sampling session)
+  return sol_render_impl(s, first, n, seed, false);
+}
+int sol_render_counted(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
+  if (s) s->adaptive.open = false;
+  return sol_render_impl(s, first, n, seed, true);
+}
 
 // Auxiliary albedo / normal buffers (src/renderer/mod.rs:175-204): at depth 0 the reference evaluates AlbedoShader and
 // NormalShader on the hit of the primary ray (background / zero on a miss) and accumulates them beside the pixel colour.

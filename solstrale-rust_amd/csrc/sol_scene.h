@@ -82,6 +82,34 @@ struct DevTree {
   }
 };
 
+// Adaptive sampling (sol_adaptive.hip): the session opened by sol_adaptive_begin and ended by sol_clear, sol_render and
+// sol_scene_set_partition. The active list has the layout of the work order: the active traced blocks at the front (the heavy ones
+// first), the active background blocks at the very end of its n_local_blocks entries.
+struct SolAdaptiveSession {
+  bool open = false;
+  uint32_t round = 0, min_samples = 0, max_samples = 0; float threshold = 0.f;
+  uint32_t rounds_done = 0;                           // rounds rendered since sol_adaptive_begin
+  uint32_t n_first = 0, n_traced = 0, n_background = 0;  // the active list the next round renders
+  float* state = nullptr; size_t state_slots = 0;     // per slot of the accumulator: Welford mean and M2 of the rounds' luminance
+  uint32_t* active = nullptr;                         // per local block: 1 = still sampled
+  uint32_t* order = nullptr; size_t order_cap = 0;    // the active list (n_local_blocks entries)
+  uint32_t* counts = nullptr; size_t counts_cap = 0;  // per image block (row-major): samples its pixels hold
+  uint32_t* ctr = nullptr; uint32_t* ctr_host = nullptr;  // what the compaction counted: heavy, traced, background active blocks
+  DevScene* dscene = nullptr; DevScene S_uploaded{}; bool dscene_valid = false;  // the DevScene copy whose work order is the active list
+  void release() {
+    void* p[] = {state, active, order, counts, ctr, dscene};
+    for (void* q : p) if (q) hipFree(q);
+    if (ctr_host) hipHostFree(ctr_host);
+    *this = SolAdaptiveSession{};
+  }
+};
+// What sol_render_impl needs to render a round over the active list instead of the whole work order.
+struct SolAdaptiveLaunch {
+  const uint32_t* order;
+  uint32_t n_first, n_traced, n_background;
+  DevScene* dscene; DevScene* uploaded; bool* valid;
+};
+
 struct SolScene {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
@@ -151,9 +179,10 @@ struct SolScene {
   bool timing = false;  // sol_kernel_timing: HIP events around the render kernel on its own stream
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   uint32_t timed_launches = 0, last_grid = 0;
+  SolAdaptiveSession adaptive;
 };
 
 int sol_rebuild_order(SolScene* s);
 int sol_set_partition(SolScene* s, int rank, int world);
-int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count);
+int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count, const SolAdaptiveLaunch* ad = nullptr);
 inline int sol_render_probe(SolScene* s) { return sol_render_impl(s, 0, SOL_CHUNK, 0x50B3ull, true); }

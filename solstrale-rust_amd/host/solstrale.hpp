@@ -263,6 +263,12 @@ struct RenderConfig {
   std::vector<PostProcessors> post_processors{NopPostProcessor::create()};  // src/renderer/mod.rs:35,49
   RenderImageStrategy render_image_strategy;
   uint64_t seed = 0x5017A1Eull;  // the reference has no seed (entropy-seeded fastrand); the build adds one
+  // EXTENSION (not in the reference): adaptive sampling (include/solstrale_hip.h SolAdaptive) with samples_per_pixel as
+  // the most a block gets; round == 0: off (every pixel gets samples_per_pixel). One device only.
+  struct Adaptive {
+    uint32_t round = 0, min_samples = 0;
+    double threshold = 0.0;
+  } adaptive;
 };
 
 struct Scene {

@@ -601,6 +601,63 @@ std::string ray_trace(const Scene& scene, const std::function<void(RenderProgres
   auto secs = [&](clk::time_point t) { return std::chrono::duration<double>(t - t0).count(); };
   double last_image_time = -1e300;  // SystemTime::UNIX_EPOCH in the reference
 
+  if (rc.adaptive.round) {
+    // EXTENSION: adaptive sampling. One progress event per round; the image follows the strategy, with each block's own
+    // sample count (Nop: sol_tonemap_rgb8_adaptive) or the sums rescaled to samples_per_pixel in front of bloom.
+    if (n_dev > 1) return "ray_trace: adaptive sampling renders on one device";
+    SolAdaptive cfg{};
+    cfg.size = sizeof cfg; cfg.round = rc.adaptive.round; cfg.min_samples = rc.adaptive.min_samples; cfg.max_samples = spp;
+    cfg.threshold = (float)rc.adaptive.threshold;
+    if (sol_adaptive_begin(dev, &cfg) != SOL_OK) return sol_last_error();
+    const uint64_t blocks = (uint64_t)((rc.width + 7) / 8) * ((rc.height + 7) / 8);
+    const double total = (double)blocks * spp;
+    uint64_t spent = 0;
+    uint32_t active = (uint32_t)blocks, done_samples = 0;
+    bool bloom = false;
+    for (const PostProcessors& pp : rc.post_processors) bloom = bloom || pp.kind == PostProcessors::Bloom;
+    while (active > 0) {
+      if (abort && abort()) return "";
+      const uint32_t n = std::min(rc.adaptive.round, spp - done_samples);
+      uint32_t next = 0;
+      if (sol_adaptive_round(dev, rc.seed, &next) != SOL_OK) return sol_last_error();
+      spent += (uint64_t)active * n;
+      done_samples += n;
+      active = next;
+      const bool last = active == 0;
+      const double now = secs(clk::now());
+      RenderProgress p;
+      if (rc.render_image_strategy.should_generate_image(last ? spp : done_samples, spp, now, last_image_time)) {
+        last_image_time = now;
+        if (abort && abort()) return "";
+        if (!rc.post_processors.empty()) {
+          void* img = nullptr;
+          if (sol_resolve_image(dev, &img) != SOL_OK || (bloom && sol_adaptive_rescale(dev, img) != SOL_OK)) return sol_last_error();
+          for (size_t k = 0; k + 1 < rc.post_processors.size(); ++k) {
+            const PostProcessors& pp = rc.post_processors[k];
+            if (pp.kind == PostProcessors::Bloom && sol_bloom(dev, img, spp, pp.kernel_size_fraction, pp.threshold, pp.max_intensity) != SOL_OK)
+              return sol_last_error();
+          }
+          const PostProcessors& lastpp = rc.post_processors.back();
+          p.render_image.resize(npix * 3);
+          int rcode = lastpp.kind == PostProcessors::Bloom
+                          ? sol_bloom_rgb8(dev, img, spp, lastpp.kernel_size_fraction, lastpp.threshold, lastpp.max_intensity, p.render_image.data())
+                          : bloom ? sol_tonemap_rgb8(dev, img, spp, p.render_image.data()) : sol_tonemap_rgb8_adaptive(dev, img, p.render_image.data());
+          if (rcode != SOL_OK) return sol_last_error();
+          p.has_image = true;
+          p.width = (uint32_t)rc.width;
+          p.height = (uint32_t)rc.height;
+        }
+      }
+      const double elapsed = std::max(now, 1e-9);
+      p.progress = last ? 1.0 : std::min(1.0, (double)spent / total);
+      const double passes = (double)spent / (double)blocks;  // samples per pixel spent, on average
+      p.fps = passes / elapsed;
+      p.estimated_time_left_s = p.progress > 0.0 ? elapsed / p.progress * (1.0 - p.progress) : 0.0;
+      if (output) output(std::move(p));
+    }
+    return "";
+  }
+
   // Passes are batched on the device; one RenderProgress per sample index is still emitted (tests drain the
   // channel, tests/integration_tests.rs:316-321) and abort is polled between batches (renderer/mod.rs:237).
   uint32_t batch = rc.render_image_strategy.kind == RenderImageStrategy::EverySample ? 1u : 16u;

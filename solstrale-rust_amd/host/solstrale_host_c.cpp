@@ -304,6 +304,15 @@ int solh_set_post_processors(SolhBuilder* b, int n, const int* kinds, const doub
   });
 }
 
+int solh_set_adaptive(SolhBuilder* b, uint32_t round, uint32_t min_samples, double threshold) {
+  return guarded([&] {
+    if (round % 16 || min_samples % 16) throw std::runtime_error("solh_set_adaptive: round and min_samples must be multiples of 16");
+    if (!(threshold >= 0.0)) throw std::runtime_error("solh_set_adaptive: threshold must be >= 0");
+    b->scene.render_config.adaptive = {round, min_samples, threshold};
+    return 0;
+  });
+}
+
 void solh_abi_sizes(uint32_t out[11]) {
   const size_t s[11] = {sizeof(SolAabb), sizeof(SolBvhNode), sizeof(SolSphere), sizeof(SolQuad), sizeof(SolTriangle),
                         sizeof(SolMedium), sizeof(SolMaterial), sizeof(SolTexture), sizeof(SolCamera), sizeof(SolSceneDesc),

@@ -149,6 +149,12 @@ class SolPathStats(C.Structure):
     _fields_ = [("size", C.c_uint32), ("pad", C.c_uint32), ("samples", C.c_uint64), ("primary_hits", C.c_uint64), ("path_len", C.c_uint64 * 6)]
 
 
+class SolAdaptive(C.Structure):
+    """EXTENSION: adaptive sampling (sol_adaptive_begin)."""
+    _fields_ = [("size", C.c_uint32), ("round", C.c_uint32), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32),
+                ("threshold", C.c_float)]
+
+
 class SolTreeCheck(C.Structure):
     _fields_ = [("n_wide", C.c_uint32), ("n_leaf_refs", C.c_uint32), ("n_primitives", C.c_uint32), ("depth", C.c_uint32),
                 ("max_children", C.c_uint32), ("box_violations", C.c_uint32), ("leaf_mismatches", C.c_uint32),
@@ -212,6 +218,11 @@ def load_hip():
     _sig(lib, "sol_gather_local", C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)])
     _sig(lib, "sol_read_image", C.c_int, [P, C.POINTER(C.c_float)])
     _sig(lib, "sol_max_samples_per_call", C.c_uint32, [P])
+    _sig(lib, "sol_adaptive_begin", C.c_int, [P, C.POINTER(SolAdaptive)])
+    _sig(lib, "sol_adaptive_round", C.c_int, [P, C.c_uint64, C.POINTER(C.c_uint32)])
+    _sig(lib, "sol_adaptive_counts", C.c_int, [P, C.POINTER(C.c_uint32), C.c_size_t])
+    _sig(lib, "sol_tonemap_rgb8_adaptive", C.c_int, [P, C.c_void_p, C.POINTER(C.c_uint8)])
+    _sig(lib, "sol_adaptive_rescale", C.c_int, [P, C.c_void_p])
     _libs["hip"] = lib
     return lib
 
@@ -222,7 +233,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_stats", "sol_record_sizes", "sol_last_error", "sol_eval", "sol_kernel_timing", "sol_last_kernel_ms",
                "sol_debug_path", "sol_resolve_image", "sol_bloom", "sol_bloom_rgb8", "sol_gaussian_blur_weights", "sol_world_tree_check", "sol_world_tree_check_ex", "sol_render_aux", "sol_clear_aux", "sol_read_aux",
                "sol_scene_create_ex", "sol_scene_build_times", "sol_scene_set_option", "sol_scene_info", "sol_path_stats", "sol_comm_unique_id", "sol_comm_init",
-               "sol_comm_destroy", "sol_gather", "sol_gather_local", "sol_comm_self_check", "sol_read_image", "sol_max_samples_per_call", "sol_background_blocks"]
+               "sol_comm_destroy", "sol_gather", "sol_gather_local", "sol_comm_self_check", "sol_read_image", "sol_max_samples_per_call", "sol_background_blocks",
+               "sol_adaptive_begin", "sol_adaptive_round", "sol_adaptive_counts", "sol_tonemap_rgb8_adaptive", "sol_adaptive_rescale"]
 
 
 def load_host():
@@ -264,6 +276,7 @@ def load_host():
     _sig(lib, "solh_ray_trace_devices", I, [B, C.c_uint32, C.c_uint64, I, D, I, C.POINTER(C.c_int), PROGRESS_FN, ABORT_FN, C.c_void_p])
     _sig(lib, "solh_load_obj", I, [B, C.c_char_p, C.c_char_p, I, I, IMAGE_DECODER_FN, C.c_void_p])
     _sig(lib, "solh_set_post_processors", I, [B, I, C.POINTER(C.c_int), C.POINTER(C.c_double)])
+    _sig(lib, "solh_set_adaptive", I, [B, C.c_uint32, C.c_uint32, D])
     _sig(lib, "solh_abi_sizes", None, [C.POINTER(C.c_uint32)])
     _sig(lib, "solh_to_rgb_color", None, [_D3, C.c_uint32, C.POINTER(C.c_uint8)])
     _libs["host"] = lib
@@ -274,7 +287,8 @@ HOST_SYMBOLS = ["solh_builder_new", "solh_builder_free", "solh_last_error", "sol
                 "solh_image_map", "solh_normal_texture", "solh_lambertian", "solh_metal", "solh_dielectric",
                 "solh_diffuse_light", "solh_blend", "solh_sphere", "solh_quad", "solh_box", "solh_triangle",
                 "solh_triangles", "solh_spheres", "solh_constant_medium", "solh_bvh", "solh_bvh_range", "solh_finish",
-                "solh_tree_depth", "solh_environment", "solh_ray_trace", "solh_ray_trace_devices", "solh_abi_sizes", "solh_to_rgb_color", "solh_set_post_processors", "solh_load_obj"]
+                "solh_tree_depth", "solh_environment", "solh_ray_trace", "solh_ray_trace_devices", "solh_abi_sizes", "solh_to_rgb_color", "solh_set_post_processors", "solh_load_obj",
+                "solh_set_adaptive"]
 
 
 def d3(v):

@@ -220,6 +220,43 @@ class DeviceScene:
                                             out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
+    # ---- adaptive sampling (EXTENSION) ----
+    def adaptive_begin(self, round, min_samples, max_samples, threshold):
+        """sol_adaptive_begin: clears the accumulator and opens a session of rounds of `round` samples."""
+        cfg = _abi.SolAdaptive(size=C.sizeof(_abi.SolAdaptive), round=int(round), min_samples=int(min_samples),
+                               max_samples=int(max_samples), threshold=float(threshold))
+        self._chk(self.lib.sol_adaptive_begin(self.h, C.byref(cfg)))
+
+    def adaptive_round(self, seed):
+        """sol_adaptive_round: renders one round; returns the blocks the next round samples (0: done)."""
+        n = C.c_uint32()
+        self._chk(self.lib.sol_adaptive_round(self.h, seed, C.byref(n)))
+        return int(n.value)
+
+    def adaptive_run(self, seed):
+        """Rounds until every block has stopped; returns the number of rounds."""
+        rounds = 0
+        while True:
+            rounds += 1
+            if self.adaptive_round(seed) == 0:
+                return rounds
+
+    def adaptive_counts(self):
+        """Samples per pixel of every 8x8 block: uint32 array [blocks_y, blocks_x]."""
+        bx, by = (self.width + 7) // 8, (self.height + 7) // 8
+        out = np.zeros((by, bx), dtype=np.uint32)
+        self._chk(self.lib.sol_adaptive_counts(self.h, out.ctypes.data_as(C.POINTER(C.c_uint32)), out.size))
+        return out
+
+    def tonemap_rgb8_adaptive(self, image_ptr):
+        out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        self._chk(self.lib.sol_tonemap_rgb8_adaptive(self.h, C.c_void_p(image_ptr), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    def adaptive_rescale(self, image_ptr):
+        """sol_adaptive_rescale: image <- sum * max_samples / n_b in place (the input of bloom)."""
+        self._chk(self.lib.sol_adaptive_rescale(self.h, C.c_void_p(image_ptr)))
+
     def resolve_image(self):
         """Device pointer of the scene's own row-major image (W*H*3 floats) after un-permuting its accumulators."""
         p = C.c_void_p()

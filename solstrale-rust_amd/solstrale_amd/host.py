@@ -71,13 +71,20 @@ class RenderConfig:
     """src/renderer/mod.rs:26-52 (seed is the build's addition; OidnPostProcessor is not built)."""
 
     def __init__(self, width=300, height=200, samples_per_pixel=50, shader=(_abi.SHADER_PATH_TRACING, 50),
-                 seed=0x5017A1E, post_processors=None):
+                 seed=0x5017A1E, post_processors=None, adaptive=None):
+        """adaptive: EXTENSION, AdaptiveSampling(round, min_samples, threshold) or None."""
         self.width = width
         self.height = height
         self.samples_per_pixel = samples_per_pixel
         self.shader = shader
         self.seed = seed
         self.post_processors = [NopPostProcessor()] if post_processors is None else list(post_processors)
+        self.adaptive = adaptive
+
+
+def AdaptiveSampling(round=64, min_samples=128, threshold=0.02):
+    """EXTENSION (not in the reference): adaptive sampling with samples_per_pixel as the most a block gets (solh_set_adaptive)."""
+    return (int(round), int(min_samples), float(threshold))
 
 
 def PathTracingShader(max_depth):
@@ -141,6 +148,9 @@ class Scene:
         kinds = (C.c_int * max(1, len(pp)))(*[k for k, _ in pp])
         params = (C.c_double * max(1, 3 * len(pp)))(*[x for _, prm in pp for x in prm])
         if b.lib.solh_set_post_processors(b.h, len(pp), kinds, params) != 0:
+            raise HostError(b.lib.solh_last_error().decode(errors="replace"))
+        ad = getattr(rc, "adaptive", None) or (0, 0, 0.0)
+        if b.lib.solh_set_adaptive(b.h, ad[0], ad[1], ad[2]) != 0:
             raise HostError(b.lib.solh_last_error().decode(errors="replace"))
         if devices is None:
             rc_ = b.lib.solh_ray_trace(b.h, rc.samples_per_pixel, rc.seed, strat, interval_seconds, device, cb, ab, None)
