@@ -72,8 +72,15 @@ typedef struct SolSphere {
   double radius;
   SolAabb bbox;
   int32_t material;
-  uint32_t dfs_index; /* position in the depth-first leaf order of the world tree (tie rule) */
+  uint32_t dfs_index; /* position in the depth-first leaf order of the world tree (tie rule) - see below */
 } SolSphere;
+/* dfs_index (SolSphere, SolQuad, SolTriangle, SolMedium) decides which of two equal hits wins and which flat primitive a scattered ray
+ * leaves (the tie rule and rule 8), so it is checked: walk the world tree in pre-order from `root`, left child before right;
+ * every sphere, quad, triangle or medium the walk reaches takes the next number (0, 1, 2 ...), a medium before its boundary sub-tree is
+ * walked, the walk going on after the boundary. A record reached more than once (a shared sub-tree) takes the number of its LAST
+ * visit. Every reached record must carry exactly its number, or sol_scene_create, sol_world_tree_check(_ex) and sol_background_blocks
+ * return SOL_EINVAL naming the record, the value found and the one expected. Records the walk never reaches (a light outside the
+ * world) are not checked. The host library's flattening emits this numbering. */
 
 /* `Quad{q,u,v,normal,d,w,mat,b_box,area}` (src/hittable/quad.rs:19-29) */
 typedef struct SolQuad {

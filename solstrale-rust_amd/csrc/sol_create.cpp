@@ -316,6 +316,97 @@ static SolSplitOptions split_options(const SolDevOverrides& ovr, const SolCreate
   return sp;
 }
 
+// The dfs_index contract (solstrale_hip.h; DESIGN.md 4, the tie rule and rule 8): every sphere, quad, triangle and medium the world tree
+// reaches carries its number in the pre-order walk from `root` (left before right; a medium before its boundary sub-tree, the walk going on
+// after the boundary) - what the host's Flattener emits and what the float oracle's walk (later hit wins) decides ties by. A record
+// reached more than once (a shared sub-tree) carries the number of its LAST visit, the one that wins its ties in the oracle. Linear in
+// the descriptor whatever the sharing: the references form a DAG, each vertex's number of walked records is summed bottom-up, and its
+// last visit is the longest path to it (the largest of its parents' last visits plus the edge's offset), relaxed in topological order.
+// Records the walk never reaches (a light outside the tree) are never a search candidate and are not checked. Also refuses what
+// the walk cannot follow: a reference of an unknown kind or out of range, a cycle (a medium boundary's, which tb.resolve does not walk).
+// `counted`: TreeBuilder's count during the world's resolve - the whole answer for a tree without mediums and without sharing (all
+// the large scenes: the walk costs nothing beyond resolve's own, where this general one took C5's 2.3 M records 80 ms on its own).
+static int check_dfs_numbering(const SolSceneDesc& d, const TreeBuilder::DfsCount& counted) {
+  const uint32_t n_of[6] = {0u, d.n_nodes, d.n_spheres, d.n_quads, d.n_triangles, d.n_mediums};
+  static const char* const kind_name[6] = {"none", "node", "sphere", "quad", "triangle", "medium"};
+  uint64_t base[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int k = 1; k < 6; ++k) base[k + 1] = base[k] + n_of[k];
+  if (SOL_REF_KIND(d.root) == SOL_REF_NONE) return SOL_OK;
+  const uint64_t n_vert = base[6] - base[1];  // vertex of a reference = base[kind] - base[NODE] + index
+  if (n_vert >= 0xFFFFFFFFull) return sol_fail(SOL_EINVAL, "dfs_index check: %llu records", (unsigned long long)n_vert);
+  auto vertex = [&](uint32_t ref, uint32_t& v) {
+    const uint32_t k = SOL_REF_KIND(ref);
+    if (k < SOL_REF_NODE || k > SOL_REF_MEDIUM || SOL_REF_INDEX(ref) >= n_of[k]) return false;
+    v = (uint32_t)(base[k] - base[1] + SOL_REF_INDEX(ref));
+    return true;
+  };
+  auto kind_of = [&](uint32_t v) { uint32_t k = 1; while (k < 5 && v >= base[k + 1] - base[1]) ++k; return k; };
+  // the references a vertex leads to, in walk order (NONE where there is none)
+  auto child = [&](uint32_t v, int which) -> uint32_t {
+    if (v < n_of[SOL_REF_NODE]) return which == 0 ? d.nodes[v].left : which == 1 ? d.nodes[v].right : 0u;
+    if (v >= base[5] - base[1]) return which == 0 ? d.mediums[v - (base[5] - base[1])].boundary : 0u;
+    return 0u;
+  };
+  auto dfs_of = [&](uint32_t k, uint32_t i) {
+    return k == SOL_REF_SPHERE ? d.spheres[i].dfs_index : k == SOL_REF_QUAD ? d.quads[i].dfs_index : k == SOL_REF_TRIANGLE ? d.triangles[i].dfs_index : d.mediums[i].dfs_index;
+  };
+  auto wrong = [&](uint32_t k, uint32_t i, uint32_t want) {
+    return sol_fail(SOL_EINVAL, "dfs_index: %s %u carries %u, the world tree's depth-first order gives it %u (solstrale_hip.h, SolSceneDesc)", kind_name[k], i, dfs_of(k, i), want);
+  };
+  if (counted.plain) return counted.bad_ref ? wrong(SOL_REF_KIND(counted.bad_ref), SOL_REF_INDEX(counted.bad_ref), counted.bad_want) : SOL_OK;
+  const uint32_t cap = 0xFFFFFFFFu;  // (walk lengths and positions saturate - a shared sub-tree can double them per level -; past 2^31 is refused)
+  auto add = [&](uint32_t a, uint32_t b) { return a > cap - b ? cap : a + b; };
+  std::vector<uint32_t> walked(n_vert, 0), last(n_vert, 0);
+  std::vector<uint8_t> state(n_vert, 0);  // 0 unseen, 1 on the DFS path, 2 done
+  std::vector<uint32_t> post;
+  post.reserve(n_vert);
+  uint32_t root;
+  if (!vertex(d.root, root)) return sol_fail(SOL_EINVAL, "dfs_index check: root reference out of range");
+  std::vector<std::pair<uint32_t, int>> stk{{root, 0}};
+  state[root] = 1;
+  while (!stk.empty()) {
+    const uint32_t v = stk.back().first;
+    const int which = stk.back().second++;
+    if (which < 2) {
+      const uint32_t r = child(v, which);
+      if (SOL_REF_KIND(r) == SOL_REF_NONE) continue;
+      uint32_t u;
+      if (!vertex(r, u)) return sol_fail(SOL_EINVAL, "dfs_index check: %s %u leads to a reference out of range (0x%08x)", kind_name[kind_of(v)], (uint32_t)(v - (base[kind_of(v)] - base[1])), r);
+      if (state[u] == 1) return sol_fail(SOL_EINVAL, "dfs_index check: cycle through %s %u", kind_name[kind_of(u)], (uint32_t)(u - (base[kind_of(u)] - base[1])));
+      if (state[u] == 0) { state[u] = 1; stk.push_back({u, 0}); }
+      continue;
+    }
+    uint32_t n = kind_of(v) == SOL_REF_NODE ? 0u : 1u;  // the record itself (a medium: then its boundary)
+    for (int w = 0; w < 2; ++w) {
+      uint32_t u;
+      if (vertex(child(v, w), u)) n = add(n, walked[u]);
+    }
+    walked[v] = n;
+    state[v] = 2;
+    post.push_back(v);
+    stk.pop_back();
+  }
+  // reverse post-order is a topological order: every parent's last visit is final before its children are relaxed
+  for (size_t j = post.size(); j-- > 0;) {
+    const uint32_t v = post[j];
+    uint32_t at = add(last[v], kind_of(v) == SOL_REF_NODE ? 0u : 1u);
+    for (int w = 0; w < 2; ++w) {
+      uint32_t u;
+      if (!vertex(child(v, w), u)) continue;
+      last[u] = std::max(last[u], at);
+      at = add(at, walked[u]);
+    }
+  }
+  for (uint32_t v : post) {
+    const uint32_t k = kind_of(v);
+    if (k == SOL_REF_NODE) continue;
+    const uint32_t i = (uint32_t)(v - (base[k] - base[1]));
+    if (last[v] > 0x7FFFFFFFu) return sol_fail(SOL_EINVAL, "dfs_index: the world tree walks %s %u at a position beyond 2^31 - 1 (%u)", kind_name[k], i, last[v]);
+    if (dfs_of(k, i) != last[v]) return wrong(k, i, last[v]);
+  }
+  return SOL_OK;
+}
+
 static int world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* out) {
   if (!d || !out) return sol_fail(SOL_EINVAL, "null argument");
   std::memset(out, 0, sizeof *out);
@@ -325,6 +416,7 @@ static int world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* ou
   uint32_t root_ref;
   Box root_box;
   if (!tb.resolve(d->root, 0, root_ref, root_box)) return sol_fail(SOL_EINVAL, "world: %s", tb.error.c_str());
+  if (int rc = check_dfs_numbering(*d, tb.dfs)) return rc;
   if (SOL_REF_KIND(root_ref) != SOL_REF_NODE) return sol_fail(SOL_EINVAL, "the world is a single primitive: no tree");
   SahBuilder sah;
   if (!sah.collect(tb.nodes, root_ref)) return sol_fail(SOL_EINVAL, "the world's primitives cannot be collected (non-finite box or fewer than two)");
@@ -497,7 +589,7 @@ extern "C" {
 // header pass their struct's size to sol_world_tree_check_ex and get every field that fits.
 int sol_world_tree_check_ex(const SolSceneDesc* d, int use_sah, void* out, size_t out_size) {
   if (!out || out_size < SOL_TREE_CHECK_V1_BYTES) return sol_fail(SOL_EINVAL, "sol_world_tree_check_ex: out is null or smaller than the first layout (%d bytes)", (int)SOL_TREE_CHECK_V1_BYTES);
-  SolTreeCheck full;
+  SolTreeCheck full{};  // (zero where world_tree_check refuses before filling it)
   const int rc = world_tree_check(d, use_sah, &full);
   std::memset(out, 0, out_size);
   std::memcpy(out, &full, std::min(out_size, sizeof full));
@@ -519,6 +611,7 @@ int sol_background_blocks(const SolSceneDesc* d, int use_sah, uint8_t* flags, si
   uint32_t root_ref;
   Box root_box;
   if (!tb.resolve(d->root, 0, root_ref, root_box)) return sol_fail(SOL_EINVAL, "world: %s", tb.error.c_str());
+  if (int rc = check_dfs_numbering(*d, tb.dfs)) return rc;
   if (SOL_REF_KIND(root_ref) != SOL_REF_NODE) return sol_fail(SOL_EINVAL, "the world is a single primitive: no tree");
   SahBuilder sah;
   if (!sah.collect(tb.nodes, root_ref)) return sol_fail(SOL_EINVAL, "the world's primitives cannot be collected (non-finite box or fewer than two)");
@@ -688,6 +781,7 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
   Box root_box;
   if (!tb.resolve(d->root, 0, root_ref, root_box)) return sol_fail(SOL_EINVAL, "world: %s", tb.error.c_str());
   if (SOL_REF_KIND(root_ref) == SOL_REF_NONE) return sol_fail(SOL_EINVAL, "world is empty");
+  const TreeBuilder::DfsCount world_dfs = tb.dfs;  // (the boundaries' resolves below count on)
   if (sol_dev_overrides().verbose) std::fprintf(stderr, "[solstrale] create: reference tree resolved at %.1f ms\n", 1e3 * seconds_since(t_begin));
   std::vector<DMedium> mediums(d->n_mediums);
   uint32_t medium_depth = 0;
@@ -715,6 +809,7 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
       if (SOL_REF_KIND(r) == SOL_REF_NODE) { stk.push_back(tb.nodes[SOL_REF_INDEX(r)].left); stk.push_back(tb.nodes[SOL_REF_INDEX(r)].right); }
     }
   }
+  if (int rc = check_dfs_numbering(*d, world_dfs)) return rc;  // (after the boundaries: their references are known good here)
   // 7-wide tree of the world. Candidates: the reference's topology collapsed, and binned-SAH rebuilds over the same primitives
   // with 8, 16 and 64 bins (how well the binary splits line up with the wide collapse varies with the bin count: with the
   // first, 8-wide layout C2 visited 9.8 / 12.2 / 11.4 nodes per ray at 8 / 16 / 64 bins and 11.2 on the reference's

@@ -68,8 +68,30 @@ struct TreeBuilder {
   uint32_t max_depth = 0;
   std::string error;
 
+  // The dfs_index numbering (include/solstrale_hip.h), counted on the way: the walk below visits the primitives in pre-order, left
+  // before right, so while it meets no medium and nothing twice (`plain`) the n-th primitive it reaches must carry n; `bad_ref` is the
+  // first that does not (0: none). Otherwise check_dfs_numbering (sol_create.cpp) walks the descriptor itself. Read it after the
+  // world's resolve: a medium boundary's resolve counts on.
+  struct DfsCount {
+    uint32_t next = 0, bad_ref = 0, bad_want = 0;
+    bool plain = true;
+  } dfs;
+  std::vector<uint64_t> prim_seen;  // spheres, quads, triangles: reached already
+
   const float pad;  // the fp32 box pad of this scene (box_pad_for)
-  TreeBuilder(const SolSceneDesc& desc, float box_pad) : d(desc), dev_index(desc.n_nodes, -1), on_path(desc.n_nodes, 0), pad(box_pad) {}
+  TreeBuilder(const SolSceneDesc& desc, float box_pad)
+      : d(desc), dev_index(desc.n_nodes, -1), on_path(desc.n_nodes, 0), prim_seen(((uint64_t)desc.n_spheres + desc.n_quads + desc.n_triangles + 63) / 64, 0), pad(box_pad) {}
+
+  void count_leaf(uint32_t ref) {  // (a reference prim_box accepted)
+    const uint32_t k = SOL_REF_KIND(ref), i = SOL_REF_INDEX(ref);
+    if (k == SOL_REF_MEDIUM) { dfs.plain = false; return; }
+    const uint64_t bit = (k == SOL_REF_SPHERE ? 0u : k == SOL_REF_QUAD ? (uint64_t)d.n_spheres : (uint64_t)d.n_spheres + d.n_quads) + i;
+    if ((prim_seen[bit >> 6] >> (bit & 63)) & 1u) { dfs.plain = false; return; }
+    prim_seen[bit >> 6] |= 1ull << (bit & 63);
+    const uint32_t have = k == SOL_REF_SPHERE ? d.spheres[i].dfs_index : k == SOL_REF_QUAD ? d.quads[i].dfs_index : d.triangles[i].dfs_index;
+    if (have != dfs.next && !dfs.bad_ref) { dfs.bad_ref = ref; dfs.bad_want = dfs.next; }
+    dfs.next++;
+  }
 
   bool prim_box(uint32_t ref, Box& box) {
     uint32_t k = SOL_REF_KIND(ref), i = SOL_REF_INDEX(ref);
@@ -88,6 +110,7 @@ struct TreeBuilder {
     if (k == SOL_REF_NONE) { out_ref = SOL_MAKE_REF(SOL_REF_NONE, 0); out_box = empty_box(); return true; }
     if (k != SOL_REF_NODE) {
       if (!prim_box(ref, out_box)) { error = "primitive reference out of range"; return false; }
+      count_leaf(ref);
       out_ref = ref;
       return true;
     }
@@ -101,11 +124,13 @@ struct TreeBuilder {
       // goes straight to the primitive.
       Box pb;
       if (!prim_box(n.left, pb)) { error = "primitive reference out of range"; return false; }
+      count_leaf(n.left);
       out_ref = n.left;
       out_box = cast_box(n.bbox, pad);
       return true;
     }
     if (dev_index[i] >= 0) {  // shared sub-tree
+      dfs.plain = false;
       out_ref = SOL_MAKE_REF(SOL_REF_NODE, (uint32_t)dev_index[i]);
       out_box = cast_box(n.bbox, pad);
       return true;
