@@ -27,6 +27,7 @@
 //   * the FLOAT instantiation alone carries the eight fp32-only rules of DESIGN.md 4 (`sizeof(R) == 4` branches: box pad, sphere
 //     roots in the sphere's box, needle triangles, rotated triangle records, sphere / quad hit points back on their surface, the
 //     cancellation-free sphere test, no hit on the flat primitive a ray leaves); the double instantiation is the reference's lines.
+//     Each can be switched off per render for the float instantiation (orc_render_rules; the mutants of tests/test_f64_gate_power.py).
 //
 // Build: see oracle/Makefile (g++ -O2 -ffp-contract=off: no FMA contraction, so float results are the plain
 // IEEE sequence the device code reproduces).
@@ -239,9 +240,13 @@ template <typename R> struct Scene {
   R box_pad = 0;  // fp32 box pad (0 in f64)
   R tri_delta = 0; // tolerance of the triangle consistency rule (strict_tri): 0.8 box pads
   bool strict_tri = false;  // fp32 only: the scene has needle triangles - fatter pad, consistency rule of hit_triangle (solstrale_hip.h, sol_scene_has_needles)
+  uint32_t disabled = 0;    // TEST INFRASTRUCTURE (orc_render_rules): bit k-1 switches fp32 rule k of DESIGN.md 4 off; read by the float instantiation only
+  // fp32 rule k (1 - 8) applies: float instantiation, and not switched off for this render
+  bool rule(int k) const { return sizeof(R) == 4 && !((disabled >> (k - 1)) & 1u); }
 
   static V3<R> cv(const double* p) { return {(R)p[0], (R)p[1], (R)p[2]}; }
-  explicit Scene(const SolSceneDesc& d) {
+  explicit Scene(const SolSceneDesc& d, uint32_t disabled_rules = 0) {
+    disabled = sizeof(R) == 4 ? disabled_rules : 0u;
     root = d.root; width = d.width; height = d.height; shader = d.shader_kind; max_depth = d.max_depth;
     background = cv(d.background);
     if (d.abi_version >= 2 && d.env_texels && d.env_width && d.env_height) { env = d.env_texels; env_w = d.env_width; env_h = d.env_height; env_scale = (R)d.env_scale; }
@@ -265,16 +270,17 @@ template <typename R> struct Scene {
       pad = (R)(S * (1.0f / 1048576.0f));
       // (ORC_NO_NEEDLE_RULE: a diagnostic switch of this checker only - "plain fp32" for tests/tools/needle_bias.py, which measures what the
       // rule does to the image; the device has no such switch and the parity tests never set it)
-      strict_tri = sol_scene_has_needles(&d) != 0 && !std::getenv("ORC_NO_NEEDLE_RULE");
+      strict_tri = rule(3) && sol_scene_has_needles(&d) != 0 && !std::getenv("ORC_NO_NEEDLE_RULE");
       if (strict_tri) pad = (R)(S * (SOL_NEEDLE_PAD / 1048576.0f));  // (the consistency tolerance of hit_triangle is 0.8 of it)
     }
     box_pad = pad;
     tri_delta = pad * (R)0.8f;
+    const R node_pad = rule(1) ? pad : (R)0;  // (rule 1 off: the cast boxes unpadded, the needle rule's fatter pad included; its tolerance and rule 2's slack stay)
     nodes.resize(d.n_nodes);
     for (uint32_t i = 0; i < d.n_nodes; ++i) {
       for (int k = 0; k < 6; k += 2) {
-        nodes[i].box[k] = (R)d.nodes[i].bbox.v[k] - pad;
-        nodes[i].box[k + 1] = (R)d.nodes[i].bbox.v[k + 1] + pad;
+        nodes[i].box[k] = (R)d.nodes[i].bbox.v[k] - node_pad;
+        nodes[i].box[k + 1] = (R)d.nodes[i].bbox.v[k + 1] + node_pad;
       }
       nodes[i].left = d.nodes[i].left; nodes[i].right = d.nodes[i].right;
     }
@@ -293,7 +299,7 @@ template <typename R> struct Scene {
       const SolTriangle& s = d.triangles[i];
       // fp32 contract (solstrale_hip.h, sol_triangle_rotation): the float record starts at the vertex opposite the longest edge; f64
       // keeps the reference's order (a triangle LIGHT is sampled in the reference's frame either way: light_frames below)
-      const int k = sizeof(R) == 4 ? sol_triangle_rotation(&s) : 0;
+      const int k = rule(4) ? sol_triangle_rotation(&s) : 0;
       double v0[3], e1[3], e2[3];
       int uo[3];
       sol_triangle_rotated(&s, k, v0, e1, e2, uo);
@@ -422,7 +428,7 @@ template <typename R> struct Tracer {
     // same quad from behind at t > 0.001 and the path goes dark (C1: 4 samples in 10^5, a frame 6e-5 darker than f64, every difference of one sign; found by the
     // device-against-f64 gate of round 5). n . x = d is the quad's own plane (quad.rs:40-45), n a unit vector: one dot product and three FMAs put the point on it.
     // u, v, t and the normal stay as computed. f64: nothing changes.
-    if (sizeof(R) == 4) hp = hp + Q.normal * (Q.d - Q.normal.dot(hp));
+    if (sc.rule(7)) hp = hp + Q.normal * (Q.d - Q.normal.dot(hp));
     out = {t, hp, {Q.u.unit(), Q.v.unit(), normal}, {u, v}, front, Q.mat};
     return true;
   }
@@ -439,7 +445,7 @@ template <typename R> struct Tracer {
     // that does not cancel (Haines, Guenther, Akenine-Moeller, "Precision improvements for ray / sphere intersection", Ray Tracing Gems 2019,
     // ch. 7). Same roots, same order, to the last digits fp32 has. f64: the reference's lines, below.
     R root_first, root_second;
-    if (sizeof(R) == 4) {
+    if (sc.rule(6)) {
       const R k = half_b / a;
       const V3<R> l = oc - r.direction * k;
       const R disc1 = S.radius * S.radius - l.length_squared();
@@ -461,7 +467,7 @@ template <typename R> struct Tracer {
     // otherwise report points that lie outside every box bounding the sphere. In f64 (the reference) nothing is added.
     auto root_ok = [&](R root) {
       if (!contains(tmin, tmax, root)) return false;
-      if (sizeof(R) == 4) {
+      if (sc.rule(2)) {
         const V3<R> p = r.at(root);
         const R lim = std::fabs(S.radius) + sphere_slack;  // (|r|: the reference knows a radius only through r^2 and its min/max box - a negative one is the hollow-glass idiom)
         return std::fabs(p.x - S.center.x) <= lim && std::fabs(p.y - S.center.y) <= lim && std::fabs(p.z - S.center.z) <= lim;
@@ -490,7 +496,7 @@ template <typename R> struct Tracer {
     // t > 0.001: one more bounce, darker (Cornell box + 10 000 spheres: 7 % more rays, the frame 8 % darker than f64). The direction
     // centre -> point is good to an ulp whatever t is; the point at distance r along it is what f64 computes to 13 digits. Normal, uv and
     // tangents are taken from the point as computed, as before. f64: nothing changes.
-    if (sizeof(R) == 4) hp = S.center + n * (std::fabs(S.radius) / n.length());  // (|r|: a negative radius must not send the point to the antipode)
+    if (sc.rule(5)) hp = S.center + n * (std::fabs(S.radius) / n.length());  // (|r|: a negative radius must not send the point to the antipode)
     out = {root, hp, {tangent, bi_tangent, normal}, uv, front, S.mat};
     return true;
   }
@@ -742,7 +748,7 @@ template <typename R> struct Tracer {
     // 1e-5 off its plane at coordinates of hundreds, and a grazing ray (|n.d| of a few per cent) finds the plane again at t just above RAY_MIN = 1e-3 - from
     // C1's camera 7 samples in a million went into the box they had just left and came back black. When the closest hit is that primitive, the search is
     // repeated behind it.
-    if (sizeof(R) == 4 && any_hit && ray.from != 0u && c.ref == ray.from) {
+    if (sc.rule(8) && any_hit && ray.from != 0u && c.ref == ray.from) {
       Cand<R> behind;
       any_hit = hit_ref(sc.root, ray, std::nextafter(c.t, std::numeric_limits<R>::infinity()), std::numeric_limits<R>::infinity(), behind);
       if (any_hit) c = behind;
@@ -808,11 +814,11 @@ template <typename R> struct Tracer {
 
 template <typename R>
 int render_impl(const SolSceneDesc* d, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t first, uint32_t n,
-                uint64_t seed, int threads, double* out, OrcStats* stats) {
+                uint64_t seed, int threads, double* out, OrcStats* stats, uint32_t disabled_rules) {
   if (!d || !out || d->width < 2 || d->height < 2) return -1;
   if (d->n_lights == 0) return -2;
   x1 = std::min(x1, d->width); y1 = std::min(y1, d->height);
-  Scene<R> sc(*d);
+  Scene<R> sc(*d, disabled_rules);
   if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
   if (threads <= 0) threads = 1;
   std::atomic<uint32_t> next_row{y0};
@@ -854,8 +860,13 @@ extern "C" {
 
 int orc_render(const SolSceneDesc* d, int real_kind, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t first,
                uint32_t n, uint64_t seed, int threads, double* out, OrcStats* stats) {
-  if (real_kind == ORC_F32) return render_impl<float>(d, x0, y0, x1, y1, first, n, seed, threads, out, stats);
-  return render_impl<double>(d, x0, y0, x1, y1, first, n, seed, threads, out, stats);
+  return orc_render_rules(d, real_kind, x0, y0, x1, y1, first, n, seed, threads, out, stats, 0u);
+}
+
+int orc_render_rules(const SolSceneDesc* d, int real_kind, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t first,
+                     uint32_t n, uint64_t seed, int threads, double* out, OrcStats* stats, uint32_t disabled_rules) {
+  if (real_kind == ORC_F32) return render_impl<float>(d, x0, y0, x1, y1, first, n, seed, threads, out, stats, disabled_rules);
+  return render_impl<double>(d, x0, y0, x1, y1, first, n, seed, threads, out, stats, 0u);
 }
 
 // ---- known-answer-test hooks (tests/test_oracle_kat.py) ------------------------------------------------------

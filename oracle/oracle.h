@@ -27,6 +27,10 @@ typedef struct OrcStats {
  * Returns 0, -1 bad input, -2 no light. */
 int orc_render(const SolSceneDesc* d, int real_kind, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t first,
                uint32_t n, uint64_t seed, int threads, double* out, OrcStats* stats);
+/* orc_render with fp32 rules switched off: bit k-1 of disabled_rules turns off rule k (1 - 8) of DESIGN.md 4 in the FLOAT instantiation
+ * (the double one has none). Mask 0 is orc_render. A mutant of the contract for measuring what the f64 gate sees; the device has no such switch. */
+int orc_render_rules(const SolSceneDesc* d, int real_kind, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t first,
+                     uint32_t n, uint64_t seed, int threads, double* out, OrcStats* stats, uint32_t disabled_rules);
 
 void orc_vec3_ops(const double a[3], const double b[3], double out[16]);
 void orc_vec3_reflect(const double v[3], const double n[3], double out[3]);

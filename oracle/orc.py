@@ -52,6 +52,8 @@ def load():
 
     sig("orc_render", C.c_int, [C.POINTER(_abi.SolSceneDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                 C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, _D, C.POINTER(OrcStats)])
+    sig("orc_render_rules", C.c_int, [C.POINTER(_abi.SolSceneDesc), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, _D, C.POINTER(OrcStats), C.c_uint32])
     sig("orc_vec3_ops", None, [_D, _D, _D])
     sig("orc_vec3_reflect", None, [_D, _D, _D])
     sig("orc_vec3_refract", None, [_D, _D, C.c_double, _D])
@@ -70,16 +72,37 @@ def load():
     return lib
 
 
-def render(scene, first_sample, n_samples, seed, real=ORC_F32, rect=None, threads=0, out=None):
-    """Sums of samples [first, first+n) per pixel; returns (H, W, 3) float64 (row 0 = top) and the counters."""
+def default_threads():
+    """Worker threads of a render that names none: the CPUs this process may run on, capped by OMP_NUM_THREADS when that is set (a shared
+    machine's share; the C library's own default, hardware_concurrency, is the whole machine)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    cap = os.environ.get("OMP_NUM_THREADS", "")
+    if cap.isdigit() and int(cap) > 0:
+        n = min(n, int(cap))
+    return max(n, 1)
+
+
+def rule_bit(k):
+    """The disabled_rules bit of fp32 rule k (1 - 8) of DESIGN.md 4."""
+    assert 1 <= k <= 8, k
+    return 1 << (k - 1)
+
+
+def render(scene, first_sample, n_samples, seed, real=ORC_F32, rect=None, threads=0, out=None, disabled_rules=0):
+    """Sums of samples [first, first+n) per pixel; returns (H, W, 3) float64 (row 0 = top) and the counters. threads <= 0: default_threads()
+    (the result does not depend on the count: every pixel sums its samples in order on one thread).
+    disabled_rules: fp32 rules switched off in the float instantiation (bit k-1 = rule k; see rule_bit) - a mutant of the contract, for
+    measuring what the f64 gate sees. 0 is the contract."""
     lib = load()
     h, w = scene.height, scene.width
     if out is None:
         out = np.zeros((h, w, 3), dtype=np.float64)
     x0, y0, x1, y1 = rect if rect else (0, 0, w, h)
     st = OrcStats()
-    rc = lib.orc_render(scene.desc_ptr, real, x0, y0, x1, y1, first_sample, n_samples, seed, threads,
-                        out.ctypes.data_as(_D), C.byref(st))
+    if threads <= 0:
+        threads = default_threads()
+    rc = lib.orc_render_rules(scene.desc_ptr, real, x0, y0, x1, y1, first_sample, n_samples, seed, threads,
+                              out.ctypes.data_as(_D), C.byref(st), disabled_rules)
     if rc != 0:
         raise RuntimeError({-1: "orc_render: bad input", -2: "Scene should have at least one light"}.get(rc, str(rc)))
     return out, st.as_dict()

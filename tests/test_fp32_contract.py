@@ -94,12 +94,28 @@ def test_the_needle_rule_stays_out_of_a_lights_pdf():
     assert abs(a.mean() - b.mean()) < 2e-5 * b.mean(), (a.mean(), b.mean())  # (was 3.3e-3)
 
 
+def _two_bounce_surplus_rays(rules=()):
+    """Rays the float oracle traces beyond the double one on the f64 gate's two-bounce C2 crop (tests/f64_gate.py, c2_spheres_two_bounces), as a
+    window frame at 16 spp: at two bounces per path the two arithmetics trace the same rays, and a re-hit from inside a sphere is a surplus."""
+    from solstrale_amd import scenes
+    sc = scenes.cornell_spheres(RenderConfig(1920, 1080, 16, PathTracingShader(2)))
+    win = pu.WindowScene(sc, (900, 500, 1028, 628))
+    _, sa = orc.render(win, 0, 16, pu.SEED, real=orc.ORC_F32, disabled_rules=_mask(rules))
+    _, sb = orc.render(win, 0, 16, pu.SEED, real=orc.ORC_F64)
+    return sa["live_rays"] - sb["live_rays"]
+
+
 def test_sphere_hit_points_lie_on_the_sphere():
     """Fifth fp32-only rule, found by comparing the float oracle with the double one on BASELINE config 2 (Cornell box + 10 000 spheres of
     radius 3 - 8, camera 800 units away): the reference's quadratic in single precision reports t a few thousandths off for a distant
     origin, the hit point lay that deep inside the sphere, and the scattered ray re-hit the same sphere from within - 7 % more rays, the
     frame 8 % darker than f64. With the point put back on the sphere the two arithmetics trace the same number of rays and agree in the
-    mean within the noise of the paths that round apart."""
+    mean within the noise of the paths that round apart.
+    Since rule 6 (exact roots) the point is off by far less, and the full-depth frame below sees the two rules only together (without rule 5
+    alone: rays +7e-4, mean +7.9e-3 - inside its bounds; without 5 and 6: +7.1 %, -7.3 %). Rule 5 alone shows as surplus rays at two bounces
+    per path, where float and double otherwise trace the same rays: 30 more of 537 k without it, 1 fewer with it (the f64 gate's
+    c2_spheres_two_bounces case sees the same)."""
+    assert abs(_two_bounce_surplus_rays()) <= 3
     from solstrale_amd import scenes
     sc = scenes.cornell_spheres(RenderConfig(128, 72, 24))
     a, sa = orc.render(sc, 0, 24, pu.SEED, real=orc.ORC_F32)
@@ -211,3 +227,121 @@ def test_float_follows_double_on_the_reference_scenes():
         ok = np.isfinite(a) & np.isfinite(b)  # (the Simple shader's colours can be NaN on both sides alike)
         assert (np.isfinite(a) == np.isfinite(b)).all(), name
         assert abs(a[ok].mean() - b[ok].mean()) <= 1e-4 * abs(b[ok].mean()), (name, a[ok].mean(), b[ok].mean())
+
+
+def _mask(rules):
+    mask = 0
+    for k in rules:
+        mask |= orc.rule_bit(k)
+    return mask
+
+
+def _rel(sc, spp, rules):
+    a, _ = orc.render(sc, 0, spp, pu.SEED, real=orc.ORC_F32, disabled_rules=_mask(rules))
+    b, _ = orc.render(sc, 0, spp, pu.SEED, real=orc.ORC_F64)
+    return (a.mean() - b.mean()) / b.mean()
+
+
+def flat_node_scene(render_config):
+    """Rule 1's case: two coplanar quads that share a tree node - a box of zero depth - 3000 units from the origin, seen head-on from 800
+    units further out. The reference's PAD_DELTA (1e-4) is below fp32's spacing there (2.4e-4): cast to fp32 the box is flat."""
+    b = SceneBuilder()
+    m = b.Lambertian(b.SolidColor(.8, .6, .4))
+    z = 3000.
+    pair = b.Bvh([b.Quad((-2., -2., z), (2., 0., 0.), (0., 4., 0.), m), b.Quad((0., -2., z), (2., 0., 0.), (0., 4., 0.), m)])
+    light = b.Sphere((0., 50., z + 100.), 5., b.DiffuseLight(4., 4., 4.))
+    cam = CameraConfig(0.3, 0., (0., 0., z + 800.), (0., 0., z), (0., 1., 0.))
+    return b.finish(b.Bvh([pair, light]), cam, (.1, .1, .1), render_config)
+
+
+def _two_trees(build, render_config):
+    """The same world under two trees: one flat node over everything, and a nesting that bounds every other primitive by boxes of its own."""
+    return [build(render_config, t) for t in (0, 1)]
+
+
+def far_spheres_scene(render_config, tree):
+    """Forty small spheres over a floor, seen through a long lens from ~850 units (rule 2's regime: the reference's roots lose their digits)."""
+    b = SceneBuilder()
+    rng = np.random.default_rng(3)
+    sph = [b.Sphere(tuple(rng.uniform(-3, 3, 3)), float(rng.uniform(.2, .9)), b.Lambertian(b.SolidColor(*rng.uniform(.2, .9, 3))))
+           for _ in range(40)]
+    floor = b.Quad((-10., -4., -10.), (20., 0., 0.), (0., 0., 20.), b.Lambertian(b.SolidColor(.6, .6, .6)))
+    light = b.Sphere((0., 20., 0.), 4., b.DiffuseLight(6., 6., 6.))
+    world = (b.Bvh(sph + [floor, light]) if tree == 0 else
+             b.Bvh([b.Bvh(sph[::2]), b.Bvh([b.Bvh(sph[1::4]), b.Bvh(sph[3::4])]), floor, light]))
+    return b.finish(world, CameraConfig(0.45, 0., (0., 300., 800.), (0., 0., 0.), (0., 1., 0.)), (.3, .4, .5), render_config)
+
+
+def flat_needles_scene(render_config, tree):
+    """Sixty 2000:1 needle triangles in planes z = const (boxes of zero depth) over a floor, from ~850 units; tree 1 gives each needle a
+    node of its own (with a speck far away)."""
+    b = SceneBuilder()
+    rng = np.random.default_rng(5)
+    tris = []
+    for _ in range(60):
+        c, a = rng.uniform(-3, 3, 3), rng.uniform(0, 2 * np.pi)
+        d, w = np.array([np.cos(a), np.sin(a), 0.]), np.array([-np.sin(a), np.cos(a), 0.])
+        tris.append(b.Triangle(tuple(c), tuple(c + 4 * d), tuple(c + 4 * d + 0.002 * w), b.Lambertian(b.SolidColor(*rng.uniform(.2, .9, 3)))))
+    grey = b.Lambertian(b.SolidColor(.7, .7, .7))
+    floor = b.Quad((-10., -4., -10.), (20., 0., 0.), (0., 0., 20.), grey)
+    light = b.Sphere((0., 20., 0.), 4., b.DiffuseLight(6., 6., 6.))
+    world = (b.Bvh(tris + [floor, light]) if tree == 0 else
+             b.Bvh([b.Bvh([t, b.Sphere((0., 0., -50.), 0.1, grey)]) for t in tris] + [floor, light]))
+    return b.finish(world, CameraConfig(0.45, 0., (0., 300., 800.), (0., 0., 0.), (0., 1., 0.)), (.3, .4, .5), render_config)
+
+
+def _tree_dependent_pixels(scenes_, spp, rules):
+    a, b = (orc.render(sc, 0, spp, pu.SEED, real=orc.ORC_F32, disabled_rules=_mask(rules))[0] for sc in scenes_)
+    return int((a != b).any(axis=-1).sum())
+
+
+def test_each_rule_bit_brings_its_defect_back():
+    """orc.render's disabled_rules switches fp32 rules off in the float oracle (the mutants of tests/test_f64_gate_power.py). Each bit must
+    reach its rule: with it set, the defect the rule was made for comes back on a scene where it fires. This also tests the rule tests above.
+    Rules 1 - 3 exist so that a hit lies inside every box that bounds its primitive: the oracle tests node boxes (it only does not cull by t),
+    so their defect is a lost hit (rule 1) or a frame that depends on the tree (rules 2 and 3). Rule 2 fires only under the reference's
+    cancelling roots (rule 6 off), rule 3 only on records that start at the wrong vertex (rule 4 off): with rules 6 and 4 in, their
+    phantoms do not arise."""
+    import random_scenes
+    from solstrale_amd import scenes
+    # rule 1: the flat node collapses in fp32 and the quads vanish (mean 0.54 -> 0.10, the background: -82 %)
+    flat = flat_node_scene(RenderConfig(64, 64, 4, AlbedoShader()))
+    assert abs(_rel(flat, 4, ())) < 1e-6
+    assert _rel(flat, 4, (1,)) < -0.5
+    # rule 2: phantom roots outside the sphere's box - seen through one tree, not through the other
+    spheres = _two_trees(far_spheres_scene, RenderConfig(96, 64, 8, PathTracingShader(6)))
+    assert _tree_dependent_pixels(spheres, 8, ()) == 0
+    assert _tree_dependent_pixels(spheres, 8, (6,)) == 0
+    assert _tree_dependent_pixels(spheres, 8, (6, 2)) > 20  # (measured: 62)
+    # rule 3: phantom needle hits, likewise (rule 4 off: the needle rule alone refuses them)
+    needles = _two_trees(flat_needles_scene, RenderConfig(96, 64, 16, PathTracingShader(6)))
+    assert _tree_dependent_pixels(needles, 16, (4,)) == 0
+    assert _tree_dependent_pixels(needles, 16, (4, 3)) > 0  # (measured: 1 pixel - a phantom is rare, the defect is its dependence)
+    # rule 4: a needle whose record starts at the wrong vertex is refused by the needle rule - the strip light loses a third (round 4: -34 %)
+    strip = strip_light_scene(300, RenderConfig(96, 64, 48, PathTracingShader(8)))
+    assert _rel(strip, 48, ()) == pytest.approx(0, abs=1e-4)
+    assert _rel(strip, 48, (4,)) < -0.2
+    # rule 5: surplus rays on C2 with two bounces (test_sphere_hit_points_lie_on_the_sphere; the contract: within 3)
+    assert _two_bounce_surplus_rays((5,)) >= 15  # (measured: 30)
+    # rule 6: the long lens's sphere rims (test_spheres_through_a_long_lens: up to 10 % darker)
+    far = random_scenes.random_scene(35, spp=32, far=100.0)
+    assert abs(_rel(far, 32, ())) < 2e-3
+    assert _rel(far, 32, (6,)) < -0.05
+    # rule 7: with rule 8 off too, C1's tall box is round 5's crop again (z = -4.4 before rule 7)
+    sc = scenes.cornell_box(RenderConfig(400, 400, 64))
+    x0, y0, x1, y1 = rect = (60, 120, 188, 248)
+    b, _ = orc.render(sc, 0, 64, pu.SEED, real=orc.ORC_F64, rect=rect)
+    for rules, z_range in (((), (-3, 3)), ((7, 8), (-10, -3))):
+        a, _ = orc.render(sc, 0, 64, pu.SEED, real=orc.ORC_F32, rect=rect, disabled_rules=sum(orc.rule_bit(k) for k in rules))
+        d = (a - b)[y0:y1, x0:x1].sum(axis=-1)
+        z = d.sum() / np.sqrt((d ** 2).sum())
+        assert z_range[0] < z < z_range[1], (rules, z)
+    # rule 8: the dark samples of test_a_ray_does_not_hit_the_flat_primitive_it_leaves come back (124 in 1024 samples before the rule)
+    sc1 = scenes.cornell_box(RenderConfig(400, 400, 1))
+    dark = 0
+    for s in range(128):
+        a, _ = orc.render(sc1, s, 1, pu.SEED, real=orc.ORC_F32, rect=rect, disabled_rules=orc.rule_bit(8))
+        b, _ = orc.render(sc1, s, 1, pu.SEED, real=orc.ORC_F64, rect=rect)
+        a, b = a[y0:y1, x0:x1].sum(axis=-1), b[y0:y1, x0:x1].sum(axis=-1)
+        dark += int(((a < 1e-6) & (b > 1e-3)).sum())
+    assert dark > 8, dark  # (the contract: at most 8 in twice the samples)
