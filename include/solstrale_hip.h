@@ -180,8 +180,9 @@ typedef struct SolSceneDesc {
    * src/renderer/mod.rs:197-204; BASELINE.json config 5 names an "HDRI env light"). A latitude-longitude map of linear RGB
    * radiance, fp32, row 0 = up (+y): a ray that hits nothing returns env_scale * texel(direction) instead of `background`.
    * The direction is mapped like a point on the reference's unit sphere (calculate_sphere_uv, src/hittable/sphere.rs:134-140)
-   * and the texel picked like an ImageMap's (nearest, src/material/texture.rs:170-179). It is NOT importance-sampled: the
-   * scene still needs a light (Renderer::new). env_texels == NULL (or width/height 0) = no environment. */
+   * and the texel picked like an ImageMap's (nearest, src/material/texture.rs:170-179). By default it is NOT importance-sampled
+   * (a ray finds it only when the BSDF's direction escapes); sol_env_sampling turns on sampling it as one more light (opt-in,
+   * DESIGN.md 12). The scene still needs a light (Renderer::new). env_texels == NULL (or width/height 0) = no environment. */
   const float* env_texels;      uint32_t env_width, env_height;
   double env_scale;
 } SolSceneDesc;
@@ -476,6 +477,33 @@ int sol_tonemap_rgb8_adaptive(SolScene* scene, const void* image_dev, uint8_t* r
 /* Rescales image_dev (W*H*3 floats, device) in place to sum * max_samples / n_b, so that sol_bloom / sol_bloom_rgb8 with
  * max_samples see sums of a uniform count. */
 int sol_adaptive_rescale(SolScene* scene, void* image_dev);
+
+/* ---- environment importance sampling (EXTENSION, not in the reference; opt-in) -----------------------------------
+ * Mode 1 makes the environment map entry L = n_lights of the light mixture: the light half of a Lambertian or Isotropic scatter picks
+ * one of L + 1 entries, and its density is (sum of the lights' densities + the map's) / (L + 1). The map is drawn from per cell by
+ * luminance times sin(theta) (cell (i, j) = texel (i, j), i < max(W - 1, 1), j < max(H - 1, 1): the texels a lookup reads); the tables
+ * are built on the scene's stream on first use, in a fixed order, bit-identical on every device. Only renders of the path-tracing shader
+ * change; mode 0 (the default) leaves every frame as it was. While it is on: path-tracing renders run the product kernel whatever
+ * SOL_OPT_KERNEL says, adaptive rounds use it, sol_render_counted and sol_debug_path are SOL_EINVAL. Changing the mode ends an adaptive
+ * session. SOL_EINVAL: a bad size, an unknown mode, non-zero reserved fields (all checked before the scene), no environment map,
+ * env_scale <= 0, or a map whose cell weights sum to 0. */
+#define SOL_ENV_SAMPLING_OFF 0u
+#define SOL_ENV_SAMPLING_IMPORTANCE 1u
+typedef struct SolEnvSampling {
+  uint32_t size;           /* in: sizeof(SolEnvSampling): lets the struct grow                                           */
+  uint32_t mode;           /* SOL_ENV_SAMPLING_OFF / SOL_ENV_SAMPLING_IMPORTANCE                                          */
+  uint32_t reserved[2];    /* 0                                                                                          */
+} SolEnvSampling;
+/* config == NULL or mode 0: off. */
+int sol_env_sampling(SolScene* scene, const SolEnvSampling* config);
+/* Host only (no device needed): the checks sol_env_sampling makes, on a description. */
+int sol_env_sampling_check(const SolSceneDesc* desc, const SolEnvSampling* config);
+/* Diagnostic: the tables (built by sol_env_sampling mode 1): the marginal CDF over the H' cell rows, the conditional CDFs (H' rows of W',
+ * row-major), both normalised, and the total cell weight. NULL pointers are skipped. */
+int sol_env_tables(SolScene* scene, float* marginal, size_t n_marginal, float* conditional, size_t n_conditional, float* total);
+/* Diagnostic: the device's own sampler and density on n host rows. fn 0: (r1, r2) in [0, 1) -> (direction xyz, pdf, cell i, cell j),
+ * 2 floats in, 6 out per row; fn 1: direction xyz -> (pdf, cell i, cell j), 3 in, 3 out. Needs the tables. */
+int sol_env_eval(SolScene* scene, uint32_t fn, const float* in, uint32_t n, float* out);
 
 int sol_stats(const SolScene* scene, SolStats* out);
 /* What the paths of the last instrumented render (sol_render_counted, one-path-per-lane kernel) looked like - how hard a workload

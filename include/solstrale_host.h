@@ -97,6 +97,10 @@ int solh_set_post_processors(SolhBuilder* b, int n, const int* kinds, const doub
  * = samples spent / (blocks * samples_per_pixel), the last event 1.0); images are tone-mapped with each block's own count (Nop) or
  * rescaled to samples_per_pixel before bloom. One device: solh_ray_trace_devices with more than one device fails. */
 int solh_set_adaptive(SolhBuilder* b, uint32_t round, uint32_t min_samples, double threshold);
+/* EXTENSION, not in the reference: environment importance sampling (solstrale_hip.h sol_env_sampling) for the following
+ * solh_ray_trace calls: mode 0 off (the default), 1 importance sampling, on every device the call renders on. Unknown modes fail here;
+ * a scene without an environment map fails in solh_ray_trace. */
+int solh_set_env_sampling(SolhBuilder* b, uint32_t mode);
 typedef void (*solh_progress_fn)(void* user, double progress, double fps, double eta_seconds,
                                  const uint8_t* image_rgb8, uint32_t width, uint32_t height);
 typedef int (*solh_abort_fn)(void* user);

@@ -1119,6 +1119,7 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
     if ((rc = sol_upload(env, &s->env))) return rc;
     S.env = s->env; S.env_w = d->env_width; S.env_h = d->env_height; S.env_scale = (float)d->env_scale;
   }
+  s->env_refusal = sol_env_refusal(d);  // (environment importance sampling, sol_envmap.hip: stops at the first cell of positive weight)
   S.bgx = (float)d->background[0]; S.bgy = (float)d->background[1]; S.bgz = (float)d->background[2];
   S.cam = cast_camera(d->camera);
   s->kernel_version = ovr.kernel_version;

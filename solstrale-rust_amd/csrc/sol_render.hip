@@ -19,7 +19,9 @@
 // is a plain LDS access, the spill branches and their waits fold away.
 // STRICT = true: built for scenes with needle triangles (include/solstrale_hip.h, sol_scene_has_needles): the closest hit of a finished
 // search must pass the triangle consistency rule before it is shaded, or the lane searches the same ray again for what lies behind it.
-template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT>
+// ENV = true: environment importance sampling (sol_env_sampling): the environment map is one more entry of the light mixture.
+// Built uncounted only; ENV = false is the default estimator, and its code does not depend on the ENV builds.
+template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT, bool ENV>
 __global__ void __launch_bounds__(SOL_WG, SOL_V1_MIN_WAVES)  // 4 waves per SIMD: the 32 KiB LDS stack allows 5 workgroups per CU, 128 VGPRs 4
 sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* __restrict__ acc, float* __restrict__ partial,
                   uint32_t* __restrict__ work_counter, uint32_t* __restrict__ spill, DevCounters* __restrict__ dcnt) {
@@ -77,7 +79,7 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
         p.o = t.o; p.d = t.d;  // (the ray lives in the search state while it is traced)
         f3 c;
         if (COUNT && p.depth == 0u && SOL_REF_KIND(t.h.ref) != SOL_REF_NONE) cnt.primary_hits++;
-        if (shade_vertex<COUNT, STRICT>(S, p, t.h, c, cnt)) {
+        if (shade_vertex<COUNT, STRICT, ENV>(S, p, t.h, c, cnt)) {
           if (COUNT) count_path(cnt, p.depth + 1u);  // (depth counts the scatterings before this vertex)
           sum = sum + c;  // add_row_data (src/renderer/mod.rs:361-365): sums, not means
           alive = false;
@@ -271,10 +273,10 @@ hipError_t sol_launch_debug_path(const DevScene& S, const RenderParams& P, uint3
 }
 
 // ---- launch wrappers (called from sol_launch.cpp) ----
-template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT>
+template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT, bool ENV = false>
 static hipError_t launch_v1(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
                             uint32_t* spill, DevCounters* cnt, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL((sol_render_kernel<COUNT, MEDIUM, SPILL, STRICT>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
+  hipLaunchKernelGGL((sol_render_kernel<COUNT, MEDIUM, SPILL, STRICT, ENV>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
   return hipGetLastError();
 }
 template <bool STRICT>
@@ -287,10 +289,23 @@ static hipError_t launch_v1_any(const DevScene* dS, const RenderParams& P, float
   return medium ? launch_v1<false, true, false, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
                 : launch_v1<false, false, false, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
 }
+template <bool STRICT>  // (ENV: plain renders only - sol_render_counted refuses while importance sampling is on)
+static hipError_t launch_v1_env(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, DevCounters* cnt,
+                                uint32_t grid, bool medium, bool may_spill, hipStream_t stream) {
+  if (may_spill) return medium ? launch_v1<false, true, true, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream)
+                               : launch_v1<false, false, true, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream);
+  return medium ? launch_v1<false, true, false, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream)
+                : launch_v1<false, false, false, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream);
+}
 
 hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
                              uint32_t* spill, void* pool, DevCounters* cnt, uint32_t grid, bool count, bool medium, bool may_spill,
-                             hipStream_t stream) {
+                             bool env, hipStream_t stream) {
+  if (env) {
+    if (version != 1 || count) return hipErrorInvalidValue;  // (sol_render_impl runs importance sampling on the uncounted product kernel only)
+    return S.tri_delta > 0.0f ? launch_v1_env<true>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream)
+                              : launch_v1_env<false>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
+  }
 #ifdef SOL_AB_KERNELS
   if (version == 4) return sol_launch_pool4(S, dS, P, partial, work, spill, grid, medium, may_spill, count ? cnt : nullptr, stream);  // (sol_pool.hip)
 #endif
@@ -310,17 +325,21 @@ static int blocks_per_cu(K kernel) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
   return n;
 }
-int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict) {
+int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env) {
+  if (env) {
+    if (strict) return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true, true>);
+    return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, true>) : blocks_per_cu(sol_render_kernel<false, false, true, false, true>);
+  }
 #ifdef SOL_AB_KERNELS
   if (version == 4) return sol_pool4_blocks_per_cu(medium, strict);
 #endif
   if (version == 1) {  // (the SPILL = false builds need no more registers or LDS than these)
     if (strict) {
-      if (count) return medium ? blocks_per_cu(sol_render_kernel<true, true, true, true>) : blocks_per_cu(sol_render_kernel<true, false, true, true>);
-      return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true>);
+      if (count) return medium ? blocks_per_cu(sol_render_kernel<true, true, true, true, false>) : blocks_per_cu(sol_render_kernel<true, false, true, true, false>);
+      return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, false>) : blocks_per_cu(sol_render_kernel<false, false, true, true, false>);
     }
-    if (count) return medium ? blocks_per_cu(sol_render_kernel<true, true, true, false>) : blocks_per_cu(sol_render_kernel<true, false, true, false>);
-    return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false>) : blocks_per_cu(sol_render_kernel<false, false, true, false>);
+    if (count) return medium ? blocks_per_cu(sol_render_kernel<true, true, true, false, false>) : blocks_per_cu(sol_render_kernel<true, false, true, false, false>);
+    return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, false>) : blocks_per_cu(sol_render_kernel<false, false, true, false, false>);
   }
 #ifdef SOL_AB_KERNELS
   return sol_pool_blocks_per_cu(count, medium);

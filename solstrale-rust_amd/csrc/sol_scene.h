@@ -180,7 +180,16 @@ struct SolScene {
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   uint32_t timed_launches = 0, last_grid = 0;
   SolAdaptiveSession adaptive;
+  // Environment importance sampling (sol_envmap.hip). env_refusal: why sol_env_sampling refuses this scene ("": it may turn it on),
+  // decided at creation from the description (sol_env_refusal); env_tables: one allocation - marginal CDF (H'), conditional CDFs (H' x W'),
+  // row totals (H'), total (1) - built on first use and kept; env_is: renders of the path-tracing shader run the ENV kernels.
+  std::string env_refusal;
+  float* env_tables = nullptr;
+  float env_total = 0.f;
+  bool env_is = false;
 };
+// Why environment importance sampling cannot run on the scene `d` describes, or "" (sol_envmap.hip; host only).
+std::string sol_env_refusal(const SolSceneDesc* d);
 
 int sol_rebuild_order(SolScene* s);
 int sol_set_partition(SolScene* s, int rank, int world);

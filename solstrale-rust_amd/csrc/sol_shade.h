@@ -178,14 +178,89 @@ DEV f3 light_random_direction(const DevScene& S, uint32_t ref, uint32_t light_in
   float zz = sol_sqrt(1.0f - z * z);
   return onb_local(uvw, mk3(c * zz, s * zz, z));
 }
-template <bool COUNT, bool STRICT = false>
+// ---- EXTENSION: the environment map as one more light (tables: sol_envmap.hip) --------------------------------------
+// Cell (i, j) of the map is texel (i, j); it covers u in [i / env_cw, (i + 1) / env_cw) and 1 - v in [j / env_ch, (j + 1) / env_ch).
+DEV float ldg_f32(const float* p) { return __uint_as_float(ldg_u32(p)); }
+// The smallest k < n with r < cdf[k] (n - 1 if there is none: cdf[n - 1] == 1 > r for every draw).
+DEV uint32_t env_find(const float* cdf, uint32_t n, float r) {
+  uint32_t lo = 0, hi = n - 1u;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (r < ldg_f32(cdf + mid)) hi = mid;
+    else lo = mid + 1u;
+  }
+  return lo;
+}
+// Solid-angle density of the sampler below for a direction in cell (i, j) at polar angle theta: the cell's probability - the product of
+// the two CDF steps the sampler draws from - times cells per unit (u, v) square over d(omega) / d(u, v) = 2 pi^2 sin(theta).
+DEV float env_pdf_cell(const DevScene& S, uint32_t i, uint32_t j, float sin_theta) {
+  if (!(sin_theta > 0.0f)) return 0.0f;
+  const float* row = S.env_cond + (size_t)j * S.env_cw;
+  const float m1 = ldg_f32(S.env_marg + j), m0 = j ? ldg_f32(S.env_marg + j - 1u) : 0.0f;
+  const float c1 = ldg_f32(row + i), c0 = i ? ldg_f32(row + i - 1u) : 0.0f;
+  return (m1 - m0) * (c1 - c0) * S.env_pdf_scale / sin_theta;
+}
+// Density of a direction: its cell by env_color's mapping (sol_path.h), clamped into the cells.
+DEV float env_pdf(const DevScene& S, f3 dir, uint32_t& ci, uint32_t& cj) {
+  const f3 n = unit3(dir);
+  const float theta = acos_r(-n.y);
+  const float phi = -atan2_r(n.z, n.x) + SOL_PI;
+  const float u = phi / (2.0f * SOL_PI), v = theta / SOL_PI;
+  const float x = u * (float)S.env_cw, y = (1.0f - v) * (float)S.env_ch;
+  uint32_t xi = x >= 0.0f ? (x < 4294967296.0f ? (uint32_t)x : 0xFFFFFFFFu) : 0u;
+  uint32_t yi = y >= 0.0f ? (y < 4294967296.0f ? (uint32_t)y : 0xFFFFFFFFu) : 0u;
+  ci = min(xi, S.env_cw - 1u);
+  cj = min(yi, S.env_ch - 1u);
+  return env_pdf_cell(S, ci, cj, sol_sqrt(n.x * n.x + n.z * n.z));
+}
+// Draws a direction from (r1, r2): row j from the marginal CDF, column i from row j's conditional CDF, the offsets within the cell from
+// where the draws fall inside the chosen steps; u = (i + fu) / env_cw, 1 - v = (j + fv) / env_ch, theta = pi v, phi = 2 pi u, and the
+// direction inverts env_color's phi = -atan2(z, x) + pi, theta = acos(-y). Returns a unit vector; `pdf` is its density.
+DEV f3 env_sample(const DevScene& S, float r1, float r2, float& pdf, uint32_t& ci, uint32_t& cj) {
+  const float below_one = 0.99999994f;  // (the largest float < 1)
+  const uint32_t j = env_find(S.env_marg, S.env_ch, r1);
+  const float m0 = j ? ldg_f32(S.env_marg + j - 1u) : 0.0f, m1 = ldg_f32(S.env_marg + j);
+  const float* row = S.env_cond + (size_t)j * S.env_cw;
+  const uint32_t i = env_find(row, S.env_cw, r2);
+  const float c0 = i ? ldg_f32(row + i - 1u) : 0.0f, c1 = ldg_f32(row + i);
+  const float fv = fminf((r1 - m0) / (m1 - m0), below_one), fu = fminf((r2 - c0) / (c1 - c0), below_one);
+  const float u = ((float)i + fu) / (float)S.env_cw, w = ((float)j + fv) / (float)S.env_ch;
+  float ct, st, cp, sp;
+  sincos2pi(0.5f * (1.0f - w), ct, st);  // theta = pi v = 2 pi (v / 2)
+  sincos2pi(u, cp, sp);
+  ci = i; cj = j;
+  pdf = env_pdf_cell(S, i, j, st);
+  return mk3(-st * cp, -ct, st * sp);
+}
+
+// ENV: the environment is light entry L = n_lights of the mixture - the draw picks one of L + 1 entries, the value
+// averages L + 1 densities (the lights' in list order, then the environment's).
+template <bool COUNT, bool STRICT = false, bool ENV = false>
 DEV float container_pdf_value(const DevScene& S, f3 origin, f3 dir, Counters& cnt) {  // pdf.rs:89-96
   float sum = 0.0f;
+  if (ENV) {
+    for (uint32_t i = 0; i < S.n_lights; ++i)
+      sum += light_pdf_value<COUNT, STRICT>(S, S.n_lights == 1u ? S.light0 : ldg_u32(S.lights + i), origin, dir, cnt);
+    uint32_t ci, cj;
+    sum += env_pdf(S, dir, ci, cj);
+    return sum / (float)(S.n_lights + 1u);
+  }
   if (S.n_lights == 1u) return light_pdf_value<COUNT, STRICT>(S, S.light0, origin, dir, cnt) / 1.0f;  // (x / 1 == x: same value as the loop)
   for (uint32_t i = 0; i < S.n_lights; ++i) sum += light_pdf_value<COUNT, STRICT>(S, ldg_u32(S.lights + i), origin, dir, cnt);
   return sum / (float)S.n_lights;
 }
+template <bool ENV = false>
 DEV f3 container_pdf_generate(const DevScene& S, f3 origin, Rng& rng) {  // pdf.rs:98-101
+  if (ENV) {
+    const uint32_t k = rnd_index(rng, S.n_lights + 1u);
+    if (k == S.n_lights) {
+      const float r1 = rnd(rng), r2 = rnd(rng);
+      float pdf;
+      uint32_t ci, cj;
+      return env_sample(S, r1, r2, pdf, ci, cj);
+    }
+    return light_random_direction(S, S.n_lights == 1u ? S.light0 : ldg_u32(S.lights + k), k, origin, rng);
+  }
   uint32_t i = rnd_index(rng, S.n_lights);  // (the draw is consumed also when there is one light: same stream as the oracle)
   return light_random_direction(S, S.n_lights == 1u ? S.light0 : ldg_u32(S.lights + i), S.n_lights == 1u ? 0u : i, origin, rng);
 }
@@ -222,7 +297,7 @@ struct Scatter {
 
 // Materials::scatter (material/mod.rs:191-207 Lambertian, :239-249 Metal, :279-302 Dielectric, :359-368 DiffuseLight,
 // :396-410 Isotropic, :430-436 Blend)
-template <bool COUNT, bool STRICT = false>
+template <bool COUNT, bool STRICT = false, bool ENV = false>
 DEV void scatter(const DevScene& S, f3 ray_dir, const Surface& sf, Rng& rng, Scatter& sc, Counters& cnt) {
   DMat m = ldg_rec(S.mats + sf.mat);
   for (int guard = 0; guard < 16 && m.kind == SOL_MAT_BLEND; ++guard) m = ldg_rec(S.mats + (rnd(rng) > m.param ? m.m1 : m.m2));
@@ -233,11 +308,11 @@ DEV void scatter(const DevScene& S, f3 ray_dir, const Surface& sf, Rng& rng, Sca
     sc.color = albedo_color<COUNT>(S, m, sf.u, sf.v, cnt);
     Onb uvw = onb_new(sf.normal);  // CosinePdf::new (pdf.rs:58)
     f3 dir;
-    if (rnd(rng) < 0.5f) dir = container_pdf_generate(S, sf.p, rng);  // mix_generate (pdf.rs:42-48)
+    if (rnd(rng) < 0.5f) dir = container_pdf_generate<ENV>(S, sf.p, rng);  // mix_generate (pdf.rs:42-48)
     else dir = onb_local(uvw, random_cosine_direction(rng));
     f3 udir = unit3(dir);
     float cos_pdf = fmaxf(dot3(udir, uvw.normal) / SOL_PI, 0.0f);                                 // CosinePdf::value
-    float mix = 0.5f * container_pdf_value<COUNT, STRICT>(S, sf.p, dir, cnt) + 0.5f * cos_pdf;            // mix_value
+    float mix = 0.5f * container_pdf_value<COUNT, STRICT, ENV>(S, sf.p, dir, cnt) + 0.5f * cos_pdf;            // mix_value
     float cos_theta = dot3(sf.normal, udir);                                                      // scattering_pdf_value
     float scattering = cos_theta < 0.0f ? 0.0f : cos_theta / SOL_PI;
     sc.dir = dir;
@@ -271,10 +346,10 @@ DEV void scatter(const DevScene& S, f3 ray_dir, const Surface& sf, Rng& rng, Sca
     sc.type = SCATTER_PDF;
     sc.color = albedo_color<COUNT>(S, m, sf.u, sf.v, cnt);
     f3 dir;
-    if (rnd(rng) < 0.5f) dir = container_pdf_generate(S, sf.p, rng);
+    if (rnd(rng) < 0.5f) dir = container_pdf_generate<ENV>(S, sf.p, rng);
     else dir = unit3(random_in_unit_sphere(rng));  // SpherePdf::generate (pdf.rs:121-124)
     const float sphere_pdf = (float)(1. / (4. * 3.14159265358979323846));
-    float mix = 0.5f * container_pdf_value<COUNT, STRICT>(S, sf.p, dir, cnt) + 0.5f * sphere_pdf;
+    float mix = 0.5f * container_pdf_value<COUNT, STRICT, ENV>(S, sf.p, dir, cnt) + 0.5f * sphere_pdf;
     sc.dir = dir;
     sc.probability = sphere_pdf / mix;
   }

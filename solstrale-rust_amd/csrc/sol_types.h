@@ -203,6 +203,13 @@ struct DevScene {
   // vertex (triangle.rs:114-117), which is not the vertex the intersect record starts at (solstrale_hip.h, sol_triangle_rotation):
   // light_tri[i] = (v0, v0v1, v0v2) of light i in the reference's order when light i is a triangle (a DTri whose other fields are unused).
   const DTri* light_tri;
+  // EXTENSION, environment importance sampling (sol_envmap.hip): the normalised marginal CDF over the env_ch cell rows and
+  // the row-major conditional CDFs (env_ch x env_cw) of the cells, env_cw = max(env_w - 1, 1), env_ch = max(env_h - 1, 1); env_pdf_scale =
+  // env_cw * env_ch / (2 pi^2). Null until sol_env_sampling builds them; read only by the ENV kernels.
+  const float* env_marg;
+  const float* env_cond;
+  uint32_t env_cw, env_ch;
+  float env_pdf_scale;
 };
 
 struct RenderParams {

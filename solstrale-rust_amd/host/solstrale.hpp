@@ -269,6 +269,9 @@ struct RenderConfig {
     uint32_t round = 0, min_samples = 0;
     double threshold = 0.0;
   } adaptive;
+  // EXTENSION (not in the reference): environment importance sampling (include/solstrale_hip.h sol_env_sampling), applied to
+  // every device handle ray_trace creates; 0 off (the default), 1 importance sampling (the scene must have an environment map).
+  uint32_t env_sampling = 0;
 };
 
 struct Scene {

@@ -594,6 +594,12 @@ std::string ray_trace(const Scene& scene, const std::function<void(RenderProgres
   SolScene* const dev = devs[0];
 
   const RenderConfig& rc = scene.render_config;
+  if (rc.env_sampling) {  // EXTENSION: environment importance sampling, before any render (adaptive rounds included)
+    SolEnvSampling es{};
+    es.size = sizeof es; es.mode = rc.env_sampling;
+    for (SolScene* s : devs)
+      if (sol_env_sampling(s, &es) != SOL_OK) return sol_last_error();
+  }
   const uint32_t spp = rc.samples_per_pixel;
   const size_t npix = rc.width * rc.height;
   using clk = std::chrono::steady_clock;

@@ -313,6 +313,14 @@ int solh_set_adaptive(SolhBuilder* b, uint32_t round, uint32_t min_samples, doub
   });
 }
 
+int solh_set_env_sampling(SolhBuilder* b, uint32_t mode) {
+  return guarded([&] {
+    if (mode > SOL_ENV_SAMPLING_IMPORTANCE) throw std::runtime_error("solh_set_env_sampling: unknown mode (0 off, 1 importance)");
+    b->scene.render_config.env_sampling = mode;
+    return 0;
+  });
+}
+
 void solh_abi_sizes(uint32_t out[11]) {
   const size_t s[11] = {sizeof(SolAabb), sizeof(SolBvhNode), sizeof(SolSphere), sizeof(SolQuad), sizeof(SolTriangle),
                         sizeof(SolMedium), sizeof(SolMaterial), sizeof(SolTexture), sizeof(SolCamera), sizeof(SolSceneDesc),

@@ -155,6 +155,14 @@ class SolAdaptive(C.Structure):
                 ("threshold", C.c_float)]
 
 
+SOL_ENV_SAMPLING_OFF, SOL_ENV_SAMPLING_IMPORTANCE = 0, 1
+
+
+class SolEnvSampling(C.Structure):
+    """EXTENSION: environment importance sampling (sol_env_sampling). Not in ABI_STRUCTS (solh_abi_sizes has 11 sizes)."""
+    _fields_ = [("size", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class SolTreeCheck(C.Structure):
     _fields_ = [("n_wide", C.c_uint32), ("n_leaf_refs", C.c_uint32), ("n_primitives", C.c_uint32), ("depth", C.c_uint32),
                 ("max_children", C.c_uint32), ("box_violations", C.c_uint32), ("leaf_mismatches", C.c_uint32),
@@ -223,6 +231,10 @@ def load_hip():
     _sig(lib, "sol_adaptive_counts", C.c_int, [P, C.POINTER(C.c_uint32), C.c_size_t])
     _sig(lib, "sol_tonemap_rgb8_adaptive", C.c_int, [P, C.c_void_p, C.POINTER(C.c_uint8)])
     _sig(lib, "sol_adaptive_rescale", C.c_int, [P, C.c_void_p])
+    _sig(lib, "sol_env_sampling", C.c_int, [P, C.POINTER(SolEnvSampling)])
+    _sig(lib, "sol_env_sampling_check", C.c_int, [C.c_void_p, C.POINTER(SolEnvSampling)])
+    _sig(lib, "sol_env_tables", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)])
+    _sig(lib, "sol_env_eval", C.c_int, [P, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p])
     _libs["hip"] = lib
     return lib
 
@@ -234,7 +246,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_debug_path", "sol_resolve_image", "sol_bloom", "sol_bloom_rgb8", "sol_gaussian_blur_weights", "sol_world_tree_check", "sol_world_tree_check_ex", "sol_render_aux", "sol_clear_aux", "sol_read_aux",
                "sol_scene_create_ex", "sol_scene_build_times", "sol_scene_set_option", "sol_scene_info", "sol_path_stats", "sol_comm_unique_id", "sol_comm_init",
                "sol_comm_destroy", "sol_gather", "sol_gather_local", "sol_comm_self_check", "sol_read_image", "sol_max_samples_per_call", "sol_background_blocks",
-               "sol_adaptive_begin", "sol_adaptive_round", "sol_adaptive_counts", "sol_tonemap_rgb8_adaptive", "sol_adaptive_rescale"]
+               "sol_adaptive_begin", "sol_adaptive_round", "sol_adaptive_counts", "sol_tonemap_rgb8_adaptive", "sol_adaptive_rescale",
+               "sol_env_sampling", "sol_env_sampling_check", "sol_env_tables", "sol_env_eval"]
 
 
 def load_host():
@@ -277,6 +290,7 @@ def load_host():
     _sig(lib, "solh_load_obj", I, [B, C.c_char_p, C.c_char_p, I, I, IMAGE_DECODER_FN, C.c_void_p])
     _sig(lib, "solh_set_post_processors", I, [B, I, C.POINTER(C.c_int), C.POINTER(C.c_double)])
     _sig(lib, "solh_set_adaptive", I, [B, C.c_uint32, C.c_uint32, D])
+    _sig(lib, "solh_set_env_sampling", I, [B, C.c_uint32])
     _sig(lib, "solh_abi_sizes", None, [C.POINTER(C.c_uint32)])
     _sig(lib, "solh_to_rgb_color", None, [_D3, C.c_uint32, C.POINTER(C.c_uint8)])
     _libs["host"] = lib
@@ -288,7 +302,7 @@ HOST_SYMBOLS = ["solh_builder_new", "solh_builder_free", "solh_last_error", "sol
                 "solh_diffuse_light", "solh_blend", "solh_sphere", "solh_quad", "solh_box", "solh_triangle",
                 "solh_triangles", "solh_spheres", "solh_constant_medium", "solh_bvh", "solh_bvh_range", "solh_finish",
                 "solh_tree_depth", "solh_environment", "solh_ray_trace", "solh_ray_trace_devices", "solh_abi_sizes", "solh_to_rgb_color", "solh_set_post_processors", "solh_load_obj",
-                "solh_set_adaptive"]
+                "solh_set_adaptive", "solh_set_env_sampling"]
 
 
 def d3(v):

@@ -257,6 +257,36 @@ class DeviceScene:
         """sol_adaptive_rescale: image <- sum * max_samples / n_b in place (the input of bloom)."""
         self._chk(self.lib.sol_adaptive_rescale(self.h, C.c_void_p(image_ptr)))
 
+    # ---- environment importance sampling (EXTENSION; DESIGN.md 12) ----
+    def env_sampling(self, mode):
+        """sol_env_sampling: mode None / 0 / "off" = off, "importance" / 1 = the environment map is one more light of the mixture."""
+        m = {None: 0, 0: 0, "off": 0, 1: 1, "importance": 1}.get(mode, mode)
+        if m not in (0, 1):
+            raise ValueError(f"env_sampling: unknown mode {mode!r}")
+        cfg = _abi.SolEnvSampling(size=C.sizeof(_abi.SolEnvSampling), mode=m)
+        self._chk(self.lib.sol_env_sampling(self.h, C.byref(cfg)))
+
+    def env_tables(self):
+        """sol_env_tables: (marginal CDF [H'], conditional CDFs [H', W'], total), float32, H' = max(H - 1, 1), W' = max(W - 1, 1)."""
+        d = self.scene.desc
+        cw, ch = max(int(d.env_width) - 1, 1), max(int(d.env_height) - 1, 1)
+        marg = np.zeros(ch, dtype=np.float32)
+        cond = np.zeros((ch, cw), dtype=np.float32)
+        total = C.c_float()
+        self._chk(self.lib.sol_env_tables(self.h, marg.ctypes.data, marg.size, cond.ctypes.data, cond.size, C.byref(total)))
+        return marg, cond, float(total.value)
+
+    def env_eval(self, fn, rows):
+        """sol_env_eval on the device: fn 0 ("sample"): rows (n, 2) of (r1, r2) -> (n, 6) direction xyz, pdf, cell i, cell j;
+        fn 1 ("pdf"): rows (n, 3) of directions -> (n, 3) pdf, cell i, cell j."""
+        fn = {"sample": 0, "pdf": 1}.get(fn, fn)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if fn not in (0, 1) or rows.ndim != 2 or rows.shape[1] != (2 if fn == 0 else 3):
+            raise ValueError("env_eval: fn 0 takes (n, 2) rows, fn 1 (n, 3)")
+        out = np.zeros((rows.shape[0], 6 if fn == 0 else 3), dtype=np.float32)
+        self._chk(self.lib.sol_env_eval(self.h, fn, rows.ctypes.data, rows.shape[0], out.ctypes.data))
+        return out
+
     def resolve_image(self):
         """Device pointer of the scene's own row-major image (W*H*3 floats) after un-permuting its accumulators."""
         p = C.c_void_p()

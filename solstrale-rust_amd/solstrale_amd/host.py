@@ -71,8 +71,11 @@ class RenderConfig:
     """src/renderer/mod.rs:26-52 (seed is the build's addition; OidnPostProcessor is not built)."""
 
     def __init__(self, width=300, height=200, samples_per_pixel=50, shader=(_abi.SHADER_PATH_TRACING, 50),
-                 seed=0x5017A1E, post_processors=None, adaptive=None):
-        """adaptive: EXTENSION, AdaptiveSampling(round, min_samples, threshold) or None."""
+                 seed=0x5017A1E, post_processors=None, adaptive=None, env_sampling=None):
+        """adaptive: EXTENSION, AdaptiveSampling(round, min_samples, threshold) or None.
+        env_sampling: EXTENSION, None or "importance": sample the environment map as one more light."""
+        if env_sampling not in ENV_SAMPLING_MODES:
+            raise ValueError(f"env_sampling: None or 'importance', not {env_sampling!r}")
         self.width = width
         self.height = height
         self.samples_per_pixel = samples_per_pixel
@@ -80,6 +83,10 @@ class RenderConfig:
         self.seed = seed
         self.post_processors = [NopPostProcessor()] if post_processors is None else list(post_processors)
         self.adaptive = adaptive
+        self.env_sampling = env_sampling
+
+
+ENV_SAMPLING_MODES = {None: _abi.SOL_ENV_SAMPLING_OFF, "importance": _abi.SOL_ENV_SAMPLING_IMPORTANCE}
 
 
 def AdaptiveSampling(round=64, min_samples=128, threshold=0.02):
@@ -151,6 +158,8 @@ class Scene:
             raise HostError(b.lib.solh_last_error().decode(errors="replace"))
         ad = getattr(rc, "adaptive", None) or (0, 0, 0.0)
         if b.lib.solh_set_adaptive(b.h, ad[0], ad[1], ad[2]) != 0:
+            raise HostError(b.lib.solh_last_error().decode(errors="replace"))
+        if b.lib.solh_set_env_sampling(b.h, ENV_SAMPLING_MODES[getattr(rc, "env_sampling", None)]) != 0:
             raise HostError(b.lib.solh_last_error().decode(errors="replace"))
         if devices is None:
             rc_ = b.lib.solh_ray_trace(b.h, rc.samples_per_pixel, rc.seed, strat, interval_seconds, device, cb, ab, None)
