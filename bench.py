@@ -15,7 +15,13 @@ key-value store (the parent's socket, or the launcher's TCPStore), not through a
   --scaling weak: per-GPU work fixed (512*N spp on the shared frame).
 `value` is the whole-job aggregate Msamples/s = W*H*spp_total / step time (max over ranks).
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line: the headline fields, `config`, and what
+setting up and the timed steps report on the way (`setup_s`, `world_tree`; N > 1: the per-rank figures and the partition). Whatever
+takes work of its own after the timed steps runs with --full only, and the --full line also carries
+  mrays_per_s, rays_per_sample, background_blocks, node_visits_per_ray, ... : from counter-enabled renders of the same frame;
+                  background_blocks.value_with_every_sample_traced: the job timed again with every sample traced;
+  gather_ms     : N > 1: one more sol_gather, timed on its own;
+  rehearsal_frame_check : --rehearse: rank 0's assembled frame against the frame one rank renders alone;
   roofline      : algorithmic bytes of the dominant kernel (sol_render_kernel) per launch / its HIP-event duration, against
                   the 8 TB/s HBM peak (DESIGN.md "Measurement"; bytes per sample come from a counter-enabled run). NOTE: these
                   bytes are served almost entirely by L1/L2/Infinity Cache - `frac` is the contract's algorithmic figure, not
@@ -116,11 +122,15 @@ def parse_args():
                          "blocks' cost in the creation probe (one-GPU estimate at 8 ranks: 7.78x instead of 7.74x). The table path has run "
                          "through sol_gather over the test transport only; it becomes the default once a real multi-GPU run has passed its "
                          "frame check (ADVICE r03)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything beside the headline: the counter-enabled render (Mrays/s, "
+                         "roofline), the job with every sample traced, the rocprofv3 --pmc passes, the CPU baseline, the extra gather (N > 1) "
+                         "and the rehearsal's frame check; a plain run does none of it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes (roofline.traffic = null, no roofline_valu)")
-    ap.add_argument("--no-all-traced", action="store_true", help="skip the extra steps that time the job with every sample traced (background_blocks."
-                    "value_with_every_sample_traced = null); the counter passes use it: they must see the timed launch and nothing else")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc passes (roofline.traffic = null, no roofline_valu)")
+    ap.add_argument("--no-all-traced", action="store_true", help="--full: skip the extra steps that time the job with every sample traced "
+                    "(background_blocks.value_with_every_sample_traced = null)")
     ap.add_argument("--pmc-spp", type=int, default=64)
     ap.add_argument("--no-build", action="store_true", help="do not run the build step (use under rocprofv3: no child processes)")
     ap.add_argument("--rehearse", action="store_true",
@@ -316,8 +326,9 @@ PMC_GROUPS = [  # FETCH_SIZE takes 3 of the 4 TCC slots, WRITE_SIZE 2: separate 
 
 
 def pmc_passes(args, spp):
-    """Runs this script under `rocprofv3 --pmc` (child processes; one pass per counter group, one timed launch of `spp` samples
-    per pixel each) and returns ({counter: sum over the product kernel's dispatches}, mean kernel ns) or (None, reason)."""
+    """Runs this script under `rocprofv3 --pmc` (child processes, plain runs: one pass per counter group, one timed launch of `spp`
+    samples per pixel each and nothing else) and returns ({counter: sum over the product kernel's dispatches}, mean kernel ns) or
+    (None, reason)."""
     rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(rocprof):
         return None, "rocprofv3 not found"
@@ -328,7 +339,7 @@ def pmc_passes(args, spp):
             d = os.path.join(out, grp[0])
             cmd = [rocprof, "--pmc"] + grp + ["--kernel-trace", "--output-format", "csv", "-d", d, "--", sys.executable,
                                               os.path.abspath(__file__), "--workload", args.workload, "--spp", str(spp), "--steps", "1",
-                                              "--warmup", "0", "--no-cpu-baseline", "--no-pmc", "--no-build", "--no-all-traced"]
+                                              "--warmup", "0", "--no-build"]
             if args.hdri:
                 cmd += ["--hdri"]
             if args.camera_preset != "default":
@@ -498,15 +509,15 @@ def worker(args):
     fence()
     dt = coord.max(time.perf_counter() - t0)
     dump_frame = None
-    if args.dump_outputs and rank == 0:  # (copied now: the steps below render into the same buffers)
+    if args.dump_outputs and rank == 0:  # (copied now: --full renders into the same buffers below)
         dump_frame = image.view(h, w, 3).cpu().numpy() if image is not None else ds.read_image()
     k_ms, grid = ds.last_kernel_ms()  # duration of the last step's (last) render kernel (HIP events on its stream)
-    # what a scaling curve needs to explain itself: every rank's kernel time, and the gather timed on its own (one more, untimed,
+    # what a scaling curve needs to explain itself: every rank's kernel time, and (--full) the gather timed on its own (one more, untimed,
     # gather of the accumulators the last step left: host clock around sol_gather + synchronise, maximum over the ranks)
     per_rank_kernel_ms = coord.all(round(k_ms, 3))
     per_rank_setup_s = coord.all((round(t_build, 3), round(t_upload, 3)))  # (every rank builds and creates its own copy of the scene)
     gather_ms = None
-    if world > 1:
+    if world > 1 and args.full:
         fence()
         tg = time.perf_counter()
         ds.gather(image_ptr)
@@ -518,7 +529,7 @@ def worker(args):
     # skipped samples on trust - a scaling curve can be drawn from either.
     value_all_traced = None
     all_traced_steps = max(1, args.steps)  # the same number of steps as `value` (round-4 advisor: both figures with the same step count)
-    if tree_info["background_blocks"] > 0 and not args.no_all_traced:  # (every rank of a job finds the same blocks: the scene and the proof are deterministic)
+    if args.full and tree_info["background_blocks"] > 0 and not args.no_all_traced:  # (every rank of a job finds the same blocks: the scene and the proof are deterministic)
         ds.set_option(_abi.OPT_BACKGROUND_BLOCKS, 0)
         step()
         fence()
@@ -529,39 +540,39 @@ def worker(args):
         value_all_traced = float(w) * h * spp / (coord.max(time.perf_counter() - ta) / all_traced_steps) / 1e6  # (N > 1: maximum over the ranks, like `value`)
         ds.set_option(_abi.OPT_BACKGROUND_BLOCKS, 1)
 
-    # ---- counters: exact per-sample algorithmic bytes and rays from a counter-enabled run of the same kernels ----
-    frame = ds.read_image() if (rank == 0 and args.rehearse) else None  # the gathered frame of the last step
+    # ---- counters (--full): exact per-sample algorithmic bytes and rays from a counter-enabled run of the same kernels ----
+    frame = ds.read_image() if (rank == 0 and args.rehearse and args.full) else None  # the gathered frame of the last step
     if torch is not None:
         ds.bind_accum(0, 0)
     ds.kernel_timing(False)
-    c_spp = min(16, spp)
-    ds.clear()
-    ds.render(0, c_spp, SEED, counted=True)
-    st = ds.stats()
-    sizes = record_sizes()
-    rays_per_sample = st["rays"] / st["samples"]  # of the whole algorithm: a counted render traces every sample
-    launch_samples = st["samples"] // c_spp * last_call_spp  # samples of the launch k_ms belongs to (this rank)
-    pst = ds.path_stats()
-    # Background blocks (SolSceneInfo::background_blocks: blocks proved at scene creation to see only the constant background are summed,
-    # not traced). What the timed launches touched is counted by a second counted render that skips them as a plain render does: the
-    # roofline's algorithmic bytes and the Mrays/s below are those of the rays actually traced, never of rays that were not.
-    st_traced = st
-    if tree_info["background_blocks"] > 0 and not os.environ.get("SOL_BACKGROUND_BLOCKS") == "0":
-        ds.set_option(_abi.OPT_BACKGROUND_BLOCKS, 2)
+    if args.full:
+        c_spp = min(16, spp)
         ds.clear()
         ds.render(0, c_spp, SEED, counted=True)
-        st_traced = ds.stats()
-        ds.set_option(_abi.OPT_BACKGROUND_BLOCKS, 1)
-    background_samples = st["samples"] - st_traced["samples"]
-    bytes_per_sample = (algorithmic_bytes(st_traced, sizes) + background_samples * 12.0 / 16.0 * 3.0) / st["samples"]
-    traced_rays_per_sample = st_traced["rays"] / st["samples"]
+        st = ds.stats()
+        sizes = record_sizes()
+        rays_per_sample = st["rays"] / st["samples"]  # of the whole algorithm: a counted render traces every sample
+        launch_samples = st["samples"] // c_spp * last_call_spp  # samples of the launch k_ms belongs to (this rank)
+        pst = ds.path_stats()
+        # Background blocks (SolSceneInfo::background_blocks: blocks proved at scene creation to see only the constant background are summed,
+        # not traced). What the timed launches touched is counted by a second counted render that skips them as a plain render does: the
+        # roofline's algorithmic bytes and the Mrays/s below are those of the rays actually traced, never of rays that were not.
+        st_traced = st
+        if tree_info["background_blocks"] > 0 and not os.environ.get("SOL_BACKGROUND_BLOCKS") == "0":
+            ds.set_option(_abi.OPT_BACKGROUND_BLOCKS, 2)
+            ds.clear()
+            ds.render(0, c_spp, SEED, counted=True)
+            st_traced = ds.stats()
+            ds.set_option(_abi.OPT_BACKGROUND_BLOCKS, 1)
+        background_samples = st["samples"] - st_traced["samples"]
+        bytes_per_sample = (algorithmic_bytes(st_traced, sizes) + background_samples * 12.0 / 16.0 * 3.0) / st["samples"]
+        traced_rays_per_sample = st_traced["rays"] / st["samples"]
 
     out = None
     if rank == 0:
         total_samples = float(w) * h * spp
         ms_per_step = dt / args.steps * 1e3
         value = total_samples / (dt / args.steps) / 1e6
-        achieved = bytes_per_sample * launch_samples / (k_ms * 1e-3) / 1e9
         out = {
             "metric": "Msamples/s", "value": round(value, 2), "unit": "Msamples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
@@ -572,38 +583,44 @@ def worker(args):
                        "sharding": f"8x8 tiles " + ("dealt out by probe cost" if (world > 1 and args.partition == "balanced") else "round-robin") + f" over {world} rank(s); every rank renders its tiles with all {spp} spp; "
                                    f"gather to rank 0 " + ("inside the C ABI (sol_gather: grouped ncclSend/ncclRecv)" + (" over the one-GPU test transport stub" if args.rehearse else "")
                                                            if world > 1 else "(single rank: un-permute only)")},
-            "mrays_per_s": round(value * traced_rays_per_sample, 2),
-            "rays_per_sample": round(rays_per_sample, 4),
-            "traced_rays_per_sample": round(traced_rays_per_sample, 4),
-            "background_blocks": {"blocks": tree_info["background_blocks"], "sample_fraction": round(background_samples / st["samples"], 4),
-                                  "value_with_every_sample_traced": None if value_all_traced is None else round(value_all_traced, 2),
-                                  "value_with_every_sample_traced_steps": all_traced_steps if value_all_traced is not None else None,
-                                  "note": "8x8 pixel blocks of which sol_scene_create proved that no camera ray of theirs, whatever the jitter, comes near a "
-                                          "primitive's box: every sample is the background colour, summed in the reference's order without being traced "
-                                          "(frames bit-identical with SOL_OPT_BACKGROUND_BLOCKS 0; SOL_BACKGROUND_BLOCKS=0 in the environment switches the proof off). "
-                                          "mrays_per_s, traced_rays_per_sample and the roofline's algorithmic bytes count only what was traced; rays_per_sample, the "
-                                          "histogram and primary_hit_fraction describe the whole algorithm (one camera ray per background sample)"},
-            "node_visits_per_ray": round(st_traced["node_visits"] / max(1, st_traced["rays"]), 3),
-            "primitive_tests_per_ray": round((st_traced["triangle_tests"] + st_traced["quad_tests"] + st_traced["sphere_tests"]) / max(1, st_traced["rays"]), 3),
-            "primary_hit_fraction": round(pst["primary_hit_fraction"], 4),
-            "rays_per_path_histogram": {k: round(v, 4) for k, v in pst["rays_per_path_histogram"].items()},
-            "rays_per_sample_note": "the open-roofed atrium ends most paths on the sky after ~3 rays; a closed interior costs several "
-                                    "times more rays per sample - Mrays/s is the figure that transfers between scenes",
-            # `bound`: the contract's figure is the ALGORITHMIC-bytes rate against the HBM peak and is named so - the kernel is not
-            # HBM-bound (its records are served by L1 / L2 / Infinity Cache); what limits it is `binding` (round-4 review: a reader of one field
-            # must not take "hbm" for the limit)
-            "roofline": {"bound": "algorithmic_hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": None, "traffic_source": None,
-                         "binding": "valu_issue", "binding_achieved": None, "binding_peak": None, "binding_unit": None, "binding_frac": None,
-                         "binding_note": "what actually limits the kernel: vector-instruction issue x lane utilisation (roofline_valu, mirrored here when the "
-                                         "PMC passes ran); the hbm figures above are the contract's algorithmic-bytes bound, not the limit",
-                         "frac_note": "ALGORITHMIC bytes (every node / primitive / texel record the search touches) per second; they are "
-                                      "served by L1/L2/Infinity Cache, so this is NOT HBM utilisation (it exceeds what an HBM copy reaches, 6.3 TB/s, "
-                                      "and may pass 1.0) - see traffic_frac for what reaches the memory side and binding / roofline_valu for the limit",
-                         "kernel": "sol_render_kernel", "kernel_ms": round(k_ms, 3), "grid_blocks": grid,
-                         "algorithmic_bytes_per_sample": round(bytes_per_sample, 1),
-                         "samples_per_launch": int(launch_samples),
-                         "counters_per_sample": {k: round(v / st["samples"], 4) for k, v in st_traced.items() if k not in ("samples", "max_stack")}},
+        }
+        if args.full:
+            achieved = bytes_per_sample * launch_samples / (k_ms * 1e-3) / 1e9
+            out.update({
+                "mrays_per_s": round(value * traced_rays_per_sample, 2),
+                "rays_per_sample": round(rays_per_sample, 4),
+                "traced_rays_per_sample": round(traced_rays_per_sample, 4),
+                "background_blocks": {"blocks": tree_info["background_blocks"], "sample_fraction": round(background_samples / st["samples"], 4),
+                                      "value_with_every_sample_traced": None if value_all_traced is None else round(value_all_traced, 2),
+                                      "value_with_every_sample_traced_steps": all_traced_steps if value_all_traced is not None else None,
+                                      "note": "8x8 pixel blocks of which sol_scene_create proved that no camera ray of theirs, whatever the jitter, comes near a "
+                                              "primitive's box: every sample is the background colour, summed in the reference's order without being traced "
+                                              "(frames bit-identical with SOL_OPT_BACKGROUND_BLOCKS 0; SOL_BACKGROUND_BLOCKS=0 in the environment switches the proof off). "
+                                              "mrays_per_s, traced_rays_per_sample and the roofline's algorithmic bytes count only what was traced; rays_per_sample, the "
+                                              "histogram and primary_hit_fraction describe the whole algorithm (one camera ray per background sample)"},
+                "node_visits_per_ray": round(st_traced["node_visits"] / max(1, st_traced["rays"]), 3),
+                "primitive_tests_per_ray": round((st_traced["triangle_tests"] + st_traced["quad_tests"] + st_traced["sphere_tests"]) / max(1, st_traced["rays"]), 3),
+                "primary_hit_fraction": round(pst["primary_hit_fraction"], 4),
+                "rays_per_path_histogram": {k: round(v, 4) for k, v in pst["rays_per_path_histogram"].items()},
+                "rays_per_sample_note": "the open-roofed atrium ends most paths on the sky after ~3 rays; a closed interior costs several "
+                                        "times more rays per sample - Mrays/s is the figure that transfers between scenes",
+                # `bound`: the contract's figure is the ALGORITHMIC-bytes rate against the HBM peak and is named so - the kernel is not
+                # HBM-bound (its records are served by L1 / L2 / Infinity Cache); what limits it is `binding` (round-4 review: a reader of one field
+                # must not take "hbm" for the limit)
+                "roofline": {"bound": "algorithmic_hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                             "frac": round(achieved / HBM_PEAK_GBPS, 5), "traffic": None, "traffic_source": None,
+                             "binding": "valu_issue", "binding_achieved": None, "binding_peak": None, "binding_unit": None, "binding_frac": None,
+                             "binding_note": "what actually limits the kernel: vector-instruction issue x lane utilisation (roofline_valu, mirrored here when the "
+                                             "PMC passes ran); the hbm figures above are the contract's algorithmic-bytes bound, not the limit",
+                             "frac_note": "ALGORITHMIC bytes (every node / primitive / texel record the search touches) per second; they are "
+                                          "served by L1/L2/Infinity Cache, so this is NOT HBM utilisation (it exceeds what an HBM copy reaches, 6.3 TB/s, "
+                                          "and may pass 1.0) - see traffic_frac for what reaches the memory side and binding / roofline_valu for the limit",
+                             "kernel": "sol_render_kernel", "kernel_ms": round(k_ms, 3), "grid_blocks": grid,
+                             "algorithmic_bytes_per_sample": round(bytes_per_sample, 1),
+                             "samples_per_launch": int(launch_samples),
+                             "counters_per_sample": {k: round(v / st["samples"], 4) for k, v in st_traced.items() if k not in ("samples", "max_stack")}},
+            })
+        out.update({
             "setup_s": {"scene_and_bvh_build_host": round(t_build, 2), "sol_scene_create": round(t_upload, 2),
                         "scene_source": ("OBJ + MTL file through the host loader (parse, material table, textures, reference BVH, flatten)" if args.obj else
                                          "procedural stand-in generated in Python, reference BVH built by the C++ host"),
@@ -615,19 +632,20 @@ def worker(args):
                            "strict_triangles": tree_info["strict_triangles"],
                            "note": "pre-splitting is kept only when it shrinks the summed box area of the primitives below 0.85 (regular meshes stay unsplit); "
                                    "strict_triangles: the scene has needle triangles (aspect >= 32:1) - fatter box pad and the triangle consistency rule of the fp32 contract"},
-        }
+        })
         if world > 1:
             out["rccl_ranks"] = rccl_ranks
             out["per_rank_kernel_ms"] = per_rank_kernel_ms
             out["per_rank_setup_s"] = {"scene_and_bvh_build_host": [a for a, _ in per_rank_setup_s], "sol_scene_create": [b for _, b in per_rank_setup_s],
                                        "note": "every rank loads / generates the scene and calls sol_scene_create itself (deterministic: same tree, same partition - checked); "
                                                "outside the timed region, as the metric defines (SURVEY.md 8d)"}
-            out["gather_ms"] = gather_ms
-            out["gather_note"] = "one extra sol_gather (grouped ncclSend / ncclRecv into rank 0 + un-permute) after the timed region, host clock incl. the barrier; the timed steps contain their own"
+            if args.full:
+                out["gather_ms"] = gather_ms
+                out["gather_note"] = "one extra sol_gather (grouped ncclSend / ncclRecv into rank 0 + un-permute) after the timed region, host clock incl. the barrier; the timed steps contain their own"
             out["partition"] = {"table": bool(part["partition_table"]), "crc": part["partition_crc"], "agreed_by_all_ranks": True}
         if args.rehearse:
             out["rehearsal"] = "all ranks on cuda:0, sol_gather over the test-only transport stub (tests/stub_rccl): not a measurement"
-    if args.rehearse and world > 1:
+    if args.rehearse and world > 1 and args.full:
         # the assembled frame must equal what one rank renders alone (the image is a pure function of scene and seed)
         coord.barrier()
         ds.comm_destroy()
@@ -639,7 +657,7 @@ def worker(args):
             out["rehearsal_frame_check"] = bool(np.array_equal(ds.read(), frame))
     ds.close()
     del ds
-    if rank == 0 and world == 1 and not args.no_pmc:
+    if rank == 0 and world == 1 and args.full and not args.no_pmc:
         p_spp = min(args.pmc_spp, spp)
         counters, info = pmc_passes(args, p_spp)
         rf = out["roofline"]
@@ -681,7 +699,7 @@ def worker(args):
                 "wave_cycles_waiting_frac": round(g("SQ_WAIT_ANY", 0.0) / max(1.0, g("SQ_WAVE_CYCLES", 0.0)), 4),
                 "clock_ghz": round(clock / 1e9, 3), "kernel_ms_under_pmc": round(info * 1e-6, 3), "pmc_spp": p_spp}
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             import orc  # TEST INFRASTRUCTURE, used here only as the timed CPU baseline
             t0 = time.time()
             cores = host_cores()

@@ -1,8 +1,9 @@
-"""bench.py end to end on the GPU box: the default single-GPU contract line; two- and three-rank rehearsals of the N>1 path started
-by bench.py itself (no launcher; all ranks on cuda:0, going through sol_comm_init / sol_gather over the test-only transport stub
-tests/stub_rccl - RCCL refuses two ranks on one device) whose assembled frame must equal the single-rank frame bit for bit; and the
-real RCCL communicator behind the C ABI exercised with the one rank a one-GPU box can hold. (The ranks' rendezvous under
-torch.distributed.run - the launcher's TCPStore - is covered on the CPU: tests/test_distributed_cpu.py.)"""
+"""bench.py end to end on the GPU box: the single-GPU contract line of a --full run and the headline-only line of a plain one; two-
+and three-rank rehearsals of the N>1 path started by bench.py itself (no launcher; all ranks on cuda:0, going through sol_comm_init /
+sol_gather over the test-only transport stub tests/stub_rccl - RCCL refuses two ranks on one device) whose assembled frame must equal
+the single-rank frame bit for bit; and the real RCCL communicator behind the C ABI exercised with the one rank a one-GPU box can
+hold. (The ranks' rendezvous under torch.distributed.run - the launcher's TCPStore - is covered on the CPU:
+tests/test_distributed_cpu.py.)"""
 import json
 import os
 import subprocess
@@ -13,8 +14,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-            "dtype", "data", "config", "roofline"}
+HEADLINE = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+            "dtype", "data", "config"}
+REQUIRED = HEADLINE | {"roofline"}
+FULL_ONLY = {"mrays_per_s", "rays_per_sample", "background_blocks", "roofline", "roofline_valu", "cpu_baseline", "gather_ms",
+             "rehearsal_frame_check"}
 
 
 def _line(out):
@@ -24,7 +28,7 @@ def _line(out):
 
 
 def test_single_gpu_line_has_the_contract_fields():
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--spp", "32", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1",
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--spp", "32", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "1",
                         "--pmc-spp", "32"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -43,13 +47,16 @@ def test_single_gpu_line_has_the_contract_fields():
 
 
 def test_dump_outputs_is_the_last_timed_frame(tmp_path):
-    """--dump-outputs DIR: the frame of the last timed step, as rank 0 received it, equals a plain render of the same scene and seed."""
+    """--dump-outputs DIR: the frame of the last timed step, as rank 0 received it, equals a plain render of the same scene and seed.
+    The run is a plain one (no --full): its line carries the headline fields and none of what --full measures."""
     import bench
     from solstrale_amd import DeviceScene, RenderConfig, scenes
-    r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--spp", "16", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-pmc", "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--workload", "c1", "--spp", "16", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
-    assert _line(r.stdout)["steps"] == 2 and sorted(os.listdir(tmp_path)) == ["image.npy"]
+    d = _line(r.stdout)
+    assert d["steps"] == 2 and sorted(os.listdir(tmp_path)) == ["image.npy"]
+    assert HEADLINE <= set(d) and not FULL_ONLY & set(d) and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
     img = np.load(tmp_path / "image.npy")
     with DeviceScene(scenes.cornell_box(RenderConfig(400, 400, 16))) as ds:
         ds.render(0, 16, bench.SEED)
@@ -62,7 +69,7 @@ def test_rehearsal_without_a_launcher_goes_through_sol_gather(ranks, scaling, sp
     """`python bench.py --gpus N --rehearse` starts its own ranks; the data path is the real one (sol_comm_init, sol_render, sol_gather
     with world > 1) over the stub transport; the frame rank 0 assembles equals the single-rank frame."""
     cmd = [sys.executable, "bench.py", "--gpus", str(ranks), "--workload", "c1", "--spp", "16", "--steps", "1", "--warmup", "1", "--rehearse",
-           "--scaling", scaling, "--no-cpu-baseline"]
+           "--scaling", scaling, "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -74,7 +81,8 @@ def test_rehearsal_without_a_launcher_goes_through_sol_gather(ranks, scaling, sp
 def test_both_figures_in_a_multi_rank_line():
     """A scene with background blocks (the C3 atrium's sky) through two ranks: the N > 1 line carries the figure with every sample traced
     as well, from as many steps as `value` (round-4 review: a scaling curve must not quote only the flattering figure)."""
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--workload", "c3", "--spp", "16", "--steps", "2", "--warmup", "1", "--rehearse", "--no-cpu-baseline"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--workload", "c3", "--spp", "16", "--steps", "2", "--warmup", "1", "--rehearse", "--full",
+           "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -85,13 +93,25 @@ def test_both_figures_in_a_multi_rank_line():
     assert d["rehearsal_frame_check"] is True
 
 
+def test_plain_multi_rank_line():
+    """Without --full the ranks go through the same setup, steps and gather and nothing after them: the line carries the headline and
+    the per-rank figures the steps gave, no extra gather and no frame check."""
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--workload", "c1", "--spp", "16", "--steps", "2", "--warmup", "1", "--rehearse"]
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _line(r.stdout)
+    assert HEADLINE <= set(d) and not FULL_ONLY & set(d) and d["n_gpus"] == 2 and d["value"] > 0 and d["rccl_ranks"] == 2
+    assert len(d["per_rank_kernel_ms"]) == 2 and d["partition"]["agreed_by_all_ranks"] is True
+
+
 def test_a_supplied_obj_replaces_the_stand_in():
     """`--obj PATH`: a user-supplied OBJ (+MTL, textures) goes through the host OBJ+MTL loader (src/loader/obj.rs:38-136 restated in
     host/solstrale_obj.cpp) and is rendered in place of the procedural stand-in; the line says which file it was (SURVEY.md 8d:
     "if a real sponza.obj is supplied at run time, use it and say so")."""
     obj = os.path.join(ROOT, "tests", "golden", "resources", "spider", "spider.obj")
     r = subprocess.run([sys.executable, "bench.py", "--obj", obj, "--workload", "c1", "--spp", "16", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-pmc"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--no-pmc"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     assert "spider.obj" in d["config"]["workload"] and d["data"] == "user-supplied OBJ" and d["value"] > 0

@@ -10,7 +10,7 @@ out=$PWD/gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
 if [ "$mode" = "stats" ]; then
-  python3 bench.py --steps 3 --warmup 1 > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
+  python3 bench.py --steps 3 --warmup 1 --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
   tail -c 600 $out/${tag}_bench.json
   (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof -- python3 $OLDPWD/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc --no-build --no-all-traced \
       > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err) || exit 1

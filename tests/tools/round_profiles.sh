@@ -11,8 +11,8 @@ if [[ $part == *a* ]]; then
   bash tests/tools/profile_round.sh $tag pmc > gpurun_out/${tag}_pmc.log 2>&1; tail -2 gpurun_out/${tag}_pmc.log
 fi
 if [[ $part == *b* ]]; then
-  run() {  # name, bench arguments
-    name=$1; shift
+  run() {  # name, bench arguments (always --full: the summary below reads the roofline and the ray counts)
+    name=$1; shift; set -- --full "$@"
     timeout -k 10 500 python bench.py "$@" --cpu-seconds 5 --no-build > gpurun_out/${tag}_${name}_bench.json 2> gpurun_out/${tag}_${name}_bench.err; echo "$name rc $?"
   }
   run c1 --workload c1
