@@ -505,6 +505,44 @@ int sol_env_tables(SolScene* scene, float* marginal, size_t n_marginal, float* c
  * 2 floats in, 6 out per row; fn 1: direction xyz -> (pdf, cell i, cell j), 3 in, 3 out. Needs the tables. */
 int sol_env_eval(SolScene* scene, uint32_t fn, const float* in, uint32_t n, float* out);
 
+/* ---- denoiser (EXTENSION, opt-in) --------------------------------------------------------------------------------------
+ * An edge-aware a-trous filter of a colour image guided by the first-hit albedo and normal planes (sol_render_aux): the stand-in for the
+ * reference's OidnPostProcessor (src/post/oidn.rs), which stays the Nop post-processor. Colour sums S over n samples, albedo and normal sums
+ * A, N over m samples, all W*H*3 floats, row-major, row 0 = top, on the scene's device:
+ *   c = S / n (a value that is not finite counts as 0), a = A / m, v = N / m; per channel f = a > 0.01 ? a : 1 and e = c / f;
+ *   guide normal g = v / |v| when |v| > 1e-3, else the pixel is a miss;
+ *   pass i = 0 .. iterations-1: taps q = p + 2^i (dx, dy), dx, dy in -2..2, B3 weights h = (1/16, 1/4, 3/8, 1/4, 1/16), taps outside the
+ *   image skipped; e'_p = sum h[dx] h[dy] w_pq e_q / sum h[dx] h[dy] w_pq (dy inner, dx outer), w_pq = w_c w_n with
+ *   w_c = exp(-sum_ch (t(e_p) - t(e_q))^2 / (sigma_color^2 4^-i)), t(x) = max(x, 0) / (1 + max(x, 0)), and w_n = 1 if both are misses,
+ *   0 if one is, max(0, g_p . g_q)^normal_power otherwise; the centre tap counts with w = 1;
+ *   out = e_K * f, written as sums (out * n): sol_tonemap_rgb8 with n tones it as it tones a raw frame.
+ * Deterministic (no atomics, fixed tap order). SOL_EINVAL: see sol_denoise_check. */
+#define SOL_DENOISE_DEFAULT_ITERATIONS 5u
+#define SOL_DENOISE_DEFAULT_SIGMA_COLOR 0.25f
+#define SOL_DENOISE_DEFAULT_NORMAL_POWER 64.0f
+typedef struct SolDenoise {
+  uint32_t size;           /* in: sizeof(SolDenoise): lets the struct grow                                                  */
+  uint32_t iterations;     /* passes, 1..8                                                                                  */
+  float sigma_color;       /* finite, > 0                                                                                   */
+  float normal_power;      /* finite, >= 0                                                                                  */
+  uint32_t reserved[2];    /* 0                                                                                             */
+} SolDenoise;
+/* Host only (no device needed): SOL_EINVAL with a message for a wrong size, iterations outside 1..8, a sigma_color that is not finite or
+ * not above 0, a normal_power that is not finite or below 0, a non-zero reserved field. NULL = the defaults above. */
+int sol_denoise_check(const SolDenoise* config);
+/* Un-permutes the scene's auxiliary planes into two row-major buffers the scene owns (W*H*3 floats each, valid until the next call;
+ * not the sol_resolve_image buffer) and returns their device pointers (either may be NULL) and the aux samples added since the last
+ * clear (sol_render_aux adds, sol_clear_aux and a partition change that clears the planes reset it). SOL_EINVAL before any
+ * sol_render_aux and when world > 1 (the planes are rank-local). Asynchronous on the scene's stream. */
+int sol_resolve_aux(SolScene* scene, void** albedo_dev, void** normal_dev, uint32_t* aux_samples);
+/* The filter, in place on image_dev, asynchronous on the scene's stream. Scratch is allocated on the scene on first use and kept. */
+int sol_denoise(SolScene* scene, void* image_dev, uint32_t num_samples, const void* albedo_dev, const void* normal_dev, uint32_t aux_samples,
+                const SolDenoise* config);
+/* The same into a scratch image (image_dev is left alone), then the Nop tone map with num_samples into rgb8_host (W*H*3 bytes): the bytes
+ * of sol_denoise followed by sol_tonemap_rgb8. Blocks. */
+int sol_denoise_rgb8(SolScene* scene, const void* image_dev, uint32_t num_samples, const void* albedo_dev, const void* normal_dev,
+                     uint32_t aux_samples, const SolDenoise* config, uint8_t* rgb8_host);
+
 int sol_stats(const SolScene* scene, SolStats* out);
 /* What the paths of the last instrumented render (sol_render_counted, one-path-per-lane kernel) looked like - how hard a workload
  * is: the share of camera rays that hit something and the samples by the number of rays of their path (a path of n rays was

@@ -87,9 +87,11 @@ int solh_load_obj(SolhBuilder* b, const char* path, const char* filename, int tr
                   solh_image_decoder decoder, void* user);
 
 /* RenderConfig::post_processors (src/renderer/mod.rs:35) for the following solh_ray_trace calls: kinds[i] 0 = NopPostProcessor,
- * 1 = BloomPostProcessor with params[3i..3i+2] = kernel_size_fraction, threshold, max_intensity (NaN = None); n = 0: no image
+ * 1 = BloomPostProcessor with params[3i..3i+2] = kernel_size_fraction, threshold, max_intensity (NaN = None), 2 = DenoisePostProcessor
+ * (EXTENSION) with params[3i..3i+2] = iterations, sigma_color, normal_power (NaN = the default; the last entry only:
+ * "DenoisePostProcessor can not be used as an intermediate post processor"; one device, no adaptive sampling); n = 0: no image
  * is produced. The default is one NopPostProcessor. Errors carry the reference's strings
- * ("kernel_size_fraction must be between 0 and 0.5"). */
+ * ("kernel_size_fraction must be between 0 and 0.5") or sol_denoise_check's. */
 int solh_set_post_processors(SolhBuilder* b, int n, const int* kinds, const double* params);
 
 /* EXTENSION, not in the reference: adaptive sampling (solstrale_hip.h SolAdaptive) for the following

@@ -192,6 +192,7 @@ int sol_set_partition(SolScene* s, int rank, int world) {
     HIP_TRY(hipMemsetAsync(s->acc_own, 0, s->acc_floats * sizeof(float), s->stream));
     for (int k = 0; k < 2; ++k)
       if (s->aux[k] && s->aux_floats == s->acc_floats) HIP_TRY(hipMemsetAsync(s->aux[k], 0, s->aux_floats * sizeof(float), s->stream));
+    s->aux_samples = 0;
   }
   if (floats != s->acc_floats || !s->acc_own) {
     if (s->acc_own) { hipFree(s->acc_own); s->acc_own = nullptr; }
@@ -226,7 +227,8 @@ void sol_scene_destroy(SolScene* s) {
   sol_comm_destroy(s);
   void* ptrs[] = {s->leaf_refs, s->nodes, s->wides, s->tris, s->tri_shade, s->quads, s->spheres, s->mediums, s->mats, s->texs, s->texels, s->env, s->lights, s->light_tri,
                   s->acc_own, s->partial, s->image, s->rgb8, s->work, s->spill, s->counters, s->pool, s->queue, s->wf_ctr,
-                  s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block, s->env_tables};
+                  s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block, s->env_tables,
+                  s->aux_img[0], s->aux_img[1], s->den_buf};
   s->adaptive.release();
   if (s->wf_ctr_host) hipHostFree(s->wf_ctr_host);
   for (void* p : ptrs)

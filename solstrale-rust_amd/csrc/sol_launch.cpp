@@ -297,6 +297,7 @@ int sol_render_aux(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
       HIP_TRY(hipMemsetAsync(s->aux[k], 0, std::max<size_t>(s->acc_floats * sizeof(float), 64), s->stream));
     }
     s->aux_floats = s->acc_floats;
+    s->aux_samples = 0;
   }
   float* const acc = s->acc;
   const uint32_t shader = s->S.shader;
@@ -314,6 +315,7 @@ int sol_render_aux(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
   s->S.shader = shader;
   s->S.bgx = bg[0]; s->S.bgy = bg[1]; s->S.bgz = bg[2];
   s->S.env = env;
+  if (rc == SOL_OK) s->aux_samples += n;
   return rc;
 }
 
@@ -322,6 +324,7 @@ int sol_clear_aux(SolScene* s) {
   HIP_TRY(hipSetDevice(s->device));
   for (int k = 0; k < 2; ++k)
     if (s->aux[k] && s->aux_floats == s->acc_floats) HIP_TRY(hipMemsetAsync(s->aux[k], 0, s->aux_floats * sizeof(float), s->stream));
+  s->aux_samples = 0;
   return SOL_OK;
 }
 

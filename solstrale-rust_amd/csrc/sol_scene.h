@@ -128,6 +128,9 @@ struct SolScene {
   uint8_t* texels = nullptr; uint32_t* lights = nullptr; float* env = nullptr; DTri* light_tri = nullptr;
   float* acc_own = nullptr; float* acc = nullptr; size_t acc_floats = 0;
   float* aux[2] = {nullptr, nullptr}; size_t aux_floats = 0;
+  uint32_t aux_samples = 0;                 // samples sol_render_aux added since the planes were last cleared (sol_resolve_aux)
+  float* aux_img[2] = {nullptr, nullptr};   // row-major albedo / normal planes of sol_resolve_aux (W*H*3 floats each)
+  float4* den_buf = nullptr; size_t den_pixels = 0;  // sol_denoise scratch (sol_denoise.hip): 4 float4 per pixel
   std::vector<uint32_t> block_cost;  // per 8x8 block (global index): rays of its longest item in the cost probe; empty: no ordering
   std::vector<uint32_t> block_work;  // per 8x8 block (global index): its rays in the cost probe (balanced partition)
   bool balanced = false;             // SOL_OPT_BALANCED_PARTITION

@@ -243,8 +243,9 @@ struct RenderImageStrategy {
 // src/post/mod.rs:45-55. Post-processors run on the device (sol_tonemap_rgb8, sol_bloom*); OidnPostProcessor is not built
 // (a third-party denoiser binary, out of scope).
 struct PostProcessors {
-  enum Kind { Nop, Bloom } kind = Nop;
+  enum Kind { Nop, Bloom, Denoise } kind = Nop;
   double kernel_size_fraction = 0, threshold = 0, max_intensity = 0;  // Bloom
+  uint32_t iterations = 0; float sigma_color = 0.f, normal_power = 0.f;  // Denoise
 };
 struct NopPostProcessor { static PostProcessors create() { return {}; } };  // src/post/nop.rs:11-17
 // src/post/oidn.rs:85-128: without the crate's optional `oidn-postprocessor` feature (its default build) the OIDN
@@ -254,6 +255,15 @@ struct BloomPostProcessor {
   // src/post/bloom.rs:27-47: throws std::invalid_argument("kernel_size_fraction must be between 0 and 0.5");
   // a NaN threshold / max_intensity means None (defaults |(1,1,1)| and f64::MAX)
   static PostProcessors create(double kernel_size_fraction, double threshold = std::nan(""), double max_intensity = std::nan(""));
+};
+
+// EXTENSION (not in the reference): the albedo / normal guided a-trous denoiser of the device (include/solstrale_hip.h SolDenoise,
+// DESIGN.md 13). NaN = the default (5 iterations, sigma_color 0.25, normal_power 64); throws std::invalid_argument with
+// sol_denoise_check's message. Only as the LAST post-processor (like OidnPostProcessor, oidn.rs:75-77): ray_trace then renders the
+// albedo / normal planes beside the colour. One device, no adaptive sampling.
+struct DenoisePostProcessor {
+  static PostProcessors create(double iterations = std::nan(""), double sigma_color = std::nan(""), double normal_power = std::nan(""));
+  static SolDenoise config(const PostProcessors& p);
 };
 
 struct RenderConfig {

@@ -548,6 +548,25 @@ PostProcessors BloomPostProcessor::create(double kernel_size_fraction, double th
   return p;
 }
 
+PostProcessors DenoisePostProcessor::create(double iterations, double sigma_color, double normal_power) {
+  PostProcessors p;
+  p.kind = PostProcessors::Denoise;
+  if (!std::isnan(iterations) && !(iterations >= 1. && iterations <= 8. && iterations == std::floor(iterations)))
+    throw std::invalid_argument("DenoisePostProcessor: iterations must be an integer in 1..8");
+  p.iterations = std::isnan(iterations) ? SOL_DENOISE_DEFAULT_ITERATIONS : (uint32_t)iterations;
+  p.sigma_color = std::isnan(sigma_color) ? SOL_DENOISE_DEFAULT_SIGMA_COLOR : (float)sigma_color;
+  p.normal_power = std::isnan(normal_power) ? SOL_DENOISE_DEFAULT_NORMAL_POWER : (float)normal_power;
+  const SolDenoise c = config(p);
+  if (sol_denoise_check(&c) != SOL_OK) throw std::invalid_argument(std::string("DenoisePostProcessor: ") + sol_last_error());
+  return p;
+}
+
+SolDenoise DenoisePostProcessor::config(const PostProcessors& p) {
+  SolDenoise c{};
+  c.size = sizeof c; c.iterations = p.iterations; c.sigma_color = p.sigma_color; c.normal_power = p.normal_power;
+  return c;
+}
+
 // ---- ray_trace (src/lib.rs:93-99, src/renderer/mod.rs:140-162,209-358) ---------------------------------------
 std::string ray_trace(const Scene& scene, const std::function<void(RenderProgress&&)>& output,
                       const std::function<bool()>& abort, int device) {
@@ -563,6 +582,13 @@ std::string ray_trace(const Scene& scene, const std::function<void(RenderProgres
   // Renderer::new
   if (get_lights(scene.world).empty()) return "Scene should have at least one light";
   if (devices.empty()) return "ray_trace: no device named";
+  // EXTENSION: the denoiser is the last post-processor or none; it renders the albedo / normal planes on one device
+  const std::vector<PostProcessors>& chain = scene.render_config.post_processors;
+  for (size_t k = 0; k + 1 < chain.size(); ++k)
+    if (chain[k].kind == PostProcessors::Denoise) return "DenoisePostProcessor can not be used as an intermediate post processor";
+  const bool denoise = !chain.empty() && chain.back().kind == PostProcessors::Denoise;
+  if (denoise && devices.size() > 1) return "ray_trace: the denoiser renders on one device";
+  if (denoise && scene.render_config.adaptive.round) return "ray_trace: adaptive sampling and the denoiser cannot be combined";
   std::unique_ptr<FlatScene> fs;
   try {
     fs = flatten(scene);
@@ -684,6 +710,7 @@ std::string ray_trace(const Scene& scene, const std::function<void(RenderProgres
     const double t_batch = secs(clk::now());
     for (SolScene* d : devs)  // (asynchronous: the devices render their blocks of this batch side by side)
       if (sol_render(d, done, n, rc.seed) != SOL_OK) return sol_last_error();
+    if (denoise && sol_render_aux(dev, done, n, rc.seed) != SOL_OK) return sol_last_error();  // the guide planes of the same samples
     for (SolScene* d : devs)
       if (sol_sync(d) != SOL_OK) return sol_last_error();
     if (secs(clk::now()) - t_batch < grow_below && batch < batch_cap) batch *= 2u;
@@ -707,9 +734,18 @@ std::string ray_trace(const Scene& scene, const std::function<void(RenderProgres
           }
           const PostProcessors& last = rc.post_processors.back();
           p.render_image.resize(npix * 3);
-          int rcode = last.kind == PostProcessors::Bloom
-                          ? sol_bloom_rgb8(dev, img, s, last.kernel_size_fraction, last.threshold, last.max_intensity, p.render_image.data())
-                          : sol_tonemap_rgb8(dev, img, s, p.render_image.data());
+          int rcode;
+          if (denoise) {
+            void *albedo = nullptr, *normal = nullptr;
+            uint32_t m = 0;
+            const SolDenoise cfg = DenoisePostProcessor::config(last);
+            rcode = sol_resolve_aux(dev, &albedo, &normal, &m);
+            if (rcode == SOL_OK) rcode = sol_denoise_rgb8(dev, img, s, albedo, normal, m, &cfg, p.render_image.data());
+          } else {
+            rcode = last.kind == PostProcessors::Bloom
+                        ? sol_bloom_rgb8(dev, img, s, last.kernel_size_fraction, last.threshold, last.max_intensity, p.render_image.data())
+                        : sol_tonemap_rgb8(dev, img, s, p.render_image.data());
+          }
           if (rcode != SOL_OK) return sol_last_error();
           p.has_image = true;
           p.width = (uint32_t)rc.width;

@@ -297,8 +297,11 @@ int solh_set_post_processors(SolhBuilder* b, int n, const int* kinds, const doub
     for (int i = 0; i < n; ++i) {
       if (kinds[i] == 0) pp.push_back(NopPostProcessor::create());
       else if (kinds[i] == 1) pp.push_back(BloomPostProcessor::create(params[3 * i], params[3 * i + 1], params[3 * i + 2]));
+      else if (kinds[i] == 2) pp.push_back(DenoisePostProcessor::create(params[3 * i], params[3 * i + 1], params[3 * i + 2]));
       else throw std::runtime_error("solh_set_post_processors: unknown post-processor kind");
     }
+    for (size_t k = 0; k + 1 < pp.size(); ++k)  // (oidn.rs:75-77: the denoiser produces the image, it cannot feed another processor)
+      if (pp[k].kind == PostProcessors::Denoise) throw std::runtime_error("DenoisePostProcessor can not be used as an intermediate post processor");
     b->scene.render_config.post_processors = std::move(pp);
     return 0;
   });

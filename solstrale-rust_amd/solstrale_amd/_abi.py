@@ -163,6 +163,22 @@ class SolEnvSampling(C.Structure):
     _fields_ = [("size", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+DENOISE_DEFAULT_ITERATIONS, DENOISE_DEFAULT_SIGMA_COLOR, DENOISE_DEFAULT_NORMAL_POWER = 5, 0.25, 64.0
+
+
+class SolDenoise(C.Structure):
+    """EXTENSION: the albedo / normal guided a-trous denoiser (sol_denoise). Not in ABI_STRUCTS (solh_abi_sizes has 11 sizes)."""
+    _fields_ = [("size", C.c_uint32), ("iterations", C.c_uint32), ("sigma_color", C.c_float), ("normal_power", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+def denoise_config(iterations=None, sigma_color=None, normal_power=None):
+    """A SolDenoise with the defaults where an argument is None."""
+    return SolDenoise(size=C.sizeof(SolDenoise), iterations=DENOISE_DEFAULT_ITERATIONS if iterations is None else int(iterations),
+                      sigma_color=DENOISE_DEFAULT_SIGMA_COLOR if sigma_color is None else float(sigma_color),
+                      normal_power=DENOISE_DEFAULT_NORMAL_POWER if normal_power is None else float(normal_power))
+
+
 class SolTreeCheck(C.Structure):
     _fields_ = [("n_wide", C.c_uint32), ("n_leaf_refs", C.c_uint32), ("n_primitives", C.c_uint32), ("depth", C.c_uint32),
                 ("max_children", C.c_uint32), ("box_violations", C.c_uint32), ("leaf_mismatches", C.c_uint32),
@@ -235,6 +251,11 @@ def load_hip():
     _sig(lib, "sol_env_sampling_check", C.c_int, [C.c_void_p, C.POINTER(SolEnvSampling)])
     _sig(lib, "sol_env_tables", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)])
     _sig(lib, "sol_env_eval", C.c_int, [P, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p])
+    _sig(lib, "sol_denoise_check", C.c_int, [C.POINTER(SolDenoise)])
+    _sig(lib, "sol_resolve_aux", C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)])
+    _sig(lib, "sol_denoise", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SolDenoise)])
+    _sig(lib, "sol_denoise_rgb8", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SolDenoise),
+                                            C.POINTER(C.c_uint8)])
     _libs["hip"] = lib
     return lib
 
@@ -247,7 +268,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_scene_create_ex", "sol_scene_build_times", "sol_scene_set_option", "sol_scene_info", "sol_path_stats", "sol_comm_unique_id", "sol_comm_init",
                "sol_comm_destroy", "sol_gather", "sol_gather_local", "sol_comm_self_check", "sol_read_image", "sol_max_samples_per_call", "sol_background_blocks",
                "sol_adaptive_begin", "sol_adaptive_round", "sol_adaptive_counts", "sol_tonemap_rgb8_adaptive", "sol_adaptive_rescale",
-               "sol_env_sampling", "sol_env_sampling_check", "sol_env_tables", "sol_env_eval"]
+               "sol_env_sampling", "sol_env_sampling_check", "sol_env_tables", "sol_env_eval",
+               "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8"]
 
 
 def load_host():

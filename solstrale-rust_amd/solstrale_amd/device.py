@@ -293,6 +293,28 @@ class DeviceScene:
         self._chk(self.lib.sol_resolve_image(self.h, C.byref(p)))
         return p.value
 
+    # ---- denoiser (EXTENSION) ----
+    def resolve_aux(self):
+        """sol_resolve_aux: (albedo device pointer, normal device pointer, aux samples) - the row-major planes (W*H*3 floats each) the
+        scene owns, and the samples sol_render_aux added since they were last cleared."""
+        a, n, m = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        self._chk(self.lib.sol_resolve_aux(self.h, C.byref(a), C.byref(n), C.byref(m)))
+        return a.value, n.value, int(m.value)
+
+    def denoise(self, image_ptr, num_samples, albedo_ptr, normal_ptr, aux_samples, iterations=None, sigma_color=None, normal_power=None):
+        """sol_denoise: the guided a-trous filter on the device image (W*H*3 float sums of num_samples), in place, asynchronous."""
+        cfg = _abi.denoise_config(iterations, sigma_color, normal_power)
+        self._chk(self.lib.sol_denoise(self.h, C.c_void_p(image_ptr), num_samples, C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
+                                       aux_samples, C.byref(cfg)))
+
+    def denoise_rgb8(self, image_ptr, num_samples, albedo_ptr, normal_ptr, aux_samples, iterations=None, sigma_color=None, normal_power=None):
+        """sol_denoise_rgb8: the filter into scratch, then the Nop tone map -> RGB8 (H, W, 3); the image is left alone."""
+        cfg = _abi.denoise_config(iterations, sigma_color, normal_power)
+        out = np.empty((self.height, self.width, 3), dtype=np.uint8)
+        self._chk(self.lib.sol_denoise_rgb8(self.h, C.c_void_p(image_ptr), num_samples, C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
+                                            aux_samples, C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
     BLOOM_DEFAULT_THRESHOLD = 3.0 ** 0.5  # Vec3::new(1., 1., 1.).length() (bloom.rs:39)
     BLOOM_DEFAULT_MAX = 1.7976931348623157e308  # f64::MAX (bloom.rs:40)
 

@@ -67,6 +67,14 @@ def BloomPostProcessor(kernel_size_fraction, threshold=None, max_intensity=None)
                 nan if max_intensity is None else float(max_intensity)))
 
 
+def DenoisePostProcessor(iterations=None, sigma_color=None, normal_power=None):
+    """EXTENSION (not in the reference): the albedo / normal guided a-trous denoiser of the device; None = the default
+    (5, 0.25, 64). The last post-processor only; ray_trace then renders the albedo / normal planes beside the colour (one device, no
+    adaptive sampling). The parameters are checked where the chain is installed."""
+    nan = float("nan")
+    return (2, tuple(nan if v is None else float(v) for v in (iterations, sigma_color, normal_power)))
+
+
 class RenderConfig:
     """src/renderer/mod.rs:26-52 (seed is the build's addition; OidnPostProcessor is not built)."""
 
