@@ -505,6 +505,50 @@ int sol_env_tables(SolScene* scene, float* marginal, size_t n_marginal, float* c
  * 2 floats in, 6 out per row; fn 1: direction xyz -> (pdf, cell i, cell j), 3 in, 3 out. Needs the tables. */
 int sol_env_eval(SolScene* scene, uint32_t fn, const float* in, uint32_t n, float* out);
 
+/* ---- light tree and power-weighted light sampling (EXTENSION, not in the reference; opt-in) -------------------------------
+ * The light half of a Lambertian or Isotropic scatter evaluates the density of the light mixture, by default with one test per light.
+ *   mode 0 UNIFORM (default): as the reference - a uniform choice of light, the density a loop over every light. Frames as they were.
+ *   mode 1 TREE: the same choice and the same sum, found through a light tree: an implicit complete 4-ary tree over the light list in
+ *          list order, built on the device on first use (one launch for the leaves, one per level; bit-identical on every device), about
+ *          (4/3) 4^ceil(log4 L) x 24 bytes, freed by sol_scene_destroy. Every box is conservative for the record the light's test reads, so a
+ *          light the walk skips would have added exactly +0.0f and the others are added in the loop's order: frames are BIT-IDENTICAL to mode 0.
+ *          The tree is tight when the list is spatially coherent (the host library lists lights in the world tree's depth-first order); a
+ *          list in arbitrary order renders the same frames, more slowly.
+ *   mode 2 POWER: a light is chosen with probability q_i proportional to its power w_i = area_i x luminance of its DiffuseLight's emission
+ *          (f64, from the description, at creation; attenuation ignored; other materials 0; sol_light_weights), C_i = (float)(prefix_i / W),
+ *          C_{L-1} = 1, q_i = C_i - C_{i-1} in fp32 (sol_light_tables); one draw u, the first k with u < C_k. Density sum_{q_i > 0} q_i pdf_i
+ *          through the tree. With the environment sampled as well (sol_env_sampling): the map is entry L of L + 1 as before, a light entry takes
+ *          one more draw, and the density is (L * sum q_i pdf_i + p_env) / (L + 1). A new unbiased estimator; SOL_EINVAL if every w_i is 0.
+ * With one light modes 1 and 2 are mode 0's estimator and render with its kernels. While the mode is not 0: path-tracing renders run the
+ * product kernel whatever SOL_OPT_KERNEL says, adaptive rounds use it, sol_render_counted and sol_debug_path are SOL_EINVAL. Changing the
+ * mode ends an adaptive session. SOL_EINVAL: a bad size, an unknown mode, non-zero reserved fields (checked before the scene), more than
+ * 2^30 lights (modes 1, 2), mode 2 on a scene whose lights all have power 0. */
+#define SOL_LIGHT_SAMPLING_UNIFORM 0u
+#define SOL_LIGHT_SAMPLING_TREE 1u
+#define SOL_LIGHT_SAMPLING_POWER 2u
+typedef struct SolLightSampling {
+  uint32_t size;           /* in: sizeof(SolLightSampling): lets the struct grow                                         */
+  uint32_t mode;           /* SOL_LIGHT_SAMPLING_UNIFORM / _TREE / _POWER                                                  */
+  uint32_t reserved[2];    /* 0                                                                                          */
+} SolLightSampling;
+/* config == NULL: mode 0. */
+int sol_light_sampling(SolScene* scene, const SolLightSampling* config);
+/* Host only (no device needed): the checks sol_light_sampling makes, on a description (the all-zero power refusal of mode 2 included). */
+int sol_light_sampling_check(const SolSceneDesc* desc, const SolLightSampling* config);
+/* Host only: the power w_i of each light of the description (mode 2's weights, f64, list order); n >= desc->n_lights. */
+int sol_light_weights(const SolSceneDesc* desc, double* w, size_t n);
+/* Diagnostic: mode 2's tables as the device holds them (q, C; n >= n_lights floats each) and W, the f64 sum of the weights. Built by
+ * sol_light_sampling mode 2. NULL pointers are skipped. */
+int sol_light_tables(SolScene* scene, float* q, float* cdf, size_t n, double* total);
+/* Diagnostic: the light tree as the device holds it (6 floats per node: min xyz, max xyz; nodes may be NULL), its node count, the
+ * index of leaf 0 and its size in bytes. Built by sol_light_sampling mode 1 or 2. */
+int sol_light_tree(SolScene* scene, float* nodes, size_t n_floats, uint32_t* n_nodes, uint32_t* first_leaf, size_t* bytes);
+/* Diagnostic: the device's own functions on n host rows. fn 0: (origin xyz, direction xyz) -> (the loop's density, the tree's density,
+ * tree nodes visited, light tests), 6 floats in, 4 out, under the current mode's weighting (modes 0 and 1 uniform: the loop is the
+ * default kernels' function; mode 2 power) and with the environment's entry while sol_env_sampling is on; needs the tree. fn 1: u in
+ * [0, 1) -> the light index mode 2 selects, 1 in, 1 out; needs the tables. */
+int sol_light_eval(SolScene* scene, uint32_t fn, const float* in, uint32_t n, float* out);
+
 /* ---- denoiser (EXTENSION, opt-in) --------------------------------------------------------------------------------------
  * An edge-aware a-trous filter of a colour image guided by the first-hit albedo and normal planes (sol_render_aux): the stand-in for the
  * reference's OidnPostProcessor (src/post/oidn.rs), which stays the Nop post-processor. Colour sums S over n samples, albedo and normal sums

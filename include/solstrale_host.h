@@ -103,6 +103,10 @@ int solh_set_adaptive(SolhBuilder* b, uint32_t round, uint32_t min_samples, doub
  * solh_ray_trace calls: mode 0 off (the default), 1 importance sampling, on every device the call renders on. Unknown modes fail here;
  * a scene without an environment map fails in solh_ray_trace. */
 int solh_set_env_sampling(SolhBuilder* b, uint32_t mode);
+/* EXTENSION, not in the reference: the light sampling mode (solstrale_hip.h sol_light_sampling) for the following
+ * solh_ray_trace calls: 0 uniform (the default), 1 light tree (the same frames), 2 power-weighted, on every device the call renders on.
+ * Unknown modes fail here; mode 2 on a scene whose lights all have power 0 fails in solh_ray_trace. */
+int solh_set_light_sampling(SolhBuilder* b, uint32_t mode);
 typedef void (*solh_progress_fn)(void* user, double progress, double fps, double eta_seconds,
                                  const uint8_t* image_rgb8, uint32_t width, uint32_t height);
 typedef int (*solh_abort_fn)(void* user);

@@ -1120,6 +1120,7 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
     S.env = s->env; S.env_w = d->env_width; S.env_h = d->env_height; S.env_scale = (float)d->env_scale;
   }
   s->env_refusal = sol_env_refusal(d);  // (environment importance sampling, sol_envmap.hip: stops at the first cell of positive weight)
+  s->light_w = sol_light_weights_of(d);  // (light sampling mode 2, sol_lights.hip: O(L), decided at creation like env_refusal)
   S.bgx = (float)d->background[0]; S.bgy = (float)d->background[1]; S.bgz = (float)d->background[2];
   S.cam = cast_camera(d->camera);
   s->kernel_version = ovr.kernel_version;

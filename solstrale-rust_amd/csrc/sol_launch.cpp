@@ -36,7 +36,10 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   // environment importance sampling: path-tracing renders run the ENV builds of the product kernel, whatever SOL_OPT_KERNEL says.
   // Counted renders are the creation probes here (sol_render_counted refuses while it is on); the other shaders read only the scatter's colour.
   const bool env = s->env_is && !count && s->S.shader == SOL_SHADER_PATH_TRACING;
-  if (env) version = 1;
+  // light sampling modes 1 and 2, likewise: the LT builds. With one light they are mode 0's estimator (q_0 = 1), and the
+  // default kernels run.
+  const bool lt = s->light_mode != 0u && !count && s->S.shader == SOL_SHADER_PATH_TRACING && s->S.n_lights > 1u;
+  if (env || lt) version = 1;
   // version 4, the pool kernel (sol_pool.hip): plain renders of the path-tracing... any shader; counted renders (probes, statistics) and trees
   // of 2^17 wide nodes or more (its one-dword node groups carry a 17-bit base) stay with the one-path-per-lane kernel
   if (version == 4 && ((count && !std::getenv("SOL_POOL_COUNT")) || s->n_wide >= SOL_PACK_MAX_NODES)) version = 1;  // (SOL_POOL_COUNT: phase statistics of the pool kernel)
@@ -79,9 +82,9 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   if (version != 1 && version != 4 && s->strict_triangles) return sol_fail(SOL_EINVAL, "kernel variant %d does not implement the consistency rule of scenes with needle triangles", version);
 #ifndef SOL_AB_KERNELS
   if (version != 1) return sol_fail(SOL_EINVAL, "kernel variant %d exists only in -DSOL_AB_KERNELS builds of the library", version);
-  int bpc = sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env);
+  int bpc = sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env, lt);
 #else
-  int bpc = version == 3 ? sol_wf_trace_blocks_per_cu(count, s->has_medium) : sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env);
+  int bpc = version == 3 ? sol_wf_trace_blocks_per_cu(count, s->has_medium) : sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env, lt);
 #endif
   if (s->max_bpc > 0) bpc = std::max(1, std::min(bpc, s->max_bpc));  // SOL_OPT_MAX_BLOCKS_PER_CU
   uint32_t grid = (uint32_t)(s->n_cu * bpc);
@@ -234,7 +237,7 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
     }
     if (P.n_items > 0)
       HIP_TRY(sol_launch_render(version, Sv, dS, P, s->acc, s->partial, s->work, s->spill, s->pool, s->counters, grid, count,
-                                s->has_medium, stack_need > lds_depth, env, s->stream));
+                                s->has_medium, stack_need > lds_depth, env, lt, s->stream));
     if (ad) {
       // the active background blocks are the last ad->n_background entries of the active list: the fill kernel writes the blocks
       // behind its n_traced_blocks
@@ -275,6 +278,7 @@ int sol_render(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
 }
 int sol_render_counted(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
   if (s && s->env_is) return sol_fail(SOL_EINVAL, "sol_render_counted: the counted kernels do not implement environment importance sampling (sol_env_sampling mode 0 first)");
+  if (s && s->light_mode) return sol_fail(SOL_EINVAL, "sol_render_counted: the counted kernels do not implement the light tree (sol_light_sampling mode 0 first)");
   if (s) s->adaptive.open = false;
   return sol_render_impl(s, first, n, seed, true);
 }
@@ -372,6 +376,7 @@ int sol_eval(int device, uint32_t fn, const float* in, uint32_t n, uint32_t in_s
 int sol_debug_path(SolScene* s, uint32_t x, uint32_t y, uint32_t sample, uint64_t seed, float* rows, uint32_t max_rows) {
   if (!s || !rows || max_rows < 2 || x >= s->S.width || y >= s->S.height) return sol_fail(SOL_EINVAL, "bad argument");
   if (s->env_is) return sol_fail(SOL_EINVAL, "sol_debug_path: follows the default estimator only (sol_env_sampling mode 0 first)");
+  if (s->light_mode) return sol_fail(SOL_EINVAL, "sol_debug_path: follows the default estimator only (sol_light_sampling mode 0 first)");
   HIP_TRY(hipSetDevice(s->device));
   RenderParams P{};
   P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);

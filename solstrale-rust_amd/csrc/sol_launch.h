@@ -7,9 +7,9 @@
 // version 1: one path per lane (the product kernel); versions 2 / 3 (-DSOL_AB_KERNELS builds): the wavefront variants of sol_wavefront.hip
 hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
                              uint32_t* spill, void* pool, DevCounters* cnt, uint32_t grid, bool count, bool medium, bool may_spill,
-                             bool env, hipStream_t stream);
-// env: environment importance sampling (version 1, uncounted)
-int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env = false);
+                             bool env, bool lt, hipStream_t stream);
+// env: environment importance sampling, lt: light sampling modes 1 and 2; version 1, uncounted
+int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env = false, bool lt = false);
 hipError_t sol_launch_stage_resolve(const DevScene* dS, const RenderParams& P, float* partial, hipStream_t stream);
 hipError_t sol_launch_fill_background(const DevScene* dS, const RenderParams& P, float* partial, hipStream_t stream);
 hipError_t sol_launch_debug_path(const DevScene& S, const RenderParams& P, uint32_t px, uint32_t py, uint32_t s, uint32_t* spill,

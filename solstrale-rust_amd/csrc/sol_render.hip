@@ -21,7 +21,9 @@
 // search must pass the triangle consistency rule before it is shaded, or the lane searches the same ray again for what lies behind it.
 // ENV = true: environment importance sampling (sol_env_sampling): the environment map is one more entry of the light mixture.
 // Built uncounted only; ENV = false is the default estimator, and its code does not depend on the ENV builds.
-template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT, bool ENV>
+// LT = true: light sampling modes 1 and 2 (sol_light_sampling): the light density through the light tree, mode 2 (runtime,
+// DevScene::light_power) selects by power. Built uncounted only, like ENV.
+template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT, bool ENV, bool LT = false>
 __global__ void __launch_bounds__(SOL_WG, SOL_V1_MIN_WAVES)  // 4 waves per SIMD: the 32 KiB LDS stack allows 5 workgroups per CU, 128 VGPRs 4
 sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* __restrict__ acc, float* __restrict__ partial,
                   uint32_t* __restrict__ work_counter, uint32_t* __restrict__ spill, DevCounters* __restrict__ dcnt) {
@@ -79,7 +81,7 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
         p.o = t.o; p.d = t.d;  // (the ray lives in the search state while it is traced)
         f3 c;
         if (COUNT && p.depth == 0u && SOL_REF_KIND(t.h.ref) != SOL_REF_NONE) cnt.primary_hits++;
-        if (shade_vertex<COUNT, STRICT, ENV>(S, p, t.h, c, cnt)) {
+        if (shade_vertex<COUNT, STRICT, ENV, LT>(S, p, t.h, c, cnt)) {
           if (COUNT) count_path(cnt, p.depth + 1u);  // (depth counts the scatterings before this vertex)
           sum = sum + c;  // add_row_data (src/renderer/mod.rs:361-365): sums, not means
           alive = false;
@@ -273,10 +275,10 @@ hipError_t sol_launch_debug_path(const DevScene& S, const RenderParams& P, uint3
 }
 
 // ---- launch wrappers (called from sol_launch.cpp) ----
-template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT, bool ENV = false>
+template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT, bool ENV = false, bool LT = false>
 static hipError_t launch_v1(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
                             uint32_t* spill, DevCounters* cnt, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL((sol_render_kernel<COUNT, MEDIUM, SPILL, STRICT, ENV>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
+  hipLaunchKernelGGL((sol_render_kernel<COUNT, MEDIUM, SPILL, STRICT, ENV, LT>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
   return hipGetLastError();
 }
 template <bool STRICT>
@@ -289,22 +291,29 @@ static hipError_t launch_v1_any(const DevScene* dS, const RenderParams& P, float
   return medium ? launch_v1<false, true, false, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
                 : launch_v1<false, false, false, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
 }
-template <bool STRICT>  // (ENV: plain renders only - sol_render_counted refuses while importance sampling is on)
-static hipError_t launch_v1_env(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, DevCounters* cnt,
+template <bool STRICT, bool ENV, bool LT>  // (ENV, LT: plain renders only - sol_render_counted refuses while either is on)
+static hipError_t launch_v1_ext(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, DevCounters* cnt,
                                 uint32_t grid, bool medium, bool may_spill, hipStream_t stream) {
-  if (may_spill) return medium ? launch_v1<false, true, true, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream)
-                               : launch_v1<false, false, true, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream);
-  return medium ? launch_v1<false, true, false, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream)
-                : launch_v1<false, false, false, STRICT, true>(dS, P, acc, partial, work, spill, cnt, grid, stream);
+  if (may_spill) return medium ? launch_v1<false, true, true, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
+                               : launch_v1<false, false, true, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
+  return medium ? launch_v1<false, true, false, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
+                : launch_v1<false, false, false, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
+}
+template <bool ENV, bool LT>
+static hipError_t launch_v1_ext_any(const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill,
+                                    DevCounters* cnt, uint32_t grid, bool medium, bool may_spill, hipStream_t stream) {
+  return S.tri_delta > 0.0f ? launch_v1_ext<true, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream)
+                            : launch_v1_ext<false, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
 }
 
 hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
                              uint32_t* spill, void* pool, DevCounters* cnt, uint32_t grid, bool count, bool medium, bool may_spill,
-                             bool env, hipStream_t stream) {
-  if (env) {
-    if (version != 1 || count) return hipErrorInvalidValue;  // (sol_render_impl runs importance sampling on the uncounted product kernel only)
-    return S.tri_delta > 0.0f ? launch_v1_env<true>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream)
-                              : launch_v1_env<false>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
+                             bool env, bool lt, hipStream_t stream) {
+  if (env || lt) {
+    if (version != 1 || count) return hipErrorInvalidValue;  // (sol_render_impl runs importance sampling and the light tree on the uncounted product kernel only)
+    if (lt) return env ? launch_v1_ext_any<true, true>(S, dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream)
+                       : launch_v1_ext_any<false, true>(S, dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
+    return launch_v1_ext_any<true, false>(S, dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
   }
 #ifdef SOL_AB_KERNELS
   if (version == 4) return sol_launch_pool4(S, dS, P, partial, work, spill, grid, medium, may_spill, count ? cnt : nullptr, stream);  // (sol_pool.hip)
@@ -325,7 +334,15 @@ static int blocks_per_cu(K kernel) {
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
   return n;
 }
-int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env) {
+int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env, bool lt) {
+  if (lt) {
+    if (env) {
+      if (strict) return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true, true, true>);
+      return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, false, true, true>);
+    }
+    if (strict) return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, false, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true, false, true>);
+    return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, false, true>) : blocks_per_cu(sol_render_kernel<false, false, true, false, false, true>);
+  }
   if (env) {
     if (strict) return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true, true>);
     return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, true>) : blocks_per_cu(sol_render_kernel<false, false, true, false, true>);

@@ -190,7 +190,18 @@ struct SolScene {
   float* env_tables = nullptr;
   float env_total = 0.f;
   bool env_is = false;
+  // Light tree and power-weighted light sampling (sol_lights.hip). light_w: the f64 weights (area x luminance) of the
+  // description's lights, decided at creation; light_tree: the tree (built on first use of mode 1 or 2), light_tables: q then the CDF
+  // (mode 2, first use); light_mode: 0 uniform, 1 tree, 2 power - modes 1 and 2 run the LT kernels.
+  std::vector<double> light_w;
+  double light_total = 0.0;
+  float* light_tree = nullptr;
+  size_t light_tree_bytes = 0;
+  float* light_tables = nullptr;
+  uint32_t light_mode = 0;
 };
+// The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
+std::vector<double> sol_light_weights_of(const SolSceneDesc* d);
 // Why environment importance sampling cannot run on the scene `d` describes, or "" (sol_envmap.hip; host only).
 std::string sol_env_refusal(const SolSceneDesc* d);
 

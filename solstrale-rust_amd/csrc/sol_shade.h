@@ -233,11 +233,81 @@ DEV f3 env_sample(const DevScene& S, float r1, float r2, float& pdf, uint32_t& c
   return mk3(-st * cp, -ct, st * sp);
 }
 
+// ---- EXTENSION: light tree and power-weighted selection (tree and tables: sol_lights.hip) -------------------------
+// sum_i w_i * pdf_i over the lights in list order: w_i = 1 (uniform, modes 0 and 1) or q_i (power, mode 2: a light with q_i == 0 is
+// skipped, not added as 0 * pdf). TREE = false walks the list; TREE = true walks the light tree without a stack, depth first, children in
+// index order, and tests a light only if the ray [0, inf) enters every box from the root to its leaf. Every box is conservative for the
+// record light_pdf_value reads, so a light the walk skips would have added exactly +0.0f, and the lights it tests are added in the
+// loop's order: the two sums are bit-identical. STAT: count node visits and light tests (sol_light_eval).
+template <bool COUNT, bool STRICT, bool TREE, bool STAT = false>
+DEV float light_sum(const DevScene& S, f3 origin, f3 dir, Counters& cnt, uint32_t& visits, uint32_t& tests) {
+  const uint32_t L = S.n_lights;
+  const bool power = S.light_power != 0u;
+  float sum = 0.0f;
+  if (!TREE) {
+    for (uint32_t i = 0; i < L; ++i) {
+      const float q = power ? ldg_f32(S.light_q + i) : 1.0f;
+      if (!(q > 0.0f)) continue;
+      if (STAT) tests++;
+      const float p = light_pdf_value<COUNT, STRICT>(S, L == 1u ? S.light0 : ldg_u32(S.lights + i), origin, dir, cnt);
+      sum += power ? q * p : p;
+    }
+    return sum;
+  }
+  const f3 inv = mk3(1.0f / dir.x, 1.0f / dir.y, 1.0f / dir.z);
+  const bool sx = inv.x < 0.0f, sy = inv.y < 0.0f, sz = inv.z < 0.0f;  // (-0 -> -inf: negative; a NaN axis drops out of the slab test)
+  const uint32_t first = S.light_first_leaf;
+  uint32_t n = 0;
+  for (;;) {
+    const float2* b = reinterpret_cast<const float2*>(S.light_nodes + (size_t)n * 6u);
+    const float2 b0 = b[0], b1 = b[1], b2 = b[2];  // (xmin, ymin), (zmin, xmax), (ymax, zmax)
+    if (STAT) visits++;
+    float te;
+    if (slab(b0.x, b1.y, b0.y, b2.x, b1.x, b2.y, origin, inv, sx, sy, sz, te)) {
+      if (n < first) {  // inner node: its first child
+        n = 4u * n + 1u;
+        continue;
+      }
+      const uint32_t i = n - first;
+      if (i < L) {  // (padding leaves are empty boxes; the test matters for a NaN direction, which enters every box)
+        const float q = power ? ldg_f32(S.light_q + i) : 1.0f;
+        if (q > 0.0f) {
+          if (STAT) tests++;
+          const float p = light_pdf_value<COUNT, STRICT>(S, L == 1u ? S.light0 : ldg_u32(S.lights + i), origin, dir, cnt);
+          sum += power ? q * p : p;
+        }
+      }
+    }
+    while (n != 0u && (n & 3u) == 0u) n = (n - 1u) >> 2;  // the last of its siblings: up to the parent
+    if (n == 0u) break;
+    ++n;  // the next sibling
+  }
+  return sum;
+}
+// The mixture density from the lights' sum: uniform sum / L; power: the sum itself (the q_i sum to 1). ENV: the map is entry L of L + 1
+// (DESIGN.md 12): (sum + p_env) / (L + 1) uniform, (L * sum + p_env) / (L + 1) power.
+template <bool ENV>
+DEV float light_mix(const DevScene& S, float sum, f3 dir) {
+  if (ENV) {
+    uint32_t ci, cj;
+    const float pe = env_pdf(S, dir, ci, cj);
+    return ((S.light_power ? (float)S.n_lights * sum : sum) + pe) / (float)(S.n_lights + 1u);
+  }
+  return S.light_power ? sum : sum / (float)S.n_lights;
+}
+// Mode 2's selection: one draw u, the first k with u < cdf[k] (cdf[L - 1] == 1: never a light of q == 0).
+DEV uint32_t light_select(const DevScene& S, float u) { return env_find(S.light_cdf, S.n_lights, u); }
+
 // ENV: the environment is light entry L = n_lights of the mixture - the draw picks one of L + 1 entries, the value
 // averages L + 1 densities (the lights' in list order, then the environment's).
-template <bool COUNT, bool STRICT = false, bool ENV = false>
+// LT: light sampling modes 1 and 2 - the sum through the light tree, weighted by q in mode 2.
+template <bool COUNT, bool STRICT = false, bool ENV = false, bool LT = false>
 DEV float container_pdf_value(const DevScene& S, f3 origin, f3 dir, Counters& cnt) {  // pdf.rs:89-96
   float sum = 0.0f;
+  if (LT) {
+    uint32_t visits, tests;
+    return light_mix<ENV>(S, light_sum<COUNT, STRICT, true>(S, origin, dir, cnt, visits, tests), dir);
+  }
   if (ENV) {
     for (uint32_t i = 0; i < S.n_lights; ++i)
       sum += light_pdf_value<COUNT, STRICT>(S, S.n_lights == 1u ? S.light0 : ldg_u32(S.lights + i), origin, dir, cnt);
@@ -249,16 +319,21 @@ DEV float container_pdf_value(const DevScene& S, f3 origin, f3 dir, Counters& cn
   for (uint32_t i = 0; i < S.n_lights; ++i) sum += light_pdf_value<COUNT, STRICT>(S, ldg_u32(S.lights + i), origin, dir, cnt);
   return sum / (float)S.n_lights;
 }
-template <bool ENV = false>
+template <bool ENV = false, bool LT = false>
 DEV f3 container_pdf_generate(const DevScene& S, f3 origin, Rng& rng) {  // pdf.rs:98-101
   if (ENV) {
-    const uint32_t k = rnd_index(rng, S.n_lights + 1u);
+    uint32_t k = rnd_index(rng, S.n_lights + 1u);
     if (k == S.n_lights) {
       const float r1 = rnd(rng), r2 = rnd(rng);
       float pdf;
       uint32_t ci, cj;
       return env_sample(S, r1, r2, pdf, ci, cj);
     }
+    if (LT && S.light_power) k = light_select(S, rnd(rng));  // (mode 2: one more draw picks the light by power)
+    return light_random_direction(S, S.n_lights == 1u ? S.light0 : ldg_u32(S.lights + k), k, origin, rng);
+  }
+  if (LT && S.light_power) {  // mode 2: one draw, as rnd_index takes one
+    const uint32_t k = light_select(S, rnd(rng));
     return light_random_direction(S, S.n_lights == 1u ? S.light0 : ldg_u32(S.lights + k), k, origin, rng);
   }
   uint32_t i = rnd_index(rng, S.n_lights);  // (the draw is consumed also when there is one light: same stream as the oracle)
@@ -297,7 +372,7 @@ struct Scatter {
 
 // Materials::scatter (material/mod.rs:191-207 Lambertian, :239-249 Metal, :279-302 Dielectric, :359-368 DiffuseLight,
 // :396-410 Isotropic, :430-436 Blend)
-template <bool COUNT, bool STRICT = false, bool ENV = false>
+template <bool COUNT, bool STRICT = false, bool ENV = false, bool LT = false>
 DEV void scatter(const DevScene& S, f3 ray_dir, const Surface& sf, Rng& rng, Scatter& sc, Counters& cnt) {
   DMat m = ldg_rec(S.mats + sf.mat);
   for (int guard = 0; guard < 16 && m.kind == SOL_MAT_BLEND; ++guard) m = ldg_rec(S.mats + (rnd(rng) > m.param ? m.m1 : m.m2));
@@ -308,11 +383,11 @@ DEV void scatter(const DevScene& S, f3 ray_dir, const Surface& sf, Rng& rng, Sca
     sc.color = albedo_color<COUNT>(S, m, sf.u, sf.v, cnt);
     Onb uvw = onb_new(sf.normal);  // CosinePdf::new (pdf.rs:58)
     f3 dir;
-    if (rnd(rng) < 0.5f) dir = container_pdf_generate<ENV>(S, sf.p, rng);  // mix_generate (pdf.rs:42-48)
+    if (rnd(rng) < 0.5f) dir = container_pdf_generate<ENV, LT>(S, sf.p, rng);  // mix_generate (pdf.rs:42-48)
     else dir = onb_local(uvw, random_cosine_direction(rng));
     f3 udir = unit3(dir);
     float cos_pdf = fmaxf(dot3(udir, uvw.normal) / SOL_PI, 0.0f);                                 // CosinePdf::value
-    float mix = 0.5f * container_pdf_value<COUNT, STRICT, ENV>(S, sf.p, dir, cnt) + 0.5f * cos_pdf;            // mix_value
+    float mix = 0.5f * container_pdf_value<COUNT, STRICT, ENV, LT>(S, sf.p, dir, cnt) + 0.5f * cos_pdf;            // mix_value
     float cos_theta = dot3(sf.normal, udir);                                                      // scattering_pdf_value
     float scattering = cos_theta < 0.0f ? 0.0f : cos_theta / SOL_PI;
     sc.dir = dir;
@@ -346,10 +421,10 @@ DEV void scatter(const DevScene& S, f3 ray_dir, const Surface& sf, Rng& rng, Sca
     sc.type = SCATTER_PDF;
     sc.color = albedo_color<COUNT>(S, m, sf.u, sf.v, cnt);
     f3 dir;
-    if (rnd(rng) < 0.5f) dir = container_pdf_generate<ENV>(S, sf.p, rng);
+    if (rnd(rng) < 0.5f) dir = container_pdf_generate<ENV, LT>(S, sf.p, rng);
     else dir = unit3(random_in_unit_sphere(rng));  // SpherePdf::generate (pdf.rs:121-124)
     const float sphere_pdf = (float)(1. / (4. * 3.14159265358979323846));
-    float mix = 0.5f * container_pdf_value<COUNT, STRICT, ENV>(S, sf.p, dir, cnt) + 0.5f * sphere_pdf;
+    float mix = 0.5f * container_pdf_value<COUNT, STRICT, ENV, LT>(S, sf.p, dir, cnt) + 0.5f * sphere_pdf;
     sc.dir = dir;
     sc.probability = sphere_pdf / mix;
   }

@@ -210,6 +210,15 @@ struct DevScene {
   const float* env_cond;
   uint32_t env_cw, env_ch;
   float env_pdf_scale;
+  // EXTENSION, light tree and power-weighted light sampling (sol_lights.hip): light_nodes = the implicit complete 4-ary
+  // tree over the light list in list order, 6 floats per node (min xyz, max xyz; children of node n are 4n + 1 .. 4n + 4, leaf i is node
+  // light_first_leaf + i); light_q / light_cdf = the selection probabilities and the CDF of mode 2 (light_power = 1). Null until
+  // sol_light_sampling builds them; read only by the LT kernels and the diagnostics.
+  const float* light_nodes;
+  const float* light_q;
+  const float* light_cdf;
+  uint32_t light_first_leaf;
+  uint32_t light_power;
 };
 
 struct RenderParams {

@@ -282,6 +282,9 @@ struct RenderConfig {
   // EXTENSION (not in the reference): environment importance sampling (include/solstrale_hip.h sol_env_sampling), applied to
   // every device handle ray_trace creates; 0 off (the default), 1 importance sampling (the scene must have an environment map).
   uint32_t env_sampling = 0;
+  // EXTENSION (not in the reference): light sampling mode (include/solstrale_hip.h sol_light_sampling), applied to every device
+  // handle ray_trace creates; 0 uniform (the default), 1 tree (the same frames), 2 power.
+  uint32_t light_sampling = 0;
 };
 
 struct Scene {

@@ -626,6 +626,12 @@ std::string ray_trace(const Scene& scene, const std::function<void(RenderProgres
     for (SolScene* s : devs)
       if (sol_env_sampling(s, &es) != SOL_OK) return sol_last_error();
   }
+  if (rc.light_sampling) {  // EXTENSION: light tree / power-weighted light sampling, likewise before any render
+    SolLightSampling ls{};
+    ls.size = sizeof ls; ls.mode = rc.light_sampling;
+    for (SolScene* s : devs)
+      if (sol_light_sampling(s, &ls) != SOL_OK) return sol_last_error();
+  }
   const uint32_t spp = rc.samples_per_pixel;
   const size_t npix = rc.width * rc.height;
   using clk = std::chrono::steady_clock;

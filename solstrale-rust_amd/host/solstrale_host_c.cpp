@@ -316,6 +316,14 @@ int solh_set_adaptive(SolhBuilder* b, uint32_t round, uint32_t min_samples, doub
   });
 }
 
+int solh_set_light_sampling(SolhBuilder* b, uint32_t mode) {
+  return guarded([&] {
+    if (mode > SOL_LIGHT_SAMPLING_POWER) throw std::runtime_error("solh_set_light_sampling: unknown mode (0 uniform, 1 tree, 2 power)");
+    b->scene.render_config.light_sampling = mode;
+    return 0;
+  });
+}
+
 int solh_set_env_sampling(SolhBuilder* b, uint32_t mode) {
   return guarded([&] {
     if (mode > SOL_ENV_SAMPLING_IMPORTANCE) throw std::runtime_error("solh_set_env_sampling: unknown mode (0 off, 1 importance)");

@@ -163,6 +163,14 @@ class SolEnvSampling(C.Structure):
     _fields_ = [("size", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+SOL_LIGHT_SAMPLING_UNIFORM, SOL_LIGHT_SAMPLING_TREE, SOL_LIGHT_SAMPLING_POWER = 0, 1, 2
+
+
+class SolLightSampling(C.Structure):
+    """EXTENSION: light tree / power-weighted light sampling (sol_light_sampling). Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("mode", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 DENOISE_DEFAULT_ITERATIONS, DENOISE_DEFAULT_SIGMA_COLOR, DENOISE_DEFAULT_NORMAL_POWER = 5, 0.25, 64.0
 
 
@@ -251,6 +259,12 @@ def load_hip():
     _sig(lib, "sol_env_sampling_check", C.c_int, [C.c_void_p, C.POINTER(SolEnvSampling)])
     _sig(lib, "sol_env_tables", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)])
     _sig(lib, "sol_env_eval", C.c_int, [P, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p])
+    _sig(lib, "sol_light_sampling", C.c_int, [P, C.POINTER(SolLightSampling)])
+    _sig(lib, "sol_light_sampling_check", C.c_int, [C.c_void_p, C.POINTER(SolLightSampling)])
+    _sig(lib, "sol_light_weights", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t])
+    _sig(lib, "sol_light_tables", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double)])
+    _sig(lib, "sol_light_tree", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)])
+    _sig(lib, "sol_light_eval", C.c_int, [P, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p])
     _sig(lib, "sol_denoise_check", C.c_int, [C.POINTER(SolDenoise)])
     _sig(lib, "sol_resolve_aux", C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)])
     _sig(lib, "sol_denoise", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SolDenoise)])
@@ -269,6 +283,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_comm_destroy", "sol_gather", "sol_gather_local", "sol_comm_self_check", "sol_read_image", "sol_max_samples_per_call", "sol_background_blocks",
                "sol_adaptive_begin", "sol_adaptive_round", "sol_adaptive_counts", "sol_tonemap_rgb8_adaptive", "sol_adaptive_rescale",
                "sol_env_sampling", "sol_env_sampling_check", "sol_env_tables", "sol_env_eval",
+               "sol_light_sampling", "sol_light_sampling_check", "sol_light_weights", "sol_light_tables", "sol_light_tree", "sol_light_eval",
                "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8"]
 
 
@@ -313,6 +328,7 @@ def load_host():
     _sig(lib, "solh_set_post_processors", I, [B, I, C.POINTER(C.c_int), C.POINTER(C.c_double)])
     _sig(lib, "solh_set_adaptive", I, [B, C.c_uint32, C.c_uint32, D])
     _sig(lib, "solh_set_env_sampling", I, [B, C.c_uint32])
+    _sig(lib, "solh_set_light_sampling", I, [B, C.c_uint32])
     _sig(lib, "solh_abi_sizes", None, [C.POINTER(C.c_uint32)])
     _sig(lib, "solh_to_rgb_color", None, [_D3, C.c_uint32, C.POINTER(C.c_uint8)])
     _libs["host"] = lib
@@ -324,7 +340,7 @@ HOST_SYMBOLS = ["solh_builder_new", "solh_builder_free", "solh_last_error", "sol
                 "solh_diffuse_light", "solh_blend", "solh_sphere", "solh_quad", "solh_box", "solh_triangle",
                 "solh_triangles", "solh_spheres", "solh_constant_medium", "solh_bvh", "solh_bvh_range", "solh_finish",
                 "solh_tree_depth", "solh_environment", "solh_ray_trace", "solh_ray_trace_devices", "solh_abi_sizes", "solh_to_rgb_color", "solh_set_post_processors", "solh_load_obj",
-                "solh_set_adaptive", "solh_set_env_sampling"]
+                "solh_set_adaptive", "solh_set_env_sampling", "solh_set_light_sampling"]
 
 
 def d3(v):

@@ -287,6 +287,47 @@ class DeviceScene:
         self._chk(self.lib.sol_env_eval(self.h, fn, rows.ctypes.data, rows.shape[0], out.ctypes.data))
         return out
 
+    # ---- light tree and power-weighted light sampling (EXTENSION) ----
+    def light_sampling(self, mode):
+        """sol_light_sampling: mode None / 0 / "uniform", 1 / "tree" (the same frames through the light tree), 2 / "power"."""
+        m = {None: 0, "uniform": 0, "tree": 1, "power": 2}.get(mode, mode)
+        if m not in (0, 1, 2):
+            raise ValueError(f"light_sampling: unknown mode {mode!r}")
+        cfg = _abi.SolLightSampling(size=C.sizeof(_abi.SolLightSampling), mode=m)
+        self._chk(self.lib.sol_light_sampling(self.h, C.byref(cfg)))
+
+    def light_tables(self):
+        """sol_light_tables: (q [L], C [L]) float32 as the device holds them, and W (the f64 sum of the weights). Needs mode 2 once."""
+        n = int(self.scene.desc.n_lights)
+        q = np.zeros(n, dtype=np.float32)
+        cdf = np.zeros(n, dtype=np.float32)
+        total = C.c_double()
+        self._chk(self.lib.sol_light_tables(self.h, q.ctypes.data, cdf.ctypes.data, n, C.byref(total)))
+        return q, cdf, float(total.value)
+
+    def light_tree(self):
+        """sol_light_tree: (nodes (N, 6) float32 = min xyz, max xyz; index of leaf 0; bytes). Needs mode 1 or 2 once."""
+        nn, first, nb = C.c_uint32(), C.c_uint32(), C.c_size_t()
+        self._chk(self.lib.sol_light_tree(self.h, None, 0, C.byref(nn), C.byref(first), C.byref(nb)))
+        nodes = np.zeros((nn.value, 6), dtype=np.float32)
+        self._chk(self.lib.sol_light_tree(self.h, nodes.ctypes.data, nodes.size, None, None, None))
+        return nodes, int(first.value), int(nb.value)
+
+    def light_eval(self, fn, rows):
+        """sol_light_eval on the device: fn 0 ("density"): rows (n, 6) of origin xyz, direction xyz -> (n, 4) loop density, tree density,
+        nodes visited, light tests; fn 1 ("select"): u (n,) -> (n,) selected light index (int64)."""
+        fn = {"density": 0, "select": 1}.get(fn, fn)
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        if fn == 0 and (rows.ndim != 2 or rows.shape[1] != 6):
+            raise ValueError("light_eval: fn 0 takes (n, 6) rows")
+        if fn == 1:
+            rows = rows.reshape(-1)
+        elif fn != 0:
+            raise ValueError(f"light_eval: unknown function {fn!r}")
+        out = np.zeros((rows.shape[0], 4) if fn == 0 else rows.shape[0], dtype=np.float32)
+        self._chk(self.lib.sol_light_eval(self.h, fn, rows.ctypes.data, rows.shape[0], out.ctypes.data))
+        return out if fn == 0 else out.astype(np.int64)
+
     def resolve_image(self):
         """Device pointer of the scene's own row-major image (W*H*3 floats) after un-permuting its accumulators."""
         p = C.c_void_p()

@@ -79,11 +79,15 @@ class RenderConfig:
     """src/renderer/mod.rs:26-52 (seed is the build's addition; OidnPostProcessor is not built)."""
 
     def __init__(self, width=300, height=200, samples_per_pixel=50, shader=(_abi.SHADER_PATH_TRACING, 50),
-                 seed=0x5017A1E, post_processors=None, adaptive=None, env_sampling=None):
+                 seed=0x5017A1E, post_processors=None, adaptive=None, env_sampling=None, light_sampling=None):
         """adaptive: EXTENSION, AdaptiveSampling(round, min_samples, threshold) or None.
-        env_sampling: EXTENSION, None or "importance": sample the environment map as one more light."""
+        env_sampling: EXTENSION, None or "importance": sample the environment map as one more light.
+        light_sampling: EXTENSION, None (uniform), "tree" (the same frames through a light tree) or "power" (select lights by power;
+        DESIGN.md 14)."""
         if env_sampling not in ENV_SAMPLING_MODES:
             raise ValueError(f"env_sampling: None or 'importance', not {env_sampling!r}")
+        if light_sampling not in LIGHT_SAMPLING_MODES:
+            raise ValueError(f"light_sampling: None, 'tree' or 'power', not {light_sampling!r}")
         self.width = width
         self.height = height
         self.samples_per_pixel = samples_per_pixel
@@ -92,9 +96,11 @@ class RenderConfig:
         self.post_processors = [NopPostProcessor()] if post_processors is None else list(post_processors)
         self.adaptive = adaptive
         self.env_sampling = env_sampling
+        self.light_sampling = light_sampling
 
 
 ENV_SAMPLING_MODES = {None: _abi.SOL_ENV_SAMPLING_OFF, "importance": _abi.SOL_ENV_SAMPLING_IMPORTANCE}
+LIGHT_SAMPLING_MODES = {None: _abi.SOL_LIGHT_SAMPLING_UNIFORM, "tree": _abi.SOL_LIGHT_SAMPLING_TREE, "power": _abi.SOL_LIGHT_SAMPLING_POWER}
 
 
 def AdaptiveSampling(round=64, min_samples=128, threshold=0.02):
@@ -168,6 +174,8 @@ class Scene:
         if b.lib.solh_set_adaptive(b.h, ad[0], ad[1], ad[2]) != 0:
             raise HostError(b.lib.solh_last_error().decode(errors="replace"))
         if b.lib.solh_set_env_sampling(b.h, ENV_SAMPLING_MODES[getattr(rc, "env_sampling", None)]) != 0:
+            raise HostError(b.lib.solh_last_error().decode(errors="replace"))
+        if b.lib.solh_set_light_sampling(b.h, LIGHT_SAMPLING_MODES[getattr(rc, "light_sampling", None)]) != 0:
             raise HostError(b.lib.solh_last_error().decode(errors="replace"))
         if devices is None:
             rc_ = b.lib.solh_ray_trace(b.h, rc.samples_per_pixel, rc.seed, strat, interval_seconds, device, cb, ab, None)

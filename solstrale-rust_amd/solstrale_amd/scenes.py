@@ -90,6 +90,86 @@ def cornell_spheres(render_config=None, n_spheres=10000, seed=1):
     return b.finish(b.Bvh(world), CameraConfig(**_CORNELL_CAMERA), (0., 0., 0.), rc)
 
 
+
+# ---- many lights (EXTENSION: the light tree and power-weighted light sampling) -----------------------------------
+_LAMP_POWER = 15. * 130. * 105.  # the Cornell box's ceiling lamp: radiance x area
+
+
+def _cornell_walls(b, albedo_scale=1.0):
+    k = albedo_scale
+    red = b.Lambertian(b.SolidColor(.65 * k, .05 * k, .05 * k))
+    white = b.Lambertian(b.SolidColor(.73 * k, .73 * k, .73 * k))
+    green = b.Lambertian(b.SolidColor(.12 * k, .45 * k, .15 * k))
+    world = [
+        b.Quad((555, 0, 0), (0, 555, 0), (0, 0, 555), green),
+        b.Quad((0, 0, 0), (0, 555, 0), (0, 0, 555), red),
+        b.Quad((0, 0, 0), (555, 0, 0), (0, 0, 555), white),
+        b.Quad((555, 555, 555), (-555, 0, 0), (0, 0, -555), white),
+        b.Quad((0, 0, 555), (555, 0, 0), (0, 555, 0), white),
+    ]
+    world += b.new_box((0, 0, 0), (165, 330, 165), white, [RotationY(15.), Translation((265, 0, 295))])
+    world += b.new_box((0, 0, 0), (165, 165, 165), white, [RotationY(-18.), Translation((130, 0, 65))])
+    return world
+
+
+def _lamp_grid(b, n, kind, x0, x1, z0, z1, radiance_for_area):
+    """n lamps on a grid of ceil(sqrt(n)) columns over [x0, x1] x [z0, z1] just below the ceiling (y = 554), each half its cell's
+    width and depth and facing down: quads, triangles (one per lamp: half of the lamp's quad) or spheres (radius a quarter of the smaller
+    cell side). radiance_for_area(area) -> the radiance of a lamp of that emitting area. Returns the hittable ids."""
+    cols = int(math.ceil(math.sqrt(n)))
+    rows = int(math.ceil(n / cols))
+    cw, cd = (x1 - x0) / cols, (z1 - z0) / rows
+    w, d = 0.5 * cw, 0.5 * cd
+    cells = [(i % cols, i // cols) for i in range(n)]
+    ids = []
+    if kind == "quads":
+        e = radiance_for_area(w * d)
+        m = b.DiffuseLight(e, e, e)
+        for cx, cz in cells:
+            xh, zh = x0 + (cx + .75) * cw, z0 + (cz + .75) * cd  # (the far corner: u = -x, v = -z, normal u x v = -y, as the Cornell lamp)
+            ids.append(b.Quad((xh, 554., zh), (-w, 0., 0.), (0., 0., -d), m))
+    elif kind == "triangles":
+        e = radiance_for_area(0.5 * w * d)
+        m = b.DiffuseLight(e, e, e)
+        v = np.array([[(x0 + (cx + .75) * cw, 554., z0 + (cz + .75) * cd), (x0 + (cx + .25) * cw, 554., z0 + (cz + .75) * cd),
+                       (x0 + (cx + .75) * cw, 554., z0 + (cz + .25) * cd)] for cx, cz in cells], dtype=np.float64)
+        first, k = b.triangles(v, np.full(n, m, dtype=np.int32))
+        ids += list(range(first, first + k))
+    elif kind == "spheres":
+        r = 0.25 * min(cw, cd)
+        e = radiance_for_area(4. * math.pi * r * r)
+        m = b.DiffuseLight(e, e, e)
+        c = np.array([(x0 + (cx + .5) * cw, 553. - r, z0 + (cz + .5) * cd) for cx, cz in cells], dtype=np.float64)
+        first, k = b.spheres(c, r, np.full(n, m, dtype=np.int32))
+        ids += list(range(first, first + k))
+    else:
+        raise ValueError(f"kind: 'quads', 'triangles' or 'spheres', not {kind!r}")
+    return ids
+
+
+def many_lights(n, kind="quads", render_config=None):
+    """The Cornell box (C1) with its ceiling lamp replaced by a grid of n small lamps (quads, triangles or spheres) of the same total
+    power (radiance x area), over x in [113, 443], z in [127, 427] below the ceiling: n lights for the light tree."""
+    rc = render_config or RenderConfig(width=400, height=400, samples_per_pixel=50)
+    b = SceneBuilder()
+    world = _cornell_walls(b)
+    world += _lamp_grid(b, n, kind, 113., 443., 127., 427., lambda area: _LAMP_POWER / (n * area))
+    return b.finish(b.Bvh(world), CameraConfig(**_CORNELL_CAMERA), (0., 0., 0.), rc)
+
+
+def mixed_power_lights(n, render_config=None):
+    """One bright lamp (radiance 3, 100 x 100, centre of the ceiling) plus n - 1 dim ones (radiance 0.1, quads on a grid over the back
+    strip of the ceiling, z in [420, 540]) in the Cornell box with albedos scaled to at most 0.5: radiance <= 3 and albedo <= 0.5, so
+    that the min(3) filter of the path-tracing shader cannot bind ("Expectation"). Power-weighted selection
+    sends most light samples to the bright lamp, uniform selection 1 in n."""
+    rc = render_config or RenderConfig(width=400, height=400, samples_per_pixel=50)
+    b = SceneBuilder()
+    world = _cornell_walls(b, albedo_scale=0.5 / 0.73)
+    world.append(b.Quad((328., 554., 300.), (-100., 0., 0.), (0., 0., -100.), b.DiffuseLight(3., 3., 3.)))
+    if n > 1:
+        world += _lamp_grid(b, n - 1, "quads", 15., 540., 420., 540., lambda area: 0.1)
+    return b.finish(b.Bvh(world), CameraConfig(**_CORNELL_CAMERA), (0., 0., 0.), rc)
+
 # ---- C3: "Sponza-class" procedural atrium ---------------------------------------------------------------------
 def _grid(f, nu, nv, tile=(1., 1.)):
     """Tessellates the parametric surface f(u, v) -> (x, y, z), u,v in [0,1], into 2*nu*nv triangles."""
