@@ -225,10 +225,11 @@ void sol_scene_destroy(SolScene* s) {
   hipSetDevice(s->device);
   if (s->stream) hipStreamSynchronize(s->stream);
   sol_comm_destroy(s);
-  void* ptrs[] = {s->leaf_refs, s->nodes, s->wides, s->tris, s->tri_shade, s->quads, s->spheres, s->mediums, s->mats, s->texs, s->texels, s->env, s->lights, s->light_tri,
+  void* ptrs[] = {s->mats, s->texs, s->texels, s->env, s->light_tri,
                   s->acc_own, s->partial, s->image, s->rgb8, s->work, s->spill, s->counters, s->pool, s->queue, s->wf_ctr,
                   s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block, s->env_tables, s->light_tree, s->light_tables,
                   s->aux_img[0], s->aux_img[1], s->den_buf};
+  s->tree.release();
   s->adaptive.release();
   if (s->wf_ctr_host) hipHostFree(s->wf_ctr_host);
   for (void* p : ptrs)
@@ -243,7 +244,7 @@ int sol_scene_info(const SolScene* s, SolSceneInfo* out) {
   if (!s || !out || out->size < 8 || out->size > 4096) return sol_fail(SOL_EINVAL, "bad argument (SolSceneInfo.size?)");
   SolSceneInfo r{};
   r.size = (uint32_t)std::min<size_t>(out->size, sizeof r);
-  r.stack_bound = s->tree_depth;
+  r.stack_bound = s->tree.depth;
   r.lds_stack = SOL_LDS_STACK;
   r.spill_stack = SOL_SPILL_STACK;
   r.tree_fallback = s->tree_note.empty() ? 0u : 1u;

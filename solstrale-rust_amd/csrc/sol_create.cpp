@@ -1,5 +1,5 @@
-// sol_create.cpp -- sol_scene_create: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h),
-// the world tree (built on the GPU by sol_build.hip, or host candidates + probe), upload, work-order probe; sol_world_tree_check.
+// sol_create.cpp -- sol_scene_create as a sequence of stages: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h),
+// the world tree (built on the GPU by sol_build.hip, or host candidates - host_tree - and a probe), upload, probes; the two tree diagnostics.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -35,7 +35,6 @@ struct DeviceSplitInfo {
   float area_ratio = 1.f;
   uint32_t reinsertion_moves = 0;
   double area_before = 0., area_after = 0.;
-  float collapse_cost = 0.f;  // (SolDeviceTree) the collapse's surface-area cost of the tree
 };
 // The world's primitives as the device builder takes them (each once, in the order of their references): collected once per scene,
 // whatever the number of candidate trees.
@@ -110,7 +109,6 @@ static int device_world_tree_finish(DevicePrepared& pr, const uint32_t counts[3]
     split_info->area_ratio = dt.split_area_ratio;
     split_info->split_triangles = dt.split_triangles;
     split_info->reinsertion_moves = dt.reinsertion_moves; split_info->area_before = dt.area_before; split_info->area_after = dt.area_after;
-    split_info->collapse_cost = dt.collapse_cost;
   }
   if (split_info && split.want_boxes) {
     split_info->ref_of_dev = lay.old_of_new[0];
@@ -129,13 +127,6 @@ static int device_world_tree_finish(DevicePrepared& pr, const uint32_t counts[3]
   }
   dbg("layout adopted");
   return SOL_OK;
-}
-static int device_world_tree(const std::vector<SolBuildPrim>& prims, const Box& root_box, float box_pad, const uint32_t counts[3],
-                             const std::vector<DTri>& tris, const SolSplitOptions& split, int ploc_radius, hipStream_t stream, WideLayout& lay, uint32_t& emin,
-                             DeviceSplitInfo* split_info) {
-  DevicePrepared pr;
-  if (int rc = device_world_tree_prepare(prims, root_box, box_pad, counts, tris, split, ploc_radius, stream, pr)) return rc;
-  return device_world_tree_finish(pr, counts, split, lay, emin, split_info);
 }
 
 // A triangle's fp32 intersect record: starts at the vertex opposite the longest edge (fp32 arithmetic contract, solstrale_hip.h
@@ -265,24 +256,17 @@ static void find_background_blocks(const WideLayout& L, uint32_t emin, const DCa
         const uint32_t ni = stack.back();
         stack.pop_back();
         if (ni >= L.nodes.size() || ++visits > 4096u) { reached = true; break; }
-        const DWide& w = L.nodes[ni];
-        const float origin[3] = {w.ox, w.oy, w.oz};
-        float scale[3];
-        for (int a = 0; a < 3; ++a) { const uint32_t bits = (((w.meta >> (5 * a)) & 31u) + emin) << 23; std::memcpy(&scale[a], &bits, 4); }
-        const uint32_t imask = (w.meta >> 15) & 0x7Fu, lmask = (w.meta >> 22) & 0x7Fu;
+        const WideView v(L.nodes[ni], emin);
         for (int sl = 0; sl < SOL_WIDE_CHILDREN; ++sl) {
-          const uint32_t bit = 1u << sl;
-          if (!((imask | lmask) & bit)) continue;
-          double lo[3], hi[3];
-          for (int a = 0; a < 3; ++a) {
-            const uint32_t ql = (w.q[2 * a + (sl >> 2)] >> (8 * (sl & 3))) & 0xFFu, qh = (w.q[6 + 2 * a + (sl >> 2)] >> (8 * (sl & 3))) & 0xFFu;
-            lo[a] = (double)WideBuilder::decode(origin[a], ql, scale[a]) - margin;
-            hi[a] = (double)WideBuilder::decode(origin[a], qh, scale[a]) + margin;
-          }
+          if (!v.occupied(sl)) continue;
+          float flo[3], fhi[3];
+          v.box(sl, flo, fhi);
+          const double lo[3] = {(double)flo[0] - margin, (double)flo[1] - margin, (double)flo[2] - margin};
+          const double hi[3] = {(double)fhi[0] + margin, (double)fhi[1] + margin, (double)fhi[2] + margin};
           if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) { reached = true; break; }  // (not a box: trace)
           if (outside(lo, hi)) continue;
-          if (lmask & bit) { reached = true; break; }
-          stack.push_back(WideLayout::base_inner(w) + (uint32_t)__builtin_popcount(imask & (bit - 1u)));
+          if (v.leaf(sl)) { reached = true; break; }
+          stack.push_back(v.inner_index(sl));
         }
       }
       if (!reached) {
@@ -407,42 +391,86 @@ static int check_dfs_numbering(const SolSceneDesc& d, const TreeBuilder::DfsCoun
   return SOL_OK;
 }
 
+// ---- what sol_scene_create and the two tree diagnostics share: the world, and the ONE host pipeline from it to a device layout ----
+static bool has_environment(const SolSceneDesc& d) { return d.abi_version >= 2u && d.env_texels && d.env_width && d.env_height; }  // (a version-1 description ends before these fields)
+// The world as every entry point sees it: the fp32 box pad, the reference-shaped binary tree (TreeBuilder) and its resolved root.
+struct World {
+  const float box_pad; TreeBuilder tb;
+  uint32_t root_ref = 0, medium_depth = 0;  // medium_depth: the deepest boundary tree of a constant medium
+  Box root_box = empty_box();
+  bool needles = false; const uint32_t counts[3];  // sol_scene_has_needles (a pass over every triangle: asked once); triangles, spheres, quads
+  explicit World(const SolSceneDesc& d) : box_pad(box_pad_for(d)), tb(d, box_pad), counts{d.n_triangles, d.n_spheres, d.n_quads} {}
+  bool single() const { return SOL_REF_KIND(root_ref) != SOL_REF_NODE; }  // the world is ONE primitive
+  uint32_t stack_dwords(const WideLayout& l) const { return 2u * l.depth + medium_depth + 2; }  // (a wide level keeps at most one sibling group of two dwords)
+};
+static const uint32_t STACK_LIMIT = SOL_LDS_STACK + SOL_SPILL_STACK;
+// A finished host-built world tree: the binary tree it was collapsed from (`sah`: a rebuild; null: the reference's topology), the
+// collapse with its area estimate (wb->cost()), the device layout.
+struct HostTree { std::unique_ptr<SahBuilder> sah; std::unique_ptr<WideBuilder> wb; WideLayout lay; uint32_t emin = 1; };
+static const char* const COLLECT_ERROR = "the world's primitives cannot be collected (non-finite box or fewer than two)";
+// The host pipeline, written once: collect and binned-SAH rebuild (`bins` > 0; 0 = the reference's topology as resolved; primitives a
+// caller has collected already come in t.sah), collapse into wide nodes under the three SolDevOverrides tunables, device layout; a world of
+// one primitive becomes a root with a single child. Returns "" or why there is no tree (t.wb->range_error: the exponent range).
+static std::string host_tree(const World& w, int bins, const SolDevOverrides& ovr, HostTree& t) {
+  const std::vector<DNode>* bin = &w.tb.nodes;
+  uint32_t bin_root = w.root_ref;
+  if (bins && !w.single()) {
+    if (!t.sah) { t.sah.reset(new SahBuilder()); if (!t.sah->collect(w.tb.nodes, w.root_ref)) return COLLECT_ERROR; }
+    Box b;
+    t.sah->BINS = bins; bin_root = t.sah->build(0, t.sah->prims.size(), 0, b); bin = &t.sah->nodes;
+  }
+  t.wb.reset(new WideBuilder(*bin, w.box_pad));
+  t.wb->dp_collapse = !ovr.greedy_collapse; t.wb->slot_by_assignment = !ovr.octant_slots; t.wb->NODE_COST = ovr.node_cost;
+  t.wb->set_exponent_range(w.root_box);
+  const uint32_t wide_root = w.single() ? t.wb->build_single(w.root_ref, w.root_box) : t.wb->build(SOL_REF_INDEX(bin_root), 0);
+  if (t.wb->range_error) return "exponent range";
+  if (!t.lay.run(t.wb->out, SOL_REF_INDEX(wide_root), t.wb->emin, w.counts[0], w.counts[1], w.counts[2])) return t.lay.error;
+  t.emin = t.wb->emin;
+  return "";
+}
+// The diagnostics' world: resolved and numbered as sol_scene_create does it, a tree (no single primitive), its primitives collected (`prims`: a copy,
+// before a rebuild reorders them) and the host-built tree `use_sah` names: 0 the reference's topology, 1 sixteen bins, n > 1 that many (at most MAX_BINS), < 0 none.
+static int diag_world(const SolSceneDesc& d, int use_sah, const SolDevOverrides& ovr, World& w, HostTree& t, std::vector<SahBuilder::Prim>* prims) {
+  if (!w.tb.resolve(d.root, 0, w.root_ref, w.root_box)) return sol_fail(SOL_EINVAL, "world: %s", w.tb.error.c_str());
+  if (int rc = check_dfs_numbering(d, w.tb.dfs)) return rc;
+  if (w.single()) return sol_fail(SOL_EINVAL, "the world is a single primitive: no tree");
+  t.sah.reset(new SahBuilder());
+  if (!t.sah->collect(w.tb.nodes, w.root_ref)) return sol_fail(SOL_EINVAL, "%s", COLLECT_ERROR);
+  if (prims) *prims = t.sah->prims;
+  if (use_sah < 0) return SOL_OK;
+  const std::string err = host_tree(w, use_sah > 1 ? std::min((int)SahBuilder::MAX_BINS, use_sah) : use_sah ? 16 : 0, ovr, t);
+  return err.empty() ? SOL_OK : sol_fail(SOL_EINVAL, "wide tree layout: %s", err.c_str());
+}
 static int world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* out) {
   if (!d || !out) return sol_fail(SOL_EINVAL, "null argument");
   std::memset(out, 0, sizeof *out);
   const SolDevOverrides ovr = sol_dev_overrides();
-  const float box_pad = box_pad_for(*d);
-  TreeBuilder tb(*d, box_pad);
-  uint32_t root_ref;
-  Box root_box;
-  if (!tb.resolve(d->root, 0, root_ref, root_box)) return sol_fail(SOL_EINVAL, "world: %s", tb.error.c_str());
-  if (int rc = check_dfs_numbering(*d, tb.dfs)) return rc;
-  if (SOL_REF_KIND(root_ref) != SOL_REF_NODE) return sol_fail(SOL_EINVAL, "the world is a single primitive: no tree");
-  SahBuilder sah;
-  if (!sah.collect(tb.nodes, root_ref)) return sol_fail(SOL_EINVAL, "the world's primitives cannot be collected (non-finite box or fewer than two)");
+  World w(*d);
+  HostTree tree;
+  std::vector<SahBuilder::Prim> prims;
+  if (int rc = diag_world(*d, use_sah, ovr, w, tree, &prims)) return rc;
   std::map<uint32_t, int> expected;  // primitive reference -> multiplicity
   std::map<uint32_t, Box> prim_box;
-  for (const auto& p : sah.prims) { expected[p.ref]++; prim_box[p.ref] = p.box; }
+  for (const auto& p : prims) { expected[p.ref]++; prim_box[p.ref] = p.box; }
   if (use_sah < 0)
     for (auto& e : expected) e.second = 1;  // (the device build keeps one copy of a shared sub-tree's primitives)
-  out->n_primitives = (uint32_t)sah.prims.size();
+  out->n_primitives = (uint32_t)prims.size();
   if (use_sah < 0) out->n_primitives = (uint32_t)expected.size();
-  WideLayout lay;
-  uint32_t emin_used = 1;
-  double inner_area = 0., leaf_area = 0.;
+  const WideLayout& lay = tree.lay;
   DeviceSplitInfo split;
   std::vector<DTri> dev_tris;
   if (use_sah < 0) {  // the tree sol_build.hip builds on the GPU, checked like the host-built ones
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
     HIP_TRY(hipSetDevice(0));
-    const uint32_t counts[3] = {d->n_triangles, d->n_spheres, d->n_quads};
     dev_tris = cast_triangles(*d);
     SolSplitOptions sp = split_options(ovr, nullptr);
     sp.want_boxes = true;
     std::vector<SolBuildPrim> build_prims;
-    int rc = collect_build_prims(tb.nodes, root_ref, root_box, build_prims);
-    if (!rc) rc = device_world_tree(build_prims, root_box, box_pad, counts, dev_tris, sp, ovr.ploc_radius, nullptr, lay, emin_used, &split);
+    int rc = collect_build_prims(w.tb.nodes, w.root_ref, w.root_box, build_prims);
+    DevicePrepared pr;
+    if (!rc) rc = device_world_tree_prepare(build_prims, w.root_box, w.box_pad, w.counts, dev_tris, sp, ovr.ploc_radius, nullptr, pr);
+    if (!rc) rc = device_world_tree_finish(pr, w.counts, sp, tree.lay, tree.emin, &split);
     if (rc) return rc;
     // a split triangle has several references; each is expected once
     for (uint32_t e = d->n_triangles; e < split.tri_of_ref.size(); ++e) {
@@ -452,55 +480,35 @@ static int world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* ou
     out->n_extra_references = (uint32_t)(split.tri_of_ref.size() - d->n_triangles);
     out->n_split_triangles = split.split_triangles;
   } else {
-    uint32_t bin_root = root_ref;
-    if (use_sah) { Box b; sah.BINS = use_sah > 1 ? std::min((int)SahBuilder::MAX_BINS, use_sah) : 16; bin_root = sah.build(0, sah.prims.size(), 0, b); }
-    WideBuilder wb(use_sah ? sah.nodes : tb.nodes, box_pad);
-    wb.dp_collapse = !ovr.greedy_collapse;
-    wb.slot_by_assignment = !ovr.octant_slots;
-    wb.NODE_COST = ovr.node_cost;
-    wb.set_exponent_range(root_box);
-    const uint32_t xroot = wb.build(SOL_REF_INDEX(bin_root), 0);
-    if (wb.range_error || !lay.run(wb.out, SOL_REF_INDEX(xroot), wb.emin, d->n_triangles, d->n_spheres, d->n_quads))
-      return sol_fail(SOL_EINVAL, "wide tree layout: %s", wb.range_error ? "exponent range" : lay.error.c_str());
-    emin_used = wb.emin;
-    inner_area = wb.inner_area; leaf_area = wb.leaf_area;
+    out->inner_area = tree.wb->inner_area; out->leaf_area = tree.wb->leaf_area;
   }
   out->n_wide = (uint32_t)lay.nodes.size();
   out->depth = lay.depth;
-  out->inner_area = inner_area; out->leaf_area = leaf_area;
   std::map<uint32_t, int> found;
-  // The DEVICE form is what gets checked, decoded exactly as the kernel decodes it (sol_trace.h): 5-bit exponents over emin,
-  // implicit child addresses, permuted primitive arrays (mapped back to the caller's indices for the comparison).
+  // The DEVICE form is what gets checked, decoded exactly as the kernel decodes it (WideView), permuted primitive arrays mapped back
+  // to the caller's indices for the comparison.
   const uint32_t ref_kind_of[4] = {SOL_REF_NONE, SOL_REF_TRIANGLE, SOL_REF_SPHERE, SOL_REF_QUAD};
   // returns the union of the padded primitive boxes below node `ni`
   std::function<Box(uint32_t, uint32_t)> walk = [&](uint32_t ni, uint32_t depth) -> Box {
     Box all = empty_box();
     if (depth > 4096 || ni >= lay.nodes.size()) { out->leaf_mismatches++; return all; }
-    const DWide& w = lay.nodes[ni];
-    const float origin[3] = {w.ox, w.oy, w.oz};
-    float scale[3];
-    for (int a = 0; a < 3; ++a) { uint32_t bits = (((w.meta >> (5 * a)) & 31u) + emin_used) << 23; std::memcpy(&scale[a], &bits, 4); }
-    const uint32_t imask = (w.meta >> 15) & 0x7Fu, lmask = (w.meta >> 22) & 0x7Fu, kind = (w.meta >> 29) & 3u;
-    if (imask & lmask) out->bad_empty_slots++;
+    const WideView v(lay.nodes[ni], tree.emin);
+    if (v.imask & v.lmask) out->bad_empty_slots++;
     uint32_t n_children = 0;
     for (int s = 0; s < SOL_WIDE_CHILDREN; ++s) {
-      uint32_t ql[3], qh[3];
-      for (int a = 0; a < 3; ++a) {
-        ql[a] = (w.q[2 * a + (s >> 2)] >> (8 * (s & 3))) & 0xFFu;
-        qh[a] = (w.q[6 + 2 * a + (s >> 2)] >> (8 * (s & 3))) & 0xFFu;
-      }
-      const uint32_t bit = 1u << s, below_mask = bit - 1u;
-      if (!((imask | lmask) & bit)) {  // an empty slot must have an inverted box (never hit)
+      if (!v.occupied(s)) {  // an empty slot must have an inverted box (never hit)
+        uint32_t ql[3], qh[3];
+        v.plane_bytes(s, ql, qh);
         if (!(ql[0] == 255u && qh[0] == 0u && ql[1] == 255u && qh[1] == 0u && ql[2] == 255u && qh[2] == 0u)) out->bad_empty_slots++;
         continue;
       }
       n_children++;
       Box below;
-      if (imask & bit) {
-        below = walk(WideLayout::base_inner(w) + (uint32_t)__builtin_popcount(imask & below_mask), depth + 1);
+      if (v.inner(s)) {
+        below = walk(v.inner_index(s), depth + 1);
       } else {
-        const uint32_t idx = WideLayout::base_prim(w) + (uint32_t)__builtin_popcount(lmask & below_mask);
-        uint32_t ref = kind == SOL_LEAF_REFS ? (idx < lay.leaf_refs.size() ? lay.leaf_refs[idx] : 0u) : SOL_MAKE_REF(ref_kind_of[kind], idx);
+        const uint32_t idx = v.prim_index(s);
+        uint32_t ref = v.kind == SOL_LEAF_REFS ? (idx < lay.leaf_refs.size() ? lay.leaf_refs[idx] : 0u) : SOL_MAKE_REF(ref_kind_of[v.kind], idx);
         const int a = WideLayout::arr(SOL_REF_KIND(ref));
         const uint32_t dev_idx = SOL_REF_INDEX(ref);  // (index into the permuted device array; for a listed reference too)
         if (a >= 0) ref = SOL_REF_INDEX(ref) < lay.old_of_new[a].size() ? SOL_MAKE_REF(SOL_REF_KIND(ref), lay.old_of_new[a][SOL_REF_INDEX(ref)]) : 0u;
@@ -514,11 +522,11 @@ static int world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* ou
           if ((size_t)e * 6 + 6 <= split.ref_box.size()) std::memcpy(below.v, &split.ref_box[(size_t)e * 6], 24);
         }
       }
+      float lo[3], hi[3];
+      v.box(s, lo, hi);
       bool ok = true;
-      for (int a = 0; a < 3; ++a) {
-        const float lo = WideBuilder::decode(origin[a], ql[a], scale[a]), hi = WideBuilder::decode(origin[a], qh[a], scale[a]);
-        if (below.v[2 * a] <= below.v[2 * a + 1] && !(lo <= below.v[2 * a] && hi >= below.v[2 * a + 1])) ok = false;
-      }
+      for (int a = 0; a < 3; ++a)
+        if (below.v[2 * a] <= below.v[2 * a + 1] && !(lo[a] <= below.v[2 * a] && hi[a] >= below.v[2 * a + 1])) ok = false;
       if (!ok) out->box_violations++;
       SahBuilder::grow(all, below);
     }
@@ -582,65 +590,28 @@ static int world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* ou
   return SOL_OK;
 }
 
-extern "C" {
-
-// The struct has no size field of its own and grew in round 4 (the three split counters): the plain entry point keeps writing the FIRST
-// LAYOUT (through leaf_area, SOL_TREE_CHECK_V1_BYTES) so that a binding compiled against that header is not overrun; callers of this
-// header pass their struct's size to sol_world_tree_check_ex and get every field that fits.
-int sol_world_tree_check_ex(const SolSceneDesc* d, int use_sah, void* out, size_t out_size) {
-  if (!out || out_size < SOL_TREE_CHECK_V1_BYTES) return sol_fail(SOL_EINVAL, "sol_world_tree_check_ex: out is null or smaller than the first layout (%d bytes)", (int)SOL_TREE_CHECK_V1_BYTES);
-  SolTreeCheck full{};  // (zero where world_tree_check refuses before filling it)
-  const int rc = world_tree_check(d, use_sah, &full);
-  std::memset(out, 0, out_size);
-  std::memcpy(out, &full, std::min(out_size, sizeof full));
-  return rc;
-}
-int sol_world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* out) { return sol_world_tree_check_ex(d, use_sah, out, SOL_TREE_CHECK_V1_BYTES); }
-
-// Diagnostic, host only: the background blocks sol_scene_create would find with the host-built tree `use_sah` names (as in
-// sol_world_tree_check; the proof does not depend on which tree carries it, the count may).
-int sol_background_blocks(const SolSceneDesc* d, int use_sah, uint8_t* flags, size_t n_flags, uint32_t* n_found) {
-  if (!d || !n_found || use_sah < 0) return sol_fail(SOL_EINVAL, "bad argument");
-  *n_found = 0;
-  if (d->width < 2 || d->height < 2 || (uint64_t)d->width * d->height > 0x3FFFFFFFull) return sol_fail(SOL_EINVAL, "bad image size %ux%u", d->width, d->height);
-  const uint32_t nb = ((d->width + SOL_TILE - 1) / SOL_TILE) * ((d->height + SOL_TILE - 1) / SOL_TILE);
-  if (flags && n_flags < nb) return sol_fail(SOL_EINVAL, "%zu flags for %u blocks", n_flags, nb);
-  const SolDevOverrides ovr = sol_dev_overrides();
-  const float box_pad = box_pad_for(*d);
-  TreeBuilder tb(*d, box_pad);
-  uint32_t root_ref;
-  Box root_box;
-  if (!tb.resolve(d->root, 0, root_ref, root_box)) return sol_fail(SOL_EINVAL, "world: %s", tb.error.c_str());
-  if (int rc = check_dfs_numbering(*d, tb.dfs)) return rc;
-  if (SOL_REF_KIND(root_ref) != SOL_REF_NODE) return sol_fail(SOL_EINVAL, "the world is a single primitive: no tree");
-  SahBuilder sah;
-  if (!sah.collect(tb.nodes, root_ref)) return sol_fail(SOL_EINVAL, "the world's primitives cannot be collected (non-finite box or fewer than two)");
-  uint32_t bin_root = root_ref;
-  if (use_sah) { Box b; sah.BINS = use_sah > 1 ? std::min((int)SahBuilder::MAX_BINS, use_sah) : 16; bin_root = sah.build(0, sah.prims.size(), 0, b); }
-  WideBuilder wb(use_sah ? sah.nodes : tb.nodes, box_pad);
-  wb.dp_collapse = !ovr.greedy_collapse;
-  wb.slot_by_assignment = !ovr.octant_slots;
-  wb.NODE_COST = ovr.node_cost;
-  wb.set_exponent_range(root_box);
-  const uint32_t xroot = wb.build(SOL_REF_INDEX(bin_root), 0);
-  WideLayout lay;
-  if (wb.range_error || !lay.run(wb.out, SOL_REF_INDEX(xroot), wb.emin, d->n_triangles, d->n_spheres, d->n_quads))
-    return sol_fail(SOL_EINVAL, "wide tree layout: %s", wb.range_error ? "exponent range" : lay.error.c_str());
-  const bool has_env = d->abi_version >= 2u && d->env_texels && d->env_width && d->env_height;
-  std::vector<uint8_t> f(nb, 0);
-  uint32_t pixels = 0;
-  if (!has_env) find_background_blocks(lay, wb.emin, cast_camera(d->camera), d->width, d->height, 64.0 * (double)box_pad, f, *n_found, pixels);
-  if (flags) std::memcpy(flags, f.data(), nb);
-  return SOL_OK;
-}
-
-int sol_scene_create(const SolSceneDesc* d, int device, SolScene** out) { return sol_scene_create_ex(d, device, nullptr, out); }
-
-int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOptions* opt_in, SolScene** out) {
-  if (!d || !out) return sol_fail(SOL_EINVAL, "null argument");
-  *out = nullptr;
-  const SolDevOverrides ovr = sol_dev_overrides();
-  SolCreateOptions opt{};
+// ---- sol_scene_create: the stages, in the order sol_scene_create_ex calls them ----
+static double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+// What every stage may read: the description, the developer overrides (parsed once) and the options in force, SOL_VERBOSE's clock.
+struct CreateCtx {
+  const SolSceneDesc& d; const SolDevOverrides ovr; SolCreateOptions opt{}; bool has_env = false;
+  const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+  void say(const char* what) const { if (ovr.verbose) std::fprintf(stderr, "[solstrale] create: %s at %.1f ms\n", what, 1e3 * seconds_since(t_begin)); }
+};
+// The description in the device's record types, in the caller's order.
+struct HostRecords {
+  std::vector<DTex> texs; std::vector<DMat> mats; std::vector<DTri> tris; std::vector<DTriShade> tshade; std::vector<DQuad> quads;
+  std::vector<DSphere> spheres; std::vector<DMedium> mediums; std::vector<uint32_t> lights;
+};
+// A candidate world tree: a host-built one (HostTree) or a device-built layout (lay and emin alone, `built`: what its build did), and
+// its device arrays once uploaded - released with the candidate unless the scene has taken them.
+struct TreeCand : HostTree { std::string name; uint32_t depth = 0; double cost = 0.; DeviceSplitInfo built; DevTree dev; };
+struct SceneDestroy { void operator()(SolScene* s) const { sol_scene_destroy(s); } };
+using ScenePtr = std::unique_ptr<SolScene, SceneDestroy>;  // (a stage that fails leaves nothing of the scene behind)
+// 1. options and the description's header
+static int check_options_and_header(CreateCtx& c, const SolCreateOptions* opt_in) {
+  const SolSceneDesc* d = &c.d;
+  SolCreateOptions& opt = c.opt;
   if (opt_in) {
     if (opt_in->size < 8 || opt_in->size > 4096) return sol_fail(SOL_EINVAL, "SolCreateOptions.size %u", opt_in->size);
     std::memcpy(&opt, opt_in, std::min<size_t>(opt_in->size, sizeof opt));
@@ -648,11 +619,9 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
   if (opt.world_tree < SOL_TREE_AUTO || opt.world_tree > SOL_TREE_HOST_PROBE) return sol_fail(SOL_EINVAL, "bad world_tree option %d", opt.world_tree);
   if (opt.split_percent > 1000 || opt.reinsertion_rounds > 1024)  // (a typo must not become a build of hours: ten times the references, a thousand rounds)
     return sol_fail(SOL_EINVAL, "SolCreateOptions: split_percent %d (at most 1000) / reinsertion_rounds %d (at most 1024)", opt.split_percent, opt.reinsertion_rounds);
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto seconds_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); };
   if (d->abi_version != SOL_ABI_VERSION && d->abi_version != 1u) return sol_fail(SOL_EINVAL, "abi_version %u, expected %u (or 1)", d->abi_version, SOL_ABI_VERSION);
-  const bool has_env = d->abi_version >= 2u && d->env_texels && d->env_width && d->env_height;  // (a version-1 description ends before these fields)
-  if (has_env && ((uint64_t)d->env_width * d->env_height > (1ull << 28) || !std::isfinite(d->env_scale))) return sol_fail(SOL_EINVAL, "bad environment map");
+  c.has_env = has_environment(*d);
+  if (c.has_env && ((uint64_t)d->env_width * d->env_height > (1ull << 28) || !std::isfinite(d->env_scale))) return sol_fail(SOL_EINVAL, "bad environment map");
   if (d->width < 2 || d->height < 2 || (uint64_t)d->width * d->height > 0x3FFFFFFFull) return sol_fail(SOL_EINVAL, "bad image size %ux%u", d->width, d->height);
   if (d->shader_kind > SOL_SHADER_SIMPLE) return sol_fail(SOL_EINVAL, "bad shader kind %u", d->shader_kind);
   if ((d->n_nodes && !d->nodes) || (d->n_spheres && !d->spheres) || (d->n_quads && !d->quads) ||
@@ -662,9 +631,12 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
   // Renderer::new: "Scene should have at least one light" (src/renderer/mod.rs:143-147)
   if (d->n_lights == 0) return sol_fail(SOL_ENOLIGHT, "Scene should have at least one light");
   if (d->n_texel_bytes > 0xFFFFFFF0ull) return sol_fail(SOL_EINVAL, "more than 4 GiB of texels");
-
-  // ---- materials / textures ----
-  std::vector<DTex> texs(d->n_textures);
+  return SOL_OK;
+}
+// 2. textures, materials and the NEEDS_UV closure
+static int cast_materials(const SolSceneDesc* d, HostRecords& r) {
+  std::vector<DTex>& texs = r.texs;
+  texs.resize(d->n_textures);
   for (uint32_t i = 0; i < d->n_textures; ++i) {
     const SolTexture& t = d->textures[i];
     DTex& o = texs[i];
@@ -683,7 +655,8 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
     }
   }
   auto tex_ok = [&](int32_t id, bool optional) { return (optional && id < 0) || (id >= 0 && (uint32_t)id < d->n_textures); };
-  std::vector<DMat> mats(d->n_materials);
+  std::vector<DMat>& mats = r.mats;
+  mats.resize(d->n_materials);
   for (uint32_t i = 0; i < d->n_materials; ++i) {
     const SolMaterial& m = d->materials[i];
     DMat& o = mats[i];
@@ -719,75 +692,76 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
       else need = (o.albedo >= 0 && texs[o.albedo].kind == SOL_TEX_IMAGE) || (o.normal >= 0 && texs[o.normal].kind == SOL_TEX_IMAGE);
       if (need) o.flags |= DMAT_NEEDS_UV;
     }
-  auto mat_ok = [&](int32_t id) { return id >= 0 && (uint32_t)id < d->n_materials; };
+  return SOL_OK;
+}
+static bool mat_ok(const SolSceneDesc* d, int32_t id) { return id >= 0 && (uint32_t)id < d->n_materials; }
 
-  // ---- primitives (plain casts) ----
-  std::vector<DTri> tris(d->n_triangles);
-  std::vector<DTriShade> tshade(d->n_triangles);
-  {
-    // (a million triangles are 0.03 s of casts on one core: split over a few threads above 64 k; every triangle is independent)
-    auto cast_range = [&](uint32_t i0, uint32_t i1, int64_t* bad) {
-      for (uint32_t i = i0; i < i1; ++i) {
-        const SolTriangle& t = d->triangles[i];
-        if (!mat_ok(t.material)) { if (*bad < 0) *bad = i; continue; }
-        int uo[3];
-        cast_triangle(t, false, tris[i], uo);
-        const float* uvs[3] = {t.uv0, t.uv1, t.uv2};
-        DTriShade& s = tshade[i];
-        s.nx = (float)t.normal[0]; s.ny = (float)t.normal[1]; s.nz = (float)t.normal[2]; s.mat = t.material;
-        s.tx = (float)t.tangent[0]; s.ty = (float)t.tangent[1]; s.tz = (float)t.tangent[2];
-        s.bx = (float)t.bi_tangent[0]; s.by = (float)t.bi_tangent[1]; s.bz = (float)t.bi_tangent[2];
-        s.u0 = uvs[uo[0]][0]; s.v0 = uvs[uo[0]][1]; s.u1 = uvs[uo[1]][0]; s.v1 = uvs[uo[1]][1]; s.u2 = uvs[uo[2]][0]; s.v2 = uvs[uo[2]][1];
-      }
-    };
-    const uint32_t nt = d->n_triangles;
-    const uint32_t n_thr = nt >= 65536u ? std::min<uint32_t>(8u, std::max<uint32_t>(1u, std::thread::hardware_concurrency())) : 1u;
-    std::vector<int64_t> bad(n_thr, -1);
-    std::vector<std::thread> pool;
-    for (uint32_t k = 1; k < n_thr; ++k) pool.emplace_back(cast_range, (uint32_t)((uint64_t)nt * k / n_thr), (uint32_t)((uint64_t)nt * (k + 1) / n_thr), &bad[k]);
-    cast_range(0, (uint32_t)((uint64_t)nt / n_thr), &bad[0]);
-    for (auto& th : pool) th.join();
-    for (int64_t b : bad)
-      if (b >= 0) return sol_fail(SOL_EINVAL, "triangle %u: bad material", (uint32_t)b);
-  }
-  std::vector<DQuad> quads(d->n_quads);
+// 3. primitives (plain casts)
+static int cast_primitives(const SolSceneDesc* d, HostRecords& r) {
+  std::vector<DTri>& tris = r.tris;
+  std::vector<DTriShade>& tshade = r.tshade;
+  tris.resize(d->n_triangles); tshade.resize(d->n_triangles);
+  // (a million triangles are 0.03 s of casts on one core: split over a few threads above 64 k; every triangle is independent)
+  auto cast_range = [&](uint32_t i0, uint32_t i1, int64_t* bad) {
+    for (uint32_t i = i0; i < i1; ++i) {
+      const SolTriangle& t = d->triangles[i];
+      if (!mat_ok(d, t.material)) { if (*bad < 0) *bad = i; continue; }
+      int uo[3];
+      cast_triangle(t, false, tris[i], uo);
+      const float* uvs[3] = {t.uv0, t.uv1, t.uv2};
+      DTriShade& s = tshade[i];
+      s.nx = (float)t.normal[0]; s.ny = (float)t.normal[1]; s.nz = (float)t.normal[2]; s.mat = t.material;
+      s.tx = (float)t.tangent[0]; s.ty = (float)t.tangent[1]; s.tz = (float)t.tangent[2];
+      s.bx = (float)t.bi_tangent[0]; s.by = (float)t.bi_tangent[1]; s.bz = (float)t.bi_tangent[2];
+      s.u0 = uvs[uo[0]][0]; s.v0 = uvs[uo[0]][1]; s.u1 = uvs[uo[1]][0]; s.v1 = uvs[uo[1]][1]; s.u2 = uvs[uo[2]][0]; s.v2 = uvs[uo[2]][1];
+    }
+  };
+  const uint32_t nt = d->n_triangles;
+  const uint32_t n_thr = nt >= 65536u ? std::min<uint32_t>(8u, std::max<uint32_t>(1u, std::thread::hardware_concurrency())) : 1u;
+  std::vector<int64_t> bad(n_thr, -1);
+  std::vector<std::thread> pool;
+  for (uint32_t k = 1; k < n_thr; ++k) pool.emplace_back(cast_range, (uint32_t)((uint64_t)nt * k / n_thr), (uint32_t)((uint64_t)nt * (k + 1) / n_thr), &bad[k]);
+  cast_range(0, (uint32_t)((uint64_t)nt / n_thr), &bad[0]);
+  for (auto& th : pool) th.join();
+  for (int64_t b : bad)
+    if (b >= 0) return sol_fail(SOL_EINVAL, "triangle %u: bad material", (uint32_t)b);
+  r.quads.resize(d->n_quads);
   for (uint32_t i = 0; i < d->n_quads; ++i) {
     const SolQuad& q = d->quads[i];
-    if (!mat_ok(q.material)) return sol_fail(SOL_EINVAL, "quad %u: bad material", i);
-    DQuad& o = quads[i];
+    if (!mat_ok(d, q.material)) return sol_fail(SOL_EINVAL, "quad %u: bad material", i);
+    DQuad& o = r.quads[i];
     o.nx = (float)q.normal[0]; o.ny = (float)q.normal[1]; o.nz = (float)q.normal[2]; o.d = (float)q.d;
     o.qx = (float)q.q[0]; o.qy = (float)q.q[1]; o.qz = (float)q.q[2]; o.dfs = q.dfs_index;
     o.wx = (float)q.w[0]; o.wy = (float)q.w[1]; o.wz = (float)q.w[2]; o.mat = q.material;
     o.ux = (float)q.u[0]; o.uy = (float)q.u[1]; o.uz = (float)q.u[2]; o.area = (float)q.area;
     o.vx = (float)q.v[0]; o.vy = (float)q.v[1]; o.vz = (float)q.v[2]; o.pad = 0.f;
   }
-  std::vector<DSphere> spheres(d->n_spheres);
+  r.spheres.resize(d->n_spheres);
   for (uint32_t i = 0; i < d->n_spheres; ++i) {
     const SolSphere& s = d->spheres[i];
-    if (!mat_ok(s.material)) return sol_fail(SOL_EINVAL, "sphere %u: bad material", i);
-    DSphere& o = spheres[i];
+    if (!mat_ok(d, s.material)) return sol_fail(SOL_EINVAL, "sphere %u: bad material", i);
+    DSphere& o = r.spheres[i];
     o.cx = (float)s.center[0]; o.cy = (float)s.center[1]; o.cz = (float)s.center[2]; o.radius = std::fabs((float)s.radius);  // |r|: the reference uses r^2 and a min/max box only (sphere.rs:26-28,68), the fp32 rules of sol_trace.h / sol_shade.h use r itself
     o.dfs = s.dfs_index; o.mat = s.material; o.pad0 = o.pad1 = 0;
   }
-
-  if (sol_dev_overrides().verbose) std::fprintf(stderr, "[solstrale] create: records cast at %.1f ms\n", 1e3 * seconds_since(t_begin));
-  // ---- tree ----
-  const float box_pad = box_pad_for(*d);
-  const bool scene_has_needles = sol_scene_has_needles(d) != 0;  // (a pass over every triangle: asked once more here, not once per use)
+  return SOL_OK;
+}
+// 4. the world: box pad and needles, the 2^38 bound, the reference tree resolved, the constant mediums, the dfs_index numbering
+static int resolve_world(const CreateCtx& c, World& w, HostRecords& r) {
+  const SolSceneDesc* d = &c.d;
+  TreeBuilder& tb = w.tb;
+  w.needles = sol_scene_has_needles(d) != 0;
   // (the 7-wide node test's plane parameters must not overflow: sol_trace.h, wide_node_test; pad = largest |coordinate| * 2^-20)
-  if (!(box_pad * 1048576.0f <= 2.7487791e11f)) return sol_fail(SOL_EINVAL, "the scene's coordinates reach beyond 2^38 (%g): not supported by the fp32 search", (double)box_pad * 1048576.0);
-  TreeBuilder tb(*d, box_pad);
-  uint32_t root_ref;
-  Box root_box;
-  if (!tb.resolve(d->root, 0, root_ref, root_box)) return sol_fail(SOL_EINVAL, "world: %s", tb.error.c_str());
-  if (SOL_REF_KIND(root_ref) == SOL_REF_NONE) return sol_fail(SOL_EINVAL, "world is empty");
+  if (!(w.box_pad * 1048576.0f <= 2.7487791e11f)) return sol_fail(SOL_EINVAL, "the scene's coordinates reach beyond 2^38 (%g): not supported by the fp32 search", (double)w.box_pad * 1048576.0);
+  if (!tb.resolve(d->root, 0, w.root_ref, w.root_box)) return sol_fail(SOL_EINVAL, "world: %s", tb.error.c_str());
+  if (SOL_REF_KIND(w.root_ref) == SOL_REF_NONE) return sol_fail(SOL_EINVAL, "world is empty");
   const TreeBuilder::DfsCount world_dfs = tb.dfs;  // (the boundaries' resolves below count on)
-  if (sol_dev_overrides().verbose) std::fprintf(stderr, "[solstrale] create: reference tree resolved at %.1f ms\n", 1e3 * seconds_since(t_begin));
-  std::vector<DMedium> mediums(d->n_mediums);
-  uint32_t medium_depth = 0;
+  c.say("reference tree resolved");
+  std::vector<DMedium>& mediums = r.mediums;
+  mediums.resize(d->n_mediums);
   for (uint32_t i = 0; i < d->n_mediums; ++i) {
     const SolMedium& m = d->mediums[i];
-    if (!mat_ok(m.material)) return sol_fail(SOL_EINVAL, "medium %u: bad material", i);
+    if (!mat_ok(d, m.material)) return sol_fail(SOL_EINVAL, "medium %u: bad material", i);
     if (i >= 0x1000u) return sol_fail(SOL_EINVAL, "more than 4096 constant mediums");
     DMedium& o = mediums[i];
     std::memset(&o, 0, sizeof o);
@@ -796,7 +770,7 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
     Box bb;
     if (!tb.resolve(m.boundary, 0, bref, bb)) return sol_fail(SOL_EINVAL, "medium %u boundary: %s", i, tb.error.c_str());
     if (SOL_REF_KIND(bref) == SOL_REF_MEDIUM || SOL_REF_KIND(bref) == SOL_REF_NONE) return sol_fail(SOL_EINVAL, "medium %u: unsupported boundary", i);
-    medium_depth = std::max(medium_depth, tb.max_depth);
+    w.medium_depth = std::max(w.medium_depth, tb.max_depth);
     o.boundary = bref; o.mat = m.material; o.nid = (float)m.negative_inverse_density; o.dfs = m.dfs_index;
     o.bxmin = bb.v[0]; o.bxmax = bb.v[1]; o.bymin = bb.v[2]; o.bymax = bb.v[3]; o.bzmin = bb.v[4]; o.bzmax = bb.v[5];
   }
@@ -804,317 +778,258 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
   for (uint32_t i = 0; i < d->n_mediums; ++i) {
     std::vector<uint32_t> stk{mediums[i].boundary};
     while (!stk.empty()) {
-      uint32_t r = stk.back(); stk.pop_back();
-      if (SOL_REF_KIND(r) == SOL_REF_MEDIUM) return sol_fail(SOL_EINVAL, "medium %u: nested ConstantMedium in a boundary is unsupported", i);
-      if (SOL_REF_KIND(r) == SOL_REF_NODE) { stk.push_back(tb.nodes[SOL_REF_INDEX(r)].left); stk.push_back(tb.nodes[SOL_REF_INDEX(r)].right); }
+      uint32_t ref = stk.back(); stk.pop_back();
+      if (SOL_REF_KIND(ref) == SOL_REF_MEDIUM) return sol_fail(SOL_EINVAL, "medium %u: nested ConstantMedium in a boundary is unsupported", i);
+      if (SOL_REF_KIND(ref) == SOL_REF_NODE) { stk.push_back(tb.nodes[SOL_REF_INDEX(ref)].left); stk.push_back(tb.nodes[SOL_REF_INDEX(ref)].right); }
     }
   }
-  if (int rc = check_dfs_numbering(*d, world_dfs)) return rc;  // (after the boundaries: their references are known good here)
-  // 7-wide tree of the world. Candidates: the reference's topology collapsed, and binned-SAH rebuilds over the same primitives
-  // with 8, 16 and 64 bins (how well the binary splits line up with the wide collapse varies with the bin count: with the
-  // first, 8-wide layout C2 visited 9.8 / 12.2 / 11.4 nodes per ray at 8 / 16 / 64 bins and 11.2 on the reference's
-  // topology; C3 13.3 / 13.0 / 12.9 vs 14.4). A counted probe render on the device picks one (below).
-  // SolCreateOptions.world_tree (or SOL_BVH=ref | sah (16 bins) | sah8 | sah16 | sah64) forces a candidate.
-  struct TreeCand {
-    std::string name;
-    std::unique_ptr<SahBuilder> sah;
-    std::unique_ptr<WideBuilder> wb;
-    WideLayout lay;
-    uint32_t depth = 0, emin = 1;
-    DevTree dev;
-    double cost = 0.;
-  };
-  std::vector<TreeCand> cands;
-  // stack entries (dwords): a wide level keeps at most one sibling group of two dwords
-  auto depth_of = [&](const WideLayout& l) { return 2u * l.depth + medium_depth + 2; };
-  const uint32_t stack_limit = SOL_LDS_STACK + SOL_SPILL_STACK;
-  // AUTO = the device build: as good a tree as the probed host candidates (node visits per ray, host probe / device: C2 11.0 /
-  // 10.9, C3 12.8 / 13.0, C5 6.8 / 6.9) in a sixth to an eighth of the time (sol_scene_create, C3: 0.40 s -> 0.06 s, C5 2.2 s -> 0.3 s)
-  static const char* const tree_names[] = {"device", "ref", "sah8", "sah16", "sah64", "device", ""};
-  std::string want = !ovr.bvh.empty() ? ovr.bvh : tree_names[opt.world_tree];  // (SOL_BVH: developer override of SolCreateOptions.world_tree)
-  if (want == "host") want = "";  // all host candidates + the probe
-  auto tune = [&](WideBuilder& wb) { wb.dp_collapse = !ovr.greedy_collapse; wb.slot_by_assignment = !ovr.octant_slots; wb.NODE_COST = ovr.node_cost; };
-  auto finish_cand = [&](TreeCand& c, uint32_t wide_root) {  // explicit tree -> device layout
-    if (c.wb->range_error || !c.lay.run(c.wb->out, SOL_REF_INDEX(wide_root), c.wb->emin, d->n_triangles, d->n_spheres, d->n_quads)) {
-      c.wb.reset();
-      return;
-    }
-    c.depth = depth_of(c.lay);
-    c.emin = c.wb->emin;
-  };
-  // The host candidates wanted by `want` ("" = all of them, the probe decides): into `cands`, the provisional best first.
-  auto host_candidates = [&](const std::string& want) -> int {
+  return check_dfs_numbering(*d, world_dfs);  // (after the boundaries: their references are known good here)
+}
+// 5. 7-wide tree of the world, host candidates: the reference's topology collapsed, and binned-SAH rebuilds over the same primitives
+// with 8, 16 and 64 bins (how well the binary splits line up with the wide collapse varies with the bin count: with the
+// first, 8-wide layout C2 visited 9.8 / 12.2 / 11.4 nodes per ray at 8 / 16 / 64 bins and 11.2 on the reference's
+// topology; C3 13.3 / 13.0 / 12.9 vs 14.4). A counted probe render on the device picks one (probe_candidates).
+// SolCreateOptions.world_tree (or SOL_BVH=ref | sah (16 bins) | sah8 | sah16 | sah64) forces a candidate.
+// The candidates wanted by `want` ("" = all of them, the probe decides): into `cands`, the provisional best first.
+static TreeCand host_candidate(const World& w, const SolDevOverrides& ovr, const std::string& name, int bins) {  // (wb stays null where host_tree makes no tree)
+  TreeCand t;
+  t.name = name;
+  if (!host_tree(w, bins, ovr, t).empty()) t.wb.reset();
+  else t.depth = w.stack_dwords(t.lay);
+  return t;
+}
+static int host_candidates(const CreateCtx& c, const World& w, const std::string& want, std::vector<TreeCand>& cands) {
+  TreeCand ref = host_candidate(w, c.ovr, "ref", 0);
+  if (w.single()) {
+    if (!ref.wb) return sol_fail(SOL_EINVAL, "world: %s", ref.lay.error.c_str());
+    cands.push_back(std::move(ref));
+    return SOL_OK;
+  }
   std::string layout_error;
-  if (SOL_REF_KIND(root_ref) == SOL_REF_NODE) {
-    {
-      TreeCand c;
-      c.name = "ref";
-      c.wb.reset(new WideBuilder(tb.nodes, box_pad));
-      tune(*c.wb);
-      c.wb->set_exponent_range(root_box);
-      finish_cand(c, c.wb->build(SOL_REF_INDEX(root_ref), 0));
-      if (!c.wb) layout_error = c.lay.error.empty() ? "wide tree: exponent range" : c.lay.error;
-      else cands.push_back(std::move(c));
-    }
-    std::vector<int> bin_list = {8, 16, 64};
-    if (!ovr.sah_bins.empty()) bin_list = ovr.sah_bins;  // (SOL_SAH_LIST)
-    // (the rebuilds are independent of each other: one host thread each)
-    std::vector<std::future<TreeCand>> jobs;
-    for (int bins : bin_list) {
-      const std::string name = "sah" + std::to_string(bins);
-      if (want == "ref" || (!want.empty() && want != name)) continue;
-      jobs.push_back(std::async(std::launch::async, [&, bins, name]() {
-        TreeCand c;
-        c.name = name;
-        c.sah.reset(new SahBuilder());
-        c.sah->BINS = bins;
-        if (!c.sah->collect(tb.nodes, root_ref)) return c;  // non-finite boxes or a single primitive: no rebuild (wb stays null)
-        Box bx;
-        const uint32_t r = c.sah->build(0, c.sah->prims.size(), 0, bx);
-        c.wb.reset(new WideBuilder(c.sah->nodes, box_pad));
-        tune(*c.wb);
-        c.wb->set_exponent_range(root_box);
-        finish_cand(c, c.wb->build(SOL_REF_INDEX(r), 0));
-        return c;
-      }));
-    }
-    for (auto& j : jobs) {
-      TreeCand c = j.get();
-      if (c.wb) cands.push_back(std::move(c));
-    }
-    if (cands.empty()) return sol_fail(SOL_EINVAL, "world: %s", layout_error.c_str());
-    // drop what cannot run; a forced choice drops the rest
-    std::vector<TreeCand> keep;
-    for (auto& c : cands)
-      if (c.depth <= stack_limit && (want.empty() || c.name == want || (want != "ref" && c.name == "ref" && cands.size() == 1))) keep.push_back(std::move(c));
-    if (keep.empty()) {
-      uint32_t dmin = 0xFFFFFFFFu;
-      for (auto& c : cands) if (c.wb) dmin = std::min(dmin, c.depth);
-      return sol_fail(SOL_EDEPTH, "BVH depth %u exceeds the traversal stack (%d)", dmin, stack_limit);
-    }
-    cands = std::move(keep);
-    // provisional choice by the surface-area estimate (it knows nothing of occlusion and visit order: the probe decides)
-    size_t best = 0;
-    for (size_t i = 1; i < cands.size(); ++i)
-      if (cands[i].wb->cost() < cands[best].wb->cost()) best = i;
-    std::swap(cands[0], cands[best]);
-  } else {  // the world is ONE primitive: a root with a single child
-    TreeCand c;
-    c.name = "ref";
-    c.wb.reset(new WideBuilder(tb.nodes, box_pad));
-    c.wb->set_exponent_range(root_box);
-    finish_cand(c, c.wb->build_single(root_ref, root_box));
-    if (!c.wb) return sol_fail(SOL_EINVAL, "world: %s", c.lay.error.c_str());
-    cands.push_back(std::move(c));
+  if (!ref.wb) layout_error = ref.lay.error.empty() ? "wide tree: exponent range" : ref.lay.error;
+  else cands.push_back(std::move(ref));
+  std::vector<int> bin_list = {8, 16, 64};
+  if (!c.ovr.sah_bins.empty()) bin_list = c.ovr.sah_bins;  // (SOL_SAH_LIST)
+  // (the rebuilds are independent of each other: one host thread each)
+  std::vector<std::future<TreeCand>> jobs;
+  for (int bins : bin_list) {
+    const std::string name = "sah" + std::to_string(bins);
+    if (want == "ref" || (!want.empty() && want != name)) continue;
+    jobs.push_back(std::async(std::launch::async, host_candidate, std::cref(w), std::cref(c.ovr), name, bins));
+  }
+  for (auto& j : jobs) {
+    TreeCand t = j.get();
+    if (t.wb) cands.push_back(std::move(t));  // (non-finite boxes, a failed layout: no rebuild)
+  }
+  if (cands.empty()) return sol_fail(SOL_EINVAL, "world: %s", layout_error.c_str());
+  // drop what cannot run; a forced choice drops the rest
+  std::vector<TreeCand> keep;
+  for (auto& t : cands)
+    if (t.depth <= STACK_LIMIT && (want.empty() || t.name == want || (want != "ref" && t.name == "ref" && cands.size() == 1))) keep.push_back(std::move(t));
+  if (keep.empty()) {
+    uint32_t dmin = 0xFFFFFFFFu;
+    for (auto& t : cands) if (t.wb) dmin = std::min(dmin, t.depth);
+    return sol_fail(SOL_EDEPTH, "BVH depth %u exceeds the traversal stack (%d)", dmin, STACK_LIMIT);
+  }
+  cands = std::move(keep);
+  // provisional choice by the surface-area estimate (it knows nothing of occlusion and visit order: the probe decides)
+  size_t best = 0;
+  for (size_t i = 1; i < cands.size(); ++i)
+    if (cands[i].wb->cost() < cands[best].wb->cost()) best = i;
+  std::swap(cands[0], cands[best]);
+  return SOL_OK;
+}
+// 6. lights
+static int check_lights(const SolSceneDesc* d, HostRecords& r) {
+  r.lights.assign(d->lights, d->lights + d->n_lights);
+  for (uint32_t i = 0; i < d->n_lights; ++i) {
+    uint32_t k = SOL_REF_KIND(r.lights[i]), x = SOL_REF_INDEX(r.lights[i]);
+    if (!((k == SOL_REF_SPHERE && x < d->n_spheres) || (k == SOL_REF_QUAD && x < d->n_quads) || (k == SOL_REF_TRIANGLE && x < d->n_triangles))) return sol_fail(SOL_EINVAL, "light %u: not a sphere/quad/triangle reference", i);
   }
   return SOL_OK;
-  };
-  // AUTO falls back to the host candidates when the device build cannot make a tree (a primitive with a non-finite or inverted box -
-  // e.g. a NaN vertex of an OBJ -, more than 2^23 primitives, no memory for its scratch): scenes the host path accepts are never
-  // refused by the default. An explicit SOL_TREE_DEVICE (or SOL_BVH=device) keeps the hard error.
-  const bool device_explicit = opt.world_tree == SOL_TREE_DEVICE || ovr.bvh == "device";
-  bool device_build = want == "device";
-  std::string fallback_note;
-  if (!device_build) { int rc0 = host_candidates(want); if (rc0) return rc0; }
-  double t_host_trees = seconds_since(t_begin);
-  if (sol_dev_overrides().verbose) std::fprintf(stderr, "[solstrale] create: host part done at %.1f ms\n", 1e3 * t_host_trees);
-
-  // ---- lights ----
-  std::vector<uint32_t> lights(d->lights, d->lights + d->n_lights);
-  for (uint32_t i = 0; i < d->n_lights; ++i) {
-    uint32_t k = SOL_REF_KIND(lights[i]), x = SOL_REF_INDEX(lights[i]);
-    bool ok = (k == SOL_REF_SPHERE && x < d->n_spheres) || (k == SOL_REF_QUAD && x < d->n_quads) || (k == SOL_REF_TRIANGLE && x < d->n_triangles);
-    if (!ok) return sol_fail(SOL_EINVAL, "light %u: not a sphere/quad/triangle reference", i);
-  }
-
-  // ---- device ----
+}
+// 7. the device: the handle, its stream, the properties
+static int open_device(int device, ScenePtr& scene, std::chrono::steady_clock::time_point& t_upload0) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
   if (device < 0 || device >= ndev) return sol_fail(SOL_EDEVICE, "device %d out of range (%d devices)", device, ndev);
   HIP_TRY(hipSetDevice(device));
   SolScene* s = new SolScene();
+  scene.reset(s);
   s->device = device;
-  s->build_times[0] = t_host_trees;
-  const auto t_upload0 = std::chrono::steady_clock::now();
-  struct Cleanup { SolScene* s; bool keep = false; ~Cleanup() { if (!keep) sol_scene_destroy(s); } } cleanup{s};
+  t_upload0 = std::chrono::steady_clock::now();  // ("upload" of sol_scene_build_times starts here, before the properties and the stream)
   hipDeviceProp_t prop;
   HIP_TRY(hipGetDeviceProperties(&prop, device));
   s->n_cu = prop.multiProcessorCount;
   HIP_TRY(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
   s->stream = s->own_stream;
+  return SOL_OK;
+}
+// 8. device candidates (sol_build.hip); where the build cannot make a tree, AUTO falls back to the host candidates
+// The clustering radius of the device build decides little on average and a few per cent on any one scene, not monotonically (greedy
+// clustering; MI355X, 1080p x 64 spp, ms with radius 8 / 16 / 32 / 64: C3 61.0 / 63.0 / 63.8 / 65.0, C2 37.1 / 35.7 / 34.7 / 37.3, C5
+// 37.7 / 38.0 / 37.6 / 36.8, heterogeneous atrium 67.8 / 68.2 / 74.7 / 76.2 - profiles/r04_tree_ploc_radius.txt): round 4's SOL_TREE_AUTO
+// built the tree with radius 16, 8 and 32, uploaded all three and let the counted probe choose (the probe's cost - 2.5 per node visit,
+// 1 per primitive test - ranks them as the render times do): C5 paid twice the build time for a 0 % choice. An explicit
+// SOL_TREE_DEVICE builds one tree (radius 16); SOL_PLOC_R forces a radius.
+// Round 5: two radii (16 never won a probe on the four scene families and costs a third of the build time), each built as far as the
+// collapse's surface-area cost of the whole tree; what is emitted, uploaded and probed follows from the two costs
+// (profiles/r05_scene_creation.txt: on triangle meshes the cost ranks the candidates as the probes and the render times do - C3 1.7 %, the
+// heterogeneous atrium 2.1 % apart -; on C5 the candidates are 0.3 % apart and render within 1 % of each other; on C2's spheres they are
+// 0.6 % apart and the cost ranks them the WRONG way round - box area overstates how often a sphere is hit - by 7 % of render time):
+//   apart by less than 0.4 % or by more than 1.2 %: the cheaper tree, unprobed;   in between: both, the counted probe decides.
+static int device_candidates(const CreateCtx& c, const World& w, const std::vector<DTri>& tris, SolScene* s, std::vector<TreeCand>& cands) {
+  const SolDevOverrides& ovr = c.ovr;
+  const auto t_dev0 = std::chrono::steady_clock::now();
+  std::vector<int> radii = {16};
+  if (ovr.ploc_radius > 0) radii = {ovr.ploc_radius};
+  else if (c.opt.world_tree == SOL_TREE_AUTO && ovr.bvh.empty()) radii = {8, 32};
+  std::vector<SolBuildPrim> build_prims;
+  int rc = collect_build_prims(w.tb.nodes, w.root_ref, w.root_box, build_prims);
+  const SolSplitOptions sopt = split_options(ovr, &c.opt);
+  std::vector<std::unique_ptr<DevicePrepared>> prepared;
+  std::vector<int> prepared_radius;
+  for (int radius : radii) {
+    if (rc && prepared.empty()) break;
+    std::unique_ptr<DevicePrepared> pr(new DevicePrepared);
+    rc = device_world_tree_prepare(build_prims, w.root_box, w.box_pad, w.counts, tris, sopt, radius, s->stream, *pr);
+    if (rc) {
+      if (!prepared.empty()) { rc = SOL_OK; continue; }  // (a later candidate failed: the earlier ones stand)
+      break;
+    }
+    if (ovr.verbose) std::fprintf(stderr, "[solstrale] device tree (radius %d): collapse cost %.6g\n", radius, (double)pr->dt.collapse_cost);
+    prepared.push_back(std::move(pr));
+    prepared_radius.push_back(radius);
+  }
+  if (prepared.size() == 2) {
+    const double a = prepared[0]->dt.collapse_cost, b = prepared[1]->dt.collapse_cost;
+    const double apart = (a > 0. && b > 0.) ? std::fabs(a - b) / std::min(a, b) : 0.;
+    const bool probe_both = ovr.probe_radii > 0 || (ovr.probe_radii < 0 && apart >= 0.004 && apart <= 0.012);  // (SOL_PROBE_RADII=1 / 0 forces)
+    if (b < a) { std::swap(prepared[0], prepared[1]); std::swap(prepared_radius[0], prepared_radius[1]); }  // the cheaper one first
+    if (ovr.verbose) std::fprintf(stderr, "[solstrale] device trees: collapse costs %.4f %% apart -> %s\n", apart * 100., probe_both ? "both emitted, the probe decides" : "the cheaper one, unprobed");
+    if (!probe_both) { prepared.pop_back(); prepared_radius.pop_back(); }
+  }
+  for (size_t k = 0; k < prepared.size() && !(rc && cands.empty()); ++k) {
+    const int radius = prepared_radius[k];
+    TreeCand t;
+    t.name = radii.size() > 1 ? "device" + std::to_string(radius) : "device";
+    DeviceSplitInfo& si = t.built;
+    rc = device_world_tree_finish(*prepared[k], w.counts, sopt, t.lay, t.emin, &si);
+    if (ovr.verbose) std::fprintf(stderr, "[solstrale] device tree (radius %d): pre-splitting %u triangles into %u extra references, box area ratio %.3f%s; %u reinsertion moves\n",
+                                  radius, si.split_triangles, si.extra_references, si.area_ratio, si.extra_references ? "" : " (not kept)", si.reinsertion_moves);
+    if (!rc) {
+      t.depth = w.stack_dwords(t.lay);
+      if (t.depth > STACK_LIMIT) rc = sol_fail(SOL_EDEPTH, "BVH depth %u exceeds the traversal stack (%d)", t.depth, STACK_LIMIT);
+    }
+    if (rc) {
+      if (!cands.empty()) { rc = SOL_OK; continue; }  // (a later candidate failed: the earlier ones stand)
+      break;
+    }
+    // Small scenes: the radii often give the SAME tree (the layout is a function of the tree alone, so equal trees are equal
+    // bytes) - a duplicate is not uploaded and probed a second time (the reference's test scene: 33 identical nodes either way).
+    bool duplicate = false;
+    for (const TreeCand& p : cands) {
+      const WideLayout &a = p.lay, &b = t.lay;
+      if (p.emin != t.emin || a.nodes.size() != b.nodes.size() || a.leaf_refs != b.leaf_refs) continue;
+      if (std::memcmp(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(DWide)) != 0) continue;
+      if (a.old_of_new[0] == b.old_of_new[0] && a.old_of_new[1] == b.old_of_new[1] && a.old_of_new[2] == b.old_of_new[2]) { duplicate = true; break; }
+    }
+    if (duplicate) {
+      if (ovr.verbose) std::fprintf(stderr, "[solstrale] device tree (radius %d): the same tree as an earlier candidate, dropped\n", radius);
+      continue;
+    }
+    cands.push_back(std::move(t));
+  }
+  prepared.clear();
+  s->build_times[2] = seconds_since(t_dev0);
+  if (!cands.empty()) return SOL_OK;
+  // AUTO falls back to the host candidates when the device build cannot make a tree (a primitive with a non-finite or inverted box -
+  // e.g. a NaN vertex of an OBJ -, more than 2^23 primitives, no memory for its scratch): scenes the host path accepts are never
+  // refused by the default. An explicit SOL_TREE_DEVICE (or SOL_BVH=device) keeps the hard error.
+  if (c.opt.world_tree == SOL_TREE_DEVICE || ovr.bvh == "device") return rc;
+  s->tree_note = std::string("device build failed (") + sol_last_error() + "): host candidates";
+  if (ovr.verbose) std::fprintf(stderr, "[solstrale] world tree: %s\n", s->tree_note.c_str());
+  const auto t_host0 = std::chrono::steady_clock::now();
+  if ((rc = host_candidates(c, w, "", cands))) return rc;
+  s->build_times[0] += seconds_since(t_host0);
+  return SOL_OK;
+}
+// 9. upload. Everything that depends on the choice of the world tree - the tree itself, the permuted primitive arrays and every table of
+// references into them - goes into the candidate's DevTree: candidate 0 first, the others only if a probe has to decide.
+static int upload_tree(const SolSceneDesc& d, const World& w, const HostRecords& r, TreeCand& c) {
+  // (the node test reads plane bytes as the fp16 subnormals q * 2^-24 and keeps the 2^24 in the node scales: sol_trace.h)
+  if (c.emin + 31u + 24u > 254u) return sol_fail(SOL_EINVAL, "the scene is too large for the quantised world tree (extent beyond 2^100)");
+  const WideLayout& L = c.lay;
+  DevTree& t = c.dev;
+  std::vector<DTri> ptris(L.old_of_new[0].size());  // (more records than triangles when the device build pre-split some: copies)
+  std::vector<DTriShade> pshade(ptris.size()); std::vector<DQuad> pquads(r.quads.size()); std::vector<DSphere> pspheres(r.spheres.size());
+  for (size_t i = 0; i < ptris.size(); ++i) { ptris[i] = r.tris[L.old_of_new[0][i]]; pshade[i] = r.tshade[L.old_of_new[0][i]]; }
+  for (size_t i = 0; i < r.spheres.size(); ++i) pspheres[i] = r.spheres[L.old_of_new[1][i]];
+  for (size_t i = 0; i < r.quads.size(); ++i) pquads[i] = r.quads[L.old_of_new[2][i]];
+  std::vector<DNode> pnodes = d.n_mediums > 0 ? w.tb.nodes : std::vector<DNode>();  // the 2-wide tree serves medium boundaries only
+  for (auto& n : pnodes) { n.left = L.remap(n.left); n.right = L.remap(n.right); }
+  std::vector<DMedium> pmed = r.mediums;
+  for (auto& m : pmed) m.boundary = L.remap(m.boundary);
+  std::vector<uint32_t> plights = r.lights;
+  for (auto& l : plights) l = L.remap(l);
+  int e;
+  if ((e = sol_upload(L.nodes, t.wides)) || (e = sol_upload(L.leaf_refs, t.leaf_refs)) || (e = sol_upload(ptris, t.tris)) || (e = sol_upload(pshade, t.tri_shade)) ||
+      (e = sol_upload(pquads, t.quads)) || (e = sol_upload(pspheres, t.spheres)) || (e = sol_upload(pnodes, t.nodes)) || (e = sol_upload(pmed, t.mediums)) ||
+      (e = sol_upload(plights, t.lights)))
+    return e;  // (what was uploaded goes with the candidate)
+  t.emin = c.emin; t.depth = c.depth; t.root = L.remap(w.root_ref); t.light0 = plights.empty() ? 0u : plights[0];
+  t.n_wide = (uint32_t)L.nodes.size(); t.packed_depth = L.depth + w.medium_depth + 2u;  // (stack_dwords: 2 * L.depth + medium_depth + 2 with two dwords per group)
+  for (int a = 0; a < 3; ++a) t.old_index[a] = L.old_of_new[a];
+  return SOL_OK;
+}
+// What the kernels read of the tree the scene owns (s->tree): the ONE place that writes the tree-dependent fields of DevScene.
+static void bind_tree(SolScene* s) {
+  const DevTree& t = s->tree;
+  DevScene& S = s->S;
+  S.nodes = t.nodes.get(); S.wides = t.wides.get(); S.leaf_refs = t.leaf_refs.get(); S.tris = t.tris.get(); S.tri_shade = t.tri_shade.get();
+  S.quads = t.quads.get(); S.spheres = t.spheres.get(); S.mediums = t.mediums.get(); S.lights = t.lights.get();
+  S.light0 = t.light0; S.wroot = 0; S.wide_emin = t.emin; S.root = t.root;
+}
+static void adopt_build_info(SolScene* s, const DeviceSplitInfo& si) {  // what the chosen candidate's build did (a host-built tree: nothing)
+  s->split_references = si.extra_references; s->split_triangles = si.split_triangles; s->split_area_ratio = si.area_ratio;
+  s->reinsertion_moves = si.reinsertion_moves; s->reinsertion_area_ratio = si.area_before > 0. ? (float)(si.area_after / si.area_before) : 1.f;
+}
+// candidate 0's tree and what does not depend on the tree
+static int upload_scene(const CreateCtx& c, const World& w, const HostRecords& r, SolScene* s, TreeCand& first) {
+  const SolSceneDesc* d = &c.d;
   int rc;
-  std::vector<DeviceSplitInfo> dev_info;  // (per device candidate, in the order of `cands`)
-  if (device_build) {
-    // The clustering radius of the device build decides little on average and a few per cent on any one scene, not monotonically (greedy
-    // clustering; MI355X, 1080p x 64 spp, ms with radius 8 / 16 / 32 / 64: C3 61.0 / 63.0 / 63.8 / 65.0, C2 37.1 / 35.7 / 34.7 / 37.3, C5
-    // 37.7 / 38.0 / 37.6 / 36.8, heterogeneous atrium 67.8 / 68.2 / 74.7 / 76.2 - profiles/r04_tree_ploc_radius.txt): round 4's SOL_TREE_AUTO
-    // built the tree with radius 16, 8 and 32, uploaded all three and let the counted probe choose (the probe's cost - 2.5 per node visit,
-    // 1 per primitive test - ranks them as the render times do): C5 paid twice the build time for a 0 % choice. An explicit
-    // SOL_TREE_DEVICE builds one tree (radius 16); SOL_PLOC_R forces a radius.
-    const auto t_dev0 = std::chrono::steady_clock::now();
-    // Round 5: two radii (16 never won a probe on the four scene families and costs a third of the build time), each built as far as the
-    // collapse's surface-area cost of the whole tree; what is emitted, uploaded and probed follows from the two costs
-    // (profiles/r05_scene_creation.txt: on triangle meshes the cost ranks the candidates as the probes and the render times do - C3 1.7 %, the
-    // heterogeneous atrium 2.1 % apart -; on C5 the candidates are 0.3 % apart and render within 1 % of each other; on C2's spheres they are
-    // 0.6 % apart and the cost ranks them the WRONG way round - box area overstates how often a sphere is hit - by 7 % of render time):
-    //   apart by less than 0.4 % or by more than 1.2 %: the cheaper tree, unprobed;   in between: both, the counted probe decides.
-    std::vector<int> radii = {16};
-    if (ovr.ploc_radius > 0) radii = {ovr.ploc_radius};
-    else if (opt.world_tree == SOL_TREE_AUTO && ovr.bvh.empty()) radii = {8, 32};
-    const uint32_t counts[3] = {d->n_triangles, d->n_spheres, d->n_quads};
-    std::vector<SolBuildPrim> build_prims;
-    rc = collect_build_prims(tb.nodes, root_ref, root_box, build_prims);
-    const SolSplitOptions sopt = split_options(ovr, &opt);
-    std::vector<std::unique_ptr<DevicePrepared>> prepared;
-    std::vector<int> prepared_radius;
-    for (int radius : radii) {
-      if (rc && prepared.empty()) break;
-      std::unique_ptr<DevicePrepared> pr(new DevicePrepared);
-      rc = device_world_tree_prepare(build_prims, root_box, box_pad, counts, tris, sopt, radius, s->stream, *pr);
-      if (rc) {
-        if (!prepared.empty()) { rc = SOL_OK; continue; }  // (a later candidate failed: the earlier ones stand)
-        break;
-      }
-      if (ovr.verbose) std::fprintf(stderr, "[solstrale] device tree (radius %d): collapse cost %.6g\n", radius, (double)pr->dt.collapse_cost);
-      prepared.push_back(std::move(pr));
-      prepared_radius.push_back(radius);
-    }
-    if (prepared.size() == 2) {
-      const double a = prepared[0]->dt.collapse_cost, b = prepared[1]->dt.collapse_cost;
-      const double apart = (a > 0. && b > 0.) ? std::fabs(a - b) / std::min(a, b) : 0.;
-      const bool probe_both = ovr.probe_radii > 0 || (ovr.probe_radii < 0 && apart >= 0.004 && apart <= 0.012);  // (SOL_PROBE_RADII=1 / 0 forces)
-      if (b < a) { std::swap(prepared[0], prepared[1]); std::swap(prepared_radius[0], prepared_radius[1]); }  // the cheaper one first
-      if (ovr.verbose) std::fprintf(stderr, "[solstrale] device trees: collapse costs %.4f %% apart -> %s\n", apart * 100., probe_both ? "both emitted, the probe decides" : "the cheaper one, unprobed");
-      if (!probe_both) { prepared.pop_back(); prepared_radius.pop_back(); }
-    }
-    for (size_t k = 0; k < prepared.size() && !(rc && cands.empty()); ++k) {
-      const int radius = prepared_radius[k];
-      TreeCand c;
-      c.name = radii.size() > 1 ? "device" + std::to_string(radius) : "device";
-      DeviceSplitInfo si;
-      rc = device_world_tree_finish(*prepared[k], counts, sopt, c.lay, c.emin, &si);
-      if (ovr.verbose) std::fprintf(stderr, "[solstrale] device tree (radius %d): pre-splitting %u triangles into %u extra references, box area ratio %.3f%s; %u reinsertion moves\n",
-                                    radius, si.split_triangles, si.extra_references, si.area_ratio, si.extra_references ? "" : " (not kept)", si.reinsertion_moves);
-      if (!rc) {
-        c.depth = depth_of(c.lay);
-        if (c.depth > stack_limit) rc = sol_fail(SOL_EDEPTH, "BVH depth %u exceeds the traversal stack (%d)", c.depth, stack_limit);
-      }
-      if (rc) {
-        if (!cands.empty()) { rc = SOL_OK; continue; }  // (a later candidate failed: the earlier ones stand)
-        break;
-      }
-      // Small scenes: the radii often give the SAME tree (the layout is a function of the tree alone, so equal trees are equal
-      // bytes) - a duplicate is not uploaded and probed a second time (the reference's test scene: 33 identical nodes either way).
-      bool duplicate = false;
-      for (const TreeCand& p : cands) {
-        const WideLayout &a = p.lay, &b = c.lay;
-        if (p.emin != c.emin || a.nodes.size() != b.nodes.size() || a.leaf_refs != b.leaf_refs) continue;
-        if (std::memcmp(a.nodes.data(), b.nodes.data(), a.nodes.size() * sizeof(DWide)) != 0) continue;
-        if (a.old_of_new[0] == b.old_of_new[0] && a.old_of_new[1] == b.old_of_new[1] && a.old_of_new[2] == b.old_of_new[2]) { duplicate = true; break; }
-      }
-      if (duplicate) {
-        if (ovr.verbose) std::fprintf(stderr, "[solstrale] device tree (radius %d): the same tree as an earlier candidate, dropped\n", radius);
-        continue;
-      }
-      cands.push_back(std::move(c));
-      dev_info.push_back(si);
-    }
-    prepared.clear();
-    s->build_times[2] = seconds_since(t_dev0);
-    if (!cands.empty()) {
-      rc = SOL_OK;
-    } else if (device_explicit) {
-      return rc;
-    } else {
-      fallback_note = std::string("device build failed (") + sol_last_error() + "): host candidates";
-      if (ovr.verbose) std::fprintf(stderr, "[solstrale] world tree: %s\n", fallback_note.c_str());
-      device_build = false;
-      const auto t_host0 = std::chrono::steady_clock::now();
-      if ((rc = host_candidates(""))) return rc;
-      s->build_times[0] += seconds_since(t_host0);
-    }
-  }
-  auto adopt_info = [&](size_t k) {  // what the chosen device candidate's build did
-    if (k >= dev_info.size()) return;
-    const DeviceSplitInfo& si = dev_info[k];
-    s->split_references = si.extra_references; s->split_triangles = si.split_triangles; s->split_area_ratio = si.area_ratio;
-    s->reinsertion_moves = si.reinsertion_moves; s->reinsertion_area_ratio = si.area_before > 0. ? (float)(si.area_after / si.area_before) : 1.f;
-  };
-  adopt_info(0);
-  const bool calibrate = cands.size() > 1;
-  // everything that depends on the choice of the world tree: the tree itself, the permuted primitive arrays and every table of
-  // references into them (DevTree); candidate 0 first, the others only if a probe has to decide
-  const bool need_binary = d->n_mediums > 0;  // the 2-wide tree serves medium boundaries only
-  auto upload_tree = [&](TreeCand& c) -> int {
-    // (the node test reads plane bytes as the fp16 subnormals q * 2^-24 and keeps the 2^24 in the node scales: sol_trace.h)
-    if (c.emin + 31u + 24u > 254u) return sol_fail(SOL_EINVAL, "the scene is too large for the quantised world tree (extent beyond 2^100)");
-    const WideLayout& L = c.lay;
-    DevTree& t = c.dev;
-    std::vector<DTri> ptris(L.old_of_new[0].size());  // (more records than triangles when the device build pre-split some: copies)
-    std::vector<DTriShade> pshade(L.old_of_new[0].size());
-    std::vector<DQuad> pquads(quads.size());
-    std::vector<DSphere> pspheres(spheres.size());
-    for (size_t i = 0; i < ptris.size(); ++i) { ptris[i] = tris[L.old_of_new[0][i]]; pshade[i] = tshade[L.old_of_new[0][i]]; }
-    for (size_t i = 0; i < spheres.size(); ++i) pspheres[i] = spheres[L.old_of_new[1][i]];
-    for (size_t i = 0; i < quads.size(); ++i) pquads[i] = quads[L.old_of_new[2][i]];
-    std::vector<DNode> pnodes;
-    if (need_binary) {
-      pnodes = tb.nodes;
-      for (auto& n : pnodes) { n.left = L.remap(n.left); n.right = L.remap(n.right); }
-    }
-    std::vector<DMedium> pmed = mediums;
-    for (auto& m : pmed) m.boundary = L.remap(m.boundary);
-    std::vector<uint32_t> plights = lights;
-    for (auto& r : plights) r = L.remap(r);
-    int e;
-    if ((e = sol_upload(L.nodes, &t.wides)) || (e = sol_upload(L.leaf_refs, &t.leaf_refs)) || (e = sol_upload(ptris, &t.tris)) || (e = sol_upload(pshade, &t.tri_shade)) ||
-        (e = sol_upload(pquads, &t.quads)) || (e = sol_upload(pspheres, &t.spheres)) || (e = sol_upload(pnodes, &t.nodes)) || (e = sol_upload(pmed, &t.mediums)) ||
-        (e = sol_upload(plights, &t.lights))) {
-      t.release();
-      return e;
-    }
-    t.emin = c.emin; t.depth = c.depth; t.root = L.remap(root_ref); t.light0 = plights.empty() ? 0u : plights[0];
-    t.n_wide = (uint32_t)L.nodes.size(); t.packed_depth = L.depth + medium_depth + 2u;  // (depth_of: 2 * L.depth + medium_depth + 2 with two dwords per group)
-    t.old_tri = L.old_of_new[0]; t.old_sphere = L.old_of_new[1]; t.old_quad = L.old_of_new[2];
-    return SOL_OK;
-  };
-  auto adopt_tree = [&](DevTree& t) {  // the scene takes ownership
-    s->nodes = t.nodes; s->wides = t.wides; s->leaf_refs = t.leaf_refs; s->tris = t.tris; s->tri_shade = t.tri_shade; s->quads = t.quads;
-    s->spheres = t.spheres; s->mediums = t.mediums; s->lights = t.lights;
-    s->old_index[0] = std::move(t.old_tri); s->old_index[1] = std::move(t.old_sphere); s->old_index[2] = std::move(t.old_quad);
-    DevScene& S = s->S;
-    S.nodes = t.nodes; S.wides = t.wides; S.leaf_refs = t.leaf_refs; S.tris = t.tris; S.tri_shade = t.tri_shade; S.quads = t.quads; S.spheres = t.spheres;
-    S.mediums = t.mediums; S.lights = t.lights; S.light0 = t.light0; S.wroot = 0; S.wide_emin = t.emin; S.root = t.root;
-    s->tree_depth = t.depth; s->n_wide = t.n_wide; s->packed_depth = t.packed_depth;
-    t = DevTree{};
-  };
-  if ((rc = upload_tree(cands[0])) || (rc = sol_upload(mats, &s->mats)) || (rc = sol_upload(texs, &s->texs))) return rc;
-  {
-    std::vector<uint8_t> texels(d->texels, d->texels + d->n_texel_bytes);
-    if ((rc = sol_upload(texels, &s->texels))) return rc;
-  }
+  if ((rc = upload_tree(*d, w, r, first)) || (rc = sol_upload(r.mats, &s->mats)) || (rc = sol_upload(r.texs, &s->texs))) return rc;
+  const std::vector<uint8_t> texels(d->texels, d->texels + d->n_texel_bytes);
+  if ((rc = sol_upload(texels, &s->texels))) return rc;
   HIP_TRY(hipMalloc((void**)&s->work, 64));
   HIP_TRY(hipMalloc((void**)&s->counters, sizeof(DevCounters)));
   HIP_TRY(hipMemset(s->counters, 0, sizeof(DevCounters)));
   HIP_TRY(hipMalloc((void**)&s->image, (size_t)d->width * d->height * 3 * sizeof(float)));
   HIP_TRY(hipMalloc((void**)&s->rgb8, (size_t)d->width * d->height * 3));
-  s->build_times[1] = seconds_since(t_upload0) - s->build_times[2];
-  const auto t_probe0 = std::chrono::steady_clock::now();
-
+  return SOL_OK;
+}
+// ... and the scene's constants: DevScene, the launch parameters the overrides set, the whole-image partition
+static int set_scene_constants(const CreateCtx& c, const World& w, SolScene* s, TreeCand& first) {
+  const SolSceneDesc* d = &c.d;
+  const SolDevOverrides& ovr = c.ovr;
+  const Box& root_box = w.root_box;
+  int rc;
   DevScene& S = s->S;
   S.mats = s->mats; S.texs = s->texs; S.texels = s->texels;
   S.n_lights = d->n_lights;
-  adopt_tree(cands[0].dev);
+  s->tree = std::move(first.dev);  // the scene takes ownership
+  bind_tree(s);
+  adopt_build_info(s, first.built);
   S.rxmin = root_box.v[0]; S.rxmax = root_box.v[1]; S.rymin = root_box.v[2]; S.rymax = root_box.v[3];
   S.rzmin = root_box.v[4]; S.rzmax = root_box.v[5];
   S.width = d->width; S.height = d->height; S.shader = d->shader_kind; S.max_depth = d->max_depth;
-  S.sphere_slack = box_pad * 0.5f;
+  S.sphere_slack = w.box_pad * 0.5f;
   if ((rc = sol_upload(light_triangle_frames(*d), &s->light_tri))) return rc;
   S.light_tri = s->light_tri;
-  S.tri_delta = scene_has_needles ? box_pad * 0.8f : 0.0f;
+  S.tri_delta = w.needles ? w.box_pad * 0.8f : 0.0f;
   s->strict_triangles = S.tri_delta > 0.0f;
   S.env = nullptr; S.env_w = S.env_h = 0; S.env_scale = 1.0f;
-  if (has_env) {
+  if (c.has_env) {
     std::vector<float> env(d->env_texels, d->env_texels + (size_t)d->env_width * d->env_height * 3);
     if ((rc = sol_upload(env, &s->env))) return rc;
     S.env = s->env; S.env_w = d->env_width; S.env_h = d->env_height; S.env_scale = (float)d->env_scale;
@@ -1139,124 +1054,189 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
   s->blocks_x = (d->width + SOL_TILE - 1) / SOL_TILE;
   s->blocks_y = (d->height + SOL_TILE - 1) / SOL_TILE;
   if ((rc = sol_set_partition(s, 0, 1))) return rc;
-  {  // a null table would be a GPU memory fault at the first launch, not an error code: refuse here
-    const void* tables[] = {S.nodes, S.wides, S.leaf_refs, S.tris, S.tri_shade, S.quads, S.spheres, S.mediums, S.mats, S.texs, S.texels, S.lights};
-    for (const void* p : tables)
-      if (!p) return sol_fail(SOL_EDEVICE, "internal error: a device table of the scene is missing");
-  }
-  s->tree_name = cands[0].name;
-  s->tree_note = fallback_note;
-  size_t chosen = 0;  // the candidate the scene keeps
-  if (calibrate) {
-    // Probe every candidate tree with a counted render of 16 samples per pixel over ~256 pixel blocks spread across the image
-    // and keep the one with the least search work (a wide-node visit weighs ~2.5 primitive tests, by instruction count).
-    // Images do not depend on the tree, the counters are deterministic, so is the choice.
-    auto free_cands = [&]() { for (auto& c : cands) c.dev.release(); };
-    for (size_t k = 1; k < cands.size(); ++k)
-      if ((rc = upload_tree(cands[k]))) { free_cands(); return rc; }
-    const uint32_t nb = s->blocks_x * s->blocks_y;
-    rc = sol_set_partition(s, 0, (int)std::max(1u, nb / 256u));
-    size_t pick = 0, current = 0;  // `current`: the candidate whose arrays the scene holds at the moment
-    auto swap_in = [&](size_t k) {  // hand the scene's tree back to its candidate, adopt candidate k's
-      if (k == current) return;
-      DevTree& back = cands[current].dev;
-      back.nodes = s->nodes; back.wides = s->wides; back.leaf_refs = s->leaf_refs; back.tris = s->tris; back.tri_shade = s->tri_shade;
-      back.quads = s->quads; back.spheres = s->spheres; back.mediums = s->mediums; back.lights = s->lights;
-      back.emin = S.wide_emin; back.depth = s->tree_depth; back.root = S.root; back.light0 = S.light0; back.n_wide = s->n_wide; back.packed_depth = s->packed_depth;
-      back.old_tri = std::move(s->old_index[0]); back.old_sphere = std::move(s->old_index[1]); back.old_quad = std::move(s->old_index[2]);
-      adopt_tree(cands[k].dev);
-      current = k;
-    };
-    for (size_t k = 0; k < cands.size() && !rc; ++k) {
-      swap_in(k);
-      if (!(rc = sol_clear(s)) && !(rc = sol_render_probe(s)))
-        cands[k].cost = 2.5 * (double)s->stats.node_visits + (double)(s->stats.sphere_tests + s->stats.quad_tests + s->stats.triangle_tests);
-      if (!rc && cands[k].cost < cands[pick].cost) pick = k;
-    }
-    if (ovr.verbose) {
-      std::fprintf(stderr, "[solstrale] world tree probe:");
-      for (auto& c : cands) std::fprintf(stderr, " %s %.4g (%zu nodes)", c.name.c_str(), c.cost, c.lay.nodes.size());
-      std::fprintf(stderr, " -> %s\n", cands[pick].name.c_str());
-    }
-    if (hipStreamSynchronize(s->stream) != hipSuccess && !rc) rc = SOL_EDEVICE;
-    swap_in(pick);
-    chosen = pick;
-    s->tree_name = cands[pick].name;
-    adopt_info(pick);
-    free_cands();
-    if (rc) return rc;
-    s->stats = SolStats{};
-    if ((rc = sol_set_partition(s, 0, 1)) || (rc = sol_clear(s))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  // Background blocks: constant background only (an environment map is looked up per ray). The proof is host work (0.06 s for C5 at 1080p): it
-  // runs on a thread of its own beside the cost probe's render below and is adopted after it (the probe traces every block either way).
-  std::future<void> background_proof;
-  std::vector<uint8_t> bg_block;
-  uint32_t bg_n = 0, bg_pixels = 0;
-  const bool want_background = !opt.no_background_blocks && ovr.background_blocks != 0 && !has_env;
-  if (want_background) {
-    const WideLayout* lay_ptr = &cands[chosen].lay;
-    const uint32_t lay_emin = cands[chosen].emin;
-    const DCamera cam = S.cam;
-    const double inflate = 64.0 * (double)box_pad;
-    const uint32_t iw = d->width, ih = d->height;
-    background_proof = std::async(std::launch::async, [=, &bg_block, &bg_n, &bg_pixels]() { find_background_blocks(*lay_ptr, lay_emin, cam, iw, ih, inflate, bg_block, bg_n, bg_pixels); });
-  }
-  auto adopt_background = [&]() -> int {  // (waits for the proof; idempotent)
-    if (!background_proof.valid()) return SOL_OK;
-    background_proof.get();
-    s->background_block = std::move(bg_block); s->n_background = bg_n; s->background_pixels = bg_pixels;
-    if (ovr.verbose) std::fprintf(stderr, "[solstrale] background blocks: %u of %u (%u pixels)\n", s->n_background, s->blocks_x * s->blocks_y, s->background_pixels);
-    if (s->n_background == 0) { s->background_block.clear(); return SOL_OK; }
-    return sol_rebuild_order(s);  // (also without the cost probe below)
+  // a null table would be a GPU memory fault at the first launch, not an error code: refuse here
+  const void* tables[] = {S.nodes, S.wides, S.leaf_refs, S.tris, S.tri_shade, S.quads, S.spheres, S.mediums, S.mats, S.texs, S.texels, S.lights};
+  for (const void* p : tables)
+    if (!p) return sol_fail(SOL_EDEVICE, "internal error: a device table of the scene is missing");
+  s->tree_name = first.name;
+  return SOL_OK;
+}
+// 10. Probe every candidate tree with a counted render of 16 samples per pixel over ~256 pixel blocks spread across the image
+// and keep the one with the least search work (a wide-node visit weighs ~2.5 primitive tests, by instruction count).
+// Images do not depend on the tree, the counters are deterministic, so is the choice. `chosen`: the candidate the scene keeps.
+static int probe_candidates(const CreateCtx& c, const World& w, const HostRecords& r, SolScene* s, std::vector<TreeCand>& cands, size_t& chosen) {
+  int rc;
+  for (size_t k = 1; k < cands.size(); ++k)
+    if ((rc = upload_tree(c.d, w, r, cands[k]))) return rc;
+  const uint32_t nb = s->blocks_x * s->blocks_y;
+  rc = sol_set_partition(s, 0, (int)std::max(1u, nb / 256u));
+  size_t pick = 0, current = 0;  // `current`: the candidate whose arrays the scene holds at the moment
+  auto swap_in = [&](size_t k) {  // hand the scene's tree back to its candidate, take candidate k's
+    if (k == current) return;
+    std::swap(s->tree, cands[current].dev);
+    std::swap(s->tree, cands[k].dev);
+    bind_tree(s);
+    current = k;
   };
-  struct ProofJoin { std::future<void>& f; ~ProofJoin() { if (f.valid()) f.wait(); } } proof_join{background_proof};  // (an early return must not leave the thread behind)
-  // Cost probe: per 8x8 block, the ray count of the longest 4-sample item in a counted render of the whole frame, for the
-  // heavy-first work order
-  // (rebuild_order; sol_path.h decode_item_ordered). SOL_ORDER=0 switches it off.
-  if (!opt.no_work_order_probe && ovr.order_mode != 0 && s->blocks_x * s->blocks_y >= 64u) {
-    const uint32_t nb = s->blocks_x * s->blocks_y;
-    uint32_t* cost_dev = nullptr;
-    HIP_TRY(hipMalloc((void**)&cost_dev, (size_t)nb * sizeof(uint32_t)));
-    hipError_t e = hipMemset(cost_dev, 0, (size_t)nb * sizeof(uint32_t));
-    uint32_t* work_dev = nullptr;
-    if (e == hipSuccess) e = hipMalloc((void**)&work_dev, (size_t)nb * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemset(work_dev, 0, (size_t)nb * sizeof(uint32_t));
-    S.block_cost = cost_dev;
-    S.block_work = work_dev;
-    rc = e == hipSuccess ? sol_render_impl(s, 0, 4, 0xC057ull, true) : SOL_EDEVICE;
-    if (int rb = adopt_background()) { if (rc == SOL_OK) rc = rb; }
-    S.block_cost = nullptr;
-    S.block_work = nullptr;
-    s->block_cost.assign(nb, 0u);
-    s->block_work.assign(nb, 0u);
-    if (rc == SOL_OK && hipMemcpy(s->block_work.data(), work_dev, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = SOL_EDEVICE;
-    if (work_dev) hipFree(work_dev);
-    if (rc == SOL_OK && hipMemcpy(s->block_cost.data(), cost_dev, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = SOL_EDEVICE;
-    hipFree(cost_dev);
-    if (rc != SOL_OK) return rc == SOL_EDEVICE ? sol_fail(SOL_EDEVICE, "cost probe failed") : rc;
-    // The fine tail takes an item fetch per SAMPLE (a dependent load, three integer divisions: ~2 us): worth it where a sample
-    // is long. MI355X, 1080p x 64 spp, ms with 0 / 1 / 2 whole items per lane in the tail: C3 (38 node visits per sample) 76.5 /
-    // 75.5 / 74.4, C2 (22) 45.5 / 45.7 / 46.3, C1 (2) 10.5 / 11.2 / 11.8.
-    // Round 5, re-measured on the round-4 trees and kernel (profiles/r05_fine_tail_sweep.txt; 64 spp, ms with a tail of 0 / 2 / 4 / 8 / 16 whole
-    // items per lane): C1 (2 node visits per sample) 9.09 / 9.07 / 9.66 / 9.74 / 9.65, test scene (8) 9.75 / 8.33 / 8.39 / 8.28 / 8.16, C5 (12) 37.9 /
-    // 38.2 / 38.8 / 38.2 / 38.3, C2 (19) 33.7 / 32.5 / 31.5 / 31.4 / 31.3, C3 (36) 62.5 / 60.5 / 60.5 / 60.6 / 60.6: the per-sample fetch no longer
-    // costs what it did (the reservoir, the work order), a short launch of long paths gains most. By the probe's node visits per sample:
-    // below 5 none, 15 .. 30 eight whole items per lane, else two.
-    if (s->stats.samples > 0) {
-      const double vps = (double)s->stats.node_visits / (double)s->stats.samples;
-      s->fine_tail_auto = vps < 5.0 ? 0 : (vps >= 15.0 && vps < 30.0) ? 32 : 8;
-    }
-    s->stats = SolStats{};
-    if ((rc = sol_clear(s)) || (rc = sol_rebuild_order(s))) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (ovr.verbose) std::fprintf(stderr, "[solstrale] work order: %u of %u blocks heavy (first)\n", S.n_first, s->n_local_blocks);
+  for (size_t k = 0; k < cands.size() && !rc; ++k) {
+    swap_in(k);
+    if (!(rc = sol_clear(s)) && !(rc = sol_render_probe(s)))
+      cands[k].cost = 2.5 * (double)s->stats.node_visits + (double)(s->stats.sphere_tests + s->stats.quad_tests + s->stats.triangle_tests);
+    if (!rc && cands[k].cost < cands[pick].cost) pick = k;
   }
-  if ((rc = adopt_background())) return rc;  // (no cost probe ran: the proof is adopted here)
+  if (c.ovr.verbose) {
+    std::fprintf(stderr, "[solstrale] world tree probe:");
+    for (auto& t : cands) std::fprintf(stderr, " %s %.4g (%zu nodes)", t.name.c_str(), t.cost, t.lay.nodes.size());
+    std::fprintf(stderr, " -> %s\n", cands[pick].name.c_str());
+  }
+  if (hipStreamSynchronize(s->stream) != hipSuccess && !rc) rc = SOL_EDEVICE;
+  swap_in(pick);
+  chosen = pick;
+  s->tree_name = cands[pick].name;
+  adopt_build_info(s, cands[pick].built);
+  for (auto& t : cands) t.dev.release();  // (the losers' arrays: not kept until the candidates go)
+  if (rc) return rc;
+  s->stats = SolStats{};
+  if ((rc = sol_set_partition(s, 0, 1)) || (rc = sol_clear(s))) return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return SOL_OK;
+}
+// 11. Background blocks: constant background only (an environment map is looked up per ray). The proof is host work (0.06 s for C5 at 1080p): it
+// runs on a thread of its own beside the cost probe's render and is adopted after it (the probe traces every block either way).
+struct BackgroundProof {
+  std::future<void> job; std::vector<uint8_t> block; uint32_t n = 0, pixels = 0;
+  void start(const TreeCand& t, const DCamera& cam, uint32_t width, uint32_t height, double margin) {
+    job = std::async(std::launch::async, [this, &t, cam, width, height, margin]() { find_background_blocks(t.lay, t.emin, cam, width, height, margin, block, n, pixels); });
+  }
+  int adopt(SolScene* s, bool verbose) {  // (waits for the proof; idempotent)
+    if (!job.valid()) return SOL_OK;
+    job.get();
+    s->background_block = std::move(block); s->n_background = n; s->background_pixels = pixels;
+    if (verbose) std::fprintf(stderr, "[solstrale] background blocks: %u of %u (%u pixels)\n", s->n_background, s->blocks_x * s->blocks_y, s->background_pixels);
+    if (s->n_background == 0) { s->background_block.clear(); return SOL_OK; }
+    return sol_rebuild_order(s);  // (also without the cost probe)
+  }
+  ~BackgroundProof() { if (job.valid()) job.wait(); }  // (an early return must not leave the thread behind)
+};
+// Cost probe: per 8x8 block, the ray count of the longest 4-sample item in a counted render of the whole frame, for the
+// heavy-first work order (rebuild_order; sol_path.h decode_item_ordered). SOL_ORDER=0 switches it off.
+static int probe_work_order(const CreateCtx& c, SolScene* s, BackgroundProof& proof) {
+  DevScene& S = s->S;
+  const uint32_t nb = s->blocks_x * s->blocks_y;
+  uint32_t* cost_dev = nullptr;
+  HIP_TRY(hipMalloc((void**)&cost_dev, (size_t)nb * sizeof(uint32_t)));
+  hipError_t e = hipMemset(cost_dev, 0, (size_t)nb * sizeof(uint32_t));
+  uint32_t* work_dev = nullptr;
+  if (e == hipSuccess) e = hipMalloc((void**)&work_dev, (size_t)nb * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(work_dev, 0, (size_t)nb * sizeof(uint32_t));
+  S.block_cost = cost_dev;
+  S.block_work = work_dev;
+  int rc = e == hipSuccess ? sol_render_impl(s, 0, 4, 0xC057ull, true) : SOL_EDEVICE;
+  if (int rb = proof.adopt(s, c.ovr.verbose)) { if (rc == SOL_OK) rc = rb; }
+  S.block_cost = nullptr;
+  S.block_work = nullptr;
+  s->block_cost.assign(nb, 0u);
+  s->block_work.assign(nb, 0u);
+  if (rc == SOL_OK && hipMemcpy(s->block_work.data(), work_dev, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = SOL_EDEVICE;
+  if (work_dev) hipFree(work_dev);
+  if (rc == SOL_OK && hipMemcpy(s->block_cost.data(), cost_dev, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = SOL_EDEVICE;
+  hipFree(cost_dev);
+  if (rc != SOL_OK) return rc == SOL_EDEVICE ? sol_fail(SOL_EDEVICE, "cost probe failed") : rc;
+  // The fine tail takes an item fetch per SAMPLE (a dependent load, three integer divisions: ~2 us): worth it where a sample
+  // is long. MI355X, 1080p x 64 spp, ms with 0 / 1 / 2 whole items per lane in the tail: C3 (38 node visits per sample) 76.5 /
+  // 75.5 / 74.4, C2 (22) 45.5 / 45.7 / 46.3, C1 (2) 10.5 / 11.2 / 11.8.
+  // Round 5, re-measured on the round-4 trees and kernel (profiles/r05_fine_tail_sweep.txt; 64 spp, ms with a tail of 0 / 2 / 4 / 8 / 16 whole
+  // items per lane): C1 (2 node visits per sample) 9.09 / 9.07 / 9.66 / 9.74 / 9.65, test scene (8) 9.75 / 8.33 / 8.39 / 8.28 / 8.16, C5 (12) 37.9 /
+  // 38.2 / 38.8 / 38.2 / 38.3, C2 (19) 33.7 / 32.5 / 31.5 / 31.4 / 31.3, C3 (36) 62.5 / 60.5 / 60.5 / 60.6 / 60.6: the per-sample fetch no longer
+  // costs what it did (the reservoir, the work order), a short launch of long paths gains most. By the probe's node visits per sample:
+  // below 5 none, 15 .. 30 eight whole items per lane, else two.
+  if (s->stats.samples > 0) {
+    const double vps = (double)s->stats.node_visits / (double)s->stats.samples;
+    s->fine_tail_auto = vps < 5.0 ? 0 : (vps >= 15.0 && vps < 30.0) ? 32 : 8;
+  }
+  s->stats = SolStats{};
+  if ((rc = sol_clear(s)) || (rc = sol_rebuild_order(s))) return rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (c.ovr.verbose) std::fprintf(stderr, "[solstrale] work order: %u of %u blocks heavy (first)\n", S.n_first, s->n_local_blocks);
+  return SOL_OK;
+}
+
+extern "C" {
+
+// The struct has no size field of its own and grew in round 4 (the three split counters): the plain entry point keeps writing the FIRST
+// LAYOUT (through leaf_area, SOL_TREE_CHECK_V1_BYTES) so that a binding compiled against that header is not overrun; callers of this
+// header pass their struct's size to sol_world_tree_check_ex and get every field that fits.
+int sol_world_tree_check_ex(const SolSceneDesc* d, int use_sah, void* out, size_t out_size) {
+  if (!out || out_size < SOL_TREE_CHECK_V1_BYTES) return sol_fail(SOL_EINVAL, "sol_world_tree_check_ex: out is null or smaller than the first layout (%d bytes)", (int)SOL_TREE_CHECK_V1_BYTES);
+  SolTreeCheck full{};  // (zero where world_tree_check refuses before filling it)
+  const int rc = world_tree_check(d, use_sah, &full);
+  std::memset(out, 0, out_size);
+  std::memcpy(out, &full, std::min(out_size, sizeof full));
+  return rc;
+}
+int sol_world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* out) { return sol_world_tree_check_ex(d, use_sah, out, SOL_TREE_CHECK_V1_BYTES); }
+
+// Diagnostic, host only: the background blocks sol_scene_create would find with the host-built tree `use_sah` names (as in
+// sol_world_tree_check; the proof does not depend on which tree carries it, the count may).
+int sol_background_blocks(const SolSceneDesc* d, int use_sah, uint8_t* flags, size_t n_flags, uint32_t* n_found) {
+  if (!d || !n_found || use_sah < 0) return sol_fail(SOL_EINVAL, "bad argument");
+  *n_found = 0;
+  if (d->width < 2 || d->height < 2 || (uint64_t)d->width * d->height > 0x3FFFFFFFull) return sol_fail(SOL_EINVAL, "bad image size %ux%u", d->width, d->height);
+  const uint32_t nb = ((d->width + SOL_TILE - 1) / SOL_TILE) * ((d->height + SOL_TILE - 1) / SOL_TILE);
+  if (flags && n_flags < nb) return sol_fail(SOL_EINVAL, "%zu flags for %u blocks", n_flags, nb);
+  const SolDevOverrides ovr = sol_dev_overrides();
+  World w(*d);
+  HostTree tree;
+  if (int rc = diag_world(*d, use_sah, ovr, w, tree, nullptr)) return rc;
+  std::vector<uint8_t> f(nb, 0);
+  uint32_t pixels = 0;
+  if (!has_environment(*d)) find_background_blocks(tree.lay, tree.emin, cast_camera(d->camera), d->width, d->height, 64.0 * (double)w.box_pad, f, *n_found, pixels);
+  if (flags) std::memcpy(flags, f.data(), nb);
+  return SOL_OK;
+}
+
+int sol_scene_create(const SolSceneDesc* d, int device, SolScene** out) { return sol_scene_create_ex(d, device, nullptr, out); }
+
+int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOptions* opt_in, SolScene** out) {
+  if (!d || !out) return sol_fail(SOL_EINVAL, "null argument");
+  *out = nullptr;
+  CreateCtx c{*d, sol_dev_overrides()};
+  int rc;
+  if ((rc = check_options_and_header(c, opt_in))) return rc;
+  HostRecords rec;
+  if ((rc = cast_materials(d, rec)) || (rc = cast_primitives(d, rec))) return rc;
+  c.say("records cast");
+  World world(*d);
+  if ((rc = resolve_world(c, world, rec))) return rc;
+  std::vector<TreeCand> cands;  // candidate 0: the provisional choice
+  // AUTO = the device build: as good a tree as the probed host candidates (node visits per ray, host probe / device: C2 11.0 /
+  // 10.9, C3 12.8 / 13.0, C5 6.8 / 6.9) in a sixth to an eighth of the time (sol_scene_create, C3: 0.40 s -> 0.06 s, C5 2.2 s -> 0.3 s)
+  static const char* const tree_names[] = {"device", "ref", "sah8", "sah16", "sah64", "device", ""};
+  std::string want = !c.ovr.bvh.empty() ? c.ovr.bvh : tree_names[c.opt.world_tree];  // (SOL_BVH: developer override of SolCreateOptions.world_tree)
+  if (want == "host") want = "";  // all host candidates + the probe
+  if (want != "device" && (rc = host_candidates(c, world, want, cands))) return rc;
+  const double t_host_trees = seconds_since(c.t_begin);
+  c.say("host part done");
+  if ((rc = check_lights(d, rec))) return rc;
+  ScenePtr scene;
+  std::chrono::steady_clock::time_point t_upload0;
+  if ((rc = open_device(device, scene, t_upload0))) return rc;
+  SolScene* s = scene.get();
+  s->build_times[0] = t_host_trees;
+  if (want == "device" && (rc = device_candidates(c, world, rec.tris, s, cands))) return rc;
+  if ((rc = upload_scene(c, world, rec, s, cands[0]))) return rc;
+  s->build_times[1] = seconds_since(t_upload0) - s->build_times[2];
+  const auto t_probe0 = std::chrono::steady_clock::now();
+  if ((rc = set_scene_constants(c, world, s, cands[0]))) return rc;
+  size_t chosen = 0;
+  if (cands.size() > 1 && (rc = probe_candidates(c, world, rec, s, cands, chosen))) return rc;
+  BackgroundProof proof;  // (after `cands`: it reads the chosen candidate's layout until it is joined)
+  if (!c.opt.no_background_blocks && c.ovr.background_blocks != 0 && !c.has_env)
+    proof.start(cands[chosen], s->S.cam, d->width, d->height, 64.0 * (double)world.box_pad);
+  if (!c.opt.no_work_order_probe && c.ovr.order_mode != 0 && s->blocks_x * s->blocks_y >= 64u && (rc = probe_work_order(c, s, proof))) return rc;
+  if ((rc = proof.adopt(s, c.ovr.verbose))) return rc;  // (no cost probe ran: the proof is adopted here)
   s->build_times[3] = seconds_since(t_probe0);
-  cleanup.keep = true;
-  *out = s;
+  *out = scene.release();
   return SOL_OK;
 }
 

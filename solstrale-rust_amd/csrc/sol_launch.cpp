@@ -42,7 +42,7 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   if (env || lt) version = 1;
   // version 4, the pool kernel (sol_pool.hip): plain renders of the path-tracing... any shader; counted renders (probes, statistics) and trees
   // of 2^17 wide nodes or more (its one-dword node groups carry a 17-bit base) stay with the one-path-per-lane kernel
-  if (version == 4 && ((count && !std::getenv("SOL_POOL_COUNT")) || s->n_wide >= SOL_PACK_MAX_NODES)) version = 1;  // (SOL_POOL_COUNT: phase statistics of the pool kernel)
+  if (version == 4 && ((count && !std::getenv("SOL_POOL_COUNT")) || s->tree.n_wide >= SOL_PACK_MAX_NODES)) version = 1;  // (SOL_POOL_COUNT: phase statistics of the pool kernel)
   // one launch of the pool kernel stages ONE COLOUR PER SAMPLE: a long sample range goes through several launches (chunk-aligned, so the sums
   // do not depend on the split), each within the staging budget
   if (version == 4) {
@@ -92,10 +92,10 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   if (grid > need_blocks) grid = need_blocks;
   P.total_threads = grid * SOL_WG;
   uint32_t lds_depth = (uint32_t)SOL_LDS_STACK;
-  uint32_t stack_need = s->tree_depth;  // dwords of traversal stack a search of this scene can use
+  uint32_t stack_need = s->tree.depth;  // dwords of traversal stack a search of this scene can use
 #ifdef SOL_AB_KERNELS
   // (swap_min: lanes waiting before an exchange pass of the search loop; 64 = only when the wave would otherwise leave for the service block, the best setting measured)
-  if (version == 4) { lds_depth = (uint32_t)sol_pool4_lds_stack_depth(); stack_need = s->packed_depth; P.swap_min = s->pool_swap_min ? s->pool_swap_min : 64u; }
+  if (version == 4) { lds_depth = (uint32_t)sol_pool4_lds_stack_depth(); stack_need = s->tree.packed_depth; P.swap_min = s->pool_swap_min ? s->pool_swap_min : 64u; }
   if (version == 3) lds_depth = (uint32_t)sol_wf_lds_stack_depth();
   if (version == 3) {
     // one global pool: enough slots that the trace kernel has >= 16 rays per resident lane, never more than the items
@@ -397,9 +397,9 @@ int sol_debug_path(SolScene* s, uint32_t x, uint32_t y, uint32_t sample, uint64_
     uint32_t ref;
     std::memcpy(&ref, &rows[r * 12 + 7], 4);
     const uint32_t kind = SOL_REF_KIND(ref);
-    const int a = kind == SOL_REF_TRIANGLE ? 0 : kind == SOL_REF_SPHERE ? 1 : kind == SOL_REF_QUAD ? 2 : -1;  // (SolScene::old_index)
-    if (a >= 0 && SOL_REF_INDEX(ref) < s->old_index[a].size()) {
-      ref = SOL_MAKE_REF(SOL_REF_KIND(ref), s->old_index[a][SOL_REF_INDEX(ref)]);
+    const int a = kind == SOL_REF_TRIANGLE ? 0 : kind == SOL_REF_SPHERE ? 1 : kind == SOL_REF_QUAD ? 2 : -1;  // (DevTree::old_index)
+    if (a >= 0 && SOL_REF_INDEX(ref) < s->tree.old_index[a].size()) {
+      ref = SOL_MAKE_REF(SOL_REF_KIND(ref), s->tree.old_index[a][SOL_REF_INDEX(ref)]);
       std::memcpy(&rows[r * 12 + 7], &ref, 4);
     }
   }

@@ -1,7 +1,7 @@
 // sol_scene.h -- the handle behind the C ABI (include/solstrale_hip.h) and what the translation units of libsolstrale_hip.so
 // share: error reporting, the developer overrides (environment variables, parsed in ONE place), the device memory of a scene.
 //   sol_api.cpp     handle life cycle, options, partition, accumulators, read-back, statistics
-//   sol_create.cpp  validation of the flattened scene, conversion to the fp32 device layout (sol_types.h), world tree, upload, probes
+//   sol_create.cpp  sol_scene_create in stages: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h), world-tree candidates, upload, probes; the tree diagnostics
 //   sol_launch.cpp  sol_render* / auxiliary planes / debug hooks: launches of the kernels in sol_render.hip
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
@@ -12,6 +12,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -37,6 +38,9 @@ int sol_upload(const std::vector<T>& host, T** dev) {
   return SOL_OK;
 }
 
+struct SolHipFree { void operator()(void* p) const { hipFree(p); } };
+template <typename T> using DevPtr = std::unique_ptr<T, SolHipFree>;  // an owned device array: freed with its owner, empty after a move
+template <typename T> int sol_upload(const std::vector<T>& host, DevPtr<T>& dev) { T* p = nullptr; const int rc = sol_upload(host, &p); dev.reset(p); return rc; }
 #define SOL_MAX_ITEMS 0xFF000000ull
 
 // Developer overrides: environment variables for experiments and A/B runs, parsed by sol_dev_overrides() - the
@@ -70,16 +74,12 @@ SolDevOverrides sol_dev_overrides();
 // Device memory that depends on the choice of the world tree (sol_scene_create probes several candidates): the 7-wide tree, the
 // primitive arrays in that tree's leaf order and every table holding references into them.
 struct DevTree {
-  DWide* wides = nullptr; uint32_t* leaf_refs = nullptr; DTri* tris = nullptr; DTriShade* tri_shade = nullptr; DQuad* quads = nullptr;
-  DSphere* spheres = nullptr; DNode* nodes = nullptr; DMedium* mediums = nullptr; uint32_t* lights = nullptr;
-  uint32_t emin = 1, depth = 0, root = 0, light0 = 0;
+  DevPtr<DWide> wides; DevPtr<uint32_t> leaf_refs; DevPtr<DTri> tris; DevPtr<DTriShade> tri_shade; DevPtr<DQuad> quads;
+  DevPtr<DSphere> spheres; DevPtr<DNode> nodes; DevPtr<DMedium> mediums; DevPtr<uint32_t> lights;
+  uint32_t emin = 1, depth = 0, root = 0, light0 = 0;  // depth: dwords of traversal stack a search can use (SolSceneInfo::stack_bound)
   uint32_t n_wide = 0, packed_depth = 0;  // wide nodes; stack bound with one-dword node groups (the pool kernel, sol_pool.hip)
-  std::vector<uint32_t> old_tri, old_sphere, old_quad;  // device index -> index in the caller's arrays
-  void release() {
-    void* p[] = {wides, leaf_refs, tris, tri_shade, quads, spheres, nodes, mediums, lights};
-    for (void* q : p) if (q) hipFree(q);
-    *this = DevTree{};
-  }
+  std::vector<uint32_t> old_index[3];  // triangles / spheres / quads: device index -> index in the caller's SolSceneDesc arrays
+  void release() { *this = DevTree{}; }
 };
 
 // Adaptive sampling (sol_adaptive.hip): the session opened by sol_adaptive_begin and ended by sol_clear, sol_render and
@@ -115,19 +115,16 @@ struct SolScene {
   hipStream_t own_stream = nullptr, stream = nullptr;
   DevScene S{};
   DevScene* dscene = nullptr; DevScene S_uploaded{}; bool dscene_valid = false;  // device copy of S (the v1 kernel reads it through a pointer)
-  // owned device buffers
-  std::vector<uint32_t> old_index[3];  // triangles / spheres / quads: device index -> index in the caller's SolSceneDesc arrays
+  DevTree tree;                        // the world tree the handle walks and what hangs on it; S points into it
   std::string tree_name;               // which world tree the handle walks ("ref", "sah8", .., "device")
   std::string tree_note;               // why it is not the one asked for (AUTO: the device build failed), else empty
   uint32_t split_references = 0, split_triangles = 0;  // device build: what triangle pre-splitting added
   float split_area_ratio = 1.f;
   uint32_t reinsertion_moves = 0; float reinsertion_area_ratio = 1.f;  // device build: sub-trees moved; summed inner-node area after / before
-  uint32_t* leaf_refs = nullptr;
-  DNode* nodes = nullptr; DWide* wides = nullptr; DTri* tris = nullptr; DTriShade* tri_shade = nullptr; DQuad* quads = nullptr;
-  DSphere* spheres = nullptr; DMedium* mediums = nullptr; DMat* mats = nullptr; DTex* texs = nullptr;
-  uint8_t* texels = nullptr; uint32_t* lights = nullptr; float* env = nullptr; DTri* light_tri = nullptr;
+  // owned device buffers
+  DMat* mats = nullptr; DTex* texs = nullptr; uint8_t* texels = nullptr; float* env = nullptr; DTri* light_tri = nullptr;
   float* acc_own = nullptr; float* acc = nullptr; size_t acc_floats = 0;
-  float* aux[2] = {nullptr, nullptr}; size_t aux_floats = 0;
+  float* aux[2] = {nullptr, nullptr}; size_t aux_floats = 0;  // albedo / normal accumulators (sol_render_aux), same layout as acc
   uint32_t aux_samples = 0;                 // samples sol_render_aux added since the planes were last cleared (sol_resolve_aux)
   float* aux_img[2] = {nullptr, nullptr};   // row-major albedo / normal planes of sol_resolve_aux (W*H*3 floats each)
   float4* den_buf = nullptr; size_t den_pixels = 0;  // sol_denoise scratch (sol_denoise.hip): 4 float4 per pixel
@@ -138,7 +135,7 @@ struct SolScene {
   std::vector<uint32_t> local_blocks;  // balanced partition: image block of every local block of this rank (empty: b = lb * world + rank)
   uint32_t* block_of_local_dev = nullptr; size_t block_of_local_cap = 0;
   uint32_t* slot_of_block = nullptr;   // balanced partition (device, all blocks): owner * blocks-per-buffer + local block; null: modulo
-  uint32_t* order_dev = nullptr; size_t order_cap = 0;  // DevScene::block_order of the current partition  // albedo / normal accumulators (sol_render_aux), same layout as acc
+  uint32_t* order_dev = nullptr; size_t order_cap = 0;  // DevScene::block_order of the current partition
   float* partial = nullptr; size_t partial_floats = 0;
   int fine_tail = -1;                // SOL_OPT_FINE_TAIL / SOL_FINE_TAIL: quarters of a whole item per resident lane that the end of a launch hands
                                      // out sample by sample; 0: none; -1: by the creation probe's node visits per sample (fine_tail_auto)
@@ -152,8 +149,6 @@ struct SolScene {
   SolPathStats path_stats{};
   bool has_medium = false;
   bool strict_triangles = false;  // the scene has needle triangles: the STRICT kernel variants (sol_render.hip)
-  uint32_t tree_depth = 0;
-  uint32_t n_wide = 0, packed_depth = 0;  // (DevTree) wide nodes of the world tree; stack bound of a search with one-dword node groups
   uint32_t pool_swap_min = 0;             // SOL_POOL_SWAP (pool kernel, RenderParams::swap_min; 0: the default)
   int rank = 0, world = 1;
   uint32_t blocks_x = 0, blocks_y = 0, n_local_blocks = 0;

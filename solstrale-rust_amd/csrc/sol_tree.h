@@ -463,6 +463,40 @@ struct WideBuilder {
   std::vector<DNode> single_;
 };
 
+// A node of the device tree read as the kernel reads it (sol_trace.h: 5-bit exponents over emin, masks and leaf kind in `meta`, plane bytes per slot,
+// child addresses implicit from the two base indices in the slot-7 bytes): the host's ONE decoder - and encoder - of DWide, which the background proof and sol_world_tree_check rely on.
+struct WideView {
+  const DWide& w;
+  float origin[3], scale[3];
+  uint32_t imask, lmask, kind;
+  WideView(const DWide& n, uint32_t emin) : w(n), origin{n.ox, n.oy, n.oz}, imask((n.meta >> 15) & 0x7Fu), lmask((n.meta >> 22) & 0x7Fu), kind((n.meta >> 29) & 3u) {
+    for (int a = 0; a < 3; ++a) { const uint32_t bits = (((n.meta >> (5 * a)) & 31u) + emin) << 23; std::memcpy(&scale[a], &bits, 4); }
+  }
+  bool occupied(int s) const { return ((imask | lmask) >> s) & 1u; }
+  bool inner(int s) const { return (imask >> s) & 1u; }
+  bool leaf(int s) const { return (lmask >> s) & 1u; }
+  void plane_bytes(int s, uint32_t ql[3], uint32_t qh[3]) const {
+    for (int a = 0; a < 3; ++a) { ql[a] = (w.q[2 * a + (s >> 2)] >> (8 * (s & 3))) & 0xFFu; qh[a] = (w.q[6 + 2 * a + (s >> 2)] >> (8 * (s & 3))) & 0xFFu; }
+  }
+  void box(int s, float lo[3], float hi[3]) const {
+    uint32_t ql[3], qh[3];
+    plane_bytes(s, ql, qh);
+    for (int a = 0; a < 3; ++a) { lo[a] = WideBuilder::decode(origin[a], ql[a], scale[a]); hi[a] = WideBuilder::decode(origin[a], qh[a], scale[a]); }
+  }
+  static uint32_t base_inner(const DWide& w) { return (w.q[1] >> 24) | ((w.q[3] >> 24) << 8) | ((w.q[5] >> 24) << 16); }
+  static uint32_t base_prim(const DWide& w) { return (w.q[7] >> 24) | ((w.q[9] >> 24) << 8) | ((w.q[11] >> 24) << 16); }
+  uint32_t inner_index(int s) const { return base_inner(w) + (uint32_t)__builtin_popcount(imask & ((1u << s) - 1u)); }
+  uint32_t prim_index(int s) const { return base_prim(w) + (uint32_t)__builtin_popcount(lmask & ((1u << s) - 1u)); }
+  // the writing side: exponents relative to emin, masks, leaf kind; the base indices in the slot-7 bytes (top byte of each plane array's second word)
+  static uint32_t pack_meta(const uint32_t e[3], uint32_t emin, uint32_t imask, uint32_t lmask, uint32_t leaf_kind) { return (e[0] - emin) | ((e[1] - emin) << 5) | ((e[2] - emin) << 10) | (imask << 15) | (lmask << 22) | (leaf_kind << 29); }
+  static void set_bases(DWide& w, uint32_t inner, uint32_t prim) {
+    for (int k = 0; k < 3; ++k) {
+      w.q[2 * k + 1] = (w.q[2 * k + 1] & 0x00FFFFFFu) | (((inner >> (8 * k)) & 0xFFu) << 24);
+      w.q[6 + 2 * k + 1] = (w.q[6 + 2 * k + 1] & 0x00FFFFFFu) | (((prim >> (8 * k)) & 0xFFu) << 24);
+    }
+  }
+};
+
 // Device form of the wide tree. Depth-first: a node's inner children get consecutive node indices (in slot order), the
 // primitives of a node whose leaves are all triangles (or all spheres, or all quads) get consecutive NEW indices in their
 // array; other nodes list full references (with new indices) in `leaf_refs`. new_of_old / old_of_new are the permutations of
@@ -539,13 +573,9 @@ struct WideLayout {
       o.ox = w.o[0]; o.oy = w.o[1]; o.oz = w.o[2];
       for (int a = 0; a < 3; ++a)
         if (w.e[a] < emin || w.e[a] > emin + 31) { error = "wide-node exponent outside the 5-bit range"; return false; }
-      o.meta = (w.e[0] - emin) | ((w.e[1] - emin) << 5) | ((w.e[2] - emin) << 10) | (imask << 15) | (lmask << 22) | (leaf_kind << 29);
+      o.meta = WideView::pack_meta(w.e, emin, imask, lmask, leaf_kind);
       for (int k = 0; k < 12; ++k) o.q[k] = w.q[k];
-      const uint32_t bi = n_inner ? base_inner : 0u;
-      for (int k = 0; k < 3; ++k) {  // slot-7 bytes: top byte of the second word of each plane array
-        o.q[2 * k + 1] = (o.q[2 * k + 1] & 0x00FFFFFFu) | (((bi >> (8 * k)) & 0xFFu) << 24);
-        o.q[6 + 2 * k + 1] = (o.q[6 + 2 * k + 1] & 0x00FFFFFFu) | (((base_prim >> (8 * k)) & 0xFFu) << 24);
-      }
+      WideView::set_bases(o, n_inner ? base_inner : 0u, base_prim);
       // children in reverse slot order onto the stack: the first child's sub-tree is laid out right behind the sibling block
       uint32_t rank = n_inner;
       for (int s = SOL_WIDE_CHILDREN - 1; s >= 0; --s)
@@ -581,9 +611,9 @@ struct WideLayout {
       stk.pop_back();
       if (it.from >= nodes.size()) { error = "device tree: node index out of range"; return false; }
       DWide w = nodes[it.from];
-      const uint32_t imask = (w.meta >> 15) & 0x7Fu, lmask = (w.meta >> 22) & 0x7Fu, kind = (w.meta >> 29) & 3u;
-      const uint32_t n_inner = (uint32_t)__builtin_popcount(imask), n_leaf = (uint32_t)__builtin_popcount(lmask);
-      const uint32_t bi_from = base_inner(w), bp_from = base_prim(w);
+      const WideView v(nodes[it.from], 1);  // (the scales are not read here: any emin)
+      const uint32_t kind = v.kind, n_inner = (uint32_t)__builtin_popcount(v.imask), n_leaf = (uint32_t)__builtin_popcount(v.lmask);
+      const uint32_t bi_from = WideView::base_inner(w), bp_from = WideView::base_prim(w);
       const uint32_t bi_to = n_inner ? (uint32_t)out.size() : 0u;
       out.resize(out.size() + n_inner);
       uint32_t bp_to = 0;
@@ -608,10 +638,7 @@ struct WideLayout {
             if (place(a, bp_from + r) == 0xFFFFFFFFu) return false;
         }
       }
-      for (int k = 0; k < 3; ++k) {
-        w.q[2 * k + 1] = (w.q[2 * k + 1] & 0x00FFFFFFu) | (((bi_to >> (8 * k)) & 0xFFu) << 24);
-        w.q[6 + 2 * k + 1] = (w.q[6 + 2 * k + 1] & 0x00FFFFFFu) | (((bp_to >> (8 * k)) & 0xFFu) << 24);
-      }
+      WideView::set_bases(w, bi_to, bp_to);
       out[it.to] = w;
       for (uint32_t r = n_inner; r-- > 0;) stk.push_back(Item{bi_from + r, bi_to + r});  // first child's sub-tree right behind the siblings
     }
@@ -644,9 +671,6 @@ struct WideLayout {
     }
     return !nodes.empty();
   }
-  // decode helpers shared with sol_world_tree_check
-  static uint32_t base_inner(const DWide& w) { return (w.q[1] >> 24) | ((w.q[3] >> 24) << 8) | ((w.q[5] >> 24) << 16); }
-  static uint32_t base_prim(const DWide& w) { return (w.q[7] >> 24) | ((w.q[9] >> 24) << 8) | ((w.q[11] >> 24) << 16); }
 };
 
 // Rebuilds the WORLD's binary tree over the same primitives with a binned surface-area heuristic. The closest hit of a

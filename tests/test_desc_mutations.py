@@ -255,3 +255,106 @@ def test_what_the_validation_accepts_renders_without_a_fault(base_gpu, name):
     lib.sol_scene_destroy(hnd)
     print(f"{name}: {accepted} mutated descriptors accepted and rendered")
     assert accepted >= 20 and np.array_equal(before, after, equal_nan=True)
+
+
+# ---- characterisation: which check fires first, with which words ----
+RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "desc_characterisation.json")
+N_RECORDED = 260  # mutations per base scene (about 200 groups)
+LONG_JOBS = ("width", "height", "max_depth")  # (accepted, such a descriptor is a 2^30-pixel frame or a 2^32-deep path: not created on a GPU box)
+HOST_TREES = (_abi.TREE_HOST_PROBE, _abi.TREE_REF)  # sol_scene_create_ex with these builds - and may refuse - the host candidates BEFORE the device is opened
+
+
+def _two_defects(d):
+    """Descriptors with TWO defects, as groups like _mutations': the pair (code, text) names the one sol_scene_create meets first, which
+    pins the order of its checks. (Of the base scenes only test_scene has every table these touch.)"""
+    def m(cont, key, new):
+        return (f"{key}: -> {new!r}", cont, key, _get(cont, key), new)
+    none = _abi.REF_NONE << 28
+    groups = []
+    if d.n_triangles:
+        groups.append([m(d.triangles[d.n_triangles - 1], "material", 1000), m(d.lights, 0, none)])  # a triangle's material / a light
+    groups.append([m(d.textures[0], "kind", 7), m(d, "root", none)])                                # a texture / the empty world
+    groups.append([m(d, "root", none), m(d.lights, 0, none)])                                        # the empty world / a light
+    groups.append([m(d, "n_lights", 0), m(d, "width", 1)])                                           # the image size / no light
+    groups.append([m(d.materials[0], "kind", 99), m(d.textures[0], "kind", 7)])                      # a texture / a material
+    if d.n_quads and d.n_spheres:
+        groups.append([m(d.spheres[0], "material", -1), m(d.quads[0], "material", -1)])              # a quad / a sphere
+    if d.n_mediums:
+        groups.append([m(d.mediums[0], "material", -1), m(d.lights, 0, none)])                       # a medium / a light
+        groups.append([m(d.mediums[0], "material", -1), m(d.mediums[0], "dfs_index", 12345)])        # a medium's material / its number
+    if d.n_quads:
+        groups.append([m(d.quads[0], "dfs_index", 12345), m(d.lights, 0, none)])                     # the numbering / a light
+    return groups
+
+
+def _characterise(lib, sc, groups, recorded=None):
+    """Per group of mutations the (code, sol_last_error() text) of sol_scene_create, sol_world_tree_check, sol_background_blocks and of
+    sol_scene_create_ex with each of HOST_TREES ("" with SOL_OK). `recorded`: where it says SOL_EDEVICE for a creation - valid, and no
+    GPU there - a GPU box creates the scene, which is destroyed again and reported as recorded; LONG_JOBS are not created there, nor
+    are the HOST_TREES creations the CPU half has compared in full. One refusal lies BEHIND the device's opening and so behind a
+    recorded SOL_EDEVICE of the plain creation: the device build cannot make a tree and the host candidates it falls back to cannot
+    either - the answer must then be the RECORDED one of SOL_TREE_HOST_PROBE, the same candidates asked for outright."""
+    from solstrale_amd import device_count
+    gpu = device_count() > 0
+    d = sc.desc
+
+    def create(tree, want):
+        if gpu and want and want[0] == _abi.SOL_EDEVICE and (tree is not None or any(g[2] in LONG_JOBS for g in group)):
+            return want
+        h = C.c_void_p()
+        opt = _abi.SolCreateOptions(size=C.sizeof(_abi.SolCreateOptions), world_tree=tree or 0)
+        rc = lib.sol_scene_create(sc.desc_ptr, 0, C.byref(h)) if tree is None else lib.sol_scene_create_ex(sc.desc_ptr, 0, C.byref(opt), C.byref(h))
+        if rc == _abi.SOL_OK:
+            lib.sol_scene_destroy(h)
+            assert want and want[0] == _abi.SOL_EDEVICE, ("created", [g[0] for g in group], want)
+            return want
+        return [rc, lib.sol_last_error().decode("latin-1")]
+
+    out = []
+    for gi, group in enumerate(groups):
+        for _, cont, key, old, new in group:
+            _put(cont, key, new)
+        try:
+            want = recorded[gi] if recorded else [None] * 5
+            row = [create(None, want[0])]
+            if gpu and recorded and want[0][0] == _abi.SOL_EDEVICE and row[0] == want[3]:
+                row[0] = want[0]  # (the fallback's host candidates refused it, as recorded for SOL_TREE_HOST_PROBE)
+            chk = _abi.SolTreeCheck()
+            rc = lib.sol_world_tree_check(sc.desc_ptr, 0, C.byref(chk))
+            row.append([rc, lib.sol_last_error().decode("latin-1") if rc else ""])
+            nb = ((d.width + 7) // 8) * ((d.height + 7) // 8) if 0 < d.width < 4096 and 0 < d.height < 4096 else 1
+            flags = (C.c_uint8 * max(1, nb))()
+            n = C.c_uint32()
+            rc = lib.sol_background_blocks(sc.desc_ptr, 0, flags, nb, C.byref(n))
+            row.append([rc, lib.sol_last_error().decode("latin-1") if rc else ""])
+            row += [create(tree, w) for tree, w in zip(HOST_TREES, want[3:])]
+        finally:
+            for _, cont, key, old, new in reversed(group):
+                _put(cont, key, old)
+        out.append(row)
+    return out
+
+
+def _recorded_groups(sc, name):
+    return _mutations(sc.desc, np.random.default_rng(SEEDS[name] + 77), N_RECORDED) + _two_defects(sc.desc)
+
+
+@pytest.mark.parametrize("name", list(SEEDS))
+def test_refusals_are_the_recorded_ones(base, name):
+    """Characterisation of the validation's ORDER and WORDS: tests/desc_characterisation.json holds, for 260 seeded mutations per base
+    scene and the descriptors of _two_defects, what the library answered before sol_scene_create became a sequence of stages - return code
+    and sol_last_error() of the three descriptor-taking entry points and of sol_scene_create_ex with SOL_TREE_HOST_PROBE and SOL_TREE_REF
+    ("texts": the distinct messages; per scene one row of five [code, index into texts] per group). Every pair must come back as
+    recorded. A recorded SOL_EDEVICE of a creation means "valid, and no GPU there": with a GPU the scene is created and destroyed
+    instead. The record was written by tests/tools/record_desc_characterisation.py on a box without a GPU, from a build of the commit
+    before the staging (SOLSTRALE_BUILD_DIR); it is not to be regenerated from a later library."""
+    import json
+    with open(RECORD) as f:
+        rec = json.load(f)
+    want = [[[code, rec["texts"][t]] for code, t in row] for row in rec["scenes"][name]]
+    sc = base[name]
+    groups = _recorded_groups(sc, name)
+    assert len(groups) == len(want)
+    got = _characterise(_abi.load_hip(), sc, groups, want)
+    for group, g, w in zip(groups, got, want):
+        assert g == w, ("; ".join(m[0] for m in group), g, w)

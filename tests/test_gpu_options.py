@@ -170,6 +170,30 @@ def test_auto_tree_falls_back_when_the_device_build_cannot_make_a_tree():
         assert not info["tree_fallback"] and info["tree_name"].startswith("device") and info["tree_note"] == ""
 
 
+def test_two_device_candidates_are_probed_and_one_is_swapped_in(monkeypatch):
+    """SOL_PROBE_RADII=1 with SOL_TREE_AUTO: the device build's two clustering radii are both emitted and uploaded, the counted probe
+    decides and the scene swaps the winner's tree in - the one creation path no other test forces (the collapse costs of the test
+    scenes are never 0.4 .. 1.2 % apart). The scene is C3's atrium with 600 triangles: SOL_VERBOSE=1 shows "collapse costs 0.4237 % apart
+    -> both emitted, the probe decides", no "dropped" line, and the probe takes device32 (184 nodes against 186) - the SECOND candidate
+    (the seeded scenes of random_scenes.py have a few dozen primitives: both radii give the same tree and the duplicate is dropped).
+    The frame is the SOL_TREE_DEVICE frame bit for bit, the tree is one of the two candidates and no fallback; a second creation in the
+    same process gives the same frame and the same SolSceneInfo but for the two reinsertion statistics (nothing of the first one's candidates is left behind)."""
+    sc = scenes.sponza_like(RenderConfig(64, 64, 16), n_triangles=600)
+    with DeviceScene(sc, world_tree=_abi.TREE_DEVICE) as ds:
+        want = _frame(ds)
+    monkeypatch.setenv("SOL_PROBE_RADII", "1")
+    seen = []
+    for _ in range(2):
+        with DeviceScene(sc) as ds:  # defaults: SOL_TREE_AUTO
+            info = ds.info()
+            assert info["tree_name"] in ("device8", "device32") and not info["tree_fallback"], info
+            seen.append((info, _frame(ds)))
+    assert (seen[0][1] == want).all() and (seen[1][1] == want).all()
+    # (reinsertion_moves / reinsertion_area_ratio count what the GPU build's reinsertion rounds did: the order its atomics land in moves them)
+    stable = [{k: v for k, v in info.items() if not k.startswith("reinsertion_")} for info, _ in seen]
+    assert stable[0] == stable[1]
+
+
 def test_stack_use_stays_within_the_bound_the_kernel_choice_relies_on():
     """The render kernel without a spill path is chosen from the host's bound on the stack use (SolSceneInfo.stack_bound <=
     lds_stack): in that variant an overflow would silently overwrite other lanes' stacks. A counted render measures the deepest
