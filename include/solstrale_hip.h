@@ -653,6 +653,36 @@ int sol_record_sizes(uint32_t out[6]);
 
 const char* sol_last_error(void);
 
+/* ---- ray queries (EXTENSION, not in the reference) ------------------------------------------------------------------------
+ * Batches of the caller's own rays against the world tree the handle owns: the object under a cursor, a depth map, a visibility or
+ * ambient-occlusion bake, a line-of-sight test - without rendering a frame. A ray is origin + t * direction, t in units of |direction|
+ * (directions are not normalised, as in the reference). It is VALID when every component is finite (tmax may be +inf), the direction is
+ * not zero and 0 <= tmin <= tmax; any other ray is answered SOL_RAY_INVALID by the kernel itself, without a search - no bit pattern faults,
+ * hangs or runs unbounded.
+ *   SOL_QUERY_CLOSEST   one SolRayHit per ray: the primitive with the smallest t in [tmin, tmax] under the world search's own interval test,
+ *                       among equal t the last in depth-first order (the (t, dfs) rule); fp32 rules 1-7 as they are, rule 8
+ *                       not (a query ray leaves no primitive). u, v: barycentrics of a triangle, planar coordinates of a quad, 0 of a
+ *                       sphere; kind: SOL_REF_SPHERE / _QUAD / _TRIANGLE; dfs_index: the primitive's own number in the description (a
+ *                       pre-split triangle's parts carry their original's); material: its record's. A miss: status SOL_RAY_MISS, t = +inf,
+ *                       the other words 0. An invalid ray: status SOL_RAY_INVALID, the other words 0.
+ *   SOL_QUERY_OCCLUDED  one uint32_t status per ray: SOL_RAY_HIT exactly when SOL_QUERY_CLOSEST reports a hit for the same ray (the search
+ *                       stops early where it may).
+ * n == 0 succeeds and does nothing. SOL_EINVAL: n above 2^31, an unknown mode, a null pointer, a scene with a constant medium (its hits are
+ * random draws keyed by a path; a query has none). SOL_EDEVICE without a GPU. A query touches neither the accumulator, the auxiliary planes,
+ * the partition nor an adaptive session, and works for any rank / world (the scene is replicated). */
+typedef struct SolRay { float ox, oy, oz, tmin, dx, dy, dz, tmax; } SolRay;        /* 32 bytes; 16-byte aligned in device memory */
+typedef struct SolRayHit { float t, u, v; uint32_t status, kind, dfs_index, material, reserved; } SolRayHit; /* 32 bytes */
+enum { SOL_QUERY_CLOSEST = 0, SOL_QUERY_OCCLUDED = 1 };
+enum { SOL_RAY_MISS = 0, SOL_RAY_HIT = 1, SOL_RAY_INVALID = 2 };
+/* Device pointers (n SolRay in, n SolRayHit or n uint32_t out, on the scene's device), on the scene's stream, asynchronous. */
+int sol_query_dev(SolScene* scene, int mode, const void* rays_dev, size_t n, void* out_dev);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_query(SolScene* scene, int mode, const SolRay* rays, size_t n, void* out);
+/* Writes the camera rays of the pixels [x0, x1) x [y0, y1) (y counted from the image top), row-major, for (sample, seed) to device memory:
+ * exactly the rays a render's samples start with (the same RNG key and draws), tmin = 0.001, tmax = +inf. Asynchronous on the scene's
+ * stream. SOL_EINVAL: an empty rectangle or one that leaves the frame. */
+int sol_camera_rays(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* rays_dev);
+
 #ifdef __cplusplus
 }
 #endif

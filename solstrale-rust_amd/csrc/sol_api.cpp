@@ -228,7 +228,7 @@ void sol_scene_destroy(SolScene* s) {
   void* ptrs[] = {s->mats, s->texs, s->texels, s->env, s->light_tri,
                   s->acc_own, s->partial, s->image, s->rgb8, s->work, s->spill, s->counters, s->pool, s->queue, s->wf_ctr,
                   s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block, s->env_tables, s->light_tree, s->light_tables,
-                  s->aux_img[0], s->aux_img[1], s->den_buf};
+                  s->aux_img[0], s->aux_img[1], s->den_buf, s->query_in, s->query_out, s->query_spill};
   s->tree.release();
   s->adaptive.release();
   if (s->wf_ctr_host) hipHostFree(s->wf_ctr_host);
@@ -416,6 +416,117 @@ uint32_t sol_max_samples_per_call(const SolScene* s) {
   if (!s || s->n_local_blocks == 0) return 0xFFFFFFFFu;
   const uint64_t chunks = SOL_MAX_ITEMS / ((uint64_t)s->n_local_blocks * 64u);
   return (uint32_t)std::min<uint64_t>(chunks * SOL_CHUNK, 0xFFFFFFF0ull);
+}
+
+}  // extern "C"
+
+// s->dscene = s->S: the kernels that read the scene through a pointer (the product render kernel, the ray queries). Uploaded only when the record
+// differs from the copy on the device (rare: scene creation, an auxiliary render in between); launches already queued may still read the old copy.
+int sol_scene_to_device(SolScene* s) {
+  if (!s->dscene) HIP_TRY(hipMalloc((void**)&s->dscene, sizeof(DevScene)));
+  if (!s->dscene_valid || std::memcmp(&s->S, &s->S_uploaded, sizeof(DevScene)) != 0) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(s->dscene, &s->S, sizeof(DevScene), hipMemcpyHostToDevice));
+    std::memcpy(&s->S_uploaded, &s->S, sizeof(DevScene));
+    s->dscene_valid = true;
+  }
+  return SOL_OK;
+}
+
+// ---- ray queries (include/solstrale_hip.h; kernels: sol_query.hip) ----
+namespace {
+constexpr size_t QUERY_MAX_RAYS = (size_t)1 << 31;
+constexpr size_t QUERY_STAGE_RAYS = (size_t)1 << 22;  // the host route stages at most this many rays at a time (128 MiB each way)
+
+int query_device_check() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
+  return SOL_OK;
+}
+// What both routes refuse, before the device is touched. *go = false: nothing to do (n == 0).
+int query_check(const SolScene* s, const char* fn, int mode, const void* rays, size_t n, const void* out, bool* go) {
+  *go = false;
+  if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
+  if (mode != SOL_QUERY_CLOSEST && mode != SOL_QUERY_OCCLUDED) return sol_fail(SOL_EINVAL, "%s: unknown mode %d (SOL_QUERY_CLOSEST or SOL_QUERY_OCCLUDED)", fn, mode);
+  if (s->has_medium)
+    return sol_fail(SOL_EINVAL, "%s: the scene has a constant medium - its hits are random draws keyed by a path, which a query ray does not have", fn);
+  if (n > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: %zu rays in one call (at most 2^31)", fn, n);
+  if (n == 0) return SOL_OK;
+  if (!rays || !out) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? "ray" : "output");
+  *go = true;
+  return SOL_OK;
+}
+// One launch over n <= 2^31 rays in device memory, on the scene's stream.
+int query_launch(SolScene* s, int mode, const void* rays_dev, size_t n, void* out_dev) {
+  int rc;
+  if ((rc = sol_scene_to_device(s))) return rc;
+  const bool any = mode == SOL_QUERY_OCCLUDED;
+  int bpc = sol_query_blocks_per_cu(any, s->strict_triangles);
+  if (s->max_bpc > 0) bpc = std::max(1, std::min(bpc, s->max_bpc));
+  const uint32_t need_blocks = (uint32_t)((n + SOL_WG - 1) / SOL_WG);
+  const uint32_t grid = std::max(1u, std::min((uint32_t)(s->n_cu * bpc), need_blocks));
+  // the spill tail of THIS grid (the render launch's area is sized for another)
+  const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
+  const size_t spill_words = may_spill ? (size_t)grid * SOL_WG * (s->tree.depth - SOL_LDS_STACK) : 16;
+  if (spill_words > s->query_spill_words) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->query_spill) hipFree(s->query_spill);
+    s->query_spill = nullptr; s->query_spill_words = 0;
+    HIP_TRY(hipMalloc((void**)&s->query_spill, spill_words * sizeof(uint32_t)));
+    s->query_spill_words = spill_words;
+  }
+  HIP_TRY(sol_launch_query(s->dscene, any, may_spill, s->strict_triangles, rays_dev, (uint32_t)n, out_dev, s->query_spill, grid, s->stream));
+  return SOL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sol_query_dev(SolScene* s, int mode, const void* rays_dev, size_t n, void* out_dev) {
+  int rc;
+  bool go;
+  if ((rc = query_device_check()) || (rc = query_check(s, "sol_query_dev", mode, rays_dev, n, out_dev, &go)) || !go) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return query_launch(s, mode, rays_dev, n, out_dev);
+}
+
+int sol_query(SolScene* s, int mode, const SolRay* rays, size_t n, void* out) {
+  int rc;
+  bool go;
+  if ((rc = query_device_check()) || (rc = query_check(s, "sol_query", mode, rays, n, out, &go)) || !go) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t out_bytes = mode == SOL_QUERY_OCCLUDED ? sizeof(uint32_t) : sizeof(SolRayHit);
+  const size_t cap = std::min(n, QUERY_STAGE_RAYS);
+  if (cap > s->query_cap) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (s->query_in) hipFree(s->query_in);
+    if (s->query_out) hipFree(s->query_out);
+    s->query_in = s->query_out = nullptr; s->query_cap = 0;
+    HIP_TRY(hipMalloc(&s->query_in, cap * sizeof(SolRay)));
+    HIP_TRY(hipMalloc(&s->query_out, cap * sizeof(SolRayHit)));
+    s->query_cap = cap;
+  }
+  for (size_t at = 0; at < n; at += cap) {  // (answers are per ray: the split changes nothing)
+    const size_t k = std::min(cap, n - at);
+    HIP_TRY(hipMemcpyAsync(s->query_in, rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
+    if ((rc = query_launch(s, mode, s->query_in, k, s->query_out))) return rc;
+    HIP_TRY(hipMemcpyAsync((char*)out + at * out_bytes, s->query_out, k * out_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  return SOL_OK;
+}
+
+int sol_camera_rays(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* rays_dev) {
+  int rc;
+  if ((rc = query_device_check())) return rc;
+  if (!s || !rays_dev) return sol_fail(SOL_EINVAL, "sol_camera_rays: null %s", !s ? "scene" : "ray pointer");
+  if (x0 >= x1 || y0 >= y1 || x1 > s->S.width || y1 > s->S.height)
+    return sol_fail(SOL_EINVAL, "sol_camera_rays: the rectangle [%u, %u) x [%u, %u) is empty or leaves the %u x %u frame", x0, x1, y0, y1, s->S.width, s->S.height);
+  if ((uint64_t)(x1 - x0) * (y1 - y0) > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "sol_camera_rays: more than 2^31 rays");
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = sol_scene_to_device(s))) return rc;
+  HIP_TRY(sol_launch_camera_rays(s->dscene, x0, y0, x1 - x0, y1 - y0, sample, seed, rays_dev, s->stream));
+  return SOL_OK;
 }
 
 }  // extern "C"

@@ -33,6 +33,12 @@ hipError_t sol_launch_wf_trace(const DevScene& S, const RenderParams& P, void* c
 int sol_wf_trace_blocks_per_cu(bool count, bool medium);
 size_t sol_wf_pool_bytes(uint32_t slots);
 int sol_wf_lds_stack_depth();
+// ---- sol_query.hip: ray queries. rays: n SolRay on the device; out: n SolRayHit, or n status words when `any` ----
+hipError_t sol_launch_query(const DevScene* dS, bool any, bool may_spill, bool strict, const void* rays, uint32_t n, void* out, uint32_t* spill,
+                            uint32_t grid, hipStream_t stream);
+int sol_query_blocks_per_cu(bool any, bool strict);
+hipError_t sol_launch_camera_rays(const DevScene* dS, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, void* rays,
+                                  hipStream_t stream);
 // ---- sol_aux.hip ----
 hipError_t sol_launch_resolve(float* acc, const float* partial, uint32_t n_floats, uint32_t n_chunks, hipStream_t stream);
 hipError_t sol_launch_unpermute(const float* gathered, float* image, uint32_t width, uint32_t height, uint32_t blocks_x,

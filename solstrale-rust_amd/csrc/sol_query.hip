@@ -1,0 +1,209 @@
+// sol_query.hip -- ray queries (include/solstrale_hip.h, sol_query / sol_query_dev / sol_camera_rays): batches of
+// caller-made rays answered by the world search of sol_trace.h - the 7-wide tree, the LDS [level][lane] stack, the octant table and the
+// wave-level stepper the render kernel runs - without a path around them: no shading, no accumulator, no RNG.
+//
+//  sol_query_kernel<ANY, SPILL, STRICT> -- one ray per lane, run to completion, grid-stride over the batch by whole waves. ANY = false
+//    (SOL_QUERY_CLOSEST) writes one SolRayHit per ray, ANY = true (SOL_QUERY_OCCLUDED) one status word and ends a lane's search at its first
+//    accepted primitive. SPILL / STRICT as in sol_render.hip: a tree deeper than the LDS stack, a scene with needle triangles.
+//  sol_camera_rays_kernel -- generate_path (sol_path.h) of a pixel rectangle, written as rays: the render kernel's own camera rays.
+//  (The measured alternative schedule - persistent waves that refill finished lanes from a batch counter - gave the same bytes at half
+//  the rate and is not kept: profiles/ray_queries_ab.txt.)
+//
+// A ray's answer is a function of the ray and the scene alone: the (t, dfs) order of `better` is total, so neither the schedule nor the
+// neighbours in the wave (postponed primitive tests, SOL_PRIM_MIN) can change it.
+#include <hip/hip_runtime.h>
+
+#include "sol_launch.h"
+#include "sol_path.h"
+
+namespace {
+
+struct QueryLane {
+  Trav t;
+  float tmax;         // the ray's own upper end (a search behind a refused needle hit starts over with it)
+  uint32_t index;     // which ray of the batch
+  uint32_t left;      // searches behind a refused hit this ray may still start (closest_hit's guard: 64 searches in all)
+  bool busy;          // the lane holds a ray that is not answered yet
+};
+
+// finite: neither an infinity nor a NaN
+DEV bool query_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
+// a = (origin, tmin), b = (direction, tmax). Valid: every component finite (tmax may be +inf), a direction that is not zero, 0 <= tmin <= tmax
+// (a NaN tmax fails the last comparison, -inf the one before).
+DEV bool query_ray_valid(float4 a, float4 b) {
+  const bool finite = query_finite(a.x) && query_finite(a.y) && query_finite(a.z) && query_finite(a.w) && query_finite(b.x) &&
+                      query_finite(b.y) && query_finite(b.z);
+  const bool dir = b.x != 0.0f || b.y != 0.0f || b.z != 0.0f;
+  return finite && dir && a.w >= 0.0f && a.w <= b.w;
+}
+
+template <bool ANY>
+DEV void query_write(const DevScene& S, const Stack& st, void* __restrict__ out, uint32_t i, uint32_t status, const Hit& h) {
+  if (ANY) {
+    ((uint32_t*)out)[i] = status;
+    return;
+  }
+  sol_v4u w0 = {__float_as_uint(__builtin_huge_valf()), 0u, 0u, status}, w1 = {0u, 0u, 0u, 0u};
+  if (status == SOL_RAY_INVALID) w0.x = 0u;
+  if (status == SOL_RAY_HIT) {
+    const uint32_t kind = SOL_REF_KIND(h.ref), idx = SOL_REF_INDEX(h.ref);
+    // the material of the primitive's own record; a sphere's Hit carries no u, v (whatever an earlier candidate left there is not its)
+    int32_t mat;
+    float u = h.u, v = h.v;
+    if (kind == SOL_REF_TRIANGLE) mat = ldg_i32(&st.tris[idx].mat);
+    else if (kind == SOL_REF_QUAD) mat = ldg_i32(&S.quads[idx].mat);
+    else { mat = ldg_i32(&S.spheres[idx].mat); u = v = 0.0f; }
+    w0.x = __float_as_uint(h.t); w0.y = __float_as_uint(u); w0.z = __float_as_uint(v);
+    w1.x = kind; w1.y = h.dfs; w1.z = (uint32_t)mat;
+  }
+  sol_v4u* o = (sol_v4u*)out + (size_t)i * 2u;
+  o[0] = w0;
+  o[1] = w1;
+}
+
+// Takes ray `i` of the batch into the lane: an invalid ray is answered at once, a valid one starts its search.
+template <bool ANY>
+DEV void query_take(const DevScene& S, const Stack& st, const float4* __restrict__ rays, void* __restrict__ out, uint32_t i, QueryLane& q) {
+  const float4 a = ldg_f4(rays + (size_t)i * 2u), b = ldg_f4(rays + (size_t)i * 2u + 1u);
+  if (!query_ray_valid(a, b)) {
+    Hit none = {};
+    query_write<ANY>(S, st, out, i, SOL_RAY_INVALID, none);
+    return;
+  }
+  trav_begin<true>(q.t, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
+  q.tmax = b.w;
+  q.index = i;
+  q.left = 63u;
+  q.busy = true;
+}
+
+// The lane's search is over (t.cur == REF_DONE). True: the ray is answered and written. False (STRICT): its closest hit was a triangle the
+// consistency rule refuses, and the lane searches the same ray again behind it - at most 63 times, then the ray misses (closest_hit's guard).
+template <bool ANY, bool STRICT>
+DEV bool query_settle(const DevScene& S, const Stack& st, void* __restrict__ out, QueryLane& q) {
+  if (STRICT && SOL_REF_KIND(q.t.h.ref) != SOL_REF_NONE && !trav_accept_or_restart(S, q.t, st)) {
+    q.t.h.t = q.tmax;  // (trav_accept_or_restart starts over with an open interval: the query's own upper end again)
+    if (q.left != 0u) { q.left--; return false; }
+    q.t.cur = REF_DONE;  // (the search state holds no hit after the restart: a miss)
+  }
+  const bool hit = SOL_REF_KIND(q.t.h.ref) != SOL_REF_NONE;
+  query_write<ANY>(S, st, out, q.index, hit ? SOL_RAY_HIT : SOL_RAY_MISS, q.t.h);
+  q.busy = false;
+  return true;
+}
+
+// One step of the wave's searches. ANY: a lane whose search holds an accepted primitive is done - in a scene with needles only when that
+// primitive is not a triangle (a triangle must pass the consistency rule first: its lane runs the bounded closest search to the end, and a
+// sphere or a quad inside the interval stays a hit whatever the rule refuses).
+template <bool ANY, bool STRICT>
+DEV void query_step(const DevScene& S, const Stack& st, const Rng& rng, Counters& cnt, QueryLane& q, bool act) {
+  trav_step_wave<false, false, STRICT>(S, q.t, act, st, rng, 0u, cnt);
+  if (ANY && act) {
+    const uint32_t kind = SOL_REF_KIND(q.t.h.ref);
+    if (kind != SOL_REF_NONE && (!STRICT || kind != SOL_REF_TRIANGLE)) q.t.cur = REF_DONE;
+  }
+}
+
+DEV void query_stack(Stack& st, const DevScene& S, uint32_t* lds_stack, uint8_t* oct_table, uint32_t* spill, uint32_t total_threads, bool may_spill) {
+  const uint32_t tid = threadIdx.x;
+  st.lds = (lds_u32*)lds_stack + tid;
+  st.spill = (SOL_AS1 uint32_t*)spill + (blockIdx.x * SOL_WG + tid);
+  st.stride = total_threads;
+  st.depth = may_spill ? SOL_LDS_STACK : SOL_NO_SPILL;
+  sol_search_context<true>(st, S);
+  sol_fill_oct_table((lds_u8*)oct_table, tid, SOL_WG);
+  st.oct_table = (const lds_u8*)oct_table;
+  st.oct_table_on = true;
+  __syncthreads();
+}
+
+}  // namespace
+
+template <bool ANY, bool SPILL, bool STRICT>
+__global__ void __launch_bounds__(SOL_WG, SOL_V1_MIN_WAVES)
+sol_query_kernel(const DevScene* __restrict__ Sp, const float4* __restrict__ rays, uint32_t n, void* __restrict__ out, uint32_t* __restrict__ spill,
+                 uint32_t total_threads) {
+  const DevScene& S = *Sp;
+  __shared__ uint32_t lds_stack[SOL_LDS_STACK * SOL_WG];
+  __shared__ uint8_t oct_table[SOL_OCT_TABLE_BYTES];
+  Stack st;
+  query_stack(st, S, lds_stack, oct_table, spill, total_threads, SPILL);
+  Counters cnt = {};
+  Rng rng = {};
+  QueryLane q;
+  q.t.cur = REF_DONE;
+  q.busy = false;
+  const uint32_t lane = threadIdx.x & 63u;
+  // whole waves stride over the batch: `base` is the same in every lane of a wave, so the wave's votes see all of its lanes
+  // (n <= 2^31 and the grid holds far fewer than 2^31 threads: base + total_threads does not wrap)
+  for (uint32_t base = blockIdx.x * SOL_WG + (threadIdx.x & ~63u); base < n; base += total_threads) {
+    if (base + lane < n) query_take<ANY>(S, st, rays, out, base + lane, q);
+#if SOL_LOOP_PRIO
+    __builtin_amdgcn_s_setprio(SOL_LOOP_PRIO);
+#endif
+    for (;;) {
+      if (q.busy && q.t.cur == REF_DONE) query_settle<ANY, STRICT>(S, st, out, q);
+      if (sol_ballot(q.busy) == 0ull) break;
+      for (;;) {
+        const bool act = q.t.cur != REF_DONE;  // (a lane without a ray rests at REF_DONE)
+        if (sol_ballot(act) == 0ull) break;
+        query_step<ANY, STRICT>(S, st, rng, cnt, q, act);
+      }
+    }
+#if SOL_LOOP_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
+  }
+}
+
+// One thread per pixel of [x0, x0 + w) x [y0, y0 + h), row-major: the camera ray generate_path makes for (pixel, sample, seed).
+__global__ void __launch_bounds__(256) sol_camera_rays_kernel(const DevScene* __restrict__ Sp, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
+                                                              uint32_t sample, uint32_t seed_lo, uint32_t seed_hi, float4* __restrict__ rays) {
+  const DevScene& S = *Sp;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;  // (w * h <= 2^31: checked by the caller)
+  if (i >= w * h) return;
+  const uint32_t y = i / w, x = i - y * w;
+  Path p = {};
+  Counters cnt = {};
+  generate_path<false>(S, seed_lo, seed_hi, x0 + x, y0 + y, sample, p, cnt);
+  sol_v4f a = {p.o.x, p.o.y, p.o.z, RAY_MIN_F}, b = {p.d.x, p.d.y, p.d.z, __builtin_huge_valf()};
+  sol_v4f* o = (sol_v4f*)rays + (size_t)i * 2u;
+  o[0] = a;
+  o[1] = b;
+}
+
+// ---- launch wrappers (called from sol_api.cpp) ----
+#define QUERY_PICK(K, any, spill, strict, ...)                                         \
+  do {                                                                                 \
+    if (any) { if (spill) { if (strict) K(true, true, true, __VA_ARGS__); else K(true, true, false, __VA_ARGS__); }     \
+               else { if (strict) K(true, false, true, __VA_ARGS__); else K(true, false, false, __VA_ARGS__); } }        \
+    else { if (spill) { if (strict) K(false, true, true, __VA_ARGS__); else K(false, true, false, __VA_ARGS__); }      \
+           else { if (strict) K(false, false, true, __VA_ARGS__); else K(false, false, false, __VA_ARGS__); } }           \
+  } while (0)
+
+hipError_t sol_launch_query(const DevScene* dS, bool any, bool may_spill, bool strict, const void* rays, uint32_t n, void* out, uint32_t* spill,
+                            uint32_t grid, hipStream_t stream) {
+#define QUERY_A(A, SP, ST, ...) hipLaunchKernelGGL((sol_query_kernel<A, SP, ST>), dim3(grid), dim3(SOL_WG), 0, stream, dS, (const float4*)rays, n, out, spill, grid * SOL_WG)
+  QUERY_PICK(QUERY_A, any, may_spill, strict, 0);
+#undef QUERY_A
+  return hipGetLastError();
+}
+
+template <typename K>
+static int query_blocks_per_cu(K kernel) {
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
+  return n;
+}
+int sol_query_blocks_per_cu(bool any, bool strict) {  // (the SPILL = false builds need no more registers or LDS than these)
+  if (any) return strict ? query_blocks_per_cu(sol_query_kernel<true, true, true>) : query_blocks_per_cu(sol_query_kernel<true, true, false>);
+  return strict ? query_blocks_per_cu(sol_query_kernel<false, true, true>) : query_blocks_per_cu(sol_query_kernel<false, true, false>);
+}
+
+hipError_t sol_launch_camera_rays(const DevScene* dS, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, void* rays,
+                                  hipStream_t stream) {
+  const uint32_t n = w * h;
+  hipLaunchKernelGGL(sol_camera_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, dS, x0, y0, w, h, sample, (uint32_t)seed, (uint32_t)(seed >> 32),
+                     (float4*)rays);
+  return hipGetLastError();
+}

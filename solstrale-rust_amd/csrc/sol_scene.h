@@ -194,6 +194,10 @@ struct SolScene {
   size_t light_tree_bytes = 0;
   float* light_tables = nullptr;
   uint32_t light_mode = 0;
+  // Ray queries (sol_query.hip): the handle's staging buffers of the host route (rays in, answers out; query_cap rays each) and
+  // the spill area of the query kernel's own grid. None of them is the render launch's.
+  void* query_in = nullptr; void* query_out = nullptr; size_t query_cap = 0;
+  uint32_t* query_spill = nullptr; size_t query_spill_words = 0;
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
 std::vector<double> sol_light_weights_of(const SolSceneDesc* d);
@@ -201,6 +205,7 @@ std::vector<double> sol_light_weights_of(const SolSceneDesc* d);
 std::string sol_env_refusal(const SolSceneDesc* d);
 
 int sol_rebuild_order(SolScene* s);
+int sol_scene_to_device(SolScene* s);  // s->dscene holds s->S (uploaded when it does not yet)
 int sol_set_partition(SolScene* s, int rank, int world);
 int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count, const SolAdaptiveLaunch* ad = nullptr);
 inline int sol_render_probe(SolScene* s) { return sol_render_impl(s, 0, SOL_CHUNK, 0x50B3ull, true); }

@@ -187,6 +187,22 @@ def denoise_config(iterations=None, sigma_color=None, normal_power=None):
                       normal_power=DENOISE_DEFAULT_NORMAL_POWER if normal_power is None else float(normal_power))
 
 
+SOL_QUERY_CLOSEST, SOL_QUERY_OCCLUDED = 0, 1
+SOL_RAY_MISS, SOL_RAY_HIT, SOL_RAY_INVALID = 0, 1, 2
+
+
+class SolRay(C.Structure):
+    """EXTENSION: a query ray (sol_query): origin + t * direction, t in [tmin, tmax]. Not in ABI_STRUCTS."""
+    _fields_ = [("ox", C.c_float), ("oy", C.c_float), ("oz", C.c_float), ("tmin", C.c_float),
+                ("dx", C.c_float), ("dy", C.c_float), ("dz", C.c_float), ("tmax", C.c_float)]
+
+
+class SolRayHit(C.Structure):
+    """EXTENSION: the answer of SOL_QUERY_CLOSEST to one ray. Not in ABI_STRUCTS."""
+    _fields_ = [("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("status", C.c_uint32), ("kind", C.c_uint32),
+                ("dfs_index", C.c_uint32), ("material", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class SolTreeCheck(C.Structure):
     _fields_ = [("n_wide", C.c_uint32), ("n_leaf_refs", C.c_uint32), ("n_primitives", C.c_uint32), ("depth", C.c_uint32),
                 ("max_children", C.c_uint32), ("box_violations", C.c_uint32), ("leaf_mismatches", C.c_uint32),
@@ -270,6 +286,9 @@ def load_hip():
     _sig(lib, "sol_denoise", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SolDenoise)])
     _sig(lib, "sol_denoise_rgb8", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(SolDenoise),
                                             C.POINTER(C.c_uint8)])
+    _sig(lib, "sol_query_dev", C.c_int, [P, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_query", C.c_int, [P, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_camera_rays", C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p])
     _libs["hip"] = lib
     return lib
 
@@ -284,7 +303,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_adaptive_begin", "sol_adaptive_round", "sol_adaptive_counts", "sol_tonemap_rgb8_adaptive", "sol_adaptive_rescale",
                "sol_env_sampling", "sol_env_sampling_check", "sol_env_tables", "sol_env_eval",
                "sol_light_sampling", "sol_light_sampling_check", "sol_light_weights", "sol_light_tables", "sol_light_tree", "sol_light_eval",
-               "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8"]
+               "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8",
+               "sol_query_dev", "sol_query", "sol_camera_rays"]
 
 
 def load_host():

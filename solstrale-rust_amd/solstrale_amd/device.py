@@ -91,6 +91,7 @@ class DeviceScene:
             self.h = None
             raise DeviceError(rc, self.lib.sol_last_error().decode(errors="replace"))
         self.width, self.height = scene.width, scene.height
+        self.device = int(device)
 
     def _chk(self, rc):
         if rc != 0:
@@ -354,6 +355,54 @@ class DeviceScene:
         out = np.empty((self.height, self.width, 3), dtype=np.uint8)
         self._chk(self.lib.sol_denoise_rgb8(self.h, C.c_void_p(image_ptr), num_samples, C.c_void_p(albedo_ptr), C.c_void_p(normal_ptr),
                                             aux_samples, C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return out
+
+    # ---- ray queries (EXTENSION) ----
+    RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("status", np.uint32), ("kind", np.uint32),
+                              ("dfs_index", np.uint32), ("material", np.uint32), ("reserved", np.uint32)])
+
+    def _query(self, mode, rays):
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: sol_query stages the arrays itself
+            a = np.ascontiguousarray(rays, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError("rays: an [n, 8] float32 array of (origin xyz, tmin, direction xyz, tmax)")
+            out = np.zeros(a.shape[0], dtype=np.uint32 if mode == _abi.SOL_QUERY_OCCLUDED else self.RAY_HIT_DTYPE)
+            self._chk(self.lib.sol_query(self.h, mode, a.ctypes.data, a.shape[0], out.ctypes.data))
+            return out
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
+            raise ValueError("rays: a contiguous [n, 8] float32 tensor on the scene's device")
+        n = int(rays.shape[0])
+        out = torch.empty((n,) if mode == _abi.SOL_QUERY_OCCLUDED else (n, 8), dtype=torch.int32, device=rays.device)
+        torch.cuda.current_stream(rays.device).synchronize()  # (the rays may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_query_dev(self.h, mode, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def closest_hits(self, rays):
+        """sol_query, SOL_QUERY_CLOSEST. A numpy [n, 8] float32 array of (origin xyz, tmin, direction xyz, tmax) goes the host route and
+        returns a structured array (RAY_HIT_DTYPE); a contiguous [n, 8] float32 torch tensor on the scene's device goes through sol_query_dev
+        without a host copy and returns an [n, 8] int32 device tensor of the same eight words (hits_to_numpy views it as the structured
+        array); the call waits for torch's stream before and for the scene's stream after the launch."""
+        return self._query(_abi.SOL_QUERY_CLOSEST, rays)
+
+    def occluded(self, rays):
+        """sol_query, SOL_QUERY_OCCLUDED: one status per ray (SOL_RAY_HIT exactly when closest_hits reports a hit); uint32 array, or an
+        int32 device tensor for a device tensor of rays."""
+        return self._query(_abi.SOL_QUERY_OCCLUDED, rays)
+
+    @classmethod
+    def hits_to_numpy(cls, hits):
+        """The [n, 8] int32 device tensor closest_hits returned, as the structured host array."""
+        return hits.cpu().numpy().view(cls.RAY_HIT_DTYPE).reshape(-1)
+
+    def camera_rays(self, x0, y0, x1, y1, sample, seed):
+        """sol_camera_rays: the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 8] float32 device tensor."""
+        import torch
+        h, w = max(int(y1) - int(y0), 0), max(int(x1) - int(x0), 0)
+        out = torch.empty((h, w, 8), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._chk(self.lib.sol_camera_rays(self.h, x0, y0, x1, y1, sample, seed, C.c_void_p(out.data_ptr())))
+        self.sync()  # (the scene's stream is not torch's)
         return out
 
     BLOOM_DEFAULT_THRESHOLD = 3.0 ** 0.5  # Vec3::new(1., 1., 1.).length() (bloom.rs:39)
