@@ -104,7 +104,7 @@ DEV void query_step(const DevScene& S, const Stack& st, const Rng& rng, Counters
   }
 }
 
-DEV void query_stack(Stack& st, const DevScene& S, uint32_t* lds_stack, uint8_t* oct_table, uint32_t* spill, uint32_t total_threads, bool may_spill) {
+DEV void query_stack(Stack& st, const DevScene& S, uint32_t* lds_stack, uint8_t* oct_table, uint32_t* sel_table, uint32_t* spill, uint32_t total_threads, bool may_spill) {
   const uint32_t tid = threadIdx.x;
   st.lds = (lds_u32*)lds_stack + tid;
   st.spill = (SOL_AS1 uint32_t*)spill + (blockIdx.x * SOL_WG + tid);
@@ -114,6 +114,11 @@ DEV void query_stack(Stack& st, const DevScene& S, uint32_t* lds_stack, uint8_t*
   sol_fill_oct_table((lds_u8*)oct_table, tid, SOL_WG);
   st.oct_table = (const lds_u8*)oct_table;
   st.oct_table_on = true;
+#if SOL_SEL_TABLE
+  sol_fill_sel_table((lds_u32*)sel_table, tid, SOL_WG);
+  st.sel_table = (const lds_u32*)sel_table;
+  st.sel_table_on = true;
+#endif
   __syncthreads();
 }
 
@@ -126,8 +131,9 @@ sol_query_kernel(const DevScene* __restrict__ Sp, const float4* __restrict__ ray
   const DevScene& S = *Sp;
   __shared__ uint32_t lds_stack[SOL_LDS_STACK * SOL_WG];
   __shared__ uint8_t oct_table[SOL_OCT_TABLE_BYTES];
+  __shared__ __attribute__((aligned(16))) uint32_t sel_table[SOL_SEL_TABLE_DWORDS];  // (the node test's permute selectors, as in the render kernel)
   Stack st;
-  query_stack(st, S, lds_stack, oct_table, spill, total_threads, SPILL);
+  query_stack(st, S, lds_stack, oct_table, sel_table, spill, total_threads, SPILL);
   Counters cnt = {};
   Rng rng = {};
   QueryLane q;

@@ -45,6 +45,12 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
   sol_fill_oct_table((lds_u8*)oct_table, tid, SOL_WG);
   st.oct_table = (const lds_u8*)oct_table;
   st.oct_table_on = true;
+#if SOL_SEL_TABLE
+  __shared__ __attribute__((aligned(16))) uint32_t sel_table[SOL_SEL_TABLE_DWORDS];
+  sol_fill_sel_table((lds_u32*)sel_table, tid, SOL_WG);
+  st.sel_table = (const lds_u32*)sel_table;
+  st.sel_table_on = true;
+#endif
   __syncthreads();
   Counters cnt = {};
   const float inf = __builtin_huge_valf();

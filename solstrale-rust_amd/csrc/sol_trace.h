@@ -68,6 +68,10 @@ struct Stack {
   // bound by vector-instruction issue and its LDS pipe idles, so the render kernel trades them for one ds_read_u8.
   const lds_u8* oct_table;
   bool oct_table_on;
+  // Byte-permute selectors of the node test by octant (SOL_SEL_TABLE, sol_fill_sel_table), 384 bytes in LDS, or off: the node test then
+  // picks the near and far plane words with twelve selects in front of the permutes.
+  const lds_u32* sel_table;
+  bool sel_table_on;
 };
 // Fills a workgroup's octant table (all threads call it; the caller synchronises the workgroup before the first search).
 DEV void sol_fill_oct_table(lds_u8* tbl, uint32_t tid, uint32_t n_threads) {
@@ -76,6 +80,24 @@ DEV void sol_fill_oct_table(lds_u8* tbl, uint32_t tid, uint32_t n_threads) {
     uint32_t r = 0u;
     for (uint32_t p = 0; p < 8u; ++p) r |= ((m >> (p ^ oct)) & 1u) << p;
     tbl[i] = (uint8_t)r;
+  }
+}
+// The node test expands two plane bytes into two halves with one byte permute (SOL_H2). A permute reads TWO source words, so it can take the
+// bytes from the low-plane word or from the high-plane word of an axis by its selector alone: "near, bytes 0/1" is 0x0C010C00 (second source)
+// for a positive direction and 0x0C050C04 (first source) for a negative one, far is the other of the two, bytes 2/3 add 0x00020002. The four
+// selectors of an axis depend on the ray's octant only, so they come from a table [axis][octant][near01, near23, far01, far23]: three
+// ds_read_b128 per visit on the idle LDS pipe instead of twelve v_cndmask_b32. The lanes of one read touch at most the eight 16-byte entries
+// of one axis, 128 consecutive bytes: no bank conflict. The bytes selected are the same ones: every hit mask, hence every frame, is unchanged.
+#ifndef SOL_SEL_TABLE
+#define SOL_SEL_TABLE 1  // (0: the selects; profiles/node_visit_ab.txt)
+#endif
+#define SOL_SEL_TABLE_DWORDS 96
+typedef __attribute__((address_space(3))) sol_v4u lds_v4u;
+DEV void sol_fill_sel_table(lds_u32* tbl, uint32_t tid, uint32_t n_threads) {
+  for (uint32_t i = tid; i < SOL_SEL_TABLE_DWORDS; i += n_threads) {
+    const uint32_t axis = i >> 5, oct = (i >> 2) & 7u, far = (i >> 1) & 1u, pair = i & 1u;
+    const uint32_t neg = (oct >> (2u - axis)) & 1u;  // (oct = x<<2 | y<<1 | z)
+    tbl[i] = (0x0C010C00u + pair * 0x00020002u) ^ ((neg ^ far) * 0x00040004u);
   }
 }
 // Fills the scene fields of a search context. PIN keeps the node fields in vector registers (3 VGPRs) by hiding where they came from.
@@ -89,6 +111,8 @@ DEV void sol_search_context(Stack& st, const DevScene& S) {
   st.wide_emin = e + 24u;  // (the node test reads plane bytes as the halves q * 2^-24: the scales carry the 2^24)
   st.oct_table = nullptr;
   st.oct_table_on = false;
+  st.sel_table = nullptr;
+  st.sel_table_on = false;
 }
 #define SOL_NO_SPILL 0x3FFFFFFF  // Stack::depth of a kernel built for searches that fit the LDS stack (a compile-time constant there)
 DEV void stack_store(const Stack& s, int level, uint32_t v) {
@@ -335,9 +359,8 @@ typedef uint32_t sol_h2;
 // The slab tests of one fetched 7-wide node (h = origin + meta, qa / qb / qc = the six plane arrays) for the ray of search `t`:
 // the search's new node group and primitive group.
 template <bool COUNT>
-DEV void wide_node_test(const Stack& st, Trav& t, uint32_t oct, float4 h, uint4 qa, uint4 qb, uint4 qc) {
+DEV void wide_node_test(const Stack& st, Trav& t, uint32_t oct, float4 h, uint4 qa, uint4 qb, uint4 qc, sol_v4u kx, sol_v4u ky, sol_v4u kz) {
   const uint32_t wide_emin = st.wide_emin;
-  const bool sx = (oct & 4u) != 0u, sy = (oct & 2u) != 0u, sz = (oct & 1u) != 0u;
   const uint32_t meta = __float_as_uint(h.w);
   const float scx = __uint_as_float(((meta & 31u) + wide_emin) << 23), scy = __uint_as_float((((meta >> 5) & 31u) + wide_emin) << 23);
   const float scz = __uint_as_float((((meta >> 10) & 31u) + wide_emin) << 23);
@@ -353,24 +376,39 @@ DEV void wide_node_test(const Stack& st, Trav& t, uint32_t oct, float4 h, uint4 
   const float az = (h.z - t.o.z) * ivz, bz = scz * ivz;
   // q words: qa = {lo_x[0..3], lo_x[4..7], lo_y[0..3], lo_y[4..7]}, qb = {lo_z.., lo_z.., hi_x.., hi_x..},
   //          qc = {hi_y.., hi_y.., hi_z.., hi_z..}; near = the plane the ray meets first on that axis
-  const uint32_t nx0 = sx ? qb.z : qa.x, nx1 = sx ? qb.w : qa.y, fx0 = sx ? qa.x : qb.z, fx1 = sx ? qa.y : qb.w;
-  const uint32_t ny0 = sy ? qc.x : qa.z, ny1 = sy ? qc.y : qa.w, fy0 = sy ? qa.z : qc.x, fy1 = sy ? qa.w : qc.y;
-  const uint32_t nz0 = sz ? qc.z : qb.x, nz1 = sz ? qc.w : qb.y, fz0 = sz ? qb.x : qc.z, fz1 = sz ? qb.y : qc.w;
-  {
+#define SOL_WIDE_TEST_ALL                                          \
+    SOL_WIDE_CHILD(6, hnx6, hny6, hnz6, hfx6, hfy6, hfz6, x)        \
+    SOL_WIDE_CHILD(5, hnx45, hny45, hnz45, hfx45, hfy45, hfz45, y)  \
+    SOL_WIDE_CHILD(4, hnx45, hny45, hnz45, hfx45, hfy45, hfz45, x)  \
+    SOL_WIDE_CHILD(3, hnx23, hny23, hnz23, hfx23, hfy23, hfz23, y)  \
+    SOL_WIDE_CHILD(2, hnx23, hny23, hnz23, hfx23, hfy23, hfz23, x)  \
+    SOL_WIDE_CHILD(1, hnx01, hny01, hnz01, hfx01, hfy01, hfz01, y)  \
+    SOL_WIDE_CHILD(0, hnx01, hny01, hnz01, hfx01, hfy01, hfz01, x)
+  if (st.sel_table_on) {
+    // (kx, ky, kz: the selectors {near01, near23, far01, far23} of each axis for this octant, read by wide_visit; first source = the high-plane word)
+#define SOL_P2 __builtin_amdgcn_perm
+    const sol_h2 hnx01 = SOL_P2(qb.z, qa.x, kx.x), hnx23 = SOL_P2(qb.z, qa.x, kx.y), hnx45 = SOL_P2(qb.w, qa.y, kx.x), hnx6 = SOL_P2(qb.w, qa.y, kx.y);
+    const sol_h2 hny01 = SOL_P2(qc.x, qa.z, ky.x), hny23 = SOL_P2(qc.x, qa.z, ky.y), hny45 = SOL_P2(qc.y, qa.w, ky.x), hny6 = SOL_P2(qc.y, qa.w, ky.y);
+    const sol_h2 hnz01 = SOL_P2(qc.z, qb.x, kz.x), hnz23 = SOL_P2(qc.z, qb.x, kz.y), hnz45 = SOL_P2(qc.w, qb.y, kz.x), hnz6 = SOL_P2(qc.w, qb.y, kz.y);
+    const sol_h2 hfx01 = SOL_P2(qb.z, qa.x, kx.z), hfx23 = SOL_P2(qb.z, qa.x, kx.w), hfx45 = SOL_P2(qb.w, qa.y, kx.z), hfx6 = SOL_P2(qb.w, qa.y, kx.w);
+    const sol_h2 hfy01 = SOL_P2(qc.x, qa.z, ky.z), hfy23 = SOL_P2(qc.x, qa.z, ky.w), hfy45 = SOL_P2(qc.y, qa.w, ky.z), hfy6 = SOL_P2(qc.y, qa.w, ky.w);
+    const sol_h2 hfz01 = SOL_P2(qc.z, qb.x, kz.z), hfz23 = SOL_P2(qc.z, qb.x, kz.w), hfz45 = SOL_P2(qc.w, qb.y, kz.z), hfz6 = SOL_P2(qc.w, qb.y, kz.w);
+#undef SOL_P2
+    SOL_WIDE_TEST_ALL
+  } else {
+    const bool sx = (oct & 4u) != 0u, sy = (oct & 2u) != 0u, sz = (oct & 1u) != 0u;
+    const uint32_t nx0 = sx ? qb.z : qa.x, nx1 = sx ? qb.w : qa.y, fx0 = sx ? qa.x : qb.z, fx1 = sx ? qa.y : qb.w;
+    const uint32_t ny0 = sy ? qc.x : qa.z, ny1 = sy ? qc.y : qa.w, fy0 = sy ? qa.z : qc.x, fy1 = sy ? qa.w : qc.y;
+    const uint32_t nz0 = sz ? qc.z : qb.x, nz1 = sz ? qc.w : qb.y, fz0 = sz ? qb.x : qc.z, fz1 = sz ? qb.y : qc.w;
     const sol_h2 hnx01 = SOL_H2(nx0, 0x04010400u), hnx23 = SOL_H2(nx0, 0x04030402u), hnx45 = SOL_H2(nx1, 0x04010400u), hnx6 = SOL_H2(nx1, 0x04030402u);
     const sol_h2 hny01 = SOL_H2(ny0, 0x04010400u), hny23 = SOL_H2(ny0, 0x04030402u), hny45 = SOL_H2(ny1, 0x04010400u), hny6 = SOL_H2(ny1, 0x04030402u);
     const sol_h2 hnz01 = SOL_H2(nz0, 0x04010400u), hnz23 = SOL_H2(nz0, 0x04030402u), hnz45 = SOL_H2(nz1, 0x04010400u), hnz6 = SOL_H2(nz1, 0x04030402u);
     const sol_h2 hfx01 = SOL_H2(fx0, 0x04010400u), hfx23 = SOL_H2(fx0, 0x04030402u), hfx45 = SOL_H2(fx1, 0x04010400u), hfx6 = SOL_H2(fx1, 0x04030402u);
     const sol_h2 hfy01 = SOL_H2(fy0, 0x04010400u), hfy23 = SOL_H2(fy0, 0x04030402u), hfy45 = SOL_H2(fy1, 0x04010400u), hfy6 = SOL_H2(fy1, 0x04030402u);
     const sol_h2 hfz01 = SOL_H2(fz0, 0x04010400u), hfz23 = SOL_H2(fz0, 0x04030402u), hfz45 = SOL_H2(fz1, 0x04010400u), hfz6 = SOL_H2(fz1, 0x04030402u);
-    SOL_WIDE_CHILD(6, hnx6, hny6, hnz6, hfx6, hfy6, hfz6, x)
-    SOL_WIDE_CHILD(5, hnx45, hny45, hnz45, hfx45, hfy45, hfz45, y)
-    SOL_WIDE_CHILD(4, hnx45, hny45, hnz45, hfx45, hfy45, hfz45, x)
-    SOL_WIDE_CHILD(3, hnx23, hny23, hnz23, hfx23, hfy23, hfz23, y)
-    SOL_WIDE_CHILD(2, hnx23, hny23, hnz23, hfx23, hfy23, hfz23, x)
-    SOL_WIDE_CHILD(1, hnx01, hny01, hnz01, hfx01, hfy01, hfz01, y)
-    SOL_WIDE_CHILD(0, hnx01, hny01, hnz01, hfx01, hfy01, hfz01, x)
+    SOL_WIDE_TEST_ALL
   }
+#undef SOL_WIDE_TEST_ALL
   const uint32_t hits = miss;  // (the clamped form shifts in HIT bits)
   const uint32_t imask = (meta >> 15) & 0x7Fu, lmask = (meta >> 22) & 0x7Fu;
   // inner hits into visit order: bit p <- bit p ^ octant (three conditional butterfly stages)
@@ -485,11 +523,18 @@ DEV void wide_visit(Trav& t, const Stack& st, Counters& cnt) {
   const float4* wp = reinterpret_cast<const float4*>(st.wides + idx);
   const float4 h = ldg_f4(wp);
   const uint4 qa = ldg_u4(wp + 1), qb = ldg_u4(wp + 2), qc = ldg_u4(wp + 3);
+  // (the permute selectors are read right behind the node's loads: the s_setprio statement below clobbers memory, so the compiler keeps the three
+  // LDS reads in front of it and they are in flight while the node's lines arrive)
+  sol_v4u kx = {}, ky = {}, kz = {};
+  if (st.sel_table_on) {
+    const lds_v4u* sel = (const lds_v4u*)st.sel_table + oct;
+    kx = sel[0]; ky = sel[8]; kz = sel[16];
+  }
 #if SOL_FETCH_PRIO
   asm volatile("s_setprio %0" ::"n"(SOL_LOOP_PRIO) : "memory");  // (after the loads are issued; asm: the builtin may be moved across them)
 #endif
   if (COUNT) cnt.node_visits++;
-  wide_node_test<COUNT>(st, t, oct, h, qa, qb, qc);
+  wide_node_test<COUNT>(st, t, oct, h, qa, qb, qc, kx, ky, kz);
 }
 
 // One step of a search of the 2-wide DNode tree (the boundary of a constant medium, whose interval includes negative t): visits
