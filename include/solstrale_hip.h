@@ -683,6 +683,35 @@ int sol_query(SolScene* scene, int mode, const SolRay* rays, size_t n, void* out
  * stream. SOL_EINVAL: an empty rectangle or one that leaves the frame. */
 int sol_camera_rays(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* rays_dev);
 
+/* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
+ * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
+ * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every
+ * output of the handle - sol_render + sol_read, sol_render_aux + sol_read_aux, sol_camera_rays, sol_debug_path, queries, adaptive rounds - is
+ * byte-identical to that of a handle freshly created from the same description with `camera` in it and brought to the same options, modes and
+ * partition. The camera is cast to fp32 exactly as sol_scene_create casts it; nothing is validated that creation does not validate.
+ *   Reset: the colour accumulator (also a caller-bound one) and the auxiliary planes with their sample count are zeroed; an open adaptive
+ *          session ends, as after sol_clear. The call waits for the scene's stream first and blocks until it is done.
+ *   Kept:  the tree and every device table, every SOL_OPT_* value, the sol_env_sampling / sol_light_sampling modes and their tables, the stream,
+ *          a bound accumulator, the communicator, the partition in force (rank, world, a balanced table; partition_crc does not change). Every
+ *          rank of a job calls it with the same camera; it is not a collective.
+ *   Background blocks (SolSceneInfo::background_blocks) are proved again for the new camera, on the device, over the tree the handle walks (the
+ *          proof sol_scene_create makes on the host, in the same f64 operations), under creation's conditions: none for a scene with an environment
+ *          map, for a handle created with no_background_blocks, or for a camera whose fp32 rays err by three pixels or more.
+ *          SOL_CAMERA_NO_BACKGROUND_PROOF skips the proof: every block is traced. Images never depend on it.
+ *   Work order: the creation probe's block costs describe the old view and are dropped - launches run in plain chunk-major order, background
+ *          blocks last; the fine tail and the balanced partition keep what creation measured. SOL_CAMERA_REPROBE runs creation's 4-spp cost
+ *          probe again for the new camera (a no-op where creation ran none; SOL_EINVAL while world > 1). Images do not depend on it either.
+ * SOL_EINVAL, before the device is touched: a null scene or camera, a size below 8 or above 4096, unknown flag bits, a non-zero reserved field.
+ * SOL_EDEVICE: runtime errors; the handle is then as it was, or has the new camera and no background table - never the new camera with the
+ * old table. With sol_kernel_timing on, sol_last_kernel_ms after a call without SOL_CAMERA_REPROBE is the proof kernel's duration. */
+#define SOL_CAMERA_NO_BACKGROUND_PROOF 1u  /* do not look for background blocks for the new camera (every block is traced) */
+#define SOL_CAMERA_REPROBE             2u  /* run the creation's 4-spp cost probe again for the new camera */
+typedef struct SolCameraUpdate { uint32_t size, flags, reserved[2]; } SolCameraUpdate;   /* NULL = all zero */
+int sol_scene_set_camera(SolScene* scene, const SolCamera* camera, const SolCameraUpdate* update);
+/* Diagnostic: the background-block flags in force (row-major over 8x8 blocks, as sol_background_blocks writes them) and their number. flags may be
+ * NULL. SOL_EINVAL: a null scene, a null n_found, n_flags below the block count when flags is not NULL. */
+int sol_scene_background_flags(const SolScene* scene, uint8_t* flags, size_t n_flags, uint32_t* n_found);
+
 #ifdef __cplusplus
 }
 #endif

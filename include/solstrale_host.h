@@ -67,6 +67,10 @@ const SolSceneDesc* solh_finish(SolhBuilder* b, int world, uint32_t width, uint3
                                 uint32_t max_depth, const double background[3], double vertical_fov_degrees,
                                 double aperture_size, const double look_from[3], const double look_at[3],
                                 const double up[3]);
+/* Camera::new (src/camera.rs:47-74) on its own: exactly the bytes solh_finish puts into SolSceneDesc.camera for the same frame size and
+ * CameraConfig - the argument of sol_scene_set_camera (solstrale_hip.h). Needs no builder. Negative for a null pointer. */
+int solh_camera(uint32_t width, uint32_t height, double vertical_fov_degrees, double aperture_size, const double look_from[3],
+                const double look_at[3], const double up[3], SolCamera* out);
 /* deepest Bvh nesting of the flattened tree (information for the device stack) */
 /* EXTENSION, not in the reference: a latitude-longitude environment map (width * height * 3 floats, linear radiance, row 0 =
  * up) that rays which hit nothing return, scaled, instead of Scene.background_color (SolSceneDesc.env_*). Before solh_finish. */

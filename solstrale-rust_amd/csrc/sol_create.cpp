@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "sol_build.h"
+#include "sol_camera.h"
 #include "sol_scene.h"
 #include "sol_tree.h"
 
@@ -176,30 +177,18 @@ static void find_background_blocks(const WideLayout& L, uint32_t emin, const DCa
   const uint32_t bx_n = (width + SOL_TILE - 1) / SOL_TILE, by_n = (height + SOL_TILE - 1) / SOL_TILE;
   flags.assign((size_t)bx_n * by_n, 0);
   n_found = 0; n_pixels = 0;
-  if (L.nodes.empty() || width < 2 || height < 2 || !(cam.lens_radius >= 0.0f) || !std::isfinite(cam.lens_radius)) return;
+  SolProofCamera pc;  // the per-camera part, shared with the device proof of a camera move (sol_camera.h)
+  if (!sol_proof_camera(cam, width, height, margin, pc) || L.nodes.empty()) return;
   struct V { double x, y, z; };
   auto dot = [](const V& a, const V& b) { return a.x * b.x + a.y * b.y + a.z * b.z; };
   auto cross = [](const V& a, const V& b) { return V{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; };
   auto sub = [](const V& a, const V& b) { return V{a.x - b.x, a.y - b.y, a.z - b.z}; };
-  const V org{cam.ox, cam.oy, cam.oz}, ll{cam.llx, cam.lly, cam.llz}, hh{cam.hx, cam.hy, cam.hz}, vv{cam.vx, cam.vy, cam.vz};
-  const V lu{cam.ux, cam.uy, cam.uz}, lw{cam.wx, cam.wy, cam.wz};
-  // the lens: corners of the square around the disc (one point for a pinhole), and of a larger one for the candidate planes
-  const int n_lens = cam.lens_radius > 0.0f ? 4 : 1;
+  auto vec = [](const double v[3]) { return V{v[0], v[1], v[2]}; };
+  const V org = vec(pc.org), ll = vec(pc.ll), hh = vec(pc.hh), vv = vec(pc.vv);
+  const int n_lens = pc.n_lens;
   V lens[4], lens_wide[4];
-  for (int k = 0; k < 4; ++k) {
-    const double sx = (k == 0 || k == 3) ? -1. : 1., sy = k < 2 ? -1. : 1., r = (double)cam.lens_radius * 1.0001, rw = (double)cam.lens_radius * 1.05;
-    lens[k] = V{org.x + (lu.x * sx + lw.x * sy) * r, org.y + (lu.y * sx + lw.y * sy) * r, org.z + (lu.z * sx + lw.z * sy) * r};
-    lens_wide[k] = V{org.x + (lu.x * sx + lw.x * sy) * rw, org.y + (lu.y * sx + lw.y * sy) * rw, org.z + (lu.z * sx + lw.z * sy) * rw};
-  }
-  // generate_path forms T and the direction T - L in fp32: each component errs by a few ulps of the largest term. In pixels of the
-  // focal plane that is 10^-4 for an ordinary camera; a camera a million units from the origin with a narrow field of view is another
-  // matter - the margin grows with it, and beyond three pixels the proof is not attempted.
-  const double norm_max = std::max(std::max(std::fabs(ll.x), std::max(std::fabs(ll.y), std::fabs(ll.z))) + std::max(std::fabs(hh.x), std::max(std::fabs(hh.y), std::fabs(hh.z))) +
-                                   std::max(std::fabs(vv.x), std::max(std::fabs(vv.y), std::fabs(vv.z))), std::max(std::fabs(org.x), std::max(std::fabs(org.y), std::fabs(org.z)))) + (double)cam.lens_radius * 2.;
-  const double pixel = std::min(std::sqrt(dot(hh, hh)) / (double)(width - 1), std::sqrt(dot(vv, vv)) / (double)(height - 1));
-  const double rounding_px = pixel > 0. ? 8.0 * 1.1920929e-7 * norm_max / pixel : 1e300;
-  if (!(rounding_px < 3.0)) return;
-  const double grow = 1.0 + rounding_px;
+  for (int k = 0; k < 4; ++k) { lens[k] = vec(pc.lens[k]); lens_wide[k] = vec(pc.lens_wide[k]); }
+  const double grow = pc.grow;
   struct Plane { V n; double a; };
   std::vector<uint32_t> stack;
   for (uint32_t by = 0; by < by_n; ++by)
@@ -277,14 +266,6 @@ static void find_background_blocks(const WideLayout& L, uint32_t emin, const DCa
     }
 }
 
-static DCamera cast_camera(const SolCamera& c) {
-  return DCamera{(float)c.origin[0], (float)c.origin[1], (float)c.origin[2],
-                 (float)c.lower_left_corner[0], (float)c.lower_left_corner[1], (float)c.lower_left_corner[2],
-                 (float)c.horizontal[0], (float)c.horizontal[1], (float)c.horizontal[2],
-                 (float)c.vertical[0], (float)c.vertical[1], (float)c.vertical[2],
-                 (float)c.u[0], (float)c.u[1], (float)c.u[2], (float)c.v[0], (float)c.v[1], (float)c.v[2],
-                 (float)c.lens_radius};
-}
 static SolSplitOptions split_options(const SolDevOverrides& ovr, const SolCreateOptions* opt) {
   SolSplitOptions sp;  // (the default: a budget of 30 %, kept when the splits shrink the primitives' summed box area below 85 %)
   if (opt && opt->split_percent < 0) sp.budget = 0.f;
@@ -1120,19 +1101,26 @@ struct BackgroundProof {
 };
 // Cost probe: per 8x8 block, the ray count of the longest 4-sample item in a counted render of the whole frame, for the
 // heavy-first work order (rebuild_order; sol_path.h decode_item_ordered). SOL_ORDER=0 switches it off.
-static int probe_work_order(const CreateCtx& c, SolScene* s, BackgroundProof& proof) {
+// Two halves, so that creation can adopt its host proof between them and a camera move's SOL_CAMERA_REPROBE (sol_camera.cpp) can run both:
+// sol_cost_probe_render makes the counted render into the probe's device tables, sol_cost_probe_adopt takes the render's status `rc`, frees
+// the tables and, where all went well, adopts the costs.
+int sol_cost_probe_render(SolScene* s, SolCostProbe& p) {
   DevScene& S = s->S;
   const uint32_t nb = s->blocks_x * s->blocks_y;
-  uint32_t* cost_dev = nullptr;
-  HIP_TRY(hipMalloc((void**)&cost_dev, (size_t)nb * sizeof(uint32_t)));
-  hipError_t e = hipMemset(cost_dev, 0, (size_t)nb * sizeof(uint32_t));
-  uint32_t* work_dev = nullptr;
-  if (e == hipSuccess) e = hipMalloc((void**)&work_dev, (size_t)nb * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemset(work_dev, 0, (size_t)nb * sizeof(uint32_t));
-  S.block_cost = cost_dev;
-  S.block_work = work_dev;
-  int rc = e == hipSuccess ? sol_render_impl(s, 0, 4, 0xC057ull, true) : SOL_EDEVICE;
-  if (int rb = proof.adopt(s, c.ovr.verbose)) { if (rc == SOL_OK) rc = rb; }
+  HIP_TRY(hipMalloc((void**)&p.cost_dev, (size_t)nb * sizeof(uint32_t)));
+  hipError_t e = hipMemset(p.cost_dev, 0, (size_t)nb * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc((void**)&p.work_dev, (size_t)nb * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemset(p.work_dev, 0, (size_t)nb * sizeof(uint32_t));
+  S.block_cost = p.cost_dev;
+  S.block_work = p.work_dev;
+  return e == hipSuccess ? sol_render_impl(s, 0, 4, 0xC057ull, true) : SOL_EDEVICE;
+}
+int sol_cost_probe_adopt(SolScene* s, SolCostProbe& p, int rc, bool verbose) {
+  DevScene& S = s->S;
+  const uint32_t nb = s->blocks_x * s->blocks_y;
+  uint32_t* const cost_dev = p.cost_dev; uint32_t* const work_dev = p.work_dev;
+  p = SolCostProbe{};
+  if (!cost_dev) return rc;  // (the render half failed before it had a table)
   S.block_cost = nullptr;
   S.block_work = nullptr;
   s->block_cost.assign(nb, 0u);
@@ -1157,7 +1145,7 @@ static int probe_work_order(const CreateCtx& c, SolScene* s, BackgroundProof& pr
   s->stats = SolStats{};
   if ((rc = sol_clear(s)) || (rc = sol_rebuild_order(s))) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
-  if (c.ovr.verbose) std::fprintf(stderr, "[solstrale] work order: %u of %u blocks heavy (first)\n", S.n_first, s->n_local_blocks);
+  if (verbose) std::fprintf(stderr, "[solstrale] work order: %u of %u blocks heavy (first)\n", S.n_first, s->n_local_blocks);
   return SOL_OK;
 }
 
@@ -1231,9 +1219,18 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
   size_t chosen = 0;
   if (cands.size() > 1 && (rc = probe_candidates(c, world, rec, s, cands, chosen))) return rc;
   BackgroundProof proof;  // (after `cands`: it reads the chosen candidate's layout until it is joined)
-  if (!c.opt.no_background_blocks && c.ovr.background_blocks != 0 && !c.has_env)
-    proof.start(cands[chosen], s->S.cam, d->width, d->height, 64.0 * (double)world.box_pad);
-  if (!c.opt.no_work_order_probe && c.ovr.order_mode != 0 && s->blocks_x * s->blocks_y >= 64u && (rc = probe_work_order(c, s, proof))) return rc;
+  // (what a later sol_scene_set_camera must know of this creation: sol_camera.cpp)
+  s->box_pad = world.box_pad;
+  s->background_proof = !c.opt.no_background_blocks && c.ovr.background_blocks != 0 && !c.has_env;
+  s->cost_probe = !c.opt.no_work_order_probe && c.ovr.order_mode != 0;
+  s->verbose = c.ovr.verbose;
+  if (s->background_proof) proof.start(cands[chosen], s->S.cam, d->width, d->height, 64.0 * (double)world.box_pad);
+  if (s->cost_probe && s->blocks_x * s->blocks_y >= 64u) {
+    SolCostProbe probe;
+    rc = sol_cost_probe_render(s, probe);
+    if (int rb = proof.adopt(s, c.ovr.verbose)) { if (rc == SOL_OK) rc = rb; }  // (beside the render; before the costs, whose order puts the background blocks last)
+    if ((rc = sol_cost_probe_adopt(s, probe, rc, c.ovr.verbose))) return rc;
+  }
   if ((rc = proof.adopt(s, c.ovr.verbose))) return rc;  // (no cost probe ran: the proof is adopted here)
   s->build_times[3] = seconds_since(t_probe0);
   *out = scene.release();

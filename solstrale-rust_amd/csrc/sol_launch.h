@@ -39,6 +39,9 @@ hipError_t sol_launch_query(const DevScene* dS, bool any, bool may_spill, bool s
 int sol_query_blocks_per_cu(bool any, bool strict);
 hipError_t sol_launch_camera_rays(const DevScene* dS, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, void* rays,
                                   hipStream_t stream);
+// ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
+struct SolProofCamera;
+hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);
 // ---- sol_aux.hip ----
 hipError_t sol_launch_resolve(float* acc, const float* partial, uint32_t n_floats, uint32_t n_chunks, hipStream_t stream);
 hipError_t sol_launch_unpermute(const float* gathered, float* image, uint32_t width, uint32_t height, uint32_t blocks_x,

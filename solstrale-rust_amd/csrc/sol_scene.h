@@ -3,6 +3,7 @@
 //   sol_api.cpp     handle life cycle, options, partition, accumulators, read-back, statistics
 //   sol_create.cpp  sol_scene_create in stages: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h), world-tree candidates, upload, probes; the tree diagnostics
 //   sol_launch.cpp  sol_render* / auxiliary planes / debug hooks: launches of the kernels in sol_render.hip
+//   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
 // There is NO CPU fallback: without a HIP device every compute entry point fails with SOL_EDEVICE.
@@ -168,6 +169,12 @@ struct SolScene {
   // background; n_background_local: how many of them this rank owns - the LAST so many entries of the work order
   std::vector<uint8_t> background_block;
   uint32_t n_background = 0, n_background_local = 0, background_pixels = 0;
+  // what sol_scene_set_camera (sol_camera.cpp) must remember of the creation: the fp32 box pad (the proof's margin is 64 of
+  // them), whether creation looked for background blocks (no environment map, not switched off) and ran the cost probe, SOL_VERBOSE; and
+  // the device flags its proof kernel writes (one byte per block; allocated by the first move, kept)
+  float box_pad = 0.f;
+  bool background_proof = false, cost_probe = false, verbose = false;
+  uint8_t* proof_flags = nullptr;
   bool background_enabled = true;    // SOL_OPT_BACKGROUND_BLOCKS
   bool background_in_counted = false;  // (value 2) counted renders skip them too: the counters of exactly what a plain render does
   int order_mode = 2;                // (SOL_ORDER) 1: heavy blocks first only; 2: + cost classes within a chunk
@@ -205,6 +212,10 @@ std::vector<double> sol_light_weights_of(const SolSceneDesc* d);
 std::string sol_env_refusal(const SolSceneDesc* d);
 
 int sol_rebuild_order(SolScene* s);
+// The 4-spp cost probe of the whole frame (sol_create.cpp): the counted render, then its adoption (`rc`: the render's status; frees the tables).
+struct SolCostProbe { uint32_t* cost_dev = nullptr; uint32_t* work_dev = nullptr; };
+int sol_cost_probe_render(SolScene* s, SolCostProbe& p);
+int sol_cost_probe_adopt(SolScene* s, SolCostProbe& p, int rc, bool verbose);
 int sol_scene_to_device(SolScene* s);  // s->dscene holds s->S (uploaded when it does not yet)
 int sol_set_partition(SolScene* s, int rank, int world);
 int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count, const SolAdaptiveLaunch* ad = nullptr);

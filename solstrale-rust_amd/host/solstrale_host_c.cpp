@@ -233,6 +233,20 @@ const SolSceneDesc* solh_finish(SolhBuilder* b, int world, uint32_t width, uint3
     return nullptr;
   }
 }
+int solh_camera(uint32_t width, uint32_t height, double vfov, double aperture, const double look_from[3], const double look_at[3], const double up[3],
+                SolCamera* out) {
+  return guarded([&] {
+    if (!look_from || !look_at || !up || !out) throw std::runtime_error("solh_camera: null argument");
+    CameraConfig c;
+    c.vertical_fov_degrees = vfov;
+    c.aperture_size = aperture;
+    c.look_from = v3(look_from);
+    c.look_at = v3(look_at);
+    c.up = v3(up);
+    *out = camera_new(width, height, c);
+    return 0;
+  });
+}
 int solh_environment(SolhBuilder* b, uint32_t width, uint32_t height, const float* rgb, double scale) {
   return guarded([&] {
     if (!rgb || !width || !height) throw std::runtime_error("environment: empty map");

@@ -203,6 +203,14 @@ class SolRayHit(C.Structure):
                 ("dfs_index", C.c_uint32), ("material", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
+
+
+class SolCameraUpdate(C.Structure):
+    """EXTENSION: how sol_scene_set_camera moves the camera of a live scene. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class SolTreeCheck(C.Structure):
     _fields_ = [("n_wide", C.c_uint32), ("n_leaf_refs", C.c_uint32), ("n_primitives", C.c_uint32), ("depth", C.c_uint32),
                 ("max_children", C.c_uint32), ("box_violations", C.c_uint32), ("leaf_mismatches", C.c_uint32),
@@ -289,6 +297,8 @@ def load_hip():
     _sig(lib, "sol_query_dev", C.c_int, [P, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_query", C.c_int, [P, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_camera_rays", C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p])
+    _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
+    _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _libs["hip"] = lib
     return lib
 
@@ -304,7 +314,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_env_sampling", "sol_env_sampling_check", "sol_env_tables", "sol_env_eval",
                "sol_light_sampling", "sol_light_sampling_check", "sol_light_weights", "sol_light_tables", "sol_light_tree", "sol_light_eval",
                "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8",
-               "sol_query_dev", "sol_query", "sol_camera_rays"]
+               "sol_query_dev", "sol_query", "sol_camera_rays", "sol_scene_set_camera", "sol_scene_background_flags"]
 
 
 def load_host():
@@ -340,6 +350,7 @@ def load_host():
     _sig(lib, "solh_bvh_range", I, [B, I, I])
     _sig(lib, "solh_finish", C.POINTER(SolSceneDesc),
          [B, I, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _D3, D, D, _D3, _D3, _D3])
+    _sig(lib, "solh_camera", I, [C.c_uint32, C.c_uint32, D, D, _D3, _D3, _D3, C.POINTER(SolCamera)])
     _sig(lib, "solh_environment", I, [B, C.c_uint32, C.c_uint32, C.c_void_p, D])
     _sig(lib, "solh_tree_depth", C.c_uint32, [B])
     _sig(lib, "solh_ray_trace", I, [B, C.c_uint32, C.c_uint64, I, D, I, PROGRESS_FN, ABORT_FN, C.c_void_p])
@@ -360,7 +371,7 @@ HOST_SYMBOLS = ["solh_builder_new", "solh_builder_free", "solh_last_error", "sol
                 "solh_diffuse_light", "solh_blend", "solh_sphere", "solh_quad", "solh_box", "solh_triangle",
                 "solh_triangles", "solh_spheres", "solh_constant_medium", "solh_bvh", "solh_bvh_range", "solh_finish",
                 "solh_tree_depth", "solh_environment", "solh_ray_trace", "solh_ray_trace_devices", "solh_abi_sizes", "solh_to_rgb_color", "solh_set_post_processors", "solh_load_obj",
-                "solh_set_adaptive", "solh_set_env_sampling", "solh_set_light_sampling"]
+                "solh_set_adaptive", "solh_set_env_sampling", "solh_set_light_sampling", "solh_camera"]
 
 
 def d3(v):

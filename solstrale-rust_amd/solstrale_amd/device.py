@@ -405,6 +405,27 @@ class DeviceScene:
         self.sync()  # (the scene's stream is not torch's)
         return out
 
+    # ---- a new camera for a live scene (EXTENSION) ----
+    def set_camera(self, camera, background_proof=True, reprobe=False):
+        """sol_scene_set_camera: the same scene from another viewpoint, without building anything again. `camera`: a CameraConfig (cast by
+        host.camera_record for this frame size) or a SolCamera. background_proof=False: do not look for background blocks for the new camera;
+        reprobe=True: run creation's cost probe again. Clears the accumulator and the auxiliary planes, ends an adaptive session; blocks."""
+        if not isinstance(camera, _abi.SolCamera):
+            from .host import camera_record
+            camera = camera_record(self.width, self.height, camera)
+        upd = _abi.SolCameraUpdate(size=C.sizeof(_abi.SolCameraUpdate),
+                                   flags=(0 if background_proof else _abi.SOL_CAMERA_NO_BACKGROUND_PROOF) | (_abi.SOL_CAMERA_REPROBE if reprobe else 0))
+        self._chk(self.lib.sol_scene_set_camera(self.h, C.byref(camera), C.byref(upd)))
+
+    def background_flags(self):
+        """sol_scene_background_flags: the background blocks in force, a bool array [blocks_y, blocks_x] (as background_blocks() returns)."""
+        bx, by = (self.width + 7) // 8, (self.height + 7) // 8
+        flags = np.zeros((by, bx), dtype=np.uint8)
+        n = C.c_uint32()
+        self._chk(self.lib.sol_scene_background_flags(self.h, flags.ctypes.data, flags.size, C.byref(n)))
+        assert int(flags.sum()) == n.value
+        return flags.astype(bool)
+
     BLOOM_DEFAULT_THRESHOLD = 3.0 ** 0.5  # Vec3::new(1., 1., 1.).length() (bloom.rs:39)
     BLOOM_DEFAULT_MAX = 1.7976931348623157e308  # f64::MAX (bloom.rs:40)
 

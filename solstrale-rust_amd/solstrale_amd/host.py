@@ -50,6 +50,17 @@ class CameraConfig:
         self.up = up
 
 
+def camera_record(width, height, camera):
+    """`Camera::new` on its own (solh_camera): the SolCamera that finish() puts into the description for this frame size and CameraConfig,
+    byte for byte - what DeviceScene.set_camera hands to sol_scene_set_camera."""
+    lib = _abi.load_host()
+    out = _abi.SolCamera()
+    if lib.solh_camera(int(width), int(height), camera.vertical_fov_degrees, camera.aperture_size, _abi.d3(camera.look_from),
+                       _abi.d3(camera.look_at), _abi.d3(camera.up), C.byref(out)) != 0:
+        raise HostError(lib.solh_last_error().decode(errors="replace"))
+    return out
+
+
 def NopPostProcessor():
     """src/post/nop.rs:11-17"""
     return (0, (0., 0., 0.))

@@ -642,12 +642,17 @@ def statue_mesh(n_triangles=STATUE_TRIANGLES):
 # ---------------------------------------------------------------------------------------------------------------
 # The reference's test scenes (tests/scenes.rs)
 # ---------------------------------------------------------------------------------------------------------------
+def create_test_scene_camera():
+    """The thin-lens camera of create_test_scene (tests/scenes.rs:19-25)."""
+    return CameraConfig(20., 0.1, (-5., 3., 6.), (.25, 1., 0.), (0., 1., 0.))
+
+
 def create_test_scene(render_config, environment=None):
     """tests/scenes.rs:17-122 (environment = (map, scale): the extension of create_test_scene_with_environment)"""
     b = SceneBuilder()
     if environment is not None:
         b.environment(*environment)
-    cam = CameraConfig(20., 0.1, (-5., 3., 6.), (.25, 1., 0.), (0., 1., 0.))
+    cam = create_test_scene_camera()
     ground = b.Lambertian(b.ImageMap(load_image("textures/tex.jpg")))
     glass = b.Dielectric(b.SolidColor(1., 1., 1.), None, 1.5)
     light = b.DiffuseLight(10., 10., 10.)
