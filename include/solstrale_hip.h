@@ -38,6 +38,7 @@ extern "C" {
 #define SOL_EDEVICE (-3)   /* HIP runtime error / no GPU                                               */
 #define SOL_EDEPTH (-4)    /* BVH deeper than the traversal stack supports                             */
 #define SOL_ENOMEM (-5)
+#define SOL_ERANGE (-6)    /* sol_scene_set_triangles: the moved geometry leaves the exponent range of the tree - re-create the scene */
 
 /* ---- child / primitive references ------------------------------------------------------------------
  * A 32-bit reference: kind in bits 31..28, index into the array of that kind in bits 27..0.
@@ -299,6 +300,10 @@ typedef struct SolCreateOptions {
                                at most 1024 (the rounds end when nothing moves)                                                  */
   int32_t no_background_blocks; /* 1: do not look for background blocks (below, SolSceneInfo::background_blocks)            */
   int32_t reserved[2];
+  int32_t dynamic_triangles; /* 1: the handle keeps what sol_scene_set_triangles needs (per triangle: texture coordinates, material, dfs_index;
+                                the primitives' unpadded fp32 boxes; the tree's levels; staging copies of the tree and the triangle records).
+                                0: nothing of it is allocated and sol_scene_set_triangles is refused                                         */
+  int32_t reserved2;
 } SolCreateOptions;
 int sol_scene_create_ex(const SolSceneDesc* desc, int device, const SolCreateOptions* options, SolScene** out);
 /* Seconds sol_scene_create spent in: [0] host tree candidates, [1] uploads, [2] device tree build, [3] probe renders. */
@@ -711,6 +716,39 @@ int sol_scene_set_camera(SolScene* scene, const SolCamera* camera, const SolCame
 /* Diagnostic: the background-block flags in force (row-major over 8x8 blocks, as sol_background_blocks writes them) and their number. flags may be
  * NULL. SOL_EINVAL: a null scene, a null n_found, n_flags below the block count when flags is not NULL. */
 int sol_scene_background_flags(const SolScene* scene, uint8_t* flags, size_t n_flags, uint32_t* n_found);
+
+/* ---- moving the triangles of a live scene (EXTENSION, not in the reference) ------------------------------------------------
+ * sol_triangle_from_vertices: Triangle::new_with_tex_coords (src/hittable/triangle.rs:53-96) on the CPU, no device needed: fills v0, v0v1, v0v2,
+ * normal, tangent, bi_tangent, area, uv0..2 and bbox of `out` from v = (v0, v1, v2) and uv = (uv0, uv1, uv2), bit for bit as the host library
+ * builds a triangle; material and dfs_index are left as they are. SOL_EINVAL: a null argument.
+ *
+ * sol_scene_set_triangles gives every triangle of a handle created with SolCreateOptions.dynamic_triangles = 1 new vertices: row i of `vertices`
+ * (9 doubles: v0, v1, v2) is triangle i of the creation description. The device computes every triangle record again (the same f64 code as
+ * sol_triangle_from_vertices) and refits the boxes of the tree it walks in place - topology, slots and exponent origin kept. After SOL_OK every
+ * output of the handle (frames, auxiliary planes, sol_camera_rays, queries, sol_debug_path, adaptive rounds, SolSceneInfo::strict_triangles) is
+ * byte-identical to that of a handle freshly created, with the same options, from the description D' in which every SolTriangle is
+ * sol_triangle_from_vertices of its new vertices (uv, material, dfs_index kept) and every SolBvhNode::bbox the union of its children's, then brought
+ * to the same modes, partition and - if the camera was moved - sol_scene_set_camera. The dfs_index numbers stay creation's.
+ *   Reset / kept / background blocks / work order: as sol_scene_set_camera (SOL_GEOM_NO_BACKGROUND_PROOF, SOL_GEOM_REPROBE).
+ *   SOL_EINVAL before the device is touched: null arguments, n != the scene's triangle count, a size below 8 or above 4096, unknown flag bits,
+ *     non-zero reserved words, a handle created without the option, a scene with a constant medium, SOL_GEOM_REPROBE while world > 1.
+ *   Refused with the handle exactly as before (no sums cleared): a non-finite vertex (SOL_EINVAL), coordinates beyond 2^38 (SOL_EINVAL), a node
+ *     extent beyond the tree's exponent range (SOL_ERANGE: re-create the scene).
+ *   Any other failure (SOL_EDEVICE, SOL_ENOMEM: a runtime error after the new records and boxes were adopted, while the light tables, the
+ *     background blocks or the scene record were being made again) leaves a handle that is fit only for sol_scene_destroy.
+ * sol_scene_set_triangles_dev takes the vertices from device memory (16-byte aligned), without a host copy. Both block until done. */
+#define SOL_GEOM_NO_BACKGROUND_PROOF 1u
+#define SOL_GEOM_REPROBE             2u
+typedef struct SolGeometryUpdate { uint32_t size, flags, reserved[2]; } SolGeometryUpdate;   /* NULL = all zero */
+int sol_triangle_from_vertices(const double v[9], const float uv[6], SolTriangle* out);
+int sol_scene_set_triangles(SolScene* scene, const double* vertices, uint32_t n, const SolGeometryUpdate* update);
+int sol_scene_set_triangles_dev(SolScene* scene, const double* vertices_dev, uint32_t n, const SolGeometryUpdate* update);
+/* With sol_kernel_timing on: device-event milliseconds of the last successful sol_scene_set_triangles(_dev) - [0] the upload of the vertices (0 for
+ * the device route), [1] the records and lights kernels, [2] the refit launches, [3] the rest (light tables, background proof, probe, uploads). */
+int sol_scene_set_triangles_ms(const SolScene* scene, float ms[4]);
+/* Diagnostic / tests: copies the triangle records the kernels read (n_records x 48 bytes of intersect records, n_records x 64 bytes of shading
+ * records, in the tree's leaf order) and the caller's triangle index of each to the host; any pointer may be NULL; *n_records: their number. */
+int sol_scene_triangle_records(SolScene* scene, void* tris, void* shade, uint32_t* triangle_of, size_t capacity, uint32_t* n_records);
 
 #ifdef __cplusplus
 }

@@ -228,12 +228,14 @@ void sol_scene_destroy(SolScene* s) {
   void* ptrs[] = {s->mats, s->texs, s->texels, s->env, s->light_tri,
                   s->acc_own, s->partial, s->image, s->rgb8, s->work, s->spill, s->counters, s->pool, s->queue, s->wf_ctr,
                   s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block, s->env_tables, s->light_tree, s->light_tables,
-                  s->aux_img[0], s->aux_img[1], s->den_buf, s->query_in, s->query_out, s->query_spill, s->proof_flags};
+                  s->aux_img[0], s->aux_img[1], s->den_buf, s->query_in, s->query_out, s->query_spill, s->proof_flags, s->dyn.light_tri2};
   s->tree.release();
   s->adaptive.release();
   if (s->wf_ctr_host) hipHostFree(s->wf_ctr_host);
   for (void* p : ptrs)
     if (p) hipFree(p);
+  for (hipEvent_t e : s->dyn.ev)
+    if (e) hipEventDestroy(e);
   if (s->ev_start) hipEventDestroy(s->ev_start);
   if (s->ev_stop) hipEventDestroy(s->ev_stop);
   if (s->own_stream) hipStreamDestroy(s->own_stream);

@@ -43,6 +43,7 @@
 
 #include "../../include/solstrale_hip.h"
 #include "sol_build.h"
+#include "sol_quant.h"
 #include "sol_types.h"
 
 namespace {
@@ -730,18 +731,9 @@ __global__ void __launch_bounds__(64) k_emit(EmitParams P, const Frontier* __res
   uint32_t eb[3];
   float scale[3];
   for (int a = 0; a < 3; ++a) {
-    if (!(hi[a] >= lo[a])) { lo[a] = 0.f; hi[a] = 0.f; }
-    int e = 1;
-    const float ext = hi[a] - lo[a];
-    if (ext > 0.f && ext < __builtin_huge_valf()) {
-      int ex;
-      frexpf(ext / 255.0f, &ex);
-      e = min(254, max(1, ex + 127));
-    }
-    if (e > (int)P.emin + 31) atomicOr(&P.counters[6], 1u);
-    e = max((int)P.emin, min((int)P.emin + 31, e));
-    eb[a] = (uint32_t)e;
-    scale[a] = __uint_as_float(eb[a] << 23);
+    bool over;
+    eb[a] = sol_wide_axis_grid(lo[a], hi[a], P.emin, scale[a], over);  // (sol_quant.h, shared with the refit of sol_geometry.hip)
+    if (over) atomicOr(&P.counters[6], 1u);
   }
   // ---- slots: maximise the summed projections of the child centres on their slots' octant directions (Kuhn-Munkres) ----
   int slot_of[MAXC];
@@ -810,14 +802,10 @@ __global__ void __launch_bounds__(64) k_emit(EmitParams P, const Frontier* __res
     const float* b = P.nbox + (size_t)child[c] * 6;
     for (int a = 0; a < 3; ++a) {
       const float cl = b[2 * a] - 2.0f * pad, chh = b[2 * a + 1] + 2.0f * pad;  // two more pads: the device evaluates the planes in t-space (sol_tree.h)
-      long ql = (long)floorf((cl - lo[a]) / scale[a]), qh = (long)ceilf((chh - lo[a]) / scale[a]);
-      ql = min(255L, max(0L, ql));
-      qh = min(255L, max(0L, qh));
-      while (ql > 0 && lo[a] + (float)ql * scale[a] > cl) --ql;      // conservative under the device's own decode arithmetic
-      while (qh < 255 && lo[a] + (float)qh * scale[a] < chh) ++qh;
-      if (lo[a] + (float)ql * scale[a] > cl || lo[a] + (float)qh * scale[a] < chh) { ql = 0; qh = 255; atomicOr(&P.counters[6], 2u); }
-      q[2 * a + (s >> 2)] |= (uint32_t)ql << (8 * (s & 3));
-      q[6 + 2 * a + (s >> 2)] |= (uint32_t)qh << (8 * (s & 3));
+      uint32_t ql, qh;
+      if (!sol_wide_axis_quantise(cl, chh, lo[a], scale[a], ql, qh)) atomicOr(&P.counters[6], 2u);  // conservative under the device's own decode arithmetic
+      q[2 * a + (s >> 2)] |= ql << (8 * (s & 3));
+      q[6 + 2 * a + (s >> 2)] |= qh << (8 * (s & 3));
     }
   }
   // ---- implicit addresses: consecutive node indices for the inner children, consecutive primitive indices for the leaves ----

@@ -19,7 +19,7 @@ void drop_camera_tables(SolScene* s) {
   s->S.block_order = nullptr; s->S.n_first = 0; s->n_background_local = 0;
 }
 // The flags the proof kernel wrote, adopted as creation adopts the host proof's (BackgroundProof::adopt, sol_create.cpp).
-int adopt_flags(SolScene* s, std::vector<uint8_t>& flags) {
+int adopt_flags(SolScene* s, std::vector<uint8_t>& flags, const char* who) {
   uint32_t n = 0, pixels = 0;
   const uint32_t width = s->S.width, height = s->S.height;
   for (uint32_t by = 0; by < s->blocks_y; ++by)
@@ -31,30 +31,18 @@ int adopt_flags(SolScene* s, std::vector<uint8_t>& flags) {
       n++;
       pixels += (x1 - x0) * (y1 - y0);
     }
-  if (s->verbose) std::fprintf(stderr, "[solstrale] set_camera: background blocks: %u of %u (%u pixels)\n", n, s->blocks_x * s->blocks_y, pixels);
+  if (s->verbose) std::fprintf(stderr, "[solstrale] %s: background blocks: %u of %u (%u pixels)\n", who, n, s->blocks_x * s->blocks_y, pixels);
   if (n == 0) return SOL_OK;
   s->background_block = std::move(flags); s->n_background = n; s->background_pixels = pixels;
   return sol_rebuild_order(s);
 }
 }  // namespace
 
-extern "C" {
-
-int sol_scene_set_camera(SolScene* s, const SolCamera* camera, const SolCameraUpdate* update) {
-  if (!s || !camera) return sol_fail(SOL_EINVAL, "sol_scene_set_camera: null %s", !s ? "scene" : "camera");
-  SolCameraUpdate u{};
-  if (update) {
-    if (update->size < 8 || update->size > 4096) return sol_fail(SOL_EINVAL, "SolCameraUpdate.size %u", update->size);
-    std::memcpy(&u, update, std::min<size_t>(update->size, sizeof u));
-  }
-  if (u.flags & ~(SOL_CAMERA_NO_BACKGROUND_PROOF | SOL_CAMERA_REPROBE)) return sol_fail(SOL_EINVAL, "SolCameraUpdate.flags 0x%x: unknown bits", u.flags);
-  if (u.reserved[0] || u.reserved[1]) return sol_fail(SOL_EINVAL, "SolCameraUpdate.reserved must be 0");
-  const bool reprobe = (u.flags & SOL_CAMERA_REPROBE) != 0;
-  if (reprobe && s->world > 1) return sol_fail(SOL_EINVAL, "SOL_CAMERA_REPROBE: the cost probe renders the whole frame on one rank (world is %d)", s->world);
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipStreamSynchronize(s->stream));  // a launch in flight reads the scene record and the work order
+// The tail of a camera move and of a geometry move (sol_geometry.cpp): the caller has waited for the stream and changed the scene record.
+// flags: SOL_CAMERA_NO_BACKGROUND_PROOF / SOL_CAMERA_REPROBE (= SOL_GEOM_*), checked by the caller.
+int sol_rederive_view_tables(SolScene* s, uint32_t flags, const char* who) {
+  const bool reprobe = (flags & SOL_CAMERA_REPROBE) != 0;
   s->adaptive.open = false;
-  s->S.cam = cast_camera(*camera);
   drop_camera_tables(s);
   HIP_TRY(hipMemsetAsync(s->acc, 0, s->acc_floats * sizeof(float), s->stream));
   int rc;
@@ -62,7 +50,7 @@ int sol_scene_set_camera(SolScene* s, const SolCamera* camera, const SolCameraUp
   // the proof, on the scene's stream (in front of the probe's render, as creation starts the host proof before its probe)
   const uint32_t nb = s->blocks_x * s->blocks_y;
   SolProofCamera pc;
-  const bool prove = !(u.flags & SOL_CAMERA_NO_BACKGROUND_PROOF) && s->background_proof && s->tree.n_wide > 0 &&
+  const bool prove = !(flags & SOL_CAMERA_NO_BACKGROUND_PROOF) && s->background_proof && s->tree.n_wide > 0 &&
                      sol_proof_camera(s->S.cam, s->S.width, s->S.height, 64.0 * (double)s->box_pad, pc);
   if (prove) {
     if (!s->proof_flags) HIP_TRY(hipMalloc((void**)&s->proof_flags, std::max<size_t>(nb, 64)));
@@ -77,14 +65,32 @@ int sol_scene_set_camera(SolScene* s, const SolCamera* camera, const SolCameraUp
     if ((rc = sol_cost_probe_adopt(s, probe, rc, s->verbose))) return rc;
   }
   if (prove) {
-    std::vector<uint8_t> flags(nb);
-    HIP_TRY(hipMemcpyAsync(flags.data(), s->proof_flags, nb, hipMemcpyDeviceToHost, s->stream));
+    std::vector<uint8_t> flags_host(nb);
+    HIP_TRY(hipMemcpyAsync(flags_host.data(), s->proof_flags, nb, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
-    if ((rc = adopt_flags(s, flags))) { drop_camera_tables(s); return rc; }
+    if ((rc = adopt_flags(s, flags_host, who))) { drop_camera_tables(s); return rc; }
   }
   if ((rc = sol_scene_to_device(s))) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   return SOL_OK;
+}
+
+extern "C" {
+
+int sol_scene_set_camera(SolScene* s, const SolCamera* camera, const SolCameraUpdate* update) {
+  if (!s || !camera) return sol_fail(SOL_EINVAL, "sol_scene_set_camera: null %s", !s ? "scene" : "camera");
+  SolCameraUpdate u{};
+  if (update) {
+    if (update->size < 8 || update->size > 4096) return sol_fail(SOL_EINVAL, "SolCameraUpdate.size %u", update->size);
+    std::memcpy(&u, update, std::min<size_t>(update->size, sizeof u));
+  }
+  if (u.flags & ~(SOL_CAMERA_NO_BACKGROUND_PROOF | SOL_CAMERA_REPROBE)) return sol_fail(SOL_EINVAL, "SolCameraUpdate.flags 0x%x: unknown bits", u.flags);
+  if (u.reserved[0] || u.reserved[1]) return sol_fail(SOL_EINVAL, "SolCameraUpdate.reserved must be 0");
+  if ((u.flags & SOL_CAMERA_REPROBE) && s->world > 1) return sol_fail(SOL_EINVAL, "SOL_CAMERA_REPROBE: the cost probe renders the whole frame on one rank (world is %d)", s->world);
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));  // a launch in flight reads the scene record and the work order
+  s->S.cam = cast_camera(*camera);
+  return sol_rederive_view_tables(s, u.flags, "set_camera");
 }
 
 int sol_scene_background_flags(const SolScene* s, uint8_t* flags, size_t n_flags, uint32_t* n_found) {

@@ -20,6 +20,7 @@
 #include "sol_camera.h"
 #include "sol_scene.h"
 #include "sol_tree.h"
+#include "sol_triangle.h"
 
 // The world tree built on the GPU (sol_build.hip): primitives of the reference-shaped tree under `root_ref` (each once - a
 // shared sub-tree is the same geometry twice, one copy finds the same hits), pre-split, clustered and collapsed on the current device.
@@ -130,17 +131,8 @@ static int device_world_tree_finish(DevicePrepared& pr, const uint32_t counts[3]
   return SOL_OK;
 }
 
-// A triangle's fp32 intersect record: starts at the vertex opposite the longest edge (fp32 arithmetic contract, solstrale_hip.h
-// sol_triangle_rotation; the oracle's float instantiation makes the same choice); `reference_order`: as the reference lists the vertices -
-// the frame a triangle LIGHT is sampled in (DevScene::light_tri). uv_of = which of {uv0, uv1, uv2} belongs to the record's three vertices.
-static void cast_triangle(const SolTriangle& t, bool reference_order, DTri& o, int uv_of[3]) {
-  double v0[3], e1[3], e2[3];
-  sol_triangle_rotated(&t, reference_order ? 0 : sol_triangle_rotation(&t), v0, e1, e2, uv_of);
-  o.v0x = (float)v0[0]; o.v0y = (float)v0[1]; o.v0z = (float)v0[2];
-  o.e1x = (float)e1[0]; o.e1y = (float)e1[1]; o.e1z = (float)e1[2];
-  o.e2x = (float)e2[0]; o.e2y = (float)e2[1]; o.e2z = (float)e2[2];
-  o.dfs = t.dfs_index; o.mat = t.material; o.area = (float)t.area;
-}
+// A triangle's fp32 intersect record (sol_triangle.h, shared with the records kernel of sol_scene_set_triangles): rotated, or `reference_order`.
+static void cast_triangle(const SolTriangle& t, bool reference_order, DTri& o, int uv_of[3]) { sol_tri_cast(&t, reference_order, &o, uv_of); }
 // the sampling frames of the triangle lights, by light index (entries of other lights stay zero)
 static std::vector<DTri> light_triangle_frames(const SolSceneDesc& d) {
   std::vector<DTri> frames(std::max<uint32_t>(1u, d.n_lights), DTri{});
@@ -600,6 +592,8 @@ static int check_options_and_header(CreateCtx& c, const SolCreateOptions* opt_in
   if (opt.world_tree < SOL_TREE_AUTO || opt.world_tree > SOL_TREE_HOST_PROBE) return sol_fail(SOL_EINVAL, "bad world_tree option %d", opt.world_tree);
   if (opt.split_percent > 1000 || opt.reinsertion_rounds > 1024)  // (a typo must not become a build of hours: ten times the references, a thousand rounds)
     return sol_fail(SOL_EINVAL, "SolCreateOptions: split_percent %d (at most 1000) / reinsertion_rounds %d (at most 1024)", opt.split_percent, opt.reinsertion_rounds);
+  if (opt.dynamic_triangles != 0 && opt.dynamic_triangles != 1) return sol_fail(SOL_EINVAL, "SolCreateOptions.dynamic_triangles %d (0 or 1)", opt.dynamic_triangles);
+  if (opt.reserved2 != 0) return sol_fail(SOL_EINVAL, "SolCreateOptions.reserved2 must be 0");
   if (d->abi_version != SOL_ABI_VERSION && d->abi_version != 1u) return sol_fail(SOL_EINVAL, "abi_version %u, expected %u (or 1)", d->abi_version, SOL_ABI_VERSION);
   c.has_env = has_environment(*d);
   if (c.has_env && ((uint64_t)d->env_width * d->env_height > (1ull << 28) || !std::isfinite(d->env_scale))) return sol_fail(SOL_EINVAL, "bad environment map");
@@ -689,12 +683,7 @@ static int cast_primitives(const SolSceneDesc* d, HostRecords& r) {
       if (!mat_ok(d, t.material)) { if (*bad < 0) *bad = i; continue; }
       int uo[3];
       cast_triangle(t, false, tris[i], uo);
-      const float* uvs[3] = {t.uv0, t.uv1, t.uv2};
-      DTriShade& s = tshade[i];
-      s.nx = (float)t.normal[0]; s.ny = (float)t.normal[1]; s.nz = (float)t.normal[2]; s.mat = t.material;
-      s.tx = (float)t.tangent[0]; s.ty = (float)t.tangent[1]; s.tz = (float)t.tangent[2];
-      s.bx = (float)t.bi_tangent[0]; s.by = (float)t.bi_tangent[1]; s.bz = (float)t.bi_tangent[2];
-      s.u0 = uvs[uo[0]][0]; s.v0 = uvs[uo[0]][1]; s.u1 = uvs[uo[1]][0]; s.v1 = uvs[uo[1]][1]; s.u2 = uvs[uo[2]][0]; s.v2 = uvs[uo[2]][1];
+      sol_tri_cast_shade(&t, uo, &tshade[i]);
     }
   };
   const uint32_t nt = d->n_triangles;
@@ -1082,6 +1071,85 @@ static int probe_candidates(const CreateCtx& c, const World& w, const HostRecord
   HIP_TRY(hipStreamSynchronize(s->stream));
   return SOL_OK;
 }
+// 10b. SolCreateOptions.dynamic_triangles: what sol_scene_set_triangles (sol_geometry.cpp) needs of this creation and cannot derive
+// later - the caller's per-triangle constants, the unpadded fp32 boxes of the primitives that do not move, the chosen layout's nodes level by
+// level (the layout is on the host here: no kernel), which records the world tree reaches (box_pad_for's S reads the ROOT's box, the union of
+// exactly those), the camera's share of S - and the staging copies both kernels write.
+template <typename T> static int dev_alloc(DevPtr<T>& p, size_t count) {
+  T* q = nullptr;
+  const size_t bytes = std::max<size_t>(count * sizeof(T), 64);
+  HIP_TRY(hipMalloc((void**)&q, bytes));
+  p.reset(q);
+  HIP_TRY(hipMemset(q, 0, bytes));
+  return SOL_OK;
+}
+static int keep_dynamic(const CreateCtx& c, const HostRecords& r, SolScene* s, const TreeCand& cand) {
+  const SolSceneDesc& d = c.d;
+  const WideLayout& L = cand.lay;
+  SolDynamic& y = s->dyn;
+  y.n_tris = d.n_triangles; y.n_recs = (uint32_t)L.old_of_new[0].size();
+  y.n_spheres = (uint32_t)r.spheres.size(); y.n_quads = (uint32_t)r.quads.size(); y.n_leaf_refs = (uint32_t)L.leaf_refs.size();
+  std::vector<SolTriStatic> st(d.n_triangles);
+  for (uint32_t i = 0; i < d.n_triangles; ++i) {
+    const SolTriangle& t = d.triangles[i];
+    st[i] = SolTriStatic{{t.uv0[0], t.uv0[1], t.uv1[0], t.uv1[1], t.uv2[0], t.uv2[1]}, t.material, t.dfs_index};
+  }
+  // the levels of the layout, and which device records it reaches
+  std::vector<uint8_t> reached[3];
+  for (int a = 0; a < 3; ++a) reached[a].assign(L.old_of_new[a].size(), 0);
+  std::vector<uint32_t> level_nodes, level{0u}, next;
+  y.level_off.assign(1, 0u);
+  const uint32_t ref_kind_of[4] = {SOL_REF_NONE, SOL_REF_TRIANGLE, SOL_REF_SPHERE, SOL_REF_QUAD};
+  while (!level.empty()) {
+    if (y.level_off.size() > 4096u || level_nodes.size() + level.size() > L.nodes.size()) return sol_fail(SOL_EDEVICE, "dynamic_triangles: the tree layout is not a tree");
+    next.clear();
+    for (uint32_t ni : level) {
+      if (ni >= L.nodes.size()) return sol_fail(SOL_EDEVICE, "dynamic_triangles: node index out of range");
+      level_nodes.push_back(ni);
+      const WideView v(L.nodes[ni], cand.emin);
+      for (int sl = 0; sl < SOL_WIDE_CHILDREN; ++sl) {
+        if (v.inner(sl)) { next.push_back(v.inner_index(sl)); continue; }
+        if (!v.leaf(sl)) continue;
+        const uint32_t idx = v.prim_index(sl);
+        uint32_t ref = SOL_MAKE_REF(ref_kind_of[v.kind], idx);
+        if (v.kind == SOL_LEAF_REFS) { if (idx >= L.leaf_refs.size()) return sol_fail(SOL_EDEVICE, "dynamic_triangles: listed reference out of range"); ref = L.leaf_refs[idx]; }
+        const int a = WideLayout::arr(SOL_REF_KIND(ref));
+        if (a < 0) continue;  // (a constant medium: sol_scene_set_triangles refuses such a scene)
+        if (SOL_REF_INDEX(ref) >= reached[a].size()) return sol_fail(SOL_EDEVICE, "dynamic_triangles: a leaf reference out of range");
+        reached[a][SOL_REF_INDEX(ref)] = 1;
+      }
+    }
+    y.level_off.push_back((uint32_t)level_nodes.size());
+    level.swap(next);
+  }
+  if (level_nodes.size() != L.nodes.size()) return sol_fail(SOL_EDEVICE, "dynamic_triangles: unreachable wide nodes");
+  std::vector<uint32_t> rec_tri(y.n_recs);
+  for (uint32_t i = 0; i < y.n_recs; ++i) rec_tri[i] = L.old_of_new[0][i] | (reached[0][i] ? 0u : SOL_DYN_OUTSIDE);
+  float S = 0.0f;
+  auto take = [&](double v) { const float a = std::fabs((float)v); if (std::isfinite(a) && a > S) S = a; };  // (box_pad_for's)
+  std::vector<float> sbox(r.spheres.size() * 6), qbox(r.quads.size() * 6);
+  for (size_t i = 0; i < r.spheres.size(); ++i)
+    for (int j = 0; j < 6; ++j) { const double v = d.spheres[L.old_of_new[1][i]].bbox.v[j]; sbox[i * 6 + j] = (float)v; if (reached[1][i]) take(v); }
+  for (size_t i = 0; i < r.quads.size(); ++i)
+    for (int j = 0; j < 6; ++j) { const double v = d.quads[L.old_of_new[2][i]].bbox.v[j]; qbox[i * 6 + j] = (float)v; if (reached[2][i]) take(v); }
+  y.static_S = S;
+  S = 0.0f;
+  for (int j = 0; j < 3; ++j) take(d.camera.origin[j]);
+  y.cam_S = S;
+  y.light_src_host.assign(d.n_lights, 0xFFFFFFFFu);
+  for (uint32_t i = 0; i < d.n_lights; ++i)
+    if (SOL_REF_KIND(d.lights[i]) == SOL_REF_TRIANGLE) y.light_src_host[i] = SOL_REF_INDEX(d.lights[i]);
+  y.light_lum = sol_light_luminances_of(&d);
+  int rc;
+  if ((rc = sol_upload(st, y.tri_static)) || (rc = sol_upload(rec_tri, y.rec_tri)) || (rc = sol_upload(sbox, y.sphere_box)) || (rc = sol_upload(qbox, y.quad_box)) ||
+      (rc = sol_upload(level_nodes, y.level_nodes)) || (rc = sol_upload(y.light_src_host, y.light_src)) || (rc = sol_upload(light_triangle_frames(d), &y.light_tri2)) ||
+      (rc = dev_alloc(y.tri_box, (size_t)y.n_recs * 8)) || (rc = dev_alloc(y.node_box, L.nodes.size() * 6)) || (rc = dev_alloc(y.wides2, L.nodes.size())) ||
+      (rc = dev_alloc(y.tris2, y.n_recs)) || (rc = dev_alloc(y.shade2, y.n_recs)) || (rc = dev_alloc(y.verts, (size_t)y.n_tris * 9)) ||
+      (rc = dev_alloc(y.out, 4 + 2 * (size_t)d.n_lights)))
+    return rc;
+  y.on = true;
+  return SOL_OK;
+}
 // 11. Background blocks: constant background only (an environment map is looked up per ray). The proof is host work (0.06 s for C5 at 1080p): it
 // runs on a thread of its own beside the cost probe's render and is adopted after it (the probe traces every block either way).
 struct BackgroundProof {
@@ -1218,6 +1286,7 @@ int sol_scene_create_ex(const SolSceneDesc* d, int device, const SolCreateOption
   if ((rc = set_scene_constants(c, world, s, cands[0]))) return rc;
   size_t chosen = 0;
   if (cands.size() > 1 && (rc = probe_candidates(c, world, rec, s, cands, chosen))) return rc;
+  if (c.opt.dynamic_triangles && (rc = keep_dynamic(c, rec, s, cands[chosen]))) return rc;
   BackgroundProof proof;  // (after `cands`: it reads the chosen candidate's layout until it is joined)
   // (what a later sol_scene_set_camera must know of this creation: sol_camera.cpp)
   s->box_pad = world.box_pad;

@@ -1,0 +1,253 @@
+// sol_geometry.hip -- the kernels of sol_scene_set_triangles (host side: sol_geometry.cpp).
+//
+// Records. One thread per device triangle record (a pre-split triangle has several, all copies of one): the caller's 72 bytes of vertices and
+// the 32-byte row of what does not move (texture coordinates, material, dfs_index) go through sol_triangle_new (sol_triangle.h: the f64 code the
+// CPU entry point sol_triangle_from_vertices runs) and the casts creation uses, and come out as the 48-byte intersect record in the rotated
+// frame, the 64-byte shading record and the unpadded fp32 cast box (32 bytes), all stored as dwordx4. Three scene-wide facts are reduced by
+// wave, then with one atomic per wave on words whose values order like unsigned integers: a vertex that is not finite, a needle triangle, and
+// the largest |fp32 coordinate| over the boxes of the records the world tree reaches - which is the largest |coordinate| of their union, the
+// root's box that creation's box_pad_for reads (bvh.rs:95,105: a node's box is the union of its children's): per axis the union is [min of the
+// mins, max of the maxs]; a min that is not the least has its own max at or above it, and that max is at most the greatest, so no coordinate
+// of any box exceeds max(|least min|, |greatest max|) in magnitude, and both of those are coordinates of some box.
+// A second, small launch runs over the lights: a triangle light's sampling frame in the reference's vertex order and its f64 area.
+//
+// Refit. One launch per level of the tree, deepest first, over that level's nodes. A child's box is the record's unpadded box plus the scene's
+// pad (a leaf, found as the render kernel finds it: base_prim or leaf_refs) or what the level below left in node_box (an inner node); from there
+// it is the emission's arithmetic (sol_build.hip k_emit, sol_tree.h WideBuilder::build): the node's grid origin two more pads out, the three
+// frexpf exponents clamped to [emin, emin + 31] (a larger one raises SOL_REFIT_RANGE), floor / ceil quantisation with the fix-ups under the
+// device's own decode - the functions of sol_quant.h, which k_emit calls too. Masks, leaf kind, exponent origin and the slot-7 base bytes
+// are copied: the topology does not change. Eight lanes per node: lane s loads and quantises child s, the union goes through three
+// __shfl_xor steps, the plane bytes are packed across the lanes and four lanes store the node as dwordx4. (One thread per node was built
+// and measured 2.4-3.1x slower over the refit launches, profiles/set_triangles_ab.txt; it is in the history, not in the library.)
+// Both kernels write staging buffers only.
+#include <hip/hip_runtime.h>
+
+#include "sol_geometry.h"
+#include "sol_quant.h"
+#include "sol_triangle.h"
+
+namespace {
+
+__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, m));
+  return v;
+}
+
+__device__ __forceinline__ void load_triangle(const double* __restrict__ verts, const SolTriStatic* __restrict__ st, uint32_t t, SolTriangle& T, bool& finite) {
+  double v[9];
+  const double* p = verts + (size_t)t * 9;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) v[k] = p[k];
+  const float4* q = reinterpret_cast<const float4*>(st + t);
+  const float4 a = q[0], b = q[1];
+  const float uv[6] = {a.x, a.y, a.z, a.w, b.x, b.y};
+  T.material = __float_as_int(b.z);
+  T.dfs_index = __float_as_uint(b.w);
+  finite = true;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) finite = finite && (fabs(v[k]) < __builtin_huge_val());  // (false for a NaN too)
+  sol_triangle_new(v, uv, &T);
+}
+
+__global__ void __launch_bounds__(256) sol_triangle_records_kernel(const double* __restrict__ verts, const SolTriStatic* __restrict__ st, const uint32_t* __restrict__ rec_tri,
+                                                                   uint32_t n_recs, uint32_t n_tris, DTri* __restrict__ tris, DTriShade* __restrict__ shade,
+                                                                   float* __restrict__ tri_box, uint32_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool bad = false, needle = false;
+  uint32_t s_bits = 0u;
+  const uint32_t rt = i < n_recs ? rec_tri[i] : 0xFFFFFFFFu;
+  const uint32_t t = rt & ~SOL_DYN_OUTSIDE;
+  if (i < n_recs && t < n_tris) {
+    SolTriangle T;
+    bool finite;
+    load_triangle(verts, st, t, T, finite);
+    bad = !finite;
+    needle = sol_triangle_is_needle(&T);
+    union { DTri r; float4 q[3]; } ri;
+    union { DTriShade r; float4 q[4]; } rs;
+    int uo[3];
+    sol_tri_cast(&T, false, &ri.r, uo);
+    sol_tri_cast_shade(&T, uo, &rs.r);
+    float bx[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) bx[k] = (float)T.bbox.v[k];
+    if (!(rt & SOL_DYN_OUTSIDE)) {
+#pragma unroll
+      for (int k = 0; k < 6; ++k) s_bits = max(s_bits, __float_as_uint(fabsf(bx[k])));  // (a NaN's bits are the largest: refused as not finite anyway)
+    }
+    float4* td = reinterpret_cast<float4*>(tris + i);
+    td[0] = ri.q[0]; td[1] = ri.q[1]; td[2] = ri.q[2];
+    float4* sd = reinterpret_cast<float4*>(shade + i);
+    sd[0] = rs.q[0]; sd[1] = rs.q[1]; sd[2] = rs.q[2]; sd[3] = rs.q[3];
+    float4* bd = reinterpret_cast<float4*>(tri_box + (size_t)i * 8);
+    bd[0] = make_float4(bx[0], bx[1], bx[2], bx[3]);
+    bd[1] = make_float4(bx[4], bx[5], 0.f, 0.f);
+  }
+  // by wave first, then one atomic per wave and fact (every value is a non-negative float's bits or a flag: unsigned order)
+  const bool any_bad = __ballot(bad) != 0ull, any_needle = __ballot(needle) != 0ull;
+  s_bits = wave_max_u32(s_bits);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (any_bad) atomicOr(&out[0], 1u);
+    if (any_needle) atomicOr(&out[1], 1u);
+    if (s_bits) atomicMax(&out[2], s_bits);
+  }
+}
+
+__global__ void __launch_bounds__(64) sol_triangle_lights_kernel(const double* __restrict__ verts, const SolTriStatic* __restrict__ st, const uint32_t* __restrict__ light_src,
+                                                                 uint32_t n_lights, uint32_t n_tris, DTri* __restrict__ light_tri, double* __restrict__ area) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n_lights) return;
+  const uint32_t t = light_src[i];
+  if (t >= n_tris) { area[i] = 0.0; return; }
+  SolTriangle T;
+  bool finite;
+  load_triangle(verts, st, t, T, finite);
+  union { DTri r; float4 q[3]; } ri;
+  int uo[3];
+  sol_tri_cast(&T, true, &ri.r, uo);
+  float4* td = reinterpret_cast<float4*>(light_tri + i);
+  td[0] = ri.q[0]; td[1] = ri.q[1]; td[2] = ri.q[2];
+  area[i] = T.area;
+}
+
+// ---- refit ----
+struct Box6 { float lo[3], hi[3]; };
+
+__device__ __forceinline__ Box6 empty_box6() {
+  const float inf = __builtin_huge_valf();
+  return Box6{{inf, inf, inf}, {-inf, -inf, -inf}};
+}
+// The padded fp32 box of the child in slot s of a node with `meta` and the two base indices; an empty box for an empty slot.
+__device__ __forceinline__ Box6 child_box(const SolRefitParams& P, uint32_t meta, uint32_t base_inner, uint32_t base_prim, int s, uint32_t& flags) {
+  const uint32_t imask = (meta >> 15) & 0x7Fu, lmask = (meta >> 22) & 0x7Fu, kind = (meta >> 29) & 3u;
+  const uint32_t below = (1u << s) - 1u;
+  Box6 b = empty_box6();
+  if ((imask >> s) & 1u) {
+    const uint32_t ni = base_inner + __popc(imask & below);
+    if (ni >= P.n_wide) { flags |= SOL_REFIT_CORRUPT; return b; }
+    const float* p = P.node_box + (size_t)ni * 6;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { b.lo[a] = p[2 * a]; b.hi[a] = p[2 * a + 1]; }
+    return b;
+  }
+  if (!((lmask >> s) & 1u)) return b;
+  uint32_t idx = base_prim + __popc(lmask & below), k = kind;
+  if (kind == SOL_LEAF_REFS) {
+    if (idx >= P.n_leaf_refs) { flags |= SOL_REFIT_CORRUPT; return b; }
+    const uint32_t ref = P.leaf_refs[idx];
+    const uint32_t rk = SOL_REF_KIND(ref);
+    k = rk == SOL_REF_TRIANGLE ? SOL_LEAF_TRIANGLES : rk == SOL_REF_SPHERE ? SOL_LEAF_SPHERES : rk == SOL_REF_QUAD ? SOL_LEAF_QUADS : 0u;
+    idx = SOL_REF_INDEX(ref);
+  }
+  const float* p = nullptr;
+  if (k == SOL_LEAF_TRIANGLES && idx < P.n_recs) p = P.tri_box + (size_t)idx * 8;
+  else if (k == SOL_LEAF_SPHERES && idx < P.n_spheres) p = P.sphere_box + (size_t)idx * 6;
+  else if (k == SOL_LEAF_QUADS && idx < P.n_quads) p = P.quad_box + (size_t)idx * 6;
+  if (!p) { flags |= SOL_REFIT_CORRUPT; return b; }
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { b.lo[a] = p[2 * a] - P.pad; b.hi[a] = p[2 * a + 1] + P.pad; }  // cast_box (sol_tree.h)
+  return b;
+}
+// The node's grid from the union of its children's boxes: origin two pads out, exponent and scale per axis (sol_quant.h, k_emit's own).
+__device__ __forceinline__ void node_grid(const Box6& u, float pad, uint32_t emin, float lo[3], float hi[3], uint32_t eb[3], float scale[3], uint32_t& flags) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = u.lo[a] - 2.0f * pad; hi[a] = u.hi[a] + 2.0f * pad;
+    bool over;
+    eb[a] = sol_wide_axis_grid(lo[a], hi[a], emin, scale[a], over);
+    if (over) flags |= SOL_REFIT_RANGE;
+  }
+}
+// One axis of one child: the plane bytes that contain [bl - 2 pad, bh + 2 pad]; a bound that is not finite (a primitive whose fp32 box
+// overflows: the host's WideBuilder::build makes the same substitution) takes the node's.
+__device__ __forceinline__ void quantise_axis(float bl, float bh, float pad, float lo, float hi, float scale, uint32_t& ql, uint32_t& qh, uint32_t& flags) {
+  float cl = bl - 2.0f * pad, chh = bh + 2.0f * pad;  // two more pads: the device evaluates the planes in t-space (sol_tree.h)
+  if (!(fabsf(cl) < __builtin_huge_valf())) cl = lo;
+  if (!(fabsf(chh) < __builtin_huge_valf())) chh = hi;
+  if (!sol_wide_axis_quantise(cl, chh, lo, scale, ql, qh)) flags |= SOL_REFIT_OPENED;
+}
+
+// Eight lanes per node: lane s of the group is slot s (lane 7, the slot that does not exist, carries the base bytes)
+__global__ void __launch_bounds__(64) sol_refit_level8_kernel(SolRefitParams P, uint32_t first, uint32_t count) {
+  const uint32_t gi = blockIdx.x * 8u + (threadIdx.x >> 3);
+  const int s = (int)(threadIdx.x & 7u);
+  const bool live = gi < count;  // (whole groups: every shuffle below stays inside a group of eight)
+  uint32_t ni = live ? P.level_nodes[first + gi] : 0u;
+  uint32_t flags = 0u;
+  if (live && ni >= P.n_wide) { flags |= SOL_REFIT_CORRUPT; ni = 0u; }
+  const DWide* wp = P.cur + ni;
+  const uint32_t meta = wp->meta;
+  const uint32_t t1 = wp->q[1] >> 24, t3 = wp->q[3] >> 24, t5 = wp->q[5] >> 24, t7 = wp->q[7] >> 24, t9 = wp->q[9] >> 24, t11 = wp->q[11] >> 24;
+  const uint32_t base_inner = t1 | (t3 << 8) | (t5 << 16), base_prim = t7 | (t9 << 8) | (t11 << 16);
+  const uint32_t occupied = ((meta >> 15) | (meta >> 22)) & 0x7Fu;
+  Box6 c = empty_box6();
+  if (live && s < SOL_WIDE_CHILDREN) c = child_box(P, meta, base_inner, base_prim, s, flags);
+  Box6 u;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    u.lo[a] = fabsf(c.lo[a]) < __builtin_huge_valf() ? c.lo[a] : __builtin_huge_valf();
+    u.hi[a] = fabsf(c.hi[a]) < __builtin_huge_valf() ? c.hi[a] : -__builtin_huge_valf();
+#pragma unroll
+    for (int m = 1; m <= 4; m <<= 1) {
+      u.lo[a] = fminf(u.lo[a], __shfl_xor(u.lo[a], m));
+      u.hi[a] = fmaxf(u.hi[a], __shfl_xor(u.hi[a], m));
+    }
+  }
+  float lo[3], hi[3], scale[3];
+  uint32_t eb[3];
+  node_grid(u, P.pad, P.emin, lo, hi, eb, scale, flags);
+  // this lane's six plane bytes, in place in the word of its half of the slots
+  uint32_t wl[3], wh[3];
+  const int shift = 8 * (s & 3);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    uint32_t ql = 255u, qh = 0u;
+    if (s < SOL_WIDE_CHILDREN && ((occupied >> s) & 1u)) quantise_axis(c.lo[a], c.hi[a], P.pad, lo[a], hi[a], scale[a], ql, qh, flags);
+    wl[a] = ql << shift; wh[a] = qh << shift;
+  }
+  if (s == 7) { wl[0] = t1 << 24; wl[1] = t3 << 24; wl[2] = t5 << 24; wh[0] = t7 << 24; wh[1] = t9 << 24; wh[2] = t11 << 24; }
+  // packed across the four lanes of a half, then exchanged between the halves
+  uint32_t ol[3], oh[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    wl[a] |= (uint32_t)__shfl_xor((int)wl[a], 1); wl[a] |= (uint32_t)__shfl_xor((int)wl[a], 2);
+    wh[a] |= (uint32_t)__shfl_xor((int)wh[a], 1); wh[a] |= (uint32_t)__shfl_xor((int)wh[a], 2);
+    ol[a] = (uint32_t)__shfl_xor((int)wl[a], 4); oh[a] = (uint32_t)__shfl_xor((int)wh[a], 4);
+  }
+  if (live && !(flags & SOL_REFIT_CORRUPT) && s < 4) {
+    // (lanes 0 .. 3 hold the words of slots 0 .. 3 in w*, of slots 4 .. 7 in o*): q[2a] = wl[a], q[2a + 1] = ol[a], q[6 + 2a] = wh[a], q[7 + 2a] = oh[a]
+    uint4 v;
+    if (s == 0) v = make_uint4(__float_as_uint(lo[0]), __float_as_uint(lo[1]), __float_as_uint(lo[2]),
+                               (meta & 0xFFFF8000u) | (eb[0] - P.emin) | ((eb[1] - P.emin) << 5) | ((eb[2] - P.emin) << 10));
+    else if (s == 1) v = make_uint4(wl[0], ol[0], wl[1], ol[1]);
+    else if (s == 2) v = make_uint4(wl[2], ol[2], wh[0], oh[0]);
+    else v = make_uint4(wh[1], oh[1], wh[2], oh[2]);
+    reinterpret_cast<uint4*>(P.out + ni)[s] = v;
+    if (s < 3) {  // the union, for the level above
+      float2* nb = reinterpret_cast<float2*>(P.node_box + (size_t)ni * 6);
+      nb[s] = s == 0 ? make_float2(u.lo[0], u.hi[0]) : s == 1 ? make_float2(u.lo[1], u.hi[1]) : make_float2(u.lo[2], u.hi[2]);
+    }
+  }
+  if (flags) atomicOr(P.flags, flags);
+}
+
+}  // namespace
+
+hipError_t sol_launch_triangle_records(const double* verts, const SolTriStatic* st, const uint32_t* rec_tri, uint32_t n_recs, uint32_t n_tris, DTri* tris,
+                                       DTriShade* shade, float* tri_box, uint32_t* out, hipStream_t stream) {
+  if (n_recs == 0) return hipSuccess;
+  hipLaunchKernelGGL(sol_triangle_records_kernel, dim3((n_recs + 255u) / 256u), dim3(256), 0, stream, verts, st, rec_tri, n_recs, n_tris, tris, shade, tri_box, out);
+  return hipGetLastError();
+}
+hipError_t sol_launch_triangle_lights(const double* verts, const SolTriStatic* st, const uint32_t* light_src, uint32_t n_lights, uint32_t n_tris, DTri* light_tri,
+                                      double* area, hipStream_t stream) {
+  if (n_lights == 0) return hipSuccess;
+  hipLaunchKernelGGL(sol_triangle_lights_kernel, dim3((n_lights + 63u) / 64u), dim3(64), 0, stream, verts, st, light_src, n_lights, n_tris, light_tri, area);
+  return hipGetLastError();
+}
+hipError_t sol_launch_refit_level(const SolRefitParams& P, uint32_t first, uint32_t count, hipStream_t stream) {
+  if (count == 0) return hipSuccess;
+  hipLaunchKernelGGL(sol_refit_level8_kernel, dim3((count + 7u) / 8u), dim3(64), 0, stream, P, first, count);
+  return hipGetLastError();
+}

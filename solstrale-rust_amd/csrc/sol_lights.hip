@@ -151,6 +151,22 @@ std::vector<double> sol_light_weights_of(const SolSceneDesc* d) {
   return w;
 }
 
+// The luminance factor alone, per light: what a geometry move (sol_geometry.cpp) multiplies the new areas of the triangle lights with.
+std::vector<double> sol_light_luminances_of(const SolSceneDesc* d) {
+  std::vector<double> y;
+  if (!d || !d->lights) return y;
+  y.assign(d->n_lights, 0.0);
+  for (uint32_t i = 0; i < d->n_lights; ++i) {
+    const uint32_t kind = SOL_REF_KIND(d->lights[i]), idx = SOL_REF_INDEX(d->lights[i]);
+    int32_t mat = -1;
+    if (kind == SOL_REF_QUAD && idx < d->n_quads && d->quads) mat = d->quads[idx].material;
+    else if (kind == SOL_REF_TRIANGLE && idx < d->n_triangles && d->triangles) mat = d->triangles[idx].material;
+    else if (kind == SOL_REF_SPHERE && idx < d->n_spheres && d->spheres) mat = d->spheres[idx].material;
+    y[i] = light_luminance(d, mat);
+  }
+  return y;
+}
+
 // q_i and C_i (above) from the weights; W = 0: nothing can be drawn.
 static double light_tables_of(const std::vector<double>& w, std::vector<float>& q, std::vector<float>& cdf) {
   const size_t L = w.size();
@@ -227,6 +243,23 @@ static int light_tables_build(SolScene* s) {
   s->light_tables = t;
   s->S.light_q = t;
   s->S.light_cdf = t + L;
+  return SOL_OK;
+}
+
+// After a geometry move: the light records, the box pad and s->light_w have changed - what was built from them is built again.
+int sol_light_rebuild(SolScene* s) {
+  int rc;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (s->light_tree) {
+    hipFree(s->light_tree);
+    s->light_tree = nullptr; s->light_tree_bytes = 0; s->S.light_nodes = nullptr;
+    if ((rc = light_tree_build(s))) return rc;
+  }
+  if (s->light_tables) {
+    hipFree(s->light_tables);
+    s->light_tables = nullptr; s->S.light_q = nullptr; s->S.light_cdf = nullptr;
+    if ((rc = light_tables_build(s))) return rc;
+  }
   return SOL_OK;
 }
 

@@ -4,6 +4,7 @@
 //   sol_create.cpp  sol_scene_create in stages: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h), world-tree candidates, upload, probes; the tree diagnostics
 //   sol_launch.cpp  sol_render* / auxiliary planes / debug hooks: launches of the kernels in sol_render.hip
 //   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
+//   sol_geometry.cpp sol_scene_set_triangles: new vertices for the triangles of a live scene, records and tree boxes recomputed on the device (sol_geometry.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
 // There is NO CPU fallback: without a HIP device every compute entry point fails with SOL_EDEVICE.
@@ -81,6 +82,33 @@ struct DevTree {
   uint32_t n_wide = 0, packed_depth = 0;  // wide nodes; stack bound with one-dword node groups (the pool kernel, sol_pool.hip)
   std::vector<uint32_t> old_index[3];  // triangles / spheres / quads: device index -> index in the caller's SolSceneDesc arrays
   void release() { *this = DevTree{}; }
+};
+
+// What a handle created with SolCreateOptions.dynamic_triangles keeps for sol_scene_set_triangles (sol_geometry.cpp); empty otherwise.
+struct SolTriStatic { float uv[6]; int32_t material; uint32_t dfs_index; };  // per caller triangle: what a move does not change (uv0, uv1, uv2 in the reference's order)
+static_assert(sizeof(SolTriStatic) == 32, "SolTriStatic");
+#define SOL_DYN_OUTSIDE 0x80000000u  // rec_tri: the record's triangle is not reached by the world tree (its box is no part of the root's)
+struct SolDynamic {
+  bool on = false;
+  uint32_t n_tris = 0, n_recs = 0;       // caller triangles; device triangle records (more where pre-splitting made copies)
+  uint32_t n_spheres = 0, n_quads = 0, n_leaf_refs = 0;  // lengths of the arrays the refit indexes
+  float cam_S = 0.f, static_S = 0.f;     // box_pad_for's S: the creation camera's share, the spheres' and quads' share (largest |fp32 coordinate|)
+  DevPtr<SolTriStatic> tri_static;       // [n_tris]
+  DevPtr<uint32_t> rec_tri;              // [n_recs] DevTree::old_index[0], SOL_DYN_OUTSIDE or-ed in
+  DevPtr<float> tri_box;                 // [n_recs][8] the unpadded fp32 cast box of the record's triangle (xmin xmax ymin ymax zmin zmax 0 0): the records kernel writes it
+  DevPtr<float> sphere_box, quad_box;    // [n][6] the same of the spheres / quads, in device order (they do not move)
+  DevPtr<uint32_t> level_nodes;          // wide node indices, level by level (the root first)
+  std::vector<uint32_t> level_off;       // level l = level_nodes[level_off[l] .. level_off[l + 1])
+  DevPtr<float> node_box;                // [n_wide][6] scratch of the refit: the union of a node's padded child boxes
+  DevPtr<DWide> wides2; DevPtr<DTri> tris2; DevPtr<DTriShade> shade2;  // staging: both kernels write here, the commit swaps them with the tree's
+  DTri* light_tri2 = nullptr;            // staging of SolScene::light_tri
+  DevPtr<uint32_t> light_src;            // [n_lights] caller triangle of light i, 0xFFFFFFFF: not a triangle
+  std::vector<uint32_t> light_src_host;
+  std::vector<double> light_lum;         // [n_lights] luminance of the light's emission (sol_light_weights_of's factor)
+  DevPtr<double> verts;                  // [n_tris][9] where the host route uploads the caller's vertices
+  DevPtr<uint32_t> out;                  // device: 4 flag words (non-finite, needle, S bits, refit flags), then n_lights f64 areas
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // with sol_kernel_timing: call start, vertices uploaded, records written, tree refitted, call end
+  float last_ms[4] = {0.f, 0.f, 0.f, 0.f};
 };
 
 // Adaptive sampling (sol_adaptive.hip): the session opened by sol_adaptive_begin and ended by sol_clear, sol_render and
@@ -205,12 +233,20 @@ struct SolScene {
   // the spill area of the query kernel's own grid. None of them is the render launch's.
   void* query_in = nullptr; void* query_out = nullptr; size_t query_cap = 0;
   uint32_t* query_spill = nullptr; size_t query_spill_words = 0;
+  SolDynamic dyn;  // sol_scene_set_triangles (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
 std::vector<double> sol_light_weights_of(const SolSceneDesc* d);
 // Why environment importance sampling cannot run on the scene `d` describes, or "" (sol_envmap.hip; host only).
 std::string sol_env_refusal(const SolSceneDesc* d);
 
+// The luminance factor of sol_light_weights_of per light (w_i = area_i x luminance_i), and, after a geometry move changed s->light_w and the
+// light records: the light tree and the power tables that exist are freed and built again (sol_lights.hip).
+std::vector<double> sol_light_luminances_of(const SolSceneDesc* d);
+int sol_light_rebuild(SolScene* s);
+// What sol_scene_set_camera and sol_scene_set_triangles end with (sol_camera.cpp): the sums and the auxiliary planes cleared, an adaptive session
+// ended, the background blocks proved again on the device (unless flags & 1), the cost probe (flags & 2), the work order, the scene record uploaded.
+int sol_rederive_view_tables(SolScene* s, uint32_t flags, const char* who);
 int sol_rebuild_order(SolScene* s);
 // The 4-spp cost probe of the whole frame (sol_create.cpp): the counted render, then its adoption (`rc`: the render's status; frees the tables).
 struct SolCostProbe { uint32_t* cost_dev = nullptr; uint32_t* work_dev = nullptr; };

@@ -14,7 +14,7 @@ HIP_LIB = os.path.join(BUILD_DIR, "libsolstrale_hip.so")
 HOST_LIB = os.path.join(BUILD_DIR, "libsolstrale_host.so")
 
 SOL_ABI_VERSION = 2
-SOL_OK, SOL_EINVAL, SOL_ENOLIGHT, SOL_EDEVICE, SOL_EDEPTH, SOL_ENOMEM = 0, -1, -2, -3, -4, -5
+SOL_OK, SOL_EINVAL, SOL_ENOLIGHT, SOL_EDEVICE, SOL_EDEPTH, SOL_ENOMEM, SOL_ERANGE = 0, -1, -2, -3, -4, -5, -6
 REF_NONE, REF_NODE, REF_SPHERE, REF_QUAD, REF_TRIANGLE, REF_MEDIUM = range(6)
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC, MAT_BLEND = range(6)
 TEX_SOLID, TEX_IMAGE = 0, 1
@@ -133,7 +133,8 @@ UNIQUE_ID_BYTES = 128
 
 class SolCreateOptions(C.Structure):
     _fields_ = [("size", C.c_uint32), ("world_tree", C.c_int32), ("no_work_order_probe", C.c_int32), ("split_percent", C.c_int32),
-                ("reinsertion_rounds", C.c_int32), ("no_background_blocks", C.c_int32), ("reserved", C.c_int32 * 2)]
+                ("reinsertion_rounds", C.c_int32), ("no_background_blocks", C.c_int32), ("reserved", C.c_int32 * 2),
+                ("dynamic_triangles", C.c_int32), ("reserved2", C.c_int32)]
 
 
 class SolSceneInfo(C.Structure):
@@ -208,6 +209,14 @@ SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
 
 class SolCameraUpdate(C.Structure):
     """EXTENSION: how sol_scene_set_camera moves the camera of a live scene. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+SOL_GEOM_NO_BACKGROUND_PROOF, SOL_GEOM_REPROBE = 1, 2
+
+
+class SolGeometryUpdate(C.Structure):
+    """EXTENSION: how sol_scene_set_triangles moves the triangles of a live scene. Not in ABI_STRUCTS."""
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
@@ -299,6 +308,11 @@ def load_hip():
     _sig(lib, "sol_camera_rays", C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p])
     _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
     _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
+    _sig(lib, "sol_triangle_from_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolTriangle)])
+    _sig(lib, "sol_scene_set_triangles", C.c_int, [P, C.c_void_p, C.c_uint32, C.POINTER(SolGeometryUpdate)])
+    _sig(lib, "sol_scene_set_triangles_dev", C.c_int, [P, C.c_void_p, C.c_uint32, C.POINTER(SolGeometryUpdate)])
+    _sig(lib, "sol_scene_set_triangles_ms", C.c_int, [P, C.POINTER(C.c_float)])
+    _sig(lib, "sol_scene_triangle_records", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _libs["hip"] = lib
     return lib
 
@@ -314,7 +328,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_env_sampling", "sol_env_sampling_check", "sol_env_tables", "sol_env_eval",
                "sol_light_sampling", "sol_light_sampling_check", "sol_light_weights", "sol_light_tables", "sol_light_tree", "sol_light_eval",
                "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8",
-               "sol_query_dev", "sol_query", "sol_camera_rays", "sol_scene_set_camera", "sol_scene_background_flags"]
+               "sol_query_dev", "sol_query", "sol_camera_rays", "sol_scene_set_camera", "sol_scene_background_flags",
+               "sol_triangle_from_vertices", "sol_scene_set_triangles", "sol_scene_set_triangles_dev", "sol_scene_set_triangles_ms", "sol_scene_triangle_records"]
 
 
 def load_host():

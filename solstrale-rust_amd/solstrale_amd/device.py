@@ -71,21 +71,35 @@ def background_blocks(scene, use_sah=0):
     return out
 
 
+def triangle_from_vertices(v, uv=None, out=None):
+    """sol_triangle_from_vertices (CPU, no device): the SolTriangle of the vertices v (3 x 3 float64: v0, v1, v2) and the texture coordinates uv
+    (3 x 2 float32, default zeros) - geometry, uvs and bbox; `out`: a SolTriangle to fill instead of a new one (its material and dfs_index stay)."""
+    lib = _abi.load_hip()
+    a = np.ascontiguousarray(v, dtype=np.float64).reshape(9)
+    t = np.zeros(6, dtype=np.float32) if uv is None else np.ascontiguousarray(uv, dtype=np.float32).reshape(6)
+    out = _abi.SolTriangle() if out is None else out
+    rc = lib.sol_triangle_from_vertices(a.ctypes.data, t.ctypes.data, C.byref(out))
+    if rc != 0:
+        raise DeviceError(rc, lib.sol_last_error().decode(errors="replace"))
+    return out
+
+
 class DeviceScene:
     """sol_scene_create .. sol_scene_destroy"""
 
-    def __init__(self, scene, device=0, world_tree=None, no_work_order_probe=False, split_percent=0, no_background_blocks=False):
+    def __init__(self, scene, device=0, world_tree=None, no_work_order_probe=False, split_percent=0, no_background_blocks=False, dynamic_triangles=False):
         """split_percent: SolCreateOptions.split_percent (0: the default budget of the device build's triangle pre-splitting, < 0: none);
-        no_background_blocks: SolCreateOptions.no_background_blocks (do not look for blocks that provably see only the background)."""
+        no_background_blocks: SolCreateOptions.no_background_blocks (do not look for blocks that provably see only the background);
+        dynamic_triangles: SolCreateOptions.dynamic_triangles (keep what set_triangles needs)."""
         self.lib = _abi.load_hip()
         self.scene = scene
         self.h = C.c_void_p()
-        if world_tree is None and not no_work_order_probe and not split_percent and not no_background_blocks:
+        if world_tree is None and not no_work_order_probe and not split_percent and not no_background_blocks and not dynamic_triangles:
             rc = self.lib.sol_scene_create(scene.desc_ptr, device, C.byref(self.h))
         else:
             opt = _abi.SolCreateOptions(size=C.sizeof(_abi.SolCreateOptions), world_tree=int(world_tree or 0),
                                         no_work_order_probe=1 if no_work_order_probe else 0, split_percent=int(split_percent),
-                                        no_background_blocks=1 if no_background_blocks else 0)
+                                        no_background_blocks=1 if no_background_blocks else 0, dynamic_triangles=1 if dynamic_triangles else 0)
             rc = self.lib.sol_scene_create_ex(scene.desc_ptr, device, C.byref(opt), C.byref(self.h))
         if rc != 0:
             self.h = None
@@ -425,6 +439,47 @@ class DeviceScene:
         self._chk(self.lib.sol_scene_background_flags(self.h, flags.ctypes.data, flags.size, C.byref(n)))
         assert int(flags.sum()) == n.value
         return flags.astype(bool)
+
+    # ---- new vertices for the triangles of a live scene (EXTENSION) ----
+    def set_triangles(self, vertices, background_proof=True, reprobe=False):
+        """sol_scene_set_triangles: row i of `vertices` (float64 [n, 3, 3]: v0, v1, v2) moves triangle i of the creation description; the scene
+        must have been created with dynamic_triangles=True. A numpy array goes the host route; a contiguous float64 torch tensor on the scene's
+        device goes through sol_scene_set_triangles_dev without a copy. Clears the sums and the auxiliary planes, ends an adaptive session; blocks."""
+        upd = _abi.SolGeometryUpdate(size=C.sizeof(_abi.SolGeometryUpdate),
+                                     flags=(0 if background_proof else _abi.SOL_GEOM_NO_BACKGROUND_PROOF) | (_abi.SOL_GEOM_REPROBE if reprobe else 0))
+        if isinstance(vertices, np.ndarray) or not hasattr(vertices, "data_ptr"):
+            a = np.ascontiguousarray(vertices, dtype=np.float64)
+            if a.ndim != 3 or a.shape[1:] != (3, 3):
+                raise ValueError("vertices: a float64 [n, 3, 3] array of (v0, v1, v2)")
+            self._chk(self.lib.sol_scene_set_triangles(self.h, a.ctypes.data, a.shape[0], C.byref(upd)))
+            return
+        import torch
+        if vertices.dtype != torch.float64 or vertices.dim() != 3 or tuple(vertices.shape[1:]) != (3, 3) or not vertices.is_contiguous() or not vertices.is_cuda:
+            raise ValueError("vertices: a contiguous float64 [n, 3, 3] tensor on the scene's device")
+        if vertices.device.index != self.device:
+            raise ValueError(f"vertices: the tensor is on cuda:{vertices.device.index}, the scene on cuda:{self.device}")
+        torch.cuda.current_stream(vertices.device).synchronize()  # (the vertices may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_scene_set_triangles_dev(self.h, C.c_void_p(vertices.data_ptr()), int(vertices.shape[0]), C.byref(upd)))
+
+    def set_triangles_ms(self):
+        """sol_scene_set_triangles_ms: device-event ms of the last timed move: upload, records, refit, rest."""
+        out = (C.c_float * 4)()
+        self._chk(self.lib.sol_scene_set_triangles_ms(self.h, out))
+        return dict(zip(("upload", "records", "refit", "rest"), [float(x) for x in out]))
+
+    TRI_DTYPE = np.dtype([("v0", np.float32, 3), ("e1", np.float32, 3), ("e2", np.float32, 3), ("dfs", np.uint32), ("mat", np.int32), ("area", np.float32)])
+    TRI_SHADE_DTYPE = np.dtype([("n", np.float32, 3), ("mat", np.int32), ("t", np.float32, 3), ("u0", np.float32), ("b", np.float32, 3), ("v0", np.float32),
+                                ("u1", np.float32), ("v1", np.float32), ("u2", np.float32), ("v2", np.float32)])
+
+    def triangle_records(self):
+        """sol_scene_triangle_records: (intersect records, shading records, caller triangle of each record) as the device holds them."""
+        n = C.c_uint32()
+        self._chk(self.lib.sol_scene_triangle_records(self.h, None, None, None, 0, C.byref(n)))
+        tris = np.zeros(n.value, dtype=self.TRI_DTYPE)
+        shade = np.zeros(n.value, dtype=self.TRI_SHADE_DTYPE)
+        of = np.zeros(n.value, dtype=np.uint32)
+        self._chk(self.lib.sol_scene_triangle_records(self.h, tris.ctypes.data, shade.ctypes.data, of.ctypes.data, n.value, C.byref(n)))
+        return tris, shade, of
 
     BLOOM_DEFAULT_THRESHOLD = 3.0 ** 0.5  # Vec3::new(1., 1., 1.).length() (bloom.rs:39)
     BLOOM_DEFAULT_MAX = 1.7976931348623157e308  # f64::MAX (bloom.rs:40)
