@@ -45,6 +45,7 @@
 #include "sol_build.h"
 #include "sol_quant.h"
 #include "sol_types.h"
+#include "sol_wide.h"
 
 namespace {
 
@@ -853,12 +854,9 @@ __global__ void __launch_bounds__(64) k_emit(EmitParams P, const Frontier* __res
   if (base_inner + n_inner > SOL_WIDE_MAX_INDEX || base_prim + n_leaf > SOL_WIDE_MAX_INDEX) atomicOr(&P.counters[6], 4u);
   DWide w;
   w.ox = lo[0]; w.oy = lo[1]; w.oz = lo[2];
-  w.meta = (eb[0] - P.emin) | ((eb[1] - P.emin) << 5) | ((eb[2] - P.emin) << 10) | (imask << 15) | (lmask << 22) | (leaf_kind << 29);
+  w.meta = sol_wide_pack_meta(eb, P.emin, imask, lmask, leaf_kind);
   for (int k = 0; k < 12; ++k) w.q[k] = q[k];
-  for (int k = 0; k < 3; ++k) {
-    w.q[2 * k + 1] = (w.q[2 * k + 1] & 0x00FFFFFFu) | (((base_inner >> (8 * k)) & 0xFFu) << 24);
-    w.q[6 + 2 * k + 1] = (w.q[6 + 2 * k + 1] & 0x00FFFFFFu) | (((base_prim >> (8 * k)) & 0xFFu) << 24);
-  }
+  sol_wide_set_bases(w.q, base_inner, base_prim);
   P.wides[f.wide] = w;
 }
 

@@ -13,6 +13,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <system_error>
 #include <thread>
 #include <vector>
 
@@ -149,112 +150,24 @@ static std::vector<DTri> cast_triangles(const SolSceneDesc& d) {
   for (uint32_t i = 0; i < d.n_triangles; ++i) cast_triangle(d.triangles[i], false, tris[i], uv_of);
   return tris;
 }
-// Background blocks (include/solstrale_hip.h, SolSceneInfo::background_blocks): the 8x8 pixel blocks of which it can be PROVED that
-// every camera ray of every pixel, whatever the jitter and the lens sample, sees nothing - so that every sample is the background
-// colour and none has to be generated. A ray of the block (generate_path; Camera::get_ray, src/camera.rs:77-89) leaves a point L of
-// the lens - the eye, or eye + lens_radius * (x u + y w) with (x, y) in the unit disc - towards a point T of the focal plane's
-// rectangle of the block's pixels. Both sets are bounded by quadrilaterals (the lens disc's square; the rectangle widened by a whole
-// pixel on every side plus a bound on the fp32 rounding of generate_path, ordinarily 10^-4 of a pixel). For a plane normal n all those rays lie in the half
-// space n . x <= a with a = max n . L as soon as b = max n . (T - L) <= 0, both maxima taken over the corners (n . (T - L) is linear in
-// T and in L): candidate normals come from the rectangle's edges and the lens corners (and the viewing direction, for what lies behind
-// the camera), built from slightly LARGER quadrilaterals so that the check b <= 0 on the real ones holds with room to spare, and a
-// candidate that fails the check is simply not used. The ray set so bounded walks the DEVICE tree as the kernel decodes it, every
-// child box inflated by `margin` (64 box pads: the kernel's and the oracle's fp32 slab tests err by about one); a box is passed
-// only when a valid plane has the whole box on its outer side. A block whose rays reach no primitive's (leaf) box is a background
-// block: for each of its rays the kernel would find every leaf box missed - the quantised leaf boxes contain the primitives' own
-// padded boxes, which the reference tree of the oracle tests -, so no primitive test would run on either side.
-// Conservative in every step (a block near a silhouette is traced like any other); images never depend on it.
+// Background blocks: the host side of the proof (sol_proof.h has the argument and the per-block function, which a camera move runs on the
+// device). The walk's stack is sized from the layout's own depth: the host gives up on no tree for want of room.
 static void find_background_blocks(const WideLayout& L, uint32_t emin, const DCamera& cam, uint32_t width, uint32_t height, double margin,
                                    std::vector<uint8_t>& flags, uint32_t& n_found, uint32_t& n_pixels) {
-  const uint32_t bx_n = (width + SOL_TILE - 1) / SOL_TILE, by_n = (height + SOL_TILE - 1) / SOL_TILE;
-  flags.assign((size_t)bx_n * by_n, 0);
+  SolProofCamera pc;
+  const bool attempted = sol_proof_camera(cam, width, height, margin, pc) && !L.nodes.empty();
+  flags.assign((size_t)pc.bx_n * pc.by_n, 0);
   n_found = 0; n_pixels = 0;
-  SolProofCamera pc;  // the per-camera part, shared with the device proof of a camera move (sol_camera.h)
-  if (!sol_proof_camera(cam, width, height, margin, pc) || L.nodes.empty()) return;
-  struct V { double x, y, z; };
-  auto dot = [](const V& a, const V& b) { return a.x * b.x + a.y * b.y + a.z * b.z; };
-  auto cross = [](const V& a, const V& b) { return V{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; };
-  auto sub = [](const V& a, const V& b) { return V{a.x - b.x, a.y - b.y, a.z - b.z}; };
-  auto vec = [](const double v[3]) { return V{v[0], v[1], v[2]}; };
-  const V org = vec(pc.org), ll = vec(pc.ll), hh = vec(pc.hh), vv = vec(pc.vv);
-  const int n_lens = pc.n_lens;
-  V lens[4], lens_wide[4];
-  for (int k = 0; k < 4; ++k) { lens[k] = vec(pc.lens[k]); lens_wide[k] = vec(pc.lens_wide[k]); }
-  const double grow = pc.grow;
-  struct Plane { V n; double a; };
-  std::vector<uint32_t> stack;
-  for (uint32_t by = 0; by < by_n; ++by)
-    for (uint32_t bx = 0; bx < bx_n; ++bx) {
-      const uint32_t x0 = bx * SOL_TILE, x1 = std::min(x0 + SOL_TILE, width), y0 = by * SOL_TILE, y1 = std::min(y0 + SOL_TILE, height);
-      // generate_path: u = (px + r) / (W - 1), v = ((H - 1 - py) + r) / (H - 1), r in [0, 1); `grow` pixels of margin on every side
-      auto corners = [&](double grow, V t[4]) {
-        const double u0 = ((double)x0 - grow) / (double)(width - 1), u1 = ((double)x1 + grow) / (double)(width - 1);
-        const double v0 = ((double)height - (double)y1 - grow) / (double)(height - 1), v1 = ((double)height - (double)y0 + grow) / (double)(height - 1);
-        const double cu[4] = {u0, u1, u1, u0}, cv[4] = {v0, v0, v1, v1};
-        for (int k = 0; k < 4; ++k) t[k] = V{ll.x + hh.x * cu[k] + vv.x * cv[k], ll.y + hh.y * cu[k] + vv.y * cv[k], ll.z + hh.z * cu[k] + vv.z * cv[k]};
-      };
-      V T[4], Tw[4];
-      corners(grow, T);
-      corners(grow + 1.0, Tw);
-      Plane plane[17];
-      int n_planes = 0;
-      // keeps the candidate n (pointing AWAY from the rays) if every ray of the block provably stays in n . x <= a
-      auto offer = [&](V n) {
-        const double len = std::sqrt(dot(n, n));
-        if (!(len > 0.) || !std::isfinite(len)) return;
-        double a = -1e300, b = -1e300;
-        for (int j = 0; j < n_lens; ++j) {
-          a = std::max(a, dot(n, lens[j]));
-          for (int k = 0; k < 4; ++k) b = std::max(b, dot(n, sub(T[k], lens[j])));
-        }
-        if (b <= 0.) plane[n_planes++] = Plane{n, a};
-      };
-      for (int k = 0; k < 4; ++k)
-        for (int j = 0; j < n_lens; ++j) {
-          const V& Lj = n_lens == 1 ? org : lens_wide[j];
-          V n = cross(sub(Tw[(k + 1) & 3], Tw[k]), sub(Tw[k], Lj));
-          if (dot(n, sub(Tw[(k + 2) & 3], Lj)) > 0.) n = V{-n.x, -n.y, -n.z};  // the rectangle's far side is inside
-          offer(n);
-        }
-      {
-        const V c{T[0].x + T[1].x + T[2].x + T[3].x - 4. * org.x, T[0].y + T[1].y + T[2].y + T[3].y - 4. * org.y, T[0].z + T[1].z + T[2].z + T[3].z - 4. * org.z};
-        offer(V{-c.x, -c.y, -c.z});  // what lies behind the camera
-      }
-      if (n_planes == 0) continue;
-      // the least value of n . p over a box: > a = the whole box on the outer side
-      auto outside = [&](const double lo[3], const double hi[3]) {
-        for (int k = 0; k < n_planes; ++k) {
-          const V& n = plane[k].n;
-          const double m = std::min(n.x * lo[0], n.x * hi[0]) + std::min(n.y * lo[1], n.y * hi[1]) + std::min(n.z * lo[2], n.z * hi[2]);
-          if (m > plane[k].a) return true;
-        }
-        return false;
-      };
-      bool reached = false;
-      uint32_t visits = 0;
-      stack.assign(1, 0u);
-      while (!stack.empty() && !reached) {
-        const uint32_t ni = stack.back();
-        stack.pop_back();
-        if (ni >= L.nodes.size() || ++visits > 4096u) { reached = true; break; }
-        const WideView v(L.nodes[ni], emin);
-        for (int sl = 0; sl < SOL_WIDE_CHILDREN; ++sl) {
-          if (!v.occupied(sl)) continue;
-          float flo[3], fhi[3];
-          v.box(sl, flo, fhi);
-          const double lo[3] = {(double)flo[0] - margin, (double)flo[1] - margin, (double)flo[2] - margin};
-          const double hi[3] = {(double)fhi[0] + margin, (double)fhi[1] + margin, (double)fhi[2] + margin};
-          if (!(lo[0] <= hi[0] && lo[1] <= hi[1] && lo[2] <= hi[2])) { reached = true; break; }  // (not a box: trace)
-          if (outside(lo, hi)) continue;
-          if (v.leaf(sl)) { reached = true; break; }
-          stack.push_back(v.inner_index(sl));
-        }
-      }
-      if (!reached) {
-        flags[(size_t)by * bx_n + bx] = 1;
-        n_found++;
-        n_pixels += (x1 - x0) * (y1 - y0);
-      }
+  if (!attempted) return;
+  std::vector<uint32_t> stack(std::max(L.depth, 1u));
+  for (uint32_t by = 0; by < pc.by_n; ++by)
+    for (uint32_t bx = 0; bx < pc.bx_n; ++bx) {
+      const bool background = pc.n_lens == 1 ? sol_block_is_background<1>(L.nodes.data(), (uint32_t)L.nodes.size(), emin, pc, bx, by, stack.data(), (uint32_t)stack.size())
+                                             : sol_block_is_background<4>(L.nodes.data(), (uint32_t)L.nodes.size(), emin, pc, bx, by, stack.data(), (uint32_t)stack.size());
+      if (!background) continue;
+      flags[(size_t)by * pc.bx_n + bx] = 1;
+      n_found++;
+      n_pixels += (std::min((bx + 1) * SOL_TILE, width) - bx * SOL_TILE) * (std::min((by + 1) * SOL_TILE, height) - by * SOL_TILE);
     }
 }
 
@@ -1155,7 +1068,9 @@ static int keep_dynamic(const CreateCtx& c, const HostRecords& r, SolScene* s, c
 struct BackgroundProof {
   std::future<void> job; std::vector<uint8_t> block; uint32_t n = 0, pixels = 0;
   void start(const TreeCand& t, const DCamera& cam, uint32_t width, uint32_t height, double margin) {
-    job = std::async(std::launch::async, [this, &t, cam, width, height, margin]() { find_background_blocks(t.lay, t.emin, cam, width, height, margin, block, n, pixels); });
+    auto prove = [this, &t, cam, width, height, margin]() { find_background_blocks(t.lay, t.emin, cam, width, height, margin, block, n, pixels); };
+    try { job = std::async(std::launch::async, prove); }
+    catch (const std::system_error&) { prove(); job = std::async(std::launch::deferred, []() {}); }  // (no thread to be had: proved here, adopted as usual)
   }
   int adopt(SolScene* s, bool verbose) {  // (waits for the proof; idempotent)
     if (!job.valid()) return SOL_OK;

@@ -25,6 +25,7 @@
 #include "sol_geometry.h"
 #include "sol_quant.h"
 #include "sol_triangle.h"
+#include "sol_wide.h"
 
 namespace {
 
@@ -120,11 +121,10 @@ __device__ __forceinline__ Box6 empty_box6() {
 }
 // The padded fp32 box of the child in slot s of a node with `meta` and the two base indices; an empty box for an empty slot.
 __device__ __forceinline__ Box6 child_box(const SolRefitParams& P, uint32_t meta, uint32_t base_inner, uint32_t base_prim, int s, uint32_t& flags) {
-  const uint32_t imask = (meta >> 15) & 0x7Fu, lmask = (meta >> 22) & 0x7Fu, kind = (meta >> 29) & 3u;
-  const uint32_t below = (1u << s) - 1u;
+  const uint32_t imask = sol_wide_imask(meta), lmask = sol_wide_lmask(meta), kind = sol_wide_leaf_kind(meta);
   Box6 b = empty_box6();
   if ((imask >> s) & 1u) {
-    const uint32_t ni = base_inner + __popc(imask & below);
+    const uint32_t ni = base_inner + sol_wide_rank(imask, s);
     if (ni >= P.n_wide) { flags |= SOL_REFIT_CORRUPT; return b; }
     const float* p = P.node_box + (size_t)ni * 6;
 #pragma unroll
@@ -132,7 +132,7 @@ __device__ __forceinline__ Box6 child_box(const SolRefitParams& P, uint32_t meta
     return b;
   }
   if (!((lmask >> s) & 1u)) return b;
-  uint32_t idx = base_prim + __popc(lmask & below), k = kind;
+  uint32_t idx = base_prim + sol_wide_rank(lmask, s), k = kind;
   if (kind == SOL_LEAF_REFS) {
     if (idx >= P.n_leaf_refs) { flags |= SOL_REFIT_CORRUPT; return b; }
     const uint32_t ref = P.leaf_refs[idx];
@@ -178,9 +178,8 @@ __global__ void __launch_bounds__(64) sol_refit_level8_kernel(SolRefitParams P, 
   if (live && ni >= P.n_wide) { flags |= SOL_REFIT_CORRUPT; ni = 0u; }
   const DWide* wp = P.cur + ni;
   const uint32_t meta = wp->meta;
-  const uint32_t t1 = wp->q[1] >> 24, t3 = wp->q[3] >> 24, t5 = wp->q[5] >> 24, t7 = wp->q[7] >> 24, t9 = wp->q[9] >> 24, t11 = wp->q[11] >> 24;
-  const uint32_t base_inner = t1 | (t3 << 8) | (t5 << 16), base_prim = t7 | (t9 << 8) | (t11 << 16);
-  const uint32_t occupied = ((meta >> 15) | (meta >> 22)) & 0x7Fu;
+  const uint32_t base_inner = sol_wide_base_inner(wp->q), base_prim = sol_wide_base_prim(wp->q);
+  const uint32_t occupied = sol_wide_imask(meta) | sol_wide_lmask(meta);
   Box6 c = empty_box6();
   if (live && s < SOL_WIDE_CHILDREN) c = child_box(P, meta, base_inner, base_prim, s, flags);
   Box6 u;
@@ -206,7 +205,9 @@ __global__ void __launch_bounds__(64) sol_refit_level8_kernel(SolRefitParams P, 
     if (s < SOL_WIDE_CHILDREN && ((occupied >> s) & 1u)) quantise_axis(c.lo[a], c.hi[a], P.pad, lo[a], hi[a], scale[a], ql, qh, flags);
     wl[a] = ql << shift; wh[a] = qh << shift;
   }
-  if (s == 7) { wl[0] = t1 << 24; wl[1] = t3 << 24; wl[2] = t5 << 24; wh[0] = t7 << 24; wh[1] = t9 << 24; wh[2] = t11 << 24; }
+  uint32_t qb[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // (the slot-7 bytes alone)
+  sol_wide_set_bases(qb, base_inner, base_prim);
+  if (s == 7) { wl[0] = qb[1]; wl[1] = qb[3]; wl[2] = qb[5]; wh[0] = qb[7]; wh[1] = qb[9]; wh[2] = qb[11]; }
   // packed across the four lanes of a half, then exchanged between the halves
   uint32_t ol[3], oh[3];
 #pragma unroll
@@ -219,7 +220,7 @@ __global__ void __launch_bounds__(64) sol_refit_level8_kernel(SolRefitParams P, 
     // (lanes 0 .. 3 hold the words of slots 0 .. 3 in w*, of slots 4 .. 7 in o*): q[2a] = wl[a], q[2a + 1] = ol[a], q[6 + 2a] = wh[a], q[7 + 2a] = oh[a]
     uint4 v;
     if (s == 0) v = make_uint4(__float_as_uint(lo[0]), __float_as_uint(lo[1]), __float_as_uint(lo[2]),
-                               (meta & 0xFFFF8000u) | (eb[0] - P.emin) | ((eb[1] - P.emin) << 5) | ((eb[2] - P.emin) << 10));
+                               sol_wide_regrid_meta(meta, eb, P.emin));
     else if (s == 1) v = make_uint4(wl[0], ol[0], wl[1], ol[1]);
     else if (s == 2) v = make_uint4(wl[2], ol[2], wh[0], oh[0]);
     else v = make_uint4(wh[1], oh[1], wh[2], oh[2]);

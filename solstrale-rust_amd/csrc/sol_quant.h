@@ -1,6 +1,7 @@
 // sol_quant.h -- the quantisation grid of a 7-wide node on the device, written ONCE for the kernel that emits the tree (sol_build.hip, k_emit)
 // and the kernels that refit it (sol_geometry.hip): a node's exponent and scale per axis, and the plane bytes of one child on one axis, which
-// must CONTAIN the child's box under the device's own decode origin + q * scale (sol_trace.h). The host's twin is WideBuilder::build (sol_tree.h).
+// must CONTAIN the child's box under the device's own decode origin + q * scale (sol_trace.h). The host's own quantiser stays WideBuilder::build (sol_tree.h: its clamping of non-finite quotients differs);
+// the bit fields of the node are sol_wide.h's on both sides.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

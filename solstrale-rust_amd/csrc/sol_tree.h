@@ -22,6 +22,7 @@
 
 #include "../../include/solstrale_hip.h"
 #include "sol_types.h"
+#include "sol_wide.h"
 
 namespace {
 
@@ -211,7 +212,7 @@ struct WideBuilder {
     dx = std::min(dx, 1e15f); dy = std::min(dy, 1e15f); dz = std::min(dz, 1e15f);
     return dx * dy + dy * dz + dz * dx;
   }
-  static float decode(float origin, uint32_t q, float scale) { return origin + (float)q * scale; }  // == device decode
+  static float decode(float origin, uint32_t q, float scale) { return sol_wide_decode(origin, q, scale); }  // == device decode
 
   // ---- which binary sub-trees become the (up to eight) children of a wide node ----
   // GREEDY: open the inner child with the largest surface until eight children (or only leaves) remain.
@@ -464,37 +465,31 @@ struct WideBuilder {
 };
 
 // A node of the device tree read as the kernel reads it (sol_trace.h: 5-bit exponents over emin, masks and leaf kind in `meta`, plane bytes per slot,
-// child addresses implicit from the two base indices in the slot-7 bytes): the host's ONE decoder - and encoder - of DWide, which the background proof and sol_world_tree_check rely on.
+// child addresses implicit from the two base indices in the slot-7 bytes): a view over the field codec of sol_wide.h, which the device's readers and writers of DWide call too.
 struct WideView {
   const DWide& w;
   float origin[3], scale[3];
   uint32_t imask, lmask, kind;
-  WideView(const DWide& n, uint32_t emin) : w(n), origin{n.ox, n.oy, n.oz}, imask((n.meta >> 15) & 0x7Fu), lmask((n.meta >> 22) & 0x7Fu), kind((n.meta >> 29) & 3u) {
-    for (int a = 0; a < 3; ++a) { const uint32_t bits = (((n.meta >> (5 * a)) & 31u) + emin) << 23; std::memcpy(&scale[a], &bits, 4); }
+  WideView(const DWide& n, uint32_t emin) : w(n), origin{n.ox, n.oy, n.oz}, imask(sol_wide_imask(n.meta)), lmask(sol_wide_lmask(n.meta)), kind(sol_wide_leaf_kind(n.meta)) {
+    for (int a = 0; a < 3; ++a) scale[a] = sol_wide_scale(n.meta, a, emin);
   }
   bool occupied(int s) const { return ((imask | lmask) >> s) & 1u; }
   bool inner(int s) const { return (imask >> s) & 1u; }
   bool leaf(int s) const { return (lmask >> s) & 1u; }
   void plane_bytes(int s, uint32_t ql[3], uint32_t qh[3]) const {
-    for (int a = 0; a < 3; ++a) { ql[a] = (w.q[2 * a + (s >> 2)] >> (8 * (s & 3))) & 0xFFu; qh[a] = (w.q[6 + 2 * a + (s >> 2)] >> (8 * (s & 3))) & 0xFFu; }
+    for (int a = 0; a < 3; ++a) { ql[a] = sol_wide_lo_byte(w.q, a, s); qh[a] = sol_wide_hi_byte(w.q, a, s); }
   }
   void box(int s, float lo[3], float hi[3]) const {
     uint32_t ql[3], qh[3];
     plane_bytes(s, ql, qh);
-    for (int a = 0; a < 3; ++a) { lo[a] = WideBuilder::decode(origin[a], ql[a], scale[a]); hi[a] = WideBuilder::decode(origin[a], qh[a], scale[a]); }
+    for (int a = 0; a < 3; ++a) { lo[a] = sol_wide_decode(origin[a], ql[a], scale[a]); hi[a] = sol_wide_decode(origin[a], qh[a], scale[a]); }
   }
-  static uint32_t base_inner(const DWide& w) { return (w.q[1] >> 24) | ((w.q[3] >> 24) << 8) | ((w.q[5] >> 24) << 16); }
-  static uint32_t base_prim(const DWide& w) { return (w.q[7] >> 24) | ((w.q[9] >> 24) << 8) | ((w.q[11] >> 24) << 16); }
-  uint32_t inner_index(int s) const { return base_inner(w) + (uint32_t)__builtin_popcount(imask & ((1u << s) - 1u)); }
-  uint32_t prim_index(int s) const { return base_prim(w) + (uint32_t)__builtin_popcount(lmask & ((1u << s) - 1u)); }
-  // the writing side: exponents relative to emin, masks, leaf kind; the base indices in the slot-7 bytes (top byte of each plane array's second word)
-  static uint32_t pack_meta(const uint32_t e[3], uint32_t emin, uint32_t imask, uint32_t lmask, uint32_t leaf_kind) { return (e[0] - emin) | ((e[1] - emin) << 5) | ((e[2] - emin) << 10) | (imask << 15) | (lmask << 22) | (leaf_kind << 29); }
-  static void set_bases(DWide& w, uint32_t inner, uint32_t prim) {
-    for (int k = 0; k < 3; ++k) {
-      w.q[2 * k + 1] = (w.q[2 * k + 1] & 0x00FFFFFFu) | (((inner >> (8 * k)) & 0xFFu) << 24);
-      w.q[6 + 2 * k + 1] = (w.q[6 + 2 * k + 1] & 0x00FFFFFFu) | (((prim >> (8 * k)) & 0xFFu) << 24);
-    }
-  }
+  static uint32_t base_inner(const DWide& w) { return sol_wide_base_inner(w.q); }
+  static uint32_t base_prim(const DWide& w) { return sol_wide_base_prim(w.q); }
+  uint32_t inner_index(int s) const { return base_inner(w) + sol_wide_rank(imask, s); }
+  uint32_t prim_index(int s) const { return base_prim(w) + sol_wide_rank(lmask, s); }
+  static uint32_t pack_meta(const uint32_t e[3], uint32_t emin, uint32_t imask, uint32_t lmask, uint32_t leaf_kind) { return sol_wide_pack_meta(e, emin, imask, lmask, leaf_kind); }
+  static void set_bases(DWide& w, uint32_t inner, uint32_t prim) { sol_wide_set_bases(w.q, inner, prim); }
 };
 
 // Device form of the wide tree. Depth-first: a node's inner children get consecutive node indices (in slot order), the

@@ -11,12 +11,6 @@
 #include "../../include/solstrale_hip.h"
 #include "sol_types.h"
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define SOL_HD __host__ __device__ __attribute__((always_inline))  // (a call would pass the triangle through scratch memory on the device)
-#else
-#define SOL_HD
-#endif
-
 #define SOL_TRI_PAD_DELTA 0.0001  // PAD_DELTA (src/geo/mod.rs:11)
 
 // A NaN the arithmetic below makes (a zero-area triangle's normal is 0 / 0; equal texture coordinates give r = 1 / 0 and tangents 0 x inf) is

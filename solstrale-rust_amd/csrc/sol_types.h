@@ -4,6 +4,14 @@
 #pragma once
 #include <stdint.h>
 
+// Code written ONCE for the host and the device (sol_wide.h, sol_proof.h, sol_triangle.h): one implementation that both sides compile, so that
+// their agreement bit for bit is a property of the build.
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SOL_HD __host__ __device__ __attribute__((always_inline))  // (a call would pass structs through scratch memory on the device)
+#else
+#define SOL_HD
+#endif
+
 #define SOL_WG 256          // threads per workgroup = 4 wave64
 #ifndef SOL_LDS_STACK
 #define SOL_LDS_STACK 32    // traversal stack entries per lane kept in LDS (u32 each -> 32 KiB per workgroup)

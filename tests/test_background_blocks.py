@@ -2,6 +2,10 @@
 nothing but the constant background, whose samples sol_render sums without tracing them. The proof runs on the host
 (sol_background_blocks, no device needed) and is checked here against the oracle, which knows nothing of it: every sample of every
 pixel of a flagged block must be the background colour, in the float AND the double instantiation."""
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -129,3 +133,55 @@ def test_random_scenes_flagged_blocks_are_background(first):
             img, _ = orc.render(sc, 0, 4, pu.SEED, real=orc.ORC_F32)
             assert (img[_pixel_mask(f, sc)] == _background_sum(sc, 4)).all(), seed
     assert flagged > 200
+
+
+# ---- the host proof's flags, pinned: tests/background_flags_recorded.json is what the commit BEFORE the proof became one function for host
+# and device (csrc/sol_proof.h) answered, written by tests/tools/record_background_flags.py from a build of that commit ----
+RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "background_flags_recorded.json")
+
+
+def _silhouette_scene():  # (test_a_silhouette_block_is_traced)
+    b = SceneBuilder()
+    cam = CameraConfig(40., 0., (0., 0., 5.), (0., 0., 0.), (0., 1., 0.))
+    light = b.DiffuseLight(5., 5., 5.)
+    world = [b.Sphere((0., 0., 0.), .5, light), b.Sphere((0.2, 0.1, -1.), .3, b.Lambertian(b.SolidColor(.5, .5, .5)))]
+    return b.finish(b.Bvh(world), cam, (.2, .3, .5), RenderConfig(256, 256, 8))
+
+
+def _recorded_cases():
+    """(case id, scene maker, tree) of every pinned case: the seven named scenes above with trees 0 and 16, the silhouette scene, the two
+    far-camera scenes, and the random scenes of seeds 0-119 as test_random_scenes_flagged_blocks_are_background makes them, trees 0 and 16."""
+    import random_scenes
+    for name, make, _ in test_flagged_blocks_are_background_in_the_oracle.pytestmark[0].args[1]:
+        yield name, make, (0, 16)
+    yield "silhouette", _silhouette_scene, (0,)
+    for offset in (1e4, 2e6):
+        yield f"far_{offset:g}", (lambda o=offset: _far_scene(o, RenderConfig(256, 256, 6))), (0,)
+    for seed in range(120):
+        make = random_scenes.random_scene if seed % 2 == 0 else random_scenes.needle_scene
+        yield f"random_{seed}", (lambda s=seed, m=make: m(s, width=96, height=72, spp=4)), (0, 16)
+
+
+def flag_records():
+    """{case id/tree: [blocks, flagged blocks, SHA-1 of np.packbits(flags)]} of the loaded library's host proof."""
+    out = {}
+    for name, make, trees in _recorded_cases():
+        sc = make()
+        for tree in trees:
+            f = background_blocks(sc, tree)
+            out[f"{name}/{tree}"] = [int(f.size), int(f.sum()), hashlib.sha1(np.packbits(f).tobytes()).hexdigest()]
+    return out
+
+
+def test_host_flags_match_the_recorded_parent():
+    """The host proof flags, block for block, what it flagged when host and device each had a copy of their own: 257 cases (the named scenes, the
+    silhouette and far-camera scenes, 120 random scenes; trees 0 and 16), at least 60 of which flag something. A difference is a change of
+    which samples are traced: the record is written again (tests/tools/record_background_flags.py) only where that is the intention."""
+    with open(RECORD) as fh:
+        want = json.load(fh)["cases"]
+    assert len(want) == 7 * 2 + 1 + 2 + 120 * 2
+    assert sum(1 for v in want.values() if v[1] > 0) >= 60  # the record is not vacuous
+    got = flag_records()
+    assert sorted(got) == sorted(want)
+    differ = [k for k in want if got[k] != want[k]]
+    assert not differ, (len(differ), differ[:8], [(got[k][:2], want[k][:2]) for k in differ[:8]])

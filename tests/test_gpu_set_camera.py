@@ -47,6 +47,31 @@ _MAKERS = {"statue": _statue, "test_scene": lambda: scenes.create_test_scene(RC)
 _PROVED = ("statue", "test_scene", "lens_balls")
 _scene_cache = {}
 
+# A frame of 100x52: 13x7 = 91 blocks - two workgroups of the proof kernel, the second partly empty - with edge blocks in x and in y.
+RAGGED = RenderConfig(100, 52, SPP, PathTracingShader(8))
+_RAGGED = {"ragged_lens_balls": "lens_balls", "ragged_statue": "statue"}
+_MAKERS["ragged_lens_balls"] = lambda: _lens_balls(RAGGED)
+_MAKERS["ragged_statue"] = lambda: scenes.statue_like(RAGGED, n_triangles=20000)
+for _ragged, _plain in _RAGGED.items():
+    _PAIRS[_ragged] = _PAIRS[_plain]
+
+CHAIN_LEVELS = 48
+_PAIRS["chain"] = (CameraConfig(40., 0., (0., 1., 16.), (0., 0., 0.), (0., 1., 0.)), CameraConfig(40., 0.2, (9., 4., 11.), (0., 0., 0.), (0., 1., 0.)))
+
+
+def _chain():
+    """Spheres along a line whose caller-given BVH is a chain: every node holds one sphere and the rest, CHAIN_LEVELS levels deep."""
+    b = SceneBuilder()
+    grey = b.Lambertian(b.SolidColor(.6, .6, .6))
+    balls = [b.Sphere((-6. + 12. * k / CHAIN_LEVELS, .3 * math.sin(k), .3 * math.cos(2. * k)), .22, b.DiffuseLight(4., 4., 4.) if k == 0 else grey) for k in range(CHAIN_LEVELS + 1)]
+    rest = balls[-1]
+    for ball in reversed(balls[:-1]):
+        rest = b.Bvh([ball, rest])
+    return b.finish(rest, _PAIRS["chain"][0], (.2, .3, .5), RC)
+
+
+_MAKERS["chain"] = _chain
+
 
 def _scene(name, cam):
     """The scene `name` with `cam` in its description (the description's camera field is Camera::new of it: tests/test_camera_abi.py)."""
@@ -68,6 +93,13 @@ def the_camera_pairs_exercise_the_proof():
         a, b = _PAIRS[name]
         fa, fb = background_blocks(_scene(name, a), 0).copy(), background_blocks(_scene(name, b), 0).copy()
         assert fa.mean() >= 0.1 and fb.mean() >= 0.1 and (fa != fb).mean() >= 0.1, (name, fa.mean(), fb.mean(), (fa != fb).mean())
+    for name in _RAGGED:  # the 16-bin host tree the ragged case is created with: both cameras flag something at that size
+        for cam in _PAIRS[name]:
+            f = background_blocks(_scene(name, cam), 1)
+            assert f.shape == (7, 13) and f.any(), name
+    for cam in _PAIRS["chain"]:  # the reference's topology: neither everything nor nothing is flagged
+        f = background_blocks(_scene("chain", cam), 0)
+        assert 0.1 <= f.mean() <= 0.9, f.mean()
 
 
 def _outputs(ds, aux=True):
@@ -146,6 +178,31 @@ def test_the_device_proof_flags_what_the_host_proof_flags(name, tree):
         assert info["background_blocks"] == int(moved.sum()) and info["background_pixels"] == int(_pixel_mask(moved, sc_b).sum())
         ds.set_camera(cam_a)  # and back
         assert (ds.background_flags() == created).all()
+
+
+@pytest.mark.parametrize("name", list(_RAGGED))
+def test_the_device_proof_on_a_ragged_frame(name):
+    """2a. 91 blocks in two workgroups, the last lanes of the second without a block, edge blocks of 4 pixels in x and in y: with the 16-bin
+    host tree the flags after each move are the host proof's over the same tree."""
+    cam_a, cam_b = _PAIRS[name]
+    with DeviceScene(_scene(name, cam_a), world_tree=_abi.TREE_SAH16) as ds:
+        for cam in (cam_a, cam_b, cam_a):
+            ds.set_camera(cam)
+            want = background_blocks(_scene(name, cam), 1)
+            assert (ds.background_flags() == want).all(), (name, int((ds.background_flags() != want).sum()))
+            assert ds.info()["background_blocks"] == int(want.sum()) and ds.info()["background_pixels"] == int(_pixel_mask(want, _scene(name, cam)).sum())
+
+
+def test_the_device_proof_on_a_deep_tree():
+    """2b. A chain of CHAIN_LEVELS binary nodes, created with the host tree that keeps the reference's topology: the walk goes down level after
+    level through its one stack entry per level, and flags what the host proof (the diagnostic, over the same tree) flags."""
+    cam_a, cam_b = _PAIRS["chain"]
+    with DeviceScene(_scene("chain", cam_a), world_tree=_abi.TREE_REF) as ds:
+        assert (ds.background_flags() == background_blocks(_scene("chain", cam_a), 0)).all()
+        for cam in (cam_b, cam_a):
+            ds.set_camera(cam)
+            want = background_blocks(_scene("chain", cam), 0)
+            assert (ds.background_flags() == want).all(), int((ds.background_flags() != want).sum())
 
 
 @pytest.mark.parametrize("name", ["statue", "lens_balls"])
