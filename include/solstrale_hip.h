@@ -38,7 +38,7 @@ extern "C" {
 #define SOL_EDEVICE (-3)   /* HIP runtime error / no GPU                                               */
 #define SOL_EDEPTH (-4)    /* BVH deeper than the traversal stack supports                             */
 #define SOL_ENOMEM (-5)
-#define SOL_ERANGE (-6)    /* sol_scene_set_triangles: the moved geometry leaves the exponent range of the tree - re-create the scene */
+#define SOL_ERANGE (-6)    /* sol_scene_set_triangles / sol_scene_set_primitives: the moved geometry leaves the exponent range of the tree - re-create the scene */
 
 /* ---- child / primitive references ------------------------------------------------------------------
  * A 32-bit reference: kind in bits 31..28, index into the array of that kind in bits 27..0.
@@ -303,7 +303,9 @@ typedef struct SolCreateOptions {
   int32_t dynamic_triangles; /* 1: the handle keeps what sol_scene_set_triangles needs (per triangle: texture coordinates, material, dfs_index;
                                 the primitives' unpadded fp32 boxes; the tree's levels; staging copies of the tree and the triangle records).
                                 0: nothing of it is allocated and sol_scene_set_triangles is refused                                         */
-  int32_t reserved2;
+  int32_t dynamic_primitives; /* 1 (with dynamic_triangles = 1, which it extends): the handle also keeps what sol_scene_set_primitives needs to move
+                                spheres and quads (per sphere and quad: material, dfs_index; a second copy of every box array and of the sphere and
+                                quad records). 0: nothing of it is allocated. This word was `reserved2` (0) in earlier headers: same size, same offset */
 } SolCreateOptions;
 int sol_scene_create_ex(const SolSceneDesc* desc, int device, const SolCreateOptions* options, SolScene** out);
 /* Seconds sol_scene_create spent in: [0] host tree candidates, [1] uploads, [2] device tree build, [3] probe renders. */
@@ -749,6 +751,47 @@ int sol_scene_set_triangles_ms(const SolScene* scene, float ms[4]);
 /* Diagnostic / tests: copies the triangle records the kernels read (n_records x 48 bytes of intersect records, n_records x 64 bytes of shading
  * records, in the tree's leaf order) and the caller's triangle index of each to the host; any pointer may be NULL; *n_records: their number. */
 int sol_scene_triangle_records(SolScene* scene, void* tris, void* shade, uint32_t* triangle_of, size_t capacity, uint32_t* n_records);
+
+/* ---- moving the spheres and quads of a live scene, lights included (EXTENSION, not in the reference) ------------------------------
+ * sol_sphere_from_center: Sphere::new (src/hittable/sphere.rs:25-36) on the CPU, no device needed: fills center, radius and bbox of `out`, bit for
+ * bit as the host library builds a sphere. sol_quad_from_corner: Quad::new (src/hittable/quad.rs:34-66) without a transformer: fills q, u, v, normal,
+ * d, w, area and bbox (padded where an extent is below 0.0001). material and dfs_index are left as they are. SOL_EINVAL: a null argument.
+ *
+ * sol_scene_set_primitives moves any of the three kinds of a handle created with SolCreateOptions.dynamic_primitives = 1 (and dynamic_triangles = 1).
+ * Row i of a kind is primitive i of that kind in the creation description: a triangle row is 9 doubles (v0, v1, v2), a sphere row 4 (centre,
+ * radius), a quad row 9 (q, u, v). A NULL pointer: that kind stays where the last successful call left it; at least one is not NULL; the count
+ * of every kind given equals the scene's. SOL_PRIMS_DEVICE: every pointer given is device memory, 16-byte aligned, and no host copy is made.
+ * All kinds of one call share one refit of the tree, one rebuild of the light tables and one background proof. After SOL_OK every output of the
+ * handle (frames, auxiliary planes, sol_camera_rays, queries, sol_debug_path, adaptive rounds, SolSceneInfo::strict_triangles, sol_light_tables /
+ * sol_light_tree) is byte-identical to that of a handle freshly created, with the same options, from the description D' in which every moved
+ * SolSphere / SolQuad / SolTriangle is the CPU constructor's result for its row (material, uv, dfs_index kept) and every SolBvhNode::bbox the
+ * union of its children's, then brought to the same modes, partition and - if the camera was moved - sol_scene_set_camera. A sphere or quad that
+ * is a light moves as a light: its weight follows sol_light_weights (the quad's area, 4 pi r^2), the light tree and the power tables are rebuilt.
+ *   Reset / kept / background blocks / work order: as sol_scene_set_triangles (SolGeometryUpdate and its two flags are the same).
+ *   SOL_EINVAL before the device is touched: a null scene or set, all three pointers NULL, a wrong count, a size below 8 or above 4096 (either
+ *     struct), unknown flag bits, non-zero reserved words, a misaligned device pointer, a sphere or quad pointer on a handle created without
+ *     dynamic_primitives (a triangle pointer alone needs only dynamic_triangles), a scene with a constant medium, SOL_GEOM_REPROBE while world > 1.
+ *   Refused with the handle exactly as before (no sums cleared; the kinds the call did not move, and those it tried to move, are where the last
+ *     successful call left them): a parameter that is not finite (SOL_EINVAL), coordinates beyond 2^38 (SOL_EINVAL), a node extent beyond the
+ *     tree's exponent range (SOL_ERANGE: re-create the scene).
+ *   Any other failure: as sol_scene_set_triangles - a handle fit only for sol_scene_destroy.
+ * sol_scene_set_triangles(_dev) are this call with the triangle pointer alone. sol_scene_set_triangles_ms reports the last successful move of
+ * either entry point ([0] the upload of the rows, [1] the records and lights kernels of every kind moved, [2] the refit, [3] the rest). */
+#define SOL_PRIMS_DEVICE 1u  /* the pointers of the set are device memory */
+typedef struct SolPrimitiveSet {
+  uint32_t size, flags;     /* sizeof(SolPrimitiveSet); SOL_PRIMS_* */
+  const double* triangles;  /* [n_triangles][9] or NULL */
+  const double* spheres;    /* [n_spheres][4] or NULL   */
+  const double* quads;      /* [n_quads][9] or NULL     */
+  uint32_t n_triangles, n_spheres, n_quads;
+  uint32_t reserved[3];     /* 0 */
+} SolPrimitiveSet;
+int sol_sphere_from_center(const double center[3], double radius, SolSphere* out);
+int sol_quad_from_corner(const double q[3], const double u[3], const double v[3], SolQuad* out);
+int sol_scene_set_primitives(SolScene* scene, const SolPrimitiveSet* set, const SolGeometryUpdate* update);
+/* Diagnostic / tests: copies the sphere (kind SOL_REF_SPHERE: n_records x 32 bytes) or quad (SOL_REF_QUAD: n_records x 80 bytes) records the
+ * kernels read, in device order, and the caller's index of each to the host; either pointer may be NULL; *n_records: their number. */
+int sol_scene_primitive_records(SolScene* scene, int kind, void* records, uint32_t* index_of, size_t capacity, uint32_t* n_records);
 
 #ifdef __cplusplus
 }

@@ -21,6 +21,7 @@
 #include "sol_camera.h"
 #include "sol_scene.h"
 #include "sol_tree.h"
+#include "sol_primitive.h"
 #include "sol_triangle.h"
 
 // The world tree built on the GPU (sol_build.hip): primitives of the reference-shaped tree under `root_ref` (each once - a
@@ -506,7 +507,10 @@ static int check_options_and_header(CreateCtx& c, const SolCreateOptions* opt_in
   if (opt.split_percent > 1000 || opt.reinsertion_rounds > 1024)  // (a typo must not become a build of hours: ten times the references, a thousand rounds)
     return sol_fail(SOL_EINVAL, "SolCreateOptions: split_percent %d (at most 1000) / reinsertion_rounds %d (at most 1024)", opt.split_percent, opt.reinsertion_rounds);
   if (opt.dynamic_triangles != 0 && opt.dynamic_triangles != 1) return sol_fail(SOL_EINVAL, "SolCreateOptions.dynamic_triangles %d (0 or 1)", opt.dynamic_triangles);
-  if (opt.reserved2 != 0) return sol_fail(SOL_EINVAL, "SolCreateOptions.reserved2 must be 0");
+  if (opt.dynamic_primitives != 0 && opt.dynamic_primitives != 1)
+    return sol_fail(SOL_EINVAL, "SolCreateOptions.dynamic_primitives %d (0 or 1; the reserved2 word of earlier headers)", opt.dynamic_primitives);
+  if (opt.dynamic_primitives && !opt.dynamic_triangles)  // (it extends dynamic_triangles; and a stray 1 in what used to be reserved2 is still refused)
+    return sol_fail(SOL_EINVAL, "SolCreateOptions.dynamic_primitives (the reserved2 word of earlier headers) needs dynamic_triangles = 1 as well");
   if (d->abi_version != SOL_ABI_VERSION && d->abi_version != 1u) return sol_fail(SOL_EINVAL, "abi_version %u, expected %u (or 1)", d->abi_version, SOL_ABI_VERSION);
   c.has_env = has_environment(*d);
   if (c.has_env && ((uint64_t)d->env_width * d->env_height > (1ull << 28) || !std::isfinite(d->env_scale))) return sol_fail(SOL_EINVAL, "bad environment map");
@@ -612,20 +616,13 @@ static int cast_primitives(const SolSceneDesc* d, HostRecords& r) {
   for (uint32_t i = 0; i < d->n_quads; ++i) {
     const SolQuad& q = d->quads[i];
     if (!mat_ok(d, q.material)) return sol_fail(SOL_EINVAL, "quad %u: bad material", i);
-    DQuad& o = r.quads[i];
-    o.nx = (float)q.normal[0]; o.ny = (float)q.normal[1]; o.nz = (float)q.normal[2]; o.d = (float)q.d;
-    o.qx = (float)q.q[0]; o.qy = (float)q.q[1]; o.qz = (float)q.q[2]; o.dfs = q.dfs_index;
-    o.wx = (float)q.w[0]; o.wy = (float)q.w[1]; o.wz = (float)q.w[2]; o.mat = q.material;
-    o.ux = (float)q.u[0]; o.uy = (float)q.u[1]; o.uz = (float)q.u[2]; o.area = (float)q.area;
-    o.vx = (float)q.v[0]; o.vy = (float)q.v[1]; o.vz = (float)q.v[2]; o.pad = 0.f;
+    sol_quad_cast(&q, &r.quads[i]);
   }
   r.spheres.resize(d->n_spheres);
   for (uint32_t i = 0; i < d->n_spheres; ++i) {
     const SolSphere& s = d->spheres[i];
     if (!mat_ok(d, s.material)) return sol_fail(SOL_EINVAL, "sphere %u: bad material", i);
-    DSphere& o = r.spheres[i];
-    o.cx = (float)s.center[0]; o.cy = (float)s.center[1]; o.cz = (float)s.center[2]; o.radius = std::fabs((float)s.radius);  // |r|: the reference uses r^2 and a min/max box only (sphere.rs:26-28,68), the fp32 rules of sol_trace.h / sol_shade.h use r itself
-    o.dfs = s.dfs_index; o.mat = s.material; o.pad0 = o.pad1 = 0;
+    sol_sphere_cast(&s, &r.spheres[i]);
   }
   return SOL_OK;
 }
@@ -996,6 +993,46 @@ template <typename T> static int dev_alloc(DevPtr<T>& p, size_t count) {
   HIP_TRY(hipMemset(q, 0, bytes));
   return SOL_OK;
 }
+// SolCreateOptions.dynamic_primitives: what sol_scene_set_primitives needs on top - per sphere and quad what a move does not change
+// and which caller primitive a device record holds, a second copy of every box array and of the sphere and quad records (staging: a refused
+// call must leave the boxes the next partial move refits over as they were), the triangles' boxes and share of S as creation saw them (a
+// first call may move the spheres alone), room for the host route's rows, and which sphere or quad each light is.
+static int keep_dynamic_primitives(const CreateCtx& c, SolScene* s, const WideLayout& L, const std::vector<uint8_t> (&reached)[3], const std::vector<uint32_t>& rec_tri,
+                                   const std::vector<float>& sbox, const std::vector<float>& qbox) {
+  const SolSceneDesc& d = c.d;
+  SolDynamic& y = s->dyn;
+  std::vector<SolPrimStatic> sst(d.n_spheres), qst(d.n_quads);
+  for (uint32_t i = 0; i < d.n_spheres; ++i) sst[i] = SolPrimStatic{d.spheres[i].material, d.spheres[i].dfs_index};
+  for (uint32_t i = 0; i < d.n_quads; ++i) qst[i] = SolPrimStatic{d.quads[i].material, d.quads[i].dfs_index};
+  std::vector<uint32_t> rec_sphere(y.n_spheres), rec_quad(y.n_quads);
+  for (uint32_t i = 0; i < y.n_spheres; ++i) rec_sphere[i] = L.old_of_new[1][i] | (reached[1][i] ? 0u : SOL_DYN_OUTSIDE);
+  for (uint32_t i = 0; i < y.n_quads; ++i) rec_quad[i] = L.old_of_new[2][i] | (reached[2][i] ? 0u : SOL_DYN_OUTSIDE);
+  std::vector<float> tbox((size_t)y.n_recs * 8, 0.0f);
+  float S = 0.0f;
+  for (uint32_t i = 0; i < y.n_recs; ++i)
+    for (int j = 0; j < 6; ++j) {
+      const float v = (float)d.triangles[rec_tri[i] & ~SOL_DYN_OUTSIDE].bbox.v[j];
+      tbox[(size_t)i * 8 + j] = v;
+      const float a = std::fabs(v);
+      if (!(rec_tri[i] & SOL_DYN_OUTSIDE) && std::isfinite(a) && a > S) S = a;
+    }
+  y.S_tri = S;
+  y.needles = sol_scene_has_needles(&d) != 0;
+  y.light_prim_host.assign(d.n_lights, 0u);
+  for (uint32_t i = 0; i < d.n_lights; ++i) {
+    const uint32_t k = SOL_REF_KIND(d.lights[i]);
+    if (k == SOL_REF_SPHERE || k == SOL_REF_QUAD) y.light_prim_host[i] = d.lights[i];
+  }
+  int rc;
+  if ((rc = sol_upload(sst, y.sphere_static)) || (rc = sol_upload(qst, y.quad_static)) || (rc = sol_upload(rec_sphere, y.rec_sphere)) ||
+      (rc = sol_upload(rec_quad, y.rec_quad)) || (rc = sol_upload(tbox, y.tri_box)) || (rc = sol_upload(tbox, y.tri_box2)) ||
+      (rc = sol_upload(sbox, y.sphere_box2)) || (rc = sol_upload(qbox, y.quad_box2)) || (rc = sol_upload(y.light_prim_host, y.light_prim)) ||
+      (rc = dev_alloc(y.spheres2, y.n_spheres)) || (rc = dev_alloc(y.quads2, y.n_quads)) || (rc = dev_alloc(y.sphere_rows, (size_t)y.n_spheres * 4)) ||
+      (rc = dev_alloc(y.quad_rows, (size_t)y.n_quads * 9)) || (rc = dev_alloc(y.out, 4 + 2 * (size_t)d.n_lights + 2)))
+    return rc;
+  y.primitives = true;
+  return SOL_OK;
+}
 static int keep_dynamic(const CreateCtx& c, const HostRecords& r, SolScene* s, const TreeCand& cand) {
   const SolSceneDesc& d = c.d;
   const WideLayout& L = cand.lay;
@@ -1041,11 +1078,20 @@ static int keep_dynamic(const CreateCtx& c, const HostRecords& r, SolScene* s, c
   float S = 0.0f;
   auto take = [&](double v) { const float a = std::fabs((float)v); if (std::isfinite(a) && a > S) S = a; };  // (box_pad_for's)
   std::vector<float> sbox(r.spheres.size() * 6), qbox(r.quads.size() * 6);
-  for (size_t i = 0; i < r.spheres.size(); ++i)
-    for (int j = 0; j < 6; ++j) { const double v = d.spheres[L.old_of_new[1][i]].bbox.v[j]; sbox[i * 6 + j] = (float)v; if (reached[1][i]) take(v); }
-  for (size_t i = 0; i < r.quads.size(); ++i)
-    for (int j = 0; j < 6; ++j) { const double v = d.quads[L.old_of_new[2][i]].bbox.v[j]; qbox[i * 6 + j] = (float)v; if (reached[2][i]) take(v); }
-  y.static_S = S;
+  // the unpadded fp32 boxes of one kind in device order, and that kind's share of S (over the records the tree reaches)
+  auto share = [&](int a, std::vector<float>& box) {
+    S = 0.0f;
+    for (size_t i = 0; i < box.size() / 6; ++i)
+      for (int j = 0; j < 6; ++j) {
+        const uint32_t o = L.old_of_new[a][i];
+        const double v = a == 1 ? d.spheres[o].bbox.v[j] : d.quads[o].bbox.v[j];
+        box[i * 6 + j] = (float)v;
+        if (reached[a][i]) take(v);
+      }
+    return S;
+  };
+  y.S_sphere = share(1, sbox);
+  y.S_quad = share(2, qbox);
   S = 0.0f;
   for (int j = 0; j < 3; ++j) take(d.camera.origin[j]);
   y.cam_S = S;
@@ -1061,7 +1107,7 @@ static int keep_dynamic(const CreateCtx& c, const HostRecords& r, SolScene* s, c
       (rc = dev_alloc(y.out, 4 + 2 * (size_t)d.n_lights)))
     return rc;
   y.on = true;
-  return SOL_OK;
+  return c.opt.dynamic_primitives ? keep_dynamic_primitives(c, s, L, reached, rec_tri, sbox, qbox) : SOL_OK;
 }
 // 11. Background blocks: constant background only (an environment map is looked up per ray). The proof is host work (0.06 s for C5 at 1080p): it
 // runs on a thread of its own beside the cost probe's render and is adopted after it (the probe traces every block either way).

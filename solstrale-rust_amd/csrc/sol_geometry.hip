@@ -1,4 +1,4 @@
-// sol_geometry.hip -- the kernels of sol_scene_set_triangles (host side: sol_geometry.cpp).
+// sol_geometry.hip -- the kernels of sol_scene_set_triangles and sol_scene_set_primitives (host side: sol_geometry.cpp).
 //
 // Records. One thread per device triangle record (a pre-split triangle has several, all copies of one): the caller's 72 bytes of vertices and
 // the 32-byte row of what does not move (texture coordinates, material, dfs_index) go through sol_triangle_new (sol_triangle.h: the f64 code the
@@ -19,10 +19,16 @@
 // are copied: the topology does not change. Eight lanes per node: lane s loads and quantises child s, the union goes through three
 // __shfl_xor steps, the plane bytes are packed across the lanes and four lanes store the node as dwordx4. (One thread per node was built
 // and measured 2.4-3.1x slower over the refit launches, profiles/set_triangles_ab.txt; it is in the history, not in the library.)
-// Both kernels write staging buffers only.
+// Spheres and quads. One thread per device record: the caller's row (32 / 72 bytes) through the record's caller index and the 8 bytes
+// of what does not move go through sol_sphere_new / sol_quad_new (sol_primitive.h: the f64 code of the CPU entry points) and creation's casts; the
+// record leaves as dwordx4 stores (2 / 5), the unpadded fp32 box as three dwordx2 (the refit reads these arrays with a stride of 24 bytes). The
+// same reduction as the triangles': a parameter that is not finite, the largest |fp32 box coordinate| of the reached records. A third launch over
+// the lights writes the f64 area (the quad's |u x v|, 4 pi r^2) of every light of a moved kind.
+// Every kernel writes staging buffers only.
 #include <hip/hip_runtime.h>
 
 #include "sol_geometry.h"
+#include "sol_primitive.h"
 #include "sol_quant.h"
 #include "sol_triangle.h"
 #include "sol_wide.h"
@@ -110,6 +116,109 @@ __global__ void __launch_bounds__(64) sol_triangle_lights_kernel(const double* _
   float4* td = reinterpret_cast<float4*>(light_tri + i);
   td[0] = ri.q[0]; td[1] = ri.q[1]; td[2] = ri.q[2];
   area[i] = T.area;
+}
+
+// ---- spheres and quads ----
+__device__ __forceinline__ bool all_finite(const double* v, int n) {
+  bool f = true;
+  for (int k = 0; k < n; ++k) f = f && (fabs(v[k]) < __builtin_huge_val());  // (false for a NaN too)
+  return f;
+}
+// the end of a records kernel: by wave first, then one atomic per wave and fact
+__device__ __forceinline__ void reduce_records(bool bad, uint32_t bad_bit, uint32_t s_bits, uint32_t* __restrict__ flags, uint32_t* __restrict__ s_out) {
+  const bool any_bad = __ballot(bad) != 0ull;
+  s_bits = wave_max_u32(s_bits);
+  if ((threadIdx.x & 63u) == 0u) {
+    if (any_bad) atomicOr(flags, bad_bit);
+    if (s_bits) atomicMax(s_out, s_bits);
+  }
+}
+__device__ __forceinline__ uint32_t store_box(const SolAabb& b, bool reached, float* __restrict__ dst) {
+  float bx[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) bx[k] = (float)b.v[k];
+  uint32_t s_bits = 0u;
+  if (reached) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) s_bits = max(s_bits, __float_as_uint(fabsf(bx[k])));
+  }
+  float2* bd = reinterpret_cast<float2*>(dst);
+  bd[0] = make_float2(bx[0], bx[1]); bd[1] = make_float2(bx[2], bx[3]); bd[2] = make_float2(bx[4], bx[5]);
+  return s_bits;
+}
+
+__global__ void __launch_bounds__(256) sol_sphere_records_kernel(const double* __restrict__ rows, const SolPrimStatic* __restrict__ st, const uint32_t* __restrict__ rec,
+                                                                 uint32_t n_recs, uint32_t n_rows, DSphere* __restrict__ spheres, float* __restrict__ box,
+                                                                 uint32_t* __restrict__ flags, uint32_t* __restrict__ s_out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool bad = false;
+  uint32_t s_bits = 0u;
+  const uint32_t rs = i < n_recs ? rec[i] : 0xFFFFFFFFu;
+  const uint32_t t = rs & ~SOL_DYN_OUTSIDE;
+  if (i < n_recs && t < n_rows) {
+    const double2* p = reinterpret_cast<const double2*>(rows + (size_t)t * 4);
+    const double2 a = p[0], b = p[1];
+    const double v[4] = {a.x, a.y, b.x, b.y};
+    const SolPrimStatic c = st[t];
+    SolSphere S;
+    S.material = c.material; S.dfs_index = c.dfs_index;
+    bad = !all_finite(v, 4);
+    sol_sphere_new(v, v[3], &S);
+    union { DSphere r; float4 q[2]; } o;
+    sol_sphere_cast(&S, &o.r);
+    float4* d = reinterpret_cast<float4*>(spheres + i);
+    d[0] = o.q[0]; d[1] = o.q[1];
+    s_bits = store_box(S.bbox, !(rs & SOL_DYN_OUTSIDE), box + (size_t)i * 6);
+  }
+  reduce_records(bad, 2u, s_bits, flags, s_out);
+}
+
+__global__ void __launch_bounds__(256) sol_quad_records_kernel(const double* __restrict__ rows, const SolPrimStatic* __restrict__ st, const uint32_t* __restrict__ rec,
+                                                               uint32_t n_recs, uint32_t n_rows, DQuad* __restrict__ quads, float* __restrict__ box,
+                                                               uint32_t* __restrict__ flags, uint32_t* __restrict__ s_out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  bool bad = false;
+  uint32_t s_bits = 0u;
+  const uint32_t rs = i < n_recs ? rec[i] : 0xFFFFFFFFu;
+  const uint32_t t = rs & ~SOL_DYN_OUTSIDE;
+  if (i < n_recs && t < n_rows) {
+    double v[9];
+    const double* p = rows + (size_t)t * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = p[k];
+    const SolPrimStatic c = st[t];
+    SolQuad Q;
+    Q.material = c.material; Q.dfs_index = c.dfs_index;
+    bad = !all_finite(v, 9);
+    sol_quad_new(v, v + 3, v + 6, &Q);
+    union { DQuad r; float4 q[5]; } o;
+    sol_quad_cast(&Q, &o.r);
+    float4* d = reinterpret_cast<float4*>(quads + i);
+#pragma unroll
+    for (int k = 0; k < 5; ++k) d[k] = o.q[k];
+    s_bits = store_box(Q.bbox, !(rs & SOL_DYN_OUTSIDE), box + (size_t)i * 6);
+  }
+  reduce_records(bad, 4u, s_bits, flags, s_out);
+}
+
+__global__ void __launch_bounds__(64) sol_primitive_lights_kernel(const double* __restrict__ sphere_rows, const double* __restrict__ quad_rows,
+                                                                  const uint32_t* __restrict__ light_prim, uint32_t n_lights, uint32_t n_spheres, uint32_t n_quads,
+                                                                  double* __restrict__ area) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n_lights) return;
+  const uint32_t ref = light_prim[i], kind = SOL_REF_KIND(ref), idx = SOL_REF_INDEX(ref);
+  if (kind == SOL_REF_SPHERE && sphere_rows && idx < n_spheres) {
+    const double r = sphere_rows[(size_t)idx * 4 + 3];
+    area[i] = 4.0 * 3.14159265358979323846 * r * r;  // sol_light_weights_of's expression
+  } else if (kind == SOL_REF_QUAD && quad_rows && idx < n_quads) {
+    double v[9];
+    const double* p = quad_rows + (size_t)idx * 9;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[k] = p[k];
+    SolQuad Q;
+    sol_quad_new(v, v + 3, v + 6, &Q);
+    area[i] = Q.area;
+  }
 }
 
 // ---- refit ----
@@ -250,5 +359,23 @@ hipError_t sol_launch_triangle_lights(const double* verts, const SolTriStatic* s
 hipError_t sol_launch_refit_level(const SolRefitParams& P, uint32_t first, uint32_t count, hipStream_t stream) {
   if (count == 0) return hipSuccess;
   hipLaunchKernelGGL(sol_refit_level8_kernel, dim3((count + 7u) / 8u), dim3(64), 0, stream, P, first, count);
+  return hipGetLastError();
+}
+hipError_t sol_launch_sphere_records(const double* rows, const SolPrimStatic* st, const uint32_t* rec, uint32_t n_recs, uint32_t n_rows, DSphere* spheres,
+                                     float* box, uint32_t* flags, uint32_t* s_bits, hipStream_t stream) {
+  if (n_recs == 0) return hipSuccess;
+  hipLaunchKernelGGL(sol_sphere_records_kernel, dim3((n_recs + 255u) / 256u), dim3(256), 0, stream, rows, st, rec, n_recs, n_rows, spheres, box, flags, s_bits);
+  return hipGetLastError();
+}
+hipError_t sol_launch_quad_records(const double* rows, const SolPrimStatic* st, const uint32_t* rec, uint32_t n_recs, uint32_t n_rows, DQuad* quads,
+                                   float* box, uint32_t* flags, uint32_t* s_bits, hipStream_t stream) {
+  if (n_recs == 0) return hipSuccess;
+  hipLaunchKernelGGL(sol_quad_records_kernel, dim3((n_recs + 255u) / 256u), dim3(256), 0, stream, rows, st, rec, n_recs, n_rows, quads, box, flags, s_bits);
+  return hipGetLastError();
+}
+hipError_t sol_launch_primitive_lights(const double* sphere_rows, const double* quad_rows, const uint32_t* light_prim, uint32_t n_lights, uint32_t n_spheres,
+                                       uint32_t n_quads, double* area, hipStream_t stream) {
+  if (n_lights == 0 || (!sphere_rows && !quad_rows)) return hipSuccess;
+  hipLaunchKernelGGL(sol_primitive_lights_kernel, dim3((n_lights + 63u) / 64u), dim3(64), 0, stream, sphere_rows, quad_rows, light_prim, n_lights, n_spheres, n_quads, area);
   return hipGetLastError();
 }

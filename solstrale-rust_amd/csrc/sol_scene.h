@@ -4,7 +4,7 @@
 //   sol_create.cpp  sol_scene_create in stages: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h), world-tree candidates, upload, probes; the tree diagnostics
 //   sol_launch.cpp  sol_render* / auxiliary planes / debug hooks: launches of the kernels in sol_render.hip
 //   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
-//   sol_geometry.cpp sol_scene_set_triangles: new vertices for the triangles of a live scene, records and tree boxes recomputed on the device (sol_geometry.hip)
+//   sol_geometry.cpp sol_scene_set_triangles / sol_scene_set_primitives: the triangles, spheres and quads of a live scene moved, records and tree boxes recomputed on the device (sol_geometry.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
 // There is NO CPU fallback: without a HIP device every compute entry point fails with SOL_EDEVICE.
@@ -87,16 +87,19 @@ struct DevTree {
 // What a handle created with SolCreateOptions.dynamic_triangles keeps for sol_scene_set_triangles (sol_geometry.cpp); empty otherwise.
 struct SolTriStatic { float uv[6]; int32_t material; uint32_t dfs_index; };  // per caller triangle: what a move does not change (uv0, uv1, uv2 in the reference's order)
 static_assert(sizeof(SolTriStatic) == 32, "SolTriStatic");
-#define SOL_DYN_OUTSIDE 0x80000000u  // rec_tri: the record's triangle is not reached by the world tree (its box is no part of the root's)
+#define SOL_DYN_OUTSIDE 0x80000000u  // rec_tri / rec_sphere / rec_quad: the record's primitive is not reached by the world tree (its box is no part of the root's)
+struct SolPrimStatic { int32_t material; uint32_t dfs_index; };  // per caller sphere / quad: what a move does not change
 struct SolDynamic {
   bool on = false;
   uint32_t n_tris = 0, n_recs = 0;       // caller triangles; device triangle records (more where pre-splitting made copies)
   uint32_t n_spheres = 0, n_quads = 0, n_leaf_refs = 0;  // lengths of the arrays the refit indexes
-  float cam_S = 0.f, static_S = 0.f;     // box_pad_for's S: the creation camera's share, the spheres' and quads' share (largest |fp32 coordinate|)
+  float cam_S = 0.f;                     // box_pad_for's S (largest |fp32 coordinate| of the root box and the camera): the creation camera's share,
+  float S_sphere = 0.f, S_quad = 0.f;    //   the spheres' and the quads' as creation or the last committed move left them,
+  float S_tri = 0.f; bool needles = false;  // and (dynamic_primitives) the triangles' with the needle flag - a call combines them with the fresh shares of the kinds it moves
   DevPtr<SolTriStatic> tri_static;       // [n_tris]
   DevPtr<uint32_t> rec_tri;              // [n_recs] DevTree::old_index[0], SOL_DYN_OUTSIDE or-ed in
   DevPtr<float> tri_box;                 // [n_recs][8] the unpadded fp32 cast box of the record's triangle (xmin xmax ymin ymax zmin zmax 0 0): the records kernel writes it
-  DevPtr<float> sphere_box, quad_box;    // [n][6] the same of the spheres / quads, in device order (they do not move)
+  DevPtr<float> sphere_box, quad_box;    // [n][6] the same of the spheres / quads, in device order
   DevPtr<uint32_t> level_nodes;          // wide node indices, level by level (the root first)
   std::vector<uint32_t> level_off;       // level l = level_nodes[level_off[l] .. level_off[l + 1])
   DevPtr<float> node_box;                // [n_wide][6] scratch of the refit: the union of a node's padded child boxes
@@ -106,7 +109,17 @@ struct SolDynamic {
   std::vector<uint32_t> light_src_host;
   std::vector<double> light_lum;         // [n_lights] luminance of the light's emission (sol_light_weights_of's factor)
   DevPtr<double> verts;                  // [n_tris][9] where the host route uploads the caller's vertices
-  DevPtr<uint32_t> out;                  // device: 4 flag words (non-finite, needle, S bits, refit flags), then n_lights f64 areas
+  DevPtr<uint32_t> out;                  // device: 4 flag words (non-finite: bit 0 a triangle, 1 a sphere, 2 a quad; needle; the triangles' S bits; refit flags), then
+                                         // n_lights f64 areas, then (dynamic_primitives) the spheres' and the quads' S bits
+  // ---- SolCreateOptions.dynamic_primitives (sol_scene_set_primitives); empty otherwise ----
+  bool primitives = false;
+  DevPtr<SolPrimStatic> sphere_static, quad_static;  // [caller spheres] / [caller quads]
+  DevPtr<uint32_t> rec_sphere, rec_quad; // [n] DevTree::old_index[1] / [2], SOL_DYN_OUTSIDE or-ed in
+  DevPtr<float> tri_box2, sphere_box2, quad_box2;  // staging of the box arrays: swapped at the commit with the records of the kinds a call moved
+  DevPtr<DSphere> spheres2; DevPtr<DQuad> quads2;  // staging of DevTree::spheres / quads
+  DevPtr<double> sphere_rows, quad_rows; // [n][4] / [n][9] where the host route uploads the caller's rows
+  DevPtr<uint32_t> light_prim;           // [n_lights] the description's reference of light i where it is a sphere or a quad, else 0
+  std::vector<uint32_t> light_prim_host;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // with sol_kernel_timing: call start, vertices uploaded, records written, tree refitted, call end
   float last_ms[4] = {0.f, 0.f, 0.f, 0.f};
 };
@@ -233,7 +246,7 @@ struct SolScene {
   // the spill area of the query kernel's own grid. None of them is the render launch's.
   void* query_in = nullptr; void* query_out = nullptr; size_t query_cap = 0;
   uint32_t* query_spill = nullptr; size_t query_spill_words = 0;
-  SolDynamic dyn;  // sol_scene_set_triangles (sol_geometry.cpp)
+  SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
 std::vector<double> sol_light_weights_of(const SolSceneDesc* d);

@@ -131,10 +131,16 @@ OPT_SWITCH_BELOW, OPT_MAX_BLOCKS_PER_CU, OPT_KERNEL, OPT_WORK_ORDER, OPT_FINE_TA
 UNIQUE_ID_BYTES = 128
 
 
+class _DynamicPrimitivesWord(C.Union):
+    """The last word of SolCreateOptions under both of its names: `reserved2` in the header before DESIGN.md 18, `dynamic_primitives` since."""
+    _fields_ = [("dynamic_primitives", C.c_int32), ("reserved2", C.c_int32)]
+
+
 class SolCreateOptions(C.Structure):
+    _anonymous_ = ("_last",)
     _fields_ = [("size", C.c_uint32), ("world_tree", C.c_int32), ("no_work_order_probe", C.c_int32), ("split_percent", C.c_int32),
                 ("reinsertion_rounds", C.c_int32), ("no_background_blocks", C.c_int32), ("reserved", C.c_int32 * 2),
-                ("dynamic_triangles", C.c_int32), ("reserved2", C.c_int32)]
+                ("dynamic_triangles", C.c_int32), ("_last", _DynamicPrimitivesWord)]
 
 
 class SolSceneInfo(C.Structure):
@@ -218,6 +224,15 @@ SOL_GEOM_NO_BACKGROUND_PROOF, SOL_GEOM_REPROBE = 1, 2
 class SolGeometryUpdate(C.Structure):
     """EXTENSION: how sol_scene_set_triangles moves the triangles of a live scene. Not in ABI_STRUCTS."""
     _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+SOL_PRIMS_DEVICE = 1
+
+
+class SolPrimitiveSet(C.Structure):
+    """EXTENSION: the rows sol_scene_set_primitives moves the triangles, spheres and quads of a live scene to. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("flags", C.c_uint32), ("triangles", C.c_void_p), ("spheres", C.c_void_p), ("quads", C.c_void_p),
+                ("n_triangles", C.c_uint32), ("n_spheres", C.c_uint32), ("n_quads", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 class SolTreeCheck(C.Structure):
@@ -313,6 +328,10 @@ def load_hip():
     _sig(lib, "sol_scene_set_triangles_dev", C.c_int, [P, C.c_void_p, C.c_uint32, C.POINTER(SolGeometryUpdate)])
     _sig(lib, "sol_scene_set_triangles_ms", C.c_int, [P, C.POINTER(C.c_float)])
     _sig(lib, "sol_scene_triangle_records", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
+    _sig(lib, "sol_sphere_from_center", C.c_int, [C.c_void_p, C.c_double, C.POINTER(SolSphere)])
+    _sig(lib, "sol_quad_from_corner", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SolQuad)])
+    _sig(lib, "sol_scene_set_primitives", C.c_int, [P, C.POINTER(SolPrimitiveSet), C.POINTER(SolGeometryUpdate)])
+    _sig(lib, "sol_scene_primitive_records", C.c_int, [P, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _libs["hip"] = lib
     return lib
 
@@ -329,7 +348,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_light_sampling", "sol_light_sampling_check", "sol_light_weights", "sol_light_tables", "sol_light_tree", "sol_light_eval",
                "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8",
                "sol_query_dev", "sol_query", "sol_camera_rays", "sol_scene_set_camera", "sol_scene_background_flags",
-               "sol_triangle_from_vertices", "sol_scene_set_triangles", "sol_scene_set_triangles_dev", "sol_scene_set_triangles_ms", "sol_scene_triangle_records"]
+               "sol_triangle_from_vertices", "sol_scene_set_triangles", "sol_scene_set_triangles_dev", "sol_scene_set_triangles_ms", "sol_scene_triangle_records",
+               "sol_sphere_from_center", "sol_quad_from_corner", "sol_scene_set_primitives", "sol_scene_primitive_records"]
 
 
 def load_host():

@@ -84,22 +84,50 @@ def triangle_from_vertices(v, uv=None, out=None):
     return out
 
 
+def sphere_from_center(center, radius, out=None):
+    """sol_sphere_from_center (CPU, no device): the SolSphere of a centre (3 float64) and a radius - center, radius and bbox; `out`: a SolSphere to
+    fill instead of a new one (its material and dfs_index stay)."""
+    lib = _abi.load_hip()
+    c = np.ascontiguousarray(center, dtype=np.float64).reshape(3)
+    out = _abi.SolSphere() if out is None else out
+    rc = lib.sol_sphere_from_center(c.ctypes.data, float(radius), C.byref(out))
+    if rc != 0:
+        raise DeviceError(rc, lib.sol_last_error().decode(errors="replace"))
+    return out
+
+
+def quad_from_corner(q, u, v, out=None):
+    """sol_quad_from_corner (CPU, no device): the SolQuad of a corner q and the edges u, v (3 float64 each) - q, u, v, normal, d, w, area and the
+    padded bbox; `out`: a SolQuad to fill instead of a new one (its material and dfs_index stay)."""
+    lib = _abi.load_hip()
+    a = [np.ascontiguousarray(x, dtype=np.float64).reshape(3) for x in (q, u, v)]
+    out = _abi.SolQuad() if out is None else out
+    rc = lib.sol_quad_from_corner(a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, C.byref(out))
+    if rc != 0:
+        raise DeviceError(rc, lib.sol_last_error().decode(errors="replace"))
+    return out
+
+
 class DeviceScene:
     """sol_scene_create .. sol_scene_destroy"""
 
-    def __init__(self, scene, device=0, world_tree=None, no_work_order_probe=False, split_percent=0, no_background_blocks=False, dynamic_triangles=False):
+    def __init__(self, scene, device=0, world_tree=None, no_work_order_probe=False, split_percent=0, no_background_blocks=False, dynamic_triangles=False,
+                 dynamic_primitives=False):
         """split_percent: SolCreateOptions.split_percent (0: the default budget of the device build's triangle pre-splitting, < 0: none);
         no_background_blocks: SolCreateOptions.no_background_blocks (do not look for blocks that provably see only the background);
-        dynamic_triangles: SolCreateOptions.dynamic_triangles (keep what set_triangles needs)."""
+        dynamic_triangles: SolCreateOptions.dynamic_triangles (keep what set_triangles needs); dynamic_primitives: SolCreateOptions.dynamic_primitives
+        (keep what set_primitives needs to move spheres and quads as well; it extends dynamic_triangles and sets it)."""
         self.lib = _abi.load_hip()
         self.scene = scene
         self.h = C.c_void_p()
+        dynamic_triangles = bool(dynamic_triangles or dynamic_primitives)
         if world_tree is None and not no_work_order_probe and not split_percent and not no_background_blocks and not dynamic_triangles:
             rc = self.lib.sol_scene_create(scene.desc_ptr, device, C.byref(self.h))
         else:
             opt = _abi.SolCreateOptions(size=C.sizeof(_abi.SolCreateOptions), world_tree=int(world_tree or 0),
                                         no_work_order_probe=1 if no_work_order_probe else 0, split_percent=int(split_percent),
-                                        no_background_blocks=1 if no_background_blocks else 0, dynamic_triangles=1 if dynamic_triangles else 0)
+                                        no_background_blocks=1 if no_background_blocks else 0, dynamic_triangles=1 if dynamic_triangles else 0,
+                                        dynamic_primitives=1 if dynamic_primitives else 0)
             rc = self.lib.sol_scene_create_ex(scene.desc_ptr, device, C.byref(opt), C.byref(self.h))
         if rc != 0:
             self.h = None
@@ -480,6 +508,60 @@ class DeviceScene:
         of = np.zeros(n.value, dtype=np.uint32)
         self._chk(self.lib.sol_scene_triangle_records(self.h, tris.ctypes.data, shade.ctypes.data, of.ctypes.data, n.value, C.byref(n)))
         return tris, shade, of
+
+    # ---- new places for the spheres and quads of a live scene, lights included (EXTENSION) ----
+    def set_primitives(self, triangles=None, spheres=None, quads=None, background_proof=True, reprobe=False):
+        """sol_scene_set_primitives: row i of `triangles` (float64 [n, 3, 3]: v0, v1, v2), `spheres` ([n, 4]: centre, radius) and `quads` ([n, 3, 3]:
+        q, u, v) moves primitive i of that kind in the creation description; None: that kind stays. The scene must have been created with
+        dynamic_primitives=True (triangles alone: dynamic_triangles=True is enough). numpy arrays go the host route; contiguous float64 torch
+        tensors on the scene's device go the device route without a copy; the two are not mixed. One refit, one light rebuild and one background
+        proof per call. Clears the sums and the auxiliary planes, ends an adaptive session; blocks."""
+        upd = _abi.SolGeometryUpdate(size=C.sizeof(_abi.SolGeometryUpdate),
+                                     flags=(0 if background_proof else _abi.SOL_GEOM_NO_BACKGROUND_PROOF) | (_abi.SOL_GEOM_REPROBE if reprobe else 0))
+        given = {"triangles": (triangles, (3, 3)), "spheres": (spheres, (4,)), "quads": (quads, (3, 3))}
+        given = {k: v for k, v in given.items() if v[0] is not None}
+        if not given:
+            raise ValueError("set_primitives: at least one of triangles, spheres, quads")
+        on_device = [not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") for a, _ in given.values()]
+        if any(on_device) and not all(on_device):
+            raise ValueError("set_primitives: host arrays and device tensors in one call (give all kinds the same way)")
+        ps = _abi.SolPrimitiveSet(size=C.sizeof(_abi.SolPrimitiveSet), flags=_abi.SOL_PRIMS_DEVICE if on_device[0] else 0)
+        keep = []
+        for name, (a, shape) in given.items():
+            what = f"{name}: a contiguous float64 [n, {', '.join(map(str, shape))}] " + ("tensor on the scene's device" if on_device[0] else "array")
+            if on_device[0]:
+                import torch
+                if a.dtype != torch.float64 or a.dim() != 1 + len(shape) or tuple(a.shape[1:]) != shape or not a.is_contiguous() or not a.is_cuda:
+                    raise ValueError(what)
+                if a.device.index != self.device:
+                    raise ValueError(f"{name}: the tensor is on cuda:{a.device.index}, the scene on cuda:{self.device}")
+                torch.cuda.current_stream(a.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
+                ptr = a.data_ptr()
+            else:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.ndim != 1 + len(shape) or a.shape[1:] != shape:
+                    raise ValueError(what)
+                ptr = a.ctypes.data
+            keep.append(a)
+            # (an empty array's pointer may be null: the kind is given all the same)
+            setattr(ps, name, C.c_void_p(ptr or 16))
+            setattr(ps, "n_" + name, int(a.shape[0]))
+        self._chk(self.lib.sol_scene_set_primitives(self.h, C.byref(ps), C.byref(upd)))
+
+    SPHERE_DTYPE = np.dtype([("c", np.float32, 3), ("radius", np.float32), ("dfs", np.uint32), ("mat", np.int32), ("pad", np.uint32, 2)])
+    QUAD_DTYPE = np.dtype([("n", np.float32, 3), ("d", np.float32), ("q", np.float32, 3), ("dfs", np.uint32), ("w", np.float32, 3), ("mat", np.int32),
+                           ("u", np.float32, 3), ("area", np.float32), ("v", np.float32, 3), ("pad", np.float32)])
+
+    def primitive_records(self, kind):
+        """sol_scene_primitive_records: (records, caller index of each record) of the spheres (kind "sphere" or REF_SPHERE) or the quads ("quad",
+        REF_QUAD) as the device holds them."""
+        kind = {"sphere": _abi.REF_SPHERE, "quad": _abi.REF_QUAD}.get(kind, kind)
+        n = C.c_uint32()
+        self._chk(self.lib.sol_scene_primitive_records(self.h, int(kind), None, None, 0, C.byref(n)))
+        rec = np.zeros(n.value, dtype=self.SPHERE_DTYPE if kind == _abi.REF_SPHERE else self.QUAD_DTYPE)
+        of = np.zeros(n.value, dtype=np.uint32)
+        self._chk(self.lib.sol_scene_primitive_records(self.h, int(kind), rec.ctypes.data, of.ctypes.data, n.value, C.byref(n)))
+        return rec, of
 
     BLOOM_DEFAULT_THRESHOLD = 3.0 ** 0.5  # Vec3::new(1., 1., 1.).length() (bloom.rs:39)
     BLOOM_DEFAULT_MAX = 1.7976931348623157e308  # f64::MAX (bloom.rs:40)
