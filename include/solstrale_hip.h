@@ -690,6 +690,41 @@ int sol_query(SolScene* scene, int mode, const SolRay* rays, size_t n, void* out
  * stream. SOL_EINVAL: an empty rectangle or one that leaves the frame. */
 int sol_camera_rays(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* rays_dev);
 
+/* ---- radiance queries (EXTENSION, not in the reference) -------------------------------------------------------------------
+ * "How much light arrives along this ray?" - the path-traced colour along the caller's own rays: light probes and irradiance volumes,
+ * lightmap texels, reflection captures, a second viewpoint without a second handle. Rays are SolRay rows, valid by the rule of the ray
+ * queries above and decided by the kernel itself before any search; an invalid ray answers (0, 0, 0, samples = 0).
+ *   Paths.    For a valid ray i, each sample s in [first_sample, first_sample + samples) is one path: the render's RNG stream of
+ *             (seed, key, s) with its counter set to first_draw, where (key, first_draw) is the ray's SolRayKey (pixel, first_draw) or, with
+ *             keys == NULL, (key_base + i wrapping, the configuration's first_draw). The path starts as a camera path does, with the caller's
+ *             origin and direction. Its first search runs over the ray's own [tmin, tmax] - a miss there is the background, or the
+ *             environment map along the direction -, every later segment over [0.001, +inf) as in a render.
+ *   Shading.  The handle's current shader, max_depth, sol_env_sampling and sol_light_sampling modes: the answer a render would give in
+ *             that state (an Albedo or Normal shader gives those quantities along the rays).
+ *   Sums.     SolRadiance holds SUMS over the samples, not means, added in the render's order: samples in chunks of 16 counted from
+ *             first_sample, a chunk sum 0 + c0 + c1 + .. in sample order, the result ((0 + chunk0) + chunk1) + ..
+ *   Identity. Over the rays sol_camera_rays writes for (rectangle, sample s, seed), keyed by what sol_camera_ray_keys writes for the same
+ *             arguments, with samples = 1 and first_sample = s, the answers equal bit for bit what sol_clear; sol_render(s, 1, seed);
+ *             sol_read leaves in those pixels.
+ *   Neutral.  A radiance query writes the caller's output and scratch of its own; it touches neither the accumulator, the auxiliary planes,
+ *             the render's work counter, the partition, an adaptive session nor SolStats. Frames rendered around it do not change.
+ * SOL_EINVAL (sol_last_error names the reason): a null scene or configuration; a wrong size; reserved != 0; samples == 0, or
+ * first_sample + samples beyond 2^32 - 16; n above 2^31; a scene with a constant medium (not supported yet); with n > 0 a null ray or output
+ * pointer. n == 0 succeeds and touches nothing. These are checked before the device is: SOL_EDEVICE without a GPU comes after them. */
+typedef struct SolRayKey { uint32_t pixel, first_draw; } SolRayKey;            /* 8 bytes; 8-byte aligned in device memory */
+typedef struct SolRadiance { float r, g, b; uint32_t samples; } SolRadiance;   /* 16 bytes; sums, not means; 16-byte aligned in device memory */
+/* size = sizeof(SolRadianceConfig) = 32: size 0, samples 4, first_sample 8, first_draw 12, seed 16, key_base 24, reserved 28 */
+typedef struct SolRadianceConfig { uint32_t size, samples, first_sample, first_draw; uint64_t seed; uint32_t key_base, reserved; } SolRadianceConfig;
+/* Device pointers (n SolRay, n SolRayKey or NULL, n SolRadiance out, on the scene's device), on the scene's stream, asynchronous. */
+int sol_radiance_dev(SolScene* scene, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig* config, void* out_dev);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_radiance(SolScene* scene, const SolRay* rays, const SolRayKey* keys, size_t n, const SolRadianceConfig* config, SolRadiance* out);
+/* Writes one SolRayKey per pixel of [x0, x1) x [y0, y1), row-major like sol_camera_rays, for (sample, seed) to device memory:
+ * pixel = row * width + x, first_draw = the RNG counter after the camera ray was made (2 for a pinhole; with a thin lens 2 plus twice the
+ * rejection rounds of the lens disc). Asynchronous on the scene's stream. SOL_EINVAL: a null pointer, an empty rectangle or one that
+ * leaves the frame. */
+int sol_camera_ray_keys(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* keys_dev);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

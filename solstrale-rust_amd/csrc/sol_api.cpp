@@ -56,6 +56,7 @@ SolDevOverrides sol_dev_overrides() {
   o.max_bpc = num("SOL_MAX_BPC", -1);
   o.fine_tail = std::max(-2, num("SOL_FINE_TAIL", -2));
   o.pool_swap_min = std::max(0, num("SOL_POOL_SWAP", 0));
+  o.radiance_rows = std::max(0, num("SOL_RADIANCE_ROWS", 0));
   o.probe_radii = num("SOL_PROBE_RADII", -1);
   o.pool_slots = std::max(0, num("SOL_POOL_SLOTS", 0));
   o.wf_slots = std::max(0, num("SOL_WF_SLOTS", 0));
@@ -228,7 +229,8 @@ void sol_scene_destroy(SolScene* s) {
   void* ptrs[] = {s->mats, s->texs, s->texels, s->env, s->light_tri,
                   s->acc_own, s->partial, s->image, s->rgb8, s->work, s->spill, s->counters, s->pool, s->queue, s->wf_ctr,
                   s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block, s->env_tables, s->light_tree, s->light_tables,
-                  s->aux_img[0], s->aux_img[1], s->den_buf, s->query_in, s->query_out, s->query_spill, s->proof_flags, s->dyn.light_tri2};
+                  s->aux_img[0], s->aux_img[1], s->den_buf, s->query_in, s->query_out, s->query_spill, s->proof_flags, s->dyn.light_tri2,
+                  s->rad_work, s->rad_partial, s->rad_spill, s->rad_in, s->rad_keys, s->rad_out};
   s->tree.release();
   s->adaptive.release();
   if (s->wf_ctr_host) hipHostFree(s->wf_ctr_host);
@@ -528,6 +530,149 @@ int sol_camera_rays(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t
   HIP_TRY(hipSetDevice(s->device));
   if ((rc = sol_scene_to_device(s))) return rc;
   HIP_TRY(sol_launch_camera_rays(s->dscene, x0, y0, x1 - x0, y1 - y0, sample, seed, rays_dev, s->stream));
+  return SOL_OK;
+}
+
+}  // extern "C"
+
+// ---- radiance queries (include/solstrale_hip.h; kernels: sol_radiance.hip) ----
+namespace {
+constexpr size_t RADIANCE_STAGE_RAYS = (size_t)1 << 20;    // the host route stages at most this many rays at a time (32 + 8 + 16 bytes each)
+
+// What both routes refuse; nothing here needs a device. The part that needs no handle either is a function that is not given one:
+// behind a non-null scene pointer the configuration and n are judged before the handle is read for the first time.
+int radiance_config_check(const char* fn, size_t n, const SolRadianceConfig* cfg) {
+  if (!cfg) return sol_fail(SOL_EINVAL, "%s: null configuration", fn);
+  if (cfg->size != sizeof(SolRadianceConfig)) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.size is %u, not %zu", fn, cfg->size, sizeof(SolRadianceConfig));
+  if (cfg->reserved != 0u) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.reserved must be 0", fn);
+  if (cfg->samples == 0u) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.samples is 0", fn);
+  if ((uint64_t)cfg->first_sample + cfg->samples > 0xFFFFFFF0ull) return sol_fail(SOL_EINVAL, "%s: first_sample + samples goes beyond 2^32 - 16", fn);
+  if (n > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: %zu rays in one call (at most 2^31)", fn, n);
+  return SOL_OK;
+}
+// *go = false: nothing to do (n == 0, which succeeds on any scene and touches nothing).
+int radiance_check(const SolScene* s, const char* fn, const void* rays, size_t n, const SolRadianceConfig* cfg, const void* out, bool* go) {
+  *go = false;
+  if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
+  if (const int rc = radiance_config_check(fn, n, cfg)) return rc;
+  if (n == 0) return SOL_OK;
+  if (s->has_medium)
+    return sol_fail(SOL_EINVAL, "%s: the scene has a constant medium - the render kernels for media have no register left for a radiance lane's ray; not supported yet", fn);
+  if (!rays || !out) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? "ray" : "output");
+  *go = true;
+  return SOL_OK;
+}
+
+template <typename T>
+int radiance_grow(SolScene* s, T** buf, size_t* have, size_t need, size_t elem) {
+  if (need <= *have) return SOL_OK;
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  if (*buf) hipFree(*buf);
+  *buf = nullptr; *have = 0;
+  HIP_TRY(hipMalloc((void**)buf, need * elem));
+  *have = need;
+  return SOL_OK;
+}
+
+// n <= 2^31 rays (and keys, or null) in device memory, on the scene's stream. key_base: the key of ray 0 of THIS batch when keys is null.
+int radiance_launch(SolScene* s, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
+  int rc;
+  if ((rc = sol_scene_to_device(s))) return rc;
+  // the estimator a render would run now (sol_render_impl): the ENV / LT builds under the path-tracing shader only
+  const bool env = s->env_is && s->S.shader == SOL_SHADER_PATH_TRACING;
+  const bool lt = s->light_mode != 0u && s->S.shader == SOL_SHADER_PATH_TRACING && s->S.n_lights > 1u;
+  int bpc = sol_radiance_blocks_per_cu(s->strict_triangles, env, lt);
+  if (s->max_bpc > 0) bpc = std::max(1, std::min(bpc, s->max_bpc));
+  const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
+  if (!s->rad_work) HIP_TRY(hipMalloc((void**)&s->rad_work, 64));
+  const uint32_t total_chunks = (uint32_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
+  // One chunk: one launch writes the answers. More: the chunk sums go through the partial buffer, at most SolScene::rad_partial_max_rows of them per
+  // launch - the call is split over rays (answers are per ray) and, for sample ranges beyond 16 * 2^18, over windows of chunks (the resolve
+  // kernel carries a ray's sum from one window to the next: the same additions in the same order).
+  const size_t max_rows = std::max<size_t>(64, s->rad_partial_max_rows);
+  const size_t win_chunks = std::min<size_t>(total_chunks, max_rows / 64);
+  const size_t slice_rays = total_chunks == 1 ? n : std::max<size_t>(64, max_rows / win_chunks / 64 * 64);
+  for (size_t at = 0; at < n; at += slice_rays) {
+    const size_t k = std::min(slice_rays, n - at);
+    RadianceParams P{};
+    P.n_rays = (uint32_t)k;
+    P.n_groups = (uint32_t)((k + 63) / 64);
+    P.end_sample = cfg.first_sample + cfg.samples;
+    P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
+    P.key_base = key_base + (uint32_t)at;
+    P.first_draw = cfg.first_draw;
+    P.switch_below = s->switch_below;
+    P.direct = total_chunks == 1 ? 1u : 0u;
+    const char* rays_at = (const char*)rays_dev + at * sizeof(SolRay);
+    const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
+    char* out_at = (char*)out_dev + at * sizeof(SolRadiance);
+    if (!P.direct && (rc = radiance_grow(s, &s->rad_partial, &s->rad_partial_rows, (size_t)P.n_groups * 64 * win_chunks, sizeof(SolRadiance)))) return rc;
+    for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
+      P.n_chunks = (uint32_t)std::min<size_t>(win_chunks, total_chunks - c0);
+      P.first_sample = cfg.first_sample + (uint32_t)c0 * SOL_CHUNK;
+      const uint64_t items = (uint64_t)P.n_chunks * P.n_groups * 64u;  // (<= 2^31: far below the headroom of the 32-bit work counter, SOL_MAX_ITEMS)
+      P.n_items = (uint32_t)items;
+      // the grid and the spill tail of THIS launch (the render launch's area is sized for another)
+      const uint32_t need_blocks = (uint32_t)((items + SOL_WG - 1) / SOL_WG);
+      const uint32_t grid = std::max(1u, std::min((uint32_t)(s->n_cu * bpc), need_blocks));
+      P.total_threads = grid * SOL_WG;
+      const size_t spill_words = may_spill ? (size_t)grid * SOL_WG * (s->tree.depth - SOL_LDS_STACK) : 16;
+      if ((rc = radiance_grow(s, &s->rad_spill, &s->rad_spill_words, spill_words, sizeof(uint32_t)))) return rc;
+      HIP_TRY(hipMemsetAsync(s->rad_work, 0, sizeof(uint32_t), s->stream));
+      HIP_TRY(sol_launch_radiance(s->dscene, P, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial, s->rad_work, s->rad_spill, grid, s->stream));
+      if (!P.direct) HIP_TRY(sol_launch_radiance_resolve(P, rays_at, s->rad_partial, out_at, cfg.samples, c0 != 0, s->stream));
+    }
+  }
+  return SOL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sol_radiance_dev(SolScene* s, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig* cfg, void* out_dev) {
+  int rc;
+  bool go;
+  if ((rc = radiance_check(s, "sol_radiance_dev", rays_dev, n, cfg, out_dev, &go)) || !go || (rc = query_device_check())) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return radiance_launch(s, rays_dev, keys_dev, n, *cfg, cfg->key_base, out_dev);
+}
+
+int sol_radiance(SolScene* s, const SolRay* rays, const SolRayKey* keys, size_t n, const SolRadianceConfig* cfg, SolRadiance* out) {
+  int rc;
+  bool go;
+  if ((rc = radiance_check(s, "sol_radiance", rays, n, cfg, out, &go)) || !go || (rc = query_device_check())) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
+  if (cap > s->rad_cap) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (void** p : {&s->rad_in, &s->rad_keys, &s->rad_out}) { if (*p) hipFree(*p); *p = nullptr; }
+    s->rad_cap = 0;
+    HIP_TRY(hipMalloc(&s->rad_in, cap * sizeof(SolRay)));
+    HIP_TRY(hipMalloc(&s->rad_keys, cap * sizeof(SolRayKey)));
+    HIP_TRY(hipMalloc(&s->rad_out, cap * sizeof(SolRadiance)));
+    s->rad_cap = cap;
+  }
+  for (size_t at = 0; at < n; at += cap) {  // (answers are per ray: the split changes nothing)
+    const size_t k = std::min(cap, n - at);
+    HIP_TRY(hipMemcpyAsync(s->rad_in, rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
+    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys, keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
+    if ((rc = radiance_launch(s, s->rad_in, keys ? s->rad_keys : nullptr, k, *cfg, cfg->key_base + (uint32_t)at, s->rad_out))) return rc;
+    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out, k * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  return SOL_OK;
+}
+
+int sol_camera_ray_keys(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* keys_dev) {
+  int rc;
+  if (!s || !keys_dev) return sol_fail(SOL_EINVAL, "sol_camera_ray_keys: null %s", !s ? "scene" : "key pointer");
+  if ((rc = query_device_check())) return rc;
+  if (x0 >= x1 || y0 >= y1 || x1 > s->S.width || y1 > s->S.height)
+    return sol_fail(SOL_EINVAL, "sol_camera_ray_keys: the rectangle [%u, %u) x [%u, %u) is empty or leaves the %u x %u frame", x0, x1, y0, y1, s->S.width, s->S.height);
+  if ((uint64_t)(x1 - x0) * (y1 - y0) > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "sol_camera_ray_keys: more than 2^31 rays");
+  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = sol_scene_to_device(s))) return rc;
+  HIP_TRY(sol_launch_camera_ray_keys(s->dscene, x0, y0, x1 - x0, y1 - y0, sample, seed, keys_dev, s->stream));
   return SOL_OK;
 }
 

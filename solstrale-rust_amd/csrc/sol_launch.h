@@ -39,6 +39,28 @@ hipError_t sol_launch_query(const DevScene* dS, bool any, bool may_spill, bool s
 int sol_query_blocks_per_cu(bool any, bool strict);
 hipError_t sol_launch_camera_rays(const DevScene* dS, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, void* rays,
                                   hipStream_t stream);
+// ---- sol_radiance.hip: radiance queries. One launch: n_rays SolRay (and SolRayKey, or null) on the device, samples
+// [first_sample, ..) in n_chunks chunks of SOL_CHUNK, the last one ending at end_sample. Work item = (ray, chunk), chunk-major, 64 consecutive rays per wave ----
+struct RadianceParams {
+  uint32_t n_rays, n_groups;   // rays of this launch; groups of 64 of them ((n_rays + 63) / 64)
+  uint32_t n_chunks, n_items;  // chunks of this launch; n_chunks * n_groups * 64
+  uint32_t first_sample;       // the first sample of this launch's first chunk
+  uint32_t end_sample;         // one past the call's last sample (the last chunk may be short)
+  uint32_t seed_lo, seed_hi;
+  uint32_t key_base;           // keys == null: ray i of the launch draws from the stream of key_base + i (wrapping) ..
+  uint32_t first_draw;         // .. with its counter starting here
+  uint32_t switch_below;       // as RenderParams::switch_below
+  uint32_t total_threads;      // grid * SOL_WG (spill stack stride)
+  uint32_t direct;             // 1: the call has one chunk, the kernel writes the answers itself; 0: chunk sums into `partial` [chunk][n_groups * 64]
+};
+hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool may_spill, bool strict, bool env, bool lt, const void* rays, const void* keys,
+                               void* out, void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream);
+int sol_radiance_blocks_per_cu(bool strict, bool env, bool lt);
+// the chunk sums of one launch added in chunk order onto 0 (or, accumulate, onto what `out` holds) and written with `samples`
+hipError_t sol_launch_radiance_resolve(const RadianceParams& P, const void* rays, const void* partial, void* out, uint32_t samples, bool accumulate,
+                                       hipStream_t stream);
+hipError_t sol_launch_camera_ray_keys(const DevScene* dS, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, void* keys,
+                                      hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

@@ -15,6 +15,7 @@
 
 #include "sol_launch.h"
 #include "sol_path.h"
+#include "sol_ray.h"
 
 namespace {
 
@@ -26,16 +27,7 @@ struct QueryLane {
   bool busy;          // the lane holds a ray that is not answered yet
 };
 
-// finite: neither an infinity nor a NaN
-DEV bool query_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
-// a = (origin, tmin), b = (direction, tmax). Valid: every component finite (tmax may be +inf), a direction that is not zero, 0 <= tmin <= tmax
-// (a NaN tmax fails the last comparison, -inf the one before).
-DEV bool query_ray_valid(float4 a, float4 b) {
-  const bool finite = query_finite(a.x) && query_finite(a.y) && query_finite(a.z) && query_finite(a.w) && query_finite(b.x) &&
-                      query_finite(b.y) && query_finite(b.z);
-  const bool dir = b.x != 0.0f || b.y != 0.0f || b.z != 0.0f;
-  return finite && dir && a.w >= 0.0f && a.w <= b.w;
-}
+// (query_ray_valid, the validity rule of a ray: sol_ray.h - the radiance queries decide by the same one)
 
 template <bool ANY>
 DEV void query_write(const DevScene& S, const Stack& st, void* __restrict__ out, uint32_t i, uint32_t status, const Hit& h) {

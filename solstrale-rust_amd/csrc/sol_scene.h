@@ -66,6 +66,7 @@ struct SolDevOverrides {
   int max_bpc = -1;              // SOL_MAX_BPC
   int fine_tail = -2;            // SOL_FINE_TAIL (-2: not set)
   int probe_radii = -1;          // SOL_PROBE_RADII (AUTO device build: 1 = emit and probe both clustering radii, 0 = never, -1 = by the collapse costs)
+  int radiance_rows = 0;         // SOL_RADIANCE_ROWS: bound of the radiance queries' partial buffer in rows (0: the default, 2^24) - tests drive the splits with a small one
   int pool_swap_min = 0;         // SOL_POOL_SWAP (pool kernel: RenderParams::swap_min; 0: the default)
   int pool_slots = 0, wf_slots = 0, wf_min_items = -1;  // SOL_POOL_SLOTS / SOL_WF_SLOTS / SOL_WF_MIN_ITEMS (v2 / v3)
   std::string rccl_lib;          // SOL_RCCL_LIB: the communication library to dlopen instead of librccl.so.1 (tests)
@@ -246,6 +247,13 @@ struct SolScene {
   // the spill area of the query kernel's own grid. None of them is the render launch's.
   void* query_in = nullptr; void* query_out = nullptr; size_t query_cap = 0;
   uint32_t* query_spill = nullptr; size_t query_spill_words = 0;
+  // Radiance queries (sol_radiance.hip): their own work counter, partial buffer (chunk sums, 16 bytes per (chunk, ray); grown on
+  // demand up to a bound), spill tail and host-route staging (rays, keys, answers; rad_cap rays each). None of them is the render launch's.
+  uint32_t* rad_work = nullptr;
+  void* rad_partial = nullptr; size_t rad_partial_rows = 0;
+  size_t rad_partial_max_rows = (size_t)1 << 24;  // the bound: 256 MiB of chunk sums (SOL_RADIANCE_ROWS)
+  uint32_t* rad_spill = nullptr; size_t rad_spill_words = 0;
+  void* rad_in = nullptr; void* rad_keys = nullptr; void* rad_out = nullptr; size_t rad_cap = 0;
   SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).

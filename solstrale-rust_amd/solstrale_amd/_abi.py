@@ -210,6 +210,22 @@ class SolRayHit(C.Structure):
                 ("dfs_index", C.c_uint32), ("material", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SolRayKey(C.Structure):
+    """EXTENSION: the RNG key and the starting counter of a radiance-query ray (sol_radiance). Not in ABI_STRUCTS."""
+    _fields_ = [("pixel", C.c_uint32), ("first_draw", C.c_uint32)]
+
+
+class SolRadiance(C.Structure):
+    """EXTENSION: the answer of sol_radiance to one ray: colour SUMS over `samples` samples. Not in ABI_STRUCTS."""
+    _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("samples", C.c_uint32)]
+
+
+class SolRadianceConfig(C.Structure):
+    """EXTENSION: the sample range, seed and default keys of a radiance query. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("samples", C.c_uint32), ("first_sample", C.c_uint32), ("first_draw", C.c_uint32),
+                ("seed", C.c_uint64), ("key_base", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
 
 
@@ -321,6 +337,9 @@ def load_hip():
     _sig(lib, "sol_query_dev", C.c_int, [P, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_query", C.c_int, [P, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_camera_rays", C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p])
+    _sig(lib, "sol_radiance_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolRadianceConfig), C.c_void_p])
+    _sig(lib, "sol_radiance", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolRadianceConfig), C.c_void_p])
+    _sig(lib, "sol_camera_ray_keys", C.c_int, [P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p])
     _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
     _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _sig(lib, "sol_triangle_from_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolTriangle)])
@@ -349,7 +368,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_denoise_check", "sol_resolve_aux", "sol_denoise", "sol_denoise_rgb8",
                "sol_query_dev", "sol_query", "sol_camera_rays", "sol_scene_set_camera", "sol_scene_background_flags",
                "sol_triangle_from_vertices", "sol_scene_set_triangles", "sol_scene_set_triangles_dev", "sol_scene_set_triangles_ms", "sol_scene_triangle_records",
-               "sol_sphere_from_center", "sol_quad_from_corner", "sol_scene_set_primitives", "sol_scene_primitive_records"]
+               "sol_sphere_from_center", "sol_quad_from_corner", "sol_scene_set_primitives", "sol_scene_primitive_records",
+               "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys"]
 
 
 def load_host():

@@ -447,6 +447,55 @@ class DeviceScene:
         self.sync()  # (the scene's stream is not torch's)
         return out
 
+    # ---- radiance queries (EXTENSION) ----
+    def radiance(self, rays, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0):
+        """sol_radiance: the path-traced colour along the caller's rays, `samples` samples from `first_sample` on, in the handle's current shader
+        and sampling modes. keys: per ray (pixel, first_draw) - the RNG key and the starting counter; None: key_base + i and first_draw. A numpy
+        [n, 8] float32 array (and an optional [n, 2] uint32 one) goes the host route and returns (rgb_sum [n, 3] float32, samples [n] uint32);
+        contiguous torch tensors on the scene's device ([n, 8] float32, [n, 2] int32) go through sol_radiance_dev without a host copy and return
+        one [n, 4] float32 device tensor of the raw rows (r, g, b sums and the bits of the sample count); the call waits for torch's stream
+        before and for the scene's stream after the launch."""
+        cfg = _abi.SolRadianceConfig(size=C.sizeof(_abi.SolRadianceConfig), samples=int(samples), first_sample=int(first_sample), first_draw=int(first_draw),
+                                     seed=int(seed), key_base=int(key_base) & 0xFFFFFFFF)
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: sol_radiance stages the arrays itself
+            a = np.ascontiguousarray(rays, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError("rays: an [n, 8] float32 array of (origin xyz, tmin, direction xyz, tmax)")
+            k = None
+            if keys is not None:
+                k = np.ascontiguousarray(keys.cpu().numpy() if hasattr(keys, "data_ptr") else keys).astype(np.uint32, copy=False)
+                if k.shape != (a.shape[0], 2):
+                    raise ValueError("keys: an [n, 2] uint32 array of (pixel, first_draw), one row per ray")
+                k = np.ascontiguousarray(k)
+            out = np.zeros((a.shape[0], 4), dtype=np.float32)
+            self._chk(self.lib.sol_radiance(self.h, a.ctypes.data, None if k is None else k.ctypes.data, a.shape[0], C.byref(cfg), out.ctypes.data))
+            return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
+        import torch
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
+            raise ValueError("rays: a contiguous [n, 8] float32 tensor on the scene's device")
+        if rays.device.index != self.device:
+            raise ValueError(f"rays: the tensor is on cuda:{rays.device.index}, the scene on cuda:{self.device}")
+        n = int(rays.shape[0])
+        if keys is not None and (not hasattr(keys, "data_ptr") or keys.dtype != torch.int32 or tuple(keys.shape) != (n, 2) or not keys.is_contiguous()
+                                 or keys.device != rays.device):
+            raise ValueError("keys: a contiguous [n, 2] int32 tensor of (pixel, first_draw) on the rays' device")
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        torch.cuda.current_stream(rays.device).synchronize()  # (the rays may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_radiance_dev(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(cfg),
+                                            C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def camera_ray_keys(self, x0, y0, x1, y1, sample, seed):
+        """sol_camera_ray_keys: (pixel, first_draw) of the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 2] int32 device
+        tensor: with them, radiance() over camera_rays() of the same arguments is the render's own sample."""
+        import torch
+        h, w = max(int(y1) - int(y0), 0), max(int(x1) - int(x0), 0)
+        out = torch.empty((h, w, 2), dtype=torch.int32, device=f"cuda:{self.device}")
+        self._chk(self.lib.sol_camera_ray_keys(self.h, x0, y0, x1, y1, sample, seed, C.c_void_p(out.data_ptr())))
+        self.sync()  # (the scene's stream is not torch's)
+        return out
+
     # ---- a new camera for a live scene (EXTENSION; DESIGN.md 16) ----
     def set_camera(self, camera, background_proof=True, reprobe=False):
         """sol_scene_set_camera: the same scene from another viewpoint, without building anything again. `camera`: a CameraConfig (cast by
