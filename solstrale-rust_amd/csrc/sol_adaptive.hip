@@ -156,21 +156,11 @@ static int adaptive_compact(SolScene* s) {
   const uint32_t n_bg = s->background_enabled && s->S.block_order && s->n_background_local <= s->n_local_blocks ? s->n_background_local : 0u;
   const uint32_t n_first = s->S.block_order ? std::min(s->S.n_first, s->n_local_blocks - n_bg) : 0u;
   hipLaunchKernelGGL(sol_adaptive_compact_kernel, dim3(1), dim3(SOL_COMPACT_WG), 0, s->stream, s->S.block_order, s->n_local_blocks, n_first, n_bg,
-                     A.active, A.order, A.ctr);
+                     A.active.get(), A.order.get(), A.ctr.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(A.ctr_host, A.ctr, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(A.ctr_host.get(), A.ctr.get(), 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  A.n_first = A.ctr_host[0]; A.n_traced = A.ctr_host[1]; A.n_background = A.ctr_host[2];
-  return SOL_OK;
-}
-
-template <typename T>
-static int ensure(T** p, size_t& cap, size_t n) {
-  if (*p && cap >= n) return SOL_OK;
-  if (*p) hipFree(*p);
-  *p = nullptr; cap = 0;
-  HIP_TRY(hipMalloc((void**)p, std::max<size_t>(n, 16) * sizeof(T)));
-  cap = n;
+  A.n_first = A.ctr_host.get()[0]; A.n_traced = A.ctr_host.get()[1]; A.n_background = A.ctr_host.get()[2];
   return SOL_OK;
 }
 
@@ -191,19 +181,16 @@ int sol_adaptive_begin(SolScene* s, const SolAdaptive* c) {
   SolAdaptiveSession& A = s->adaptive;
   A.open = false;
   const size_t nl = s->n_local_blocks, nb = (size_t)s->blocks_x * s->blocks_y;
-  size_t active_cap = A.order_cap;  // (active and order have the same length)
   int rc;
-  if ((rc = ensure(&A.state, A.state_slots, nl * 64u * 2u)) || (rc = ensure(&A.order, A.order_cap, nl)) || (rc = ensure(&A.active, active_cap, nl)) ||
-      (rc = ensure(&A.counts, A.counts_cap, nb)))
+  if ((rc = A.state.reserve(s->stream, nl * 64u * 2u)) || (rc = A.order.reserve(s->stream, nl)) || (rc = A.active.reserve(s->stream, nl)) ||
+      (rc = A.counts.reserve(s->stream, nb)) || (rc = A.ctr.reserve(s->stream, 4)))
     return rc;
-  if (!A.ctr) HIP_TRY(hipMalloc((void**)&A.ctr, 4 * sizeof(uint32_t)));
-  if (!A.ctr_host) HIP_TRY(hipHostMalloc((void**)&A.ctr_host, 4 * sizeof(uint32_t), hipHostMallocDefault));
-  if (!A.dscene) HIP_TRY(hipMalloc((void**)&A.dscene, sizeof(DevScene)));
+  if (!A.ctr_host) HIP_TRY(sol_pinned_alloc(A.ctr_host, 4));
   HIP_TRY(hipMemsetAsync(s->acc, 0, s->acc_floats * sizeof(float), s->stream));
-  HIP_TRY(hipMemsetAsync(A.state, 0, nl * 64u * 2u * sizeof(float), s->stream));
-  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)A.active, 1, nl, s->stream));
-  HIP_TRY(hipMemsetAsync(A.counts, 0, nb * sizeof(uint32_t), s->stream));
-  HIP_TRY(hipMemsetAsync(A.ctr, 0, 4 * sizeof(uint32_t), s->stream));
+  HIP_TRY(hipMemsetAsync(A.state.get(), 0, nl * 64u * 2u * sizeof(float), s->stream));
+  HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)A.active.get(), 1, nl, s->stream));
+  HIP_TRY(hipMemsetAsync(A.counts.get(), 0, nb * sizeof(uint32_t), s->stream));
+  HIP_TRY(hipMemsetAsync(A.ctr.get(), 0, 4 * sizeof(uint32_t), s->stream));
   A.round = c->round; A.min_samples = c->min_samples; A.max_samples = c->max_samples; A.threshold = c->threshold;
   A.rounds_done = 0;
   if ((rc = adaptive_compact(s))) return rc;
@@ -219,11 +206,11 @@ int sol_adaptive_round(SolScene* s, uint64_t seed, uint32_t* active_blocks) {
   const uint32_t first = A.rounds_done * A.round;
   if (A.n_traced + A.n_background == 0 || first >= A.max_samples) { *active_blocks = 0; return SOL_OK; }
   const uint32_t n = std::min(A.round, A.max_samples - first);
-  const SolAdaptiveLaunch L{A.order, A.n_first, A.n_traced, A.n_background, A.dscene, &A.S_uploaded, &A.dscene_valid};
+  const SolAdaptiveLaunch L{A.order.get(), A.n_first, A.n_traced, A.n_background, &A.mirror};
   int rc = sol_render_impl(s, first, n, seed, false, &L);
   if (rc) { A.open = false; return rc; }
   AdaptiveUpdate U;
-  U.acc = s->acc; U.partial = s->partial; U.state = A.state; U.active = A.active; U.counts = A.counts; U.order = A.order;
+  U.acc = s->acc; U.partial = s->partial.get(); U.state = A.state.get(); U.active = A.active.get(); U.counts = A.counts.get(); U.order = A.order.get();
   U.block_of_local = s->S.block_of_local;
   U.n_local = s->n_local_blocks; U.n_traced = A.n_traced; U.n_background = A.n_background;
   U.world = (uint32_t)s->world; U.rank = (uint32_t)s->rank; U.blocks_x = s->blocks_x; U.width = s->S.width; U.height = s->S.height;
@@ -243,35 +230,35 @@ int sol_adaptive_counts(SolScene* s, uint32_t* per_block, size_t n) {
   if (!s || !per_block) return sol_fail(SOL_EINVAL, "null argument");
   const size_t nb = (size_t)s->blocks_x * s->blocks_y;
   if (n < nb) return sol_fail(SOL_EINVAL, "sol_adaptive_counts: %zu entries < %zu blocks", n, nb);
-  if (!s->adaptive.counts || s->adaptive.counts_cap < nb) return sol_fail(SOL_EINVAL, "sol_adaptive_counts: no adaptive session has begun");
+  if (s->adaptive.counts.capacity() < nb) return sol_fail(SOL_EINVAL, "sol_adaptive_counts: no adaptive session has begun");
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipMemcpyAsync(per_block, s->adaptive.counts, nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(per_block, s->adaptive.counts.get(), nb * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return SOL_OK;
 }
 
 int sol_tonemap_rgb8_adaptive(SolScene* s, const void* image, uint8_t* out) {
   if (!s || !image || !out) return sol_fail(SOL_EINVAL, "bad argument");
-  if (!s->adaptive.counts || s->adaptive.counts_cap < (size_t)s->blocks_x * s->blocks_y) return sol_fail(SOL_EINVAL, "sol_tonemap_rgb8_adaptive: no adaptive session has begun");
+  if (s->adaptive.counts.capacity() < (size_t)s->blocks_x * s->blocks_y) return sol_fail(SOL_EINVAL, "sol_tonemap_rgb8_adaptive: no adaptive session has begun");
   HIP_TRY(hipSetDevice(s->device));
   const uint32_t n = s->S.width * s->S.height * 3;
   const uint32_t grid = std::min(4096u, (n + 255u) / 256u);
-  hipLaunchKernelGGL(sol_tonemap_counts_kernel, dim3(grid), dim3(256), 0, s->stream, (const float*)image, s->rgb8, s->S.width, s->S.height,
-                     s->blocks_x, s->adaptive.counts);
+  hipLaunchKernelGGL(sol_tonemap_counts_kernel, dim3(grid), dim3(256), 0, s->stream, (const float*)image, s->rgb8.get(), s->S.width, s->S.height,
+                     s->blocks_x, s->adaptive.counts.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, s->rgb8, n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out, s->rgb8.get(), n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return SOL_OK;
 }
 
 int sol_adaptive_rescale(SolScene* s, void* image) {
   if (!s || !image) return sol_fail(SOL_EINVAL, "bad argument");
-  if (!s->adaptive.counts || s->adaptive.counts_cap < (size_t)s->blocks_x * s->blocks_y) return sol_fail(SOL_EINVAL, "sol_adaptive_rescale: no adaptive session has begun");
+  if (s->adaptive.counts.capacity() < (size_t)s->blocks_x * s->blocks_y) return sol_fail(SOL_EINVAL, "sol_adaptive_rescale: no adaptive session has begun");
   HIP_TRY(hipSetDevice(s->device));
   const uint32_t n = s->S.width * s->S.height * 3;
   const uint32_t grid = std::min(4096u, (n + 255u) / 256u);
   hipLaunchKernelGGL(sol_adaptive_rescale_kernel, dim3(grid), dim3(256), 0, s->stream, (float*)image, s->S.width, s->S.height, s->blocks_x,
-                     s->adaptive.counts, s->adaptive.max_samples);
+                     s->adaptive.counts.get(), s->adaptive.max_samples);
   HIP_TRY(hipGetLastError());
   return SOL_OK;
 }

@@ -117,16 +117,10 @@ int sol_rebuild_order(SolScene* s) {
   const uint32_t n_first = rest.empty() ? 0u : (uint32_t)heavy.size();  // (nothing but heavy blocks: they are the chunk-major "rest")
   heavy.insert(heavy.end(), rest.begin(), rest.end());
   heavy.insert(heavy.end(), background.begin(), background.end());
-  if (n > s->order_cap) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->order_dev) hipFree(s->order_dev);
-    s->order_dev = nullptr; s->order_cap = 0;
-    HIP_TRY(hipMalloc((void**)&s->order_dev, (size_t)n * sizeof(uint32_t)));
-    s->order_cap = n;
-  }
+  if (const int rc = s->order_dev.reserve(s->stream, n)) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));  // a launch in flight may still read the old table
-  HIP_TRY(hipMemcpy(s->order_dev, heavy.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
-  s->S.block_order = s->order_dev;
+  HIP_TRY(hipMemcpy(s->order_dev.get(), heavy.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
+  s->S.block_order = s->order_dev.get();
   s->S.n_first = n_first;
   s->n_background_local = (uint32_t)background.size();
   return SOL_OK;
@@ -149,7 +143,7 @@ int sol_set_partition(SolScene* s, int rank, int world) {
   s->S.block_of_local = nullptr;
   const bool table = s->balanced && world > 1 && s->block_work.size() == nb;
   const uint32_t crc_before = s->partition_crc;
-  const bool had_sums = s->acc_own != nullptr && s->acc_floats > 0;
+  const bool had_sums = s->acc_own && s->acc_floats > 0;
   // Which block sits where: a checksum of the block -> (rank, local block) table that every rank must agree on (SolSceneInfo;
   // bench.py compares it across the ranks before the timed region). Modulo partition: a function of (blocks, world) alone.
   s->partition_table = table ? 1u : 0u;
@@ -169,37 +163,30 @@ int sol_set_partition(SolScene* s, int rank, int world) {
     // takes part in every full round
     s->n_local_blocks = (uint32_t)s->local_blocks.size();
     HIP_TRY(hipStreamSynchronize(s->stream));
-    if (!s->slot_of_block) HIP_TRY(hipMalloc((void**)&s->slot_of_block, std::max<size_t>((size_t)nb * 4, 64)));
-    HIP_TRY(hipMemcpy(s->slot_of_block, slot.data(), (size_t)nb * 4, hipMemcpyHostToDevice));
-    if (s->local_blocks.size() > s->block_of_local_cap) {
-      if (s->block_of_local_dev) hipFree(s->block_of_local_dev);
-      s->block_of_local_dev = nullptr; s->block_of_local_cap = 0;
-      HIP_TRY(hipMalloc((void**)&s->block_of_local_dev, std::max<size_t>(s->local_blocks.size() * 4, 64)));
-      s->block_of_local_cap = s->local_blocks.size();
-    }
-    if (!s->local_blocks.empty()) HIP_TRY(hipMemcpy(s->block_of_local_dev, s->local_blocks.data(), s->local_blocks.size() * 4, hipMemcpyHostToDevice));
-    s->S.block_of_local = s->block_of_local_dev;
+    int rc;
+    if ((rc = s->slot_of_block.reserve(s->stream, nb)) || (rc = s->block_of_local_dev.reserve(s->stream, s->local_blocks.size()))) return rc;
+    HIP_TRY(hipMemcpy(s->slot_of_block.get(), slot.data(), (size_t)nb * 4, hipMemcpyHostToDevice));
+    if (!s->local_blocks.empty()) HIP_TRY(hipMemcpy(s->block_of_local_dev.get(), s->local_blocks.data(), s->local_blocks.size() * 4, hipMemcpyHostToDevice));
+    s->S.block_of_local = s->block_of_local_dev.get();
   } else if (s->slot_of_block) {
     HIP_TRY(hipStreamSynchronize(s->stream));
-    hipFree(s->slot_of_block);
-    s->slot_of_block = nullptr;
+    s->slot_of_block.reset();
   }
   size_t floats = (size_t)max_blocks * 64u * 3u;
   // a different block -> slot mapping: sums already in the accumulators (and the auxiliary planes) lie in the old layout - cleared,
   // so that a later sol_read cannot mix the two (the caller re-renders; a caller-bound accumulator was refused above)
   // (the checksum is rank-independent - every rank of a job reports the same one -, so a change of rank alone is compared too)
   const bool layout_changed = crc_before != s->partition_crc || rank_before != rank || world_before != world;
-  if (had_sums && layout_changed && floats == s->acc_floats && s->acc == s->acc_own) {
-    HIP_TRY(hipMemsetAsync(s->acc_own, 0, s->acc_floats * sizeof(float), s->stream));
+  if (had_sums && layout_changed && floats == s->acc_floats && s->acc == s->acc_own.get()) {
+    HIP_TRY(hipMemsetAsync(s->acc_own.get(), 0, s->acc_floats * sizeof(float), s->stream));
     for (int k = 0; k < 2; ++k)
-      if (s->aux[k] && s->aux_floats == s->acc_floats) HIP_TRY(hipMemsetAsync(s->aux[k], 0, s->aux_floats * sizeof(float), s->stream));
+      if (s->aux[k] && s->aux_floats == s->acc_floats) HIP_TRY(hipMemsetAsync(s->aux[k].get(), 0, s->aux_floats * sizeof(float), s->stream));
     s->aux_samples = 0;
   }
-  if (floats != s->acc_floats || !s->acc_own) {
-    if (s->acc_own) { hipFree(s->acc_own); s->acc_own = nullptr; }
-    HIP_TRY(hipMalloc((void**)&s->acc_own, std::max<size_t>(floats * sizeof(float), 64)));
-    HIP_TRY(hipMemset(s->acc_own, 0, std::max<size_t>(floats * sizeof(float), 64)));
-    s->acc = s->acc_own;
+  if (floats != s->acc_floats || !s->acc_own) {  // another size, larger or smaller: new sums, all zero
+    if (const int rc = s->acc_own.reserve(s->stream, floats)) return rc;
+    HIP_TRY(hipMemset(s->acc_own.get(), 0, std::max<size_t>(floats * sizeof(float), 64)));
+    s->acc = s->acc_own.get();
     s->acc_floats = floats;
   }
   return sol_rebuild_order(s);
@@ -226,22 +213,13 @@ void sol_scene_destroy(SolScene* s) {
   hipSetDevice(s->device);
   if (s->stream) hipStreamSynchronize(s->stream);
   sol_comm_destroy(s);
-  void* ptrs[] = {s->mats, s->texs, s->texels, s->env, s->light_tri,
-                  s->acc_own, s->partial, s->image, s->rgb8, s->work, s->spill, s->counters, s->pool, s->queue, s->wf_ctr,
-                  s->bloom_a, s->bloom_b, s->bloom_w, s->aux[0], s->aux[1], s->dscene, s->order_dev, s->block_of_local_dev, s->slot_of_block, s->env_tables, s->light_tree, s->light_tables,
-                  s->aux_img[0], s->aux_img[1], s->den_buf, s->query_in, s->query_out, s->query_spill, s->proof_flags, s->dyn.light_tri2,
-                  s->rad_work, s->rad_partial, s->rad_spill, s->rad_in, s->rad_keys, s->rad_out};
-  s->tree.release();
-  s->adaptive.release();
-  if (s->wf_ctr_host) hipHostFree(s->wf_ctr_host);
-  for (void* p : ptrs)
-    if (p) hipFree(p);
   for (hipEvent_t e : s->dyn.ev)
     if (e) hipEventDestroy(e);
   if (s->ev_start) hipEventDestroy(s->ev_start);
   if (s->ev_stop) hipEventDestroy(s->ev_stop);
-  if (s->own_stream) hipStreamDestroy(s->own_stream);
-  delete s;
+  const hipStream_t own_stream = s->own_stream;
+  delete s;  // every device and pinned allocation of the handle: its DevPtr, DevBuf and PinnedPtr members
+  if (own_stream) hipStreamDestroy(own_stream);
 }
 
 int sol_scene_info(const SolScene* s, SolSceneInfo* out) {
@@ -302,7 +280,7 @@ int sol_scene_set_option(SolScene* s, int option, int64_t value) {
       if (value != 0 && value != 1) return sol_fail(SOL_EINVAL, "SOL_OPT_BALANCED_PARTITION: 0 or 1");
       if (s->comm) return sol_fail(SOL_EINVAL, "SOL_OPT_BALANCED_PARTITION: set it before sol_comm_init (every rank the same)");
       HIP_TRY(hipSetDevice(s->device));
-      if (s->acc != s->acc_own && s->world > 1) return sol_fail(SOL_EINVAL, "unbind the caller's accumulator before changing the partition");
+      if (s->acc != s->acc_own.get() && s->world > 1) return sol_fail(SOL_EINVAL, "unbind the caller's accumulator before changing the partition");
       {  // (validated first; the flag changes only together with the tables that describe the partition)
         const bool before = s->balanced;
         s->balanced = value != 0;
@@ -327,7 +305,7 @@ int sol_scene_set_partition(SolScene* s, int rank, int world) {
   s->adaptive.open = false;  // (ends an adaptive sampling session)
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(hipStreamSynchronize(s->stream));
-  if (world >= 1 && s->acc != s->acc_own) {
+  if (world >= 1 && s->acc != s->acc_own.get()) {
     const uint32_t nb = s->blocks_x * s->blocks_y;
     const size_t floats = (size_t)((nb + (uint32_t)world - 1u) / (uint32_t)world) * 64u * 3u;
     if (floats != s->acc_floats)
@@ -341,7 +319,7 @@ void* sol_accum_ptr(SolScene* s) { return s ? s->acc : nullptr; }
 
 int sol_scene_bind_accum(SolScene* s, void* p, size_t n_floats) {
   if (!s) return sol_fail(SOL_EINVAL, "null scene");
-  if (!p) { s->acc = s->acc_own; return SOL_OK; }
+  if (!p) { s->acc = s->acc_own.get(); return SOL_OK; }
   if (n_floats < s->acc_floats) return sol_fail(SOL_EINVAL, "bound accumulator too small: %zu < %zu floats", n_floats, s->acc_floats);
   s->acc = (float*)p;
   return SOL_OK;
@@ -373,9 +351,9 @@ int sol_sync(SolScene* s) {
 int sol_read(SolScene* s, float* rgb_sum) {
   if (!s || !rgb_sum) return sol_fail(SOL_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_unpermute(s->acc, s->image, s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
-                               s->acc_floats, s->slot_of_block, s->stream));
-  HIP_TRY(hipMemcpyAsync(rgb_sum, s->image, (size_t)s->S.width * s->S.height * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(sol_launch_unpermute(s->acc, s->image.get(), s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
+                               s->acc_floats, s->slot_of_block.get(), s->stream));
+  HIP_TRY(hipMemcpyAsync(rgb_sum, s->image.get(), (size_t)s->S.width * s->S.height * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return SOL_OK;
 }
@@ -411,7 +389,7 @@ int sol_stats(const SolScene* s, SolStats* out) {
 int sol_read_image(SolScene* s, float* rgb_sum) {
   if (!s || !rgb_sum) return sol_fail(SOL_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipMemcpyAsync(rgb_sum, s->image, (size_t)s->S.width * s->S.height * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(rgb_sum, s->image.get(), (size_t)s->S.width * s->S.height * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return SOL_OK;
 }
@@ -423,19 +401,6 @@ uint32_t sol_max_samples_per_call(const SolScene* s) {
 }
 
 }  // extern "C"
-
-// s->dscene = s->S: the kernels that read the scene through a pointer (the product render kernel, the ray queries). Uploaded only when the record
-// differs from the copy on the device (rare: scene creation, an auxiliary render in between); launches already queued may still read the old copy.
-int sol_scene_to_device(SolScene* s) {
-  if (!s->dscene) HIP_TRY(hipMalloc((void**)&s->dscene, sizeof(DevScene)));
-  if (!s->dscene_valid || std::memcmp(&s->S, &s->S_uploaded, sizeof(DevScene)) != 0) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    HIP_TRY(hipMemcpy(s->dscene, &s->S, sizeof(DevScene), hipMemcpyHostToDevice));
-    std::memcpy(&s->S_uploaded, &s->S, sizeof(DevScene));
-    s->dscene_valid = true;
-  }
-  return SOL_OK;
-}
 
 // ---- ray queries (include/solstrale_hip.h; kernels: sol_query.hip) ----
 namespace {
@@ -460,26 +425,23 @@ int query_check(const SolScene* s, const char* fn, int mode, const void* rays, s
   *go = true;
   return SOL_OK;
 }
+// The pixel rectangle of sol_camera_rays / sol_camera_ray_keys (`fn`): not empty, inside the frame, at most 2^31 pixels.
+int camera_rect_check(const SolScene* s, const char* fn, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
+  if (x0 >= x1 || y0 >= y1 || x1 > s->S.width || y1 > s->S.height)
+    return sol_fail(SOL_EINVAL, "%s: the rectangle [%u, %u) x [%u, %u) is empty or leaves the %u x %u frame", fn, x0, x1, y0, y1, s->S.width, s->S.height);
+  if ((uint64_t)(x1 - x0) * (y1 - y0) > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: more than 2^31 rays", fn);
+  return SOL_OK;
+}
 // One launch over n <= 2^31 rays in device memory, on the scene's stream.
 int query_launch(SolScene* s, int mode, const void* rays_dev, size_t n, void* out_dev) {
   int rc;
   if ((rc = sol_scene_to_device(s))) return rc;
   const bool any = mode == SOL_QUERY_OCCLUDED;
-  int bpc = sol_query_blocks_per_cu(any, s->strict_triangles);
-  if (s->max_bpc > 0) bpc = std::max(1, std::min(bpc, s->max_bpc));
-  const uint32_t need_blocks = (uint32_t)((n + SOL_WG - 1) / SOL_WG);
-  const uint32_t grid = std::max(1u, std::min((uint32_t)(s->n_cu * bpc), need_blocks));
   // the spill tail of THIS grid (the render launch's area is sized for another)
   const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
-  const size_t spill_words = may_spill ? (size_t)grid * SOL_WG * (s->tree.depth - SOL_LDS_STACK) : 16;
-  if (spill_words > s->query_spill_words) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->query_spill) hipFree(s->query_spill);
-    s->query_spill = nullptr; s->query_spill_words = 0;
-    HIP_TRY(hipMalloc((void**)&s->query_spill, spill_words * sizeof(uint32_t)));
-    s->query_spill_words = spill_words;
-  }
-  HIP_TRY(sol_launch_query(s->dscene, any, may_spill, s->strict_triangles, rays_dev, (uint32_t)n, out_dev, s->query_spill, grid, s->stream));
+  uint32_t grid;
+  if ((rc = sol_launch_plan(s, sol_query_blocks_per_cu(any, s->strict_triangles), n, SOL_LDS_STACK, s->tree.depth, s->query_spill, &grid))) return rc;
+  HIP_TRY(sol_launch_query(s->mirror.dev.get(), any, may_spill, s->strict_triangles, rays_dev, (uint32_t)n, out_dev, s->query_spill.get(), grid, s->stream));
   return SOL_OK;
 }
 }  // namespace
@@ -501,20 +463,12 @@ int sol_query(SolScene* s, int mode, const SolRay* rays, size_t n, void* out) {
   HIP_TRY(hipSetDevice(s->device));
   const size_t out_bytes = mode == SOL_QUERY_OCCLUDED ? sizeof(uint32_t) : sizeof(SolRayHit);
   const size_t cap = std::min(n, QUERY_STAGE_RAYS);
-  if (cap > s->query_cap) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->query_in) hipFree(s->query_in);
-    if (s->query_out) hipFree(s->query_out);
-    s->query_in = s->query_out = nullptr; s->query_cap = 0;
-    HIP_TRY(hipMalloc(&s->query_in, cap * sizeof(SolRay)));
-    HIP_TRY(hipMalloc(&s->query_out, cap * sizeof(SolRayHit)));
-    s->query_cap = cap;
-  }
+  if ((rc = s->query_in.reserve(s->stream, cap)) || (rc = s->query_out.reserve(s->stream, cap))) return rc;
   for (size_t at = 0; at < n; at += cap) {  // (answers are per ray: the split changes nothing)
     const size_t k = std::min(cap, n - at);
-    HIP_TRY(hipMemcpyAsync(s->query_in, rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-    if ((rc = query_launch(s, mode, s->query_in, k, s->query_out))) return rc;
-    HIP_TRY(hipMemcpyAsync((char*)out + at * out_bytes, s->query_out, k * out_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->query_in.get(), rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
+    if ((rc = query_launch(s, mode, s->query_in.get(), k, s->query_out.get()))) return rc;
+    HIP_TRY(hipMemcpyAsync((char*)out + at * out_bytes, s->query_out.get(), k * out_bytes, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
@@ -524,12 +478,10 @@ int sol_camera_rays(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t
   int rc;
   if ((rc = query_device_check())) return rc;
   if (!s || !rays_dev) return sol_fail(SOL_EINVAL, "sol_camera_rays: null %s", !s ? "scene" : "ray pointer");
-  if (x0 >= x1 || y0 >= y1 || x1 > s->S.width || y1 > s->S.height)
-    return sol_fail(SOL_EINVAL, "sol_camera_rays: the rectangle [%u, %u) x [%u, %u) is empty or leaves the %u x %u frame", x0, x1, y0, y1, s->S.width, s->S.height);
-  if ((uint64_t)(x1 - x0) * (y1 - y0) > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "sol_camera_rays: more than 2^31 rays");
+  if ((rc = camera_rect_check(s, "sol_camera_rays", x0, y0, x1, y1))) return rc;
   HIP_TRY(hipSetDevice(s->device));
   if ((rc = sol_scene_to_device(s))) return rc;
-  HIP_TRY(sol_launch_camera_rays(s->dscene, x0, y0, x1 - x0, y1 - y0, sample, seed, rays_dev, s->stream));
+  HIP_TRY(sol_launch_camera_rays(s->mirror.dev.get(), x0, y0, x1 - x0, y1 - y0, sample, seed, rays_dev, s->stream));
   return SOL_OK;
 }
 
@@ -563,17 +515,6 @@ int radiance_check(const SolScene* s, const char* fn, const void* rays, size_t n
   return SOL_OK;
 }
 
-template <typename T>
-int radiance_grow(SolScene* s, T** buf, size_t* have, size_t need, size_t elem) {
-  if (need <= *have) return SOL_OK;
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  if (*buf) hipFree(*buf);
-  *buf = nullptr; *have = 0;
-  HIP_TRY(hipMalloc((void**)buf, need * elem));
-  *have = need;
-  return SOL_OK;
-}
-
 // n <= 2^31 rays (and keys, or null) in device memory, on the scene's stream. key_base: the key of ray 0 of THIS batch when keys is null.
 int radiance_launch(SolScene* s, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
   int rc;
@@ -581,10 +522,9 @@ int radiance_launch(SolScene* s, const void* rays_dev, const void* keys_dev, siz
   // the estimator a render would run now (sol_render_impl): the ENV / LT builds under the path-tracing shader only
   const bool env = s->env_is && s->S.shader == SOL_SHADER_PATH_TRACING;
   const bool lt = s->light_mode != 0u && s->S.shader == SOL_SHADER_PATH_TRACING && s->S.n_lights > 1u;
-  int bpc = sol_radiance_blocks_per_cu(s->strict_triangles, env, lt);
-  if (s->max_bpc > 0) bpc = std::max(1, std::min(bpc, s->max_bpc));
+  const int bpc = sol_radiance_blocks_per_cu(s->strict_triangles, env, lt);
   const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
-  if (!s->rad_work) HIP_TRY(hipMalloc((void**)&s->rad_work, 64));
+  if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
   const uint32_t total_chunks = (uint32_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
   // One chunk: one launch writes the answers. More: the chunk sums go through the partial buffer, at most SolScene::rad_partial_max_rows of them per
   // launch - the call is split over rays (answers are per ray) and, for sample ranges beyond 16 * 2^18, over windows of chunks (the resolve
@@ -606,21 +546,20 @@ int radiance_launch(SolScene* s, const void* rays_dev, const void* keys_dev, siz
     const char* rays_at = (const char*)rays_dev + at * sizeof(SolRay);
     const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
     char* out_at = (char*)out_dev + at * sizeof(SolRadiance);
-    if (!P.direct && (rc = radiance_grow(s, &s->rad_partial, &s->rad_partial_rows, (size_t)P.n_groups * 64 * win_chunks, sizeof(SolRadiance)))) return rc;
+    if (!P.direct && (rc = s->rad_partial.reserve(s->stream, (size_t)P.n_groups * 64 * win_chunks))) return rc;
     for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
       P.n_chunks = (uint32_t)std::min<size_t>(win_chunks, total_chunks - c0);
       P.first_sample = cfg.first_sample + (uint32_t)c0 * SOL_CHUNK;
       const uint64_t items = (uint64_t)P.n_chunks * P.n_groups * 64u;  // (<= 2^31: far below the headroom of the 32-bit work counter, SOL_MAX_ITEMS)
       P.n_items = (uint32_t)items;
       // the grid and the spill tail of THIS launch (the render launch's area is sized for another)
-      const uint32_t need_blocks = (uint32_t)((items + SOL_WG - 1) / SOL_WG);
-      const uint32_t grid = std::max(1u, std::min((uint32_t)(s->n_cu * bpc), need_blocks));
+      uint32_t grid;
+      if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
       P.total_threads = grid * SOL_WG;
-      const size_t spill_words = may_spill ? (size_t)grid * SOL_WG * (s->tree.depth - SOL_LDS_STACK) : 16;
-      if ((rc = radiance_grow(s, &s->rad_spill, &s->rad_spill_words, spill_words, sizeof(uint32_t)))) return rc;
-      HIP_TRY(hipMemsetAsync(s->rad_work, 0, sizeof(uint32_t), s->stream));
-      HIP_TRY(sol_launch_radiance(s->dscene, P, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial, s->rad_work, s->rad_spill, grid, s->stream));
-      if (!P.direct) HIP_TRY(sol_launch_radiance_resolve(P, rays_at, s->rad_partial, out_at, cfg.samples, c0 != 0, s->stream));
+      HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
+      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial.get(), s->rad_work.get(),
+                                  s->rad_spill.get(), grid, s->stream));
+      if (!P.direct) HIP_TRY(sol_launch_radiance_resolve(P, rays_at, s->rad_partial.get(), out_at, cfg.samples, c0 != 0, s->stream));
     }
   }
   return SOL_OK;
@@ -643,21 +582,13 @@ int sol_radiance(SolScene* s, const SolRay* rays, const SolRayKey* keys, size_t 
   if ((rc = radiance_check(s, "sol_radiance", rays, n, cfg, out, &go)) || !go || (rc = query_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
-  if (cap > s->rad_cap) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    for (void** p : {&s->rad_in, &s->rad_keys, &s->rad_out}) { if (*p) hipFree(*p); *p = nullptr; }
-    s->rad_cap = 0;
-    HIP_TRY(hipMalloc(&s->rad_in, cap * sizeof(SolRay)));
-    HIP_TRY(hipMalloc(&s->rad_keys, cap * sizeof(SolRayKey)));
-    HIP_TRY(hipMalloc(&s->rad_out, cap * sizeof(SolRadiance)));
-    s->rad_cap = cap;
-  }
+  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap))) return rc;
   for (size_t at = 0; at < n; at += cap) {  // (answers are per ray: the split changes nothing)
     const size_t k = std::min(cap, n - at);
-    HIP_TRY(hipMemcpyAsync(s->rad_in, rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys, keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
-    if ((rc = radiance_launch(s, s->rad_in, keys ? s->rad_keys : nullptr, k, *cfg, cfg->key_base + (uint32_t)at, s->rad_out))) return rc;
-    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out, k * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
+    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
+    if ((rc = radiance_launch(s, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, *cfg, cfg->key_base + (uint32_t)at, s->rad_out.get()))) return rc;
+    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
@@ -667,12 +598,10 @@ int sol_camera_ray_keys(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint
   int rc;
   if (!s || !keys_dev) return sol_fail(SOL_EINVAL, "sol_camera_ray_keys: null %s", !s ? "scene" : "key pointer");
   if ((rc = query_device_check())) return rc;
-  if (x0 >= x1 || y0 >= y1 || x1 > s->S.width || y1 > s->S.height)
-    return sol_fail(SOL_EINVAL, "sol_camera_ray_keys: the rectangle [%u, %u) x [%u, %u) is empty or leaves the %u x %u frame", x0, x1, y0, y1, s->S.width, s->S.height);
-  if ((uint64_t)(x1 - x0) * (y1 - y0) > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "sol_camera_ray_keys: more than 2^31 rays");
+  if ((rc = camera_rect_check(s, "sol_camera_ray_keys", x0, y0, x1, y1))) return rc;
   HIP_TRY(hipSetDevice(s->device));
   if ((rc = sol_scene_to_device(s))) return rc;
-  HIP_TRY(sol_launch_camera_ray_keys(s->dscene, x0, y0, x1 - x0, y1 - y0, sample, seed, keys_dev, s->stream));
+  HIP_TRY(sol_launch_camera_ray_keys(s->mirror.dev.get(), x0, y0, x1 - x0, y1 - y0, sample, seed, keys_dev, s->stream));
   return SOL_OK;
 }
 

@@ -53,9 +53,9 @@ int sol_rederive_view_tables(SolScene* s, uint32_t flags, const char* who) {
   const bool prove = !(flags & SOL_CAMERA_NO_BACKGROUND_PROOF) && s->background_proof && s->tree.n_wide > 0 &&
                      sol_proof_camera(s->S.cam, s->S.width, s->S.height, 64.0 * (double)s->box_pad, pc);
   if (prove) {
-    if (!s->proof_flags) HIP_TRY(hipMalloc((void**)&s->proof_flags, std::max<size_t>(nb, 64)));
+    if ((rc = s->proof_flags.reserve(s->stream, nb))) return rc;
     if (s->timing) HIP_TRY(hipEventRecord(s->ev_start, s->stream));
-    HIP_TRY(sol_launch_background_proof(s->S.wides, s->tree.n_wide, s->S.wide_emin, pc, s->proof_flags, s->stream));
+    HIP_TRY(sol_launch_background_proof(s->S.wides, s->tree.n_wide, s->S.wide_emin, pc, s->proof_flags.get(), s->stream));
     if (s->timing) { HIP_TRY(hipEventRecord(s->ev_stop, s->stream)); s->timed_launches++; s->last_grid = (nb + 63u) / 64u; }
   }
   // the cost probe, where creation ran one (it traces every block: the table is still empty)
@@ -66,7 +66,7 @@ int sol_rederive_view_tables(SolScene* s, uint32_t flags, const char* who) {
   }
   if (prove) {
     std::vector<uint8_t> flags_host(nb);
-    HIP_TRY(hipMemcpyAsync(flags_host.data(), s->proof_flags, nb, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(flags_host.data(), s->proof_flags.get(), nb, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     if ((rc = adopt_flags(s, flags_host, who))) { drop_camera_tables(s); return rc; }
   }

@@ -92,7 +92,7 @@ int sol_comm_destroy(SolScene* s) {
     rccl().CommDestroy((ncclComm_t)s->comm);
     s->comm = nullptr;
   }
-  if (s->gathered) { hipFree(s->gathered); s->gathered = nullptr; s->gathered_floats = 0; }
+  s->gathered.reset();
   return SOL_OK;
 }
 
@@ -119,30 +119,24 @@ int sol_gather(SolScene* s, void* image_dev) {
   if (!s) return sol_fail(SOL_EINVAL, "null scene");
   HIP_TRY(hipSetDevice(s->device));
   if (s->world > 1 && !s->comm) return sol_fail(SOL_EINVAL, "the scene is partitioned %d-way but has no communicator: call sol_comm_init", s->world);
-  float* image = image_dev ? (float*)image_dev : s->image;
+  float* image = image_dev ? (float*)image_dev : s->image.get();
   if (s->world == 1) {
-    HIP_TRY(sol_launch_unpermute(s->acc, image, s->S.width, s->S.height, s->blocks_x, 1u, 0u, s->acc_floats, s->slot_of_block, s->stream));
+    HIP_TRY(sol_launch_unpermute(s->acc, image, s->S.width, s->S.height, s->blocks_x, 1u, 0u, s->acc_floats, s->slot_of_block.get(), s->stream));
     return SOL_OK;
   }
   Rccl& R = rccl();
   ncclComm_t comm = (ncclComm_t)s->comm;
   const size_t n = s->acc_floats;
   if (s->rank == 0) {
-    if (s->gathered_floats != n * (size_t)s->world) {
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      if (s->gathered) hipFree(s->gathered);
-      s->gathered = nullptr; s->gathered_floats = 0;
-      HIP_TRY(hipMalloc((void**)&s->gathered, n * (size_t)s->world * sizeof(float)));
-      s->gathered_floats = n * (size_t)s->world;
-    }
-    HIP_TRY(hipMemcpyAsync(s->gathered, s->acc, n * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
+    if (const int rc = s->gathered.reserve(s->stream, n * (size_t)s->world)) return rc;
+    HIP_TRY(hipMemcpyAsync(s->gathered.get(), s->acc, n * sizeof(float), hipMemcpyDeviceToDevice, s->stream));
     RCCL_TRY(R.GroupStart());
     for (int r = 1; r < s->world; ++r) {
-      ncclResult_t e = R.Recv(s->gathered + (size_t)r * n, n, ncclFloat, r, comm, s->stream);
+      ncclResult_t e = R.Recv(s->gathered.get() + (size_t)r * n, n, ncclFloat, r, comm, s->stream);
       if (e != ncclSuccess) { R.GroupEnd(); return sol_fail(SOL_EDEVICE, "ncclRecv from rank %d: %s", r, R.GetErrorString(e)); }
     }
     RCCL_TRY(R.GroupEnd());
-    HIP_TRY(sol_launch_unpermute(s->gathered, image, s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, 0xFFFFFFFFu, n, s->slot_of_block, s->stream));
+    HIP_TRY(sol_launch_unpermute(s->gathered.get(), image, s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, 0xFFFFFFFFu, n, s->slot_of_block.get(), s->stream));
   } else {
     RCCL_TRY(R.Send(s->acc, n, ncclFloat, 0, comm, s->stream));
   }
@@ -172,21 +166,15 @@ int sol_gather_local(SolScene* const* scenes, int n, void** image_dev) {
   }
   HIP_TRY(hipSetDevice(root->device));
   if (n == 1) {
-    HIP_TRY(sol_launch_unpermute(root->acc, root->image, root->S.width, root->S.height, root->blocks_x, 1u, 0u, floats, root->slot_of_block, root->stream));
-    *image_dev = root->image;
+    HIP_TRY(sol_launch_unpermute(root->acc, root->image.get(), root->S.width, root->S.height, root->blocks_x, 1u, 0u, floats, root->slot_of_block.get(), root->stream));
+    *image_dev = root->image.get();
     return SOL_OK;
   }
-  if (root->gathered_floats != floats * (size_t)n) {
-    HIP_TRY(hipStreamSynchronize(root->stream));
-    if (root->gathered) hipFree(root->gathered);
-    root->gathered = nullptr; root->gathered_floats = 0;
-    HIP_TRY(hipMalloc((void**)&root->gathered, floats * (size_t)n * sizeof(float)));
-    root->gathered_floats = floats * (size_t)n;
-  }
+  if (const int rc = root->gathered.reserve(root->stream, floats * (size_t)n)) return rc;
   for (int i = 0; i < n; ++i)
-    HIP_TRY(hipMemcpyPeerAsync(root->gathered + (size_t)i * floats, root->device, scenes[i]->acc, scenes[i]->device, floats * sizeof(float), root->stream));
-  HIP_TRY(sol_launch_unpermute(root->gathered, root->image, root->S.width, root->S.height, root->blocks_x, (uint32_t)n, 0xFFFFFFFFu, floats, root->slot_of_block, root->stream));
-  *image_dev = root->image;
+    HIP_TRY(hipMemcpyPeerAsync(root->gathered.get() + (size_t)i * floats, root->device, scenes[i]->acc, scenes[i]->device, floats * sizeof(float), root->stream));
+  HIP_TRY(sol_launch_unpermute(root->gathered.get(), root->image.get(), root->S.width, root->S.height, root->blocks_x, (uint32_t)n, 0xFFFFFFFFu, floats, root->slot_of_block.get(), root->stream));
+  *image_dev = root->image.get();
   return SOL_OK;
 }
 
@@ -198,8 +186,9 @@ int sol_comm_self_check(SolScene* s) {
   HIP_TRY(hipSetDevice(s->device));
   Rccl& R = rccl();
   const size_t n = s->acc_floats;
-  float* tmp = nullptr;
-  HIP_TRY(hipMalloc((void**)&tmp, n * sizeof(float)));
+  DevPtr<float> tmp_own;
+  HIP_TRY(sol_dev_alloc(tmp_own, n));
+  float* const tmp = tmp_own.get();
   hipError_t e = hipMemsetAsync(tmp, 0xFF, n * sizeof(float), s->stream);
   ncclResult_t r = ncclSuccess;
   if (e == hipSuccess) {
@@ -213,7 +202,6 @@ int sol_comm_self_check(SolScene* s) {
   if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(a.data(), s->acc, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess && r == ncclSuccess) e = hipMemcpyAsync(b.data(), tmp, n * sizeof(float), hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  hipFree(tmp);
   if (r != ncclSuccess) return sol_fail(SOL_EDEVICE, "RCCL self transfer: %s", R.GetErrorString(r));
   if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "self check: %s", hipGetErrorString(e));
   if (std::memcmp(a.data(), b.data(), n * sizeof(float)) != 0) return sol_fail(SOL_EDEVICE, "RCCL self transfer returned different bytes");

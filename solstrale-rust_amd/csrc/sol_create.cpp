@@ -878,14 +878,14 @@ static void adopt_build_info(SolScene* s, const DeviceSplitInfo& si) {  // what 
 static int upload_scene(const CreateCtx& c, const World& w, const HostRecords& r, SolScene* s, TreeCand& first) {
   const SolSceneDesc* d = &c.d;
   int rc;
-  if ((rc = upload_tree(*d, w, r, first)) || (rc = sol_upload(r.mats, &s->mats)) || (rc = sol_upload(r.texs, &s->texs))) return rc;
+  if ((rc = upload_tree(*d, w, r, first)) || (rc = sol_upload(r.mats, s->mats)) || (rc = sol_upload(r.texs, s->texs))) return rc;
   const std::vector<uint8_t> texels(d->texels, d->texels + d->n_texel_bytes);
-  if ((rc = sol_upload(texels, &s->texels))) return rc;
-  HIP_TRY(hipMalloc((void**)&s->work, 64));
-  HIP_TRY(hipMalloc((void**)&s->counters, sizeof(DevCounters)));
-  HIP_TRY(hipMemset(s->counters, 0, sizeof(DevCounters)));
-  HIP_TRY(hipMalloc((void**)&s->image, (size_t)d->width * d->height * 3 * sizeof(float)));
-  HIP_TRY(hipMalloc((void**)&s->rgb8, (size_t)d->width * d->height * 3));
+  if ((rc = sol_upload(texels, s->texels))) return rc;
+  HIP_TRY(sol_dev_alloc(s->work, 1));
+  HIP_TRY(sol_dev_alloc(s->counters, 1));
+  HIP_TRY(hipMemset(s->counters.get(), 0, sizeof(DevCounters)));
+  HIP_TRY(sol_dev_alloc(s->image, (size_t)d->width * d->height * 3));
+  HIP_TRY(sol_dev_alloc(s->rgb8, (size_t)d->width * d->height * 3));
   return SOL_OK;
 }
 // ... and the scene's constants: DevScene, the launch parameters the overrides set, the whole-image partition
@@ -895,7 +895,7 @@ static int set_scene_constants(const CreateCtx& c, const World& w, SolScene* s, 
   const Box& root_box = w.root_box;
   int rc;
   DevScene& S = s->S;
-  S.mats = s->mats; S.texs = s->texs; S.texels = s->texels;
+  S.mats = s->mats.get(); S.texs = s->texs.get(); S.texels = s->texels.get();
   S.n_lights = d->n_lights;
   s->tree = std::move(first.dev);  // the scene takes ownership
   bind_tree(s);
@@ -904,15 +904,15 @@ static int set_scene_constants(const CreateCtx& c, const World& w, SolScene* s, 
   S.rzmin = root_box.v[4]; S.rzmax = root_box.v[5];
   S.width = d->width; S.height = d->height; S.shader = d->shader_kind; S.max_depth = d->max_depth;
   S.sphere_slack = w.box_pad * 0.5f;
-  if ((rc = sol_upload(light_triangle_frames(*d), &s->light_tri))) return rc;
-  S.light_tri = s->light_tri;
+  if ((rc = sol_upload(light_triangle_frames(*d), s->light_tri))) return rc;
+  S.light_tri = s->light_tri.get();
   S.tri_delta = w.needles ? w.box_pad * 0.8f : 0.0f;
   s->strict_triangles = S.tri_delta > 0.0f;
   S.env = nullptr; S.env_w = S.env_h = 0; S.env_scale = 1.0f;
   if (c.has_env) {
     std::vector<float> env(d->env_texels, d->env_texels + (size_t)d->env_width * d->env_height * 3);
-    if ((rc = sol_upload(env, &s->env))) return rc;
-    S.env = s->env; S.env_w = d->env_width; S.env_h = d->env_height; S.env_scale = (float)d->env_scale;
+    if ((rc = sol_upload(env, s->env))) return rc;
+    S.env = s->env.get(); S.env_w = d->env_width; S.env_h = d->env_height; S.env_scale = (float)d->env_scale;
   }
   s->env_refusal = sol_env_refusal(d);  // (environment importance sampling, sol_envmap.hip: stops at the first cell of positive weight)
   s->light_w = sol_light_weights_of(d);  // (light sampling mode 2, sol_lights.hip: O(L), decided at creation like env_refusal)
@@ -987,11 +987,8 @@ static int probe_candidates(const CreateCtx& c, const World& w, const HostRecord
 // level (the layout is on the host here: no kernel), which records the world tree reaches (box_pad_for's S reads the ROOT's box, the union of
 // exactly those), the camera's share of S - and the staging copies both kernels write.
 template <typename T> static int dev_alloc(DevPtr<T>& p, size_t count) {
-  T* q = nullptr;
-  const size_t bytes = std::max<size_t>(count * sizeof(T), 64);
-  HIP_TRY(hipMalloc((void**)&q, bytes));
-  p.reset(q);
-  HIP_TRY(hipMemset(q, 0, bytes));
+  HIP_TRY(sol_dev_alloc(p, count));
+  HIP_TRY(hipMemset(p.get(), 0, std::max<size_t>(count * sizeof(T), 64)));
   return SOL_OK;
 }
 // SolCreateOptions.dynamic_primitives: what sol_scene_set_primitives needs on top - per sphere and quad what a move does not change
@@ -1102,7 +1099,7 @@ static int keep_dynamic(const CreateCtx& c, const HostRecords& r, SolScene* s, c
   y.light_lum = sol_light_luminances_of(&d);
   int rc;
   if ((rc = sol_upload(st, y.tri_static)) || (rc = sol_upload(rec_tri, y.rec_tri)) || (rc = sol_upload(sbox, y.sphere_box)) || (rc = sol_upload(qbox, y.quad_box)) ||
-      (rc = sol_upload(level_nodes, y.level_nodes)) || (rc = sol_upload(y.light_src_host, y.light_src)) || (rc = sol_upload(light_triangle_frames(d), &y.light_tri2)) ||
+      (rc = sol_upload(level_nodes, y.level_nodes)) || (rc = sol_upload(y.light_src_host, y.light_src)) || (rc = sol_upload(light_triangle_frames(d), y.light_tri2)) ||
       (rc = dev_alloc(y.tri_box, (size_t)y.n_recs * 8)) || (rc = dev_alloc(y.node_box, L.nodes.size() * 6)) || (rc = dev_alloc(y.wides2, L.nodes.size())) ||
       (rc = dev_alloc(y.tris2, y.n_recs)) || (rc = dev_alloc(y.shade2, y.n_recs)) || (rc = dev_alloc(y.verts, (size_t)y.n_tris * 9)) ||
       (rc = dev_alloc(y.out, 4 + 2 * (size_t)d.n_lights)))
@@ -1137,28 +1134,26 @@ struct BackgroundProof {
 int sol_cost_probe_render(SolScene* s, SolCostProbe& p) {
   DevScene& S = s->S;
   const uint32_t nb = s->blocks_x * s->blocks_y;
-  HIP_TRY(hipMalloc((void**)&p.cost_dev, (size_t)nb * sizeof(uint32_t)));
-  hipError_t e = hipMemset(p.cost_dev, 0, (size_t)nb * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void**)&p.work_dev, (size_t)nb * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemset(p.work_dev, 0, (size_t)nb * sizeof(uint32_t));
-  S.block_cost = p.cost_dev;
-  S.block_work = p.work_dev;
+  HIP_TRY(sol_dev_alloc(p.cost_dev, nb));
+  hipError_t e = hipMemset(p.cost_dev.get(), 0, (size_t)nb * sizeof(uint32_t));
+  if (e == hipSuccess) e = sol_dev_alloc(p.work_dev, nb);
+  if (e == hipSuccess) e = hipMemset(p.work_dev.get(), 0, (size_t)nb * sizeof(uint32_t));
+  S.block_cost = p.cost_dev.get();
+  S.block_work = p.work_dev.get();
   return e == hipSuccess ? sol_render_impl(s, 0, 4, 0xC057ull, true) : SOL_EDEVICE;
 }
 int sol_cost_probe_adopt(SolScene* s, SolCostProbe& p, int rc, bool verbose) {
   DevScene& S = s->S;
   const uint32_t nb = s->blocks_x * s->blocks_y;
-  uint32_t* const cost_dev = p.cost_dev; uint32_t* const work_dev = p.work_dev;
-  p = SolCostProbe{};
+  const SolCostProbe tables = std::move(p);  // (freed on every way out; p is empty again)
+  uint32_t* const cost_dev = tables.cost_dev.get(); uint32_t* const work_dev = tables.work_dev.get();
   if (!cost_dev) return rc;  // (the render half failed before it had a table)
   S.block_cost = nullptr;
   S.block_work = nullptr;
   s->block_cost.assign(nb, 0u);
   s->block_work.assign(nb, 0u);
   if (rc == SOL_OK && hipMemcpy(s->block_work.data(), work_dev, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = SOL_EDEVICE;
-  if (work_dev) hipFree(work_dev);
   if (rc == SOL_OK && hipMemcpy(s->block_cost.data(), cost_dev, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = SOL_EDEVICE;
-  hipFree(cost_dev);
   if (rc != SOL_OK) return rc == SOL_EDEVICE ? sol_fail(SOL_EDEVICE, "cost probe failed") : rc;
   // The fine tail takes an item fetch per SAMPLE (a dependent load, three integer divisions: ~2 us): worth it where a sample
   // is long. MI355X, 1080p x 64 spp, ms with 0 / 1 / 2 whole items per lane in the tail: C3 (38 node visits per sample) 76.5 /

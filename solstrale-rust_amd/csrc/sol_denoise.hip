@@ -136,18 +136,12 @@ static int denoise_impl(SolScene* s, const void* image, uint32_t n, const void* 
   const uint32_t W = s->S.width, H = s->S.height;
   const size_t npix = (size_t)W * H;
   // scratch: ping-pong buffers, guide, and (rgb8) W*H*3 floats of result - one float4 per pixel is room enough for it
-  if (s->den_pixels < npix || !s->den_buf) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->den_buf) hipFree(s->den_buf);
-    s->den_buf = nullptr; s->den_pixels = 0;
-    HIP_TRY(hipMalloc((void**)&s->den_buf, std::max<size_t>(npix * 4 * sizeof(float4), 64)));
-    s->den_pixels = npix;
-  }
-  float* dst = out ? out : (float*)(s->den_buf + 3 * npix);
-  HIP_TRY(sol_launch_denoise((const float*)image, (const float*)albedo, (const float*)normal, dst, s->den_buf, W, H, n, m, c, s->stream));
+  if (const int rc = s->den_buf.reserve(s->stream, npix * 4)) return rc;
+  float* dst = out ? out : (float*)(s->den_buf.get() + 3 * npix);
+  HIP_TRY(sol_launch_denoise((const float*)image, (const float*)albedo, (const float*)normal, dst, s->den_buf.get(), W, H, n, m, c, s->stream));
   if (rgb8_host) {
-    HIP_TRY(sol_launch_tonemap(dst, s->rgb8, (uint32_t)(npix * 3), n, s->stream));
-    HIP_TRY(hipMemcpyAsync(rgb8_host, s->rgb8, npix * 3, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(sol_launch_tonemap(dst, s->rgb8.get(), (uint32_t)(npix * 3), n, s->stream));
+    HIP_TRY(hipMemcpyAsync(rgb8_host, s->rgb8.get(), npix * 3, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
@@ -175,10 +169,10 @@ int sol_resolve_aux(SolScene* s, void** albedo_dev, void** normal_dev, uint32_t*
   const size_t floats = (size_t)s->S.width * s->S.height * 3;
   void** outs[2] = {albedo_dev, normal_dev};
   for (int k = 0; k < 2; ++k) {
-    if (!s->aux_img[k]) HIP_TRY(hipMalloc((void**)&s->aux_img[k], std::max<size_t>(floats * sizeof(float), 64)));
-    HIP_TRY(sol_launch_unpermute(s->aux[k], s->aux_img[k], s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
-                                 s->acc_floats, s->slot_of_block, s->stream));
-    if (outs[k]) *outs[k] = s->aux_img[k];
+    if (const int rc = s->aux_img[k].reserve(s->stream, floats)) return rc;
+    HIP_TRY(sol_launch_unpermute(s->aux[k].get(), s->aux_img[k].get(), s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
+                                 s->acc_floats, s->slot_of_block.get(), s->stream));
+    if (outs[k]) *outs[k] = s->aux_img[k].get();
   }
   if (aux_samples) *aux_samples = s->aux_samples;
   return SOL_OK;

@@ -102,8 +102,9 @@ static int env_config_check(const SolEnvSampling* c, const char* fn) {
 static int env_build(SolScene* s) {
   const uint32_t cw = std::max(s->S.env_w - 1u, 1u), ch = std::max(s->S.env_h - 1u, 1u);
   const size_t cells = (size_t)cw * ch;
-  float* t = nullptr;
-  if (hipMalloc((void**)&t, (2 * (size_t)ch + cells + 1) * sizeof(float)) != hipSuccess) return sol_fail(SOL_ENOMEM, "sol_env_sampling: no memory for the tables");
+  DevPtr<float> tables;
+  if (sol_dev_alloc(tables, 2 * (size_t)ch + cells + 1) != hipSuccess) return sol_fail(SOL_ENOMEM, "sol_env_sampling: no memory for the tables");
+  float* const t = tables.get();
   float *marg = t, *cond = t + ch, *rowtot = cond + cells, *total = rowtot + ch;
   float tot = 0.0f;
   hipLaunchKernelGGL(sol_env_weights_kernel, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, s->stream, s->S.env, s->S.env_w, cw, ch, cond);
@@ -112,15 +113,9 @@ static int env_build(SolScene* s) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(&tot, total, sizeof(float), hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess) {
-    hipFree(t);
-    return sol_fail(SOL_EDEVICE, "sol_env_sampling: %s", hipGetErrorString(e));
-  }
-  if (!(tot > 0.0f && tot < __builtin_huge_valf())) {
-    hipFree(t);
-    return sol_fail(SOL_EINVAL, "sol_env_sampling: the cell weights of the environment map sum to %g", (double)tot);
-  }
-  s->env_tables = t;
+  if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "sol_env_sampling: %s", hipGetErrorString(e));
+  if (!(tot > 0.0f && tot < __builtin_huge_valf())) return sol_fail(SOL_EINVAL, "sol_env_sampling: the cell weights of the environment map sum to %g", (double)tot);
+  s->env_tables = std::move(tables);
   s->env_total = tot;
   s->S.env_marg = marg;
   s->S.env_cond = cond;
@@ -178,9 +173,10 @@ int sol_env_eval(SolScene* s, uint32_t fn, const float* in, uint32_t n, float* o
   if (n > (1u << 26)) return sol_fail(SOL_EINVAL, "sol_env_eval: more than 2^26 rows");
   HIP_TRY(hipSetDevice(s->device));
   const size_t ib = (size_t)n * (fn == 0 ? 2 : 3) * sizeof(float), ob = (size_t)n * (fn == 0 ? 6 : 3) * sizeof(float);
-  float *din = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc((void**)&din, ib));
-  if (hipMalloc((void**)&dout, ob) != hipSuccess) { hipFree(din); return sol_fail(SOL_ENOMEM, "hipMalloc failed"); }
+  DevPtr<float> din_own, dout_own;
+  HIP_TRY(sol_dev_alloc(din_own, ib / sizeof(float)));
+  if (sol_dev_alloc(dout_own, ob / sizeof(float)) != hipSuccess) return sol_fail(SOL_ENOMEM, "hipMalloc failed");
+  float *const din = din_own.get(), *const dout = dout_own.get();
   hipError_t e = hipMemcpyAsync(din, in, ib, hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(sol_env_eval_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s->stream, s->S, fn, (const float*)din, n, dout);
@@ -188,8 +184,6 @@ int sol_env_eval(SolScene* s, uint32_t fn, const float* in, uint32_t n, float* o
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  hipFree(din);
-  hipFree(dout);
   if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "sol_env_eval: %s", hipGetErrorString(e));
   return SOL_OK;
 }

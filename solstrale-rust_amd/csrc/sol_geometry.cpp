@@ -66,7 +66,7 @@ int move_primitives(SolScene* s, const Rows& r, const SolGeometryUpdate& u, bool
   if (y.primitives) HIP_TRY(hipMemsetAsync(s_prim, 0, 8, s->stream));
   if (mt) {
     HIP_TRY(sol_launch_triangle_records(r.p[0], y.tri_static.get(), y.rec_tri.get(), y.n_recs, y.n_tris, y.tris2.get(), y.shade2.get(), tri_box_st, out, s->stream));
-    HIP_TRY(sol_launch_triangle_lights(r.p[0], y.tri_static.get(), y.light_src.get(), n_lights, y.n_tris, y.light_tri2, area_dev, s->stream));
+    HIP_TRY(sol_launch_triangle_lights(r.p[0], y.tri_static.get(), y.light_src.get(), n_lights, y.n_tris, y.light_tri2.get(), area_dev, s->stream));
   }
   if (ms) HIP_TRY(sol_launch_sphere_records(r.p[1], y.sphere_static.get(), y.rec_sphere.get(), y.n_spheres, y.n_spheres, y.spheres2.get(), y.sphere_box2.get(), out, s_prim, s->stream));
   if (mq) HIP_TRY(sol_launch_quad_records(r.p[2], y.quad_static.get(), y.rec_quad.get(), y.n_quads, y.n_quads, y.quads2.get(), y.quad_box2.get(), out, s_prim + 1, s->stream));
@@ -116,7 +116,7 @@ int move_primitives(SolScene* s, const Rows& r, const SolGeometryUpdate& u, bool
   if (mt) {
     std::swap(s->tree.tris, y.tris2); std::swap(s->tree.tri_shade, y.shade2); std::swap(s->light_tri, y.light_tri2);
     if (y.primitives) std::swap(y.tri_box, y.tri_box2);
-    D.tris = s->tree.tris.get(); D.tri_shade = s->tree.tri_shade.get(); D.light_tri = s->light_tri;
+    D.tris = s->tree.tris.get(); D.tri_shade = s->tree.tri_shade.get(); D.light_tri = s->light_tri.get();
   }
   if (ms) { std::swap(s->tree.spheres, y.spheres2); std::swap(y.sphere_box, y.sphere_box2); D.spheres = s->tree.spheres.get(); }
   if (mq) { std::swap(s->tree.quads, y.quads2); std::swap(y.quad_box, y.quad_box2); D.quads = s->tree.quads.get(); }

@@ -17,6 +17,14 @@
 
 #include "sol_scene.h"
 
+int sol_launch_plan(SolScene* s, int blocks_per_cu, uint64_t items, uint32_t lds_depth, uint32_t stack_need, DevBuf<uint32_t>& spill, uint32_t* grid) {
+  if (s->max_bpc > 0) blocks_per_cu = std::max(1, std::min(blocks_per_cu, s->max_bpc));  // SOL_OPT_MAX_BLOCKS_PER_CU
+  const uint64_t need_blocks = std::max<uint64_t>(1, (items + SOL_WG - 1) / SOL_WG);
+  *grid = (uint32_t)std::min<uint64_t>((uint64_t)(s->n_cu * blocks_per_cu), need_blocks);
+  // spill stack only when the tree can out-grow the LDS stack
+  return spill.reserve(s->stream, stack_need > lds_depth ? (size_t)*grid * SOL_WG * (stack_need - lds_depth) : 16);
+}
+
 // ad != null: one round of adaptive sampling (sol_adaptive.hip). The launch traces the active list `ad->order` - a DevScene copy
 // with that work order, uploaded to its own device copy - and leaves the chunk sums in `partial` for sol_adaptive_round, which
 // adds them to the accumulator; the product kernel itself is the one a plain render runs.
@@ -69,6 +77,7 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   const uint64_t items = (uint64_t)P.n_chunks * P.n_traced_blocks * 64u;
   DevScene Sv = s->S;  // the scene this launch renders: the work order is the active list in a round of adaptive sampling
   if (ad) { Sv.block_order = ad->order; Sv.n_first = ad->n_first; }
+  SolSceneMirror& mirror = ad ? *ad->mirror : s->mirror;  // .. and has its own device copy
   // the 32-bit work counter keeps counting after the items run out (every wave adds 64 per refused fetch until all its
   // lanes have left): 16 M of headroom is > 100 times what 5120 resident waves can add
   if ((uint64_t)P.n_chunks * P.n_local_blocks * 64u > SOL_MAX_ITEMS) return sol_fail(SOL_EINVAL, "too many work items in one call (%llu): split the sample range", (unsigned long long)items);
@@ -82,47 +91,30 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   if (version != 1 && version != 4 && s->strict_triangles) return sol_fail(SOL_EINVAL, "kernel variant %d does not implement the consistency rule of scenes with needle triangles", version);
 #ifndef SOL_AB_KERNELS
   if (version != 1) return sol_fail(SOL_EINVAL, "kernel variant %d exists only in -DSOL_AB_KERNELS builds of the library", version);
-  int bpc = sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env, lt);
+  const int bpc = sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env, lt);
 #else
-  int bpc = version == 3 ? sol_wf_trace_blocks_per_cu(count, s->has_medium) : sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env, lt);
+  const int bpc = version == 3 ? sol_wf_trace_blocks_per_cu(count, s->has_medium) : sol_render_blocks_per_cu(version, count, s->has_medium, s->strict_triangles, env, lt);
 #endif
-  if (s->max_bpc > 0) bpc = std::max(1, std::min(bpc, s->max_bpc));  // SOL_OPT_MAX_BLOCKS_PER_CU
-  uint32_t grid = (uint32_t)(s->n_cu * bpc);
-  const uint32_t need_blocks = std::max(1u, (P.n_items + SOL_WG - 1) / SOL_WG);
-  if (grid > need_blocks) grid = need_blocks;
-  P.total_threads = grid * SOL_WG;
   uint32_t lds_depth = (uint32_t)SOL_LDS_STACK;
   uint32_t stack_need = s->tree.depth;  // dwords of traversal stack a search of this scene can use
 #ifdef SOL_AB_KERNELS
   // (swap_min: lanes waiting before an exchange pass of the search loop; 64 = only when the wave would otherwise leave for the service block, the best setting measured)
   if (version == 4) { lds_depth = (uint32_t)sol_pool4_lds_stack_depth(); stack_need = s->tree.packed_depth; P.swap_min = s->pool_swap_min ? s->pool_swap_min : 64u; }
   if (version == 3) lds_depth = (uint32_t)sol_wf_lds_stack_depth();
+#endif
+  uint32_t grid;
+  int rc;
+  if ((rc = sol_launch_plan(s, bpc, P.n_items, lds_depth, stack_need, s->spill, &grid))) return rc;
+  P.total_threads = grid * SOL_WG;
+#ifdef SOL_AB_KERNELS
   if (version == 3) {
     // one global pool: enough slots that the trace kernel has >= 16 rays per resident lane, never more than the items
     uint64_t want = std::min<uint64_t>(P.n_items, s->wf_slots);
     want = ((want + SOL_WG - 1) / SOL_WG) * SOL_WG;
     P.pool_slots = (uint32_t)want;
-    const size_t need = sol_wf_pool_bytes(P.pool_slots);  // POOL_RECORDS float4 per slot
-    if (need > s->pool_bytes) {
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      if (s->pool) hipFree(s->pool);
-      s->pool = nullptr;
-      s->pool_bytes = 0;
-      HIP_TRY(hipMalloc(&s->pool, need));
-      s->pool_bytes = need;
-    }
-    if ((size_t)P.pool_slots > s->queue_slots) {  // item reservoirs: one uint2 per 64 slots (shade wave)
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      if (s->queue) hipFree(s->queue);
-      s->queue = nullptr;
-      s->queue_slots = 0;
-      HIP_TRY(hipMalloc((void**)&s->queue, (size_t)P.pool_slots / 64 * 8));
-      s->queue_slots = P.pool_slots;
-    }
-    if (!s->wf_ctr) {
-      HIP_TRY(hipMalloc(&s->wf_ctr, 64));
-      HIP_TRY(hipHostMalloc((void**)&s->wf_ctr_host, 64, hipHostMallocDefault));
-    }
+    // POOL_RECORDS float4 per slot; item reservoirs: one uint2 per 64 slots (shade wave)
+    if ((rc = s->pool.reserve(s->stream, sol_wf_pool_bytes(P.pool_slots))) || (rc = s->queue.reserve(s->stream, P.pool_slots / 64)) || (rc = s->wf_ctr.reserve(s->stream, 16))) return rc;
+    if (!s->wf_ctr_host) HIP_TRY(sol_pinned_alloc(s->wf_ctr_host, 16));
   } else if (version == 2) {
     // pool of path slots: per wave a multiple of 64, enough that every wave has several rays per lane in flight
     const uint32_t waves = grid * (SOL_WG / 64);
@@ -130,26 +122,9 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
     per_wave = ((per_wave + 63u) / 64u) * 64u;
     P.pool_slots = std::min<uint32_t>(SOL_POOL_MAX, std::max<uint32_t>(64u, per_wave));
     if (s->pool_slots_override) P.pool_slots = std::min<uint32_t>(SOL_POOL_MAX, ((s->pool_slots_override + 63u) / 64u) * 64u);
-    const size_t need = sol_pool_bytes_per_wave(P.pool_slots) * waves;
-    if (need > s->pool_bytes) {
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      if (s->pool) hipFree(s->pool);
-      s->pool = nullptr;
-      s->pool_bytes = 0;
-      HIP_TRY(hipMalloc(&s->pool, need));
-      s->pool_bytes = need;
-    }
+    if ((rc = s->pool.reserve(s->stream, sol_pool_bytes_per_wave(P.pool_slots) * waves))) return rc;
   }
 #endif
-  // spill stack only when the tree can out-grow the LDS stack
-  size_t spill_words = stack_need > lds_depth ? (size_t)P.total_threads * (stack_need - lds_depth) : 16;
-  if (spill_words > s->spill_words) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->spill) hipFree(s->spill);
-    s->spill = nullptr;
-    HIP_TRY(hipMalloc((void**)&s->spill, spill_words * sizeof(uint32_t)));
-    s->spill_words = spill_words;
-  }
   const size_t slots3 = (size_t)P.n_local_blocks * 64u * 3u;
   // Fine tail (v1): the last pairs (block, chunk) of the work order - all of them in the last chunk, blocks the probe found light -
   // are handed out one sample at a time: about one whole item per resident lane (SOL_FINE_TAIL quarters), so that single
@@ -183,39 +158,31 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   // into the accumulator
   const bool via_partial = version == 1 || version == 4 || P.n_chunks > 1;
   if (via_partial) {
-    size_t need = slots3 * P.n_chunks + stage_floats;
-    if (need > s->partial_floats) {
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      if (s->partial) hipFree(s->partial);
-      s->partial = nullptr;
-      s->partial_floats = 0;
-      HIP_TRY(hipMalloc((void**)&s->partial, need * sizeof(float)));
-      s->partial_floats = need;
-    }
+    if ((rc = s->partial.reserve(s->stream, slots3 * P.n_chunks + stage_floats))) return rc;
     // padding pixels of edge blocks are never written: keep them zero
-    if ((s->S.width % SOL_TILE) || (s->S.height % SOL_TILE)) HIP_TRY(hipMemsetAsync(s->partial, 0, slots3 * P.n_chunks * sizeof(float), s->stream));
+    if ((s->S.width % SOL_TILE) || (s->S.height % SOL_TILE)) HIP_TRY(hipMemsetAsync(s->partial.get(), 0, slots3 * P.n_chunks * sizeof(float), s->stream));
   }
-  HIP_TRY(hipMemsetAsync(s->work, 0, sizeof(uint32_t), s->stream));
-  if (count) HIP_TRY(hipMemsetAsync(s->counters, 0, sizeof(DevCounters), s->stream));
+  HIP_TRY(hipMemsetAsync(s->work.get(), 0, sizeof(uint32_t), s->stream));
+  if (count) HIP_TRY(hipMemsetAsync(s->counters.get(), 0, sizeof(DevCounters), s->stream));
   if (s->timing) HIP_TRY(hipEventRecord(s->ev_start, s->stream));
 #ifdef SOL_AB_KERNELS
   if (version == 3) {
     // rounds of (shade, trace) until no slot holds work; the live-slot count is read back every few rounds
-    uint32_t* ctr = (uint32_t*)s->wf_ctr;  // WfCounters {work_next, slot_cursor, live, pad}
+    uint32_t* ctr = s->wf_ctr.get();  // WfCounters {work_next, slot_cursor, live, pad}
     HIP_TRY(hipMemsetAsync(ctr, 0, 16, s->stream));
-    HIP_TRY(hipMemsetAsync((char*)s->pool + (size_t)P.pool_slots * 16, 0, (size_t)P.pool_slots * 16, s->stream));  // record 1: flags
-    HIP_TRY(hipMemsetAsync(s->queue, 0, (size_t)P.pool_slots / 64 * 8, s->stream));                              // reservoirs
+    HIP_TRY(hipMemsetAsync(s->pool.get() + (size_t)P.pool_slots * 16, 0, (size_t)P.pool_slots * 16, s->stream));  // record 1: flags
+    HIP_TRY(hipMemsetAsync(s->queue.get(), 0, (size_t)P.pool_slots / 64 * 8, s->stream));                              // reservoirs
     const uint32_t check_every = 16;
     uint32_t rounds = 0;
     for (;;) {
       HIP_TRY(hipMemsetAsync(ctr + 1, 0, 8, s->stream));  // slot_cursor, live
-      HIP_TRY(sol_launch_wf_shade(s->S, P, s->acc, s->partial, ctr, s->pool, s->queue, s->counters, count, s->stream));
-      HIP_TRY(sol_launch_wf_trace(s->S, P, ctr, s->pool, s->spill, s->counters, grid, count, s->has_medium, s->stream));
+      HIP_TRY(sol_launch_wf_shade(s->S, P, s->acc, s->partial.get(), ctr, s->pool.get(), s->queue.get(), s->counters.get(), count, s->stream));
+      HIP_TRY(sol_launch_wf_trace(s->S, P, ctr, s->pool.get(), s->spill.get(), s->counters.get(), grid, count, s->has_medium, s->stream));
       ++rounds;
       if (rounds % check_every == 0) {
-        HIP_TRY(hipMemcpyAsync(s->wf_ctr_host, ctr, 16, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipMemcpyAsync(s->wf_ctr_host.get(), ctr, 16, hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
-        if (s->wf_ctr_host[2] == 0) break;
+        if (s->wf_ctr_host.get()[2] == 0) break;
         if (rounds > 4000000u) return sol_fail(SOL_EDEVICE, "wavefront did not drain");
       }
     }
@@ -223,20 +190,9 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
   } else
 #endif
   {
-    if (!s->dscene) HIP_TRY(hipMalloc((void**)&s->dscene, sizeof(DevScene)));
-    DevScene* dS = ad ? ad->dscene : s->dscene;
-    DevScene* up = ad ? ad->uploaded : &s->S_uploaded;
-    bool* valid = ad ? ad->valid : &s->dscene_valid;
-    if (!*valid || std::memcmp(&Sv, up, sizeof(DevScene)) != 0) {
-      // rare (scene creation, tree probe, auxiliary renders; a round whose active list has a new heavy prefix): launches already
-      // queued may still read the old copy
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      HIP_TRY(hipMemcpy(dS, &Sv, sizeof(DevScene), hipMemcpyHostToDevice));
-      std::memcpy(up, &Sv, sizeof(DevScene));
-      *valid = true;
-    }
+    if ((rc = mirror.upload(s->stream, Sv))) return rc;
     if (P.n_items > 0)
-      HIP_TRY(sol_launch_render(version, Sv, dS, P, s->acc, s->partial, s->work, s->spill, s->pool, s->counters, grid, count,
+      HIP_TRY(sol_launch_render(version, Sv, mirror.dev.get(), P, s->acc, s->partial.get(), s->work.get(), s->spill.get(), s->pool.get(), s->counters.get(), grid, count,
                                 s->has_medium, stack_need > lds_depth, env, lt, s->stream));
     if (ad) {
       // the active background blocks are the last ad->n_background entries of the active list: the fill kernel writes the blocks
@@ -244,20 +200,20 @@ int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool
       if (ad->n_background) {
         RenderParams Q = P;
         Q.n_traced_blocks = P.n_local_blocks - ad->n_background;
-        HIP_TRY(sol_launch_fill_background(dS, Q, s->partial, s->stream));
+        HIP_TRY(sol_launch_fill_background(mirror.dev.get(), Q, s->partial.get(), s->stream));
       }
     } else if (P.n_traced_blocks != P.n_local_blocks) {
-      HIP_TRY(sol_launch_fill_background(dS, P, s->partial, s->stream));
+      HIP_TRY(sol_launch_fill_background(mirror.dev.get(), P, s->partial.get(), s->stream));
     }
   }
   if (s->timing) { HIP_TRY(hipEventRecord(s->ev_stop, s->stream)); s->timed_launches++; }
   s->last_grid = grid;
   s->last_version = version;
-  if (P.n_coarse != P.n_items) HIP_TRY(sol_launch_stage_resolve(ad ? ad->dscene : s->dscene, P, s->partial, s->stream));
-  if (via_partial && !ad) HIP_TRY(sol_launch_resolve(s->acc, s->partial, (uint32_t)slots3, P.n_chunks, s->stream));
+  if (P.n_coarse != P.n_items) HIP_TRY(sol_launch_stage_resolve(mirror.dev.get(), P, s->partial.get(), s->stream));
+  if (via_partial && !ad) HIP_TRY(sol_launch_resolve(s->acc, s->partial.get(), (uint32_t)slots3, P.n_chunks, s->stream));
   if (count) {
     DevCounters c;
-    HIP_TRY(hipMemcpyAsync(&c, s->counters, sizeof c, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(&c, s->counters.get(), sizeof c, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->stats.samples = c.samples; s->stats.rays = c.rays; s->stats.node_visits = c.node_visits;
     s->stats.sphere_tests = c.sphere_tests; s->stats.quad_tests = c.quad_tests; s->stats.triangle_tests = c.triangle_tests;
@@ -292,13 +248,12 @@ int sol_render_counted(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
 int sol_render_aux(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
   if (!s) return sol_fail(SOL_EINVAL, "null scene");
   HIP_TRY(hipSetDevice(s->device));
-  if (s->aux_floats != s->acc_floats || !s->aux[0]) {
+  if (s->aux_floats != s->acc_floats || !s->aux[0]) {  // none yet, or planes of another partition's layout: new sums, all zero
     HIP_TRY(hipStreamSynchronize(s->stream));
+    s->aux_floats = 0;  // (no planes until both exist)
     for (int k = 0; k < 2; ++k) {
-      if (s->aux[k]) hipFree(s->aux[k]);
-      s->aux[k] = nullptr;
-      HIP_TRY(hipMalloc((void**)&s->aux[k], std::max<size_t>(s->acc_floats * sizeof(float), 64)));
-      HIP_TRY(hipMemsetAsync(s->aux[k], 0, std::max<size_t>(s->acc_floats * sizeof(float), 64), s->stream));
+      if (const int rc = s->aux[k].reserve(s->stream, s->acc_floats)) return rc;
+      HIP_TRY(hipMemsetAsync(s->aux[k].get(), 0, std::max<size_t>(s->acc_floats * sizeof(float), 64), s->stream));
     }
     s->aux_floats = s->acc_floats;
     s->aux_samples = 0;
@@ -310,7 +265,7 @@ int sol_render_aux(SolScene* s, uint32_t first, uint32_t n, uint64_t seed) {
   const float bg[3] = {s->S.bgx, s->S.bgy, s->S.bgz};
   const float* const env = s->S.env;
   for (int k = 0; k < 2 && rc == SOL_OK; ++k) {
-    s->acc = s->aux[k];
+    s->acc = s->aux[k].get();
     s->S.shader = kinds[k];
     if (k == 1) { s->S.bgx = s->S.bgy = s->S.bgz = 0.0f; s->S.env = nullptr; }  // a miss: albedo = background colour, normal = ZERO_VECTOR (mod.rs:197-204)
     rc = sol_render_impl(s, first, n, seed, false);
@@ -327,7 +282,7 @@ int sol_clear_aux(SolScene* s) {
   if (!s) return sol_fail(SOL_EINVAL, "null scene");
   HIP_TRY(hipSetDevice(s->device));
   for (int k = 0; k < 2; ++k)
-    if (s->aux[k] && s->aux_floats == s->acc_floats) HIP_TRY(hipMemsetAsync(s->aux[k], 0, s->aux_floats * sizeof(float), s->stream));
+    if (s->aux[k] && s->aux_floats == s->acc_floats) HIP_TRY(hipMemsetAsync(s->aux[k].get(), 0, s->aux_floats * sizeof(float), s->stream));
   s->aux_samples = 0;
   return SOL_OK;
 }
@@ -339,9 +294,9 @@ int sol_read_aux(SolScene* s, float* albedo_sum, float* normal_sum) {
   float* outs[2] = {albedo_sum, normal_sum};
   for (int k = 0; k < 2; ++k) {
     if (!outs[k]) continue;
-    HIP_TRY(sol_launch_unpermute(s->aux[k], s->image, s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
-                                 s->acc_floats, s->slot_of_block, s->stream));
-    HIP_TRY(hipMemcpyAsync(outs[k], s->image, (size_t)s->S.width * s->S.height * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(sol_launch_unpermute(s->aux[k].get(), s->image.get(), s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
+                                 s->acc_floats, s->slot_of_block.get(), s->stream));
+    HIP_TRY(hipMemcpyAsync(outs[k], s->image.get(), (size_t)s->S.width * s->S.height * 3 * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
@@ -358,17 +313,15 @@ int sol_eval(int device, uint32_t fn, const float* in, uint32_t n, uint32_t in_s
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
   HIP_TRY(hipSetDevice(device));
-  float *din = nullptr, *dout = nullptr;
+  DevPtr<float> din, dout;
   const size_t ib = (size_t)n * in_stride * sizeof(float), ob = (size_t)n * out_stride * sizeof(float);
-  HIP_TRY(hipMalloc((void**)&din, std::max<size_t>(ib, 64)));
-  if (hipMalloc((void**)&dout, std::max<size_t>(ob, 64)) != hipSuccess) { hipFree(din); return sol_fail(SOL_ENOMEM, "hipMalloc failed"); }
-  hipError_t e = hipMemcpy(din, in, ib, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemset(dout, 0, std::max<size_t>(ob, 64));
-  if (e == hipSuccess) e = sol_launch_eval(fn, din, n, in_stride, dout, out_stride, nullptr);
+  HIP_TRY(sol_dev_alloc(din, (size_t)n * in_stride));
+  if (sol_dev_alloc(dout, (size_t)n * out_stride) != hipSuccess) return sol_fail(SOL_ENOMEM, "hipMalloc failed");
+  hipError_t e = hipMemcpy(din.get(), in, ib, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(dout.get(), 0, std::max<size_t>(ob, 64));
+  if (e == hipSuccess) e = sol_launch_eval(fn, din.get(), n, in_stride, dout.get(), out_stride, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(out, dout, ob, hipMemcpyDeviceToHost);
-  hipFree(din);
-  hipFree(dout);
+  if (e == hipSuccess) e = hipMemcpy(out, dout.get(), ob, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "sol_eval: %s", hipGetErrorString(e));
   return SOL_OK;
 }
@@ -381,17 +334,15 @@ int sol_debug_path(SolScene* s, uint32_t x, uint32_t y, uint32_t sample, uint64_
   RenderParams P{};
   P.seed_lo = (uint32_t)seed; P.seed_hi = (uint32_t)(seed >> 32);
   P.total_threads = 1;
-  float* dout = nullptr;
-  uint32_t* dspill = nullptr;
+  DevPtr<float> dout;
+  DevPtr<uint32_t> dspill;
   const size_t ob = (size_t)max_rows * 12 * sizeof(float);
-  HIP_TRY(hipMalloc((void**)&dout, ob));
-  hipError_t e = hipMalloc((void**)&dspill, (size_t)(SOL_SPILL_STACK + 8) * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemset(dout, 0, ob);
-  if (e == hipSuccess) e = sol_launch_debug_path(s->S, P, x, y, sample, dspill, dout, max_rows, s->has_medium, nullptr);
+  HIP_TRY(sol_dev_alloc(dout, (size_t)max_rows * 12));
+  hipError_t e = sol_dev_alloc(dspill, (size_t)SOL_SPILL_STACK + 8);
+  if (e == hipSuccess) e = hipMemset(dout.get(), 0, ob);
+  if (e == hipSuccess) e = sol_launch_debug_path(s->S, P, x, y, sample, dspill.get(), dout.get(), max_rows, s->has_medium, nullptr);
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(rows, dout, ob, hipMemcpyDeviceToHost);
-  hipFree(dout);
-  if (dspill) hipFree(dspill);
+  if (e == hipSuccess) e = hipMemcpy(rows, dout.get(), ob, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "sol_debug_path: %s", hipGetErrorString(e));
   for (uint32_t r = 0; r < max_rows && rows[r * 12 + 3] != -1.0f; ++r) {  // hit references: device order -> the caller's indices
     uint32_t ref;

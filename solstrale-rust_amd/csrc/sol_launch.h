@@ -4,6 +4,16 @@
 
 #include "sol_types.h"
 
+// Workgroups of SOL_WG threads of `kernel` that one CU holds at a time (at least 1): what every persistent launch sizes its grid by. Each kernel
+// family asks about the function its variant table (sol_render_variant, ..) names for SPILL = true: the SPILL = false builds need no more registers
+// or LDS than those.
+template <typename K>
+int sol_blocks_per_cu(K kernel) {
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
+  return n;
+}
+
 // version 1: one path per lane (the product kernel); versions 2 / 3 (-DSOL_AB_KERNELS builds): the wavefront variants of sol_wavefront.hip
 hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
                              uint32_t* spill, void* pool, DevCounters* cnt, uint32_t grid, bool count, bool medium, bool may_spill,

@@ -206,8 +206,9 @@ static int light_tree_build(SolScene* s) {
   uint64_t leaves = 1;
   while (leaves < L) { leaves *= 4u; ++depth; }
   const uint64_t first = (leaves - 1u) / 3u, total = (4u * leaves - 1u) / 3u;
-  float* t = nullptr;
-  if (hipMalloc((void**)&t, (size_t)total * 6u * sizeof(float)) != hipSuccess) return sol_fail(SOL_ENOMEM, "sol_light_sampling: no memory for the light tree");
+  DevPtr<float> tree;
+  if (sol_dev_alloc(tree, (size_t)total * 6u) != hipSuccess) return sol_fail(SOL_ENOMEM, "sol_light_sampling: no memory for the light tree");
+  float* const t = tree.get();
   hipLaunchKernelGGL(sol_light_leaves_kernel, dim3((uint32_t)((leaves + 255u) / 256u)), dim3(256), 0, s->stream, s->S, (uint32_t)leaves, (uint32_t)first,
                      2.0f * s->S.sphere_slack, t);
   for (uint32_t l = depth; l-- > 0;) {  // levels bottom-up: level l holds nodes (4^l - 1) / 3 .. (4^(l+1) - 1) / 3 - 1
@@ -216,11 +217,8 @@ static int light_tree_build(SolScene* s) {
   }
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess) {
-    hipFree(t);
-    return sol_fail(SOL_EDEVICE, "sol_light_sampling: %s", hipGetErrorString(e));
-  }
-  s->light_tree = t;
+  if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "sol_light_sampling: %s", hipGetErrorString(e));
+  s->light_tree = std::move(tree);
   s->light_tree_bytes = (size_t)total * 6u * sizeof(float);
   s->S.light_nodes = t;
   s->S.light_first_leaf = (uint32_t)first;
@@ -231,16 +229,14 @@ static int light_tables_build(SolScene* s) {
   std::vector<float> q, cdf;
   light_tables_of(s->light_w, q, cdf);
   const size_t L = q.size();
-  float* t = nullptr;
-  if (hipMalloc((void**)&t, 2 * L * sizeof(float)) != hipSuccess) return sol_fail(SOL_ENOMEM, "sol_light_sampling: no memory for the tables");
+  DevPtr<float> tables;
+  if (sol_dev_alloc(tables, 2 * L) != hipSuccess) return sol_fail(SOL_ENOMEM, "sol_light_sampling: no memory for the tables");
+  float* const t = tables.get();
   hipError_t e = hipMemcpyAsync(t, q.data(), L * sizeof(float), hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(t + L, cdf.data(), L * sizeof(float), hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess) {
-    hipFree(t);
-    return sol_fail(SOL_EDEVICE, "sol_light_sampling: %s", hipGetErrorString(e));
-  }
-  s->light_tables = t;
+  if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "sol_light_sampling: %s", hipGetErrorString(e));
+  s->light_tables = std::move(tables);
   s->S.light_q = t;
   s->S.light_cdf = t + L;
   return SOL_OK;
@@ -251,13 +247,11 @@ int sol_light_rebuild(SolScene* s) {
   int rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   if (s->light_tree) {
-    hipFree(s->light_tree);
-    s->light_tree = nullptr; s->light_tree_bytes = 0; s->S.light_nodes = nullptr;
+    s->light_tree.reset(); s->light_tree_bytes = 0; s->S.light_nodes = nullptr;
     if ((rc = light_tree_build(s))) return rc;
   }
   if (s->light_tables) {
-    hipFree(s->light_tables);
-    s->light_tables = nullptr; s->S.light_q = nullptr; s->S.light_cdf = nullptr;
+    s->light_tables.reset(); s->S.light_q = nullptr; s->S.light_cdf = nullptr;
     if ((rc = light_tables_build(s))) return rc;
   }
   return SOL_OK;
@@ -326,7 +320,7 @@ int sol_light_tree(SolScene* s, float* nodes, size_t n_floats, uint32_t* n_nodes
   if (bytes) *bytes = s->light_tree_bytes;
   if (nodes) {
     HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipMemcpyAsync(nodes, s->light_tree, s->light_tree_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(nodes, s->light_tree.get(), s->light_tree_bytes, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
@@ -341,9 +335,10 @@ int sol_light_eval(SolScene* s, uint32_t fn, const float* in, uint32_t n, float*
   if (n > (1u << 26)) return sol_fail(SOL_EINVAL, "sol_light_eval: more than 2^26 rows");
   HIP_TRY(hipSetDevice(s->device));
   const size_t ib = (size_t)n * (fn == 0 ? 6 : 1) * sizeof(float), ob = (size_t)n * (fn == 0 ? 4 : 1) * sizeof(float);
-  float *din = nullptr, *dout = nullptr;
-  HIP_TRY(hipMalloc((void**)&din, ib));
-  if (hipMalloc((void**)&dout, ob) != hipSuccess) { hipFree(din); return sol_fail(SOL_ENOMEM, "hipMalloc failed"); }
+  DevPtr<float> din_own, dout_own;
+  HIP_TRY(sol_dev_alloc(din_own, ib / sizeof(float)));
+  if (sol_dev_alloc(dout_own, ob / sizeof(float)) != hipSuccess) return sol_fail(SOL_ENOMEM, "hipMalloc failed");
+  float *const din = din_own.get(), *const dout = dout_own.get();
   hipError_t e = hipMemcpyAsync(din, in, ib, hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) {
     DevScene S = s->S;
@@ -354,8 +349,6 @@ int sol_light_eval(SolScene* s, uint32_t fn, const float* in, uint32_t n, float*
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, dout, ob, hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  hipFree(din);
-  hipFree(dout);
   if (e != hipSuccess) return sol_fail(SOL_EDEVICE, "sol_light_eval: %s", hipGetErrorString(e));
   return SOL_OK;
 }

@@ -285,38 +285,25 @@ sol_render_pool4_kernel(const DevScene* __restrict__ Sp, const RenderParams P, f
   if (COUNT) flush_counters(cnt, dcnt);
 }
 
-template <bool MEDIUM, bool SPILL, bool STRICT>
-static hipError_t launch_pool4(const DevScene* dS, const RenderParams& P, float* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL((sol_render_pool4_kernel<MEDIUM, SPILL, STRICT>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, partial, work, spill, (DevCounters*)nullptr);
-  return hipGetLastError();
+// The variant table of the family: the launch and the occupancy query both ask here. Instrumented (SOL_POOL_COUNT=1: phase statistics of the
+// pool kernel): two variants only, with the spill tail and without the consistency rule.
+using Pool4Kernel = void (*)(const DevScene*, const RenderParams, float*, uint32_t*, uint32_t*, DevCounters*);
+template <bool MEDIUM>
+static Pool4Kernel pool4_variant_of(bool spill, bool strict, bool count) {
+  if (count) return strict ? nullptr : sol_render_pool4_kernel<MEDIUM, true, false, true>;
+  if (spill) return strict ? sol_render_pool4_kernel<MEDIUM, true, true> : sol_render_pool4_kernel<MEDIUM, true, false>;
+  return strict ? sol_render_pool4_kernel<MEDIUM, false, true> : sol_render_pool4_kernel<MEDIUM, false, false>;
+}
+static Pool4Kernel sol_pool4_variant(bool medium, bool spill, bool strict, bool count) {
+  return medium ? pool4_variant_of<true>(spill, strict, count) : pool4_variant_of<false>(spill, strict, count);
 }
 hipError_t sol_launch_pool4(const DevScene& S, const DevScene* dS, const RenderParams& P, float* partial, uint32_t* work, uint32_t* spill, uint32_t grid,
                             bool medium, bool may_spill, DevCounters* cnt, hipStream_t stream) {
-  const bool strict = S.tri_delta > 0.0f;
-  if (cnt) {  // instrumented (SOL_POOL_COUNT=1: phase statistics of the pool kernel; two variants only)
-    if (strict) return hipErrorInvalidValue;
-    if (medium) hipLaunchKernelGGL((sol_render_pool4_kernel<true, true, false, true>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, partial, work, spill, cnt);
-    else hipLaunchKernelGGL((sol_render_pool4_kernel<false, true, false, true>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, partial, work, spill, cnt);
-    return hipGetLastError();
-  }
-#define POOL4(M, SP, ST) launch_pool4<M, SP, ST>(dS, P, partial, work, spill, grid, stream)
-  if (strict) {
-    if (may_spill) return medium ? POOL4(true, true, true) : POOL4(false, true, true);
-    return medium ? POOL4(true, false, true) : POOL4(false, false, true);
-  }
-  if (may_spill) return medium ? POOL4(true, true, false) : POOL4(false, true, false);
-  return medium ? POOL4(true, false, false) : POOL4(false, false, false);
-#undef POOL4
+  const Pool4Kernel kernel = sol_pool4_variant(medium, may_spill, S.tri_delta > 0.0f, cnt != nullptr);
+  if (!kernel) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, dS, P, partial, work, spill, cnt);
+  return hipGetLastError();
 }
-template <typename K>
-static int pool4_blocks(K kernel) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
-  return n;
-}
-int sol_pool4_blocks_per_cu(bool medium, bool strict) {  // (the SPILL = false builds need no more registers or LDS than these)
-  if (strict) return medium ? pool4_blocks(sol_render_pool4_kernel<true, true, true>) : pool4_blocks(sol_render_pool4_kernel<false, true, true>);
-  return medium ? pool4_blocks(sol_render_pool4_kernel<true, true, false>) : pool4_blocks(sol_render_pool4_kernel<false, true, false>);
-}
+int sol_pool4_blocks_per_cu(bool medium, bool strict) { return sol_blocks_per_cu(sol_pool4_variant(medium, true, strict, false)); }
 int sol_pool4_lds_stack_depth() { return POOL_LDS_STACK; }
 #endif  // SOL_AB_KERNELS

@@ -24,7 +24,7 @@ int sol_unpermute(SolScene* s, const void* gathered, int world, void* image) {
   if (world != s->world) return sol_fail(SOL_EINVAL, "world %d differs from the scene's partition (%d)", world, s->world);
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(sol_launch_unpermute((const float*)gathered, (float*)image, s->S.width, s->S.height, s->blocks_x, (uint32_t)world,
-                               0xFFFFFFFFu, s->acc_floats, s->slot_of_block, s->stream));
+                               0xFFFFFFFFu, s->acc_floats, s->slot_of_block.get(), s->stream));
   return SOL_OK;
 }
 
@@ -32,8 +32,8 @@ int sol_tonemap_rgb8(SolScene* s, const void* image, uint32_t spp, uint8_t* out)
   if (!s || !image || !out || spp == 0) return sol_fail(SOL_EINVAL, "bad argument");
   HIP_TRY(hipSetDevice(s->device));
   const uint32_t n = s->S.width * s->S.height * 3;
-  HIP_TRY(sol_launch_tonemap((const float*)image, s->rgb8, n, spp, s->stream));
-  HIP_TRY(hipMemcpyAsync(out, s->rgb8, n, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(sol_launch_tonemap((const float*)image, s->rgb8.get(), n, spp, s->stream));
+  HIP_TRY(hipMemcpyAsync(out, s->rgb8.get(), n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return SOL_OK;
 }
@@ -41,9 +41,9 @@ int sol_tonemap_rgb8(SolScene* s, const void* image, uint32_t spp, uint8_t* out)
 int sol_resolve_image(SolScene* s, void** image_dev) {
   if (!s || !image_dev) return sol_fail(SOL_EINVAL, "null argument");
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_unpermute(s->acc, s->image, s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
-                               s->acc_floats, s->slot_of_block, s->stream));
-  *image_dev = s->image;
+  HIP_TRY(sol_launch_unpermute(s->acc, s->image.get(), s->S.width, s->S.height, s->blocks_x, (uint32_t)s->world, (uint32_t)s->rank,
+                               s->acc_floats, s->slot_of_block.get(), s->stream));
+  *image_dev = s->image.get();
   return SOL_OK;
 }
 
@@ -84,21 +84,14 @@ static int bloom_impl(SolScene* s, void* image, uint32_t spp, double ksf, double
   const double thr = threshold * (double)spp, maxi = max_intensity * (double)spp;
   const size_t k = (size_t)(ksf * (double)W) * 2 + 1;
   std::vector<double> w = gaussian_blur_weights(k, (double)k / 5.0);
-  if (!s->bloom_a) HIP_TRY(hipMalloc((void**)&s->bloom_a, n * sizeof(double)));
-  if (!s->bloom_b) HIP_TRY(hipMalloc((void**)&s->bloom_b, n * sizeof(double)));
-  if (k > s->bloom_w_cap) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (s->bloom_w) hipFree(s->bloom_w);
-    s->bloom_w = nullptr; s->bloom_w_cap = 0;
-    HIP_TRY(hipMalloc((void**)&s->bloom_w, k * sizeof(double)));
-    s->bloom_w_cap = k;
-  }
-  HIP_TRY(hipMemcpyAsync(s->bloom_w, w.data(), k * sizeof(double), hipMemcpyHostToDevice, s->stream));
+  int rc;
+  if ((rc = s->bloom_a.reserve(s->stream, n)) || (rc = s->bloom_b.reserve(s->stream, n)) || (rc = s->bloom_w.reserve(s->stream, k))) return rc;
+  HIP_TRY(hipMemcpyAsync(s->bloom_w.get(), w.data(), k * sizeof(double), hipMemcpyHostToDevice, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));  // `w` is pageable host memory about to go out of scope
-  HIP_TRY(sol_launch_bloom((float*)image, s->bloom_a, s->bloom_b, s->bloom_w, (uint32_t)k, W, H, thr, maxi, out ? s->rgb8 : nullptr, spp,
+  HIP_TRY(sol_launch_bloom((float*)image, s->bloom_a.get(), s->bloom_b.get(), s->bloom_w.get(), (uint32_t)k, W, H, thr, maxi, out ? s->rgb8.get() : nullptr, spp,
                            s->stream));
   if (out) {
-    HIP_TRY(hipMemcpyAsync(out, s->rgb8, n, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(out, s->rgb8.get(), n, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;

@@ -171,32 +171,22 @@ __global__ void __launch_bounds__(256) sol_camera_rays_kernel(const DevScene* __
 }
 
 // ---- launch wrappers (called from sol_api.cpp) ----
-#define QUERY_PICK(K, any, spill, strict, ...)                                         \
-  do {                                                                                 \
-    if (any) { if (spill) { if (strict) K(true, true, true, __VA_ARGS__); else K(true, true, false, __VA_ARGS__); }     \
-               else { if (strict) K(true, false, true, __VA_ARGS__); else K(true, false, false, __VA_ARGS__); } }        \
-    else { if (spill) { if (strict) K(false, true, true, __VA_ARGS__); else K(false, true, false, __VA_ARGS__); }      \
-           else { if (strict) K(false, false, true, __VA_ARGS__); else K(false, false, false, __VA_ARGS__); } }           \
-  } while (0)
+// The variant table of the family: which instantiation the run-time flags name - the launch and the occupancy query both ask here.
+using QueryKernel = void (*)(const DevScene*, const float4*, uint32_t, void*, uint32_t*, uint32_t);
+template <bool ANY>
+static QueryKernel query_variant_of(bool spill, bool strict) {
+  if (spill) return strict ? sol_query_kernel<ANY, true, true> : sol_query_kernel<ANY, true, false>;
+  return strict ? sol_query_kernel<ANY, false, true> : sol_query_kernel<ANY, false, false>;
+}
+static QueryKernel sol_query_variant(bool any, bool spill, bool strict) { return any ? query_variant_of<true>(spill, strict) : query_variant_of<false>(spill, strict); }
 
 hipError_t sol_launch_query(const DevScene* dS, bool any, bool may_spill, bool strict, const void* rays, uint32_t n, void* out, uint32_t* spill,
                             uint32_t grid, hipStream_t stream) {
-#define QUERY_A(A, SP, ST, ...) hipLaunchKernelGGL((sol_query_kernel<A, SP, ST>), dim3(grid), dim3(SOL_WG), 0, stream, dS, (const float4*)rays, n, out, spill, grid * SOL_WG)
-  QUERY_PICK(QUERY_A, any, may_spill, strict, 0);
-#undef QUERY_A
+  const QueryKernel kernel = sol_query_variant(any, may_spill, strict);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, dS, (const float4*)rays, n, out, spill, grid * SOL_WG);
   return hipGetLastError();
 }
-
-template <typename K>
-static int query_blocks_per_cu(K kernel) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
-  return n;
-}
-int sol_query_blocks_per_cu(bool any, bool strict) {  // (the SPILL = false builds need no more registers or LDS than these)
-  if (any) return strict ? query_blocks_per_cu(sol_query_kernel<true, true, true>) : query_blocks_per_cu(sol_query_kernel<true, true, false>);
-  return strict ? query_blocks_per_cu(sol_query_kernel<false, true, true>) : query_blocks_per_cu(sol_query_kernel<false, true, false>);
-}
+int sol_query_blocks_per_cu(bool any, bool strict) { return sol_blocks_per_cu(sol_query_variant(any, true, strict)); }
 
 hipError_t sol_launch_camera_rays(const DevScene* dS, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, void* rays,
                                   hipStream_t stream) {

@@ -223,31 +223,23 @@ __global__ void __launch_bounds__(256) sol_camera_ray_keys_kernel(const DevScene
 // ---- launch wrappers (called from sol_api.cpp) ----
 // Built: the default estimator with and without the spill tail, plain and STRICT (4); the ENV / LT estimators SPILL-capable only, plain and
 // STRICT (6) - a scene whose tree fits the LDS stack runs them with a spill area it never touches.
-#define RADIANCE_LAUNCH(SP, ST, E, L) \
-  hipLaunchKernelGGL((sol_radiance_kernel<SP, ST, E, L>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, (const float4*)rays, (const uint2*)keys, (sol_v4f*)out, (sol_v4f*)partial, work, spill)
+// The variant table: which of them the run-time flags name - the launch and the occupancy query both ask here.
+using RadianceKernel = void (*)(const DevScene*, const RadianceParams, const float4*, const uint2*, sol_v4f*, sol_v4f*, uint32_t*, uint32_t*);
+template <bool SPILL, bool ENV, bool LT>
+static RadianceKernel radiance_variant_of(bool strict) { return strict ? sol_radiance_kernel<SPILL, true, ENV, LT> : sol_radiance_kernel<SPILL, false, ENV, LT>; }
+static RadianceKernel sol_radiance_variant(bool spill, bool strict, bool env, bool lt) {
+  if (env) return lt ? radiance_variant_of<true, true, true>(strict) : radiance_variant_of<true, true, false>(strict);
+  if (lt) return radiance_variant_of<true, false, true>(strict);
+  return spill ? radiance_variant_of<true, false, false>(strict) : radiance_variant_of<false, false, false>(strict);
+}
+
 hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool may_spill, bool strict, bool env, bool lt, const void* rays, const void* keys,
                                void* out, void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream) {
-  if (env && lt) { if (strict) RADIANCE_LAUNCH(true, true, true, true); else RADIANCE_LAUNCH(true, false, true, true); }
-  else if (env) { if (strict) RADIANCE_LAUNCH(true, true, true, false); else RADIANCE_LAUNCH(true, false, true, false); }
-  else if (lt) { if (strict) RADIANCE_LAUNCH(true, true, false, true); else RADIANCE_LAUNCH(true, false, false, true); }
-  else if (may_spill) { if (strict) RADIANCE_LAUNCH(true, true, false, false); else RADIANCE_LAUNCH(true, false, false, false); }
-  else { if (strict) RADIANCE_LAUNCH(false, true, false, false); else RADIANCE_LAUNCH(false, false, false, false); }
+  const RadianceKernel kernel = sol_radiance_variant(may_spill, strict, env, lt);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, dS, P, (const float4*)rays, (const uint2*)keys, (sol_v4f*)out, (sol_v4f*)partial, work, spill);
   return hipGetLastError();
 }
-#undef RADIANCE_LAUNCH
-
-template <typename K>
-static int radiance_blocks_per_cu(K kernel) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
-  return n;
-}
-int sol_radiance_blocks_per_cu(bool strict, bool env, bool lt) {  // (the SPILL = false builds need no more registers or LDS than these)
-  if (env && lt) return strict ? radiance_blocks_per_cu(sol_radiance_kernel<true, true, true, true>) : radiance_blocks_per_cu(sol_radiance_kernel<true, false, true, true>);
-  if (env) return strict ? radiance_blocks_per_cu(sol_radiance_kernel<true, true, true, false>) : radiance_blocks_per_cu(sol_radiance_kernel<true, false, true, false>);
-  if (lt) return strict ? radiance_blocks_per_cu(sol_radiance_kernel<true, true, false, true>) : radiance_blocks_per_cu(sol_radiance_kernel<true, false, false, true>);
-  return strict ? radiance_blocks_per_cu(sol_radiance_kernel<true, true, false, false>) : radiance_blocks_per_cu(sol_radiance_kernel<true, false, false, false>);
-}
+int sol_radiance_blocks_per_cu(bool strict, bool env, bool lt) { return sol_blocks_per_cu(sol_radiance_variant(true, strict, env, lt)); }
 
 hipError_t sol_launch_radiance_resolve(const RadianceParams& P, const void* rays, const void* partial, void* out, uint32_t samples, bool accumulate,
                                        hipStream_t stream) {

@@ -281,52 +281,36 @@ hipError_t sol_launch_debug_path(const DevScene& S, const RenderParams& P, uint3
 }
 
 // ---- launch wrappers (called from sol_launch.cpp) ----
-template <bool COUNT, bool MEDIUM, bool SPILL, bool STRICT, bool ENV = false, bool LT = false>
-static hipError_t launch_v1(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
-                            uint32_t* spill, DevCounters* cnt, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL((sol_render_kernel<COUNT, MEDIUM, SPILL, STRICT, ENV, LT>), dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
-  return hipGetLastError();
-}
-template <bool STRICT>
-static hipError_t launch_v1_any(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, DevCounters* cnt,
-                                uint32_t grid, bool count, bool medium, bool may_spill, hipStream_t stream) {
-  if (count) return medium ? launch_v1<true, true, true, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
-                           : launch_v1<true, false, true, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
-  if (may_spill) return medium ? launch_v1<false, true, true, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
-                               : launch_v1<false, false, true, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
-  return medium ? launch_v1<false, true, false, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
-                : launch_v1<false, false, false, STRICT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
-}
-template <bool STRICT, bool ENV, bool LT>  // (ENV, LT: plain renders only - sol_render_counted refuses while either is on)
-static hipError_t launch_v1_ext(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, DevCounters* cnt,
-                                uint32_t grid, bool medium, bool may_spill, hipStream_t stream) {
-  if (may_spill) return medium ? launch_v1<false, true, true, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
-                               : launch_v1<false, false, true, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
-  return medium ? launch_v1<false, true, false, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream)
-                : launch_v1<false, false, false, STRICT, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, stream);
+// The variant table of the family: which instantiation the run-time flags name - the launch and the occupancy query both ask here. Built: counted
+// renders with the spill tail only and the default estimator only (12 kernels with the uncounted ones), ENV / LT uncounted (24).
+using RenderKernel = void (*)(const DevScene*, const RenderParams, float*, float*, uint32_t*, uint32_t*, DevCounters*);
+template <bool COUNT, bool SPILL, bool ENV, bool LT>
+static RenderKernel render_variant_of(bool medium, bool strict) {
+  if (medium) return strict ? sol_render_kernel<COUNT, true, SPILL, true, ENV, LT> : sol_render_kernel<COUNT, true, SPILL, false, ENV, LT>;
+  return strict ? sol_render_kernel<COUNT, false, SPILL, true, ENV, LT> : sol_render_kernel<COUNT, false, SPILL, false, ENV, LT>;
 }
 template <bool ENV, bool LT>
-static hipError_t launch_v1_ext_any(const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill,
-                                    DevCounters* cnt, uint32_t grid, bool medium, bool may_spill, hipStream_t stream) {
-  return S.tri_delta > 0.0f ? launch_v1_ext<true, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream)
-                            : launch_v1_ext<false, ENV, LT>(dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
+static RenderKernel render_variant_of(bool medium, bool spill, bool strict) {
+  return spill ? render_variant_of<false, true, ENV, LT>(medium, strict) : render_variant_of<false, false, ENV, LT>(medium, strict);
+}
+static RenderKernel sol_render_variant(bool count, bool medium, bool spill, bool strict, bool env, bool lt) {
+  if (count) return render_variant_of<true, true, false, false>(medium, strict);  // (never with ENV or LT: sol_render_counted refuses while either is on)
+  if (env) return lt ? render_variant_of<true, true>(medium, spill, strict) : render_variant_of<true, false>(medium, spill, strict);
+  return lt ? render_variant_of<false, true>(medium, spill, strict) : render_variant_of<false, false>(medium, spill, strict);
 }
 
 hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
                              uint32_t* spill, void* pool, DevCounters* cnt, uint32_t grid, bool count, bool medium, bool may_spill,
                              bool env, bool lt, hipStream_t stream) {
-  if (env || lt) {
-    if (version != 1 || count) return hipErrorInvalidValue;  // (sol_render_impl runs importance sampling and the light tree on the uncounted product kernel only)
-    if (lt) return env ? launch_v1_ext_any<true, true>(S, dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream)
-                       : launch_v1_ext_any<false, true>(S, dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
-    return launch_v1_ext_any<true, false>(S, dS, P, acc, partial, work, spill, cnt, grid, medium, may_spill, stream);
-  }
+  if ((env || lt) && (version != 1 || count)) return hipErrorInvalidValue;  // (sol_render_impl runs importance sampling and the light tree on the uncounted product kernel only)
 #ifdef SOL_AB_KERNELS
   if (version == 4) return sol_launch_pool4(S, dS, P, partial, work, spill, grid, medium, may_spill, count ? cnt : nullptr, stream);  // (sol_pool.hip)
 #endif
-  if (version == 1)
-    return S.tri_delta > 0.0f ? launch_v1_any<true>(dS, P, acc, partial, work, spill, cnt, grid, count, medium, may_spill, stream)
-                              : launch_v1_any<false>(dS, P, acc, partial, work, spill, cnt, grid, count, medium, may_spill, stream);
+  if (version == 1) {
+    const RenderKernel kernel = sol_render_variant(count, medium, may_spill, S.tri_delta > 0.0f, env, lt);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
+    return hipGetLastError();
+  }
 #ifdef SOL_AB_KERNELS
   return sol_launch_pool(S, P, acc, partial, work, spill, pool, cnt, grid, count, medium, stream);  // (sol_wavefront.hip)
 #else
@@ -334,36 +318,12 @@ hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS,
 #endif
 }
 
-template <typename K>
-static int blocks_per_cu(K kernel) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, SOL_WG, 0) != hipSuccess || n < 1) n = 1;
-  return n;
-}
 int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env, bool lt) {
-  if (lt) {
-    if (env) {
-      if (strict) return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true, true, true>);
-      return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, false, true, true>);
-    }
-    if (strict) return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, false, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true, false, true>);
-    return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, false, true>) : blocks_per_cu(sol_render_kernel<false, false, true, false, false, true>);
-  }
-  if (env) {
-    if (strict) return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, true>) : blocks_per_cu(sol_render_kernel<false, false, true, true, true>);
-    return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, true>) : blocks_per_cu(sol_render_kernel<false, false, true, false, true>);
-  }
+  if (env || lt) { version = 1; count = false; }  // (as sol_render_impl chooses: the ENV / LT builds are the uncounted product kernel)
 #ifdef SOL_AB_KERNELS
   if (version == 4) return sol_pool4_blocks_per_cu(medium, strict);
 #endif
-  if (version == 1) {  // (the SPILL = false builds need no more registers or LDS than these)
-    if (strict) {
-      if (count) return medium ? blocks_per_cu(sol_render_kernel<true, true, true, true, false>) : blocks_per_cu(sol_render_kernel<true, false, true, true, false>);
-      return medium ? blocks_per_cu(sol_render_kernel<false, true, true, true, false>) : blocks_per_cu(sol_render_kernel<false, false, true, true, false>);
-    }
-    if (count) return medium ? blocks_per_cu(sol_render_kernel<true, true, true, false, false>) : blocks_per_cu(sol_render_kernel<true, false, true, false, false>);
-    return medium ? blocks_per_cu(sol_render_kernel<false, true, true, false, false>) : blocks_per_cu(sol_render_kernel<false, false, true, false, false>);
-  }
+  if (version == 1) return sol_blocks_per_cu(sol_render_variant(count, medium, true, strict, env, lt));
 #ifdef SOL_AB_KERNELS
   return sol_pool_blocks_per_cu(count, medium);
 #else

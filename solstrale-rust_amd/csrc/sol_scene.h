@@ -1,8 +1,11 @@
 // sol_scene.h -- the handle behind the C ABI (include/solstrale_hip.h) and what the translation units of libsolstrale_hip.so
-// share: error reporting, the developer overrides (environment variables, parsed in ONE place), the device memory of a scene.
+// share: error reporting, the developer overrides (environment variables, parsed in ONE place), the device memory of a scene - owned, all of
+// it, by DevPtr (an array made once), DevBuf (an array that grows on demand: reserve) and PinnedPtr members that free themselves with their
+// owner -, the device copy of the scene record (SolSceneMirror) and the launch plan of the persistent kernels (sol_launch_plan).
 //   sol_api.cpp     handle life cycle, options, partition, accumulators, read-back, statistics
 //   sol_create.cpp  sol_scene_create in stages: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h), world-tree candidates, upload, probes; the tree diagnostics
-//   sol_launch.cpp  sol_render* / auxiliary planes / debug hooks: launches of the kernels in sol_render.hip
+//   sol_launch.cpp  sol_render* / auxiliary planes / debug hooks: launches of the kernels in sol_render.hip; sol_launch_plan (grid and spill tail)
+//   sol_launch.h    the launch wrappers of the .hip files (each family: one variant table for the launch and the occupancy query; sol_blocks_per_cu)
 //   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
 //   sol_geometry.cpp sol_scene_set_triangles / sol_scene_set_primitives: the triangles, spheres and quads of a live scene moved, records and tree boxes recomputed on the device (sol_geometry.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
@@ -30,19 +33,73 @@ int sol_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)
     if (e_ != hipSuccess) return sol_fail(SOL_EDEVICE, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-template <typename T>
-int sol_upload(const std::vector<T>& host, T** dev) {
-  *dev = nullptr;
-  size_t bytes = std::max<size_t>(host.size() * sizeof(T), 64);  // never a null device pointer
-  HIP_TRY(hipMalloc((void**)dev, bytes));
-  HIP_TRY(hipMemset(*dev, 0, bytes));
-  if (!host.empty()) HIP_TRY(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-  return SOL_OK;
-}
-
 struct SolHipFree { void operator()(void* p) const { hipFree(p); } };
 template <typename T> using DevPtr = std::unique_ptr<T, SolHipFree>;  // an owned device array: freed with its owner, empty after a move
-template <typename T> int sol_upload(const std::vector<T>& host, DevPtr<T>& dev) { T* p = nullptr; const int rc = sol_upload(host, &p); dev.reset(p); return rc; }
+// `dev` <- n uninitialised elements (at least 64 bytes: never a null device pointer), or empty when the allocation fails. The callers name the error.
+template <typename T> hipError_t sol_dev_alloc(DevPtr<T>& dev, size_t n) {
+  T* p = nullptr;
+  const hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n * sizeof(T), 64));
+  dev.reset(e == hipSuccess ? p : nullptr);
+  return e;
+}
+// `dev` <- a copy of `host`, the rest of the allocation zero
+template <typename T>
+int sol_upload(const std::vector<T>& host, DevPtr<T>& dev) {
+  HIP_TRY(sol_dev_alloc(dev, host.size()));
+  HIP_TRY(hipMemset(dev.get(), 0, std::max<size_t>(host.size() * sizeof(T), 64)));
+  if (!host.empty()) HIP_TRY(hipMemcpy(dev.get(), host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+  return SOL_OK;
+}
+struct SolHipHostFree { void operator()(void* p) const { hipHostFree(p); } };
+template <typename T> using PinnedPtr = std::unique_ptr<T, SolHipHostFree>;  // an owned array of pinned host memory
+template <typename T> hipError_t sol_pinned_alloc(PinnedPtr<T>& host, size_t n) {
+  T* p = nullptr;
+  const hipError_t e = hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault);
+  host.reset(e == hipSuccess ? p : nullptr);
+  return e;
+}
+
+// An owned device array that grows on demand, with its capacity in elements: every scratch buffer and table of a handle whose size follows the
+// calls (DevPtr: the arrays whose size is fixed when they are made). Freed with its owner.
+template <typename T>
+class DevBuf {
+ public:
+  T* get() const { return p_.get(); }
+  size_t capacity() const { return cap_; }
+  explicit operator bool() const { return (bool)p_; }
+  void reset() { p_.reset(); cap_ = 0; }
+  // Room for n elements; the contents are NOT kept and NOT zeroed. Nothing happens while the buffer exists and holds n already (no
+  // synchronisation, no allocation: the steady state of every launch path). Otherwise launches queued on `stream` may still use the old array:
+  // the stream is drained, the array freed and a new one allocated - never a null pointer, also for n = 0. The capacity is recorded after the
+  // allocation succeeded; after a failure the buffer is empty with capacity 0, so the next call allocates again instead of trusting a stale size.
+  int reserve(hipStream_t stream, size_t n) {
+    if (p_ && cap_ >= n) return SOL_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    reset();
+    HIP_TRY(sol_dev_alloc(p_, n));
+    cap_ = n;
+    return SOL_OK;
+  }
+ private:
+  DevPtr<T> p_;
+  size_t cap_ = 0;
+};
+// The device copy of a scene record, which the kernels read through a pointer: the copy, the host image last uploaded and whether there is one.
+struct SolSceneMirror {
+  DevPtr<DevScene> dev; DevScene uploaded{}; bool valid = false;
+  // dev holds S afterwards. Uploaded only when S differs from the copy on the device (rare: scene creation, a tree probe, an auxiliary render in
+  // between, a round of adaptive sampling whose active list has a new heavy prefix): launches already queued may still read the old copy.
+  int upload(hipStream_t stream, const DevScene& S) {
+    if (!dev) HIP_TRY(sol_dev_alloc(dev, 1));
+    if (!valid || std::memcmp(&S, &uploaded, sizeof(DevScene)) != 0) {
+      HIP_TRY(hipStreamSynchronize(stream));
+      HIP_TRY(hipMemcpy(dev.get(), &S, sizeof(DevScene), hipMemcpyHostToDevice));
+      std::memcpy(&uploaded, &S, sizeof(DevScene));
+      valid = true;
+    }
+    return SOL_OK;
+  }
+};
 #define SOL_MAX_ITEMS 0xFF000000ull
 
 // Developer overrides: environment variables for experiments and A/B runs, parsed by sol_dev_overrides() - the
@@ -105,7 +162,7 @@ struct SolDynamic {
   std::vector<uint32_t> level_off;       // level l = level_nodes[level_off[l] .. level_off[l + 1])
   DevPtr<float> node_box;                // [n_wide][6] scratch of the refit: the union of a node's padded child boxes
   DevPtr<DWide> wides2; DevPtr<DTri> tris2; DevPtr<DTriShade> shade2;  // staging: both kernels write here, the commit swaps them with the tree's
-  DTri* light_tri2 = nullptr;            // staging of SolScene::light_tri
+  DevPtr<DTri> light_tri2;               // staging of SolScene::light_tri
   DevPtr<uint32_t> light_src;            // [n_lights] caller triangle of light i, 0xFFFFFFFF: not a triangle
   std::vector<uint32_t> light_src_host;
   std::vector<double> light_lum;         // [n_lights] luminance of the light's emission (sol_light_weights_of's factor)
@@ -133,61 +190,56 @@ struct SolAdaptiveSession {
   uint32_t round = 0, min_samples = 0, max_samples = 0; float threshold = 0.f;
   uint32_t rounds_done = 0;                           // rounds rendered since sol_adaptive_begin
   uint32_t n_first = 0, n_traced = 0, n_background = 0;  // the active list the next round renders
-  float* state = nullptr; size_t state_slots = 0;     // per slot of the accumulator: Welford mean and M2 of the rounds' luminance
-  uint32_t* active = nullptr;                         // per local block: 1 = still sampled
-  uint32_t* order = nullptr; size_t order_cap = 0;    // the active list (n_local_blocks entries)
-  uint32_t* counts = nullptr; size_t counts_cap = 0;  // per image block (row-major): samples its pixels hold
-  uint32_t* ctr = nullptr; uint32_t* ctr_host = nullptr;  // what the compaction counted: heavy, traced, background active blocks
-  DevScene* dscene = nullptr; DevScene S_uploaded{}; bool dscene_valid = false;  // the DevScene copy whose work order is the active list
-  void release() {
-    void* p[] = {state, active, order, counts, ctr, dscene};
-    for (void* q : p) if (q) hipFree(q);
-    if (ctr_host) hipHostFree(ctr_host);
-    *this = SolAdaptiveSession{};
-  }
+  DevBuf<float> state;      // per slot of the accumulator (2 floats): Welford mean and M2 of the rounds' luminance
+  DevBuf<uint32_t> active;  // per local block: 1 = still sampled
+  DevBuf<uint32_t> order;   // the active list (n_local_blocks entries)
+  DevBuf<uint32_t> counts;  // per image block (row-major): samples its pixels hold
+  DevBuf<uint32_t> ctr; PinnedPtr<uint32_t> ctr_host;  // what the compaction counted: heavy, traced, background active blocks
+  SolSceneMirror mirror;    // the DevScene copy whose work order is the active list
 };
 // What sol_render_impl needs to render a round over the active list instead of the whole work order.
 struct SolAdaptiveLaunch {
   const uint32_t* order;
   uint32_t n_first, n_traced, n_background;
-  DevScene* dscene; DevScene* uploaded; bool* valid;
+  SolSceneMirror* mirror;
 };
 
 struct SolScene {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
   DevScene S{};
-  DevScene* dscene = nullptr; DevScene S_uploaded{}; bool dscene_valid = false;  // device copy of S (the v1 kernel reads it through a pointer)
+  SolSceneMirror mirror;               // device copy of S (the product render kernel and the queries read it through a pointer)
   DevTree tree;                        // the world tree the handle walks and what hangs on it; S points into it
   std::string tree_name;               // which world tree the handle walks ("ref", "sah8", .., "device")
   std::string tree_note;               // why it is not the one asked for (AUTO: the device build failed), else empty
   uint32_t split_references = 0, split_triangles = 0;  // device build: what triangle pre-splitting added
   float split_area_ratio = 1.f;
   uint32_t reinsertion_moves = 0; float reinsertion_area_ratio = 1.f;  // device build: sub-trees moved; summed inner-node area after / before
-  // owned device buffers
-  DMat* mats = nullptr; DTex* texs = nullptr; uint8_t* texels = nullptr; float* env = nullptr; DTri* light_tri = nullptr;
-  float* acc_own = nullptr; float* acc = nullptr; size_t acc_floats = 0;
-  float* aux[2] = {nullptr, nullptr}; size_t aux_floats = 0;  // albedo / normal accumulators (sol_render_aux), same layout as acc
+  // Device memory. Every allocation of the handle is owned by a DevPtr (made once) or a DevBuf (grows on demand) here, in `tree`, `dyn` or
+  // `adaptive`, and is freed with the handle (sol_scene_destroy); S and every other raw pointer are views into them.
+  DevPtr<DMat> mats; DevPtr<DTex> texs; DevPtr<uint8_t> texels; DevPtr<float> env; DevPtr<DTri> light_tri;
+  DevBuf<float> acc_own; float* acc = nullptr; size_t acc_floats = 0;  // acc: acc_own or the caller's bound memory; acc_floats: the size the partition gives it
+  DevBuf<float> aux[2]; size_t aux_floats = 0;  // albedo / normal accumulators (sol_render_aux), same layout as acc; aux_floats: the acc_floats they were cleared for
   uint32_t aux_samples = 0;                 // samples sol_render_aux added since the planes were last cleared (sol_resolve_aux)
-  float* aux_img[2] = {nullptr, nullptr};   // row-major albedo / normal planes of sol_resolve_aux (W*H*3 floats each)
-  float4* den_buf = nullptr; size_t den_pixels = 0;  // sol_denoise scratch (sol_denoise.hip): 4 float4 per pixel
+  DevBuf<float> aux_img[2];                 // row-major albedo / normal planes of sol_resolve_aux (W*H*3 floats each)
+  DevBuf<float4> den_buf;                   // sol_denoise scratch (sol_denoise.hip): 4 float4 per pixel
   std::vector<uint32_t> block_cost;  // per 8x8 block (global index): rays of its longest item in the cost probe; empty: no ordering
   std::vector<uint32_t> block_work;  // per 8x8 block (global index): its rays in the cost probe (balanced partition)
   bool balanced = false;             // SOL_OPT_BALANCED_PARTITION
   uint32_t partition_table = 0, partition_crc = 0;  // the partition in force: 1 = the balanced table (0: b % world), checksum of block -> slot
   std::vector<uint32_t> local_blocks;  // balanced partition: image block of every local block of this rank (empty: b = lb * world + rank)
-  uint32_t* block_of_local_dev = nullptr; size_t block_of_local_cap = 0;
-  uint32_t* slot_of_block = nullptr;   // balanced partition (device, all blocks): owner * blocks-per-buffer + local block; null: modulo
-  uint32_t* order_dev = nullptr; size_t order_cap = 0;  // DevScene::block_order of the current partition
-  float* partial = nullptr; size_t partial_floats = 0;
+  DevBuf<uint32_t> block_of_local_dev;
+  DevBuf<uint32_t> slot_of_block;      // balanced partition (device, all blocks): owner * blocks-per-buffer + local block; empty: modulo
+  DevBuf<uint32_t> order_dev;          // DevScene::block_order of the current partition
+  DevBuf<float> partial;
   int fine_tail = -1;                // SOL_OPT_FINE_TAIL / SOL_FINE_TAIL: quarters of a whole item per resident lane that the end of a launch hands
                                      // out sample by sample; 0: none; -1: by the creation probe's node visits per sample (fine_tail_auto)
   int fine_tail_auto = 0;
-  float* image = nullptr;  // W*H*3 scratch for sol_read / sol_resolve_image
-  uint8_t* rgb8 = nullptr;
-  double* bloom_a = nullptr; double* bloom_b = nullptr; double* bloom_w = nullptr; size_t bloom_w_cap = 0;  // sol_bloom scratch
-  uint32_t* work = nullptr; uint32_t* spill = nullptr; size_t spill_words = 0;
-  DevCounters* counters = nullptr;
+  DevPtr<float> image;  // W*H*3 scratch for sol_read / sol_resolve_image
+  DevPtr<uint8_t> rgb8;
+  DevBuf<double> bloom_a, bloom_b, bloom_w;  // sol_bloom scratch
+  DevPtr<uint32_t> work; DevBuf<uint32_t> spill;  // the render launch's work counter and the spill tail of its grid (sol_launch_plan)
+  DevPtr<DevCounters> counters;
   SolStats stats{};
   SolPathStats path_stats{};
   bool has_medium = false;
@@ -197,11 +249,11 @@ struct SolScene {
   uint32_t blocks_x = 0, blocks_y = 0, n_local_blocks = 0;
   int n_cu = 0;
   int kernel_version = 0;          // 0 auto; SOL_KERNEL=v1|v2|v3 forces one (A/B comparisons)
-  void* pool = nullptr; size_t pool_bytes = 0;  // path-slot pool of the wavefront kernels
+  DevBuf<char> pool;               // path-slot pool of the wavefront kernels
   uint32_t pool_slots_override = 0;  // SOL_POOL_SLOTS (v2: slots per wave)
   uint32_t switch_below = 0;         // SOL_SWITCH (v1, RenderParams::switch_below)
-  uint32_t* queue = nullptr; size_t queue_slots = 0;  // v3 ray queue
-  void* wf_ctr = nullptr; uint32_t* wf_ctr_host = nullptr;
+  DevBuf<uint2> queue;               // v3 ray queue: one reservoir per 64 pool slots
+  DevBuf<uint32_t> wf_ctr; PinnedPtr<uint32_t> wf_ctr_host;
   uint32_t wf_slots = 4u << 20;       // SOL_WF_SLOTS: pool size of the two-kernel wavefront
   uint32_t wf_min_items = 2u << 20;   // SOL_WF_MIN_ITEMS: jobs below this use the single-launch kernel
   uint32_t last_rounds = 0; int last_version = 0;
@@ -216,13 +268,13 @@ struct SolScene {
   // the device flags its proof kernel writes (one byte per block; allocated by the first move, kept)
   float box_pad = 0.f;
   bool background_proof = false, cost_probe = false, verbose = false;
-  uint8_t* proof_flags = nullptr;
+  DevBuf<uint8_t> proof_flags;
   bool background_enabled = true;    // SOL_OPT_BACKGROUND_BLOCKS
   bool background_in_counted = false;  // (value 2) counted renders skip them too: the counters of exactly what a plain render does
   int order_mode = 2;                // (SOL_ORDER) 1: heavy blocks first only; 2: + cost classes within a chunk
   int max_bpc = 0;                   // SOL_OPT_MAX_BLOCKS_PER_CU (0 = what the occupancy query allows)
   // multi-GPU (sol_comm_init): RCCL communicator of the tile partition and rank 0's receive buffer
-  void* comm = nullptr; float* gathered = nullptr; size_t gathered_floats = 0;
+  void* comm = nullptr; DevBuf<float> gathered;
   bool timing = false;  // sol_kernel_timing: HIP events around the render kernel on its own stream
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   uint32_t timed_launches = 0, last_grid = 0;
@@ -231,7 +283,7 @@ struct SolScene {
   // decided at creation from the description (sol_env_refusal); env_tables: one allocation - marginal CDF (H'), conditional CDFs (H' x W'),
   // row totals (H'), total (1) - built on first use and kept; env_is: renders of the path-tracing shader run the ENV kernels.
   std::string env_refusal;
-  float* env_tables = nullptr;
+  DevPtr<float> env_tables;
   float env_total = 0.f;
   bool env_is = false;
   // Light tree and power-weighted light sampling (sol_lights.hip). light_w: the f64 weights (area x luminance) of the
@@ -239,21 +291,21 @@ struct SolScene {
   // (mode 2, first use); light_mode: 0 uniform, 1 tree, 2 power - modes 1 and 2 run the LT kernels.
   std::vector<double> light_w;
   double light_total = 0.0;
-  float* light_tree = nullptr;
+  DevPtr<float> light_tree;
   size_t light_tree_bytes = 0;
-  float* light_tables = nullptr;
+  DevPtr<float> light_tables;
   uint32_t light_mode = 0;
   // Ray queries (sol_query.hip): the handle's staging buffers of the host route (rays in, answers out; query_cap rays each) and
   // the spill area of the query kernel's own grid. None of them is the render launch's.
-  void* query_in = nullptr; void* query_out = nullptr; size_t query_cap = 0;
-  uint32_t* query_spill = nullptr; size_t query_spill_words = 0;
+  DevBuf<SolRay> query_in; DevBuf<SolRayHit> query_out;
+  DevBuf<uint32_t> query_spill;
   // Radiance queries (sol_radiance.hip): their own work counter, partial buffer (chunk sums, 16 bytes per (chunk, ray); grown on
   // demand up to a bound), spill tail and host-route staging (rays, keys, answers; rad_cap rays each). None of them is the render launch's.
-  uint32_t* rad_work = nullptr;
-  void* rad_partial = nullptr; size_t rad_partial_rows = 0;
+  DevBuf<uint32_t> rad_work;
+  DevBuf<SolRadiance> rad_partial;
   size_t rad_partial_max_rows = (size_t)1 << 24;  // the bound: 256 MiB of chunk sums (SOL_RADIANCE_ROWS)
-  uint32_t* rad_spill = nullptr; size_t rad_spill_words = 0;
-  void* rad_in = nullptr; void* rad_keys = nullptr; void* rad_out = nullptr; size_t rad_cap = 0;
+  DevBuf<uint32_t> rad_spill;
+  DevBuf<SolRay> rad_in; DevBuf<SolRayKey> rad_keys; DevBuf<SolRadiance> rad_out;
   SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
@@ -270,10 +322,14 @@ int sol_light_rebuild(SolScene* s);
 int sol_rederive_view_tables(SolScene* s, uint32_t flags, const char* who);
 int sol_rebuild_order(SolScene* s);
 // The 4-spp cost probe of the whole frame (sol_create.cpp): the counted render, then its adoption (`rc`: the render's status; frees the tables).
-struct SolCostProbe { uint32_t* cost_dev = nullptr; uint32_t* work_dev = nullptr; };
+struct SolCostProbe { DevPtr<uint32_t> cost_dev, work_dev; };
 int sol_cost_probe_render(SolScene* s, SolCostProbe& p);
 int sol_cost_probe_adopt(SolScene* s, SolCostProbe& p, int rc, bool verbose);
-int sol_scene_to_device(SolScene* s);  // s->dscene holds s->S (uploaded when it does not yet)
+inline int sol_scene_to_device(SolScene* s) { return s->mirror.upload(s->stream, s->S); }  // s->mirror.dev holds s->S
+// The launch plan of the render, query and radiance launches (sol_launch.cpp): *grid = n_cu x blocks_per_cu (the occupancy of the chosen kernel,
+// clamped by SOL_OPT_MAX_BLOCKS_PER_CU), at least 1 and at most the blocks `items` need; `spill` holds the spill tail of that grid afterwards -
+// grid x SOL_WG x (stack_need - lds_depth) words, 16 when the searches fit the kernel's LDS stack.
+int sol_launch_plan(SolScene* s, int blocks_per_cu, uint64_t items, uint32_t lds_depth, uint32_t stack_need, DevBuf<uint32_t>& spill, uint32_t* grid);
 int sol_set_partition(SolScene* s, int rank, int world);
 int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count, const SolAdaptiveLaunch* ad = nullptr);
 inline int sol_render_probe(SolScene* s) { return sol_render_impl(s, 0, SOL_CHUNK, 0x50B3ull, true); }

@@ -210,31 +210,18 @@ sol_render_pool_kernel(const DevScene S, const RenderParams P, float* __restrict
 }
 
 
-template <bool COUNT, bool MEDIUM>
-static hipError_t launch_v2(const DevScene& S, const RenderParams& P, float* acc, float* partial, uint32_t* work,
-                            uint32_t* spill, float4* pool, DevCounters* cnt, uint32_t grid, hipStream_t stream) {
-  hipLaunchKernelGGL((sol_render_pool_kernel<COUNT, MEDIUM>), dim3(grid), dim3(SOL_WG), 0, stream, S, P, acc, partial, work, spill,
-                     pool, cnt);
-  return hipGetLastError();
+using PoolKernel = void (*)(const DevScene, const RenderParams, float*, float*, uint32_t*, uint32_t*, float4*, DevCounters*);
+static PoolKernel sol_pool_variant(bool count, bool medium) {  // the variant table: the launch and the occupancy query both ask here
+  if (count) return medium ? sol_render_pool_kernel<true, true> : sol_render_pool_kernel<true, false>;
+  return medium ? sol_render_pool_kernel<false, true> : sol_render_pool_kernel<false, false>;
 }
 hipError_t sol_launch_pool(const DevScene& S, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, void* pool,
                            DevCounters* cnt, uint32_t grid, bool count, bool medium, hipStream_t stream) {
-  float4* pl = (float4*)pool;
-  if (count) return medium ? launch_v2<true, true>(S, P, acc, partial, work, spill, pl, cnt, grid, stream)
-                           : launch_v2<true, false>(S, P, acc, partial, work, spill, pl, cnt, grid, stream);
-  return medium ? launch_v2<false, true>(S, P, acc, partial, work, spill, pl, cnt, grid, stream)
-                : launch_v2<false, false>(S, P, acc, partial, work, spill, pl, cnt, grid, stream);
+  const PoolKernel kernel = sol_pool_variant(count, medium);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, S, P, acc, partial, work, spill, (float4*)pool, cnt);
+  return hipGetLastError();
 }
-int sol_pool_blocks_per_cu(bool count, bool medium) {
-  int n = 0;
-  hipError_t e;
-  if (count) e = medium ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_render_pool_kernel<true, true>, SOL_WG, 0)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_render_pool_kernel<true, false>, SOL_WG, 0);
-  else e = medium ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_render_pool_kernel<false, true>, SOL_WG, 0)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_render_pool_kernel<false, false>, SOL_WG, 0);
-  if (e != hipSuccess || n < 1) n = 1;
-  return n;
-}
+int sol_pool_blocks_per_cu(bool count, bool medium) { return sol_blocks_per_cu(sol_pool_variant(count, medium)); }
 size_t sol_pool_bytes_per_wave(uint32_t slots) { return (size_t)POOL_RECORDS * slots * sizeof(float4); }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -475,24 +462,18 @@ hipError_t sol_launch_wf_shade(const DevScene& S, const RenderParams& P, float* 
   else hipLaunchKernelGGL((sol_wf_shade_kernel<false>), dim3(grid), dim3(SOL_WG), 0, stream, S, P, acc, partial, (WfCounters*)ctr, (float4*)rec, (uint2*)reservoir, cnt);
   return hipGetLastError();
 }
+using WfTraceKernel = void (*)(const DevScene, const RenderParams, WfCounters*, float4*, uint32_t*, DevCounters*);
+static WfTraceKernel sol_wf_trace_variant(bool count, bool medium) {  // the variant table: the launch and the occupancy query both ask here
+  if (count) return medium ? sol_wf_trace_kernel<true, true> : sol_wf_trace_kernel<true, false>;
+  return medium ? sol_wf_trace_kernel<false, true> : sol_wf_trace_kernel<false, false>;
+}
 hipError_t sol_launch_wf_trace(const DevScene& S, const RenderParams& P, void* ctr, void* rec, uint32_t* spill, DevCounters* cnt,
                                uint32_t grid, bool count, bool medium, hipStream_t stream) {
-#define WF_TRACE(C, M) hipLaunchKernelGGL((sol_wf_trace_kernel<C, M>), dim3(grid), dim3(SOL_WG), 0, stream, S, P, (WfCounters*)ctr, (float4*)rec, spill, cnt)
-  if (count) { if (medium) WF_TRACE(true, true); else WF_TRACE(true, false); }
-  else { if (medium) WF_TRACE(false, true); else WF_TRACE(false, false); }
-#undef WF_TRACE
+  const WfTraceKernel kernel = sol_wf_trace_variant(count, medium);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, S, P, (WfCounters*)ctr, (float4*)rec, spill, cnt);
   return hipGetLastError();
 }
-int sol_wf_trace_blocks_per_cu(bool count, bool medium) {
-  int n = 0;
-  hipError_t e;
-  if (count) e = medium ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_wf_trace_kernel<true, true>, SOL_WG, 0)
-                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_wf_trace_kernel<true, false>, SOL_WG, 0);
-  else e = medium ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_wf_trace_kernel<false, true>, SOL_WG, 0)
-                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sol_wf_trace_kernel<false, false>, SOL_WG, 0);
-  if (e != hipSuccess || n < 1) n = 1;
-  return n;
-}
+int sol_wf_trace_blocks_per_cu(bool count, bool medium) { return sol_blocks_per_cu(sol_wf_trace_variant(count, medium)); }
 size_t sol_wf_pool_bytes(uint32_t slots) { return (size_t)POOL_RECORDS * slots * sizeof(float4); }
 int sol_wf_lds_stack_depth() { return SOL_LDS_STACK_TRACE; }
 #endif  // SOL_AB_KERNELS
