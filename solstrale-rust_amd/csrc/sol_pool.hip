@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sol_launch.h"
-#include "sol_path.h"
+#include "sol_wave.h"
 
 // (RenderParams::pool_slots = items per reservation of the wave's reservoir: 1024 - 16 samples x 64 pixels of one (block, chunk) pair - in a
 // long launch, 64 in a short one, whose tail would otherwise be a thousand samples per wave)
@@ -41,9 +41,9 @@ struct PoolCtx {
 };
 
 
-// The next sample of the work order for every lane that calls (the callers are the wave's lanes without a context): the reservoir of
-// sol_render.hip - 64 consecutive items, one sample index of one 8x8 pixel block, per returning atomic -, item -> (pair (block, chunk),
-// sample of the chunk, pixel of the block), camera ray. False: the item names no sample (a padding pixel of an edge block, a sample beyond
+// The next sample of the work order for every lane that calls (the callers are the wave's lanes without a context): wave_take_item's
+// reservoir (sol_wave.h) with a third word, "dry", and P.pool_slots items per returning atomic - an aligned run of 64 is one sample index
+// of one 8x8 pixel block -, item -> (pair (block, chunk), sample of the chunk, pixel of the block), camera ray. False: the item names no sample (a padding pixel of an edge block, a sample beyond
 // a ragged last chunk) or the work has run out (no_work).
 DEV bool pool_fetch_sample(const DevScene& S, const RenderParams& P, volatile lds_u32* res, uint32_t* __restrict__ work_counter, uint32_t lane,
                            unsigned long long below, bool& no_work, Path& p, uint32_t& out_at, Counters& cnt) {
@@ -90,21 +90,12 @@ sol_render_pool4_kernel(const DevScene* __restrict__ Sp, const RenderParams P, f
   __shared__ uint8_t ray_queue[SOL_WG], hit_queue[SOL_WG];
   __shared__ uint32_t reservoir[SOL_WG / 64][4];
   const uint32_t tid = threadIdx.x;
-  const uint32_t gtid = blockIdx.x * SOL_WG + tid;
   const uint32_t lane = tid & 63u;
   const uint32_t wbase = tid & ~63u;  // this wave's first slot / queue entry
   const unsigned long long below = (1ull << lane) - 1ull;
   Stack st;
-  st.lds = (lds_u32*)lds_stack + tid;
-  st.spill = (SOL_AS1 uint32_t*)spill + gtid;
-  st.stride = P.total_threads;
-  st.depth = SPILL ? POOL_LDS_STACK : SOL_NO_SPILL;
-  sol_search_context<true>(st, S);
-  sol_fill_oct_table((lds_u8*)oct_table, tid, SOL_WG);
-  st.oct_table = (const lds_u8*)oct_table;
-  st.oct_table_on = true;
-  if (lane == 0) { reservoir[tid >> 6][0] = 0u; reservoir[tid >> 6][1] = 0u; reservoir[tid >> 6][2] = 0u; }
-  __syncthreads();
+  wave_search_stack(st, S, lds_stack, POOL_LDS_STACK, SPILL, spill, P.total_threads, oct_table, nullptr);  // (no selector table: the selects)
+  if (lane == 0) { reservoir[tid >> 6][0] = 0u; reservoir[tid >> 6][1] = 0u; reservoir[tid >> 6][2] = 0u; }  // (pool_fetch_sample's three words)
   lds_u4* const rec4 = (lds_u4*)pool4 + wbase;
   lds_u2* const rec2 = (lds_u2*)pool2 + wbase;
   volatile lds_u8* const rq = (volatile lds_u8*)ray_queue + wbase;
@@ -213,7 +204,7 @@ sol_render_pool4_kernel(const DevScene* __restrict__ Sp, const RenderParams P, f
     }
     // fresh rays start their search: world.hit(ray, RAY_INTERVAL) (src/renderer/mod.rs:165)
     if (have && !in_flight) {
-      trav_begin<true>(t, p.o, p.d, RAY_MIN_F, inf, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
+      trav_begin_world(t, S, p.o, p.d, RAY_MIN_F, inf);
       in_flight = true;
     }
     if (sol_ballot(have || !no_work) == 0ull && n_ray == 0u) break;  // no context left in the wave and none to fetch (no parked hit either: the service block drained them)
@@ -250,7 +241,7 @@ sol_render_pool4_kernel(const DevScene* __restrict__ Sp, const RenderParams P, f
               hq[n_hit + (uint32_t)__popcll(wm & below)] = (uint8_t)slot;
             }
             POOL_ADOPT(c)
-            trav_begin<true>(t, p.o, p.d, RAY_MIN_F, inf, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
+            trav_begin_world(t, S, p.o, p.d, RAY_MIN_F, inf);
             have = true;
             in_flight = true;
           }
@@ -268,12 +259,7 @@ sol_render_pool4_kernel(const DevScene* __restrict__ Sp, const RenderParams P, f
       }
       trav_step_wave<COUNT, MEDIUM, STRICT, true>(S, t, act, st, p.rng, p.depth, cnt);
       // (rule 8, sol_path.h) a finished search whose closest hit is the flat primitive the ray left: searched again behind that hit
-      if (act && t.cur == REF_DONE && sol_self_hit(p.from, t.h)) {
-        const float bt = t.bt;
-        const uint32_t bdfs = t.bdfs;
-        trav_begin<true>(t, t.o, t.d, sol_behind(t.h.t), inf, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
-        t.bt = bt; t.bdfs = bdfs;
-      }
+      if (act && t.cur == REF_DONE && sol_self_hit(p.from, t.h)) trav_restart_world<true>(t, S, t.o, t.d, sol_behind(t.h.t), inf);
       if (COUNT && act && t.cur == REF_DONE) cnt.rays++;
       // (STRICT) a finished search whose closest hit is a triangle the consistency rule refuses searches again, behind that hit
       if (STRICT && act && t.cur == REF_DONE) trav_accept_or_restart(S, t, st);

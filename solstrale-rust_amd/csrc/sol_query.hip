@@ -1,6 +1,6 @@
 // sol_query.hip -- ray queries (include/solstrale_hip.h, sol_query / sol_query_dev / sol_camera_rays): batches of
-// caller-made rays answered by the world search of sol_trace.h - the 7-wide tree, the LDS [level][lane] stack, the octant table and the
-// wave-level stepper the render kernel runs - without a path around them: no shading, no accumulator, no RNG.
+// caller-made rays answered by the world search of sol_trace.h in the search context of sol_wave.h (wave_search_stack), as the render
+// kernel runs it, without a path around them: no shading, no accumulator, no RNG.
 //
 //  sol_query_kernel<ANY, SPILL, STRICT> -- one ray per lane, run to completion, grid-stride over the batch by whole waves. ANY = false
 //    (SOL_QUERY_CLOSEST) writes one SolRayHit per ray, ANY = true (SOL_QUERY_OCCLUDED) one status word and ends a lane's search at its first
@@ -14,8 +14,8 @@
 #include <hip/hip_runtime.h>
 
 #include "sol_launch.h"
-#include "sol_path.h"
 #include "sol_ray.h"
+#include "sol_wave.h"
 
 namespace {
 
@@ -62,7 +62,7 @@ DEV void query_take(const DevScene& S, const Stack& st, const float4* __restrict
     query_write<ANY>(S, st, out, i, SOL_RAY_INVALID, none);
     return;
   }
-  trav_begin<true>(q.t, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
+  trav_begin_world(q.t, S, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), a.w, b.w);
   q.tmax = b.w;
   q.index = i;
   q.left = 63u;
@@ -96,24 +96,6 @@ DEV void query_step(const DevScene& S, const Stack& st, const Rng& rng, Counters
   }
 }
 
-DEV void query_stack(Stack& st, const DevScene& S, uint32_t* lds_stack, uint8_t* oct_table, uint32_t* sel_table, uint32_t* spill, uint32_t total_threads, bool may_spill) {
-  const uint32_t tid = threadIdx.x;
-  st.lds = (lds_u32*)lds_stack + tid;
-  st.spill = (SOL_AS1 uint32_t*)spill + (blockIdx.x * SOL_WG + tid);
-  st.stride = total_threads;
-  st.depth = may_spill ? SOL_LDS_STACK : SOL_NO_SPILL;
-  sol_search_context<true>(st, S);
-  sol_fill_oct_table((lds_u8*)oct_table, tid, SOL_WG);
-  st.oct_table = (const lds_u8*)oct_table;
-  st.oct_table_on = true;
-#if SOL_SEL_TABLE
-  sol_fill_sel_table((lds_u32*)sel_table, tid, SOL_WG);
-  st.sel_table = (const lds_u32*)sel_table;
-  st.sel_table_on = true;
-#endif
-  __syncthreads();
-}
-
 }  // namespace
 
 template <bool ANY, bool SPILL, bool STRICT>
@@ -125,7 +107,7 @@ sol_query_kernel(const DevScene* __restrict__ Sp, const float4* __restrict__ ray
   __shared__ uint8_t oct_table[SOL_OCT_TABLE_BYTES];
   __shared__ __attribute__((aligned(16))) uint32_t sel_table[SOL_SEL_TABLE_DWORDS];  // (the node test's permute selectors, as in the render kernel)
   Stack st;
-  query_stack(st, S, lds_stack, oct_table, sel_table, spill, total_threads, SPILL);
+  wave_search_stack(st, S, lds_stack, SOL_LDS_STACK, SPILL, spill, total_threads, oct_table, sel_table);
   Counters cnt = {};
   Rng rng = {};
   QueryLane q;

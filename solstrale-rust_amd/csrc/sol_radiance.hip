@@ -2,11 +2,9 @@
 // path-traced colour along the caller's own rays. A path starts from a SolRay instead of the camera and is then the render's path: the
 // same search (sol_trace.h), the same vertex shading (shade_vertex, sol_path.h), the same RNG stream keyed by (seed, key, sample).
 //
-//  sol_radiance_kernel<SPILL, STRICT, ENV, LT> -- the render kernel's schedule (sol_render.hip): persistent waves, one path per lane with
-//    its state in registers, alternating between the search loop and the service block (settle the finished search, shade the vertex,
-//    fetch work from the wave's LDS reservoir, start the next path). A work item is (ray, chunk): the owning lane sums the chunk's
-//    samples in order and writes once - no float atomic. Paths differ in length by two orders of magnitude (glass), so the
-//    run-to-completion schedule of sol_query_kernel is wrong here.
+//  sol_radiance_kernel<SPILL, STRICT, ENV, LT> -- the persistent-wave schedule of sol_wave.h around a service block of its own, as
+//    sol_render_kernel is. A work item is (ray, chunk): the owning lane sums the chunk's samples in order and writes once - no float
+//    atomic. Paths differ in length by two orders of magnitude (glass), so the run-to-completion schedule of sol_query_kernel is wrong here.
 //  sol_radiance_resolve_kernel -- more than one chunk: adds a ray's chunk sums in chunk order, the association of sol_resolve_kernel.
 //  sol_camera_ray_keys_kernel -- the RNG key and the counter generate_path leaves behind for each pixel of a rectangle: with them a
 //    radiance query over sol_camera_rays' rays is the render's own sample, bit for bit.
@@ -18,8 +16,8 @@
 #include <hip/hip_runtime.h>
 
 #include "sol_launch.h"
-#include "sol_path.h"
 #include "sol_ray.h"
+#include "sol_wave.h"
 
 namespace {
 
@@ -39,26 +37,13 @@ sol_radiance_kernel(const DevScene* __restrict__ Sp, const RadianceParams P, con
                     sol_v4f* __restrict__ out, sol_v4f* __restrict__ partial, uint32_t* __restrict__ work_counter, uint32_t* __restrict__ spill) {
   const DevScene& S = *Sp;
   __shared__ uint32_t lds_stack[SOL_LDS_STACK * SOL_WG];
-  const uint32_t tid = threadIdx.x;
-  const uint32_t gtid = blockIdx.x * SOL_WG + tid;
-  const uint32_t lane = tid & 63u;
-  Stack st;
-  st.lds = (lds_u32*)lds_stack + tid;
-  st.spill = (SOL_AS1 uint32_t*)spill + gtid;
-  st.stride = P.total_threads;
-  st.depth = SPILL ? SOL_LDS_STACK : SOL_NO_SPILL;
-  sol_search_context<true>(st, S);
   __shared__ uint8_t oct_table[SOL_OCT_TABLE_BYTES];
-  sol_fill_oct_table((lds_u8*)oct_table, tid, SOL_WG);
-  st.oct_table = (const lds_u8*)oct_table;
-  st.oct_table_on = true;
-#if SOL_SEL_TABLE
   __shared__ __attribute__((aligned(16))) uint32_t sel_table[SOL_SEL_TABLE_DWORDS];
-  sol_fill_sel_table((lds_u32*)sel_table, tid, SOL_WG);
-  st.sel_table = (const lds_u32*)sel_table;
-  st.sel_table_on = true;
-#endif
-  __syncthreads();
+  __shared__ uint32_t reservoir[SOL_WG / 64][2];  // per wave: next reserved item, end of the reservation
+  const uint32_t lane = threadIdx.x & 63u;
+  Stack st;
+  wave_search_stack(st, S, lds_stack, SOL_LDS_STACK, SPILL, spill, P.total_threads, oct_table, sel_table);
+  volatile lds_u32* const res = wave_reservoir(reservoir);
   Counters cnt = {};
   const float inf = __builtin_huge_valf();
 
@@ -68,11 +53,9 @@ sol_radiance_kernel(const DevScene* __restrict__ Sp, const RadianceParams P, con
   Path p = {};
   Trav t;
   t.cur = REF_DONE;
-  __shared__ uint32_t reservoir[SOL_WG / 64][2];  // per wave: next reserved item, end of the reservation
-  if (lane == 0) { reservoir[tid >> 6][0] = 0u; reservoir[tid >> 6][1] = 0u; }
 
   for (;;) {
-    // ---- lanes whose search is over: the render kernel's service block (sol_render.hip), with the caller's interval at depth 0 ----
+    // ---- lanes whose search is over: the service block of sol_render_kernel, with the caller's ray and its interval at depth 0 ----
     const bool again = t.cur == REF_DONE && in_flight && sol_self_hit(p.from, t.h);  // (rule 8; a caller's ray leaves no primitive: depth > 0 only)
     // (STRICT) a refused needle hit: the lane searches the same ray again behind it - at depth 0 up to the ray's own upper end, as query_settle does
     if (STRICT && !again && t.cur == REF_DONE && in_flight && !trav_accept_or_restart(S, t, st) && p.depth == 0u) t.h.t = radiance_tmax(rays, index);
@@ -100,24 +83,9 @@ sol_radiance_kernel(const DevScene* __restrict__ Sp, const RadianceParams P, con
           }
         }
       }
-      // work fetch: the render kernel's reservoir - [next, end) of reserved items per wave in LDS, refilled 64 items at a time (64
-      // consecutive rays of one chunk) with ONE returning atomic; lanes take consecutive items from it by popcount prefix
+      // work fetch: the next item from the wave's reservoir (sol_wave.h) - 64 items, 64 consecutive rays of one chunk, per refill
       if (!again && !have_item) {
-        const unsigned long long need = sol_ballot(true);
-        const uint32_t leader = (uint32_t)__ffsll((long long)need) - 1u;
-        const uint32_t n_need = (uint32_t)__popcll(need), my = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-        volatile lds_u32* res = (volatile lds_u32*)reservoir[tid >> 6];  // (volatile: real LDS accesses in program order, as in the render kernel)
-        const uint32_t next = res[0], left = res[1] - next;
-        uint32_t fresh = 0;
-        if (n_need > left) {  // take what is left, then continue in a fresh block of 64
-          if (lane == leader) fresh = atomicAdd(work_counter, 64u);
-          fresh = __shfl(fresh, (int)leader);
-        }
-        if (lane == leader) {
-          res[0] = n_need > left ? fresh + (n_need - left) : next + n_need;
-          if (n_need > left) res[1] = fresh + 64u;
-        }
-        const uint32_t item = my < left ? next + my : fresh + (my - left);
+        const uint32_t item = wave_take_item(res, work_counter, lane);
         if (item >= P.n_items) break;  // no work left for this lane
         // item -> (ray, chunk), chunk-major: an aligned run of 64 items is 64 consecutive rays of one chunk
         const uint32_t pair = item >> 6, chunk = pair / P.n_groups;
@@ -159,22 +127,16 @@ sol_radiance_kernel(const DevScene* __restrict__ Sp, const RadianceParams P, con
         tmin = a.w; tmax = b.w;  // the depth-0 search runs over the ray's own interval; every later one over [RAY_MIN, +inf)
         alive = true;
       }
-      const float bt = t.bt;
-      const uint32_t bdfs = t.bdfs;
-      trav_begin<true>(t, p.o, p.d, tmin, tmax, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
-      if (STRICT && again) { t.bt = bt; t.bdfs = bdfs; }  // (a bound the needle rule had set for this ray stays)
+      trav_restart_world<STRICT>(t, S, p.o, p.d, tmin, tmax, again);  // (again: a bound the needle rule had set for this ray stays)
       in_flight = true;
     }
-    // ---- search: one step per turn for every lane that has one; the wave leaves for the service block under switch_below ----
+    // ---- search: one step per turn for every lane that has one, until the wave votes to leave for the service block ----
 #if SOL_LOOP_PRIO
     __builtin_amdgcn_s_setprio(SOL_LOOP_PRIO);
 #endif
     for (;;) {
       const bool act = t.cur != REF_DONE;
-      const unsigned long long am = sol_ballot(act);
-      if (am == 0ull) break;
-      const unsigned long long live = sol_ballot(true);
-      if (am != live && (uint32_t)__popcll(am) * 64u < P.switch_below * (uint32_t)__popcll(live)) break;
+      if (!wave_keeps_searching(act, P.switch_below)) break;
       trav_step_wave<false, false, STRICT>(S, t, act, st, p.rng, p.depth, cnt);
     }
 #if SOL_LOOP_PRIO

@@ -4,7 +4,8 @@
 //  sol_render_kernel -- ONE persistent kernel, one path per lane, state in registers. A wave alternates between the search loop
 //    (one resumable BVH step per turn, per-lane stack in LDS) and the service block (shade the closest hit, fetch work, generate
 //    the next camera ray); it leaves the search loop as soon as too few of its lanes are still searching while others wait
-//    (RenderParams::switch_below), unfinished searches keep their state across the service block. DESIGN.md 3.
+//    (RenderParams::switch_below), unfinished searches keep their state across the service block. DESIGN.md 3. The schedule's pieces -
+//    search context, work reservoir, leave vote - are sol_wave.h's, shared with sol_radiance.hip, sol_query.hip and sol_pool.hip.
 //  (The measured alternatives - a wave-private wavefront over a pool of path slots and a two-kernel wavefront, bit-identical
 //  frames, slower - live in sol_wavefront.hip, which only the -DSOL_AB_KERNELS build of the library carries.)
 //
@@ -13,7 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sol_launch.h"
-#include "sol_path.h"
+#include "sol_wave.h"
 
 // SPILL = false: built for scenes whose searches fit the LDS stack (sol_api.cpp picks it by the tree's depth): every stack access
 // is a plain LDS access, the spill branches and their waits fold away.
@@ -32,26 +33,15 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
   // the compiler re-loads fields with scalar loads where it needs them (2 spills; C1 +13 %, C2 +5 %, C3 +1.5 %).
   const DevScene& S = *Sp;
   __shared__ uint32_t lds_stack[SOL_LDS_STACK * SOL_WG];
+  __shared__ uint8_t oct_table[SOL_OCT_TABLE_BYTES];
+  __shared__ __attribute__((aligned(16))) uint32_t sel_table[SOL_SEL_TABLE_DWORDS];
+  __shared__ uint32_t reservoir[SOL_WG / 64][2];  // per wave: next reserved item, end of the reservation
+  __shared__ uint32_t from_lds[MEDIUM ? SOL_WG : 1];  // (MEDIUM kernels: Path::from of the ray being searched, below)
   const uint32_t tid = threadIdx.x;
-  const uint32_t gtid = blockIdx.x * SOL_WG + tid;
   const uint32_t lane = tid & 63u;
   Stack st;
-  st.lds = (lds_u32*)lds_stack + tid;
-  st.spill = (SOL_AS1 uint32_t*)spill + gtid;
-  st.stride = P.total_threads;
-  st.depth = SPILL ? SOL_LDS_STACK : SOL_NO_SPILL;
-  sol_search_context<true>(st, S);
-  __shared__ uint8_t oct_table[SOL_OCT_TABLE_BYTES];
-  sol_fill_oct_table((lds_u8*)oct_table, tid, SOL_WG);
-  st.oct_table = (const lds_u8*)oct_table;
-  st.oct_table_on = true;
-#if SOL_SEL_TABLE
-  __shared__ __attribute__((aligned(16))) uint32_t sel_table[SOL_SEL_TABLE_DWORDS];
-  sol_fill_sel_table((lds_u32*)sel_table, tid, SOL_WG);
-  st.sel_table = (const lds_u32*)sel_table;
-  st.sel_table_on = true;
-#endif
-  __syncthreads();
+  wave_search_stack(st, S, lds_stack, SOL_LDS_STACK, SPILL, spill, P.total_threads, oct_table, sel_table);
+  volatile lds_u32* const res = wave_reservoir(reservoir);
   Counters cnt = {};
   const float inf = __builtin_huge_valf();
 
@@ -63,15 +53,12 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
   Trav t;
   t.cur = REF_DONE;
   uint32_t item_rays0 = 0;  // (counted builds) ray count when the lane took its item
-  __shared__ uint32_t reservoir[SOL_WG / 64][2];  // per wave: next reserved item, end of the reservation
-  __shared__ uint32_t from_lds[MEDIUM ? SOL_WG : 1];  // (MEDIUM kernels: Path::from of the ray being searched, below)
-  if (lane == 0) { reservoir[tid >> 6][0] = 0u; reservoir[tid >> 6][1] = 0u; }
 
   for (;;) {
     // ---- lanes whose search is over: shade the vertex, then start the next ray of the path / sample / item ----
     // (STRICT) a finished search whose closest hit is a triangle the consistency rule refuses: the lane searches again, behind that hit
     // (rule 8) a finished search whose closest hit is the flat primitive the ray had just left is not shaded: the same ray is searched again behind
-    // that hit (through the one trav_begin at the end of this block: a second call site cost the MEDIUM kernels 28 spilled registers)
+    // that hit (through the one search start at the end of this block: a second call site cost the MEDIUM kernels 28 spilled registers)
     // (MEDIUM kernels sit at the 128-register limit: Path::from waits in LDS while the ray is searched - one dword per lane, written when a ray is made, read
     // when its search is over - instead of costing 26 spilled registers)
     const bool again = t.cur == REF_DONE && in_flight && sol_self_hit(MEDIUM ? from_lds[tid] : p.from, t.h);
@@ -105,28 +92,10 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
           }
         }
       }
-      // work fetch. The wave keeps a reservoir [next, end) of reserved items in LDS and refills it 64 items at a time (one
-      // aligned 8x8 pixel block of one chunk) with ONE returning atomic; lanes take consecutive items from it by popcount
-      // prefix. The wave thus waits for the global counter (1-3 us under load, ~88 dequeues/us per address) once per 64
-      // items instead of once per service pass.
+      // work fetch: the next item of the work order from the wave's reservoir (sol_wave.h) - 64 items, one aligned 8x8 pixel block of one
+      // chunk, per refill
       if (!again && !have_item) {
-        const unsigned long long need = sol_ballot(true);
-        const uint32_t leader = (uint32_t)__ffsll((long long)need) - 1u;
-        const uint32_t n_need = (uint32_t)__popcll(need), my = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-        // volatile: the leader's stores and every lane's loads must stay real LDS accesses in program order (one wave's LDS
-        // operations execute in order; without it the compiler may forward a stale value to the non-leader lanes)
-        volatile lds_u32* res = (volatile lds_u32*)reservoir[tid >> 6];
-        const uint32_t next = res[0], left = res[1] - next;
-        uint32_t fresh = 0;
-        if (n_need > left) {  // take what is left, then continue in a fresh block of 64
-          if (lane == leader) fresh = atomicAdd(work_counter, 64u);
-          fresh = __shfl(fresh, (int)leader);
-        }
-        if (lane == leader) {
-          res[0] = n_need > left ? fresh + (n_need - left) : next + n_need;
-          if (n_need > left) res[1] = fresh + 64u;
-        }
-        const uint32_t item = my < left ? next + my : fresh + (my - left);
+        const uint32_t item = wave_take_item(res, work_counter, lane);
         if (item >= P.n_items) break;  // no work left for this lane
         // The fine tail: the last pairs of the work order are handed out sample by sample, so that the launch does not end with
         // every lane inside a 16-sample item of its own (~2.5 ms on C3, 4 ms of a launch whatever its length) but inside a
@@ -155,23 +124,16 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
       }
       // world.hit(ray, RAY_INTERVAL) (src/renderer/mod.rs:165)
       if (MEDIUM && !again) from_lds[tid] = p.from;  // (of the ray made above: scattered by shade_vertex, or a camera ray)
-      const float bt = t.bt;
-      const uint32_t bdfs = t.bdfs;
-      trav_begin<true>(t, p.o, p.d, tmin, inf, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
-      if (STRICT && again) { t.bt = bt; t.bdfs = bdfs; }  // (a bound the needle rule had set for this ray stays)
+      trav_restart_world<STRICT>(t, S, p.o, p.d, tmin, inf, again);  // (again: a bound the needle rule had set for this ray stays)
       in_flight = true;
     }
-    // ---- search: one step per turn for every lane that has one. The wave leaves for the shading block when too few of
-    // its lanes are still searching while others wait (P.switch_below 64ths of the live lanes; 0: when none is searching).
+    // ---- search: one step per turn for every lane that has one, until the wave votes to leave for the service block (sol_wave.h) ----
 #if SOL_LOOP_PRIO
     __builtin_amdgcn_s_setprio(SOL_LOOP_PRIO);
 #endif
     for (;;) {
       const bool act = t.cur != REF_DONE;
-      const unsigned long long am = sol_ballot(act);
-      if (am == 0ull) break;
-      const unsigned long long live = sol_ballot(true);
-      if (am != live && (uint32_t)__popcll(am) * 64u < P.switch_below * (uint32_t)__popcll(live)) break;
+      if (!wave_keeps_searching(act, P.switch_below)) break;
       trav_step_wave<COUNT, MEDIUM, STRICT>(S, t, act, st, p.rng, p.depth, cnt);
     }
 #if SOL_LOOP_PRIO

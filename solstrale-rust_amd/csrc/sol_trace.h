@@ -316,6 +316,19 @@ DEV void trav_begin(Trav& t, f3 o, f3 d, float tmin, float tmax, uint32_t root, 
   if (WIDE) t.inv = mk3(__builtin_amdgcn_fmed3f(t.inv.x, -SOL_INV_CLAMP, SOL_INV_CLAMP), __builtin_amdgcn_fmed3f(t.inv.y, -SOL_INV_CLAMP, SOL_INV_CLAMP),
                         __builtin_amdgcn_fmed3f(t.inv.z, -SOL_INV_CLAMP, SOL_INV_CLAMP));
 }
+// A search of the whole scene: the 7-wide tree from its root.
+DEV void trav_begin_world(Trav& t, const DevScene& S, f3 o, f3 d, float tmin, float tmax, int sp_base = 0) {
+  trav_begin<true>(t, o, d, tmin, tmax, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, sp_base);
+}
+// The same for a lane whose last search may have been of this ray: `again` (STRICT kernels only) - the ray is searched again, over another
+// interval, and a bound the needle rule had set for it (Trav::bt, bdfs) stays.
+template <bool STRICT>
+DEV void trav_restart_world(Trav& t, const DevScene& S, f3 o, f3 d, float tmin, float tmax, bool again = true, int sp_base = 0) {
+  const float bt = t.bt;
+  const uint32_t bdfs = t.bdfs;
+  trav_begin_world(t, S, o, d, tmin, tmax, sp_base);
+  if (STRICT && again) { t.bt = bt; t.bdfs = bdfs; }
+}
 
 // Decodes child `i` (compile-time) of a wide node and tests it; sets bit i of `hits` when the child must be visited.
 // The slab test runs in t-space: plane q of an axis is crossed at  t = A + q * B  with  A = (origin - o) * inv,
@@ -722,7 +735,7 @@ DEV bool trav_accept_or_restart(const DevScene& S, Trav& t, const Stack& st) {
   const float bt = t.h.t;
   const uint32_t bdfs = t.h.dfs;
   // (the lower end of the interval stays what it was: RAY_MIN, or the bound of rule 8 - sol_path.h, sol_self_hit)
-  trav_begin<true>(t, t.o, t.d, t.tmin, __builtin_huge_valf(), S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
+  trav_begin_world(t, S, t.o, t.d, t.tmin, __builtin_huge_valf());
   t.bt = bt;
   t.bdfs = bdfs;
   return false;
@@ -733,14 +746,11 @@ template <bool COUNT, bool MEDIUM>
 DEV void closest_hit(const DevScene& S, f3 o, f3 d, float tmin, float tmax, Hit& h, const Stack& st, int sp_base, const Rng& rng,
                      uint32_t depth, Counters& cnt, uint32_t from = 0u) {
   Trav t;
-  trav_begin<true>(t, o, d, tmin, tmax, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, sp_base);
+  trav_begin_world(t, S, o, d, tmin, tmax, sp_base);
   for (int guard = 0; guard < 64; ++guard) {
     while (t.cur != REF_DONE) trav_step<COUNT, MEDIUM, true>(S, t, st, rng, depth, cnt);
     if (from != 0u && (0x80000000u | t.h.dfs) == from && SOL_REF_KIND(t.h.ref) != SOL_REF_NONE) {  // (fp32 rule 8, sol_path.h sol_self_hit: searched again behind that hit)
-      const float bt = t.bt;
-      const uint32_t bdfs = t.bdfs;
-      trav_begin<true>(t, o, d, __uint_as_float(__float_as_uint(t.h.t) + 1u), tmax, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, sp_base);
-      t.bt = bt; t.bdfs = bdfs;  // (a bound the needle rule had set stays)
+      trav_restart_world<true>(t, S, o, d, __uint_as_float(__float_as_uint(t.h.t) + 1u), tmax, true, sp_base);  // (a bound the needle rule had set stays)
       continue;
     }
     if (!(S.tri_delta > 0.0f) || trav_accept_or_restart(S, t, st)) break;

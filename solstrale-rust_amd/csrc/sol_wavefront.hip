@@ -185,8 +185,7 @@ sol_render_pool_kernel(const DevScene S, const RenderParams P, float* __restrict
               rng_medium.k0 = __float_as_uint(r2.w); rng_medium.k1 = __float_as_uint(r3.w);
               depth_medium = __float_as_uint(r1.w) >> 8;
             }
-            trav_begin<true>(t, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), RAY_MIN_F, inf, S.wroot, S.rxmin, S.rxmax, S.rymin,
-                       S.rymax, S.rzmin, S.rzmax, 0);
+            trav_begin_world(t, S, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), RAY_MIN_F, inf);
             my_from = __float_as_uint(rec[6 * NS + my_slot].y);
             have = true;
           }
@@ -197,7 +196,7 @@ sol_render_pool_kernel(const DevScene S, const RenderParams P, float* __restrict
       if (have) {
         for (int k = 0; k < SOL_TRAV_BURST && t.cur != REF_DONE; ++k) trav_step<COUNT, MEDIUM>(S, t, st, rng_medium, depth_medium, cnt);
         if (t.cur == REF_DONE && sol_self_hit(my_from, t.h)) {  // (rule 8, sol_path.h: searched again behind the primitive the ray left)
-          trav_begin<true>(t, t.o, t.d, sol_behind(t.h.t), inf, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
+          trav_begin_world(t, S, t.o, t.d, sol_behind(t.h.t), inf);
         } else if (t.cur == REF_DONE) {
           rec[6 * NS + my_slot] = make_float4(t.h.t, __uint_as_float(t.h.ref), t.h.u, t.h.v);
           if (COUNT) cnt.rays++;
@@ -423,8 +422,7 @@ sol_wf_trace_kernel(const DevScene S, const RenderParams P, WfCounters* __restri
             rng_medium.k0 = __float_as_uint(r2.w); rng_medium.k1 = __float_as_uint(r3.w);
             depth_medium = __float_as_uint(r1.w) >> 8;
           }
-          trav_begin<true>(t, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), RAY_MIN_F, inf, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax,
-                     S.rzmin, S.rzmax, 0);
+          trav_begin_world(t, S, mk3(r0.x, r0.y, r0.z), mk3(r1.x, r1.y, r1.z), RAY_MIN_F, inf);
           my_from = __float_as_uint(rec[6 * NS + my_slot].y);
           have = true;
           need = false;
@@ -443,7 +441,7 @@ sol_wf_trace_kernel(const DevScene S, const RenderParams P, WfCounters* __restri
     if (have) {
       for (int k = 0; k < SOL_TRAV_BURST && t.cur != REF_DONE; ++k) trav_step<COUNT, MEDIUM>(S, t, st, rng_medium, depth_medium, cnt);
       if (t.cur == REF_DONE && sol_self_hit(my_from, t.h)) {  // (rule 8, sol_path.h: searched again behind the primitive the ray left)
-        trav_begin<true>(t, t.o, t.d, sol_behind(t.h.t), inf, S.wroot, S.rxmin, S.rxmax, S.rymin, S.rymax, S.rzmin, S.rzmax, 0);
+        trav_begin_world(t, S, t.o, t.d, sol_behind(t.h.t), inf);
       } else if (t.cur == REF_DONE) {
         rec[6 * NS + my_slot] = make_float4(t.h.t, __uint_as_float(t.h.ref), t.h.u, t.h.v);
         if (COUNT) cnt.rays++;
