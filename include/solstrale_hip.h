@@ -691,8 +691,8 @@ int sol_query(SolScene* scene, int mode, const SolRay* rays, size_t n, void* out
 int sol_camera_rays(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* rays_dev);
 
 /* ---- radiance queries (EXTENSION, not in the reference) -------------------------------------------------------------------
- * "How much light arrives along this ray?" - the path-traced colour along the caller's own rays: light probes and irradiance volumes,
- * lightmap texels, reflection captures, a second viewpoint without a second handle. Rays are SolRay rows, valid by the rule of the ray
+ * "How much light arrives along this ray?" - the path-traced colour along the caller's own rays: reflection captures, a second viewpoint
+ * without a second handle; for light probes, irradiance volumes and lightmap texels see the irradiance queries below. Rays are SolRay rows, valid by the rule of the ray
  * queries above and decided by the kernel itself before any search; an invalid ray answers (0, 0, 0, samples = 0).
  *   Paths.    For a valid ray i, each sample s in [first_sample, first_sample + samples) is one path: the render's RNG stream of
  *             (seed, key, s) with its counter set to first_draw, where (key, first_draw) is the ray's SolRayKey (pixel, first_draw) or, with
@@ -724,6 +724,44 @@ int sol_radiance(SolScene* scene, const SolRay* rays, const SolRayKey* keys, siz
  * rejection rounds of the lens disc). Asynchronous on the scene's stream. SOL_EINVAL: a null pointer, an empty rectangle or one that
  * leaves the frame. */
 int sol_camera_ray_keys(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* keys_dev);
+
+/* ---- irradiance queries (EXTENSION, not in the reference) -----------------------------------------------------------------
+ * "How much light arrives at this point?" - the hemisphere (or sphere) gather a lightmap texel, a light probe or an irradiance volume needs:
+ * a radiance query whose every sample draws a fresh direction on the device, so the caller uploads n points, not n x samples rays. (sol_gather
+ * is the multi-rank image gather; hence the name.)
+ *   Points.   A point is a SolRay row read as (position xyz, tmin, normal xyz, tmax), valid by the ray queries' rule exactly as it stands: every
+ *             word finite (tmax may be +inf), the normal not zero, 0 <= tmin <= tmax. The normal need not be unit length (its squared length
+ *             must be a finite, normal fp32 number). An invalid point answers (0, 0, 0, samples = 0), decided before any search.
+ *   Paths.    For a valid point i, each sample s in [first_sample, first_sample + samples) is one path: the RNG stream of (seed, key, s) with
+ *             its counter set to first_draw, (key, first_draw) by sol_radiance's rules (the point's SolRayKey or, with keys == NULL,
+ *             (key_base + i wrapping, the configuration's first_draw)). The direction is drawn from that generator:
+ *               SOL_IRRADIANCE_COSINE  cosine-weighted about the normal, the two draws of a Lambertian vertex (the reference's CosinePdf::generate);
+ *               SOL_IRRADIANCE_SPHERE  uniform over the sphere (random_unit_vector: three draws per rejection round); the normal only counts
+ *                                      towards validity.
+ *             The path is then sol_radiance's path from (position, direction, [tmin, tmax]) with the generator where the direction left it:
+ *             the handle's current shader, max_depth, sol_env_sampling and sol_light_sampling modes.
+ *   Sums.     SolRadiance holds SUMS, in sol_radiance's association (chunks of 16 samples counted from first_sample).
+ *             COSINE: irradiance = pi x sum / samples.     SPHERE: mean radiance over the sphere = sum / samples.
+ *   Rays.     sol_irradiance_rays (samples must be 1) writes, for sample first_sample, one SolRay per point - position, tmin, the drawn direction,
+ *             tmax - and one SolRayKey - the key and the generator's counter after the direction. An invalid point gives an all-zero ray (itself
+ *             invalid) beside (key, first_draw).
+ *   Identity. With the same scene, seed and modes, sol_radiance_dev(rays_out, keys_out, samples = 1, first_sample = s) equals sample s's
+ *             contribution to sol_irradiance_dev bit for bit: a caller can project the samples onto a basis of their own (spherical harmonics).
+ *   Neutral.  As sol_radiance: neither the accumulator, the auxiliary planes, the render's work counter, the partition, an adaptive session nor
+ *             SolStats is touched. Irradiance and radiance queries share their scratch; calls on one handle are ordered by its stream.
+ * SOL_EINVAL (sol_last_error names the reason), in sol_radiance's order and before the device is looked for: a null scene or configuration; a
+ * wrong size; samples == 0 (sol_irradiance_rays: samples != 1), or first_sample + samples beyond 2^32 - 16; n above 2^31; an unknown mode; a
+ * scene with a constant medium; with n > 0 a null point or output pointer. n == 0 succeeds and touches nothing. */
+enum { SOL_IRRADIANCE_COSINE = 0, SOL_IRRADIANCE_SPHERE = 1 };
+/* size = sizeof(SolIrradianceConfig) = 32: size 0, samples 4, first_sample 8, first_draw 12, seed 16, key_base 24, mode 28 */
+typedef struct SolIrradianceConfig { uint32_t size, samples, first_sample, first_draw; uint64_t seed; uint32_t key_base, mode; } SolIrradianceConfig;
+/* Device pointers (n SolRay points, n SolRayKey or NULL, n SolRadiance out, on the scene's device), on the scene's stream, asynchronous. */
+int sol_irradiance_dev(SolScene* scene, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_irradiance(SolScene* scene, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolRadiance* out);
+/* Device pointers (n SolRay points, n SolRayKey or NULL; n SolRay and n SolRayKey out), on the scene's stream, asynchronous. */
+int sol_irradiance_rays(SolScene* scene, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* rays_out_dev,
+                        void* keys_out_dev);
 
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment

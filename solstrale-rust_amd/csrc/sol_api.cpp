@@ -487,42 +487,58 @@ int sol_camera_rays(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t
 
 }  // extern "C"
 
-// ---- radiance queries (include/solstrale_hip.h; kernels: sol_radiance.hip) ----
+// ---- radiance queries (include/solstrale_hip.h; kernels: sol_radiance.hip) and irradiance queries ----
 namespace {
 constexpr size_t RADIANCE_STAGE_RAYS = (size_t)1 << 20;    // the host route stages at most this many rays at a time (32 + 8 + 16 bytes each)
 
+// An irradiance query is a radiance query whose samples draw their own directions: one configuration layout - the last word is `reserved`
+// for the one and `mode` for the other -, one set of checks, one launch.
+static_assert(sizeof(SolIrradianceConfig) == sizeof(SolRadianceConfig) && offsetof(SolIrradianceConfig, samples) == offsetof(SolRadianceConfig, samples) &&
+              offsetof(SolIrradianceConfig, first_sample) == offsetof(SolRadianceConfig, first_sample) &&
+              offsetof(SolIrradianceConfig, first_draw) == offsetof(SolRadianceConfig, first_draw) && offsetof(SolIrradianceConfig, seed) == offsetof(SolRadianceConfig, seed) &&
+              offsetof(SolIrradianceConfig, key_base) == offsetof(SolRadianceConfig, key_base) && offsetof(SolIrradianceConfig, mode) == offsetof(SolRadianceConfig, reserved),
+              "SolIrradianceConfig is SolRadianceConfig with `mode` in the place of `reserved`");
+enum RadianceKind { RADIANCE = 0, IRRADIANCE = 1, IRRADIANCE_RAYS = 2 };  // (the last: sol_irradiance_rays, one sample only)
+SolRadianceConfig radiance_config_of(const SolIrradianceConfig& c) { return SolRadianceConfig{c.size, c.samples, c.first_sample, c.first_draw, c.seed, c.key_base, c.mode}; }
+
 // What both routes refuse; nothing here needs a device. The part that needs no handle either is a function that is not given one:
 // behind a non-null scene pointer the configuration and n are judged before the handle is read for the first time.
-int radiance_config_check(const char* fn, size_t n, const SolRadianceConfig* cfg) {
+int radiance_config_check(const char* fn, RadianceKind kind, size_t n, const SolRadianceConfig* cfg) {
+  const char* rec = kind == RADIANCE ? "SolRadianceConfig" : "SolIrradianceConfig";
   if (!cfg) return sol_fail(SOL_EINVAL, "%s: null configuration", fn);
-  if (cfg->size != sizeof(SolRadianceConfig)) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.size is %u, not %zu", fn, cfg->size, sizeof(SolRadianceConfig));
-  if (cfg->reserved != 0u) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.reserved must be 0", fn);
-  if (cfg->samples == 0u) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.samples is 0", fn);
+  if (cfg->size != sizeof(SolRadianceConfig)) return sol_fail(SOL_EINVAL, "%s: %s.size is %u, not %zu", fn, rec, cfg->size, sizeof(SolRadianceConfig));
+  if (kind == RADIANCE && cfg->reserved != 0u) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.reserved must be 0", fn);
+  if (cfg->samples == 0u) return sol_fail(SOL_EINVAL, "%s: %s.samples is 0", fn, rec);
+  if (kind == IRRADIANCE_RAYS && cfg->samples != 1u) return sol_fail(SOL_EINVAL, "%s: %s.samples is %u: the rays of one sample (first_sample) per call", fn, rec, cfg->samples);
   if ((uint64_t)cfg->first_sample + cfg->samples > 0xFFFFFFF0ull) return sol_fail(SOL_EINVAL, "%s: first_sample + samples goes beyond 2^32 - 16", fn);
-  if (n > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: %zu rays in one call (at most 2^31)", fn, n);
+  if (n > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: %zu %s in one call (at most 2^31)", fn, n, kind == RADIANCE ? "rays" : "points");
+  if (kind != RADIANCE && cfg->reserved != (uint32_t)SOL_IRRADIANCE_COSINE && cfg->reserved != (uint32_t)SOL_IRRADIANCE_SPHERE)
+    return sol_fail(SOL_EINVAL, "%s: unknown mode %u (SOL_IRRADIANCE_COSINE or SOL_IRRADIANCE_SPHERE)", fn, cfg->reserved);
   return SOL_OK;
 }
-// *go = false: nothing to do (n == 0, which succeeds on any scene and touches nothing).
-int radiance_check(const SolScene* s, const char* fn, const void* rays, size_t n, const SolRadianceConfig* cfg, const void* out, bool* go) {
+// *go = false: nothing to do (n == 0, which succeeds on any scene and touches nothing). out2: the second output of sol_irradiance_rays.
+int radiance_check(const SolScene* s, const char* fn, RadianceKind kind, const void* rays, size_t n, const SolRadianceConfig* cfg, const void* out, const void* out2,
+                   bool* go) {
   *go = false;
   if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if (const int rc = radiance_config_check(fn, n, cfg)) return rc;
+  if (const int rc = radiance_config_check(fn, kind, n, cfg)) return rc;
   if (n == 0) return SOL_OK;
   if (s->has_medium)
     return sol_fail(SOL_EINVAL, "%s: the scene has a constant medium - the render kernels for media have no register left for a radiance lane's ray; not supported yet", fn);
-  if (!rays || !out) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? "ray" : "output");
+  if (!rays || !out || !out2) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? (kind == RADIANCE ? "ray" : "point") : "output");
   *go = true;
   return SOL_OK;
 }
 
 // n <= 2^31 rays (and keys, or null) in device memory, on the scene's stream. key_base: the key of ray 0 of THIS batch when keys is null.
-int radiance_launch(SolScene* s, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
+// gather: the rows are the points of an irradiance query, cfg.reserved its mode.
+int radiance_launch(SolScene* s, bool gather, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
   int rc;
   if ((rc = sol_scene_to_device(s))) return rc;
   // the estimator a render would run now (sol_render_impl): the ENV / LT builds under the path-tracing shader only
   const bool env = s->env_is && s->S.shader == SOL_SHADER_PATH_TRACING;
   const bool lt = s->light_mode != 0u && s->S.shader == SOL_SHADER_PATH_TRACING && s->S.n_lights > 1u;
-  const int bpc = sol_radiance_blocks_per_cu(s->strict_triangles, env, lt);
+  const int bpc = sol_radiance_blocks_per_cu(gather, s->strict_triangles, env, lt);
   const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
   if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
   const uint32_t total_chunks = (uint32_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
@@ -543,6 +559,7 @@ int radiance_launch(SolScene* s, const void* rays_dev, const void* keys_dev, siz
     P.first_draw = cfg.first_draw;
     P.switch_below = s->switch_below;
     P.direct = total_chunks == 1 ? 1u : 0u;
+    P.mode = gather ? cfg.reserved : 0u;
     const char* rays_at = (const char*)rays_dev + at * sizeof(SolRay);
     const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
     char* out_at = (char*)out_dev + at * sizeof(SolRadiance);
@@ -557,10 +574,27 @@ int radiance_launch(SolScene* s, const void* rays_dev, const void* keys_dev, siz
       if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
       P.total_threads = grid * SOL_WG;
       HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
-      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial.get(), s->rad_work.get(),
+      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, gather, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial.get(), s->rad_work.get(),
                                   s->rad_spill.get(), grid, s->stream));
       if (!P.direct) HIP_TRY(sol_launch_radiance_resolve(P, rays_at, s->rad_partial.get(), out_at, cfg.samples, c0 != 0, s->stream));
     }
+  }
+  return SOL_OK;
+}
+
+// The host route of both: arrays staged through buffers the handle owns, RADIANCE_STAGE_RAYS rows at a time; blocks.
+int radiance_staged(SolScene* s, bool gather, const SolRay* rays, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, SolRadiance* out) {
+  int rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
+  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap))) return rc;
+  for (size_t at = 0; at < n; at += cap) {  // (answers are per ray: the split changes nothing)
+    const size_t k = std::min(cap, n - at);
+    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
+    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
+    if ((rc = radiance_launch(s, gather, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get()))) return rc;
+    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
 }
@@ -571,26 +605,58 @@ extern "C" {
 int sol_radiance_dev(SolScene* s, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig* cfg, void* out_dev) {
   int rc;
   bool go;
-  if ((rc = radiance_check(s, "sol_radiance_dev", rays_dev, n, cfg, out_dev, &go)) || !go || (rc = query_device_check())) return rc;
+  if ((rc = radiance_check(s, "sol_radiance_dev", RADIANCE, rays_dev, n, cfg, out_dev, out_dev, &go)) || !go || (rc = query_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
-  return radiance_launch(s, rays_dev, keys_dev, n, *cfg, cfg->key_base, out_dev);
+  return radiance_launch(s, false, rays_dev, keys_dev, n, *cfg, cfg->key_base, out_dev);
 }
 
 int sol_radiance(SolScene* s, const SolRay* rays, const SolRayKey* keys, size_t n, const SolRadianceConfig* cfg, SolRadiance* out) {
   int rc;
   bool go;
-  if ((rc = radiance_check(s, "sol_radiance", rays, n, cfg, out, &go)) || !go || (rc = query_device_check())) return rc;
+  if ((rc = radiance_check(s, "sol_radiance", RADIANCE, rays, n, cfg, out, out, &go)) || !go || (rc = query_device_check())) return rc;
+  return radiance_staged(s, false, rays, keys, n, *cfg, out);
+}
+
+int sol_irradiance_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = radiance_check(s, "sol_irradiance_dev", IRRADIANCE, points_dev, n, config ? &cfg : nullptr, out_dev, out_dev, &go)) || !go || (rc = query_device_check()))
+    return rc;
   HIP_TRY(hipSetDevice(s->device));
-  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
-  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap))) return rc;
-  for (size_t at = 0; at < n; at += cap) {  // (answers are per ray: the split changes nothing)
-    const size_t k = std::min(cap, n - at);
-    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
-    if ((rc = radiance_launch(s, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, *cfg, cfg->key_base + (uint32_t)at, s->rad_out.get()))) return rc;
-    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
+  return radiance_launch(s, true, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev);
+}
+
+int sol_irradiance(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolRadiance* out) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = radiance_check(s, "sol_irradiance", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
+  return radiance_staged(s, true, points, keys, n, cfg, out);
+}
+
+int sol_irradiance_rays(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* rays_out_dev,
+                        void* keys_out_dev) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = radiance_check(s, "sol_irradiance_rays", IRRADIANCE_RAYS, points_dev, n, config ? &cfg : nullptr, rays_out_dev, keys_out_dev, &go)) || !go ||
+      (rc = query_device_check()))
+    return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  // (no search: neither the scene's device mirror nor any scratch is needed - the generator and the point are all there is)
+  RadianceParams P{};
+  P.n_rays = (uint32_t)n;  // (n == 2^31 fits; the grid is n / 256 blocks)
+  P.first_sample = cfg.first_sample;
+  P.end_sample = cfg.first_sample + 1u;
+  P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
+  P.key_base = cfg.key_base;
+  P.first_draw = cfg.first_draw;
+  P.mode = cfg.reserved;
+  HIP_TRY(sol_launch_irradiance_rays(P, points_dev, keys_dev, rays_out_dev, keys_out_dev, s->stream));
   return SOL_OK;
 }
 

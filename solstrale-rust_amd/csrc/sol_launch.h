@@ -62,10 +62,14 @@ struct RadianceParams {
   uint32_t switch_below;       // as RenderParams::switch_below
   uint32_t total_threads;      // grid * SOL_WG (spill stack stride)
   uint32_t direct;             // 1: the call has one chunk, the kernel writes the answers itself; 0: chunk sums into `partial` [chunk][n_groups * 64]
+  uint32_t mode;               // irradiance queries (gather launches only): SOL_IRRADIANCE_COSINE or SOL_IRRADIANCE_SPHERE
 };
-hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool may_spill, bool strict, bool env, bool lt, const void* rays, const void* keys,
-                               void* out, void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream);
-int sol_radiance_blocks_per_cu(bool strict, bool env, bool lt);
+// gather: an irradiance query - the rows are points (position, tmin, normal, tmax) and each sample draws its own direction (P.mode)
+hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool gather, bool may_spill, bool strict, bool env, bool lt, const void* rays,
+                               const void* keys, void* out, void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream);
+int sol_radiance_blocks_per_cu(bool gather, bool strict, bool env, bool lt);
+// one thread per point of an irradiance query with one sample (P.first_sample): the ray that sample starts with and the key it goes on from
+hipError_t sol_launch_irradiance_rays(const RadianceParams& P, const void* points, const void* keys, void* rays_out, void* keys_out, hipStream_t stream);
 // the chunk sums of one launch added in chunk order onto 0 (or, accumulate, onto what `out` holds) and written with `samples`
 hipError_t sol_launch_radiance_resolve(const RadianceParams& P, const void* rays, const void* partial, void* out, uint32_t samples, bool accumulate,
                                        hipStream_t stream);

@@ -2,10 +2,13 @@
 // path-traced colour along the caller's own rays. A path starts from a SolRay instead of the camera and is then the render's path: the
 // same search (sol_trace.h), the same vertex shading (shade_vertex, sol_path.h), the same RNG stream keyed by (seed, key, sample).
 //
-//  sol_radiance_kernel<SPILL, STRICT, ENV, LT> -- the persistent-wave schedule of sol_wave.h around a service block of its own, as
+//  sol_radiance_kernel<SPILL, STRICT, ENV, LT, GATHER> -- the persistent-wave schedule of sol_wave.h around a service block of its own, as
 //    sol_render_kernel is. A work item is (ray, chunk): the owning lane sums the chunk's samples in order and writes once - no float
 //    atomic. Paths differ in length by two orders of magnitude (glass), so the run-to-completion schedule of sol_query_kernel is wrong here.
 //  sol_radiance_resolve_kernel -- more than one chunk: adds a ray's chunk sums in chunk order, the association of sol_resolve_kernel.
+//  sol_irradiance_rays_kernel -- irradiance queries are sol_radiance_kernel<.., GATHER>: the row is a point with its normal and every
+//    sample draws a direction of its own (irradiance_direction, sol_ray.h) where a radiance path copies the caller's. This kernel writes, for
+//    one sample, those rays and the keys the paths go on from.
 //  sol_camera_ray_keys_kernel -- the RNG key and the counter generate_path leaves behind for each pixel of a rectangle: with them a
 //    radiance query over sol_camera_rays' rays is the render's own sample, bit for bit.
 //
@@ -31,7 +34,7 @@ DEV void radiance_store(sol_v4f* __restrict__ p, f3 sum, uint32_t w) {
 
 }  // namespace
 
-template <bool SPILL, bool STRICT, bool ENV, bool LT>
+template <bool SPILL, bool STRICT, bool ENV, bool LT, bool GATHER>
 __global__ void __launch_bounds__(SOL_WG, SOL_V1_MIN_WAVES)
 sol_radiance_kernel(const DevScene* __restrict__ Sp, const RadianceParams P, const float4* __restrict__ rays, const uint2* __restrict__ keys,
                     sol_v4f* __restrict__ out, sol_v4f* __restrict__ partial, uint32_t* __restrict__ work_counter, uint32_t* __restrict__ spill) {
@@ -117,7 +120,9 @@ sol_radiance_kernel(const DevScene* __restrict__ Sp, const RadianceParams P, con
         rng_init(p.rng, P.seed_lo, P.seed_hi, key, s);
         p.rng.ctr = ctr;
         p.o = mk3(a.x, a.y, a.z);
-        p.d = mk3(b.x, b.y, b.z);
+        // (GATHER) an irradiance query: the row is a point and b.xyz its normal - the sample draws its direction here, while only the row and
+        // the generator are live, and the path goes on from the counter the draws leave
+        p.d = GATHER ? irradiance_direction(P.mode, mk3(b.x, b.y, b.z), p.rng) : mk3(b.x, b.y, b.z);
         p.A = mk3(1.f, 1.f, 1.f);
         p.C = mk3(inf, inf, inf);
         p.acc_len = 0.0f;
@@ -182,26 +187,61 @@ __global__ void __launch_bounds__(256) sol_camera_ray_keys_kernel(const DevScene
   keys[i] = make_uint2((y0 + y) * S.width + (x0 + x), p.rng.ctr);
 }
 
-// ---- launch wrappers (called from sol_api.cpp) ----
-// Built: the default estimator with and without the spill tail, plain and STRICT (4); the ENV / LT estimators SPILL-capable only, plain and
-// STRICT (6) - a scene whose tree fits the LDS stack runs them with a spill area it never touches.
-// The variant table: which of them the run-time flags name - the launch and the occupancy query both ask here.
-using RadianceKernel = void (*)(const DevScene*, const RadianceParams, const float4*, const uint2*, sol_v4f*, sol_v4f*, uint32_t*, uint32_t*);
-template <bool SPILL, bool ENV, bool LT>
-static RadianceKernel radiance_variant_of(bool strict) { return strict ? sol_radiance_kernel<SPILL, true, ENV, LT> : sol_radiance_kernel<SPILL, false, ENV, LT>; }
-static RadianceKernel sol_radiance_variant(bool spill, bool strict, bool env, bool lt) {
-  if (env) return lt ? radiance_variant_of<true, true, true>(strict) : radiance_variant_of<true, true, false>(strict);
-  if (lt) return radiance_variant_of<true, false, true>(strict);
-  return spill ? radiance_variant_of<true, false, false>(strict) : radiance_variant_of<false, false, false>(strict);
+// One thread per point of an irradiance query with one sample (P.first_sample): the ray that sample's path starts with - the point's position
+// and interval around the drawn direction - and the key it goes on from, (key, the counter after the direction): a radiance query over them
+// with samples = 1 and first_sample = P.first_sample is that sample's contribution, bit for bit (the same generator, irradiance_direction,
+// from the same state). An invalid point gives an all-zero ray, itself invalid, beside (key, first_draw).
+__global__ void __launch_bounds__(256) sol_irradiance_rays_kernel(const RadianceParams P, const float4* __restrict__ points, const uint2* __restrict__ keys,
+                                                                  float4* __restrict__ rays_out, uint2* __restrict__ keys_out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= P.n_rays) return;
+  const float4 a = ldg_f4(points + (size_t)i * 2u), b = ldg_f4(points + (size_t)i * 2u + 1u);
+  uint32_t key = P.key_base + i, ctr = P.first_draw;
+  if (keys) { const uint2 k = keys[i]; key = k.x; ctr = k.y; }
+  float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
+  if (query_ray_valid(a, b)) {
+    Rng rng;
+    rng_init(rng, P.seed_lo, P.seed_hi, key, P.first_sample);
+    rng.ctr = ctr;
+    const f3 d = irradiance_direction(P.mode, mk3(b.x, b.y, b.z), rng);
+    ra = a; rb = make_float4(d.x, d.y, d.z, b.w);
+    ctr = rng.ctr;
+  }
+  rays_out[(size_t)i * 2u] = ra; rays_out[(size_t)i * 2u + 1u] = rb;
+  keys_out[i] = make_uint2(key, ctr);
 }
 
-hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool may_spill, bool strict, bool env, bool lt, const void* rays, const void* keys,
-                               void* out, void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream) {
-  const RadianceKernel kernel = sol_radiance_variant(may_spill, strict, env, lt);
+// ---- launch wrappers (called from sol_api.cpp) ----
+// Built: the default estimator with and without the spill tail, plain and STRICT (4); the ENV / LT estimators SPILL-capable only, plain and
+// STRICT (6) - a scene whose tree fits the LDS stack runs them with a spill area it never touches. Each of the ten once more with GATHER, for
+// the irradiance queries.
+// The variant table: which of them the run-time flags name - the launch and the occupancy query both ask here.
+using RadianceKernel = void (*)(const DevScene*, const RadianceParams, const float4*, const uint2*, sol_v4f*, sol_v4f*, uint32_t*, uint32_t*);
+template <bool SPILL, bool ENV, bool LT, bool GATHER>
+static RadianceKernel radiance_variant_of(bool strict) { return strict ? sol_radiance_kernel<SPILL, true, ENV, LT, GATHER> : sol_radiance_kernel<SPILL, false, ENV, LT, GATHER>; }
+template <bool GATHER>
+static RadianceKernel radiance_variant_in(bool spill, bool strict, bool env, bool lt) {
+  if (env) return lt ? radiance_variant_of<true, true, true, GATHER>(strict) : radiance_variant_of<true, true, false, GATHER>(strict);
+  if (lt) return radiance_variant_of<true, false, true, GATHER>(strict);
+  return spill ? radiance_variant_of<true, false, false, GATHER>(strict) : radiance_variant_of<false, false, false, GATHER>(strict);
+}
+static RadianceKernel sol_radiance_variant(bool gather, bool spill, bool strict, bool env, bool lt) {
+  return gather ? radiance_variant_in<true>(spill, strict, env, lt) : radiance_variant_in<false>(spill, strict, env, lt);
+}
+
+hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool gather, bool may_spill, bool strict, bool env, bool lt, const void* rays,
+                               const void* keys, void* out, void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream) {
+  const RadianceKernel kernel = sol_radiance_variant(gather, may_spill, strict, env, lt);
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, dS, P, (const float4*)rays, (const uint2*)keys, (sol_v4f*)out, (sol_v4f*)partial, work, spill);
   return hipGetLastError();
 }
-int sol_radiance_blocks_per_cu(bool strict, bool env, bool lt) { return sol_blocks_per_cu(sol_radiance_variant(true, strict, env, lt)); }
+int sol_radiance_blocks_per_cu(bool gather, bool strict, bool env, bool lt) { return sol_blocks_per_cu(sol_radiance_variant(gather, true, strict, env, lt)); }
+
+hipError_t sol_launch_irradiance_rays(const RadianceParams& P, const void* points, const void* keys, void* rays_out, void* keys_out, hipStream_t stream) {
+  hipLaunchKernelGGL(sol_irradiance_rays_kernel, dim3((P.n_rays + 255u) / 256u), dim3(256), 0, stream, P, (const float4*)points, (const uint2*)keys,
+                     (float4*)rays_out, (uint2*)keys_out);
+  return hipGetLastError();
+}
 
 hipError_t sol_launch_radiance_resolve(const RadianceParams& P, const void* rays, const void* partial, void* out, uint32_t samples, bool accumulate,
                                        hipStream_t stream) {

@@ -1,7 +1,8 @@
 // sol_ray.h -- what the kernels that take the caller's own rays share (sol_query.hip, sol_radiance.hip): the validity rule of a SolRay
-// (include/solstrale_hip.h), decided per ray by the kernel itself before any search.
+// (include/solstrale_hip.h), decided per ray by the kernel itself before any search, and the direction an irradiance query draws at a point.
 #pragma once
 #include "sol_math.h"
+#include "sol_shade.h"
 
 // finite: neither an infinity nor a NaN
 DEV bool query_finite(float x) { return (__float_as_uint(x) & 0x7F800000u) != 0x7F800000u; }
@@ -12,4 +13,13 @@ DEV bool query_ray_valid(float4 a, float4 b) {
                       query_finite(b.y) && query_finite(b.z);
   const bool dir = b.x != 0.0f || b.y != 0.0f || b.z != 0.0f;
   return finite && dir && a.w >= 0.0f && a.w <= b.w;
+}
+
+// The direction of one irradiance path (sol_irradiance), drawn from the path's own generator, which goes on from where this
+// leaves it. COSINE: CosinePdf::generate (pdf.rs:58-71) about the point's normal - the two draws a Lambertian vertex makes in scatter
+// (sol_shade.h); the normal need not be unit length (onb_new divides by it). SPHERE: random_unit_vector (vec3.rs:395), three draws per
+// rejection round. One text for sol_radiance_kernel<.., GATHER> and sol_irradiance_rays_kernel: their bits agree because they are these operations.
+DEV f3 irradiance_direction(uint32_t mode, f3 normal, Rng& rng) {
+  if (mode == (uint32_t)SOL_IRRADIANCE_SPHERE) return unit3(random_in_unit_sphere(rng));
+  return onb_local(onb_new(normal), random_cosine_direction(rng));
 }

@@ -457,34 +457,84 @@ class DeviceScene:
         before and for the scene's stream after the launch."""
         cfg = _abi.SolRadianceConfig(size=C.sizeof(_abi.SolRadianceConfig), samples=int(samples), first_sample=int(first_sample), first_draw=int(first_draw),
                                      seed=int(seed), key_base=int(key_base) & 0xFFFFFFFF)
-        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: sol_radiance stages the arrays itself
+        return self._radiance(self.lib.sol_radiance, self.lib.sol_radiance_dev, "rays", "origin xyz, tmin, direction xyz, tmax", rays, keys, cfg)
+
+    def _radiance(self, host_fn, dev_fn, what, row, rays, keys, cfg):
+        """The two routes radiance() and irradiance() share: `rays` are the [n, 8] rows (`what`: their name in messages, `row`: their words)."""
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: the library stages the arrays itself
             a = np.ascontiguousarray(rays, dtype=np.float32)
             if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError("rays: an [n, 8] float32 array of (origin xyz, tmin, direction xyz, tmax)")
+                raise ValueError(f"{what}: an [n, 8] float32 array of ({row})")
             k = None
             if keys is not None:
                 k = np.ascontiguousarray(keys.cpu().numpy() if hasattr(keys, "data_ptr") else keys).astype(np.uint32, copy=False)
                 if k.shape != (a.shape[0], 2):
-                    raise ValueError("keys: an [n, 2] uint32 array of (pixel, first_draw), one row per ray")
+                    raise ValueError(f"keys: an [n, 2] uint32 array of (pixel, first_draw), one row per row of {what}")
                 k = np.ascontiguousarray(k)
             out = np.zeros((a.shape[0], 4), dtype=np.float32)
-            self._chk(self.lib.sol_radiance(self.h, a.ctypes.data, None if k is None else k.ctypes.data, a.shape[0], C.byref(cfg), out.ctypes.data))
+            self._chk(host_fn(self.h, a.ctypes.data, None if k is None else k.ctypes.data, a.shape[0], C.byref(cfg), out.ctypes.data))
             return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
         import torch
+        n = self._device_rows(what, rays, keys)
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        torch.cuda.current_stream(rays.device).synchronize()  # (the rays may still be in the making on torch's stream: the scene's is another)
+        self._chk(dev_fn(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(cfg),
+                         C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def _device_rows(self, what, rays, keys):
+        """Checks the device tensors of a radiance or irradiance call; returns n."""
+        import torch
         if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
-            raise ValueError("rays: a contiguous [n, 8] float32 tensor on the scene's device")
+            raise ValueError(f"{what}: a contiguous [n, 8] float32 tensor on the scene's device")
         if rays.device.index != self.device:
-            raise ValueError(f"rays: the tensor is on cuda:{rays.device.index}, the scene on cuda:{self.device}")
+            raise ValueError(f"{what}: the tensor is on cuda:{rays.device.index}, the scene on cuda:{self.device}")
         n = int(rays.shape[0])
         if keys is not None and (not hasattr(keys, "data_ptr") or keys.dtype != torch.int32 or tuple(keys.shape) != (n, 2) or not keys.is_contiguous()
                                  or keys.device != rays.device):
-            raise ValueError("keys: a contiguous [n, 2] int32 tensor of (pixel, first_draw) on the rays' device")
-        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
-        torch.cuda.current_stream(rays.device).synchronize()  # (the rays may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_radiance_dev(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(cfg),
-                                            C.c_void_p(out.data_ptr())))
+            raise ValueError(f"keys: a contiguous [n, 2] int32 tensor of (pixel, first_draw) on the device of {what}")
+        return n
+
+    # ---- irradiance queries (EXTENSION; DESIGN.md 20) ----
+    IRRADIANCE_MODES = {"cosine": _abi.SOL_IRRADIANCE_COSINE, "sphere": _abi.SOL_IRRADIANCE_SPHERE}
+
+    def _irradiance_config(self, samples, first_sample, seed, key_base, first_draw, mode):
+        if mode not in self.IRRADIANCE_MODES:
+            raise ValueError(f"mode: 'cosine' or 'sphere', not {mode!r}")
+        return _abi.SolIrradianceConfig(size=C.sizeof(_abi.SolIrradianceConfig), samples=int(samples), first_sample=int(first_sample), first_draw=int(first_draw),
+                                        seed=int(seed), key_base=int(key_base) & 0xFFFFFFFF, mode=self.IRRADIANCE_MODES[mode])
+
+    def irradiance(self, points, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="cosine"):
+        """sol_irradiance: the gather at the caller's points - rows of (position xyz, tmin, normal xyz, tmax). Every sample draws a fresh direction
+        on the device ("cosine": cosine-weighted about the normal, irradiance = pi * sum / samples; "sphere": uniform, mean radiance = sum /
+        samples) and is then radiance()'s path. keys, key_base, first_draw and the two routes with their return shapes are radiance()'s."""
+        cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
+        return self._radiance(self.lib.sol_irradiance, self.lib.sol_irradiance_dev, "points", "position xyz, tmin, normal xyz, tmax", points, keys, cfg)
+
+    def irradiance_rays(self, points, sample, seed=0, keys=None, key_base=0, first_draw=0, mode="cosine"):
+        """sol_irradiance_rays: the rays sample `sample` of irradiance() starts with and the keys its paths go on from, as ([n, 8] float32, [n, 2]
+        int32) device tensors: radiance(rays, samples=1, first_sample=sample, seed=seed, keys=keys) is that sample's contribution, bit for bit.
+        points and keys: device tensors as for irradiance(), or host arrays, which are copied to the scene's device first."""
+        import torch
+        cfg = self._irradiance_config(1, sample, seed, key_base, first_draw, mode)
+        dev = f"cuda:{self.device}"
+        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError("points: an [n, 8] float32 array of (position xyz, tmin, normal xyz, tmax)")
+            points = torch.from_numpy(a).to(dev)
+        if keys is not None and not hasattr(keys, "data_ptr"):
+            k = np.ascontiguousarray(np.ascontiguousarray(keys).astype(np.uint32, copy=False))
+            keys = torch.from_numpy(k.view(np.int32)).to(dev)
+        n = self._device_rows("points", points, keys)
+        rays = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+        keys_out = torch.empty((n, 2), dtype=torch.int32, device=points.device)
+        torch.cuda.current_stream(points.device).synchronize()  # (the points may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_irradiance_rays(self.h, C.c_void_p(points.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(cfg),
+                                               C.c_void_p(rays.data_ptr()), C.c_void_p(keys_out.data_ptr())))
         self.sync()
-        return out
+        return rays, keys_out
 
     def camera_ray_keys(self, x0, y0, x1, y1, sample, seed):
         """sol_camera_ray_keys: (pixel, first_draw) of the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 2] int32 device
