@@ -9,7 +9,7 @@ IEEE sequence the parity tests pin (DESIGN.md "fp32 arithmetic contract"). Trans
 parallel to objects (only the stale ones) and linked; `build(out_dir=..., extra_hip_flags=...)` makes an A/B variant
 of the device library elsewhere (tests/tools/variants.py), selected at run time through SOLSTRALE_BUILD_DIR.
 `build_ab()` makes _build_ab/: the same library plus the measured-and-rejected render-kernel variants (-DSOL_AB_KERNELS +
-csrc/sol_wavefront.hip: the two wavefront kernels; csrc/sol_pool.hip: the pool kernel), which the product library does not carry. Rejected experiments are not kept in the sources: their records
+csrc/sol_wavefront.hip: the two wavefront kernels; csrc/sol_pool.hip: the pool kernel; csrc/sol_launch_ab.cpp: their launches), which the product library does not carry. Rejected experiments are not kept in the sources: their records
 are profiles/*_ab.txt and the git history.
 """
 import os
@@ -55,14 +55,14 @@ def _run(cmd):
 
 def build(force=False, extra_hip_flags=(), out_dir=None, ab_kernels=False):
     """Product library into _build/ (or a variant into out_dir). ab_kernels: the A/B build that also carries the two wavefront
-    render kernels (-DSOL_AB_KERNELS + sol_wavefront.hip; `build_ab()` puts it into _build_ab/) - the product has one family."""
+    render kernels and the pool kernel (-DSOL_AB_KERNELS + sol_wavefront.hip, sol_pool.hip, sol_launch_ab.cpp; `build_ab()` puts it into _build_ab/) - the product has one family."""
     out_dir = out_dir or BUILD
     os.makedirs(out_dir, exist_ok=True)
     hip_lib = os.path.join(out_dir, "libsolstrale_hip.so")
     host_lib = os.path.join(out_dir, "libsolstrale_host.so")
     flags_file = os.path.join(out_dir, "hip_flags.txt")
     flags = HIP_FLAGS + (["-DSOL_AB_KERNELS"] if ab_kernels else []) + list(extra_hip_flags)
-    sources = HIP_SRC + (["csrc/sol_wavefront.hip", "csrc/sol_pool.hip"] if ab_kernels else [])
+    sources = HIP_SRC + (["csrc/sol_wavefront.hip", "csrc/sol_pool.hip", "csrc/sol_launch_ab.cpp"] if ab_kernels else [])
     want = " ".join(flags + sources)
     have = open(flags_file).read() if os.path.exists(flags_file) else None
     if have != want:

@@ -1,7 +1,7 @@
 // sol_adaptive.hip -- adaptive sampling (include/solstrale_hip.h, sol_adaptive_*): rounds of samples over the 8x8 blocks
 // still active, a per-pixel convergence test on the rounds' luminance, one vote per block, and the order-preserving compaction of
 // the work order into the next round's active list. The rounds run the product render kernel unchanged (sol_render_impl with a
-// SolAdaptiveLaunch); only the chunk resolve is replaced, by the update kernel below, which adds the chunk sums of the ACTIVE blocks
+// SolRenderJob whose `round` is set); only the chunk resolve is replaced, by the update kernel below, which adds the chunk sums of the ACTIVE blocks
 // to the accumulator in the association of sol_resolve_kernel: inactive blocks add nothing, whatever `partial` still holds for them.
 #include <hip/hip_runtime.h>
 
@@ -152,8 +152,7 @@ __global__ void __launch_bounds__(256) sol_adaptive_rescale_kernel(float* __rest
 
 static int adaptive_compact(SolScene* s) {
   SolAdaptiveSession& A = s->adaptive;
-  // the background tail of the work order is filled rather than traced under the conditions of a plain render (sol_render_impl)
-  const uint32_t n_bg = s->background_enabled && s->S.block_order && s->n_background_local <= s->n_local_blocks ? s->n_background_local : 0u;
+  const uint32_t n_bg = sol_background_tail(s, s->S);  // (filled rather than traced, as in a plain render)
   const uint32_t n_first = s->S.block_order ? std::min(s->S.n_first, s->n_local_blocks - n_bg) : 0u;
   hipLaunchKernelGGL(sol_adaptive_compact_kernel, dim3(1), dim3(SOL_COMPACT_WG), 0, s->stream, s->S.block_order, s->n_local_blocks, n_first, n_bg,
                      A.active.get(), A.order.get(), A.ctr.get());
@@ -206,8 +205,12 @@ int sol_adaptive_round(SolScene* s, uint64_t seed, uint32_t* active_blocks) {
   const uint32_t first = A.rounds_done * A.round;
   if (A.n_traced + A.n_background == 0 || first >= A.max_samples) { *active_blocks = 0; return SOL_OK; }
   const uint32_t n = std::min(A.round, A.max_samples - first);
-  const SolAdaptiveLaunch L{A.order.get(), A.n_first, A.n_traced, A.n_background, &A.mirror};
-  int rc = sol_render_impl(s, first, n, seed, false, &L);
+  // the round's job: the scene with the active list as its work order, through the session's own device copy
+  SolRenderJob job = sol_render_job(s, first, n, seed, false);
+  job.view.block_order = A.order.get(); job.view.n_first = A.n_first;
+  job.mirror = &A.mirror;
+  job.round = true; job.n_traced = A.n_traced; job.n_background = A.n_background;
+  int rc = sol_render_impl(s, job);
   if (rc) { A.open = false; return rc; }
   AdaptiveUpdate U;
   U.acc = s->acc; U.partial = s->partial.get(); U.state = A.state.get(); U.active = A.active.get(); U.counts = A.counts.get(); U.order = A.order.get();

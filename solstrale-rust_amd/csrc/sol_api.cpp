@@ -56,6 +56,7 @@ SolDevOverrides sol_dev_overrides() {
   o.max_bpc = num("SOL_MAX_BPC", -1);
   o.fine_tail = std::max(-2, num("SOL_FINE_TAIL", -2));
   o.pool_swap_min = std::max(0, num("SOL_POOL_SWAP", 0));
+  o.pool_count = std::getenv("SOL_POOL_COUNT") != nullptr;
   o.radiance_rows = std::max(0, num("SOL_RADIANCE_ROWS", 0));
   o.probe_radii = num("SOL_PROBE_RADII", -1);
   o.pool_slots = std::max(0, num("SOL_POOL_SLOTS", 0));
@@ -535,9 +536,7 @@ int radiance_check(const SolScene* s, const char* fn, RadianceKind kind, const v
 int radiance_launch(SolScene* s, bool gather, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
   int rc;
   if ((rc = sol_scene_to_device(s))) return rc;
-  // the estimator a render would run now (sol_render_impl): the ENV / LT builds under the path-tracing shader only
-  const bool env = s->env_is && s->S.shader == SOL_SHADER_PATH_TRACING;
-  const bool lt = s->light_mode != 0u && s->S.shader == SOL_SHADER_PATH_TRACING && s->S.n_lights > 1u;
+  const auto [env, lt] = sol_estimator(s, s->S, false);  // what a render would run now
   const int bpc = sol_radiance_blocks_per_cu(gather, s->strict_triangles, env, lt);
   const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
   if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;

@@ -920,6 +920,7 @@ static int set_scene_constants(const CreateCtx& c, const World& w, SolScene* s, 
   S.cam = cast_camera(d->camera);
   s->kernel_version = ovr.kernel_version;
   s->pool_swap_min = (uint32_t)ovr.pool_swap_min;
+  s->pool_count = ovr.pool_count;
   if (ovr.radiance_rows > 0) s->rad_partial_max_rows = (size_t)ovr.radiance_rows;
   s->order_mode = ovr.order_mode;
   // v1's search/shade switch (RenderParams::switch_below), measured on MI355X at 1080p x 128 spp (ms, C1 / C2 / C3 / test scene):
@@ -1132,24 +1133,22 @@ struct BackgroundProof {
 // sol_cost_probe_render makes the counted render into the probe's device tables, sol_cost_probe_adopt takes the render's status `rc`, frees
 // the tables and, where all went well, adopts the costs.
 int sol_cost_probe_render(SolScene* s, SolCostProbe& p) {
-  DevScene& S = s->S;
   const uint32_t nb = s->blocks_x * s->blocks_y;
   HIP_TRY(sol_dev_alloc(p.cost_dev, nb));
   hipError_t e = hipMemset(p.cost_dev.get(), 0, (size_t)nb * sizeof(uint32_t));
   if (e == hipSuccess) e = sol_dev_alloc(p.work_dev, nb);
   if (e == hipSuccess) e = hipMemset(p.work_dev.get(), 0, (size_t)nb * sizeof(uint32_t));
-  S.block_cost = p.cost_dev.get();
-  S.block_work = p.work_dev.get();
-  return e == hipSuccess ? sol_render_impl(s, 0, 4, 0xC057ull, true) : SOL_EDEVICE;
+  if (e != hipSuccess) return SOL_EDEVICE;
+  SolRenderJob job = sol_render_job(s, 0, 4, 0xC057ull, true);  // the scene with the probe's tables: only this launch records into them
+  job.view.block_cost = p.cost_dev.get();
+  job.view.block_work = p.work_dev.get();
+  return sol_render_impl(s, job);
 }
 int sol_cost_probe_adopt(SolScene* s, SolCostProbe& p, int rc, bool verbose) {
-  DevScene& S = s->S;
   const uint32_t nb = s->blocks_x * s->blocks_y;
   const SolCostProbe tables = std::move(p);  // (freed on every way out; p is empty again)
   uint32_t* const cost_dev = tables.cost_dev.get(); uint32_t* const work_dev = tables.work_dev.get();
   if (!cost_dev) return rc;  // (the render half failed before it had a table)
-  S.block_cost = nullptr;
-  S.block_work = nullptr;
   s->block_cost.assign(nb, 0u);
   s->block_work.assign(nb, 0u);
   if (rc == SOL_OK && hipMemcpy(s->block_work.data(), work_dev, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) rc = SOL_EDEVICE;
@@ -1170,7 +1169,7 @@ int sol_cost_probe_adopt(SolScene* s, SolCostProbe& p, int rc, bool verbose) {
   s->stats = SolStats{};
   if ((rc = sol_clear(s)) || (rc = sol_rebuild_order(s))) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
-  if (verbose) std::fprintf(stderr, "[solstrale] work order: %u of %u blocks heavy (first)\n", S.n_first, s->n_local_blocks);
+  if (verbose) std::fprintf(stderr, "[solstrale] work order: %u of %u blocks heavy (first)\n", s->S.n_first, s->n_local_blocks);
   return SOL_OK;
 }
 

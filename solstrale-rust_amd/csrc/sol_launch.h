@@ -14,22 +14,22 @@ int sol_blocks_per_cu(K kernel) {
   return n;
 }
 
-// version 1: one path per lane (the product kernel); versions 2 / 3 (-DSOL_AB_KERNELS builds): the wavefront variants of sol_wavefront.hip
-hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
-                             uint32_t* spill, void* pool, DevCounters* cnt, uint32_t grid, bool count, bool medium, bool may_spill,
-                             bool env, bool lt, hipStream_t stream);
-// env: environment importance sampling, lt: light sampling modes 1 and 2; version 1, uncounted
-int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env = false, bool lt = false);
+// the product kernel, one path per lane. The caller (sol_render_impl) has decided the variant: strict: the scene has needle triangles; env: environment
+// importance sampling, lt: light sampling modes 1 and 2 - both uncounted only
+hipError_t sol_launch_render(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, DevCounters* cnt,
+                             uint32_t grid, bool count, bool medium, bool may_spill, bool strict, bool env, bool lt, hipStream_t stream);
+int sol_render_blocks_per_cu(bool count, bool medium, bool strict, bool env, bool lt);
 hipError_t sol_launch_stage_resolve(const DevScene* dS, const RenderParams& P, float* partial, hipStream_t stream);
 hipError_t sol_launch_fill_background(const DevScene* dS, const RenderParams& P, float* partial, hipStream_t stream);
 hipError_t sol_launch_debug_path(const DevScene& S, const RenderParams& P, uint32_t px, uint32_t py, uint32_t s, uint32_t* spill,
                                  float* out, uint32_t max_rows, bool medium, hipStream_t stream);
+// ==== the A/B kernel variants (-DSOL_AB_KERNELS builds only): launched from sol_launch_ab.cpp, nowhere else ====
 // ---- sol_pool.hip: version 4, the pool kernel (a second path context per lane in LDS, handed out wave-wide; sample-granular work items) ----
 hipError_t sol_launch_pool4(const DevScene& S, const DevScene* dS, const RenderParams& P, float* partial, uint32_t* work, uint32_t* spill, uint32_t grid,
                             bool medium, bool may_spill, DevCounters* cnt, hipStream_t stream);
 int sol_pool4_blocks_per_cu(bool medium, bool strict);
 int sol_pool4_lds_stack_depth();
-// ---- sol_wavefront.hip (-DSOL_AB_KERNELS builds only) ----
+// ---- sol_wavefront.hip ----
 // version 2: wave-private wavefront over a pool of path slots
 hipError_t sol_launch_pool(const DevScene& S, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, void* pool,
                            DevCounters* cnt, uint32_t grid, bool count, bool medium, hipStream_t stream);
@@ -43,6 +43,7 @@ hipError_t sol_launch_wf_trace(const DevScene& S, const RenderParams& P, void* c
 int sol_wf_trace_blocks_per_cu(bool count, bool medium);
 size_t sol_wf_pool_bytes(uint32_t slots);
 int sol_wf_lds_stack_depth();
+// ==== (end of the A/B kernel variants) ====
 // ---- sol_query.hip: ray queries. rays: n SolRay on the device; out: n SolRayHit, or n status words when `any` ----
 hipError_t sol_launch_query(const DevScene* dS, bool any, bool may_spill, bool strict, const void* rays, uint32_t n, void* out, uint32_t* spill,
                             uint32_t grid, hipStream_t stream);

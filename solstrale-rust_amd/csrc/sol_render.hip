@@ -7,7 +7,7 @@
 //    (RenderParams::switch_below), unfinished searches keep their state across the service block. DESIGN.md 3. The schedule's pieces -
 //    search context, work reservoir, leave vote - are sol_wave.h's, shared with sol_radiance.hip, sol_query.hip and sol_pool.hip.
 //  (The measured alternatives - a wave-private wavefront over a pool of path slots and a two-kernel wavefront, bit-identical
-//  frames, slower - live in sol_wavefront.hip, which only the -DSOL_AB_KERNELS build of the library carries.)
+//  frames, slower - live in sol_wavefront.hip, which only the A/B build of the library carries, with their launches: sol_launch_ab.cpp.)
 //
 // A work item's 16 samples are summed in sample order by the lane that owns the item and written once; no float atomic touches
 // the accumulator, so the image is a pure function of (scene, seed), bit-identical for any tile partition.
@@ -261,34 +261,13 @@ static RenderKernel sol_render_variant(bool count, bool medium, bool spill, bool
   return lt ? render_variant_of<false, true>(medium, spill, strict) : render_variant_of<false, false>(medium, spill, strict);
 }
 
-hipError_t sol_launch_render(int version, const DevScene& S, const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work,
-                             uint32_t* spill, void* pool, DevCounters* cnt, uint32_t grid, bool count, bool medium, bool may_spill,
-                             bool env, bool lt, hipStream_t stream) {
-  if ((env || lt) && (version != 1 || count)) return hipErrorInvalidValue;  // (sol_render_impl runs importance sampling and the light tree on the uncounted product kernel only)
-#ifdef SOL_AB_KERNELS
-  if (version == 4) return sol_launch_pool4(S, dS, P, partial, work, spill, grid, medium, may_spill, count ? cnt : nullptr, stream);  // (sol_pool.hip)
-#endif
-  if (version == 1) {
-    const RenderKernel kernel = sol_render_variant(count, medium, may_spill, S.tri_delta > 0.0f, env, lt);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
-    return hipGetLastError();
-  }
-#ifdef SOL_AB_KERNELS
-  return sol_launch_pool(S, P, acc, partial, work, spill, pool, cnt, grid, count, medium, stream);  // (sol_wavefront.hip)
-#else
-  return hipErrorInvalidValue;  // (the wavefront variants exist in -DSOL_AB_KERNELS builds only)
-#endif
+hipError_t sol_launch_render(const DevScene* dS, const RenderParams& P, float* acc, float* partial, uint32_t* work, uint32_t* spill, DevCounters* cnt,
+                             uint32_t grid, bool count, bool medium, bool may_spill, bool strict, bool env, bool lt, hipStream_t stream) {
+  const RenderKernel kernel = sol_render_variant(count, medium, may_spill, strict, env, lt);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(SOL_WG), 0, stream, dS, P, acc, partial, work, spill, cnt);
+  return hipGetLastError();
 }
 
-int sol_render_blocks_per_cu(int version, bool count, bool medium, bool strict, bool env, bool lt) {
-  if (env || lt) { version = 1; count = false; }  // (as sol_render_impl chooses: the ENV / LT builds are the uncounted product kernel)
-#ifdef SOL_AB_KERNELS
-  if (version == 4) return sol_pool4_blocks_per_cu(medium, strict);
-#endif
-  if (version == 1) return sol_blocks_per_cu(sol_render_variant(count, medium, true, strict, env, lt));
-#ifdef SOL_AB_KERNELS
-  return sol_pool_blocks_per_cu(count, medium);
-#else
-  return 1;
-#endif
+int sol_render_blocks_per_cu(bool count, bool medium, bool strict, bool env, bool lt) {
+  return sol_blocks_per_cu(sol_render_variant(count, medium, true, strict, env, lt));
 }

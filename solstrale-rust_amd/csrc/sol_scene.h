@@ -5,6 +5,7 @@
 //   sol_api.cpp     handle life cycle, options, partition, accumulators, read-back, statistics
 //   sol_create.cpp  sol_scene_create in stages: validation of the flattened scene, conversion to the fp32 device layout (sol_types.h), world-tree candidates, upload, probes; the tree diagnostics
 //   sol_launch.cpp  sol_render* / auxiliary planes / debug hooks: launches of the kernels in sol_render.hip; sol_launch_plan (grid and spill tail)
+//   sol_launch_ab.cpp  (A/B build only, beside sol_wavefront.hip and sol_pool.hip) sol_render_ab: the launches of the measured-and-rejected kernel variants
 //   sol_launch.h    the launch wrappers of the .hip files (each family: one variant table for the launch and the occupancy query; sol_blocks_per_cu)
 //   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
 //   sol_geometry.cpp sol_scene_set_triangles / sol_scene_set_primitives: the triangles, spheres and quads of a live scene moved, records and tree boxes recomputed on the device (sol_geometry.hip)
@@ -125,6 +126,7 @@ struct SolDevOverrides {
   int probe_radii = -1;          // SOL_PROBE_RADII (AUTO device build: 1 = emit and probe both clustering radii, 0 = never, -1 = by the collapse costs)
   int radiance_rows = 0;         // SOL_RADIANCE_ROWS: bound of the radiance queries' partial buffer in rows (0: the default, 2^24) - tests drive the splits with a small one
   int pool_swap_min = 0;         // SOL_POOL_SWAP (pool kernel: RenderParams::swap_min; 0: the default)
+  bool pool_count = false;       // SOL_POOL_COUNT (pool kernel: counted renders run its instrumented build - phase statistics)
   int pool_slots = 0, wf_slots = 0, wf_min_items = -1;  // SOL_POOL_SLOTS / SOL_WF_SLOTS / SOL_WF_MIN_ITEMS (v2 / v3)
   std::string rccl_lib;          // SOL_RCCL_LIB: the communication library to dlopen instead of librccl.so.1 (tests)
   bool verbose = false;          // SOL_VERBOSE
@@ -197,16 +199,11 @@ struct SolAdaptiveSession {
   DevBuf<uint32_t> ctr; PinnedPtr<uint32_t> ctr_host;  // what the compaction counted: heavy, traced, background active blocks
   SolSceneMirror mirror;    // the DevScene copy whose work order is the active list
 };
-// What sol_render_impl needs to render a round over the active list instead of the whole work order.
-struct SolAdaptiveLaunch {
-  const uint32_t* order;
-  uint32_t n_first, n_traced, n_background;
-  SolSceneMirror* mirror;
-};
 
 struct SolScene {
   int device = 0;
   hipStream_t own_stream = nullptr, stream = nullptr;
+  // S changes only where the scene changes: creation, the setters (sol_scene_set_*), the partition / order tables and the sampling modes. It never changes to describe a launch: a launch that renders something else renders a copy (SolRenderJob::view).
   DevScene S{};
   SolSceneMirror mirror;               // device copy of S (the product render kernel and the queries read it through a pointer)
   DevTree tree;                        // the world tree the handle walks and what hangs on it; S points into it
@@ -245,6 +242,7 @@ struct SolScene {
   bool has_medium = false;
   bool strict_triangles = false;  // the scene has needle triangles: the STRICT kernel variants (sol_render.hip)
   uint32_t pool_swap_min = 0;             // SOL_POOL_SWAP (pool kernel, RenderParams::swap_min; 0: the default)
+  bool pool_count = false;                // SOL_POOL_COUNT (pool kernel: its counted renders run the instrumented build)
   int rank = 0, world = 1;
   uint32_t blocks_x = 0, blocks_y = 0, n_local_blocks = 0;
   int n_cu = 0;
@@ -256,7 +254,6 @@ struct SolScene {
   DevBuf<uint32_t> wf_ctr; PinnedPtr<uint32_t> wf_ctr_host;
   uint32_t wf_slots = 4u << 20;       // SOL_WF_SLOTS: pool size of the two-kernel wavefront
   uint32_t wf_min_items = 2u << 20;   // SOL_WF_MIN_ITEMS: jobs below this use the single-launch kernel
-  uint32_t last_rounds = 0; int last_version = 0;
   double build_times[4] = {0., 0., 0., 0.};  // sol_scene_build_times
   bool order_enabled = true;         // SOL_OPT_WORK_ORDER
   // background blocks (solstrale_hip.h SolSceneInfo::background_blocks): per 8x8 block (global index) 1 = proved to see only the
@@ -331,5 +328,46 @@ inline int sol_scene_to_device(SolScene* s) { return s->mirror.upload(s->stream,
 // grid x SOL_WG x (stack_need - lds_depth) words, 16 when the searches fit the kernel's LDS stack.
 int sol_launch_plan(SolScene* s, int blocks_per_cu, uint64_t items, uint32_t lds_depth, uint32_t stack_need, DevBuf<uint32_t>& spill, uint32_t* grid);
 int sol_set_partition(SolScene* s, int rank, int world);
-int sol_render_impl(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count, const SolAdaptiveLaunch* ad = nullptr);
-inline int sol_render_probe(SolScene* s) { return sol_render_impl(s, 0, SOL_CHUNK, 0x50B3ull, true); }
+
+// One launch of sol_render_impl (sol_launch.cpp): what differs between its callers, and nothing else - the handle supplies what is not per launch
+// (partition, scratch buffers, options, stream, timing events). sol_render_job is the job with every default: the handle's own scene record,
+// device copy and accumulator.
+struct SolRenderJob {
+  uint32_t first, n; uint64_t seed;  // the sample range and the seed
+  bool count;                        // a counted render (statistics, the creation probes)
+  float* acc;                        // the accumulator the sums go to
+  DevScene view;                     // the scene record this launch renders: s->S, or a copy with another shader / background / environment
+                                     // pointer (auxiliary planes), cost tables (cost probe) or work order (a round of adaptive sampling)
+  SolSceneMirror* mirror;            // the device copy `view` is uploaded to
+  // a round of adaptive sampling (sol_adaptive.hip): the traced and the background blocks of the active list that is the view's work order;
+  // the chunk sums stay in `partial` for the caller, which adds them to the accumulator itself
+  bool round = false; uint32_t n_traced = 0, n_background = 0;
+};
+inline SolRenderJob sol_render_job(SolScene* s, uint32_t first, uint32_t n, uint64_t seed, bool count) { return {first, n, seed, count, s->acc, s->S, &s->mirror}; }
+int sol_render_impl(SolScene* s, const SolRenderJob& job);
+inline int sol_render_probe(SolScene* s) { return sol_render_impl(s, sol_render_job(s, 0, SOL_CHUNK, 0x50B3ull, true)); }
+
+// The estimator a path-tracing launch of `view` runs now: environment importance sampling and light sampling modes 1 and 2
+//  are the ENV / LT builds of the render and radiance kernels - uncounted, under the path-tracing shader only (the other shaders
+// read only the scatter's colour; counted renders are the creation probes, sol_render_counted refuses while either is on). With one light modes 1
+// and 2 are mode 0's estimator (q_0 = 1), and the default kernels run.
+struct SolEstimator { bool env, lt; };
+inline SolEstimator sol_estimator(const SolScene* s, const DevScene& view, bool count) {
+  const bool path_tracing = !count && view.shader == SOL_SHADER_PATH_TRACING;
+  return {s->env_is && path_tracing, s->light_mode != 0u && path_tracing && view.n_lights > 1u};
+}
+// How many blocks at the end of this rank's work order (`view`'s) are filled by sol_fill_background_kernel rather than traced.
+inline uint32_t sol_background_tail(const SolScene* s, const DevScene& view) {
+  return s->background_enabled && view.block_order && s->n_background_local <= s->n_local_blocks ? s->n_background_local : 0u;
+}
+
+// The steps of a render launch that the product path (sol_render_impl) and the A/B variants (sol_render_ab) share, in the order of a launch:
+// the base launch parameters of `job` with n_traced blocks traced (refuses more work items than the 32-bit work counter takes); room for the chunk
+// sums and stage_floats of staging in s->partial, the padding pixels zero; work counter and counters zeroed, the timing started; and behind the
+// kernels: timing stopped, the staged samples and - unless the job leaves them to its caller - the chunk sums resolved, the counters read back.
+int sol_render_params(const SolScene* s, const SolRenderJob& job, uint32_t n_traced, RenderParams& P);
+int sol_render_partial(SolScene* s, const RenderParams& P, size_t stage_floats);
+int sol_render_begin(SolScene* s, bool count);
+int sol_render_end(SolScene* s, const SolRenderJob& job, const RenderParams& P, uint32_t grid, bool via_partial);
+// sol_launch_ab.cpp, -DSOL_AB_KERNELS builds only: `job` on kernel variant 2, 3 or 4 (sol_wavefront.hip, sol_pool.hip)
+int sol_render_ab(SolScene* s, const SolRenderJob& job, int variant);

@@ -67,3 +67,14 @@ class WindowScene:
         self.desc.width, self.desc.height = w, h
         self.desc_ptr = C.pointer(self.desc)
         self.width, self.height = w, h
+
+
+def env_two_lights(rc):
+    """test_env_importance._scene_with_env with a second light, so that the environment map AND the light tree are in force at once."""
+    import test_env_importance as te
+    from solstrale_amd import CameraConfig, SceneBuilder
+    b = SceneBuilder()
+    objs = [b.Sphere((0., 1., 0.), 1., b.Lambertian(b.SolidColor(.5, .45, .4))), b.Quad((-6., 0., -6.), (12., 0., 0.), (0., 0., 12.), b.Lambertian(b.SolidColor(.4, .4, .4))),
+            b.Quad((-1., 4., -1.), (2., 0., 0.), (0., 0., 2.), b.DiffuseLight(1., 1., 1.)), b.Sphere((3., 2.5, -1.), .3, b.DiffuseLight(6., 5., 4.))]
+    b.environment(te._smooth_sky(), 1.0)
+    return b.finish(b.Bvh(objs), CameraConfig(40., 0., (0., 2., 7.), (0., 1., 0.), (0., 1., 0.)), (.2, .3, .4), rc)

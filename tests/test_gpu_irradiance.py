@@ -11,6 +11,7 @@ import pytest
 import irradiance_util as iu
 import orc
 import parity_util as pu
+from parity_util import env_two_lights as _env_two_lights
 from solstrale_amd import (AlbedoShader, CameraConfig, DeviceError, DeviceScene, NormalShader, PathTracingShader, RenderConfig, SceneBuilder, _abi,
                            scenes)
 
@@ -156,15 +157,6 @@ def test_irradiance_is_the_association_over_radiance_of_its_own_rays(make):
         points, is_valid = with_invalid_rows(surface_points(sc, ds, 300))
         assert len(points) == 300 + len(INVALID_CLASSES)
         assert_identity(ds, points, is_valid, ks=(1, 15, 16, 17, 48), distinct=True)
-
-
-def _env_two_lights(rc):
-    import test_env_importance as te
-    b = SceneBuilder()
-    objs = [b.Sphere((0., 1., 0.), 1., b.Lambertian(b.SolidColor(.5, .45, .4))), b.Quad((-6., 0., -6.), (12., 0., 0.), (0., 0., 12.), b.Lambertian(b.SolidColor(.4, .4, .4))),
-            b.Quad((-1., 4., -1.), (2., 0., 0.), (0., 0., 2.), b.DiffuseLight(1., 1., 1.)), b.Sphere((3., 2.5, -1.), .3, b.DiffuseLight(6., 5., 4.))]
-    b.environment(te._smooth_sky(), 1.0)
-    return b.finish(b.Bvh(objs), CameraConfig(40., 0., (0., 2., 7.), (0., 1., 0.), (0., 1., 0.)), (.2, .3, .4), rc)
 
 
 def _variation(name):

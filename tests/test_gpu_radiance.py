@@ -10,6 +10,7 @@ import pytest
 
 import orc
 import parity_util as pu
+from parity_util import env_two_lights as _env_two_lights
 from solstrale_amd import (AlbedoShader, CameraConfig, DeviceError, DeviceScene, NormalShader, PathTracingShader, RenderConfig, SceneBuilder, _abi,
                            camera_record, scenes)
 from test_gpu_queries import _as_rays, _cornell, _deep_chain, _needles, _random_mixed, _world_box, ray_mix
@@ -283,16 +284,6 @@ def test_a_small_partial_buffer_splits_the_call_and_changes_no_bit(monkeypatch):
 
 
 # ---- 5. modes ---------------------------------------------------------------------------------------------------------------------------
-def _env_two_lights(rc):
-    """test_env_importance._scene_with_env with a second light, so that the environment map AND the light tree are in force at once."""
-    import test_env_importance as te
-    b = SceneBuilder()
-    objs = [b.Sphere((0., 1., 0.), 1., b.Lambertian(b.SolidColor(.5, .45, .4))), b.Quad((-6., 0., -6.), (12., 0., 0.), (0., 0., 12.), b.Lambertian(b.SolidColor(.4, .4, .4))),
-            b.Quad((-1., 4., -1.), (2., 0., 0.), (0., 0., 2.), b.DiffuseLight(1., 1., 1.)), b.Sphere((3., 2.5, -1.), .3, b.DiffuseLight(6., 5., 4.))]
-    b.environment(te._smooth_sky(), 1.0)
-    return b.finish(b.Bvh(objs), CameraConfig(40., 0., (0., 2., 7.), (0., 1., 0.), (0., 1., 0.)), (.2, .3, .4), rc)
-
-
 def _mode_cases():
     import test_env_importance as te
     return {

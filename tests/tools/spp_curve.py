@@ -13,4 +13,4 @@ with DeviceScene(make(RenderConfig(1920, 1080, 16))) as ds:
         ds.clear(); ds.render(0, spp, pu.SEED); ds.sync()
         ds.clear(); ds.render(0, spp, pu.SEED); ds.sync()
         ms, grid = ds.last_kernel_ms()
-        print(f"{which} spp {spp:4d}: kernel {ms:8.2f} ms  {ms / spp:6.3f} ms/spp", flush=True)
+        print(f"{which} spp {spp:4d}: kernel {ms:8.2f} ms  {ms / spp:6.3f} ms/spp  grid {grid}", flush=True)
