@@ -746,7 +746,8 @@ int sol_camera_ray_keys(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, 
  *             tmax - and one SolRayKey - the key and the generator's counter after the direction. An invalid point gives an all-zero ray (itself
  *             invalid) beside (key, first_draw).
  *   Identity. With the same scene, seed and modes, sol_radiance_dev(rays_out, keys_out, samples = 1, first_sample = s) equals sample s's
- *             contribution to sol_irradiance_dev bit for bit: a caller can project the samples onto a basis of their own (spherical harmonics).
+ *             contribution to sol_irradiance_dev bit for bit: a caller can project the samples onto a basis of their own (for spherical
+ *             harmonics up to l = 2 see sol_irradiance_sh below, which does that in one call).
  *   Neutral.  As sol_radiance: neither the accumulator, the auxiliary planes, the render's work counter, the partition, an adaptive session nor
  *             SolStats is touched. Irradiance and radiance queries share their scratch; calls on one handle are ordered by its stream.
  * SOL_EINVAL (sol_last_error names the reason), in sol_radiance's order and before the device is looked for: a null scene or configuration; a
@@ -762,6 +763,38 @@ int sol_irradiance(SolScene* scene, const SolRay* points, const SolRayKey* keys,
 /* Device pointers (n SolRay points, n SolRayKey or NULL; n SolRay and n SolRayKey out), on the scene's stream, asynchronous. */
 int sol_irradiance_rays(SolScene* scene, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* rays_out_dev,
                         void* keys_out_dev);
+
+/* ---- SH irradiance queries (EXTENSION, not in the reference) --------------------------------------------------------------
+ * "What light arrives at this point, from where?" - the gather of an irradiance query projected onto spherical harmonics: nine coefficients
+ * per colour channel, the form light probes and irradiance volumes keep. One probe then lights any normal, and a volume of probes can be
+ * interpolated. One call in place of 2 x samples launches (sol_irradiance_rays + sol_radiance_dev per sample) and a projection of the caller's.
+ *   Points.   Points, their validity, keys, first_draw and the two modes are sol_irradiance's, word for word. An invalid point answers 27 zero
+ *             words and samples = 0, decided before any search.
+ *   Paths.    Sample s of point i draws its direction d_s as sol_irradiance does, from the stream of (seed, key, s) at first_draw, and is then
+ *             sol_radiance's path in the handle's current shader, max_depth, sol_env_sampling and sol_light_sampling modes. Its colour c_s is,
+ *             on the bits, what sol_radiance_dev(rays_out, keys_out, samples = 1, first_sample = s) answers over what sol_irradiance_rays
+ *             writes for sample s: 0 + colour.
+ *   Basis.    Real SH up to l = 2 on d_s = (x, y, z) as drawn, not normalised again, without the Condon-Shortley sign, in the order
+ *             (l, m) = (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2):
+ *               Y0 = k0                    Y1 = k1 y                Y2 = k1 z
+ *               Y3 = k1 x                  Y4 = (k2 x) y            Y5 = (k2 y) z
+ *               Y6 = k3 ((3 (z z)) - 1)    Y7 = (k2 x) z            Y8 = k4 ((x x) - (y y))
+ *             k0 .. k4 are the fp32 roundings of 0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005,
+ *             0.5462742152960396; every operation is one fp32 rounding in the bracketing shown (no fused multiply-add).
+ *   Sums.     SolSh9.c[k][channel] is the SUM over the samples of fl(c_s[channel] x Y_k(d_s)), in sol_radiance's association: chunks of 16
+ *             samples counted from first_sample, a chunk sum 0 + t + t .. in sample order, the result ((0 + chunk0) + chunk1) + ..;
+ *             SolSh9.samples is the sample count.
+ *   Estimators. SOL_IRRADIANCE_SPHERE: the radiance coefficients are L_k = 4 pi x c[k] / samples, and the irradiance for a unit normal n is
+ *             the sum over k of A_l(k) L_k Y_k(n) with A = (pi, 2 pi / 3, pi / 4) for l = 0, 1, 2. SOL_IRRADIANCE_COSINE: pi x c[k] / samples
+ *             estimates the cosine-weighted projection about the point's normal. The kernels do not care which mode is used.
+ *   Neutral.  As sol_radiance. The scratch is shared with the radiance and irradiance queries; calls on one handle are ordered by its stream.
+ * SOL_EINVAL: sol_irradiance's refusals, in the same order and with the same words, before the device is looked for - a scene with a constant
+ * medium among them. n == 0 succeeds on any scene and touches nothing. There is no host mirror. */
+typedef struct SolSh9 { float c[9][3]; uint32_t samples; } SolSh9;   /* 112 bytes; 16-byte aligned in device memory; sums, not means */
+/* Device pointers (n SolRay points, n SolRayKey or NULL, n SolSh9 out, on the scene's device), on the scene's stream, asynchronous. */
+int sol_irradiance_sh_dev(SolScene* scene, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_irradiance_sh(SolScene* scene, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolSh9* out);
 
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment

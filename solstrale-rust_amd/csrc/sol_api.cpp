@@ -537,7 +537,7 @@ int radiance_launch(SolScene* s, bool gather, const void* rays_dev, const void* 
   int rc;
   if ((rc = sol_scene_to_device(s))) return rc;
   const auto [env, lt] = sol_estimator(s, s->S, false);  // what a render would run now
-  const int bpc = sol_radiance_blocks_per_cu(gather, s->strict_triangles, env, lt);
+  const int bpc = sol_radiance_blocks_per_cu(gather, false, s->strict_triangles, env, lt);
   const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
   if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
   const uint32_t total_chunks = (uint32_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
@@ -573,9 +573,59 @@ int radiance_launch(SolScene* s, bool gather, const void* rays_dev, const void* 
       if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
       P.total_threads = grid * SOL_WG;
       HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
-      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, gather, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial.get(), s->rad_work.get(),
-                                  s->rad_spill.get(), grid, s->stream));
+      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, gather, false, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial.get(),
+                                  s->rad_work.get(), s->rad_spill.get(), grid, s->stream));
       if (!P.direct) HIP_TRY(sol_launch_radiance_resolve(P, rays_at, s->rad_partial.get(), out_at, cfg.samples, c0 != 0, s->stream));
+    }
+  }
+  return SOL_OK;
+}
+
+// SH irradiance queries: n <= 2^31 points (and keys, or null) in device memory, n SolSh9 out, on the scene's stream. Every launch
+// of the path kernel writes one colour per (point, sample) into the partial buffer and is followed by the projection kernel. A launch holds
+// whole chunks of 64 x k points: rows = points x samples <= SolScene::rad_partial_max_rows, at least one group of one chunk (1024 rows). The call is
+// split over points (answers are per point) and over windows of chunks (the projection kernel carries a point's sums from one window to the next
+// in `out`: the same additions in the same order).
+int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
+  int rc;
+  if ((rc = sol_scene_to_device(s))) return rc;
+  const auto [env, lt] = sol_estimator(s, s->S, false);  // what a render would run now
+  const int bpc = sol_radiance_blocks_per_cu(true, true, s->strict_triangles, env, lt);
+  const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
+  if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
+  const size_t total_chunks = (size_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
+  const size_t unit = (size_t)64 * SOL_CHUNK;  // rows of one group of points over one chunk
+  const size_t units = std::max<size_t>(1, std::min<size_t>(s->rad_partial_max_rows, (size_t)1 << 31) / unit);
+  const size_t win_chunks = std::min(total_chunks, units);
+  const size_t slice_points = units / win_chunks * 64;
+  for (size_t at = 0; at < n; at += slice_points) {
+    const size_t k = std::min(slice_points, n - at);
+    RadianceParams P{};
+    P.n_rays = (uint32_t)k;
+    P.n_groups = (uint32_t)((k + 63) / 64);
+    P.end_sample = cfg.first_sample + cfg.samples;
+    P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
+    P.key_base = key_base + (uint32_t)at;
+    P.first_draw = cfg.first_draw;
+    P.switch_below = s->switch_below;
+    P.mode = cfg.reserved;
+    const char* points_at = (const char*)points_dev + at * sizeof(SolRay);
+    const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
+    char* out_at = (char*)out_dev + at * sizeof(SolSh9);
+    if ((rc = s->rad_partial.reserve(s->stream, (size_t)P.n_groups * 64 * std::min<size_t>(win_chunks * SOL_CHUNK, cfg.samples)))) return rc;
+    for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
+      P.n_chunks = (uint32_t)std::min(win_chunks, total_chunks - c0);
+      P.first_sample = cfg.first_sample + (uint32_t)(c0 * SOL_CHUNK);
+      const uint32_t win_samples = std::min<uint32_t>(P.n_chunks * (uint32_t)SOL_CHUNK, P.end_sample - P.first_sample);  // (the call's last chunk may be short)
+      const uint64_t items = (uint64_t)win_samples * P.n_groups * 64u;  // (<= 2^31 rows of the partial buffer)
+      P.n_items = (uint32_t)items;
+      uint32_t grid;
+      if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
+      P.total_threads = grid * SOL_WG;
+      HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
+      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, true, true, may_spill, s->strict_triangles, env, lt, points_at, keys_at, nullptr, s->rad_partial.get(),
+                                  s->rad_work.get(), s->rad_spill.get(), grid, s->stream));
+      HIP_TRY(sol_launch_sh_project(P, points_at, keys_at, s->rad_partial.get(), out_at, win_samples, cfg.samples, c0 != 0, s->stream));
     }
   }
   return SOL_OK;
@@ -593,6 +643,24 @@ int radiance_staged(SolScene* s, bool gather, const SolRay* rays, const SolRayKe
     if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
     if ((rc = radiance_launch(s, gather, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get()))) return rc;
     HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  return SOL_OK;
+}
+
+// The host route of the SH irradiance queries: radiance_staged's buffers, the answers' staging grown to the 112 bytes (seven SolRadiance) of a SolSh9 row.
+static_assert(sizeof(SolSh9) == 7 * sizeof(SolRadiance), "a SolSh9 row is seven dwordx4");
+int irradiance_sh_staged(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, SolSh9* out) {
+  int rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
+  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap * 7))) return rc;
+  for (size_t at = 0; at < n; at += cap) {  // (answers are per point: the split changes nothing)
+    const size_t k = std::min(cap, n - at);
+    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), points + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
+    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
+    if ((rc = irradiance_sh_launch(s, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get()))) return rc;
+    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolSh9), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
@@ -634,6 +702,26 @@ int sol_irradiance(SolScene* s, const SolRay* points, const SolRayKey* keys, siz
   if (config) cfg = radiance_config_of(*config);
   if ((rc = radiance_check(s, "sol_irradiance", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
   return radiance_staged(s, true, points, keys, n, cfg, out);
+}
+
+int sol_irradiance_sh_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = radiance_check(s, "sol_irradiance_sh_dev", IRRADIANCE, points_dev, n, config ? &cfg : nullptr, out_dev, out_dev, &go)) || !go || (rc = query_device_check()))
+    return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return irradiance_sh_launch(s, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev);
+}
+
+int sol_irradiance_sh(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolSh9* out) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = radiance_check(s, "sol_irradiance_sh", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
+  return irradiance_sh_staged(s, points, keys, n, cfg, out);
 }
 
 int sol_irradiance_rays(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* rays_out_dev,

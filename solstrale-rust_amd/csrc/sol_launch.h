@@ -66,9 +66,15 @@ struct RadianceParams {
   uint32_t mode;               // irradiance queries (gather launches only): SOL_IRRADIANCE_COSINE or SOL_IRRADIANCE_SPHERE
 };
 // gather: an irradiance query - the rows are points (position, tmin, normal, tmax) and each sample draws its own direction (P.mode)
-hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool gather, bool may_spill, bool strict, bool env, bool lt, const void* rays,
+// each (with gather; SH irradiance queries): a work item is (point, sample), sample-major - n_items = n_groups * 64 * the launch's
+// samples -, and every sample's colour goes to `partial` [sample - first_sample][n_groups * 64]; `out` and P.direct are not used
+hipError_t sol_launch_radiance(const DevScene* dS, const RadianceParams& P, bool gather, bool each, bool may_spill, bool strict, bool env, bool lt, const void* rays,
                                const void* keys, void* out, void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream);
-int sol_radiance_blocks_per_cu(bool gather, bool strict, bool env, bool lt);
+int sol_radiance_blocks_per_cu(bool gather, bool each, bool strict, bool env, bool lt);
+// one thread per point after an `each` launch: the launch's win_samples colours times the SH basis of their directions, added in chunk order onto 0
+// (or, accumulate, onto what `out` holds) and written as SolSh9 rows with `samples`
+hipError_t sol_launch_sh_project(const RadianceParams& P, const void* points, const void* keys, const void* partial, void* out, uint32_t win_samples, uint32_t samples,
+                                 bool accumulate, hipStream_t stream);
 // one thread per point of an irradiance query with one sample (P.first_sample): the ray that sample starts with and the key it goes on from
 hipError_t sol_launch_irradiance_rays(const RadianceParams& P, const void* points, const void* keys, void* rays_out, void* keys_out, hipStream_t stream);
 // the chunk sums of one launch added in chunk order onto 0 (or, accumulate, onto what `out` holds) and written with `samples`

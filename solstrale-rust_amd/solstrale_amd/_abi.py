@@ -235,6 +235,12 @@ class SolIrradianceConfig(C.Structure):
                 ("seed", C.c_uint64), ("key_base", C.c_uint32), ("mode", C.c_uint32)]
 
 
+class SolSh9(C.Structure):
+    """EXTENSION: the answer of sol_irradiance_sh to one point: c[k][channel], the SUMS over `samples` samples of colour x Y_k(direction)
+    for the nine real SH terms up to l = 2. 112 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("c", (C.c_float * 3) * 9), ("samples", C.c_uint32)]
+
+
 SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
 
 
@@ -352,6 +358,8 @@ def load_hip():
     _sig(lib, "sol_irradiance_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_irradiance", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_irradiance_rays", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_irradiance_sh_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
+    _sig(lib, "sol_irradiance_sh", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
     _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _sig(lib, "sol_triangle_from_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolTriangle)])
@@ -381,7 +389,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_query_dev", "sol_query", "sol_camera_rays", "sol_scene_set_camera", "sol_scene_background_flags",
                "sol_triangle_from_vertices", "sol_scene_set_triangles", "sol_scene_set_triangles_dev", "sol_scene_set_triangles_ms", "sol_scene_triangle_records",
                "sol_sphere_from_center", "sol_quad_from_corner", "sol_scene_set_primitives", "sol_scene_primitive_records",
-               "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys", "sol_irradiance_dev", "sol_irradiance", "sol_irradiance_rays"]
+               "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys", "sol_irradiance_dev", "sol_irradiance", "sol_irradiance_rays",
+               "sol_irradiance_sh_dev", "sol_irradiance_sh"]
 
 
 def load_host():

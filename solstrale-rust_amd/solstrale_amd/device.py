@@ -108,6 +108,39 @@ def quad_from_corner(q, u, v, out=None):
     return out
 
 
+# The constants of csrc/sol_sh.h: the fp32 roundings of sqrt(1/(4 pi)), sqrt(3/(4 pi)), sqrt(15/(4 pi)), sqrt(5/(16 pi)), sqrt(15/(16 pi)).
+_SH9_K = tuple(np.float32(k) for k in (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396))
+
+
+def sh9(directions):
+    """The nine real SH terms up to l = 2 of sol_irradiance_sh on directions [..., 3], in numpy float32 and the bracketing of csrc/sol_sh.h, so
+    bit for bit what the device multiplies a sample's colour by: order (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2), no
+    Condon-Shortley sign, the direction as it comes (not normalised). Returns [..., 9] float32 - the caller's half of a reconstruction
+    (sum_k L_k Y_k(n)) and of sh9_irradiance."""
+    d = np.asarray(directions, dtype=np.float32)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    k0, k1, k2, k3, k4 = _SH9_K
+    out = np.empty(d.shape[:-1] + (9,), dtype=np.float32)
+    out[..., 0] = k0
+    out[..., 1] = k1 * y
+    out[..., 2] = k1 * z
+    out[..., 3] = k1 * x
+    out[..., 4] = (k2 * x) * y
+    out[..., 5] = (k2 * y) * z
+    out[..., 6] = k3 * ((np.float32(3.0) * (z * z)) - np.float32(1.0))
+    out[..., 7] = (k2 * x) * z
+    out[..., 8] = k4 * ((x * x) - (y * y))
+    return out
+
+
+def sh9_irradiance(L, normals):
+    """Irradiance E(n) = sum_k A_l(k) L_k Y_k(n) for unit normals [m, 3] from radiance coefficients L [..., 9, 3] (SPHERE mode: L = 4 pi x sh /
+    samples), with the cosine lobe's zonal factors A = (pi, 2 pi / 3, pi / 4) for l = 0, 1, 2. float64; returns [..., m, 3]."""
+    a = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+    y = sh9(normals).astype(np.float64)
+    return np.einsum("mk,...kc->...mc", y * a, np.asarray(L, dtype=np.float64))
+
+
 class DeviceScene:
     """sol_scene_create .. sol_scene_destroy"""
 
@@ -459,8 +492,9 @@ class DeviceScene:
                                      seed=int(seed), key_base=int(key_base) & 0xFFFFFFFF)
         return self._radiance(self.lib.sol_radiance, self.lib.sol_radiance_dev, "rays", "origin xyz, tmin, direction xyz, tmax", rays, keys, cfg)
 
-    def _radiance(self, host_fn, dev_fn, what, row, rays, keys, cfg):
-        """The two routes radiance() and irradiance() share: `rays` are the [n, 8] rows (`what`: their name in messages, `row`: their words)."""
+    def _radiance(self, host_fn, dev_fn, what, row, rays, keys, cfg, words=4):
+        """The two routes radiance(), irradiance() and irradiance_sh() share: `rays` are the [n, 8] rows (`what`: their name in messages, `row`:
+        their words), `words` the 32-bit words of an answer (4: a SolRadiance, returned split into sums and counts; 28: a SolSh9, returned raw)."""
         if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: the library stages the arrays itself
             a = np.ascontiguousarray(rays, dtype=np.float32)
             if a.ndim != 2 or a.shape[1] != 8:
@@ -471,12 +505,14 @@ class DeviceScene:
                 if k.shape != (a.shape[0], 2):
                     raise ValueError(f"keys: an [n, 2] uint32 array of (pixel, first_draw), one row per row of {what}")
                 k = np.ascontiguousarray(k)
-            out = np.zeros((a.shape[0], 4), dtype=np.float32)
+            out = np.zeros((a.shape[0], words), dtype=np.float32)
             self._chk(host_fn(self.h, a.ctypes.data, None if k is None else k.ctypes.data, a.shape[0], C.byref(cfg), out.ctypes.data))
+            if words != 4:
+                return out
             return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
         import torch
         n = self._device_rows(what, rays, keys)
-        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        out = torch.empty((n, words), dtype=torch.float32, device=rays.device)
         torch.cuda.current_stream(rays.device).synchronize()  # (the rays may still be in the making on torch's stream: the scene's is another)
         self._chk(dev_fn(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(cfg),
                          C.c_void_p(out.data_ptr())))
@@ -535,6 +571,20 @@ class DeviceScene:
                                                C.c_void_p(rays.data_ptr()), C.c_void_p(keys_out.data_ptr())))
         self.sync()
         return rays, keys_out
+
+    # ---- SH irradiance queries (EXTENSION) ----
+    def irradiance_sh(self, points, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="sphere"):
+        """sol_irradiance_sh: irradiance()'s gather projected onto the nine real SH terms up to l = 2 - per point the SUMS over the samples of
+        colour x sh9(direction), in radiance()'s association. Host arrays return (sh [n, 9, 3] float32 sums, counts [n] uint32); device tensors
+        go through sol_irradiance_sh_dev without a host copy and return one [n, 28] float32 device tensor of the raw rows (27 sums, k-major, and
+        the bits of the sample count). "sphere": 4 pi x sh / samples are the radiance coefficients L_k, and sh9_irradiance(L, normals) the
+        irradiance for any normal; "cosine": pi x sh / samples estimates the cosine-weighted projection about the point's normal. points, keys,
+        key_base, first_draw and the waits of the two routes are irradiance()'s."""
+        cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
+        rows = self._radiance(self.lib.sol_irradiance_sh, self.lib.sol_irradiance_sh_dev, "points", "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=28)
+        if isinstance(rows, np.ndarray):
+            return np.ascontiguousarray(rows[:, :27]).reshape(-1, 9, 3), np.ascontiguousarray(rows[:, 27]).view(np.uint32)
+        return rows
 
     def camera_ray_keys(self, x0, y0, x1, y1, sample, seed):
         """sol_camera_ray_keys: (pixel, first_draw) of the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 2] int32 device
