@@ -796,6 +796,45 @@ int sol_irradiance_sh_dev(SolScene* scene, const void* points_dev, const void* k
 /* Host arrays, staged through buffers the handle owns; blocks. */
 int sol_irradiance_sh(SolScene* scene, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolSh9* out);
 
+/* ---- visibility gathers (EXTENSION, not in the reference) -----------------------------------------------------------------
+ * "How much of the hemisphere, or of the sphere, is open at this point?" - ambient occlusion and bent normals for lightmap texels and vertices,
+ * sky visibility for probes, and the hit-distance moments an irradiance volume keeps beside its SH coefficients (mean and mean-square distance,
+ * the Chebyshev test against light leaking through walls). One call in place of 2 x samples launches (sol_irradiance_rays + sol_query_dev per
+ * sample) and a reduction of the caller's.
+ *   Points.   Points, their validity, keys, key_base, first_draw, seed, first_sample, samples and the two direction modes are sol_irradiance's,
+ *             word for word; the configuration is SolIrradianceConfig as it stands. A point's tmax is the occlusion radius, in units of the
+ *             drawn direction's length (1 up to rounding). mode is sol_query's: SOL_QUERY_OCCLUDED or SOL_QUERY_CLOSEST. An invalid point
+ *             answers eight zero words, decided before any search.
+ *   Samples.  For sample s of a valid point i the ray is exactly the row sol_irradiance_rays writes for (point, s): position, tmin, the
+ *             direction d drawn from the stream of (seed, key, s) with its counter at first_draw, tmax. Its status is what sol_query answers
+ *             for that ray in the given mode - the (t, dfs) rule, and in a scene with needle triangles the searches behind a refused hit: 63
+ *             of them, each up to the ray's own tmax, then a miss.
+ *               SOL_RAY_HIT   hits += 1; under SOL_QUERY_CLOSEST also t_sum += t and t2_sum += fl(t x t), t being SolRayHit.t - each one fp32
+ *                             rounding, no fused multiply-add. A hit adds nothing to b.
+ *               SOL_RAY_MISS  open += 1 and b += d per component. A miss adds nothing to the t sums.
+ *             A made ray that is itself invalid is searched for nothing and counted in neither counter; that happens only when the normal's
+ *             squared length is not a normal fp32 number (the condition sol_irradiance states). So hits + open <= samples, with equality for
+ *             every point that meets the condition. Under SOL_QUERY_OCCLUDED the counters and b are, on the bits, those of
+ *             SOL_QUERY_CLOSEST (the searches stop early where they may); t_sum and t2_sum stay +0.
+ *   Sums.     The float fields are SUMS in sol_radiance's association: chunks of 16 samples counted from first_sample, a chunk sum
+ *             0 + x + x .. in sample order, the result ((0 + chunk0) + chunk1) + ..; the counters are plain integers; `samples` is the sample count.
+ *   Estimators. SOL_IRRADIANCE_COSINE: ambient occlusion (the open share of the cosine-weighted hemisphere) = open / samples; the bent normal
+ *             is b normalised. SOL_IRRADIANCE_SPHERE: sky visibility = open / samples. With a finite radius tmax the mean hit distance
+ *             clamped to it is (t_sum + open x tmax) / samples, and the second moment (t2_sum + open x tmax x tmax) / samples.
+ *   Neutral.  As sol_query and sol_radiance: neither the accumulator, the auxiliary planes, the render's work counter, the partition, an
+ *             adaptive session nor SolStats is touched. The scratch is shared with the radiance queries; calls on one handle are ordered by
+ *             its stream.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for and in this order: a null scene; an unknown mode (sol_query's
+ * sentence); the configuration and n as sol_irradiance judges them, in its order and words; then n == 0 succeeds on any scene and touches
+ * nothing; a scene with a constant medium (sol_query's sentence: a medium's hit is a draw keyed by a path); a null point or output pointer.
+ * SOL_EDEVICE without a GPU comes after all of these. There is no host mirror. */
+/* 32 bytes; 16-byte aligned in device memory; sums and counts, not means */
+typedef struct SolVisibility { float bx, by, bz; uint32_t open; float t_sum, t2_sum; uint32_t hits, samples; } SolVisibility;
+/* Device pointers (n SolRay points, n SolRayKey or NULL, n SolVisibility out, on the scene's device), on the scene's stream, asynchronous. */
+int sol_visibility_dev(SolScene* scene, int mode, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_visibility(SolScene* scene, int mode, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolVisibility* out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

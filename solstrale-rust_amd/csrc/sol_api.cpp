@@ -413,13 +413,22 @@ int query_device_check() {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
   return SOL_OK;
 }
+// The two refusals the visibility gathers share with the ray queries, each in one sentence.
+int query_mode_check(const char* fn, int mode) {
+  if (mode != SOL_QUERY_CLOSEST && mode != SOL_QUERY_OCCLUDED) return sol_fail(SOL_EINVAL, "%s: unknown mode %d (SOL_QUERY_CLOSEST or SOL_QUERY_OCCLUDED)", fn, mode);
+  return SOL_OK;
+}
+int query_medium_check(const SolScene* s, const char* fn) {
+  if (s->has_medium)
+    return sol_fail(SOL_EINVAL, "%s: the scene has a constant medium - its hits are random draws keyed by a path, which a query ray does not have", fn);
+  return SOL_OK;
+}
 // What both routes refuse, before the device is touched. *go = false: nothing to do (n == 0).
 int query_check(const SolScene* s, const char* fn, int mode, const void* rays, size_t n, const void* out, bool* go) {
   *go = false;
   if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if (mode != SOL_QUERY_CLOSEST && mode != SOL_QUERY_OCCLUDED) return sol_fail(SOL_EINVAL, "%s: unknown mode %d (SOL_QUERY_CLOSEST or SOL_QUERY_OCCLUDED)", fn, mode);
-  if (s->has_medium)
-    return sol_fail(SOL_EINVAL, "%s: the scene has a constant medium - its hits are random draws keyed by a path, which a query ray does not have", fn);
+  if (const int rc = query_mode_check(fn, mode)) return rc;
+  if (const int rc = query_medium_check(s, fn)) return rc;
   if (n > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: %zu rays in one call (at most 2^31)", fn, n);
   if (n == 0) return SOL_OK;
   if (!rays || !out) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? "ray" : "output");
@@ -756,6 +765,113 @@ int sol_camera_ray_keys(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint
   if ((rc = sol_scene_to_device(s))) return rc;
   HIP_TRY(sol_launch_camera_ray_keys(s->mirror.dev.get(), x0, y0, x1 - x0, y1 - y0, sample, seed, keys_dev, s->stream));
   return SOL_OK;
+}
+
+}  // extern "C"
+
+// ---- visibility gathers (include/solstrale_hip.h; kernels: sol_visibility.hip) ----
+namespace {
+static_assert(sizeof(SolVisibility) == 2 * sizeof(SolRadiance), "a SolVisibility row is two dwordx4: two rows of the radiance queries' buffers");
+
+// What both routes refuse; nothing here needs a device, and nothing in front of n == 0 reads the handle. *go = false: nothing to do.
+int visibility_check(const SolScene* s, const char* fn, int mode, const void* points, size_t n, const SolRadianceConfig* cfg, const void* out, bool* go) {
+  *go = false;
+  if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
+  if (const int rc = query_mode_check(fn, mode)) return rc;
+  if (const int rc = radiance_config_check(fn, IRRADIANCE, n, cfg)) return rc;
+  if (n == 0) return SOL_OK;
+  if (const int rc = query_medium_check(s, fn)) return rc;
+  if (!points || !out) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !points ? "point" : "output");
+  *go = true;
+  return SOL_OK;
+}
+
+// n <= 2^31 points (and keys, or null) in device memory, n SolVisibility out, on the scene's stream: radiance_launch's plan with this family's
+// kernels. One chunk: one launch writes the answers. More: the chunk rows go through the radiance queries' partial buffer, two of its rows
+// each, under the same bound - the call is split over points (answers are per point) and over windows of chunks (the resolve kernel carries
+// a point's sums from one window to the next in `out`: the same additions in the same order).
+int visibility_launch(SolScene* s, int mode, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
+  int rc;
+  if ((rc = sol_scene_to_device(s))) return rc;
+  const bool any = mode == SOL_QUERY_OCCLUDED;
+  const int bpc = sol_visibility_blocks_per_cu(any, s->strict_triangles);
+  const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
+  if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
+  const uint32_t total_chunks = (uint32_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
+  const size_t max_rows = std::max<size_t>(64, std::min<size_t>(s->rad_partial_max_rows, (size_t)1 << 31) / 2);  // in visibility rows
+  const size_t win_chunks = std::min<size_t>(total_chunks, max_rows / 64);
+  const size_t slice_points = total_chunks == 1 ? n : std::max<size_t>(64, max_rows / win_chunks / 64 * 64);
+  for (size_t at = 0; at < n; at += slice_points) {
+    const size_t k = std::min(slice_points, n - at);
+    RadianceParams P{};
+    P.n_rays = (uint32_t)k;
+    P.n_groups = (uint32_t)((k + 63) / 64);
+    P.end_sample = cfg.first_sample + cfg.samples;
+    P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
+    P.key_base = key_base + (uint32_t)at;
+    P.first_draw = cfg.first_draw;
+    P.switch_below = s->switch_below;
+    P.direct = total_chunks == 1 ? 1u : 0u;
+    P.mode = cfg.reserved;
+    const char* points_at = (const char*)points_dev + at * sizeof(SolRay);
+    const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
+    char* out_at = (char*)out_dev + at * sizeof(SolVisibility);
+    if (!P.direct && (rc = s->rad_partial.reserve(s->stream, (size_t)P.n_groups * 64 * win_chunks * 2))) return rc;
+    for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
+      P.n_chunks = (uint32_t)std::min<size_t>(win_chunks, total_chunks - c0);
+      P.first_sample = cfg.first_sample + (uint32_t)c0 * SOL_CHUNK;
+      const uint64_t items = (uint64_t)P.n_chunks * P.n_groups * 64u;  // (<= 2^31: far below the headroom of the 32-bit work counter, SOL_MAX_ITEMS)
+      P.n_items = (uint32_t)items;
+      // the grid and the spill tail of THIS launch
+      uint32_t grid;
+      if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
+      P.total_threads = grid * SOL_WG;
+      HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
+      HIP_TRY(sol_launch_visibility(s->mirror.dev.get(), P, any, may_spill, s->strict_triangles, points_at, keys_at, out_at, s->rad_partial.get(), s->rad_work.get(),
+                                    s->rad_spill.get(), grid, s->stream));
+      if (!P.direct) HIP_TRY(sol_launch_visibility_resolve(P, points_at, s->rad_partial.get(), out_at, cfg.samples, c0 != 0, s->stream));
+    }
+  }
+  return SOL_OK;
+}
+
+// The host route: radiance_staged's buffers, the answers' staging grown to the two rows of a SolVisibility.
+int visibility_staged(SolScene* s, int mode, const SolRay* points, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, SolVisibility* out) {
+  int rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
+  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap * 2))) return rc;
+  for (size_t at = 0; at < n; at += cap) {  // (answers are per point: the split changes nothing)
+    const size_t k = std::min(cap, n - at);
+    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), points + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
+    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
+    if ((rc = visibility_launch(s, mode, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get()))) return rc;
+    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolVisibility), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+  }
+  return SOL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int sol_visibility_dev(SolScene* s, int mode, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = visibility_check(s, "sol_visibility_dev", mode, points_dev, n, config ? &cfg : nullptr, out_dev, &go)) || !go || (rc = query_device_check())) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return visibility_launch(s, mode, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev);
+}
+
+int sol_visibility(SolScene* s, int mode, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolVisibility* out) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = visibility_check(s, "sol_visibility", mode, points, n, config ? &cfg : nullptr, out, &go)) || !go || (rc = query_device_check())) return rc;
+  return visibility_staged(s, mode, points, keys, n, cfg, out);
 }
 
 }  // extern "C"

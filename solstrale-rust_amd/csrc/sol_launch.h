@@ -82,6 +82,15 @@ hipError_t sol_launch_radiance_resolve(const RadianceParams& P, const void* rays
                                        hipStream_t stream);
 hipError_t sol_launch_camera_ray_keys(const DevScene* dS, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t sample, uint64_t seed, void* keys,
                                       hipStream_t stream);
+// ---- sol_visibility.hip: visibility gathers. One launch: RadianceParams as for a gather launch of sol_radiance.hip - n_rays points,
+// work item = (point, chunk), chunk-major, handed out through `work` (zeroed by the caller) -, answered as a ray query in mode `any` answers each sample's ray.
+// out: n_rays SolVisibility when P.direct, else the chunk rows go to `partial`, [chunk][n_groups * 64] rows of two dwordx4 ----
+hipError_t sol_launch_visibility(const DevScene* dS, const RadianceParams& P, bool any, bool may_spill, bool strict, const void* points, const void* keys, void* out,
+                                 void* partial, uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream);
+int sol_visibility_blocks_per_cu(bool any, bool strict);
+// the chunk rows of one launch added in chunk order onto 0 (or, accumulate, onto what `out` holds) and written with `samples`
+hipError_t sol_launch_visibility_resolve(const RadianceParams& P, const void* points, const void* partial, void* out, uint32_t samples, bool accumulate,
+                                         hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

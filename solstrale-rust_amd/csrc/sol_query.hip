@@ -27,7 +27,8 @@ struct QueryLane {
   bool busy;          // the lane holds a ray that is not answered yet
 };
 
-// (query_ray_valid, the validity rule of a ray: sol_ray.h - the radiance queries decide by the same one)
+// (query_ray_valid, the validity rule of a ray: sol_ray.h - the radiance queries decide by the same one; query_when_settled and
+// query_occluded_done, the needle rule's restarts and the occlusion early-out: sol_ray.h - the visibility gathers answer by the same ones)
 
 template <bool ANY>
 DEV void query_write(const DevScene& S, const Stack& st, void* __restrict__ out, uint32_t i, uint32_t status, const Hit& h) {
@@ -69,31 +70,22 @@ DEV void query_take(const DevScene& S, const Stack& st, const float4* __restrict
   q.busy = true;
 }
 
-// The lane's search is over (t.cur == REF_DONE). True: the ray is answered and written. False (STRICT): its closest hit was a triangle the
-// consistency rule refuses, and the lane searches the same ray again behind it - at most 63 times, then the ray misses (closest_hit's guard).
+// The lane's search is over (t.cur == REF_DONE): the ray is answered and written - or (STRICT) its closest hit was a triangle the consistency
+// rule refuses, and the lane searches the same ray again behind it, at most 63 times, then the ray misses (query_when_settled, sol_ray.h).
 template <bool ANY, bool STRICT>
-DEV bool query_settle(const DevScene& S, const Stack& st, void* __restrict__ out, QueryLane& q) {
-  if (STRICT && SOL_REF_KIND(q.t.h.ref) != SOL_REF_NONE && !trav_accept_or_restart(S, q.t, st)) {
-    q.t.h.t = q.tmax;  // (trav_accept_or_restart starts over with an open interval: the query's own upper end again)
-    if (q.left != 0u) { q.left--; return false; }
-    q.t.cur = REF_DONE;  // (the search state holds no hit after the restart: a miss)
-  }
-  const bool hit = SOL_REF_KIND(q.t.h.ref) != SOL_REF_NONE;
-  query_write<ANY>(S, st, out, q.index, hit ? SOL_RAY_HIT : SOL_RAY_MISS, q.t.h);
-  q.busy = false;
-  return true;
+DEV void query_settle(const DevScene& S, const Stack& st, void* __restrict__ out, QueryLane& q) {
+  query_when_settled<STRICT>(S, st, q.t, q.tmax, q.left, [&]() __attribute__((always_inline)) {
+    const bool hit = SOL_REF_KIND(q.t.h.ref) != SOL_REF_NONE;
+    query_write<ANY>(S, st, out, q.index, hit ? SOL_RAY_HIT : SOL_RAY_MISS, q.t.h);
+    q.busy = false;
+  });
 }
 
-// One step of the wave's searches. ANY: a lane whose search holds an accepted primitive is done - in a scene with needles only when that
-// primitive is not a triangle (a triangle must pass the consistency rule first: its lane runs the bounded closest search to the end, and a
-// sphere or a quad inside the interval stays a hit whatever the rule refuses).
+// One step of the wave's searches. ANY: a lane whose search holds an accepted primitive is done (query_occluded_done, sol_ray.h).
 template <bool ANY, bool STRICT>
 DEV void query_step(const DevScene& S, const Stack& st, const Rng& rng, Counters& cnt, QueryLane& q, bool act) {
   trav_step_wave<false, false, STRICT>(S, q.t, act, st, rng, 0u, cnt);
-  if (ANY && act) {
-    const uint32_t kind = SOL_REF_KIND(q.t.h.ref);
-    if (kind != SOL_REF_NONE && (!STRICT || kind != SOL_REF_TRIANGLE)) q.t.cur = REF_DONE;
-  }
+  if (ANY) query_occluded_done<STRICT>(q.t, act);
 }
 
 }  // namespace

@@ -299,7 +299,8 @@ struct SolScene {
   // Radiance queries (sol_radiance.hip): their own work counter, partial buffer (chunk sums, 16 bytes per (chunk, ray); grown on
   // demand up to a bound), spill tail and host-route staging (rays, keys, answers; rad_cap rays each). None of them is the render launch's.
   // The SH irradiance queries share all of it: a row of rad_partial is then the colour of one (sample, point), under the same
-  // bound but never below 1024 rows, and rad_out holds seven rows per staged point.
+  // bound but never below 1024 rows, and rad_out holds seven rows per staged point. So do the visibility gathers (sol_visibility.hip, DESIGN.md
+  // 22): a chunk's row takes two rows of rad_partial, a staged answer two of rad_out.
   DevBuf<uint32_t> rad_work;
   DevBuf<SolRadiance> rad_partial;
   size_t rad_partial_max_rows = (size_t)1 << 24;  // the bound: 256 MiB of chunk sums (SOL_RADIANCE_ROWS)

@@ -1,5 +1,5 @@
 // sol_wave.h -- the pieces of the persistent-wave schedule, shared by the kernels that are assembled from them:
-// sol_render_kernel, sol_radiance_kernel, sol_query_kernel and the A/B sol_render_pool4_kernel. Every piece is force-inlined; the
+// sol_render_kernel, sol_radiance_kernel, sol_query_kernel, sol_visibility_kernel and the A/B sol_render_pool4_kernel. Every piece is force-inlined; the
 // __shared__ arrays stay declared in the kernels (LDS layout is per kernel) and come in as pointers.
 //   wave_search_stack     the search context of a lane: LDS stack, spill tail, pinned node fields, octant and selector tables
 //   wave_reservoir        the wave's reserved work items in LDS, zeroed; wave_take_item hands them out

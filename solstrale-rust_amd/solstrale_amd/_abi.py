@@ -241,6 +241,13 @@ class SolSh9(C.Structure):
     _fields_ = [("c", (C.c_float * 3) * 9), ("samples", C.c_uint32)]
 
 
+class SolVisibility(C.Structure):
+    """EXTENSION: the answer of sol_visibility to one point: the SUM of the open directions (the bent normal, not normalised), the
+    count of open samples, the sums of the hit distances and of their squares, the count of hits and the sample count. 32 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("bx", C.c_float), ("by", C.c_float), ("bz", C.c_float), ("open", C.c_uint32),
+                ("t_sum", C.c_float), ("t2_sum", C.c_float), ("hits", C.c_uint32), ("samples", C.c_uint32)]
+
+
 SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
 
 
@@ -360,6 +367,8 @@ def load_hip():
     _sig(lib, "sol_irradiance_rays", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p, C.c_void_p])
     _sig(lib, "sol_irradiance_sh_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_irradiance_sh", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
+    _sig(lib, "sol_visibility_dev", C.c_int, [P, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
+    _sig(lib, "sol_visibility", C.c_int, [P, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
     _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _sig(lib, "sol_triangle_from_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolTriangle)])
@@ -390,7 +399,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_triangle_from_vertices", "sol_scene_set_triangles", "sol_scene_set_triangles_dev", "sol_scene_set_triangles_ms", "sol_scene_triangle_records",
                "sol_sphere_from_center", "sol_quad_from_corner", "sol_scene_set_primitives", "sol_scene_primitive_records",
                "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys", "sol_irradiance_dev", "sol_irradiance", "sol_irradiance_rays",
-               "sol_irradiance_sh_dev", "sol_irradiance_sh"]
+               "sol_irradiance_sh_dev", "sol_irradiance_sh", "sol_visibility_dev", "sol_visibility"]
 
 
 def load_host():

@@ -493,8 +493,9 @@ class DeviceScene:
         return self._radiance(self.lib.sol_radiance, self.lib.sol_radiance_dev, "rays", "origin xyz, tmin, direction xyz, tmax", rays, keys, cfg)
 
     def _radiance(self, host_fn, dev_fn, what, row, rays, keys, cfg, words=4):
-        """The two routes radiance(), irradiance() and irradiance_sh() share: `rays` are the [n, 8] rows (`what`: their name in messages, `row`:
-        their words), `words` the 32-bit words of an answer (4: a SolRadiance, returned split into sums and counts; 28: a SolSh9, returned raw)."""
+        """The two routes radiance(), irradiance(), irradiance_sh() and visibility() share: `rays` are the [n, 8] rows (`what`: their name in messages,
+        `row`: their words), `words` the 32-bit words of an answer (4: a SolRadiance, returned split into sums and counts; 28: a SolSh9 and 8: a
+        SolVisibility, returned raw)."""
         if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: the library stages the arrays itself
             a = np.ascontiguousarray(rays, dtype=np.float32)
             if a.ndim != 2 or a.shape[1] != 8:
@@ -585,6 +586,31 @@ class DeviceScene:
         if isinstance(rows, np.ndarray):
             return np.ascontiguousarray(rows[:, :27]).reshape(-1, 9, 3), np.ascontiguousarray(rows[:, 27]).view(np.uint32)
         return rows
+
+    # ---- visibility gathers (EXTENSION) ----
+    VISIBILITY_DTYPE = np.dtype([("bent", np.float32, (3,)), ("open", np.uint32), ("t_sum", np.float32), ("t2_sum", np.float32),
+                                 ("hits", np.uint32), ("samples", np.uint32)])
+
+    def visibility(self, points, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="cosine", distances=False):
+        """sol_visibility: how much of the hemisphere ("cosine") or of the sphere ("sphere") is open at the caller's points - rows of (position xyz,
+        tmin, normal xyz, tmax), tmax being the occlusion radius. Every sample draws the direction irradiance() would draw and is answered as
+        occluded() answers that ray (distances=True: as closest_hits() does, which also sums the hit distances and their squares). Per point:
+        `open` samples that missed and `bent`, the sum of their directions; `hits`, `t_sum`, `t2_sum`; `samples`. open / samples is the ambient
+        occlusion or the sky visibility, bent normalised the bent normal. Host arrays go the host route and return a structured array
+        (VISIBILITY_DTYPE); device tensors go through sol_visibility_dev without a host copy and return the raw [n, 8] float32 rows
+        (visibility_to_numpy views them as the structured array). points, keys, key_base, first_draw and the waits of the two routes are irradiance()'s."""
+        cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
+        qmode = _abi.SOL_QUERY_CLOSEST if distances else _abi.SOL_QUERY_OCCLUDED
+        rows = self._radiance(lambda h, *a: self.lib.sol_visibility(h, qmode, *a), lambda h, *a: self.lib.sol_visibility_dev(h, qmode, *a), "points",
+                              "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=8)
+        if isinstance(rows, np.ndarray):
+            return rows.view(self.VISIBILITY_DTYPE).reshape(-1)
+        return rows
+
+    @classmethod
+    def visibility_to_numpy(cls, rows):
+        """The [n, 8] float32 device tensor visibility() returned, as the structured host array."""
+        return np.ascontiguousarray(rows.cpu().numpy()).view(cls.VISIBILITY_DTYPE).reshape(-1)
 
     def camera_ray_keys(self, x0, y0, x1, y1, sample, seed):
         """sol_camera_ray_keys: (pixel, first_draw) of the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 2] int32 device
