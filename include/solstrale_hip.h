@@ -835,6 +835,75 @@ int sol_visibility_dev(SolScene* scene, int mode, const void* points_dev, const 
 /* Host arrays, staged through buffers the handle owns; blocks. */
 int sol_visibility(SolScene* scene, int mode, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolVisibility* out);
 
+/* ---- lightmap texel points (EXTENSION, not in the reference) ---------------------------------------------------------------
+ * The gathers above take points the caller already has. For a lightmap the points are the texels of an atlas: sol_lightmap_points rasterises
+ * a mesh's lightmap UVs on the device into the W x H SolRay point rows sol_irradiance, sol_irradiance_sh and sol_visibility take, and
+ * sol_lightmap_dilate pads the chart borders of the baked result, so that vertices, uvs -> points -> gather -> dilate is three calls on device
+ * memory. The geometry is the caller's (typically what sol_scene_set_triangles gets, as floats); the handle supplies the device, the stream and
+ * scratch. Nothing is traced: a scene with a constant medium is not refused. All arithmetic is fp32, every operation rounded once, no fused
+ * multiply-add, `/` and sqrt correctly rounded; csrc/sol_lightmap.h is the rule as code and tests/lightmap_ref.py its restatement in numpy.
+ *   Atlas.    Texel (i, j), i in [0, W) along u, j in [0, H) along v with row 0 at v = 0, lies at index j * W + i; its centre is
+ *             P = ((float)i + 0.5f, (float)j + 0.5f). A UV corner in texel space is (u * (float)W, v * (float)H); A, B, C are a triangle's three.
+ *   Skipped.  A triangle claims nothing when one of its 6 UV words, 9 position words or (when given) 9 normal words is not finite; when
+ *             area2 = (Bx - Ax) * (Cy - Ay) - (By - Ay) * (Cx - Ax) is zero or not finite; or when the squared length of
+ *             cross3(v1 - v0, v2 - v0) is not a finite, normal fp32 number.
+ *   Candidates. A triangle claims only among the texels whose closed square [i, i + 1] x [j, j + 1] overlaps its closed texel-space bounding
+ *             box: (float)i <= max x && (float)(i + 1) >= min x, and likewise in y.
+ *   Edges.    edge(Q, R, P) = (Rx - Qx) * (Py - Qy) - (Ry - Qy) * (Px - Qx), always evaluated with (Q, R) in lexicographic order (x, then y) and
+ *             negated when the triangle's own order is the other one: two triangles that share an edge compute the same number for it, a centre
+ *             on the edge is inside both and none falls between them. e0 = edge(B, C, P), e1 = edge(C, A, P), e2 = edge(A, B, P); when
+ *             area2 < 0 all four are negated.
+ *   Claims.   Centre inside: e0 >= 0 && e1 >= 0 && e2 >= 0 at the centre. Conservative only (SOL_LIGHTMAP_CONSERVATIVE, centre not inside):
+ *             for each of the three edges the maximum over the square's four corners is >= 0 - evaluated as "some corner's value is >= 0".
+ *   Owner.    Among the triangles with the centre inside the lowest index; where there is none, the lowest index among the conservative-only
+ *             claims. Whatever the scheduling: one atomic minimum per claim on the key index | (conservative_only << 31).
+ *   Row.      b1 = e1 / area2, b2 = e2 / area2, b0 = (1 - b1) - b2. A conservative-only texel clamps first: b_k' = b_k > 0 ? b_k : 0,
+ *             s = (b0' + b1') + b2', b1 = b1' / s, b2 = b2' / s, b0 = (1 - b1) - b2. Position per component ((v0 * b0) + (v1 * b1)) + (v2 * b2).
+ *             Normal: with normals the same interpolation, then n / sqrt(n.x * n.x + n.y * n.y + n.z * n.z); when that squared length is not a
+ *             finite, normal number, or normals is null, the same of cross3(v1 - v0, v2 - v0). The row is (position, tmin, normal, tmax), the
+ *             SolTexel (index, b1, b2, 1: centre inside or 2: conservative only).
+ *   Unowned.  Eight zero words - an invalid point, which the gathers answer with zeros before any search - and the SolTexel (0xFFFFFFFF, 0, 0, 0).
+ * Neutral as the queries are: neither the accumulator, the planes, the work counter nor SolStats is touched.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for and in this order: a null scene or configuration; a wrong
+ * size; reserved != 0; unknown flags; width or height of 0 or above 16384; tmin / tmax failing the point rule (0 <= tmin <= tmax, tmin finite,
+ * tmax not NaN); n_triangles > 2^31 - 2; with n_triangles > 0 a null vertex or UV pointer; a null output pointer. n_triangles == 0 writes an
+ * all-empty atlas. SOL_EDEVICE without a GPU comes after all of these. There is no host mirror. */
+#define SOL_LIGHTMAP_CONSERVATIVE 1u
+#define SOL_LIGHTMAP_MAX_SIZE 16384u
+#define SOL_TEXEL_NONE 0xFFFFFFFFu
+typedef struct SolLightmapConfig {
+  uint32_t size, width, height, flags; /* size = sizeof(SolLightmapConfig); flags: SOL_LIGHTMAP_CONSERVATIVE */
+  float tmin, tmax;                    /* written into every point row */
+  uint32_t reserved[2];                /* zero */
+} SolLightmapConfig;
+/* 16 bytes; 16-byte aligned in device memory */
+typedef struct SolTexel {
+  uint32_t triangle; /* SOL_TEXEL_NONE: no owner */
+  float b1, b2;
+  uint32_t flags;    /* 1: centre inside; 2: conservative only; 0: no owner */
+} SolTexel;
+/* Device pointers on the scene's device (n x 9 floats, n x 9 floats or NULL, n x 6 floats; W x H SolRay and W x H SolTexel out, 16-byte aligned),
+ * on the scene's stream, asynchronous. */
+int sol_lightmap_points_dev(SolScene* scene, const void* vertices_dev, const void* normals_dev, const void* uvs_dev, size_t n_triangles,
+                            const SolLightmapConfig* config, void* points_out_dev, void* texels_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_points(SolScene* scene, const float* vertices, const float* normals, const float* uvs, size_t n_triangles, const SolLightmapConfig* config,
+                        SolRay* points_out, SolTexel* texels_out);
+/* Border dilation: what finishes a bake, so that bilinear filtering does not bleed black into the chart borders. values: W x H rows of stride_bytes
+ * (a multiple of 4, at least 4 x channels) whose leading `channels` words (1..32) are floats - SolRadiance (3 channels, stride 16), SolSh9 (27,
+ * 112), plain float planes. Rows of owned texels (texels[x].triangle != SOL_TEXEL_NONE) are copied whole. In pass k = 1 .. passes (at most 254)
+ * a texel uncovered at the pass's start with at least one covered neighbour among its eight (none outside the atlas, no wrap) is filled: per
+ * channel (0 + x + x ..) / (float)count over the covered neighbours in the order (di, dj) = (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1),
+ * (1,1); the rest of its row is zero; it counts as covered from the next pass on. A row never filled is zero. pass_of (or NULL): per texel 0
+ * owned, k filled in pass k, 255 never filled. out may not be values.
+ * SOL_EINVAL before the device is looked for, in this order: a null scene; a null texel, value or output pointer; width or height of 0 or
+ * above 16384; channels outside 1..32; a stride that is no multiple of 4 or below 4 x channels; passes above 254; out == values. */
+int sol_lightmap_dilate_dev(SolScene* scene, const void* texels_dev, uint32_t width, uint32_t height, const void* values_dev, uint32_t channels,
+                            uint32_t stride_bytes, uint32_t passes, void* out_dev, void* pass_of_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_dilate(SolScene* scene, const SolTexel* texels, uint32_t width, uint32_t height, const void* values, uint32_t channels,
+                        uint32_t stride_bytes, uint32_t passes, void* out, uint8_t* pass_of_out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

@@ -91,6 +91,17 @@ int sol_visibility_blocks_per_cu(bool any, bool strict);
 // the chunk rows of one launch added in chunk order onto 0 (or, accumulate, onto what `out` holds) and written with `samples`
 hipError_t sol_launch_visibility_resolve(const RadianceParams& P, const void* points, const void* partial, void* out, uint32_t samples, bool accumulate,
                                          hipStream_t stream);
+// ---- sol_lightmap.hip: lightmap texel points and border dilation. owner: W x H words, all 0xFFFFFFFF; ctr: two words, zero; list0,
+// list1: n words each - all on `stream` before the launch. A claim walks a box of at most small_max texels with one lane, one of at most tiles_max 8x8
+// tiles with one wave, a larger one with every wave of `persistent_blocks` blocks. points: W x H SolRay, texels: W x H SolTexel, 16-byte aligned ----
+hipError_t sol_launch_lightmap_points(const float* vertices, const float* normals, const float* uvs, uint32_t n, uint32_t W, uint32_t H, bool conservative,
+                                      float tmin, float tmax, uint32_t small_max, uint32_t tiles_max, uint32_t* owner, uint32_t* ctr, uint32_t* list0,
+                                      uint32_t* list1, uint32_t persistent_blocks, void* points, void* texels, hipStream_t stream);
+// out <- the owned rows of `values`, zero rows elsewhere; cover <- 0 (owned) or 255. Then pass k = 1, 2, ..: cover_out <- cover_in with the texels filled now
+hipError_t sol_launch_lightmap_dilate_begin(const void* texels, uint32_t n_texels, const void* values, uint32_t stride_words, void* out, uint8_t* cover,
+                                            hipStream_t stream);
+hipError_t sol_launch_lightmap_dilate_pass(uint32_t W, uint32_t H, uint32_t channels, uint32_t stride_words, uint32_t pass, void* out, const uint8_t* cover_in,
+                                           uint8_t* cover_out, hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

@@ -9,6 +9,7 @@
 //   sol_launch.h    the launch wrappers of the .hip files (each family: one variant table for the launch and the occupancy query; sol_blocks_per_cu)
 //   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
 //   sol_geometry.cpp sol_scene_set_triangles / sol_scene_set_primitives: the triangles, spheres and quads of a live scene moved, records and tree boxes recomputed on the device (sol_geometry.hip)
+//   sol_lightmap.cpp sol_lightmap_points / sol_lightmap_dilate: lightmap UVs rasterised into gather points, chart borders dilated (sol_lightmap.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
 // There is NO CPU fallback: without a HIP device every compute entry point fails with SOL_EDEVICE.
@@ -129,6 +130,7 @@ struct SolDevOverrides {
   bool pool_count = false;       // SOL_POOL_COUNT (pool kernel: counted renders run its instrumented build - phase statistics)
   int pool_slots = 0, wf_slots = 0, wf_min_items = -1;  // SOL_POOL_SLOTS / SOL_WF_SLOTS / SOL_WF_MIN_ITEMS (v2 / v3)
   std::string rccl_lib;          // SOL_RCCL_LIB: the communication library to dlopen instead of librccl.so.1 (tests)
+  int lightmap_claim = 0;        // SOL_LIGHTMAP_CLAIM=lane|wave: the claim pass of sol_lightmap_points as one of its two plain candidates (1, 2; 0: the product's hybrid)
   bool verbose = false;          // SOL_VERBOSE
 };
 SolDevOverrides sol_dev_overrides();
@@ -306,6 +308,12 @@ struct SolScene {
   size_t rad_partial_max_rows = (size_t)1 << 24;  // the bound: 256 MiB of chunk sums (SOL_RADIANCE_ROWS)
   DevBuf<uint32_t> rad_spill;
   DevBuf<SolRay> rad_in; DevBuf<SolRayKey> rad_keys; DevBuf<SolRadiance> rad_out;
+  // Lightmap texel points and dilation (sol_lightmap.hip). lm_owner: the scratch - 16 words of list counters, the W x H owner words
+  // of the claim pass, then its two work lists of n_triangles words each; a dilation keeps its two coverage planes (a byte per texel each) in the
+  // same words. lm_stage: what the host routes stage, inputs and outputs. lm_small_max / lm_tiles_max: the claim pass's thresholds (SOL_LIGHTMAP_CLAIM).
+  DevBuf<uint32_t> lm_owner;
+  DevBuf<char> lm_stage;
+  uint32_t lm_small_max = 16, lm_tiles_max = 64;
   SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).

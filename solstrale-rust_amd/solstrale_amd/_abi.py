@@ -248,6 +248,21 @@ class SolVisibility(C.Structure):
                 ("t_sum", C.c_float), ("t2_sum", C.c_float), ("hits", C.c_uint32), ("samples", C.c_uint32)]
 
 
+class SolLightmapConfig(C.Structure):
+    """EXTENSION: the atlas of sol_lightmap_points: size = sizeof, W x H texels, flags (SOL_LIGHTMAP_CONSERVATIVE), the tmin and tmax
+    written into every point row. 32 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("flags", C.c_uint32), ("tmin", C.c_float), ("tmax", C.c_float),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class SolTexel(C.Structure):
+    """EXTENSION: what sol_lightmap_points knows of one texel: the owning triangle (SOL_TEXEL_NONE: none), the barycentrics b1, b2 of the point and
+    how it was claimed (1: centre inside, 2: conservative only). 16 bytes."""
+    _fields_ = [("triangle", C.c_uint32), ("b1", C.c_float), ("b2", C.c_float), ("flags", C.c_uint32)]
+
+
+SOL_LIGHTMAP_CONSERVATIVE, SOL_LIGHTMAP_MAX_SIZE, SOL_TEXEL_NONE = 1, 16384, 0xFFFFFFFF
+
 SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
 
 
@@ -369,6 +384,10 @@ def load_hip():
     _sig(lib, "sol_irradiance_sh", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_visibility_dev", C.c_int, [P, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_visibility", C.c_int, [P, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
+    _sig(lib, "sol_lightmap_points_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolLightmapConfig), C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_points", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolLightmapConfig), C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_dilate_dev", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_dilate", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
     _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _sig(lib, "sol_triangle_from_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolTriangle)])
@@ -399,7 +418,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_triangle_from_vertices", "sol_scene_set_triangles", "sol_scene_set_triangles_dev", "sol_scene_set_triangles_ms", "sol_scene_triangle_records",
                "sol_sphere_from_center", "sol_quad_from_corner", "sol_scene_set_primitives", "sol_scene_primitive_records",
                "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys", "sol_irradiance_dev", "sol_irradiance", "sol_irradiance_rays",
-               "sol_irradiance_sh_dev", "sol_irradiance_sh", "sol_visibility_dev", "sol_visibility"]
+               "sol_irradiance_sh_dev", "sol_irradiance_sh", "sol_visibility_dev", "sol_visibility",
+               "sol_lightmap_points_dev", "sol_lightmap_points", "sol_lightmap_dilate_dev", "sol_lightmap_dilate"]
 
 
 def load_host():

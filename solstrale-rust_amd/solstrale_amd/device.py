@@ -141,6 +141,15 @@ def sh9_irradiance(L, normals):
     return np.einsum("mk,...kc->...mc", y * a, np.asarray(L, dtype=np.float64))
 
 
+# A SolTexel of sol_lightmap_points: the owning triangle (0xFFFFFFFF: none), the barycentrics b1, b2, the claim (1 centre, 2 conservative only).
+LIGHTMAP_TEXEL_DTYPE = np.dtype([("triangle", np.uint32), ("b1", np.float32), ("b2", np.float32), ("flags", np.uint32)])
+
+
+def lightmap_texels_to_numpy(rows):
+    """The [n, 4] int32 device tensor DeviceScene.lightmap_points returned on the device route, as the structured host array."""
+    return np.ascontiguousarray(rows.cpu().numpy()).view(LIGHTMAP_TEXEL_DTYPE).reshape(-1)
+
+
 class DeviceScene:
     """sol_scene_create .. sol_scene_destroy"""
 
@@ -611,6 +620,82 @@ class DeviceScene:
     def visibility_to_numpy(cls, rows):
         """The [n, 8] float32 device tensor visibility() returned, as the structured host array."""
         return np.ascontiguousarray(rows.cpu().numpy()).view(cls.VISIBILITY_DTYPE).reshape(-1)
+
+    # ---- lightmap texel points and border dilation (EXTENSION; DESIGN.md 23) ----
+    def lightmap_points(self, vertices, uvs, width, height, normals=None, tmin=1e-3, tmax=float("inf"), conservative=False):
+        """sol_lightmap_points: the mesh's lightmap UVs rasterised into a `width` x `height` atlas. vertices [n, 3, 3], uvs [n, 3, 2] and the
+        optional per-corner normals [n, 3, 3] are float32: numpy arrays go the host route, contiguous torch tensors on the scene's device go through
+        sol_lightmap_points_dev without a copy. Returns (points, texels): the [height * width, 8] float32 rows (position, tmin, normal, tmax) that
+        irradiance(), irradiance_sh() and visibility() take - eight zero words, an invalid point, where no triangle owns the texel - and the
+        SolTexel rows (owner, b1, b2, flags): a LIGHTMAP_TEXEL_DTYPE array on the host route, an [n, 4] int32 device tensor on the device route
+        (lightmap_texels_to_numpy views it). conservative: texels a triangle merely touches are claimed too, behind every centre claim."""
+        cfg = _abi.SolLightmapConfig(size=C.sizeof(_abi.SolLightmapConfig), width=int(width), height=int(height),
+                                     flags=_abi.SOL_LIGHTMAP_CONSERVATIVE if conservative else 0, tmin=float(tmin), tmax=float(tmax))
+        wh = int(width) * int(height) if 0 < int(width) <= _abi.SOL_LIGHTMAP_MAX_SIZE and 0 < int(height) <= _abi.SOL_LIGHTMAP_MAX_SIZE else 1
+        arrays = (("vertices", vertices, (3, 3)), ("uvs", uvs, (3, 2)), ("normals", normals, (3, 3)))
+        if isinstance(vertices, np.ndarray) or not hasattr(vertices, "data_ptr"):  # the host route
+            a = []
+            for name, x, tail in arrays:
+                if x is None and name == "normals":
+                    a.append(None)
+                    continue
+                x = np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=np.float32)
+                if x.ndim != 3 or x.shape[1:] != tail or (a and x.shape[0] != a[0].shape[0]):
+                    raise ValueError(f"{name}: a float32 [n, {tail[0]}, {tail[1]}] array, one row per triangle")
+                a.append(x)
+            points = np.zeros((wh, 8), dtype=np.float32)
+            texels = np.zeros(wh, dtype=LIGHTMAP_TEXEL_DTYPE)
+            self._chk(self.lib.sol_lightmap_points(self.h, a[0].ctypes.data, None if a[2] is None else a[2].ctypes.data, a[1].ctypes.data, a[0].shape[0],
+                                                   C.byref(cfg), points.ctypes.data, texels.ctypes.data))
+            return points, texels
+        import torch
+        n = int(vertices.shape[0])
+        for name, x, tail in arrays:
+            if x is None:
+                continue
+            if (not hasattr(x, "data_ptr") or x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape) != (n,) + tail or not x.is_contiguous() or not x.is_cuda
+                    or x.device.index != self.device):
+                raise ValueError(f"{name}: a contiguous float32 [n, {tail[0]}, {tail[1]}] tensor on the scene's device, one row per triangle")
+        points = torch.empty((wh, 8), dtype=torch.float32, device=vertices.device)
+        texels = torch.empty((wh, 4), dtype=torch.int32, device=vertices.device)
+        torch.cuda.current_stream(vertices.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_points_dev(self.h, C.c_void_p(vertices.data_ptr()), C.c_void_p(normals.data_ptr()) if normals is not None else None,
+                                                   C.c_void_p(uvs.data_ptr()), n, C.byref(cfg), C.c_void_p(points.data_ptr()), C.c_void_p(texels.data_ptr())))
+        self.sync()
+        return points, texels
+
+    def lightmap_dilate(self, values, texels, width, height, passes=1, channels=3, return_pass_of=False):
+        """sol_lightmap_dilate: the border dilation that finishes a bake. values: `width * height` rows whose leading `channels` 32-bit words are
+        floats (a [n, k] float32 array or tensor - the raw rows a gather returned: channels=3 for radiance / irradiance rows, 27 for irradiance_sh);
+        texels: what lightmap_points returned. Owned rows are copied whole; in each of `passes` passes an uncovered texel with a covered neighbour
+        gets their mean, the rest of its row zero. Host arrays go the host route, device tensors the device route, and the answer has the shape and
+        place of `values`. return_pass_of: also the uint8 plane [height, width] of 0 owned, k filled in pass k, 255 never filled."""
+        width, height = int(width), int(height)
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
+            v = np.ascontiguousarray(values, dtype=np.float32)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            if v.ndim != 2 or v.shape[0] != width * height or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (width * height,):
+                raise ValueError("values: [width * height, k] float32 rows; texels: width * height LIGHTMAP_TEXEL_DTYPE rows")
+            out = np.zeros_like(v)
+            pass_of = np.zeros((height, width), dtype=np.uint8) if return_pass_of else None
+            self._chk(self.lib.sol_lightmap_dilate(self.h, t.ctypes.data, width, height, v.ctypes.data, int(channels), v.shape[1] * 4, int(passes), out.ctypes.data,
+                                                   None if pass_of is None else pass_of.ctypes.data))
+            return (out, pass_of) if return_pass_of else out
+        import torch
+        if (values.dtype != torch.float32 or values.dim() != 2 or values.shape[0] != width * height or not values.is_contiguous() or not values.is_cuda
+                or values.device.index != self.device):
+            raise ValueError("values: a contiguous [width * height, k] float32 tensor on the scene's device")
+        if (not hasattr(texels, "data_ptr") or texels.dtype != torch.int32 or tuple(texels.shape) != (width * height, 4) or not texels.is_contiguous()
+                or texels.device != values.device):
+            raise ValueError("texels: the contiguous [width * height, 4] int32 tensor lightmap_points returned, on the device of values")
+        out = torch.empty_like(values)
+        pass_of = torch.empty((height, width), dtype=torch.uint8, device=values.device) if return_pass_of else None
+        torch.cuda.current_stream(values.device).synchronize()  # (the values may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_dilate_dev(self.h, C.c_void_p(texels.data_ptr()), width, height, C.c_void_p(values.data_ptr()), int(channels),
+                                                   int(values.shape[1]) * 4, int(passes), C.c_void_p(out.data_ptr()),
+                                                   C.c_void_p(pass_of.data_ptr()) if pass_of is not None else None))
+        self.sync()
+        return (out, pass_of) if return_pass_of else out
 
     def camera_ray_keys(self, x0, y0, x1, y1, sample, seed):
         """sol_camera_ray_keys: (pixel, first_draw) of the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 2] int32 device
