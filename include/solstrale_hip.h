@@ -904,6 +904,89 @@ int sol_lightmap_dilate_dev(SolScene* scene, const void* texels_dev, uint32_t wi
 int sol_lightmap_dilate(SolScene* scene, const SolTexel* texels, uint32_t width, uint32_t height, const void* values, uint32_t channels,
                         uint32_t stride_bytes, uint32_t passes, void* out, uint8_t* pass_of_out);
 
+/* ---- irradiance volumes (EXTENSION, not in the reference) -----------------------------------------------------------------
+ * The consumer of sol_irradiance_sh and of sol_visibility's hit-distance moments: a regular grid of probes that is laid out, packed and
+ * sampled on the device, so that grid -> sol_volume_points -> sol_irradiance_sh (+ sol_visibility) -> sol_volume_build -> sol_volume_sample is
+ * a chain of calls on device memory, and a viewer, a lightmap or a moving object is lit from the baked volume without new paths. The handle
+ * supplies the device, the stream and the host routes' staging; the scene is never read: nothing is traced, and a scene with a constant medium
+ * is not refused. All arithmetic is fp32, every operation rounded once, no fused multiply-add, `/` and sqrt correctly rounded;
+ * csrc/sol_volume.h is the rule as code and tests/volume_ref.py its restatement in numpy. dot(a, b) below is ((ax * bx) + (ay * by)) + (az * bz);
+ * pos(x) is x > 0 ? x : 0 (a NaN and -0 give +0).
+ *   Grid.     nx x ny x nz probes; probe (i, j, k) is row (k * ny + j) * nx + i. Its position per axis is o + ((float)i * s) - two roundings -, and o
+ *             itself on an axis with one probe, whose spacing is never read.
+ *   Points.   sol_volume_points writes the nx * ny * nz rows (position, tmin, (0, 0, 1), tmax) that sol_irradiance_sh and sol_visibility take: the
+ *             baker and the sampler then agree on every probe position on the bits.
+ *   Build.    sol_volume_build packs one SolProbe per grid row from an SolSh9 row and, where given, a SolVisibility row. The SolSh9 rows MUST have
+ *             been gathered with SOL_IRRADIANCE_SPHERE: the coefficients are that mode's estimator with the cosine lobe folded in,
+ *               e[k][c] = ((sh.c[k][c] * K4PI) / (float)sh.samples) * A[l(k)]
+ *             K4PI the fp32 rounding of 4 pi, A the fp32 roundings of pi (k = 0), 2 pi / 3 (k = 1..3), pi / 4 (k = 4..8). A probe is INVALID - 32
+ *             zero words - when sh.samples == 0 or one of the 27 sums is not finite. flags bit 0: valid; samples = sh.samples. Moments (flags bit
+ *             1; else mean = mean2 = 0) need a visibility row with samples != 0, finite t_sum and t2_sum, and a finite radius > 0 - the tmax the
+ *             visibility gather ran with, under SOL_QUERY_CLOSEST:
+ *               mean  = (t_sum  + ((float)open * radius)) / (float)samples
+ *               mean2 = (t2_sum + (((float)open * radius) * radius)) / (float)samples
+ *   Sample.   sol_volume_sample answers one SolRadiance per point row (position p, tmin, normal N, tmax; tmin and tmax are not read): r, g, b the
+ *             irradiance, `samples` the number of probes that contributed, 0 to 8 - sol_lightmap_dilate takes the rows as they are (3 channels,
+ *             stride 16). A row is INVALID - four zero words - when one of its six position or normal words is not finite or dot(N, N) is not a
+ *             finite, normal fp32 number (the condition sol_irradiance states). Otherwise
+ *               n = N / sqrtf(dot(N, N));  q = p + (n * normal_bias) per component;  Y = the nine terms of sol_irradiance_sh on n
+ *               per axis, count == 1: g = 0;  else g = (q - o) / s;  g = g > 0 ? g : 0;  g = g < (float)(count - 1) ? g : (float)(count - 1)
+ *                         i0 = min((int)floorf(g), max(count - 2, 0));  f = g - (float)i0
+ *             The eight corners (i0 + dx, j0 + dy, k0 + dz) are visited in the order dz, dy, dx ascending, each with the trilinear weight
+ *             w = ((wx * wy) * wz), w_axis = d ? f : (1 - f). A corner with w == 0 is skipped and its probe is not read (the far layer of a
+ *             one-probe axis, points on a grid plane); a corner whose probe is invalid is skipped. With P the probe's position:
+ *               SOL_VOLUME_BACKFACE   D = P - p; l2 = dot(D, D); where l2 > 0: c = dot(D, n) / sqrtf(l2); b = (c + 1) * 0.5; w = w * ((b * b) + 0.2f)
+ *               SOL_VOLUME_CHEBYSHEV  where the probe has moments: D' = P - q; d = sqrtf(dot(D', D')); where d > mean:
+ *                                     v = pos(mean2 - (mean * mean)); t = d - mean; den = v + (t * t); where den > 0: h = v / den; w = w * ((h * h) * h)
+ *             A corner whose final w is not > 0 (a NaN too) is skipped; the others count in `samples` and add
+ *               E[c] = pos((((0 + (e[0][c] * Y0)) + (e[1][c] * Y1)) + ..) + (e[8][c] * Y8));  sum[c] = sum[c] + (w * E[c]);  wsum = wsum + w
+ *             both sums from 0 in corner order. The answer is (sum[0] / wsum, sum[1] / wsum, sum[2] / wsum, samples); four zero words where no
+ *             probe contributed. One lane adds a point's corners in the stated order: the answer does not depend on the schedule.
+ *   Limitation. The moments are isotropic - one mean and one mean square of the hit distance per probe, not one per direction as in the octahedral
+ *             maps of DDGI. The Chebyshev factor is therefore a coarse test against light leaking through walls, and it is a flag.
+ * Neutral as the queries are: neither the accumulator, the planes, the work counter nor SolStats is touched.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for and in this order. All three: a null scene; a null grid; a wrong
+ * size; unknown flags; nx, ny or nz of 0; nx * ny * nz above 2^24; an origin that is not finite; on an axis with more than one probe a spacing that
+ * is not finite and > 0; a normal_bias that is not finite. Then sol_volume_points: tmin / tmax failing the point rule (0 <= tmin <= tmax, tmin
+ * finite, tmax not NaN); a null output pointer. sol_volume_build: a null SolSh9 pointer; a null output pointer (visibility may be NULL; radius is
+ * judged per probe, above). sol_volume_sample: n above 2^31; then n == 0 succeeds and writes nothing; a null probe, point or output pointer.
+ * SOL_EDEVICE without a GPU comes after all of these. There is no host mirror. */
+#define SOL_VOLUME_BACKFACE 1u
+#define SOL_VOLUME_CHEBYSHEV 2u
+#define SOL_VOLUME_MAX_PROBES 16777216u
+#define SOL_PROBE_VALID 1u
+#define SOL_PROBE_MOMENTS 2u
+/* size = sizeof(SolVolumeGrid) = 48: size 0, nx 4, ny 8, nz 12, origin 16, spacing 28, flags 40, normal_bias 44 */
+typedef struct SolVolumeGrid {
+  uint32_t size, nx, ny, nz; /* size = sizeof(SolVolumeGrid) */
+  float origin[3];           /* the position of probe (0, 0, 0) */
+  float spacing[3];          /* between neighbouring probes, per axis */
+  uint32_t flags;            /* SOL_VOLUME_BACKFACE | SOL_VOLUME_CHEBYSHEV */
+  float normal_bias;         /* a sample looks its cell up at position + unit normal * normal_bias */
+} SolVolumeGrid;
+/* 128 bytes: eight 16-byte words per probe; 16-byte aligned in device memory */
+typedef struct SolProbe {
+  float e[9][3];     /* words 0..26: the irradiance coefficients, the cosine lobe folded in */
+  float mean, mean2; /* words 27, 28: the mean and the mean square of the hit distance, clamped to the radius */
+  uint32_t flags;    /* word 29: SOL_PROBE_VALID | SOL_PROBE_MOMENTS */
+  uint32_t samples;  /* word 30: the samples of the gather */
+  uint32_t reserved; /* word 31: zero */
+} SolProbe;
+/* Device pointers (nx * ny * nz SolRay out, 16-byte aligned, on the scene's device), on the scene's stream, asynchronous. */
+int sol_volume_points_dev(SolScene* scene, const SolVolumeGrid* grid, float tmin, float tmax, void* points_out_dev);
+/* A host array, staged through a buffer the handle owns; blocks. */
+int sol_volume_points(SolScene* scene, const SolVolumeGrid* grid, float tmin, float tmax, SolRay* points_out);
+/* Device pointers (nx * ny * nz SolSh9, as many SolVisibility or NULL; as many SolProbe out; every one 16-byte aligned, on the scene's device),
+ * on the scene's stream, asynchronous. */
+int sol_volume_build_dev(SolScene* scene, const SolVolumeGrid* grid, const void* sh_dev, const void* visibility_dev, float radius, void* probes_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_volume_build(SolScene* scene, const SolVolumeGrid* grid, const SolSh9* sh, const SolVisibility* visibility, float radius, SolProbe* probes_out);
+/* Device pointers (nx * ny * nz SolProbe, n SolRay points; n SolRadiance out; every one 16-byte aligned, on the scene's device), on the scene's
+ * stream, asynchronous. */
+int sol_volume_sample_dev(SolScene* scene, const SolVolumeGrid* grid, const void* probes_dev, const void* points_dev, size_t n, void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_volume_sample(SolScene* scene, const SolVolumeGrid* grid, const SolProbe* probes, const SolRay* points, size_t n, SolRadiance* out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

@@ -64,6 +64,7 @@ SolDevOverrides sol_dev_overrides() {
   o.wf_min_items = num("SOL_WF_MIN_ITEMS", -1);
   if (const char* v = std::getenv("SOL_RCCL_LIB")) o.rccl_lib = v;
   if (const char* v = std::getenv("SOL_LIGHTMAP_CLAIM")) o.lightmap_claim = std::strcmp(v, "lane") == 0 ? 1 : std::strcmp(v, "wave") == 0 ? 2 : 0;
+  if (const char* v = std::getenv("SOL_VOLUME_SAMPLE")) o.volume_load_all = std::strcmp(v, "loadall") == 0;
   o.verbose = std::getenv("SOL_VERBOSE") != nullptr;
   return o;
 }

@@ -102,6 +102,13 @@ hipError_t sol_launch_lightmap_dilate_begin(const void* texels, uint32_t n_texel
                                             hipStream_t stream);
 hipError_t sol_launch_lightmap_dilate_pass(uint32_t W, uint32_t H, uint32_t channels, uint32_t stride_words, uint32_t pass, void* out, const uint8_t* cover_in,
                                            uint8_t* cover_out, hipStream_t stream);
+// ---- sol_volume.hip: irradiance volumes. points: nx * ny * nz SolRay; sh: as many SolSh9, visibility: as many SolVisibility or null,
+// probes: as many SolProbe; a sample reads n SolRay points and writes n SolRadiance - all 16-byte aligned. load_all: the measured alternative of the
+// sampler, which fetches the zero-weight corners too (the same words) ----
+struct SolVolumeGrid;
+hipError_t sol_launch_volume_points(const SolVolumeGrid& grid, float tmin, float tmax, void* points, hipStream_t stream);
+hipError_t sol_launch_volume_build(uint32_t n_probes, const void* sh, const void* visibility, float radius, void* probes, hipStream_t stream);
+hipError_t sol_launch_volume_sample(const SolVolumeGrid& grid, bool load_all, const void* probes, const void* points, uint32_t n, void* out, hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

@@ -10,6 +10,7 @@
 //   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
 //   sol_geometry.cpp sol_scene_set_triangles / sol_scene_set_primitives: the triangles, spheres and quads of a live scene moved, records and tree boxes recomputed on the device (sol_geometry.hip)
 //   sol_lightmap.cpp sol_lightmap_points / sol_lightmap_dilate: lightmap UVs rasterised into gather points, chart borders dilated (sol_lightmap.hip)
+//   sol_volume.cpp  sol_volume_points / sol_volume_build / sol_volume_sample: a probe grid laid out, packed and sampled (sol_volume.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
 // There is NO CPU fallback: without a HIP device every compute entry point fails with SOL_EDEVICE.
@@ -131,6 +132,7 @@ struct SolDevOverrides {
   int pool_slots = 0, wf_slots = 0, wf_min_items = -1;  // SOL_POOL_SLOTS / SOL_WF_SLOTS / SOL_WF_MIN_ITEMS (v2 / v3)
   std::string rccl_lib;          // SOL_RCCL_LIB: the communication library to dlopen instead of librccl.so.1 (tests)
   int lightmap_claim = 0;        // SOL_LIGHTMAP_CLAIM=lane|wave: the claim pass of sol_lightmap_points as one of its two plain candidates (1, 2; 0: the product's hybrid)
+  bool volume_load_all = false;  // SOL_VOLUME_SAMPLE=loadall: sol_volume_sample fetches the zero-weight corners of a cell too (the measured alternative; the same words)
   bool verbose = false;          // SOL_VERBOSE
 };
 SolDevOverrides sol_dev_overrides();
@@ -314,6 +316,10 @@ struct SolScene {
   DevBuf<uint32_t> lm_owner;
   DevBuf<char> lm_stage;
   uint32_t lm_small_max = 16, lm_tiles_max = 64;
+  // Irradiance volumes (sol_volume.hip). vol_stage: what the host routes stage, inputs and outputs. vol_load_all: the sampler's
+  // measured alternative (SOL_VOLUME_SAMPLE=loadall).
+  DevBuf<char> vol_stage;
+  bool vol_load_all = false;
   SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).

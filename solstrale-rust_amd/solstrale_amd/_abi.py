@@ -263,6 +263,24 @@ class SolTexel(C.Structure):
 
 SOL_LIGHTMAP_CONSERVATIVE, SOL_LIGHTMAP_MAX_SIZE, SOL_TEXEL_NONE = 1, 16384, 0xFFFFFFFF
 
+
+class SolVolumeGrid(C.Structure):
+    """EXTENSION: the probe grid of an irradiance volume (sol_volume_points / _build / _sample): size = sizeof, nx x ny x nz probes, the
+    position of probe (0, 0, 0), the spacing per axis, flags (SOL_VOLUME_BACKFACE | SOL_VOLUME_CHEBYSHEV) and the normal bias of a sample. 48 bytes.
+    Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("nx", C.c_uint32), ("ny", C.c_uint32), ("nz", C.c_uint32), ("origin", C.c_float * 3), ("spacing", C.c_float * 3),
+                ("flags", C.c_uint32), ("normal_bias", C.c_float)]
+
+
+class SolProbe(C.Structure):
+    """EXTENSION: one probe of an irradiance volume as sol_volume_build packs it: e[k][channel], the irradiance coefficients with the cosine lobe
+    folded in; the mean and the mean square of the hit distance; flags (SOL_PROBE_VALID | SOL_PROBE_MOMENTS); the gather's samples. 128 bytes."""
+    _fields_ = [("e", (C.c_float * 3) * 9), ("mean", C.c_float), ("mean2", C.c_float), ("flags", C.c_uint32), ("samples", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+SOL_VOLUME_BACKFACE, SOL_VOLUME_CHEBYSHEV, SOL_VOLUME_MAX_PROBES, SOL_PROBE_VALID, SOL_PROBE_MOMENTS = 1, 2, 1 << 24, 1, 2
+
 SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
 
 
@@ -388,6 +406,12 @@ def load_hip():
     _sig(lib, "sol_lightmap_points", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolLightmapConfig), C.c_void_p, C.c_void_p])
     _sig(lib, "sol_lightmap_dilate_dev", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_lightmap_dilate", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
+    _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
+    _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
+    _sig(lib, "sol_volume_build", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
+    _sig(lib, "sol_volume_sample_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_volume_sample", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
     _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _sig(lib, "sol_triangle_from_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolTriangle)])
@@ -419,7 +443,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_sphere_from_center", "sol_quad_from_corner", "sol_scene_set_primitives", "sol_scene_primitive_records",
                "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys", "sol_irradiance_dev", "sol_irradiance", "sol_irradiance_rays",
                "sol_irradiance_sh_dev", "sol_irradiance_sh", "sol_visibility_dev", "sol_visibility",
-               "sol_lightmap_points_dev", "sol_lightmap_points", "sol_lightmap_dilate_dev", "sol_lightmap_dilate"]
+               "sol_lightmap_points_dev", "sol_lightmap_points", "sol_lightmap_dilate_dev", "sol_lightmap_dilate",
+               "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample"]
 
 
 def load_host():

@@ -150,6 +150,46 @@ def lightmap_texels_to_numpy(rows):
     return np.ascontiguousarray(rows.cpu().numpy()).view(LIGHTMAP_TEXEL_DTYPE).reshape(-1)
 
 
+# A SolProbe of sol_volume_build: the irradiance coefficients e[k][channel], the hit-distance moments, flags (1 valid, 2 has moments).
+VOLUME_PROBE_DTYPE = np.dtype([("e", np.float32, (9, 3)), ("mean", np.float32), ("mean2", np.float32), ("flags", np.uint32), ("samples", np.uint32),
+                               ("reserved", np.uint32)])
+
+
+def volume_probes_to_numpy(rows):
+    """The [n, 32] float32 device tensor DeviceScene.volume_build returned on the device route, as the structured host array."""
+    return np.ascontiguousarray(rows.cpu().numpy()).view(VOLUME_PROBE_DTYPE).reshape(-1)
+
+
+class VolumeGrid:
+    """The probe grid of an irradiance volume (SolVolumeGrid): counts = (nx, ny, nz) probes, probe (i, j, k) at origin + (i, j, k) *
+    spacing and in row (k * ny + j) * nx + i. backface / chebyshev: the two weights of volume_sample (probes behind the surface count less; a
+    probe whose hit-distance moments say the point lies behind a wall counts less); normal_bias: a sample looks its cell up at position + unit
+    normal * normal_bias."""
+
+    def __init__(self, origin, spacing, counts, backface=True, chebyshev=True, normal_bias=0.0):
+        self.origin = tuple(float(x) for x in origin)
+        self.spacing = tuple(float(x) for x in (spacing if np.ndim(spacing) else (spacing,) * 3))
+        self.counts = tuple(int(x) for x in counts)
+        if len(self.origin) != 3 or len(self.spacing) != 3 or len(self.counts) != 3:
+            raise ValueError("origin, spacing, counts: three numbers each (spacing may be one)")
+        if any(c < 0 or c > 0xFFFFFFFF for c in self.counts):
+            raise ValueError(f"counts: {self.counts} - each a 32-bit count (0 and more than 2^24 probes in all are the library's to refuse)")
+        self.backface, self.chebyshev, self.normal_bias = bool(backface), bool(chebyshev), float(normal_bias)
+
+    @property
+    def n_probes(self):
+        return self.counts[0] * self.counts[1] * self.counts[2]
+
+    def record(self):
+        """The SolVolumeGrid of this grid."""
+        g = _abi.SolVolumeGrid(size=C.sizeof(_abi.SolVolumeGrid), nx=self.counts[0], ny=self.counts[1], nz=self.counts[2],
+                               flags=(_abi.SOL_VOLUME_BACKFACE if self.backface else 0) | (_abi.SOL_VOLUME_CHEBYSHEV if self.chebyshev else 0),
+                               normal_bias=self.normal_bias)
+        g.origin[:] = self.origin
+        g.spacing[:] = self.spacing
+        return g
+
+
 class DeviceScene:
     """sol_scene_create .. sol_scene_destroy"""
 
@@ -696,6 +736,106 @@ class DeviceScene:
                                                    C.c_void_p(pass_of.data_ptr()) if pass_of is not None else None))
         self.sync()
         return (out, pass_of) if return_pass_of else out
+
+    # ---- irradiance volumes (EXTENSION) ----
+    @staticmethod
+    def _volume_rows(grid):
+        """The rows to allocate for `grid`; 1 for a grid the library refuses."""
+        return grid.n_probes if all(c > 0 for c in grid.counts) and grid.n_probes <= _abi.SOL_VOLUME_MAX_PROBES else 1
+
+    def _volume_tensor(self, name, x, rows, words):
+        import torch
+        if (not hasattr(x, "data_ptr") or x.dtype != torch.float32 or x.dim() != 2 or (rows is not None and x.shape[0] != rows) or x.shape[1] != words
+                or not x.is_contiguous() or not x.is_cuda or x.device.index != self.device):
+            raise ValueError(f"{name}: a contiguous [{'n' if rows is None else rows}, {words}] float32 tensor on the scene's device")
+        if x.data_ptr() % 16:  # (a view that starts inside an allocation: the kernels move whole 16-byte words)
+            raise ValueError(f"{name}: the tensor's memory must be 16-byte aligned")
+        return C.c_void_p(x.data_ptr())
+
+    def volume_points(self, grid, tmin=1e-3, tmax=float("inf"), host=False):
+        """sol_volume_points: the rows (position, tmin, (0, 0, 1), tmax) of the probes of `grid` (a VolumeGrid), probe (i, j, k) in row (k * ny + j) *
+        nx + i - what irradiance_sh(mode="sphere") and visibility(distances=True) take, with every position on the bits the one volume_sample
+        measures from. Returns an [nx * ny * nz, 8] float32 tensor on the scene's device (sol_volume_points_dev), with host=True a numpy array
+        (the host route)."""
+        rec, rows = grid.record(), self._volume_rows(grid)
+        if host:
+            out = np.zeros((rows, 8), dtype=np.float32)
+            self._chk(self.lib.sol_volume_points(self.h, C.byref(rec), float(tmin), float(tmax), out.ctypes.data))
+            return out
+        import torch
+        out = torch.empty((rows, 8), dtype=torch.float32, device=f"cuda:{self.device}")
+        self._chk(self.lib.sol_volume_points_dev(self.h, C.byref(rec), float(tmin), float(tmax), C.c_void_p(out.data_ptr())))
+        self.sync()  # (the scene's stream is not torch's)
+        return out
+
+    def volume_build(self, grid, sh, visibility=None, radius=None):
+        """sol_volume_build: one SolProbe per probe of `grid` from what irradiance_sh(volume_points(grid), mode="sphere") answered - the sums must be
+        SPHERE mode's - and, for the hit-distance moments, what visibility(.., distances=True) answered over points whose tmax is the finite
+        `radius`. Without visibility, or with radius None, the probes carry no moments and the Chebyshev weight of volume_sample leaves them
+        alone. A probe without samples or with a sum that is not finite is invalid (32 zero words) and is skipped by volume_sample. Host route:
+        sh as irradiance_sh returned it - the pair (sums [n, 9, 3], counts [n]) - or raw [n, 28] float32 rows, visibility a VISIBILITY_DTYPE array
+        or raw [n, 8] rows; returns a VOLUME_PROBE_DTYPE array. Device route: the [n, 28] and [n, 8] float32 tensors of the gathers, without a
+        copy; returns the raw [n, 32] float32 device tensor (volume_probes_to_numpy views it)."""
+        rec, rows = grid.record(), self._volume_rows(grid)
+        radius = 0.0 if radius is None else float(radius)
+        if isinstance(sh, (tuple, list, np.ndarray)):  # the host route
+            if isinstance(sh, (tuple, list)):
+                sums, counts = sh
+                a = np.concatenate([np.ascontiguousarray(sums, dtype=np.float32).reshape(-1, 27),
+                                    np.ascontiguousarray(counts).astype(np.uint32, copy=False).view(np.float32).reshape(-1, 1)], axis=1)
+            else:
+                a = np.ascontiguousarray(sh, dtype=np.float32)
+            a = np.ascontiguousarray(a)
+            if a.shape != (rows, 28):
+                raise ValueError("sh: the (sums [n, 9, 3], counts [n]) irradiance_sh returned, or raw [n, 28] float32 rows, one per probe of the grid")
+            v = None
+            if visibility is not None:
+                v = self.visibility_to_numpy(visibility) if hasattr(visibility, "data_ptr") else np.ascontiguousarray(visibility)
+                v = v.view(np.float32).reshape(-1, 8) if v.dtype == self.VISIBILITY_DTYPE else np.ascontiguousarray(v, dtype=np.float32)
+                if v.shape != (rows, 8):
+                    raise ValueError("visibility: a VISIBILITY_DTYPE array or raw [n, 8] float32 rows, one per probe of the grid")
+                v = np.ascontiguousarray(v)
+            out = np.zeros(rows, dtype=VOLUME_PROBE_DTYPE)
+            self._chk(self.lib.sol_volume_build(self.h, C.byref(rec), a.ctypes.data, None if v is None else v.ctypes.data, radius, out.ctypes.data))
+            return out
+        import torch
+        p_sh = self._volume_tensor("sh", sh, rows, 28)
+        p_vis = None if visibility is None else self._volume_tensor("visibility", visibility, rows, 8)
+        out = torch.empty((rows, 32), dtype=torch.float32, device=sh.device)
+        torch.cuda.current_stream(sh.device).synchronize()  # (the sums may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_volume_build_dev(self.h, C.byref(rec), p_sh, p_vis, radius, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def volume_sample(self, grid, probes, points):
+        """sol_volume_sample: the irradiance at the caller's points - rows of (position xyz, tmin, normal xyz, tmax), irradiance()'s rows; tmin and
+        tmax are not read - interpolated from the probes of `grid` that volume_build packed: trilinear weights over the cell of position + unit
+        normal * normal_bias, times the backface and Chebyshev weights the grid's flags ask for, invalid probes left out. Host arrays (probes: a
+        VOLUME_PROBE_DTYPE array or raw [n, 32] float32 rows) go the host route and return (rgb [n, 3] float32, samples [n] uint32), samples being
+        the probes that contributed, 0 to 8; device tensors go through sol_volume_sample_dev without a copy and return the raw [n, 4] float32
+        rows, which lightmap_dilate takes as they are."""
+        rec, rows = grid.record(), self._volume_rows(grid)
+        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):  # the host route
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError("points: an [n, 8] float32 array of (position xyz, tmin, normal xyz, tmax)")
+            p = volume_probes_to_numpy(probes) if hasattr(probes, "data_ptr") else np.ascontiguousarray(probes)
+            p = p.view(np.float32).reshape(-1, 32) if p.dtype == VOLUME_PROBE_DTYPE else np.ascontiguousarray(p, dtype=np.float32)
+            if p.shape != (rows, 32):
+                raise ValueError("probes: a VOLUME_PROBE_DTYPE array or raw [n, 32] float32 rows, one per probe of the grid")
+            p = np.ascontiguousarray(p)
+            out = np.zeros((a.shape[0], 4), dtype=np.float32)
+            self._chk(self.lib.sol_volume_sample(self.h, C.byref(rec), p.ctypes.data, a.ctypes.data, a.shape[0], out.ctypes.data))
+            return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
+        import torch
+        p_points = self._volume_tensor("points", points, None, 8)
+        p_probes = self._volume_tensor("probes", probes, rows, 32)
+        n = int(points.shape[0])
+        out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+        torch.cuda.current_stream(points.device).synchronize()  # (the points may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_volume_sample_dev(self.h, C.byref(rec), p_probes, p_points, n, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
 
     def camera_ray_keys(self, x0, y0, x1, y1, sample, seed):
         """sol_camera_ray_keys: (pixel, first_draw) of the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 2] int32 device
