@@ -942,8 +942,9 @@ int sol_lightmap_dilate(SolScene* scene, const SolTexel* texels, uint32_t width,
  *               E[c] = pos((((0 + (e[0][c] * Y0)) + (e[1][c] * Y1)) + ..) + (e[8][c] * Y8));  sum[c] = sum[c] + (w * E[c]);  wsum = wsum + w
  *             both sums from 0 in corner order. The answer is (sum[0] / wsum, sum[1] / wsum, sum[2] / wsum, samples); four zero words where no
  *             probe contributed. One lane adds a point's corners in the stated order: the answer does not depend on the schedule.
- *   Limitation. The moments are isotropic - one mean and one mean square of the hit distance per probe, not one per direction as in the octahedral
- *             maps of DDGI. The Chebyshev factor is therefore a coarse test against light leaking through walls, and it is a flag.
+ *   Limitation. The moments of a SolProbe are isotropic - one mean and one mean square of the hit distance per probe -, so this Chebyshev factor
+ *             cannot tell a wall on one side from open space on the other. The per-direction moments are the octahedral maps of the next
+ *             section (sol_visibility_oct, sol_volume_build_depth, sol_volume_sample_depth).
  * Neutral as the queries are: neither the accumulator, the planes, the work counter nor SolStats is touched.
  * SOL_EINVAL (sol_last_error names the reason), before the device is looked for and in this order. All three: a null scene; a null grid; a wrong
  * size; unknown flags; nx, ny or nz of 0; nx * ny * nz above 2^24; an origin that is not finite; on an axis with more than one probe a spacing that
@@ -986,6 +987,73 @@ int sol_volume_build(SolScene* scene, const SolVolumeGrid* grid, const SolSh9* s
 int sol_volume_sample_dev(SolScene* scene, const SolVolumeGrid* grid, const void* probes_dev, const void* points_dev, size_t n, void* out_dev);
 /* Host arrays, staged through a buffer the handle owns; blocks. */
 int sol_volume_sample(SolScene* scene, const SolVolumeGrid* grid, const SolProbe* probes, const SolRay* points, size_t n, SolRadiance* out);
+
+/* ---- directional distance moments for irradiance volumes: octahedral maps (EXTENSION, not in the reference) ------------------
+ * A SolProbe keeps one mean and one mean square of the hit distance for the whole sphere. Here a probe keeps them per direction, in an R x R
+ * octahedral map (the depth map of DDGI): sol_visibility_oct gathers the weighted sums at the probes' points, sol_volume_build_depth turns
+ * them into moments and sol_volume_sample_depth is sol_volume_sample with the Chebyshev step reading the map towards the shaded point. All
+ * arithmetic is fp32, every operation rounded once, no fused multiply-add, `/` and sqrtf correctly rounded; csrc/sol_depth.h is the rule as code
+ * and tests/depth_ref.py its restatement in numpy. dot and pos as above; |x| clears the sign bit; sgn(x) is x >= 0 ? 1 : -1; (float)R is exact.
+ *   Map.      R = SolOctConfig.res (4, 8 or 16). Texel (i, j), i along u, j along v, is row j * R + i; the map has no gutter.
+ *   Texel direction.  u = ((((float)i + 0.5f) / (float)R) * 2) - 1, v likewise from j;  z = (1 - |u|) - |v|;  where z < 0:
+ *             (x, y) = ((1 - |v|) * sgn(u), (1 - |u|) * sgn(v)), else (x, y) = (u, v);  T = (x, y, z) / sqrtf(dot((x, y, z), (x, y, z))).
+ *   Gather.   sol_visibility_oct: points, their validity, keys, key_base, first_draw, seed, first_sample, samples and the two direction modes are
+ *             sol_irradiance's, word for word (use SOL_IRRADIANCE_SPHERE for a probe); a point's tmax is the radius. Sample s is the ray
+ *             sol_irradiance_rays writes for it, its status and t what sol_query answers for that ray under SOL_QUERY_CLOSEST, the searches
+ *             behind a refused needle hit included. For every texel  c = pos(dot(T, d)), d as drawn, then c = c * c, sharpness_log2 times, and
+ *               SOL_RAY_HIT   w = w + c;  ct = c * t;  wt = wt + ct;  wt2 = wt2 + (ct * t)
+ *               SOL_RAY_MISS  w = w + c;  w_open = w_open + c
+ *             A made ray that is itself invalid adds nothing. Each of the four sums is in sol_radiance's association over the samples: chunks of
+ *             16 counted from first_sample, a chunk 0 + x + x .. in sample order, the result ((0 + chunk0) + chunk1) + ... The answer is R * R
+ *             SolOctTexel rows per point; an invalid point answers zero words throughout.
+ *   Build.    sol_volume_build_depth, per texel:  s = w_open * radius;  mean = (wt + s) / w;  mean2 = (wt2 + (s * radius)) / w. A texel whose w is
+ *             not > 0, or one of whose four sums is not finite, is (radius, radius * radius): open as far as the radius, it never attenuates.
+ *   Sample.   sol_volume_sample_depth is sol_volume_sample's rule - rows, corner order, skips, the backface factor, the renormalisation and the
+ *             answer - with one change to the SOL_VOLUME_CHEBYSHEV step: for a valid probe at P it takes mean and mean2 from the probe's map and
+ *             does not consult the probe's SOL_PROBE_MOMENTS bit. D = q - P; d = sqrtf(dot(D, D)); where d is not > 0 the step is left out. Else
+ *               s = (|Dx| + |Dy|) + |Dz|;  px = Dx / s;  py = Dy / s;  where Dz < 0: (px, py) = ((1 - |py|) * sgn(px), (1 - |px|) * sgn(py)), both
+ *               from the unfolded pair;  u = (px * 0.5f) + 0.5f;  tx = (u * (float)R) - 0.5f;  tx = tx > -0.5f ? tx : -0.5f;
+ *               tx = tx < (float)R - 0.5f ? tx : (float)R - 0.5f;  i0 = (int)floorf(tx);  a = tx - floorf(tx);  likewise v, ty, j0, b from py.
+ *             The four neighbours (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1) have the weights (1 - a) * (1 - b), a * (1 - b),
+ *             (1 - a) * b, a * b, and m = ((m00 * w00) + (m10 * w10)) + ((m01 * w01) + (m11 * w11)) for mean and for mean2. A neighbour (i, j)
+ *             beyond the map is folded by the octahedron's edge rule in integers: oi = i < 0 || i >= R, oj likewise; ci = i clamped to
+ *             [0, R - 1], cj likewise; where oi: cj = (R - 1) - cj; where oj: ci = (R - 1) - ci - beyond one edge the other index is mirrored,
+ *             beyond a corner both. Then sol_volume_sample's Chebyshev lines as they stand (where d > mean: ..). Without the flag the map is not read.
+ * Neutral as sol_visibility is: no accumulator, plane, work counter or statistic is touched; the scratch is shared with the radiance queries.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for and in this order. SolOctConfig, wherever it is judged: null; a
+ * wrong size; a res that is not 4, 8 or 16; sharpness_log2 above 6; reserved != 0. sol_visibility_oct: a null scene; the SolIrradianceConfig and n
+ * as sol_irradiance judges them; the SolOctConfig; then n == 0 succeeds on any scene and touches nothing; a scene with a constant medium
+ * (sol_query's sentence); a null point or output pointer. sol_volume_build_depth: the grid as sol_volume_build judges it (a null scene first);
+ * the SolOctConfig; a radius that is not finite and > 0; a null SolOctTexel or output pointer. sol_volume_sample_depth: the grid; the
+ * SolOctConfig; n above 2^31; then n == 0 succeeds and writes nothing; a null probe, depth, point or output pointer. Build and sample trace
+ * nothing and serve a scene with a constant medium. SOL_EDEVICE without a GPU comes after all of these. There is no host mirror. */
+/* 16 bytes: size 0, res 4, sharpness_log2 8, reserved 12 */
+typedef struct SolOctConfig {
+  uint32_t size;           /* sizeof(SolOctConfig) */
+  uint32_t res;            /* 4, 8 or 16 texels along each side of a map */
+  uint32_t sharpness_log2; /* 0..6: the lobe is pos(dot(T, d)) to the power 2^sharpness_log2 */
+  uint32_t reserved;       /* zero */
+} SolOctConfig;
+/* 16 bytes; 16-byte aligned in device memory; sums, not means */
+typedef struct SolOctTexel { float w, w_open, wt, wt2; } SolOctTexel;
+/* 8 bytes; 8-byte aligned in device memory */
+typedef struct SolDepthTexel { float mean, mean2; } SolDepthTexel;
+/* Device pointers (n SolRay points, n SolRayKey or NULL, n * res * res SolOctTexel out, on the scene's device), on the scene's stream, asynchronous. */
+int sol_visibility_oct_dev(SolScene* scene, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, const SolOctConfig* oct_config,
+                           void* out_dev);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_visibility_oct(SolScene* scene, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, const SolOctConfig* oct_config,
+                       SolOctTexel* out);
+/* Device pointers (nx * ny * nz * res * res SolOctTexel; as many SolDepthTexel out), on the scene's stream, asynchronous. */
+int sol_volume_build_depth_dev(SolScene* scene, const SolVolumeGrid* grid, const void* oct_dev, const SolOctConfig* oct_config, float radius, void* depth_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_volume_build_depth(SolScene* scene, const SolVolumeGrid* grid, const SolOctTexel* oct, const SolOctConfig* oct_config, float radius, SolDepthTexel* depth_out);
+/* Device pointers (nx * ny * nz SolProbe, nx * ny * nz * res * res SolDepthTexel, n SolRay points; n SolRadiance out), on the scene's stream, asynchronous. */
+int sol_volume_sample_depth_dev(SolScene* scene, const SolVolumeGrid* grid, const void* probes_dev, const void* depth_dev, const SolOctConfig* oct_config,
+                                const void* points_dev, size_t n, void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_volume_sample_depth(SolScene* scene, const SolVolumeGrid* grid, const SolProbe* probes, const SolDepthTexel* depth, const SolOctConfig* oct_config,
+                            const SolRay* points, size_t n, SolRadiance* out);
 
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment

@@ -64,6 +64,7 @@ SolDevOverrides sol_dev_overrides() {
   o.wf_min_items = num("SOL_WF_MIN_ITEMS", -1);
   if (const char* v = std::getenv("SOL_RCCL_LIB")) o.rccl_lib = v;
   if (const char* v = std::getenv("SOL_LIGHTMAP_CLAIM")) o.lightmap_claim = std::strcmp(v, "lane") == 0 ? 1 : std::strcmp(v, "wave") == 0 ? 2 : 0;
+  if (const char* v = std::getenv("SOL_DEPTH_PROJECT")) o.depth_project_plain = std::strcmp(v, "plain") == 0;
   if (const char* v = std::getenv("SOL_VOLUME_SAMPLE")) o.volume_load_all = std::strcmp(v, "loadall") == 0;
   o.verbose = std::getenv("SOL_VERBOSE") != nullptr;
   return o;
@@ -642,6 +643,16 @@ int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_d
   return SOL_OK;
 }
 
+}  // namespace
+
+// (sol_scene.h: for sol_depth.cpp)
+int sol_gather_config_check(const char* fn, size_t n, const SolIrradianceConfig* config, SolRadianceConfig* cfg) {
+  if (config) *cfg = radiance_config_of(*config);
+  return radiance_config_check(fn, IRRADIANCE, n, config ? cfg : nullptr);
+}
+int sol_query_medium_check(const SolScene* s, const char* fn) { return query_medium_check(s, fn); }
+
+namespace {
 // The host route of both: arrays staged through buffers the handle owns, RADIANCE_STAGE_RAYS rows at a time; blocks.
 int radiance_staged(SolScene* s, bool gather, const SolRay* rays, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, SolRadiance* out) {
   int rc;

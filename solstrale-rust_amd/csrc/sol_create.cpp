@@ -925,6 +925,7 @@ static int set_scene_constants(const CreateCtx& c, const World& w, SolScene* s, 
   if (ovr.lightmap_claim == 1) s->lm_small_max = 0xFFFFFFFFu;                                 // a lane per triangle
   if (ovr.lightmap_claim == 2) { s->lm_small_max = 0u; s->lm_tiles_max = 0xFFFFFFFFu; }        // a wave per triangle
   s->vol_load_all = ovr.volume_load_all;
+  s->depth_project_plain = ovr.depth_project_plain;
   s->order_mode = ovr.order_mode;
   // v1's search/shade switch (RenderParams::switch_below), measured on MI355X at 1080p x 128 spp (ms, C1 / C2 / C3 / test scene):
   // 0: 29.2 / 162.9 / 236.7 / 25.9, 8: 27.7 / 124.3 / 193.1 / 25.5, 16: 27.5 / 111.8 / 186.9 / 25.6, 24: 28.6 / 108.6 / 192.3 / 26.8.

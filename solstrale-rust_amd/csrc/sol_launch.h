@@ -109,6 +109,18 @@ struct SolVolumeGrid;
 hipError_t sol_launch_volume_points(const SolVolumeGrid& grid, float tmin, float tmax, void* points, hipStream_t stream);
 hipError_t sol_launch_volume_build(uint32_t n_probes, const void* sh, const void* visibility, float radius, void* probes, hipStream_t stream);
 hipError_t sol_launch_volume_sample(const SolVolumeGrid& grid, bool load_all, const void* probes, const void* points, uint32_t n, void* out, hipStream_t stream);
+// ---- sol_depth.hip: directional distance moments. each: RadianceParams as for an `each` launch of sol_radiance.hip - a work item is
+// (point, sample), sample-major, n_items = n_groups * 64 * the launch's samples -, one word per item to `partial` [sample - first_sample][n_groups * 64].
+// project: after it, the launch's win_samples words of every point added into its res x res SolOctTexel rows in chunk order onto 0 (or, accumulate,
+// onto what `out` holds); plain: the measured alternative, a thread per texel. build: n_texels SolOctTexel in, as many SolDepthTexel out. ----
+hipError_t sol_launch_depth_each(const DevScene* dS, const RadianceParams& P, bool may_spill, bool strict, const void* points, const void* keys, void* partial,
+                                 uint32_t* work, uint32_t* spill, uint32_t grid, hipStream_t stream);
+int sol_depth_each_blocks_per_cu(bool strict);
+hipError_t sol_launch_depth_project(const RadianceParams& P, bool plain, uint32_t res, uint32_t sharpness, const void* points, const void* keys, const void* partial,
+                                    void* out, uint32_t win_samples, bool accumulate, hipStream_t stream);
+hipError_t sol_launch_depth_build(uint64_t n_texels, const void* oct, float radius, void* depth, hipStream_t stream);
+hipError_t sol_launch_volume_sample_depth(const SolVolumeGrid& grid, const void* probes, const void* depth, uint32_t res, const void* points, uint32_t n, void* out,
+                                          hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

@@ -132,6 +132,7 @@ struct SolDevOverrides {
   int pool_slots = 0, wf_slots = 0, wf_min_items = -1;  // SOL_POOL_SLOTS / SOL_WF_SLOTS / SOL_WF_MIN_ITEMS (v2 / v3)
   std::string rccl_lib;          // SOL_RCCL_LIB: the communication library to dlopen instead of librccl.so.1 (tests)
   int lightmap_claim = 0;        // SOL_LIGHTMAP_CLAIM=lane|wave: the claim pass of sol_lightmap_points as one of its two plain candidates (1, 2; 0: the product's hybrid)
+  bool depth_project_plain = false;  // SOL_DEPTH_PROJECT=plain: sol_visibility_oct projects with a thread per (point, texel) that draws every direction itself (the measured alternative; the same words)
   bool volume_load_all = false;  // SOL_VOLUME_SAMPLE=loadall: sol_volume_sample fetches the zero-weight corners of a cell too (the measured alternative; the same words)
   bool verbose = false;          // SOL_VERBOSE
 };
@@ -320,6 +321,10 @@ struct SolScene {
   // measured alternative (SOL_VOLUME_SAMPLE=loadall).
   DevBuf<char> vol_stage;
   bool vol_load_all = false;
+  // Directional distance moments (sol_depth.hip) share the radiance queries' buffers: a row of rad_partial holds the words of four
+  // (sample, point) pairs under the same bound counted in words, rad_out res x res rows per staged point; build and sample stage through vol_stage.
+  // depth_project_plain: the projection kernel's measured alternative (SOL_DEPTH_PROJECT=plain).
+  bool depth_project_plain = false;
   SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
@@ -345,6 +350,12 @@ inline int sol_scene_to_device(SolScene* s) { return s->mirror.upload(s->stream,
 // grid x SOL_WG x (stack_need - lds_depth) words, 16 when the searches fit the kernel's LDS stack.
 int sol_launch_plan(SolScene* s, int blocks_per_cu, uint64_t items, uint32_t lds_depth, uint32_t stack_need, DevBuf<uint32_t>& spill, uint32_t* grid);
 int sol_set_partition(SolScene* s, int rank, int world);
+// What sol_depth.cpp shares with the calls it extends. sol_gather_config_check (sol_api.cpp): the SolIrradianceConfig and n as sol_irradiance judge
+// them, in its order and words; *cfg is the configuration as the launches take it. sol_query_medium_check (sol_api.cpp): sol_query's refusal of a
+// constant medium. sol_volume_grid_check (sol_volume.cpp): what every volume call refuses about the scene pointer and the grid, in the header's order.
+int sol_gather_config_check(const char* fn, size_t n, const SolIrradianceConfig* config, SolRadianceConfig* cfg);
+int sol_query_medium_check(const SolScene* s, const char* fn);
+int sol_volume_grid_check(bool have_scene, const char* fn, const SolVolumeGrid* g);
 
 // One launch of sol_render_impl (sol_launch.cpp): what differs between its callers, and nothing else - the handle supplies what is not per launch
 // (partition, scratch buffers, options, stream, timing events). sol_render_job is the job with every default: the handle's own scene record,

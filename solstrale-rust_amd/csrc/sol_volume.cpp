@@ -51,6 +51,9 @@ int sample_check(bool have_scene, const char* fn, const SolVolumeGrid* g, const 
   if (n > 0 && (!probes || !points || !out)) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !probes ? "probe" : !points ? "point" : "output");
   return SOL_OK;
 }
+}  // namespace
+int sol_volume_grid_check(bool have_scene, const char* fn, const SolVolumeGrid* g) { return grid_check(have_scene, fn, g); }  // (sol_scene.h: for sol_depth.cpp)
+namespace {
 size_t probes_of(const SolVolumeGrid& g) { return (size_t)g.nx * g.ny * g.nz; }
 
 // the host routes' staging: consecutive arrays in SolScene::vol_stage, each 256-byte aligned

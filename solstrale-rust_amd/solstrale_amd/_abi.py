@@ -281,6 +281,25 @@ class SolProbe(C.Structure):
 
 SOL_VOLUME_BACKFACE, SOL_VOLUME_CHEBYSHEV, SOL_VOLUME_MAX_PROBES, SOL_PROBE_VALID, SOL_PROBE_MOMENTS = 1, 2, 1 << 24, 1, 2
 
+
+class SolOctConfig(C.Structure):
+    """EXTENSION: the octahedral maps of the directional distance moments (sol_visibility_oct, sol_volume_build_depth, sol_volume_sample_depth;
+    DESIGN.md 25): size = sizeof, res x res texels per map (4, 8 or 16), the lobe's exponent as a power of two (0..6), reserved = 0. 16 bytes.
+    Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("res", C.c_uint32), ("sharpness_log2", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SolOctTexel(C.Structure):
+    """EXTENSION: one texel of what sol_visibility_oct gathers: the sums of the lobe weights of all samples, of the open ones, and of weight x
+    distance and weight x distance^2 of the hits. 16 bytes."""
+    _fields_ = [("w", C.c_float), ("w_open", C.c_float), ("wt", C.c_float), ("wt2", C.c_float)]
+
+
+class SolDepthTexel(C.Structure):
+    """EXTENSION: one texel of a probe's depth map as sol_volume_build_depth writes it: the mean and the mean square of the hit distance in the
+    texel's direction, clamped to the radius. 8 bytes."""
+    _fields_ = [("mean", C.c_float), ("mean2", C.c_float)]
+
 SOL_CAMERA_NO_BACKGROUND_PROOF, SOL_CAMERA_REPROBE = 1, 2
 
 
@@ -412,6 +431,12 @@ def load_hip():
     _sig(lib, "sol_volume_build", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_sample_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_volume_sample", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_visibility_oct_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.POINTER(SolOctConfig), C.c_void_p])
+    _sig(lib, "sol_visibility_oct", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.POINTER(SolOctConfig), C.c_void_p])
+    _sig(lib, "sol_volume_build_depth_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.POINTER(SolOctConfig), C.c_float, C.c_void_p])
+    _sig(lib, "sol_volume_build_depth", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.POINTER(SolOctConfig), C.c_float, C.c_void_p])
+    _sig(lib, "sol_volume_sample_depth_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.POINTER(SolOctConfig), C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_volume_sample_depth", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.POINTER(SolOctConfig), C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_scene_set_camera", C.c_int, [P, C.POINTER(SolCamera), C.POINTER(SolCameraUpdate)])
     _sig(lib, "sol_scene_background_flags", C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)])
     _sig(lib, "sol_triangle_from_vertices", C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SolTriangle)])
@@ -444,7 +469,9 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys", "sol_irradiance_dev", "sol_irradiance", "sol_irradiance_rays",
                "sol_irradiance_sh_dev", "sol_irradiance_sh", "sol_visibility_dev", "sol_visibility",
                "sol_lightmap_points_dev", "sol_lightmap_points", "sol_lightmap_dilate_dev", "sol_lightmap_dilate",
-               "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample"]
+               "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
+               "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
+               "sol_volume_sample_depth"]
 
 
 def load_host():

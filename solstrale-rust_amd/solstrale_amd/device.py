@@ -150,6 +150,9 @@ def lightmap_texels_to_numpy(rows):
     return np.ascontiguousarray(rows.cpu().numpy()).view(LIGHTMAP_TEXEL_DTYPE).reshape(-1)
 
 
+# What sol_visibility_oct gathers per texel and what sol_volume_build_depth makes of it.
+OCT_TEXEL_DTYPE = np.dtype([("w", np.float32), ("w_open", np.float32), ("wt", np.float32), ("wt2", np.float32)])
+DEPTH_TEXEL_DTYPE = np.dtype([("mean", np.float32), ("mean2", np.float32)])
 # A SolProbe of sol_volume_build: the irradiance coefficients e[k][channel], the hit-distance moments, flags (1 valid, 2 has moments).
 VOLUME_PROBE_DTYPE = np.dtype([("e", np.float32, (9, 3)), ("mean", np.float32), ("mean2", np.float32), ("flags", np.uint32), ("samples", np.uint32),
                                ("reserved", np.uint32)])
@@ -541,7 +544,7 @@ class DeviceScene:
                                      seed=int(seed), key_base=int(key_base) & 0xFFFFFFFF)
         return self._radiance(self.lib.sol_radiance, self.lib.sol_radiance_dev, "rays", "origin xyz, tmin, direction xyz, tmax", rays, keys, cfg)
 
-    def _radiance(self, host_fn, dev_fn, what, row, rays, keys, cfg, words=4):
+    def _radiance(self, host_fn, dev_fn, what, row, rays, keys, cfg, words=4, raw=False):
         """The two routes radiance(), irradiance(), irradiance_sh() and visibility() share: `rays` are the [n, 8] rows (`what`: their name in messages,
         `row`: their words), `words` the 32-bit words of an answer (4: a SolRadiance, returned split into sums and counts; 28: a SolSh9 and 8: a
         SolVisibility, returned raw)."""
@@ -557,7 +560,7 @@ class DeviceScene:
                 k = np.ascontiguousarray(k)
             out = np.zeros((a.shape[0], words), dtype=np.float32)
             self._chk(host_fn(self.h, a.ctypes.data, None if k is None else k.ctypes.data, a.shape[0], C.byref(cfg), out.ctypes.data))
-            if words != 4:
+            if words != 4 or raw:
                 return out
             return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
         import torch
@@ -807,13 +810,17 @@ class DeviceScene:
         self.sync()
         return out
 
-    def volume_sample(self, grid, probes, points):
+    def volume_sample(self, grid, probes, points, depth=None, res=8):
         """sol_volume_sample: the irradiance at the caller's points - rows of (position xyz, tmin, normal xyz, tmax), irradiance()'s rows; tmin and
         tmax are not read - interpolated from the probes of `grid` that volume_build packed: trilinear weights over the cell of position + unit
         normal * normal_bias, times the backface and Chebyshev weights the grid's flags ask for, invalid probes left out. Host arrays (probes: a
         VOLUME_PROBE_DTYPE array or raw [n, 32] float32 rows) go the host route and return (rgb [n, 3] float32, samples [n] uint32), samples being
         the probes that contributed, 0 to 8; device tensors go through sol_volume_sample_dev without a copy and return the raw [n, 4] float32
-        rows, which lightmap_dilate takes as they are."""
+        rows, which lightmap_dilate takes as they are. depth (sol_volume_sample_depth): the probes' res x res depth maps as
+        volume_build_depth returned them (a DEPTH_TEXEL_DTYPE array, raw [n_probes, res * res, 2] float32 rows, or that device tensor) - the
+        Chebyshev weight then reads mean and mean2 from a probe's map in the direction of the point instead of the probe's two isotropic words."""
+        if depth is not None:
+            return self._volume_sample_depth(grid, probes, points, depth, res)
         rec, rows = grid.record(), self._volume_rows(grid)
         if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):  # the host route
             a = np.ascontiguousarray(points, dtype=np.float32)
@@ -834,6 +841,81 @@ class DeviceScene:
         out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
         torch.cuda.current_stream(points.device).synchronize()  # (the points may still be in the making on torch's stream: the scene's is another)
         self._chk(self.lib.sol_volume_sample_dev(self.h, C.byref(rec), p_probes, p_points, n, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    # ---- directional distance moments: octahedral maps (EXTENSION) ----
+    @staticmethod
+    def _oct_config(res, sharpness_log2=0):
+        return _abi.SolOctConfig(size=C.sizeof(_abi.SolOctConfig), res=int(res) & 0xFFFFFFFF, sharpness_log2=int(sharpness_log2) & 0xFFFFFFFF, reserved=0)
+
+    @staticmethod
+    def _oct_texels(res):
+        """The texels per map to allocate for `res`; 1 for a res the library refuses."""
+        return int(res) * int(res) if res in (4, 8, 16) else 1
+
+    def visibility_oct(self, points, res=8, sharpness_log2=5, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="sphere"):
+        """sol_visibility_oct: visibility(distances=True)'s samples at the caller's points, gathered per direction into a res x res octahedral map
+        (res 4, 8 or 16): every texel sums the lobe weight c = max(dot(texel direction, sample direction), 0) ^ (2 ^ sharpness_log2) of all
+        samples (w), of the misses (w_open), and c * t and c * t * t of the hits (wt, wt2) - what volume_build_depth turns into a probe's
+        depth map. Returns [n, res * res, 4] float32: a numpy array on the host route (OCT_TEXEL_DTYPE views it), a device tensor on the device
+        route. points, keys, key_base, first_draw and the waits of the two routes are irradiance()'s."""
+        cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
+        oct_cfg, texels = self._oct_config(res, sharpness_log2), self._oct_texels(res)
+        rows = self._radiance(lambda h, p, k, n, c, o: self.lib.sol_visibility_oct(h, p, k, n, c, C.byref(oct_cfg), o),
+                              lambda h, p, k, n, c, o: self.lib.sol_visibility_oct_dev(h, p, k, n, c, C.byref(oct_cfg), o), "points",
+                              "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=4 * texels, raw=True)
+        return rows.reshape(-1, texels, 4)
+
+    def volume_build_depth(self, grid, oct, radius, res=8, sharpness_log2=5):
+        """sol_volume_build_depth: the probes' depth maps from what visibility_oct(volume_points(grid, tmax=radius), res, ..) answered: per texel
+        the mean and the mean square of the hit distance clamped to `radius` - (radius, radius^2) where the texel saw nothing. Returns
+        [n_probes, res * res, 2] float32, a numpy array for a host array (DEPTH_TEXEL_DTYPE views it) and a device tensor for a device tensor."""
+        rec, rows = grid.record(), self._volume_rows(grid)
+        oct_cfg, texels = self._oct_config(res, sharpness_log2), self._oct_texels(res)
+        if isinstance(oct, np.ndarray) or not hasattr(oct, "data_ptr"):  # the host route
+            a = np.ascontiguousarray(oct)
+            a = np.ascontiguousarray(a.view(np.float32) if a.dtype == OCT_TEXEL_DTYPE else a.astype(np.float32, copy=False)).reshape(-1, texels, 4)
+            if a.shape[0] != rows:
+                raise ValueError("oct: [n_probes, res * res, 4] float32 rows as visibility_oct returned them, one map per probe of the grid")
+            out = np.zeros((rows, texels, 2), dtype=np.float32)
+            self._chk(self.lib.sol_volume_build_depth(self.h, C.byref(rec), a.ctypes.data, C.byref(oct_cfg), float(radius), out.ctypes.data))
+            return out
+        import torch
+        p_oct = self._volume_tensor("oct", oct.reshape(oct.shape[0], -1), rows, texels * 4)
+        out = torch.empty((rows, texels, 2), dtype=torch.float32, device=oct.device)
+        torch.cuda.current_stream(oct.device).synchronize()  # (the sums may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_volume_build_depth_dev(self.h, C.byref(rec), p_oct, C.byref(oct_cfg), float(radius), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def _volume_sample_depth(self, grid, probes, points, depth, res):
+        rec, rows = grid.record(), self._volume_rows(grid)
+        oct_cfg, texels = self._oct_config(res), self._oct_texels(res)
+        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):  # the host route
+            a = np.ascontiguousarray(points, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 8:
+                raise ValueError("points: an [n, 8] float32 array of (position xyz, tmin, normal xyz, tmax)")
+            p = volume_probes_to_numpy(probes) if hasattr(probes, "data_ptr") else np.ascontiguousarray(probes)
+            p = p.view(np.float32).reshape(-1, 32) if p.dtype == VOLUME_PROBE_DTYPE else np.ascontiguousarray(p, dtype=np.float32)
+            if p.shape != (rows, 32):
+                raise ValueError("probes: a VOLUME_PROBE_DTYPE array or raw [n, 32] float32 rows, one per probe of the grid")
+            d = np.ascontiguousarray(depth.cpu().numpy() if hasattr(depth, "data_ptr") else depth)
+            d = np.ascontiguousarray(d.view(np.float32) if d.dtype == DEPTH_TEXEL_DTYPE else d.astype(np.float32, copy=False)).reshape(-1, texels, 2)
+            if d.shape[0] != rows:
+                raise ValueError("depth: [n_probes, res * res, 2] float32 rows as volume_build_depth returned them, one map per probe of the grid")
+            out = np.zeros((a.shape[0], 4), dtype=np.float32)
+            self._chk(self.lib.sol_volume_sample_depth(self.h, C.byref(rec), np.ascontiguousarray(p).ctypes.data, d.ctypes.data, C.byref(oct_cfg), a.ctypes.data,
+                                                       a.shape[0], out.ctypes.data))
+            return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
+        import torch
+        p_points = self._volume_tensor("points", points, None, 8)
+        p_probes = self._volume_tensor("probes", probes, rows, 32)
+        p_depth = self._volume_tensor("depth", depth.reshape(depth.shape[0], -1) if hasattr(depth, "data_ptr") else depth, rows, texels * 2)
+        n = int(points.shape[0])
+        out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+        torch.cuda.current_stream(points.device).synchronize()  # (the points may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_volume_sample_depth_dev(self.h, C.byref(rec), p_probes, p_depth, C.byref(oct_cfg), p_points, n, C.c_void_p(out.data_ptr())))
         self.sync()
         return out
 
