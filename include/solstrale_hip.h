@@ -1055,6 +1055,63 @@ int sol_volume_sample_depth_dev(SolScene* scene, const SolVolumeGrid* grid, cons
 int sol_volume_sample_depth(SolScene* scene, const SolVolumeGrid* grid, const SolProbe* probes, const SolDepthTexel* depth, const SolOctConfig* oct_config,
                             const SolRay* points, size_t n, SolRadiance* out);
 
+/* ---- lightmap filtering: chart-aware a-trous denoising of a baked atlas (EXTENSION, not in the reference) --------------------
+ * A gather at the sample counts people bake at is noisy, and an atlas is filtered before it is padded: points -> gather -> filter -> dilate
+ * is four calls on device memory. The guides are the atlas's own: every texel's world position and normal are in the point rows
+ * sol_lightmap_points wrote, ownership is in the SolTexel rows, and irradiance is pre-albedo, so nothing is demodulated. The handle supplies the
+ * device, the stream and the scratch; the scene is never read: nothing is traced, and a scene with a constant medium is served. All arithmetic is
+ * fp32, every operation rounded once, no fused multiply-add, `/` correctly rounded, no expf or powf; every clamp is a comparison.
+ * csrc/sol_lightmap_filter.h is the rule as code and tests/lightmap_filter_ref.py its restatement in numpy. dot(a, b) is
+ * ((ax * bx) + (ay * by)) + (az * bz); pos(x) is x > 0 ? x : 0 (a NaN and -0 give +0).
+ *   Inputs.   points: W x H SolRay rows as sol_lightmap_points writes them (position, tmin, normal, tmax); texels: W x H SolTexel rows; values:
+ *             W x H rows of stride_bytes whose leading `channels` words (1..32) are floats - the rows sol_lightmap_dilate takes: SolRadiance
+ *             (3 channels, stride 16), SolSh9 (27, 112), plain planes. out: the same shape; it may not be values.
+ *   Live.     A texel is live when texels[x].triangle != SOL_TEXEL_NONE (a conservative-only texel counts), the three position words and the
+ *             three normal words of its point row are finite, and its `channels` value words are finite. Judged once, on the call's inputs.
+ *   Not live. Row x of out is row x of values, copied whole; the texel is never a tap.
+ *   Passes.   Pass i = 0 .. iterations - 1 has step = 1 << i and f = (float)step (exact). Its input x is values for pass 0, else the output of
+ *             pass i - 1. For a live centre p at (px, py) the taps are the 25 texels (px + di * step, py + dj * step), dj the outer loop from -2
+ *             to 2, di the inner loop from -2 to 2. A tap outside the atlas (no wrap) or not live is skipped.
+ *   Weight.   k = h[di + 2] * h[dj + 2], h = (1/16, 1/4, 3/8, 1/4, 1/16): exact products. The centre tap has w = k. Any other tap q, with
+ *             E = P_q - P_p per component and n_p, n_q the stored normals (not renormalised):
+ *               s  = sigma_position * f;  l2 = dot(E, E);    w_d  = 1 / (1 + (l2 / (s * s)))
+ *               sp = sigma_plane * f;     d  = dot(n_p, E);  w_pl = 1 / (1 + ((d * d) / (sp * sp)))
+ *               c  = pos(dot(n_p, n_q));  then c = c * c, normal_power_log2 times
+ *               m  = min(channels, 3);  D = 0;  per channel j < m in order:  a = pos(x_p[j] * value_scale);  ta = a / (1 + a);  tb likewise from
+ *                    x_q[j];  dv = ta - tb;  D = D + (dv * dv)
+ *               sv = sigma_value / f;     w_v = 1 / (1 + (D / (sv * sv)));  w_v = w_v * w_v
+ *               w  = (((k * w_d) * w_pl) * c) * w_v
+ *             A tap whose w is not > 0 (a NaN too) is skipped. A sigma of +inf switches its factor off exactly: x / inf = 0, 1 / (1 + 0) = 1.
+ *   Sums.     From 0, in tap order, one lane per sum: sum[j] = sum[j] + (w * x_q[j]) for every channel j < channels; wsum = wsum + w. The pass
+ *             writes sum[j] / wsum; the centre always counts, so wsum >= 9/64. The words of a row behind `channels` (a SolRadiance's samples)
+ *             are the centre's words in values, carried through every pass. The last pass writes out.
+ * No float atomics, no dependence on scheduling. Neutral as the queries are: no accumulator, plane, counter or statistic is touched.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for, from the arguments alone and in this order: a null scene; a null
+ * configuration; a wrong size; reserved != 0; width or height of 0 or above 16384; iterations outside 1..8; normal_power_log2 above 7; a sigma
+ * that is NaN or below 1e-6 (position, plane, value: the first is named); a value_scale that is not finite and > 0; channels outside 1..32; a
+ * stride that is no multiple of 4 or below 4 x channels; a null point, texel, value or output pointer, in that order; out == values.
+ * SOL_EDEVICE without a GPU comes after all of these. There is no host mirror. */
+/* 64 bytes: size 0, width 4, height 8, iterations 12, normal_power_log2 16, channels 20, stride_bytes 24, sigma_position 28, sigma_plane 32,
+ * sigma_value 36, value_scale 40, reserved 44 */
+typedef struct SolLightmapFilterConfig {
+  uint32_t size, width, height; /* size = sizeof(SolLightmapFilterConfig); the atlas, 1 .. 16384 each way */
+  uint32_t iterations;          /* 1..8 passes; pass i has step 1 << i */
+  uint32_t normal_power_log2;   /* 0..7: the normal factor is pos(dot(n_p, n_q)) to the power 2^normal_power_log2 */
+  uint32_t channels;            /* 1..32 leading float words of a row */
+  uint32_t stride_bytes;        /* of a row of values and of out: a multiple of 4, at least 4 x channels */
+  float sigma_position;         /* a world length; >= 1e-6 or +inf */
+  float sigma_plane;            /* a world length; >= 1e-6 or +inf */
+  float sigma_value;            /* in tone-mapped units (x / (1 + x)); >= 1e-6 or +inf */
+  float value_scale;            /* finite, > 0: what a value is multiplied with before it is tone-mapped (pi / samples for irradiance sums) */
+  uint32_t reserved[5];         /* zero */
+} SolLightmapFilterConfig;
+/* Device pointers (W x H SolRay, W x H SolTexel, W x H rows of stride_bytes in and out; points and texels 16-byte aligned, rows 4-byte aligned;
+ * on the scene's device), one stream-ordered sequence of launches on the scene's stream, asynchronous. */
+int sol_lightmap_filter_dev(SolScene* scene, const SolLightmapFilterConfig* config, const void* points_dev, const void* texels_dev, const void* values_dev,
+                            void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_filter(SolScene* scene, const SolLightmapFilterConfig* config, const SolRay* points, const SolTexel* texels, const void* values, void* out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

@@ -66,6 +66,8 @@ SolDevOverrides sol_dev_overrides() {
   if (const char* v = std::getenv("SOL_LIGHTMAP_CLAIM")) o.lightmap_claim = std::strcmp(v, "lane") == 0 ? 1 : std::strcmp(v, "wave") == 0 ? 2 : 0;
   if (const char* v = std::getenv("SOL_DEPTH_PROJECT")) o.depth_project_plain = std::strcmp(v, "plain") == 0;
   if (const char* v = std::getenv("SOL_VOLUME_SAMPLE")) o.volume_load_all = std::strcmp(v, "loadall") == 0;
+  if (const char* v = std::getenv("SOL_LIGHTMAP_FILTER"))
+    o.lightmap_filter = std::strcmp(v, "plain") == 0 ? 1 : std::strcmp(v, "staged") == 0 ? 2 : std::strcmp(v, "fold") == 0 ? 3 : 0;
   o.verbose = std::getenv("SOL_VERBOSE") != nullptr;
   return o;
 }

@@ -925,6 +925,7 @@ static int set_scene_constants(const CreateCtx& c, const World& w, SolScene* s, 
   if (ovr.lightmap_claim == 1) s->lm_small_max = 0xFFFFFFFFu;                                 // a lane per triangle
   if (ovr.lightmap_claim == 2) { s->lm_small_max = 0u; s->lm_tiles_max = 0xFFFFFFFFu; }        // a wave per triangle
   s->vol_load_all = ovr.volume_load_all;
+  if (ovr.lightmap_filter) { s->lf_staged = ovr.lightmap_filter == 2; s->lf_fold = ovr.lightmap_filter == 3; }
   s->depth_project_plain = ovr.depth_project_plain;
   s->order_mode = ovr.order_mode;
   // v1's search/shade switch (RenderParams::switch_below), measured on MI355X at 1080p x 128 spp (ms, C1 / C2 / C3 / test scene):

@@ -121,6 +121,15 @@ hipError_t sol_launch_depth_project(const RadianceParams& P, bool plain, uint32_
 hipError_t sol_launch_depth_build(uint64_t n_texels, const void* oct, float radius, void* depth, hipStream_t stream);
 hipError_t sol_launch_volume_sample_depth(const SolVolumeGrid& grid, const void* probes, const void* depth, uint32_t res, const void* points, uint32_t n, void* out,
                                           hipStream_t stream);
+// ---- sol_lightmap_filter.hip: lightmap filtering. guide: 2 x W x H dwordx4; a value plane: ceil(channels / 4) x W x H dwordx4, by
+// channel group. prepare: liveness judged, guides packed, the rows copied to `out` whole, the channels to `plane`. pass i: `in` -> out_plane, or,
+// the last one, -> the channel words of the live rows of out_rows. staged: steps 1 and 2 read their taps from a tile in LDS (the same words);
+// fold_groups: one lane adds every channel group of its texel instead of one ----
+struct SolLightmapFilterConfig;
+hipError_t sol_launch_lightmap_filter_prepare(const void* texels, const void* points, const void* values, uint32_t n_texels, uint32_t channels,
+                                              uint32_t stride_words, void* guide, void* plane, void* out, hipStream_t stream);
+hipError_t sol_launch_lightmap_filter_pass(const SolLightmapFilterConfig& c, uint32_t pass, bool staged, bool fold_groups, const void* guide, const void* in,
+                                           void* out_plane, void* out_rows, hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

@@ -10,6 +10,7 @@
 //   sol_camera.cpp  sol_scene_set_camera: a new camera for a live scene, its background blocks re-proved on the device (sol_camera.hip)
 //   sol_geometry.cpp sol_scene_set_triangles / sol_scene_set_primitives: the triangles, spheres and quads of a live scene moved, records and tree boxes recomputed on the device (sol_geometry.hip)
 //   sol_lightmap.cpp sol_lightmap_points / sol_lightmap_dilate: lightmap UVs rasterised into gather points, chart borders dilated (sol_lightmap.hip)
+//   sol_lightmap_filter.cpp sol_lightmap_filter: chart-aware a-trous filtering of a baked atlas (sol_lightmap_filter.hip)
 //   sol_volume.cpp  sol_volume_points / sol_volume_build / sol_volume_sample: a probe grid laid out, packed and sampled (sol_volume.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
@@ -134,6 +135,7 @@ struct SolDevOverrides {
   int lightmap_claim = 0;        // SOL_LIGHTMAP_CLAIM=lane|wave: the claim pass of sol_lightmap_points as one of its two plain candidates (1, 2; 0: the product's hybrid)
   bool depth_project_plain = false;  // SOL_DEPTH_PROJECT=plain: sol_visibility_oct projects with a thread per (point, texel) that draws every direction itself (the measured alternative; the same words)
   bool volume_load_all = false;  // SOL_VOLUME_SAMPLE=loadall: sol_volume_sample fetches the zero-weight corners of a cell too (the measured alternative; the same words)
+  int lightmap_filter = 0;       // SOL_LIGHTMAP_FILTER=plain|staged|fold: the pass kernel of sol_lightmap_filter as one of its measured shapes (1, 2, 3: plain with every channel group in one lane; 0: the product's, staged; the same words)
   bool verbose = false;          // SOL_VERBOSE
 };
 SolDevOverrides sol_dev_overrides();
@@ -317,6 +319,12 @@ struct SolScene {
   DevBuf<uint32_t> lm_owner;
   DevBuf<char> lm_stage;
   uint32_t lm_small_max = 16, lm_tiles_max = 64;
+  // Lightmap filtering (sol_lightmap_filter.hip). lf_guide: the packed guide plane, two dwordx4 per texel; lf_planes: the two ping-pong
+  // value planes, ceil(channels / 4) dwordx4 per texel each; the host route stages through lm_stage. lf_staged / lf_fold: the pass shape
+  // (SOL_LIGHTMAP_FILTER; the product's is staged - steps 1 and 2 from a tile in LDS -, a lane per (texel, channel group): the faster one at
+  // 1024^2 and 4096^2, profiles/lightmap_filter.txt).
+  DevBuf<float4> lf_guide, lf_planes;
+  bool lf_staged = true, lf_fold = false;
   // Irradiance volumes (sol_volume.hip). vol_stage: what the host routes stage, inputs and outputs. vol_load_all: the sampler's
   // measured alternative (SOL_VOLUME_SAMPLE=loadall).
   DevBuf<char> vol_stage;

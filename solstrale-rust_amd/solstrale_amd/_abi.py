@@ -264,6 +264,15 @@ class SolTexel(C.Structure):
 SOL_LIGHTMAP_CONSERVATIVE, SOL_LIGHTMAP_MAX_SIZE, SOL_TEXEL_NONE = 1, 16384, 0xFFFFFFFF
 
 
+class SolLightmapFilterConfig(C.Structure):
+    """EXTENSION: the configuration of sol_lightmap_filter: size = sizeof, W x H texels, 1..8 passes, the normal factor's exponent as a
+    power of two (0..7), the rows' channels and stride, the widths of the distance, plane and value factors (>= 1e-6 or +inf), the scale a value is
+    multiplied with before it is tone-mapped, reserved = 0. 64 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32),
+                ("channels", C.c_uint32), ("stride_bytes", C.c_uint32), ("sigma_position", C.c_float), ("sigma_plane", C.c_float),
+                ("sigma_value", C.c_float), ("value_scale", C.c_float), ("reserved", C.c_uint32 * 5)]
+
+
 class SolVolumeGrid(C.Structure):
     """EXTENSION: the probe grid of an irradiance volume (sol_volume_points / _build / _sample): size = sizeof, nx x ny x nz probes, the
     position of probe (0, 0, 0), the spacing per axis, flags (SOL_VOLUME_BACKFACE | SOL_VOLUME_CHEBYSHEV) and the normal bias of a sample. 48 bytes.
@@ -425,6 +434,8 @@ def load_hip():
     _sig(lib, "sol_lightmap_points", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolLightmapConfig), C.c_void_p, C.c_void_p])
     _sig(lib, "sol_lightmap_dilate_dev", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_lightmap_dilate", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_filter_dev", C.c_int, [P, C.POINTER(SolLightmapFilterConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_filter", C.c_int, [P, C.POINTER(SolLightmapFilterConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -469,6 +480,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_radiance_dev", "sol_radiance", "sol_camera_ray_keys", "sol_irradiance_dev", "sol_irradiance", "sol_irradiance_rays",
                "sol_irradiance_sh_dev", "sol_irradiance_sh", "sol_visibility_dev", "sol_visibility",
                "sol_lightmap_points_dev", "sol_lightmap_points", "sol_lightmap_dilate_dev", "sol_lightmap_dilate",
+               "sol_lightmap_filter_dev", "sol_lightmap_filter",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

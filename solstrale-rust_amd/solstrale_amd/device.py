@@ -740,6 +740,53 @@ class DeviceScene:
         self.sync()
         return (out, pass_of) if return_pass_of else out
 
+    # ---- lightmap filtering (EXTENSION) ----
+    def lightmap_filter(self, values, points, texels, width, height, sigma_position, sigma_plane=None, iterations=4, normal_power_log2=5, sigma_value=0.25,
+                        value_scale=1.0, channels=3):
+        """sol_lightmap_filter: the chart-aware a-trous filter between the gather and lightmap_dilate. values: `width * height` rows whose leading
+        `channels` 32-bit words are floats (a [n, k] float32 array or tensor - the raw rows a gather returned: channels=3 for radiance / irradiance
+        rows, 27 for irradiance_sh); points, texels: what lightmap_points returned. sigma_position is a WORLD LENGTH, about two texels' world size:
+        the distance factor of pass i is 1 / (1 + |P_q - P_p|^2 / (sigma_position * 2^i)^2), and it is what keeps charts that are neighbours in the
+        atlas from mixing. sigma_plane (None: sigma_position) is the same for the distance of the tap from the centre's tangent plane. The normal
+        factor is pos(n_p . n_q)^(2^normal_power_log2). sigma_value compares the values after x * value_scale -> a / (1 + a); for irradiance SUMS
+        value_scale is pi / samples, which brings them to irradiance. float("inf") switches a sigma's factor off. `iterations` passes (1..8) with
+        steps 1, 2, 4, .. Rows of texels that are not live (no owner, or a word that is not finite) come back as they went in. Host arrays go the
+        host route, device tensors the device route, and the answer has the shape and place of `values`."""
+        width, height = int(width), int(height)
+        host = isinstance(values, np.ndarray) or not hasattr(values, "data_ptr")
+        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
+        cfg = _abi.SolLightmapFilterConfig(size=C.sizeof(_abi.SolLightmapFilterConfig), width=width, height=height, iterations=int(iterations),
+                                           normal_power_log2=int(normal_power_log2), channels=int(channels), stride_bytes=4 * k,
+                                           sigma_position=float(sigma_position), sigma_plane=float(sigma_position if sigma_plane is None else sigma_plane),
+                                           sigma_value=float(sigma_value), value_scale=float(value_scale))
+        if host:
+            v = np.ascontiguousarray(values, dtype=np.float32)
+            p = np.ascontiguousarray(points.cpu().numpy() if hasattr(points, "data_ptr") else points, dtype=np.float32)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            if (v.ndim != 2 or v.shape[0] != width * height or p.shape != (width * height, 8) or t.dtype != LIGHTMAP_TEXEL_DTYPE
+                    or t.shape != (width * height,)):
+                raise ValueError("values: [width * height, k] float32 rows; points: [width * height, 8] float32 rows; texels: width * height "
+                                 "LIGHTMAP_TEXEL_DTYPE rows")
+            out = np.zeros_like(v)
+            self._chk(self.lib.sol_lightmap_filter(self.h, C.byref(cfg), p.ctypes.data, t.ctypes.data, v.ctypes.data, out.ctypes.data))
+            return out
+        import torch
+        if (values.dtype != torch.float32 or values.dim() != 2 or values.shape[0] != width * height or not values.is_contiguous() or not values.is_cuda
+                or values.device.index != self.device):
+            raise ValueError("values: a contiguous [width * height, k] float32 tensor on the scene's device")
+        if (not hasattr(points, "data_ptr") or points.dtype != torch.float32 or tuple(points.shape) != (width * height, 8) or not points.is_contiguous()
+                or points.device != values.device):
+            raise ValueError("points: the contiguous [width * height, 8] float32 tensor lightmap_points returned, on the device of values")
+        if (not hasattr(texels, "data_ptr") or texels.dtype != torch.int32 or tuple(texels.shape) != (width * height, 4) or not texels.is_contiguous()
+                or texels.device != values.device):
+            raise ValueError("texels: the contiguous [width * height, 4] int32 tensor lightmap_points returned, on the device of values")
+        out = torch.empty_like(values)
+        torch.cuda.current_stream(values.device).synchronize()  # (the values may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_filter_dev(self.h, C.byref(cfg), C.c_void_p(points.data_ptr()), C.c_void_p(texels.data_ptr()),
+                                                   C.c_void_p(values.data_ptr()), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
     # ---- irradiance volumes (EXTENSION; DESIGN.md 24) ----
     @staticmethod
     def _volume_rows(grid):
