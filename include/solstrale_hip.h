@@ -1112,6 +1112,80 @@ int sol_lightmap_filter_dev(SolScene* scene, const SolLightmapFilterConfig* conf
 /* Host arrays, staged through a buffer the handle owns; blocks. */
 int sol_lightmap_filter(SolScene* scene, const SolLightmapFilterConfig* config, const SolRay* points, const SolTexel* texels, const void* values, void* out);
 
+/* ---- irradiance moments (EXTENSION, not in the reference) -------------------------------------------------------------------
+ * "How noisy is this gather?" - sol_irradiance's answer with the sums of the squared sample colours beside it: error bars on a bake, and what a
+ * variance-guided filter (sol_lightmap_filter_var, below) weighs its taps with.
+ *   Points.   Points, their validity, keys, key_base, first_draw, seed, the sample range and the two modes are sol_irradiance's, word for word. An
+ *             invalid point answers eight zero words, decided before any search.
+ *   Samples.  c_s is the colour sample s contributes: on the bits what sol_radiance_dev(rays_out, keys_out, samples = 1, first_sample = s)
+ *             answers over what sol_irradiance_rays writes for sample s (0 + colour), as for sol_irradiance_sh.
+ *   Sums.     r, g, b are the sums of c_s[channel]; r2, g2, b2 the sums of fl(c_s[channel] x c_s[channel]) - the product rounded once, then
+ *             added: no fused multiply-add. All six in sol_radiance's association: chunks of 16 samples counted from first_sample, a chunk sum
+ *             0 + t + t .. in sample order, the result ((0 + chunk0) + chunk1) + ... samples is the sample count, reserved is 0.
+ *             Consequence: (r, g, b, samples) is sol_irradiance's answer to the same call, bit for bit.
+ *   Estimators. With N = samples: the mean is x = sum / N, and for N >= 2 the variance of that mean is pos((sum2 / N) - (x x)) / (N - 1).
+ *   Neutral.  As sol_radiance. The scratch is shared with the radiance and irradiance queries; calls on one handle are ordered by its stream.
+ * SOL_EINVAL: sol_irradiance's refusals, in the same order and with the same words, before the device is looked for - a scene with a constant
+ * medium among them. n == 0 succeeds on any scene and touches nothing. There is no host mirror. */
+typedef struct SolMoments { float r, g, b; uint32_t samples; float r2, g2, b2; uint32_t reserved; } SolMoments;  /* 32 bytes; 16-byte aligned in device memory; sums */
+/* Device pointers (n SolRay points, n SolRayKey or NULL, n SolMoments out, on the scene's device), on the scene's stream, asynchronous. */
+int sol_irradiance_moments_dev(SolScene* scene, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_irradiance_moments(SolScene* scene, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolMoments* out);
+
+/* ---- variance-guided lightmap filtering (EXTENSION, not in the reference) ---------------------------------------------------
+ * sol_lightmap_filter's value factor compares tone-mapped values against one sigma_value, which cannot serve every sample count: the filter
+ * does not know how noisy a texel is. This one does - it takes the SolMoments rows of sol_irradiance_moments, carries a variance of the mean
+ * beside every value through the passes (as SVGF does for frames) and divides the squared value difference of a tap by it. The chain is
+ * points -> sol_irradiance_moments -> sol_lightmap_filter_var -> sol_lightmap_dilate. Nothing is traced and the scene is never read: a scene
+ * with a constant medium is served. All arithmetic is fp32, every operation rounded once, no fused multiply-add, `/` correctly rounded, no
+ * expf, powf or sqrtf; every clamp is a comparison; dot and pos as for sol_lightmap_filter. csrc/sol_lightmap_filter_var.h is the rule as code
+ * and tests/lightmap_filter_var_ref.py its restatement in numpy.
+ *   Inputs.   points, texels: as for sol_lightmap_filter. moments: W x H SolMoments rows. out: W x H SolRadiance rows - what sol_lightmap_filter
+ *             returns for such a bake and what sol_lightmap_dilate takes (3 channels, stride 16). variance_out: W x H rows of four floats, or NULL.
+ *   Live.     A texel is live when texels[x].triangle != SOL_TEXEL_NONE, the three position and the three normal words of its point row are
+ *             finite, samples >= 2, and its six sums are finite. Judged once, on the call's inputs.
+ *   Not live. Row x of out is the first four words of row x of moments, copied; row x of variance_out is four zero words; never a tap.
+ *   Prepare.  Per live texel, N = (float)samples, M = (float)(samples - 1):  x[j] = sum[j] / N;  v[j] = pos((sum2[j] / N) - (x[j] * x[j])) / M.
+ *   Passes.   Pass i = 0 .. iterations - 1 has step = 1 << i and f = (float)step; its input (x, v) is the previous pass's output. For a live centre p:
+ *     Variance prefilter.  vb[j] and gs from 0 over the nine texels (px + di, py + dj) - one texel apart, not scaled by step -, dj the outer
+ *             loop and di the inner, both from -1 to 1, live taps inside the atlas only: g = h3[di + 1] * h3[dj + 1], h3 = (1/4, 1/2, 1/4), exact;
+ *             vb[j] = vb[j] + (g * v_q[j]);  gs = gs + g.  V = (((vb[0] / gs) + (vb[1] / gs)) + (vb[2] / gs)) + variance_floor.
+ *     Taps.   The 25 taps, their order, the skips, k, E, w_d, w_pl and c are sol_lightmap_filter's (s = sigma_position * f, sp = sigma_plane * f).
+ *     Value factor.  D = 0; per channel j = 0, 1, 2: dv = x_p[j] - x_q[j]; D = D + (dv * dv).  den = (sigma_value * sigma_value) * V.
+ *             w_v = 1 / (1 + (D / den));  w_v = w_v * w_v.  No tone map, and sigma_value is not divided by f: the variance shrinks from pass to
+ *             pass and tightens the factor by itself. sigma_value = +inf switches the factor off exactly.
+ *     Weight. w = (((k * w_d) * w_pl) * c) * w_v; the centre has w = k. A tap whose w is not > 0 (a NaN too) is skipped.
+ *     Sums.   From 0, in tap order: sum[j] = sum[j] + (w * x_q[j]);  vs[j] = vs[j] + ((w * w) * v_q[j]);  wsum = wsum + w.
+ *             The pass writes x'[j] = sum[j] / wsum and v'[j] = vs[j] / (wsum * wsum).
+ *   After the last pass: out = (x[0] * N, x[1] * N, x[2] * N, samples) of the centre - pi x sum / samples still reads it -, variance_out =
+ *             (v[0], v[1], v[2], 0).
+ * No float atomics, no dependence on scheduling; liveness keeps every index inside the atlas. Neutral as the queries are.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for, from the arguments alone and in this order: a null scene; a null
+ * configuration; a wrong size; reserved != 0; width or height of 0 or above 16384; iterations outside 1..8; normal_power_log2 above 7; a sigma
+ * that is NaN or below 1e-6 (position, plane, value: the first is named); a variance_floor that is not finite and > 0; a null point, texel,
+ * moments or output pointer, in that order; out == moments, or variance_out equal to moments or out. SOL_EDEVICE without a GPU comes after all
+ * of these. There is no host mirror. */
+/* 64 bytes: size 0, width 4, height 8, iterations 12, normal_power_log2 16, sigma_position 20, sigma_plane 24, sigma_value 28, variance_floor 32,
+ * reserved 36 */
+typedef struct SolLightmapFilterVarConfig {
+  uint32_t size, width, height; /* size = sizeof(SolLightmapFilterVarConfig); the atlas, 1 .. 16384 each way */
+  uint32_t iterations;          /* 1..8 passes; pass i has step 1 << i */
+  uint32_t normal_power_log2;   /* 0..7: the normal factor is pos(dot(n_p, n_q)) to the power 2^normal_power_log2 */
+  float sigma_position;         /* a world length; >= 1e-6 or +inf */
+  float sigma_plane;            /* a world length; >= 1e-6 or +inf */
+  float sigma_value;            /* in standard deviations of the mean; >= 1e-6 or +inf (4: SVGF's value; not tuned on a device) */
+  float variance_floor;         /* finite, > 0: added to the prefiltered variance (1e-12 is the Python default; not tuned on a device) */
+  uint32_t reserved[7];         /* zero */
+} SolLightmapFilterVarConfig;
+/* Device pointers (W x H SolRay, SolTexel, SolMoments in; W x H SolRadiance and, or NULL, W x H rows of four floats out; all 16-byte aligned; on
+ * the scene's device), one stream-ordered sequence of launches on the scene's stream, asynchronous. */
+int sol_lightmap_filter_var_dev(SolScene* scene, const SolLightmapFilterVarConfig* config, const void* points_dev, const void* texels_dev,
+                                const void* moments_dev, void* out_dev, void* variance_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_filter_var(SolScene* scene, const SolLightmapFilterVarConfig* config, const SolRay* points, const SolTexel* texels,
+                            const SolMoments* moments, SolRadiance* out, float* variance_out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

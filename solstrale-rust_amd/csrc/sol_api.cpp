@@ -599,8 +599,10 @@ int radiance_launch(SolScene* s, bool gather, const void* rays_dev, const void* 
 // of the path kernel writes one colour per (point, sample) into the partial buffer and is followed by the projection kernel. A launch holds
 // whole chunks of 64 x k points: rows = points x samples <= SolScene::rad_partial_max_rows, at least one group of one chunk (1024 rows). The call is
 // split over points (answers are per point) and over windows of chunks (the projection kernel carries a point's sums from one window to the next
-// in `out`: the same additions in the same order).
-int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
+// in `out`: the same additions in the same order). moments: an irradiance-moments query - the same plan and the same path launches,
+// followed by sol_moments_project_kernel, which writes n SolMoments.
+int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev,
+                         bool moments = false) {
   int rc;
   if ((rc = sol_scene_to_device(s))) return rc;
   const auto [env, lt] = sol_estimator(s, s->S, false);  // what a render would run now
@@ -625,7 +627,7 @@ int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_d
     P.mode = cfg.reserved;
     const char* points_at = (const char*)points_dev + at * sizeof(SolRay);
     const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
-    char* out_at = (char*)out_dev + at * sizeof(SolSh9);
+    char* out_at = (char*)out_dev + at * (moments ? sizeof(SolMoments) : sizeof(SolSh9));
     if ((rc = s->rad_partial.reserve(s->stream, (size_t)P.n_groups * 64 * std::min<size_t>(win_chunks * SOL_CHUNK, cfg.samples)))) return rc;
     for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
       P.n_chunks = (uint32_t)std::min(win_chunks, total_chunks - c0);
@@ -639,7 +641,10 @@ int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_d
       HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
       HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, true, true, may_spill, s->strict_triangles, env, lt, points_at, keys_at, nullptr, s->rad_partial.get(),
                                   s->rad_work.get(), s->rad_spill.get(), grid, s->stream));
-      HIP_TRY(sol_launch_sh_project(P, points_at, keys_at, s->rad_partial.get(), out_at, win_samples, cfg.samples, c0 != 0, s->stream));
+      if (moments)
+        HIP_TRY(sol_launch_moments_project(P, points_at, s->rad_partial.get(), out_at, win_samples, cfg.samples, c0 != 0, s->stream));
+      else
+        HIP_TRY(sol_launch_sh_project(P, points_at, keys_at, s->rad_partial.get(), out_at, win_samples, cfg.samples, c0 != 0, s->stream));
     }
   }
   return SOL_OK;
@@ -672,19 +677,22 @@ int radiance_staged(SolScene* s, bool gather, const SolRay* rays, const SolRayKe
   return SOL_OK;
 }
 
-// The host route of the SH irradiance queries: radiance_staged's buffers, the answers' staging grown to the 112 bytes (seven SolRadiance) of a SolSh9 row.
+// The host route of the SH irradiance queries: radiance_staged's buffers, the answers' staging grown to the 112 bytes (seven SolRadiance) of a SolSh9 row -
+// or, moments, to the 32 bytes (two SolRadiance) of a SolMoments row.
 static_assert(sizeof(SolSh9) == 7 * sizeof(SolRadiance), "a SolSh9 row is seven dwordx4");
-int irradiance_sh_staged(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, SolSh9* out) {
+static_assert(sizeof(SolMoments) == 2 * sizeof(SolRadiance), "a SolMoments row is two dwordx4");
+int irradiance_sh_staged(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, void* out, bool moments = false) {
+  const size_t rows = moments ? 2 : 7;
   int rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
-  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap * 7))) return rc;
+  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap * rows))) return rc;
   for (size_t at = 0; at < n; at += cap) {  // (answers are per point: the split changes nothing)
     const size_t k = std::min(cap, n - at);
     HIP_TRY(hipMemcpyAsync(s->rad_in.get(), points + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
     if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
-    if ((rc = irradiance_sh_launch(s, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get()))) return rc;
-    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolSh9), hipMemcpyDeviceToHost, s->stream));
+    if ((rc = irradiance_sh_launch(s, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get(), moments))) return rc;
+    HIP_TRY(hipMemcpyAsync((char*)out + at * rows * sizeof(SolRadiance), s->rad_out.get(), k * rows * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
   }
   return SOL_OK;
@@ -746,6 +754,27 @@ int sol_irradiance_sh(SolScene* s, const SolRay* points, const SolRayKey* keys, 
   if (config) cfg = radiance_config_of(*config);
   if ((rc = radiance_check(s, "sol_irradiance_sh", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
   return irradiance_sh_staged(s, points, keys, n, cfg, out);
+}
+
+int sol_irradiance_moments_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = radiance_check(s, "sol_irradiance_moments_dev", IRRADIANCE, points_dev, n, config ? &cfg : nullptr, out_dev, out_dev, &go)) || !go ||
+      (rc = query_device_check()))
+    return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return irradiance_sh_launch(s, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev, true);
+}
+
+int sol_irradiance_moments(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolMoments* out) {
+  int rc;
+  bool go;
+  SolRadianceConfig cfg{};
+  if (config) cfg = radiance_config_of(*config);
+  if ((rc = radiance_check(s, "sol_irradiance_moments", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
+  return irradiance_sh_staged(s, points, keys, n, cfg, out, true);
 }
 
 int sol_irradiance_rays(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* rays_out_dev,

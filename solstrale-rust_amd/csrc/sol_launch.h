@@ -130,6 +130,19 @@ hipError_t sol_launch_lightmap_filter_prepare(const void* texels, const void* po
                                               uint32_t stride_words, void* guide, void* plane, void* out, hipStream_t stream);
 hipError_t sol_launch_lightmap_filter_pass(const SolLightmapFilterConfig& c, uint32_t pass, bool staged, bool fold_groups, const void* guide, const void* in,
                                            void* out_plane, void* out_rows, hipStream_t stream);
+// ---- sol_lightmap_filter_var.hip: irradiance moments and the variance-guided lightmap filter. moments_project: one thread per point
+// after an `each` launch of sol_radiance.hip - the launch's win_samples colours and their squares added in chunk order onto 0 (or, accumulate, onto
+// what `out` holds) and written as SolMoments rows with `samples`. The filter: guide: 2 x W x H dwordx4; a side of the ping-pong: W x H dwordx4 of
+// means (x, samples) and as many of variances. prepare: liveness judged, guides packed, side 0 written, and the rows of `out` / `variance_out` (or
+// null) of the texels that are not live. pass i: (in_x, in_v) -> (out_x, out_v), or, the last one, -> the live rows of out_rows / var_rows (or
+// null). staged: steps 1 and 2 read their taps from a tile in LDS (the same words) ----
+hipError_t sol_launch_moments_project(const RadianceParams& P, const void* points, const void* partial, void* out, uint32_t win_samples, uint32_t samples,
+                                      bool accumulate, hipStream_t stream);
+struct SolLightmapFilterVarConfig;
+hipError_t sol_launch_lightmap_filter_var_prepare(const void* texels, const void* points, const void* moments, uint32_t n_texels, void* guide, void* plane_x,
+                                                  void* plane_v, void* out, void* variance_out, hipStream_t stream);
+hipError_t sol_launch_lightmap_filter_var_pass(const SolLightmapFilterVarConfig& c, uint32_t pass, bool staged, const void* guide, const void* in_x,
+                                               const void* in_v, void* out_x, void* out_v, void* out_rows, void* var_rows, hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

@@ -11,6 +11,7 @@
 //   sol_geometry.cpp sol_scene_set_triangles / sol_scene_set_primitives: the triangles, spheres and quads of a live scene moved, records and tree boxes recomputed on the device (sol_geometry.hip)
 //   sol_lightmap.cpp sol_lightmap_points / sol_lightmap_dilate: lightmap UVs rasterised into gather points, chart borders dilated (sol_lightmap.hip)
 //   sol_lightmap_filter.cpp sol_lightmap_filter: chart-aware a-trous filtering of a baked atlas (sol_lightmap_filter.hip)
+//   sol_lightmap_filter_var.cpp sol_lightmap_filter_var: the same under the guidance of the per-texel variance sol_irradiance_moments gathers (sol_lightmap_filter_var.hip)
 //   sol_volume.cpp  sol_volume_points / sol_volume_build / sol_volume_sample: a probe grid laid out, packed and sampled (sol_volume.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
@@ -322,7 +323,9 @@ struct SolScene {
   // Lightmap filtering (sol_lightmap_filter.hip). lf_guide: the packed guide plane, two dwordx4 per texel; lf_planes: the two ping-pong
   // value planes, ceil(channels / 4) dwordx4 per texel each; the host route stages through lm_stage. lf_staged / lf_fold: the pass shape
   // (SOL_LIGHTMAP_FILTER; the product's is staged - steps 1 and 2 from a tile in LDS -, a lane per (texel, channel group): the faster one at
-  // 1024^2 and 4096^2, profiles/lightmap_filter.txt).
+  // 1024^2 and 4096^2, profiles/lightmap_filter.txt). The variance-guided filter (sol_lightmap_filter_var.hip) shares both buffers -
+  // lf_planes then holds two sides of a mean plane and a variance plane, four dwordx4 per texel - and lf_staged; either call writes what it reads of
+  // them first.
   DevBuf<float4> lf_guide, lf_planes;
   bool lf_staged = true, lf_fold = false;
   // Irradiance volumes (sol_volume.hip). vol_stage: what the host routes stage, inputs and outputs. vol_load_all: the sampler's

@@ -273,6 +273,22 @@ class SolLightmapFilterConfig(C.Structure):
                 ("sigma_value", C.c_float), ("value_scale", C.c_float), ("reserved", C.c_uint32 * 5)]
 
 
+class SolMoments(C.Structure):
+    """EXTENSION: the answer of sol_irradiance_moments to one point: the SUMS over `samples` samples of the colour (sol_irradiance's
+    answer, bit for bit) and of its squares per channel; reserved = 0. 32 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("r", C.c_float), ("g", C.c_float), ("b", C.c_float), ("samples", C.c_uint32),
+                ("r2", C.c_float), ("g2", C.c_float), ("b2", C.c_float), ("reserved", C.c_uint32)]
+
+
+class SolLightmapFilterVarConfig(C.Structure):
+    """EXTENSION: the configuration of sol_lightmap_filter_var: size = sizeof, W x H texels, 1..8 passes, the normal factor's exponent
+    as a power of two (0..7), the widths of the distance and plane factors, the width of the value factor in standard deviations of the mean (all
+    >= 1e-6 or +inf), the floor added to the prefiltered variance (finite, > 0), reserved = 0. 64 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("iterations", C.c_uint32), ("normal_power_log2", C.c_uint32),
+                ("sigma_position", C.c_float), ("sigma_plane", C.c_float), ("sigma_value", C.c_float), ("variance_floor", C.c_float),
+                ("reserved", C.c_uint32 * 7)]
+
+
 class SolVolumeGrid(C.Structure):
     """EXTENSION: the probe grid of an irradiance volume (sol_volume_points / _build / _sample): size = sizeof, nx x ny x nz probes, the
     position of probe (0, 0, 0), the spacing per axis, flags (SOL_VOLUME_BACKFACE | SOL_VOLUME_CHEBYSHEV) and the normal bias of a sample. 48 bytes.
@@ -436,6 +452,10 @@ def load_hip():
     _sig(lib, "sol_lightmap_dilate", C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_lightmap_filter_dev", C.c_int, [P, C.POINTER(SolLightmapFilterConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_lightmap_filter", C.c_int, [P, C.POINTER(SolLightmapFilterConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_irradiance_moments_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
+    _sig(lib, "sol_irradiance_moments", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
+    _sig(lib, "sol_lightmap_filter_var_dev", C.c_int, [P, C.POINTER(SolLightmapFilterVarConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_filter_var", C.c_int, [P, C.POINTER(SolLightmapFilterVarConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -481,6 +501,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_irradiance_sh_dev", "sol_irradiance_sh", "sol_visibility_dev", "sol_visibility",
                "sol_lightmap_points_dev", "sol_lightmap_points", "sol_lightmap_dilate_dev", "sol_lightmap_dilate",
                "sol_lightmap_filter_dev", "sol_lightmap_filter",
+               "sol_irradiance_moments_dev", "sol_irradiance_moments", "sol_lightmap_filter_var_dev", "sol_lightmap_filter_var",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

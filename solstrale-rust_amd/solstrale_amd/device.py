@@ -150,6 +150,36 @@ def lightmap_texels_to_numpy(rows):
     return np.ascontiguousarray(rows.cpu().numpy()).view(LIGHTMAP_TEXEL_DTYPE).reshape(-1)
 
 
+# A SolMoments of sol_irradiance_moments: the sums of the sample colours (sol_irradiance's answer), the count, the sums of their squares.
+MOMENTS_DTYPE = np.dtype([("sum", np.float32, (3,)), ("samples", np.uint32), ("sum2", np.float32, (3,)), ("reserved", np.uint32)])
+
+
+def moments_to_numpy(rows):
+    """The [n, 8] float32 device tensor DeviceScene.irradiance_moments returned on the device route (or a host array of that shape), as the
+    structured host array."""
+    rows = rows.cpu().numpy() if hasattr(rows, "data_ptr") else rows
+    return np.ascontiguousarray(rows).view(MOMENTS_DTYPE).reshape(-1)
+
+
+def moments_mean_variance(rows):
+    """The estimators of sol_irradiance_moments from its rows (a MOMENTS_DTYPE array, or what moments_to_numpy takes): (mean [n, 3], variance of
+    the mean [n, 3]) in numpy float32 and exactly the operations of sol_lightmap_filter_var's "Prepare" - N = float32(samples), M = float32(samples
+    - 1), x = sum / N, v = pos((sum2 / N) - (x * x)) / M - so bit for bit what the filter starts from. Rows with samples < 2 give a variance of
+    zero, rows with samples = 0 a mean of zero too."""
+    m = rows if isinstance(rows, np.ndarray) and rows.dtype == MOMENTS_DTYPE else moments_to_numpy(rows)
+    f = np.float32
+    n = m["samples"]
+    with np.errstate(all="ignore"):
+        N = n.astype(f)[:, None]
+        M = (n - np.uint32(1)).astype(f)[:, None]
+        x = m["sum"] / N
+        d = (m["sum2"] / N) - (x * x)
+        v = np.where(d > 0, d, f(0)).astype(f) / M
+    x = np.where((n >= 1)[:, None], x, f(0)).astype(f)
+    v = np.where((n >= 2)[:, None], v, f(0)).astype(f)
+    return x, v
+
+
 # What sol_visibility_oct gathers per texel and what sol_volume_build_depth makes of it (DESIGN.md 25).
 OCT_TEXEL_DTYPE = np.dtype([("w", np.float32), ("w_open", np.float32), ("wt", np.float32), ("wt2", np.float32)])
 DEPTH_TEXEL_DTYPE = np.dtype([("mean", np.float32), ("mean2", np.float32)])
@@ -786,6 +816,72 @@ class DeviceScene:
                                                    C.c_void_p(values.data_ptr()), C.c_void_p(out.data_ptr())))
         self.sync()
         return out
+
+    # ---- irradiance moments and the variance-guided lightmap filter (EXTENSION) ----
+    def irradiance_moments(self, points, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="cosine"):
+        """sol_irradiance_moments: irradiance()'s gather with the sums of the squared sample colours beside it. Per point `sum` (irradiance()'s
+        answer, bit for bit), `samples`, `sum2` - the sums over the samples of colour x colour per channel, in radiance()'s association - and
+        `reserved` = 0. Host arrays go the host route and return a structured array (MOMENTS_DTYPE); device tensors go through
+        sol_irradiance_moments_dev without a host copy and return the raw [n, 8] float32 rows (moments_to_numpy views them as the structured
+        array). moments_mean_variance gives the mean and the variance of the mean. points, keys, key_base, first_draw, the modes and the waits
+        of the two routes are irradiance()'s."""
+        cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
+        rows = self._radiance(self.lib.sol_irradiance_moments, self.lib.sol_irradiance_moments_dev, "points", "position xyz, tmin, normal xyz, tmax", points, keys,
+                              cfg, words=8)
+        if isinstance(rows, np.ndarray):
+            return rows.view(MOMENTS_DTYPE).reshape(-1)
+        return rows
+
+    def lightmap_filter_var(self, moments, points, texels, width, height, sigma_position, sigma_plane=None, iterations=4, normal_power_log2=5, sigma_value=4.0,
+                            variance_floor=1e-12, return_variance=False):
+        """sol_lightmap_filter_var: the variance-guided a-trous filter between irradiance_moments() and lightmap_dilate(). moments: `width * height`
+        rows as irradiance_moments returned them (a MOMENTS_DTYPE array or [n, 8] float32 rows on the host route, the [n, 8] float32 device tensor
+        on the device route); points, texels: what lightmap_points returned. sigma_position, sigma_plane (None: sigma_position), iterations and
+        normal_power_log2 are lightmap_filter()'s. The value factor of a tap is 1 / (1 + D / (sigma_value^2 V))^2 with D the squared difference of
+        the two means and V the centre's variance of the mean, prefiltered over 3 x 3 texels, plus variance_floor: sigma_value counts standard
+        deviations, and the variance the filter carries shrinks from pass to pass. The defaults 4.0 (SVGF's value) and 1e-12 come from a CPU model
+        of a bake and are not tuned on a device. float("inf") switches a sigma's factor off. Texels that are not live (no owner, fewer than two
+        samples, a word that is not finite) come back as the first four words of their moments row. Returns the [width * height, 4] float32 rows
+        of filtered SUMS (r, g, b and the bits of the sample count: what lightmap_filter returns for such a bake and lightmap_dilate takes), and
+        with return_variance=True also the [width * height, 4] float32 rows (v_r, v_g, v_b, 0) of the variance of the filtered mean. Host arrays
+        go the host route, device tensors the device route."""
+        width, height = int(width), int(height)
+        wh = width * height
+        cfg = _abi.SolLightmapFilterVarConfig(size=C.sizeof(_abi.SolLightmapFilterVarConfig), width=width, height=height, iterations=int(iterations),
+                                              normal_power_log2=int(normal_power_log2), sigma_position=float(sigma_position),
+                                              sigma_plane=float(sigma_position if sigma_plane is None else sigma_plane), sigma_value=float(sigma_value),
+                                              variance_floor=float(variance_floor))
+        if isinstance(moments, np.ndarray) or not hasattr(moments, "data_ptr"):  # the host route
+            m = np.ascontiguousarray(moments)
+            m = m.view(np.float32).reshape(-1, 8) if m.dtype == MOMENTS_DTYPE else np.ascontiguousarray(m, dtype=np.float32)
+            p = np.ascontiguousarray(points.cpu().numpy() if hasattr(points, "data_ptr") else points, dtype=np.float32)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            if m.shape != (wh, 8) or p.shape != (wh, 8) or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,):
+                raise ValueError("moments: width * height MOMENTS_DTYPE rows (or [width * height, 8] float32); points: [width * height, 8] float32 rows; "
+                                 "texels: width * height LIGHTMAP_TEXEL_DTYPE rows")
+            out = np.zeros((wh, 4), dtype=np.float32)
+            var = np.zeros((wh, 4), dtype=np.float32) if return_variance else None
+            self._chk(self.lib.sol_lightmap_filter_var(self.h, C.byref(cfg), p.ctypes.data, t.ctypes.data, m.ctypes.data, out.ctypes.data,
+                                                       None if var is None else var.ctypes.data))
+            return (out, var) if return_variance else out
+        import torch
+        if (moments.dtype != torch.float32 or tuple(moments.shape) != (wh, 8) or not moments.is_contiguous() or not moments.is_cuda
+                or moments.device.index != self.device):
+            raise ValueError("moments: the contiguous [width * height, 8] float32 tensor irradiance_moments returned, on the scene's device")
+        if (not hasattr(points, "data_ptr") or points.dtype != torch.float32 or tuple(points.shape) != (wh, 8) or not points.is_contiguous()
+                or points.device != moments.device):
+            raise ValueError("points: the contiguous [width * height, 8] float32 tensor lightmap_points returned, on the device of moments")
+        if (not hasattr(texels, "data_ptr") or texels.dtype != torch.int32 or tuple(texels.shape) != (wh, 4) or not texels.is_contiguous()
+                or texels.device != moments.device):
+            raise ValueError("texels: the contiguous [width * height, 4] int32 tensor lightmap_points returned, on the device of moments")
+        out = torch.empty((wh, 4), dtype=torch.float32, device=moments.device)
+        var = torch.empty((wh, 4), dtype=torch.float32, device=moments.device) if return_variance else None
+        torch.cuda.current_stream(moments.device).synchronize()  # (the moments may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_filter_var_dev(self.h, C.byref(cfg), C.c_void_p(points.data_ptr()), C.c_void_p(texels.data_ptr()),
+                                                       C.c_void_p(moments.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                       C.c_void_p(var.data_ptr()) if var is not None else None))
+        self.sync()
+        return (out, var) if return_variance else out
 
     # ---- irradiance volumes (EXTENSION; DESIGN.md 24) ----
     @staticmethod
