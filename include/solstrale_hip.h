@@ -1186,6 +1186,59 @@ int sol_lightmap_filter_var_dev(SolScene* scene, const SolLightmapFilterVarConfi
 int sol_lightmap_filter_var(SolScene* scene, const SolLightmapFilterVarConfig* config, const SolRay* points, const SolTexel* texels,
                             const SolMoments* moments, SolRadiance* out, float* variance_out);
 
+/* ---- adaptive irradiance gathers (EXTENSION, not in the reference) -----------------------------------------------------------
+ * sol_irradiance_moments spends the same number of paths on every point; this call stops sampling a point once its mean has converged. It runs
+ * rounds of samples over the points still active, judges each active point after every round from its own two moments and compacts what is left.
+ *   Inputs.   SolIrradianceConfig is sol_irradiance_moments's; its `samples` is the MAXIMUM per point (max below). Points, their validity, keys,
+ *             key_base, first_draw, seed, first_sample and the two modes are sol_irradiance's, word for word. out: n SolMoments rows.
+ *   Rounds.   Round k = 0, 1, .. gives every active row the samples [first_sample + k * round, first_sample + (k + 1) * round), clipped to
+ *             first_sample + max. round is a positive multiple of 16 and min_samples a multiple of 16: every round starts on a chunk boundary
+ *             of the row's sample range, so the rounds' chunk sums continue ((0 + chunk0) + chunk1) + .. exactly.
+ *   Invariant. A row that ends with samples = N equals, in all eight words, the row sol_irradiance_moments answers for the same point, key and
+ *             configuration with samples = N. threshold = 0 never converges: the whole answer is then the fixed call's with samples = max, word
+ *             for word. An invalid row answers eight zero words and is never traced.
+ *   Stop rule. fp32, every operation rounded once, no fused multiply-add, `/` correctly rounded, no sqrtf (csrc/sol_gather_adaptive.h is the rule
+ *             as code, tests/irradiance_adaptive_ref.py its restatement in numpy). After a round a valid active row has the count N and the sums
+ *             s[3], q[3] (r, g, b and r2, g2, b2). It stops when one of these holds - the first that does names the reason:
+ *               1. one of the six sums is not finite (more samples cannot repair it);
+ *               2. N == max;
+ *               3. threshold > 0, N >= min_samples, N >= 2, and with Nf = (float)N, M = (float)(N - 1), x[j] = s[j] / Nf,
+ *                  v[j] = pos((q[j] / Nf) - (x[j] * x[j])) / M (sol_lightmap_filter_var's Prepare) every channel j has v[j] <= t * t,
+ *                  t = threshold * (x[j] > floor ? x[j] : floor).
+ *             A stopped row never becomes active again. The compaction is stable and the rule reads the sums only: which rows stop when does not
+ *             depend on scheduling.
+ *   Stats.    (or NULL) size = sizeof(SolGatherAdaptiveStats) on entry. rounds: the rounds launched (a call split over points: the most any part
+ *             ran - what the whole would have run); paths: the sum of the rows' final counts; rows_valid; rows_converged: stopped by 3;
+ *             rows_capped: stopped by 2. Written only when the call succeeds.
+ *   Neutral.  As sol_radiance. The scratch is the irradiance queries' plus compact buffers of the handle's own, grown on demand up to a bound
+ *             (2^22 rows); a larger call is split over points - answers are per point.
+ * BOTH forms block: after every round the host reads one block of counters back to learn how many rows are still active, as
+ * sol_adaptive_round does. The _dev form returns with `moments_out_dev` complete.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for and in this order: sol_irradiance's own refusals of the scene
+ * pointer, the configuration and n, in its order and words; a null adaptive configuration; a wrong size; reserved != 0; round of 0 or not a
+ * multiple of 16; min_samples not a multiple of 16; a threshold that is NaN, negative or infinite; a floor that is NaN, negative or infinite; a
+ * non-null stats of wrong size. Then n == 0 succeeds on any scene and touches nothing; then a scene with a constant medium; then a null point or
+ * output pointer. There is no host mirror. */
+/* 24 bytes: size 0, round 4, min_samples 8, reserved 12, threshold 16, floor 20 */
+typedef struct SolGatherAdaptive { uint32_t size, round, min_samples, reserved; float threshold, floor; } SolGatherAdaptive;
+/* 40 bytes: size 0, rounds 4, paths 8, rows_valid 16, rows_converged 24, rows_capped 32 */
+typedef struct SolGatherAdaptiveStats { uint32_t size, rounds; uint64_t paths, rows_valid, rows_converged, rows_capped; } SolGatherAdaptiveStats;
+/* Device pointers (n SolRay points, n SolRayKey or NULL, n SolMoments out, on the scene's device), on the scene's stream. BLOCKS: one read-back
+ * of the active count per round. */
+int sol_irradiance_adaptive_dev(SolScene* scene, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config,
+                                const SolGatherAdaptive* adaptive, void* moments_out_dev, SolGatherAdaptiveStats* stats);
+/* Host arrays, staged through buffers the handle owns; blocks. */
+int sol_irradiance_adaptive(SolScene* scene, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config,
+                            const SolGatherAdaptive* adaptive, SolMoments* out, SolGatherAdaptiveStats* stats);
+/* Rows of different counts brought to one count, after the filter and before sol_lightmap_dilate, which averages sums: per SolRadiance row whose
+ * count c >= 1 word j = 0, 1, 2 becomes (float)(((double)word_j * (double)target_samples) / (double)c) and the count target_samples
+ * (sol_adaptive_rescale's arithmetic: a row with c == target_samples comes back bit for bit); a row with count 0 is copied. out may be rows.
+ * Nothing is traced and the scene is not read: a scene with a constant medium is served. SOL_EINVAL: a null scene; target_samples == 0; with
+ * n > 0 a null pointer. Device pointers (16-byte aligned), on the scene's stream, asynchronous. */
+int sol_radiance_rescale_dev(SolScene* scene, const void* rows_dev, size_t n, uint32_t target_samples, void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_radiance_rescale(SolScene* scene, const SolRadiance* rows, size_t n, uint32_t target_samples, SolRadiance* out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

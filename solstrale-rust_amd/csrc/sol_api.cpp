@@ -58,6 +58,7 @@ SolDevOverrides sol_dev_overrides() {
   o.pool_swap_min = std::max(0, num("SOL_POOL_SWAP", 0));
   o.pool_count = std::getenv("SOL_POOL_COUNT") != nullptr;
   o.radiance_rows = std::max(0, num("SOL_RADIANCE_ROWS", 0));
+  o.gather_rows = std::max(0, num("SOL_GATHER_ROWS", 0));
   o.probe_radii = num("SOL_PROBE_RADII", -1);
   o.pool_slots = std::max(0, num("SOL_POOL_SLOTS", 0));
   o.wf_slots = std::max(0, num("SOL_WF_SLOTS", 0));
@@ -600,9 +601,11 @@ int radiance_launch(SolScene* s, bool gather, const void* rays_dev, const void* 
 // whole chunks of 64 x k points: rows = points x samples <= SolScene::rad_partial_max_rows, at least one group of one chunk (1024 rows). The call is
 // split over points (answers are per point) and over windows of chunks (the projection kernel carries a point's sums from one window to the next
 // in `out`: the same additions in the same order). moments: an irradiance-moments query - the same plan and the same path launches,
-// followed by sol_moments_project_kernel, which writes n SolMoments.
+// followed by sol_moments_project_kernel, which writes n SolMoments. carry, total_samples (moments only): a later round of an adaptive gather
+//  - `out` holds the rows' sums of the earlier rounds, so that the projection accumulates from the first window on, and the rows'
+// count is their new total rather than this call's samples.
 int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev,
-                         bool moments = false) {
+                         bool moments = false, bool carry = false, uint32_t total_samples = 0) {
   int rc;
   if ((rc = sol_scene_to_device(s))) return rc;
   const auto [env, lt] = sol_estimator(s, s->S, false);  // what a render would run now
@@ -642,7 +645,7 @@ int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_d
       HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, true, true, may_spill, s->strict_triangles, env, lt, points_at, keys_at, nullptr, s->rad_partial.get(),
                                   s->rad_work.get(), s->rad_spill.get(), grid, s->stream));
       if (moments)
-        HIP_TRY(sol_launch_moments_project(P, points_at, s->rad_partial.get(), out_at, win_samples, cfg.samples, c0 != 0, s->stream));
+        HIP_TRY(sol_launch_moments_project(P, points_at, s->rad_partial.get(), out_at, win_samples, carry ? total_samples : cfg.samples, carry || c0 != 0, s->stream));
       else
         HIP_TRY(sol_launch_sh_project(P, points_at, keys_at, s->rad_partial.get(), out_at, win_samples, cfg.samples, c0 != 0, s->stream));
     }
@@ -658,6 +661,10 @@ int sol_gather_config_check(const char* fn, size_t n, const SolIrradianceConfig*
   return radiance_config_check(fn, IRRADIANCE, n, config ? cfg : nullptr);
 }
 int sol_query_medium_check(const SolScene* s, const char* fn) { return query_medium_check(s, fn); }
+int sol_irradiance_moments_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev,
+                                  bool carry, uint32_t total_samples) {
+  return irradiance_sh_launch(s, points_dev, keys_dev, n, cfg, key_base, out_dev, true, carry, total_samples);
+}
 
 namespace {
 // The host route of both: arrays staged through buffers the handle owns, RADIANCE_STAGE_RAYS rows at a time; blocks.

@@ -922,6 +922,7 @@ static int set_scene_constants(const CreateCtx& c, const World& w, SolScene* s, 
   s->pool_swap_min = (uint32_t)ovr.pool_swap_min;
   s->pool_count = ovr.pool_count;
   if (ovr.radiance_rows > 0) s->rad_partial_max_rows = (size_t)ovr.radiance_rows;
+  if (ovr.gather_rows > 0) s->ga_max_rows = (size_t)ovr.gather_rows;
   if (ovr.lightmap_claim == 1) s->lm_small_max = 0xFFFFFFFFu;                                 // a lane per triangle
   if (ovr.lightmap_claim == 2) { s->lm_small_max = 0u; s->lm_tiles_max = 0xFFFFFFFFu; }        // a wave per triangle
   s->vol_load_all = ovr.volume_load_all;

@@ -143,6 +143,18 @@ hipError_t sol_launch_lightmap_filter_var_prepare(const void* texels, const void
                                                   void* plane_v, void* out, void* variance_out, hipStream_t stream);
 hipError_t sol_launch_lightmap_filter_var_pass(const SolLightmapFilterVarConfig& c, uint32_t pass, bool staged, const void* guide, const void* in_x,
                                                const void* in_v, void* out_x, void* out_v, void* out_rows, void* var_rows, hipStream_t stream);
+// ---- sol_gather_adaptive.hip: adaptive irradiance gathers. judge: the stop rule on the n_active SolMoments `rows` of a round - one
+// 64-bit ballot per wave of 64 rows (two words each) and one count per workgroup of 256 of the rows that go on, ctr[1..3] += rows without samples,
+// converged, capped -, then the scan of the counts: wg_offsets, and ctr[0] = the rows that go on. scatter: those rows, in order, to index_out and -
+// their point and key by their index in the call, their sums from `totals` by that index - to the compact buffers of n_next rows. writeback:
+// compact row j -> out[index[j]]. rescale: n SolRadiance rows brought to `target` samples; out may be rows ----
+hipError_t sol_launch_gather_judge(const void* rows, uint32_t n_active, uint32_t max_samples, uint32_t min_samples, float threshold, float floor, uint32_t* ballots,
+                                   uint32_t* wg_counts, uint32_t* wg_offsets, uint32_t* ctr, hipStream_t stream);
+hipError_t sol_launch_gather_scatter(uint32_t n_active, const uint32_t* index_in, const uint32_t* ballots, const uint32_t* wg_offsets, const void* points,
+                                     const void* keys, uint32_t key_base, uint32_t first_draw, const void* totals, uint32_t n_next, uint32_t* index_out,
+                                     void* points_out, void* keys_out, void* totals_out, hipStream_t stream);
+hipError_t sol_launch_gather_writeback(uint32_t n_active, const uint32_t* index, const void* rows, void* out, hipStream_t stream);
+hipError_t sol_launch_radiance_rescale(const void* rows, size_t n, uint32_t target, void* out, hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

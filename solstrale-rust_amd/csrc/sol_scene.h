@@ -12,6 +12,7 @@
 //   sol_lightmap.cpp sol_lightmap_points / sol_lightmap_dilate: lightmap UVs rasterised into gather points, chart borders dilated (sol_lightmap.hip)
 //   sol_lightmap_filter.cpp sol_lightmap_filter: chart-aware a-trous filtering of a baked atlas (sol_lightmap_filter.hip)
 //   sol_lightmap_filter_var.cpp sol_lightmap_filter_var: the same under the guidance of the per-texel variance sol_irradiance_moments gathers (sol_lightmap_filter_var.hip)
+//   sol_gather_adaptive.cpp sol_irradiance_adaptive / sol_radiance_rescale: rounds of an irradiance-moments gather over the points still active (sol_gather_adaptive.hip)
 //   sol_volume.cpp  sol_volume_points / sol_volume_build / sol_volume_sample: a probe grid laid out, packed and sampled (sol_volume.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
 //   sol_comm.cpp    RCCL communicator and the gather to rank 0
@@ -129,6 +130,7 @@ struct SolDevOverrides {
   int fine_tail = -2;            // SOL_FINE_TAIL (-2: not set)
   int probe_radii = -1;          // SOL_PROBE_RADII (AUTO device build: 1 = emit and probe both clustering radii, 0 = never, -1 = by the collapse costs)
   int radiance_rows = 0;         // SOL_RADIANCE_ROWS: bound of the radiance queries' partial buffer in rows (0: the default, 2^24) - tests drive the splits with a small one
+  int gather_rows = 0;           // SOL_GATHER_ROWS: bound of the adaptive gathers' compact buffers in rows (0: the default, 2^22) - a test forces the split over points with a small one
   int pool_swap_min = 0;         // SOL_POOL_SWAP (pool kernel: RenderParams::swap_min; 0: the default)
   bool pool_count = false;       // SOL_POOL_COUNT (pool kernel: counted renders run its instrumented build - phase statistics)
   int pool_slots = 0, wf_slots = 0, wf_min_items = -1;  // SOL_POOL_SLOTS / SOL_WF_SLOTS / SOL_WF_MIN_ITEMS (v2 / v3)
@@ -336,6 +338,14 @@ struct SolScene {
   // (sample, point) pairs under the same bound counted in words, rad_out res x res rows per staged point; build and sample stage through vol_stage.
   // depth_project_plain: the projection kernel's measured alternative (SOL_DEPTH_PROJECT=plain).
   bool depth_project_plain = false;
+  // Adaptive irradiance gathers (sol_gather_adaptive.hip). The rounds run through the irradiance queries' buffers above; these are
+  // the compaction's own, grown on demand to min(n, ga_max_rows) rows - beyond that bound (SOL_GATHER_ROWS) a call is split over points. ga_points,
+  // ga_keys, ga_totals: the compact rows a later round runs over; ga_index: two active lists (this round's, the next one's); ga_scan: per wave of
+  // 64 rows two ballot words, then per workgroup of 256 a count and an offset; ga_ctr / ga_ctr_host: rows that go on, rows without samples,
+  // converged, capped - what the host reads back once per round.
+  DevBuf<SolRay> ga_points; DevBuf<SolRayKey> ga_keys; DevBuf<SolMoments> ga_totals;
+  DevBuf<uint32_t> ga_index, ga_scan, ga_ctr; PinnedPtr<uint32_t> ga_ctr_host;
+  size_t ga_max_rows = (size_t)1 << 22;
   SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
@@ -366,6 +376,11 @@ int sol_set_partition(SolScene* s, int rank, int world);
 // constant medium. sol_volume_grid_check (sol_volume.cpp): what every volume call refuses about the scene pointer and the grid, in the header's order.
 int sol_gather_config_check(const char* fn, size_t n, const SolIrradianceConfig* config, SolRadianceConfig* cfg);
 int sol_query_medium_check(const SolScene* s, const char* fn);
+// What sol_gather_adaptive.cpp shares with sol_irradiance_moments (sol_api.cpp): its launches over n <= 2^31 points (and keys, or null) in device
+// memory, n SolMoments out, on the scene's stream. carry: the projection adds onto what `out` holds from the first window on - the rows' sums of
+// earlier rounds -, and writes total_samples as the rows' count instead of cfg.samples.
+int sol_irradiance_moments_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev,
+                                  bool carry, uint32_t total_samples);
 int sol_volume_grid_check(bool have_scene, const char* fn, const SolVolumeGrid* g);
 
 // One launch of sol_render_impl (sol_launch.cpp): what differs between its callers, and nothing else - the handle supplies what is not per launch

@@ -289,6 +289,21 @@ class SolLightmapFilterVarConfig(C.Structure):
                 ("reserved", C.c_uint32 * 7)]
 
 
+class SolGatherAdaptive(C.Structure):
+    """EXTENSION: the rounds and the stop rule of sol_irradiance_adaptive: size = sizeof, samples per round (a positive multiple of
+    16), the count below which no row is judged converged (a multiple of 16), reserved = 0, the relative standard error of the mean that counts as
+    converged (0 = never) and the floor under the mean it is relative to. 24 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("round", C.c_uint32), ("min_samples", C.c_uint32), ("reserved", C.c_uint32), ("threshold", C.c_float),
+                ("floor", C.c_float)]
+
+
+class SolGatherAdaptiveStats(C.Structure):
+    """EXTENSION: what sol_irradiance_adaptive reports: size = sizeof on entry; the rounds launched, the sum of the rows' final
+    counts, the valid rows, the rows the rule judged converged and the rows that reached the maximum. 40 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("rounds", C.c_uint32), ("paths", C.c_uint64), ("rows_valid", C.c_uint64), ("rows_converged", C.c_uint64),
+                ("rows_capped", C.c_uint64)]
+
+
 class SolVolumeGrid(C.Structure):
     """EXTENSION: the probe grid of an irradiance volume (sol_volume_points / _build / _sample): size = sizeof, nx x ny x nz probes, the
     position of probe (0, 0, 0), the spacing per axis, flags (SOL_VOLUME_BACKFACE | SOL_VOLUME_CHEBYSHEV) and the normal bias of a sample. 48 bytes.
@@ -456,6 +471,12 @@ def load_hip():
     _sig(lib, "sol_irradiance_moments", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.c_void_p])
     _sig(lib, "sol_lightmap_filter_var_dev", C.c_int, [P, C.POINTER(SolLightmapFilterVarConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_lightmap_filter_var", C.c_int, [P, C.POINTER(SolLightmapFilterVarConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_irradiance_adaptive_dev", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.POINTER(SolGatherAdaptive),
+                                                       C.c_void_p, C.POINTER(SolGatherAdaptiveStats)])
+    _sig(lib, "sol_irradiance_adaptive", C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(SolIrradianceConfig), C.POINTER(SolGatherAdaptive),
+                                                   C.c_void_p, C.POINTER(SolGatherAdaptiveStats)])
+    _sig(lib, "sol_radiance_rescale_dev", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p])
+    _sig(lib, "sol_radiance_rescale", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -502,6 +523,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_lightmap_points_dev", "sol_lightmap_points", "sol_lightmap_dilate_dev", "sol_lightmap_dilate",
                "sol_lightmap_filter_dev", "sol_lightmap_filter",
                "sol_irradiance_moments_dev", "sol_irradiance_moments", "sol_lightmap_filter_var_dev", "sol_lightmap_filter_var",
+               "sol_irradiance_adaptive_dev", "sol_irradiance_adaptive", "sol_radiance_rescale_dev", "sol_radiance_rescale",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

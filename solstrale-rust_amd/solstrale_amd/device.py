@@ -883,6 +883,63 @@ class DeviceScene:
         self.sync()
         return (out, var) if return_variance else out
 
+    # ---- adaptive irradiance gathers (EXTENSION) ----
+    def irradiance_adaptive(self, points, max_samples, round=16, min_samples=32, threshold=0.05, floor=0.0, first_sample=0, seed=0, keys=None, key_base=0,
+                            first_draw=0, mode="cosine", return_stats=False):
+        """sol_irradiance_adaptive: irradiance_moments() in rounds of `round` samples (a positive multiple of 16) over the points still active. After
+        every round a point stops when it holds max_samples, when one of its sums is not finite, or - from min_samples (a multiple of 16) on - when
+        in every channel the variance of its mean (moments_mean_variance) is at most (threshold * max(mean, floor))^2: `threshold` is a relative
+        standard error, `floor` keeps it from being relative to nothing in the dark, threshold = 0 never converges. A row that ends with N samples
+        is, in all eight words, irradiance_moments(samples=N)'s row for the same point and key: the counts differ from row to row, nothing else does
+        - lightmap_filter_var reads each row's own count, and radiance_rescale brings its output to one count for lightmap_dilate. Returns what
+        irradiance_moments returns on either route (a MOMENTS_DTYPE array for host arrays, the raw [n, 8] float32 device tensor for device
+        tensors); with return_stats=True also a dict of rounds, paths (the sum of the final counts), rows_valid, rows_converged and rows_capped.
+        Both routes block: the library reads the active count back after every round. The defaults (round 16, min_samples 32, threshold 0.05,
+        floor 0) are not tuned on a device. points, keys, key_base, first_draw and the modes are irradiance()'s."""
+        cfg = self._irradiance_config(max_samples, first_sample, seed, key_base, first_draw, mode)
+        ad = _abi.SolGatherAdaptive(size=C.sizeof(_abi.SolGatherAdaptive), round=int(round), min_samples=int(min_samples), threshold=float(threshold),
+                                    floor=float(floor))
+        stats = _abi.SolGatherAdaptiveStats(size=C.sizeof(_abi.SolGatherAdaptiveStats))
+
+        def host_fn(h, p, k, n, c, out):
+            return self.lib.sol_irradiance_adaptive(h, p, k, n, c, C.byref(ad), out, C.byref(stats))
+
+        def dev_fn(h, p, k, n, c, out):
+            return self.lib.sol_irradiance_adaptive_dev(h, p, k, n, c, C.byref(ad), out, C.byref(stats))
+
+        rows = self._radiance(host_fn, dev_fn, "points", "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=8)
+        if isinstance(rows, np.ndarray):
+            rows = rows.view(MOMENTS_DTYPE).reshape(-1)
+        if not return_stats:
+            return rows
+        return rows, {"rounds": int(stats.rounds), "paths": int(stats.paths), "rows_valid": int(stats.rows_valid), "rows_converged": int(stats.rows_converged),
+                      "rows_capped": int(stats.rows_capped)}
+
+    def radiance_rescale(self, rows, target_samples, in_place=False):
+        """sol_radiance_rescale: [n, 4] float32 rows of sums (r, g, b and the bits of the sample count: what irradiance(), lightmap_filter() and
+        lightmap_filter_var() return) brought to one count - a row with count c >= 1 becomes float32(float64(word) * target_samples / c) per
+        channel with the count target_samples, a row with count 0 is copied. After an adaptive gather the filter's rows carry different counts, and
+        lightmap_dilate averages sums: this goes between them. Host arrays go the host route and return an array, device tensors the device route
+        and return a new tensor - or, in_place=True, `rows` itself, overwritten (a contiguous float32 array or tensor)."""
+        target = int(target_samples)
+        if isinstance(rows, np.ndarray) or not hasattr(rows, "data_ptr"):
+            a = np.ascontiguousarray(rows, dtype=np.float32)
+            if a.ndim != 2 or a.shape[1] != 4:
+                raise ValueError("rows: an [n, 4] float32 array of (r, g, b sums, the bits of the sample count)")
+            if in_place and a is not rows:
+                raise ValueError("rows: in_place needs the contiguous float32 array itself")
+            out = a if in_place else np.zeros_like(a)
+            self._chk(self.lib.sol_radiance_rescale(self.h, a.ctypes.data, a.shape[0], target, out.ctypes.data))
+            return out
+        import torch
+        if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 4 or not rows.is_contiguous() or not rows.is_cuda or rows.device.index != self.device:
+            raise ValueError("rows: a contiguous [n, 4] float32 tensor on the scene's device")
+        out = rows if in_place else torch.empty_like(rows)
+        torch.cuda.current_stream(rows.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_radiance_rescale_dev(self.h, C.c_void_p(rows.data_ptr()), int(rows.shape[0]), target, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
     # ---- irradiance volumes (EXTENSION; DESIGN.md 24) ----
     @staticmethod
     def _volume_rows(grid):
