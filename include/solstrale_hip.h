@@ -1239,6 +1239,78 @@ int sol_radiance_rescale_dev(SolScene* scene, const void* rows_dev, size_t n, ui
 /* Host arrays, staged through a buffer the handle owns; blocks. */
 int sol_radiance_rescale(SolScene* scene, const SolRadiance* rows, size_t n, uint32_t target_samples, SolRadiance* out);
 
+/* ---- lightmap lookups: a baked atlas sampled at surface points and hits (EXTENSION, not in the reference) --------------------
+ * The consumer of a bake, as sol_volume_sample is the volume's: sol_camera_rays -> sol_query (CLOSEST) -> sol_lightmap_coords ->
+ * sol_lightmap_sample is a chain of calls on device memory that shows a bake from the scene's camera, lights a hit point from it, or reads it at
+ * points that are not texel centres - without the caller restating the atlas convention. Nothing is traced and the scene is never read: a scene
+ * with a constant medium is served. All arithmetic is fp32, every operation rounded once, no fused multiply-add, `/` correctly rounded, every
+ * clamp a comparison, finite(x) = the exponent field is not all ones; csrc/sol_lightmap_sample.h is the rule as code and
+ * tests/lightmap_sample_ref.py its restatement in numpy.
+ *   Surface row. A SolTexel (triangle, b1, b2, flags): `triangle` is the row of the uvs / vertices arrays sol_lightmap_points was given, b1 and b2
+ *             weigh the triangle's second and third corner, flags != 0 marks a usable row. The SolTexel rows sol_lightmap_points writes are
+ *             surface rows already.
+ *   Coords.   sol_lightmap_coords turns n SolRayHit rows into surface rows through the caller's table triangle_of_dfs[n_dfs]. A triangle hit's
+ *             (u, v) weigh the two edges of the triangle's fp32 RECORD, which starts at the vertex opposite the longest edge
+ *             (sol_triangle_rotation above), so an entry carries the rotation k of its triangle in the two top bits:
+ *             entry = triangle | k << 30 (triangle < 2^30); SOL_TEXEL_NONE, or any entry with k = 3: a primitive without lightmap. The row is
+ *             (entry & 0x3FFFFFFF, b1, b2, 1) with (b1, b2) = (u, v) for k = 0, ((1 - u) - v, u) for k = 1, (v, (1 - u) - v) for k = 2, when
+ *             status == SOL_RAY_HIT, kind == SOL_REF_TRIANGLE, dfs_index < n_dfs and the entry names a triangle; else (SOL_TEXEL_NONE, 0, 0, 0).
+ *             The parts of a pre-split triangle are copies of one record and answer the original's values. After sol_scene_set_triangles a moved
+ *             triangle's rotation is that of its new vertices: the table is made again.
+ *   Invalid.  sol_lightmap_sample answers channels + 1 zero words for a row with flags == 0; triangle == SOL_TEXEL_NONE or >= n_triangles; b1 or
+ *             b2 not finite; one of the triangle's six UV words not finite; with the chart guard, one of its nine vertex words not finite. Nothing
+ *             of the row is used as an address before this is decided.
+ *   Atlas coordinates. b0 = (1 - b1) - b2; u = ((u0 * b0) + (u1 * b1)) + (u2 * b2), v likewise (sol_lightmap_points' interpolation);
+ *             x = (u * (float)W) - 0.5f, y = (v * (float)H) - 0.5f. Unless x >= -1 && x < (float)W && y >= -1 && y < (float)H no tap is live -
+ *             decided before any conversion to an integer.
+ *   Taps.     i0 = floorf(x), fx = x - (float)i0, likewise in y. The taps (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1), in this order,
+ *             weigh (1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy - one product each of the rounded factors. A tap outside the atlas
+ *             is not live: no wrap, no clamp.
+ *   Live.     A tap is live when it is covered - pass_of[tap] != 255 where pass_of (sol_lightmap_dilate's plane) is given, else
+ *             texels[tap].triangle != SOL_TEXEL_NONE -, its `channels` value words are finite, and the chart guard does not refuse it.
+ *   Chart guard. On when vertices and points are given and chart_radius is finite. P = ((v0 * b0) + (v1 * b1)) + (v2 * b2) per component. A tap with
+ *             texels[tap].flags != 0 whose three position words in points[tap] are finite is live only when, E = P_tap - P,
+ *             ((E.x * E.x) + (E.y * E.y)) + (E.z * E.z) <= r * r, r * r one product. A tap that only the dilation filled has no point row and
+ *             stays live untested (so does an owned tap whose position is not finite): the guard protects against an owned texel of a
+ *             neighbouring chart, not against a gutter narrower than the dilation.
+ *   Answer.   Per channel sum = ((0 + (w_a * x_a)) + (w_b * x_b)) .. over the live taps in tap order, wsum = ((0 + w_a) + w_b) .. likewise. When
+ *             wsum > 0: sum / wsum per channel, then the number of live taps as a uint32_t; else channels + 1 zero words. For channels = 3 the row
+ *             is a SolRadiance whose `samples` is 0 to 4, as sol_volume_sample reports its probes.
+ *   Nearest.  With SOL_LIGHTMAP_SAMPLE_NEAREST: xn = u * (float)W, yn = v * (float)H; unless xn >= 0 && xn < (float)W && yn >= 0 &&
+ *             yn < (float)H there is no tap; else the one tap (floorf(xn), floorf(yn)) under the same liveness rules. Its value words are copied,
+ *             not multiplied; the count is 1 or 0.
+ * Neutral as the queries are: no accumulator, plane, counter or statistic is touched; calls are ordered by the handle's stream.
+ * SOL_EINVAL (sol_last_error names the reason), before the device is looked for and in this order. sol_lightmap_sample: a null scene or
+ * configuration; a wrong size; reserved != 0; unknown flags; width or height of 0 or above 16384; channels outside 1..32; a stride that is no
+ * multiple of 4 or below 4 x channels; a chart_radius that is NaN or not > 0; exactly one of vertices / points given; a finite chart_radius with
+ * neither; n_triangles > 2^31 - 2; n > 2^31; a null UV (with n_triangles > 0), texel, value, coordinate or output pointer; out == values or
+ * out == coords. sol_lightmap_coords: a null scene; n > 2^31; n_dfs > 2^31; with n_dfs > 0 a null table; a null hit or output pointer;
+ * out == hits. Then n == 0 succeeds and writes nothing. SOL_EDEVICE without a GPU comes after all of these. There is no host mirror
+ * (DESIGN.md 15). */
+#define SOL_LIGHTMAP_SAMPLE_NEAREST 1u
+#define SOL_LIGHTMAP_TABLE_ROTATION_SHIFT 30u
+#define SOL_LIGHTMAP_TABLE_TRIANGLE_MASK 0x3FFFFFFFu
+/* 32 bytes: size 0, width 4, height 8, channels 12, stride_bytes 16, flags 20, chart_radius 24, reserved 28 */
+typedef struct SolLightmapSampleConfig {
+  uint32_t size, width, height, channels, stride_bytes, flags; /* size = sizeof(SolLightmapSampleConfig); flags: SOL_LIGHTMAP_SAMPLE_NEAREST */
+  float chart_radius;                                          /* a world length, > 0; +inf: no chart guard */
+  uint32_t reserved;                                           /* zero */
+} SolLightmapSampleConfig;
+/* Device pointers (n SolRayHit in, n_dfs uint32_t, n SolTexel out, 16-byte aligned; on the scene's device), on the scene's stream, asynchronous. */
+int sol_lightmap_coords_dev(SolScene* scene, const void* hits_dev, size_t n, const void* triangle_of_dfs_dev, size_t n_dfs, void* coords_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_coords(SolScene* scene, const SolRayHit* hits, size_t n, const uint32_t* triangle_of_dfs, size_t n_dfs, SolTexel* coords_out);
+/* Device pointers (n_triangles x 6 floats; W x H SolTexel; W x H bytes or NULL; W x H rows of stride_bytes; n_triangles x 9 floats and W x H
+ * SolRay, or both NULL; n SolTexel surface rows in, n rows of channels + 1 words out; texels, points and coords 16-byte aligned, the rest 4-byte
+ * aligned), on the scene's stream, asynchronous. */
+int sol_lightmap_sample_dev(SolScene* scene, const SolLightmapSampleConfig* config, const void* uvs_dev, size_t n_triangles, const void* texels_dev,
+                            const void* pass_of_dev, const void* values_dev, const void* vertices_dev, const void* points_dev, const void* coords_dev,
+                            size_t n, void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_sample(SolScene* scene, const SolLightmapSampleConfig* config, const float* uvs, size_t n_triangles, const SolTexel* texels,
+                        const uint8_t* pass_of, const void* values, const float* vertices, const SolRay* points, const SolTexel* coords, size_t n,
+                        void* out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

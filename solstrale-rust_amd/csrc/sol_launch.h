@@ -155,6 +155,14 @@ hipError_t sol_launch_gather_scatter(uint32_t n_active, const uint32_t* index_in
                                      void* points_out, void* keys_out, void* totals_out, hipStream_t stream);
 hipError_t sol_launch_gather_writeback(uint32_t n_active, const uint32_t* index, const void* rows, void* out, hipStream_t stream);
 hipError_t sol_launch_radiance_rescale(const void* rows, size_t n, uint32_t target, void* out, hipStream_t stream);
+// ---- sol_lightmap_sample.hip: lightmap lookups. coords: n SolRayHit in, n SolTexel surface rows out, table: n_dfs words. sample: n
+// surface rows in, n rows of channels + 1 words out; pass_of, and vertices with points, or null; the chart guard is on when vertices and points are
+// given and c.chart_radius is finite ----
+hipError_t sol_launch_lightmap_coords(const void* hits, uint32_t n, const void* table, uint32_t n_dfs, void* out, hipStream_t stream);
+struct SolLightmapSampleConfig;
+hipError_t sol_launch_lightmap_sample(const SolLightmapSampleConfig& c, uint32_t n_triangles, const void* uvs, const void* texels, const void* pass_of,
+                                      const void* values, const void* vertices, const void* points, const void* coords, uint32_t n, void* out,
+                                      hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

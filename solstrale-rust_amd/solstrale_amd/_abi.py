@@ -264,6 +264,16 @@ class SolTexel(C.Structure):
 SOL_LIGHTMAP_CONSERVATIVE, SOL_LIGHTMAP_MAX_SIZE, SOL_TEXEL_NONE = 1, 16384, 0xFFFFFFFF
 
 
+class SolLightmapSampleConfig(C.Structure):
+    """EXTENSION: the configuration of sol_lightmap_sample: size = sizeof, W x H texels, the rows' channels and stride, flags
+    (SOL_LIGHTMAP_SAMPLE_NEAREST), the radius of the chart guard (> 0; +inf: off), reserved = 0. 32 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("stride_bytes", C.c_uint32),
+                ("flags", C.c_uint32), ("chart_radius", C.c_float), ("reserved", C.c_uint32)]
+
+
+SOL_LIGHTMAP_SAMPLE_NEAREST, SOL_LIGHTMAP_TABLE_ROTATION_SHIFT, SOL_LIGHTMAP_TABLE_TRIANGLE_MASK = 1, 30, 0x3FFFFFFF
+
+
 class SolLightmapFilterConfig(C.Structure):
     """EXTENSION: the configuration of sol_lightmap_filter: size = sizeof, W x H texels, 1..8 passes, the normal factor's exponent as a
     power of two (0..7), the rows' channels and stride, the widths of the distance, plane and value factors (>= 1e-6 or +inf), the scale a value is
@@ -477,6 +487,12 @@ def load_hip():
                                                    C.c_void_p, C.POINTER(SolGatherAdaptiveStats)])
     _sig(lib, "sol_radiance_rescale_dev", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p])
     _sig(lib, "sol_radiance_rescale", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p])
+    _sig(lib, "sol_lightmap_coords_dev", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_lightmap_coords", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_lightmap_sample_dev", C.c_int, [P, C.POINTER(SolLightmapSampleConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_lightmap_sample", C.c_int, [P, C.POINTER(SolLightmapSampleConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -524,6 +540,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_lightmap_filter_dev", "sol_lightmap_filter",
                "sol_irradiance_moments_dev", "sol_irradiance_moments", "sol_lightmap_filter_var_dev", "sol_lightmap_filter_var",
                "sol_irradiance_adaptive_dev", "sol_irradiance_adaptive", "sol_radiance_rescale_dev", "sol_radiance_rescale",
+               "sol_lightmap_coords_dev", "sol_lightmap_coords", "sol_lightmap_sample_dev", "sol_lightmap_sample",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

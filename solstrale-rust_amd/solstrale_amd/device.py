@@ -145,6 +145,53 @@ def sh9_irradiance(L, normals):
 LIGHTMAP_TEXEL_DTYPE = np.dtype([("triangle", np.uint32), ("b1", np.float32), ("b2", np.float32), ("flags", np.uint32)])
 
 
+def lightmap_triangle_table(description, first, count):
+    """The table sol_lightmap_coords takes: per dfs_index the lightmap triangle of the primitive, or SOL_TEXEL_NONE. Triangle first + k of the
+    description (a Scene, or its SolSceneDesc - the one the handle was created from) is lightmap triangle k, row k of the uvs / vertices arrays;
+    an entry also carries, in its two top bits, the rotation of the triangle's fp32 record (sol_triangle_rotation of include/solstrale_hip.h:
+    the record starts opposite the longest edge), which is what a hit's (u, v) are measured in. uint32 [max dfs_index + 1]."""
+    desc = getattr(description, "desc", description)
+    first, count = int(first), int(count)
+    if first < 0 or count < 0 or first + count > int(desc.n_triangles) or count > _abi.SOL_LIGHTMAP_TABLE_TRIANGLE_MASK:
+        raise ValueError(f"triangles {first} .. {first + count} of a description with {int(desc.n_triangles)}")
+    if count == 0:
+        return np.zeros(0, dtype=np.uint32)
+    rec = np.ctypeslib.as_array(C.cast(desc.triangles, C.POINTER(C.c_uint8)), shape=(int(desc.n_triangles), C.sizeof(_abi.SolTriangle)))[first:first + count]
+
+    def field(name, dtype, n):
+        at = getattr(_abi.SolTriangle, name).offset
+        return np.ascontiguousarray(rec[:, at:at + n * np.dtype(dtype).itemsize]).view(dtype).reshape(count, n)
+    a, b, dfs = field("v0v1", np.float64, 3), field("v0v2", np.float64, 3), field("dfs_index", np.uint32, 1)[:, 0]
+    c = b - a
+    l01, l02, l12 = ((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2] for e in (a, b, c))
+    k = np.where(l02 > l12, 1, 0)
+    k = np.where(l01 > np.maximum(l12, l02), 2, k)
+    table = np.full(int(dfs.max()) + 1, _abi.SOL_TEXEL_NONE, dtype=np.uint32)
+    table[dfs] = np.arange(count, dtype=np.uint32) | (k.astype(np.uint32) << np.uint32(_abi.SOL_LIGHTMAP_TABLE_ROTATION_SHIFT))
+    return table
+
+
+def lightmap_mesh(description, first, count):
+    """(vertices [count, 3, 3], uvs [count, 3, 2]) float32 of triangles first .. first + count of the description, in the description's order (the
+    flattener's, not the builder's) and the triangles' own vertex order: the arrays lightmap_points and lightmap_sample take when the lightmap UVs
+    are the description's texture coordinates - row k is the triangle lightmap_triangle_table(description, first, count) calls k."""
+    desc = getattr(description, "desc", description)
+    first, count = int(first), int(count)
+    if first < 0 or count < 0 or first + count > int(desc.n_triangles):
+        raise ValueError(f"triangles {first} .. {first + count} of a description with {int(desc.n_triangles)}")
+    if count == 0:
+        return np.zeros((0, 3, 3), dtype=np.float32), np.zeros((0, 3, 2), dtype=np.float32)
+    rec = np.ctypeslib.as_array(C.cast(desc.triangles, C.POINTER(C.c_uint8)), shape=(int(desc.n_triangles), C.sizeof(_abi.SolTriangle)))[first:first + count]
+
+    def field(name, dtype, n):
+        at = getattr(_abi.SolTriangle, name).offset
+        return np.ascontiguousarray(rec[:, at:at + n * np.dtype(dtype).itemsize]).view(dtype).reshape(count, n)
+    v0, a, b = field("v0", np.float64, 3), field("v0v1", np.float64, 3), field("v0v2", np.float64, 3)
+    V = np.stack([v0, v0 + a, v0 + b], axis=1).astype(np.float32)
+    T = np.stack([field("uv0", np.float32, 2), field("uv1", np.float32, 2), field("uv2", np.float32, 2)], axis=1)
+    return np.ascontiguousarray(V), np.ascontiguousarray(T)
+
+
 def lightmap_texels_to_numpy(rows):
     """The [n, 4] int32 device tensor DeviceScene.lightmap_points returned on the device route, as the structured host array."""
     return np.ascontiguousarray(rows.cpu().numpy()).view(LIGHTMAP_TEXEL_DTYPE).reshape(-1)
@@ -939,6 +986,95 @@ class DeviceScene:
         self._chk(self.lib.sol_radiance_rescale_dev(self.h, C.c_void_p(rows.data_ptr()), int(rows.shape[0]), target, C.c_void_p(out.data_ptr())))
         self.sync()
         return out
+
+    # ---- lightmap lookups (EXTENSION) ----
+    def lightmap_coords(self, hits, triangle_of_dfs):
+        """sol_lightmap_coords: closest_hits' rows turned into surface rows (triangle, b1, b2, flags) through `triangle_of_dfs`, the uint32 table
+        lightmap_triangle_table makes (per dfs_index the lightmap triangle and its record's rotation, or SOL_TEXEL_NONE). A RAY_HIT_DTYPE array
+        goes the host route and returns a LIGHTMAP_TEXEL_DTYPE array; the [n, 8] int32 device tensor closest_hits returned goes through
+        sol_lightmap_coords_dev and returns an [n, 4] int32 device tensor (lightmap_texels_to_numpy views it). A miss, a sphere, a quad, and a
+        triangle the table does not list answer (SOL_TEXEL_NONE, 0, 0, 0)."""
+        table = np.ascontiguousarray(triangle_of_dfs.cpu().numpy() if hasattr(triangle_of_dfs, "data_ptr") else triangle_of_dfs).astype(np.uint32, copy=False).reshape(-1)
+        if isinstance(hits, np.ndarray) or not hasattr(hits, "data_ptr"):  # the host route
+            h = np.ascontiguousarray(hits)
+            if h.dtype != self.RAY_HIT_DTYPE or h.ndim != 1:
+                raise ValueError("hits: a RAY_HIT_DTYPE array, what closest_hits returned")
+            out = np.zeros(h.shape[0], dtype=LIGHTMAP_TEXEL_DTYPE)
+            self._chk(self.lib.sol_lightmap_coords(self.h, h.ctypes.data, h.shape[0], table.ctypes.data if len(table) else None, len(table), out.ctypes.data))
+            return out
+        import torch
+        if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 8 or not hits.is_contiguous() or not hits.is_cuda or hits.device.index != self.device:
+            raise ValueError("hits: the contiguous [n, 8] int32 tensor closest_hits returned, on the scene's device")
+        d_table = (triangle_of_dfs if hasattr(triangle_of_dfs, "data_ptr") and triangle_of_dfs.is_cuda and triangle_of_dfs.dtype == torch.int32
+                   and triangle_of_dfs.is_contiguous() else torch.from_numpy(table.view(np.int32)).to(hits.device))
+        out = torch.empty((int(hits.shape[0]), 4), dtype=torch.int32, device=hits.device)
+        torch.cuda.current_stream(hits.device).synchronize()  # (the hits and the table may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_coords_dev(self.h, C.c_void_p(hits.data_ptr()), int(hits.shape[0]), C.c_void_p(d_table.data_ptr()) if len(table) else None,
+                                                   len(table), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def lightmap_sample(self, values, coords, uvs, texels, width, height, channels=3, pass_of=None, nearest=False, chart_radius=None, vertices=None, points=None):
+        """sol_lightmap_sample: the baked atlas `values` (`width * height` rows whose leading `channels` 32-bit words are floats: what
+        lightmap_dilate returned) looked up at the surface rows `coords` (what lightmap_coords or lightmap_points returned). uvs [n, 3, 2] and
+        texels are lightmap_points' arguments and answer; pass_of: lightmap_dilate's plane (a tap is covered when it is not 255), None: a tap is
+        covered when a triangle owns it. The lookup is bilinear over the covered, finite taps, renormalised; nearest=True takes the one texel
+        the point falls into. chart_radius (a world length) with vertices [n, 3, 3] and points (lightmap_points' rows) switches the chart guard
+        on: an owned tap farther than that from the shaded point is left out. Returns [n, channels + 1] float32 rows - the channels, then the
+        bits of the number of taps that contributed (0: nothing was found, the row is zero). Host arrays go the host route, device tensors the
+        device route, decided by `values`."""
+        width, height, channels = int(width), int(height), int(channels)
+        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
+        cfg = _abi.SolLightmapSampleConfig(size=C.sizeof(_abi.SolLightmapSampleConfig), width=width, height=height, channels=channels, stride_bytes=4 * k,
+                                           flags=_abi.SOL_LIGHTMAP_SAMPLE_NEAREST if nearest else 0,
+                                           chart_radius=float("inf") if chart_radius is None else float(chart_radius))
+        out_words = channels + 1 if 1 <= channels <= 32 else 1
+        wh = width * height
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
+            def host(x, dtype=None):
+                return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
+            v, u, vx, p = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
+            po = host(pass_of, np.uint8)
+            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
+                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or (vx is not None and vx.shape != (u.shape[0], 3, 3))
+                    or (p is not None and p.shape != (wh, 8))):
+                raise ValueError("values: [width * height, k] float32 rows; texels, coords: LIGHTMAP_TEXEL_DTYPE rows; uvs: [n, 3, 2]; pass_of: width * height "
+                                 "bytes; vertices: [n, 3, 3]; points: [width * height, 8]")
+            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
+            self._chk(self.lib.sol_lightmap_sample(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
+                                                   None if po is None else po.ctypes.data, v.ctypes.data, None if vx is None else vx.ctypes.data,
+                                                   None if p is None else p.ctypes.data, c.ctypes.data, c.shape[0], out.ctypes.data))
+            return out
+        import torch
+
+        def dev(name, x, dtype, shape):
+            if x is None:
+                return None
+            if (not hasattr(x, "data_ptr") or x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or x.device.index != self.device
+                    or len(shape) != x.dim() or any(s is not None and s != d for s, d in zip(shape, x.shape))):
+                raise ValueError(f"{name}: a contiguous {dtype} tensor of shape {list(shape)} on the scene's device")
+            return C.c_void_p(x.data_ptr())
+        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
+        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
+                dev("values", values, torch.float32, (wh, None)), dev("vertices", vertices, torch.float32, (n_tri, 3, 3)),
+                dev("points", points, torch.float32, (wh, 8)), dev("coords", coords, torch.int32, (None, 4)), int(coords.shape[0]))
+        out = torch.empty((int(coords.shape[0]), out_words), dtype=torch.float32, device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_sample_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def lightmap_view(self, values, uvs, texels, width, height, triangle_of_dfs, x0, y0, x1, y1, sample=0, seed=0, **sample_args):
+        """The bake seen from the scene's camera: camera_rays -> closest_hits -> lightmap_coords -> lightmap_sample over the pixels [x0, x1) x
+        [y0, y1), all on device memory (values, uvs, texels and what sample_args names are device tensors). Returns an [h, w, channels + 1]
+        float32 device tensor; a pixel that misses, or hits something without lightmap, is zero with count 0."""
+        rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
+        h, w = int(rays.shape[0]), int(rays.shape[1])
+        coords = self.lightmap_coords(self.closest_hits(rays.reshape(-1, 8)), triangle_of_dfs)
+        out = self.lightmap_sample(values, coords, uvs, texels, width, height, **sample_args)
+        return out.reshape(h, w, -1)
 
     # ---- irradiance volumes (EXTENSION; DESIGN.md 24) ----
     @staticmethod
