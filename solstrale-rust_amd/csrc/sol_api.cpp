@@ -15,7 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "sol_scene.h"
+#include "sol_gather.h"
 
 namespace {
 thread_local std::string g_err;
@@ -197,6 +197,13 @@ int sol_set_partition(SolScene* s, int rank, int world) {
     s->acc_floats = floats;
   }
   return sol_rebuild_order(s);
+}
+
+int sol_device_check(int* n_devices) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
+  if (n_devices) *n_devices = ndev;
+  return SOL_OK;
 }
 
 extern "C" {
@@ -414,27 +421,12 @@ namespace {
 constexpr size_t QUERY_MAX_RAYS = (size_t)1 << 31;
 constexpr size_t QUERY_STAGE_RAYS = (size_t)1 << 22;  // the host route stages at most this many rays at a time (128 MiB each way)
 
-int query_device_check() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
-  return SOL_OK;
-}
-// The two refusals the visibility gathers share with the ray queries, each in one sentence.
-int query_mode_check(const char* fn, int mode) {
-  if (mode != SOL_QUERY_CLOSEST && mode != SOL_QUERY_OCCLUDED) return sol_fail(SOL_EINVAL, "%s: unknown mode %d (SOL_QUERY_CLOSEST or SOL_QUERY_OCCLUDED)", fn, mode);
-  return SOL_OK;
-}
-int query_medium_check(const SolScene* s, const char* fn) {
-  if (s->has_medium)
-    return sol_fail(SOL_EINVAL, "%s: the scene has a constant medium - its hits are random draws keyed by a path, which a query ray does not have", fn);
-  return SOL_OK;
-}
 // What both routes refuse, before the device is touched. *go = false: nothing to do (n == 0).
 int query_check(const SolScene* s, const char* fn, int mode, const void* rays, size_t n, const void* out, bool* go) {
   *go = false;
   if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if (const int rc = query_mode_check(fn, mode)) return rc;
-  if (const int rc = query_medium_check(s, fn)) return rc;
+  if (const int rc = sol_query_mode_check(fn, mode)) return rc;
+  if (const int rc = sol_query_medium_check(s, fn)) return rc;
   if (n > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: %zu rays in one call (at most 2^31)", fn, n);
   if (n == 0) return SOL_OK;
   if (!rays || !out) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? "ray" : "output");
@@ -467,7 +459,7 @@ extern "C" {
 int sol_query_dev(SolScene* s, int mode, const void* rays_dev, size_t n, void* out_dev) {
   int rc;
   bool go;
-  if ((rc = query_device_check()) || (rc = query_check(s, "sol_query_dev", mode, rays_dev, n, out_dev, &go)) || !go) return rc;
+  if ((rc = sol_device_check()) || (rc = query_check(s, "sol_query_dev", mode, rays_dev, n, out_dev, &go)) || !go) return rc;
   HIP_TRY(hipSetDevice(s->device));
   return query_launch(s, mode, rays_dev, n, out_dev);
 }
@@ -475,7 +467,7 @@ int sol_query_dev(SolScene* s, int mode, const void* rays_dev, size_t n, void* o
 int sol_query(SolScene* s, int mode, const SolRay* rays, size_t n, void* out) {
   int rc;
   bool go;
-  if ((rc = query_device_check()) || (rc = query_check(s, "sol_query", mode, rays, n, out, &go)) || !go) return rc;
+  if ((rc = sol_device_check()) || (rc = query_check(s, "sol_query", mode, rays, n, out, &go)) || !go) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t out_bytes = mode == SOL_QUERY_OCCLUDED ? sizeof(uint32_t) : sizeof(SolRayHit);
   const size_t cap = std::min(n, QUERY_STAGE_RAYS);
@@ -492,7 +484,7 @@ int sol_query(SolScene* s, int mode, const SolRay* rays, size_t n, void* out) {
 
 int sol_camera_rays(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* rays_dev) {
   int rc;
-  if ((rc = query_device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   if (!s || !rays_dev) return sol_fail(SOL_EINVAL, "sol_camera_rays: null %s", !s ? "scene" : "ray pointer");
   if ((rc = camera_rect_check(s, "sol_camera_rays", x0, y0, x1, y1))) return rc;
   HIP_TRY(hipSetDevice(s->device));
@@ -503,314 +495,127 @@ int sol_camera_rays(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t
 
 }  // extern "C"
 
-// ---- radiance queries (include/solstrale_hip.h; kernels: sol_radiance.hip) and irradiance queries ----
+// ---- radiance queries (include/solstrale_hip.h; kernels: sol_radiance.hip) and irradiance queries: the checks, plan,
+// host route and entry shape are sol_gather.h's ----
 namespace {
-constexpr size_t RADIANCE_STAGE_RAYS = (size_t)1 << 20;    // the host route stages at most this many rays at a time (32 + 8 + 16 bytes each)
-
-// An irradiance query is a radiance query whose samples draw their own directions: one configuration layout - the last word is `reserved`
-// for the one and `mode` for the other -, one set of checks, one launch.
-static_assert(sizeof(SolIrradianceConfig) == sizeof(SolRadianceConfig) && offsetof(SolIrradianceConfig, samples) == offsetof(SolRadianceConfig, samples) &&
-              offsetof(SolIrradianceConfig, first_sample) == offsetof(SolRadianceConfig, first_sample) &&
-              offsetof(SolIrradianceConfig, first_draw) == offsetof(SolRadianceConfig, first_draw) && offsetof(SolIrradianceConfig, seed) == offsetof(SolRadianceConfig, seed) &&
-              offsetof(SolIrradianceConfig, key_base) == offsetof(SolRadianceConfig, key_base) && offsetof(SolIrradianceConfig, mode) == offsetof(SolRadianceConfig, reserved),
-              "SolIrradianceConfig is SolRadianceConfig with `mode` in the place of `reserved`");
-enum RadianceKind { RADIANCE = 0, IRRADIANCE = 1, IRRADIANCE_RAYS = 2 };  // (the last: sol_irradiance_rays, one sample only)
-SolRadianceConfig radiance_config_of(const SolIrradianceConfig& c) { return SolRadianceConfig{c.size, c.samples, c.first_sample, c.first_draw, c.seed, c.key_base, c.mode}; }
-
-// What both routes refuse; nothing here needs a device. The part that needs no handle either is a function that is not given one:
-// behind a non-null scene pointer the configuration and n are judged before the handle is read for the first time.
-int radiance_config_check(const char* fn, RadianceKind kind, size_t n, const SolRadianceConfig* cfg) {
-  const char* rec = kind == RADIANCE ? "SolRadianceConfig" : "SolIrradianceConfig";
-  if (!cfg) return sol_fail(SOL_EINVAL, "%s: null configuration", fn);
-  if (cfg->size != sizeof(SolRadianceConfig)) return sol_fail(SOL_EINVAL, "%s: %s.size is %u, not %zu", fn, rec, cfg->size, sizeof(SolRadianceConfig));
-  if (kind == RADIANCE && cfg->reserved != 0u) return sol_fail(SOL_EINVAL, "%s: SolRadianceConfig.reserved must be 0", fn);
-  if (cfg->samples == 0u) return sol_fail(SOL_EINVAL, "%s: %s.samples is 0", fn, rec);
-  if (kind == IRRADIANCE_RAYS && cfg->samples != 1u) return sol_fail(SOL_EINVAL, "%s: %s.samples is %u: the rays of one sample (first_sample) per call", fn, rec, cfg->samples);
-  if ((uint64_t)cfg->first_sample + cfg->samples > 0xFFFFFFF0ull) return sol_fail(SOL_EINVAL, "%s: first_sample + samples goes beyond 2^32 - 16", fn);
-  if (n > QUERY_MAX_RAYS) return sol_fail(SOL_EINVAL, "%s: %zu %s in one call (at most 2^31)", fn, n, kind == RADIANCE ? "rays" : "points");
-  if (kind != RADIANCE && cfg->reserved != (uint32_t)SOL_IRRADIANCE_COSINE && cfg->reserved != (uint32_t)SOL_IRRADIANCE_SPHERE)
-    return sol_fail(SOL_EINVAL, "%s: unknown mode %u (SOL_IRRADIANCE_COSINE or SOL_IRRADIANCE_SPHERE)", fn, cfg->reserved);
-  return SOL_OK;
-}
-// *go = false: nothing to do (n == 0, which succeeds on any scene and touches nothing). out2: the second output of sol_irradiance_rays.
-int radiance_check(const SolScene* s, const char* fn, RadianceKind kind, const void* rays, size_t n, const SolRadianceConfig* cfg, const void* out, const void* out2,
+// What both routes refuse; nothing here needs a device. *go = false: nothing to do (n == 0, which succeeds on any scene and touches nothing).
+// out2: the second output of sol_irradiance_rays.
+int radiance_check(const SolScene* s, const char* fn, SolRadianceKind kind, const void* rays, size_t n, const SolRadianceConfig* cfg, const void* out, const void* out2,
                    bool* go) {
   *go = false;
   if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if (const int rc = radiance_config_check(fn, kind, n, cfg)) return rc;
+  if (const int rc = sol_radiance_config_check(fn, kind, n, cfg)) return rc;
   if (n == 0) return SOL_OK;
   if (s->has_medium)
     return sol_fail(SOL_EINVAL, "%s: the scene has a constant medium - the render kernels for media have no register left for a radiance lane's ray; not supported yet", fn);
-  if (!rays || !out || !out2) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? (kind == RADIANCE ? "ray" : "point") : "output");
+  if (!rays || !out || !out2) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? (kind == SOL_KIND_RADIANCE ? "ray" : "point") : "output");
   *go = true;
   return SOL_OK;
 }
 
-// n <= 2^31 rays (and keys, or null) in device memory, on the scene's stream. key_base: the key of ray 0 of THIS batch when keys is null.
-// gather: the rows are the points of an irradiance query, cfg.reserved its mode.
+// n <= 2^31 rays (and keys, or null) in device memory, n SolRadiance out. key_base: the key of ray 0 of THIS batch when keys is null. gather: the
+// rows are the points of an irradiance query, cfg.reserved its mode. Chunk sums, one row each.
 int radiance_launch(SolScene* s, bool gather, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
-  int rc;
-  if ((rc = sol_scene_to_device(s))) return rc;
-  const auto [env, lt] = sol_estimator(s, s->S, false);  // what a render would run now
-  const int bpc = sol_radiance_blocks_per_cu(gather, false, s->strict_triangles, env, lt);
-  const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
-  if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
-  const uint32_t total_chunks = (uint32_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
-  // One chunk: one launch writes the answers. More: the chunk sums go through the partial buffer, at most SolScene::rad_partial_max_rows of them per
-  // launch - the call is split over rays (answers are per ray) and, for sample ranges beyond 16 * 2^18, over windows of chunks (the resolve
-  // kernel carries a ray's sum from one window to the next: the same additions in the same order).
-  const size_t max_rows = std::max<size_t>(64, s->rad_partial_max_rows);
-  const size_t win_chunks = std::min<size_t>(total_chunks, max_rows / 64);
-  const size_t slice_rays = total_chunks == 1 ? n : std::max<size_t>(64, max_rows / win_chunks / 64 * 64);
-  for (size_t at = 0; at < n; at += slice_rays) {
-    const size_t k = std::min(slice_rays, n - at);
-    RadianceParams P{};
-    P.n_rays = (uint32_t)k;
-    P.n_groups = (uint32_t)((k + 63) / 64);
-    P.end_sample = cfg.first_sample + cfg.samples;
-    P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
-    P.key_base = key_base + (uint32_t)at;
-    P.first_draw = cfg.first_draw;
-    P.switch_below = s->switch_below;
-    P.direct = total_chunks == 1 ? 1u : 0u;
-    P.mode = gather ? cfg.reserved : 0u;
-    const char* rays_at = (const char*)rays_dev + at * sizeof(SolRay);
-    const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
-    char* out_at = (char*)out_dev + at * sizeof(SolRadiance);
-    if (!P.direct && (rc = s->rad_partial.reserve(s->stream, (size_t)P.n_groups * 64 * win_chunks))) return rc;
-    for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
-      P.n_chunks = (uint32_t)std::min<size_t>(win_chunks, total_chunks - c0);
-      P.first_sample = cfg.first_sample + (uint32_t)c0 * SOL_CHUNK;
-      const uint64_t items = (uint64_t)P.n_chunks * P.n_groups * 64u;  // (<= 2^31: far below the headroom of the 32-bit work counter, SOL_MAX_ITEMS)
-      P.n_items = (uint32_t)items;
-      // the grid and the spill tail of THIS launch (the render launch's area is sized for another)
-      uint32_t grid;
-      if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
-      P.total_threads = grid * SOL_WG;
-      HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
-      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, gather, false, may_spill, s->strict_triangles, env, lt, rays_at, keys_at, out_at, s->rad_partial.get(),
-                                  s->rad_work.get(), s->rad_spill.get(), grid, s->stream));
-      if (!P.direct) HIP_TRY(sol_launch_radiance_resolve(P, rays_at, s->rad_partial.get(), out_at, cfg.samples, c0 != 0, s->stream));
-    }
-  }
-  return SOL_OK;
+  const SolEstimator est = sol_estimator(s, s->S, false);  // what a render would run now
+  const SolGatherPlan plan{sol_radiance_blocks_per_cu(gather, false, s->strict_triangles, est.env, est.lt), 1u, 0u, sizeof(SolRadiance), gather ? cfg.reserved : 0u};
+  return sol_gather_launch(s, plan, rays_dev, keys_dev, n, cfg, key_base, out_dev, [&](const SolGatherWindow& w) -> int {
+    HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), w.P, gather, false, w.may_spill, s->strict_triangles, est.env, est.lt, w.points, w.keys, w.out, s->rad_partial.get(),
+                                s->rad_work.get(), s->rad_spill.get(), w.grid, s->stream));
+    if (!w.P.direct) HIP_TRY(sol_launch_radiance_resolve(w.P, w.points, s->rad_partial.get(), w.out, cfg.samples, !w.first, s->stream));
+    return SOL_OK;
+  });
 }
 
-// SH irradiance queries: n <= 2^31 points (and keys, or null) in device memory, n SolSh9 out, on the scene's stream. Every launch
-// of the path kernel writes one colour per (point, sample) into the partial buffer and is followed by the projection kernel. A launch holds
-// whole chunks of 64 x k points: rows = points x samples <= SolScene::rad_partial_max_rows, at least one group of one chunk (1024 rows). The call is
-// split over points (answers are per point) and over windows of chunks (the projection kernel carries a point's sums from one window to the next
-// in `out`: the same additions in the same order). moments: an irradiance-moments query - the same plan and the same path launches,
-// followed by sol_moments_project_kernel, which writes n SolMoments. carry, total_samples (moments only): a later round of an adaptive gather
-//  - `out` holds the rows' sums of the earlier rounds, so that the projection accumulates from the first window on, and the rows'
-// count is their new total rather than this call's samples.
-int irradiance_sh_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev,
-                         bool moments = false, bool carry = false, uint32_t total_samples = 0) {
-  int rc;
-  if ((rc = sol_scene_to_device(s))) return rc;
-  const auto [env, lt] = sol_estimator(s, s->S, false);  // what a render would run now
-  const int bpc = sol_radiance_blocks_per_cu(true, true, s->strict_triangles, env, lt);
-  const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
-  if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
-  const size_t total_chunks = (size_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
-  const size_t unit = (size_t)64 * SOL_CHUNK;  // rows of one group of points over one chunk
-  const size_t units = std::max<size_t>(1, std::min<size_t>(s->rad_partial_max_rows, (size_t)1 << 31) / unit);
-  const size_t win_chunks = std::min(total_chunks, units);
-  const size_t slice_points = units / win_chunks * 64;
-  for (size_t at = 0; at < n; at += slice_points) {
-    const size_t k = std::min(slice_points, n - at);
-    RadianceParams P{};
-    P.n_rays = (uint32_t)k;
-    P.n_groups = (uint32_t)((k + 63) / 64);
-    P.end_sample = cfg.first_sample + cfg.samples;
-    P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
-    P.key_base = key_base + (uint32_t)at;
-    P.first_draw = cfg.first_draw;
-    P.switch_below = s->switch_below;
-    P.mode = cfg.reserved;
-    const char* points_at = (const char*)points_dev + at * sizeof(SolRay);
-    const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
-    char* out_at = (char*)out_dev + at * (moments ? sizeof(SolMoments) : sizeof(SolSh9));
-    if ((rc = s->rad_partial.reserve(s->stream, (size_t)P.n_groups * 64 * std::min<size_t>(win_chunks * SOL_CHUNK, cfg.samples)))) return rc;
-    for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
-      P.n_chunks = (uint32_t)std::min(win_chunks, total_chunks - c0);
-      P.first_sample = cfg.first_sample + (uint32_t)(c0 * SOL_CHUNK);
-      const uint32_t win_samples = std::min<uint32_t>(P.n_chunks * (uint32_t)SOL_CHUNK, P.end_sample - P.first_sample);  // (the call's last chunk may be short)
-      const uint64_t items = (uint64_t)win_samples * P.n_groups * 64u;  // (<= 2^31 rows of the partial buffer)
-      P.n_items = (uint32_t)items;
-      uint32_t grid;
-      if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
-      P.total_threads = grid * SOL_WG;
-      HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
-      HIP_TRY(sol_launch_radiance(s->mirror.dev.get(), P, true, true, may_spill, s->strict_triangles, env, lt, points_at, keys_at, nullptr, s->rad_partial.get(),
-                                  s->rad_work.get(), s->rad_spill.get(), grid, s->stream));
-      if (moments)
-        HIP_TRY(sol_launch_moments_project(P, points_at, s->rad_partial.get(), out_at, win_samples, carry ? total_samples : cfg.samples, carry || c0 != 0, s->stream));
-      else
-        HIP_TRY(sol_launch_sh_project(P, points_at, keys_at, s->rad_partial.get(), out_at, win_samples, cfg.samples, c0 != 0, s->stream));
-    }
-  }
-  return SOL_OK;
+// The two routes of a family whose launches are launch(points_dev, keys_dev, k, cfg, key_base, out_dev): over the caller's device arrays, or over
+// the caller's host arrays, staged. check(cfg, go): the family's refusals under the entry point's name.
+template <typename Config, typename Check, typename Launch>
+int gather_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const Config* config, void* out_dev, Check&& check, Launch&& launch) {
+  return sol_gather_entry(s, config, check, [&](const SolRadianceConfig& cfg) { return launch(points_dev, keys_dev, n, cfg, cfg.key_base, out_dev); });
 }
-
-}  // namespace
-
-// (sol_scene.h: for sol_depth.cpp)
-int sol_gather_config_check(const char* fn, size_t n, const SolIrradianceConfig* config, SolRadianceConfig* cfg) {
-  if (config) *cfg = radiance_config_of(*config);
-  return radiance_config_check(fn, IRRADIANCE, n, config ? cfg : nullptr);
-}
-int sol_query_medium_check(const SolScene* s, const char* fn) { return query_medium_check(s, fn); }
-int sol_irradiance_moments_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev,
-                                  bool carry, uint32_t total_samples) {
-  return irradiance_sh_launch(s, points_dev, keys_dev, n, cfg, key_base, out_dev, true, carry, total_samples);
-}
-
-namespace {
-// The host route of both: arrays staged through buffers the handle owns, RADIANCE_STAGE_RAYS rows at a time; blocks.
-int radiance_staged(SolScene* s, bool gather, const SolRay* rays, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, SolRadiance* out) {
-  int rc;
-  HIP_TRY(hipSetDevice(s->device));
-  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
-  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap))) return rc;
-  for (size_t at = 0; at < n; at += cap) {  // (answers are per ray: the split changes nothing)
-    const size_t k = std::min(cap, n - at);
-    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), rays + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
-    if ((rc = radiance_launch(s, gather, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get()))) return rc;
-    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  return SOL_OK;
-}
-
-// The host route of the SH irradiance queries: radiance_staged's buffers, the answers' staging grown to the 112 bytes (seven SolRadiance) of a SolSh9 row -
-// or, moments, to the 32 bytes (two SolRadiance) of a SolMoments row.
-static_assert(sizeof(SolSh9) == 7 * sizeof(SolRadiance), "a SolSh9 row is seven dwordx4");
-static_assert(sizeof(SolMoments) == 2 * sizeof(SolRadiance), "a SolMoments row is two dwordx4");
-int irradiance_sh_staged(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, void* out, bool moments = false) {
-  const size_t rows = moments ? 2 : 7;
-  int rc;
-  HIP_TRY(hipSetDevice(s->device));
-  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
-  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap * rows))) return rc;
-  for (size_t at = 0; at < n; at += cap) {  // (answers are per point: the split changes nothing)
-    const size_t k = std::min(cap, n - at);
-    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), points + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
-    if ((rc = irradiance_sh_launch(s, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get(), moments))) return rc;
-    HIP_TRY(hipMemcpyAsync((char*)out + at * rows * sizeof(SolRadiance), s->rad_out.get(), k * rows * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  return SOL_OK;
+template <typename Config, typename Check, typename Launch>
+int gather_host(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const Config* config, void* out, size_t out_stride, Check&& check, Launch&& launch) {
+  return sol_gather_entry(s, config, check, [&](const SolRadianceConfig& cfg) {
+    return sol_gather_stage(s, points, keys, n, SOL_GATHER_STAGE_POINTS, out, out_stride, cfg.key_base,
+                            [&](const void* p, const void* k, size_t m, uint32_t key_base, void* o) { return launch(p, k, m, cfg, key_base, o); });
+  });
 }
 }  // namespace
 
 extern "C" {
 
 int sol_radiance_dev(SolScene* s, const void* rays_dev, const void* keys_dev, size_t n, const SolRadianceConfig* cfg, void* out_dev) {
-  int rc;
-  bool go;
-  if ((rc = radiance_check(s, "sol_radiance_dev", RADIANCE, rays_dev, n, cfg, out_dev, out_dev, &go)) || !go || (rc = query_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return radiance_launch(s, false, rays_dev, keys_dev, n, *cfg, cfg->key_base, out_dev);
+  return gather_dev(s, rays_dev, keys_dev, n, cfg, out_dev,
+                    [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_radiance_dev", SOL_KIND_RADIANCE, rays_dev, n, c, out_dev, out_dev, go); },
+                    [&](auto... a) { return radiance_launch(s, false, a...); });
 }
 
 int sol_radiance(SolScene* s, const SolRay* rays, const SolRayKey* keys, size_t n, const SolRadianceConfig* cfg, SolRadiance* out) {
-  int rc;
-  bool go;
-  if ((rc = radiance_check(s, "sol_radiance", RADIANCE, rays, n, cfg, out, out, &go)) || !go || (rc = query_device_check())) return rc;
-  return radiance_staged(s, false, rays, keys, n, *cfg, out);
+  return gather_host(s, rays, keys, n, cfg, out, sizeof(SolRadiance),
+                     [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_radiance", SOL_KIND_RADIANCE, rays, n, c, out, out, go); },
+                     [&](auto... a) { return radiance_launch(s, false, a...); });
 }
 
 int sol_irradiance_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = radiance_check(s, "sol_irradiance_dev", IRRADIANCE, points_dev, n, config ? &cfg : nullptr, out_dev, out_dev, &go)) || !go || (rc = query_device_check()))
-    return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return radiance_launch(s, true, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev);
+  return gather_dev(s, points_dev, keys_dev, n, config, out_dev,
+                    [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_irradiance_dev", SOL_KIND_IRRADIANCE, points_dev, n, c, out_dev, out_dev, go); },
+                    [&](auto... a) { return radiance_launch(s, true, a...); });
 }
 
 int sol_irradiance(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolRadiance* out) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = radiance_check(s, "sol_irradiance", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
-  return radiance_staged(s, true, points, keys, n, cfg, out);
+  return gather_host(s, points, keys, n, config, out, sizeof(SolRadiance),
+                     [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_irradiance", SOL_KIND_IRRADIANCE, points, n, c, out, out, go); },
+                     [&](auto... a) { return radiance_launch(s, true, a...); });
 }
 
+// SH irradiance queries and irradiance moments: per sample, sol_irradiance_each_launch
 int sol_irradiance_sh_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = radiance_check(s, "sol_irradiance_sh_dev", IRRADIANCE, points_dev, n, config ? &cfg : nullptr, out_dev, out_dev, &go)) || !go || (rc = query_device_check()))
-    return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return irradiance_sh_launch(s, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev);
+  return gather_dev(s, points_dev, keys_dev, n, config, out_dev,
+                    [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_irradiance_sh_dev", SOL_KIND_IRRADIANCE, points_dev, n, c, out_dev, out_dev, go); },
+                    [&](auto... a) { return sol_irradiance_each_launch(s, a..., false); });
 }
 
 int sol_irradiance_sh(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolSh9* out) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = radiance_check(s, "sol_irradiance_sh", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
-  return irradiance_sh_staged(s, points, keys, n, cfg, out);
+  return gather_host(s, points, keys, n, config, out, sizeof(SolSh9),
+                     [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_irradiance_sh", SOL_KIND_IRRADIANCE, points, n, c, out, out, go); },
+                     [&](auto... a) { return sol_irradiance_each_launch(s, a..., false); });
 }
 
 int sol_irradiance_moments_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = radiance_check(s, "sol_irradiance_moments_dev", IRRADIANCE, points_dev, n, config ? &cfg : nullptr, out_dev, out_dev, &go)) || !go ||
-      (rc = query_device_check()))
-    return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return irradiance_sh_launch(s, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev, true);
+  return gather_dev(s, points_dev, keys_dev, n, config, out_dev,
+                    [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_irradiance_moments_dev", SOL_KIND_IRRADIANCE, points_dev, n, c, out_dev, out_dev, go); },
+                    [&](auto... a) { return sol_irradiance_each_launch(s, a..., true); });
 }
 
 int sol_irradiance_moments(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolMoments* out) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = radiance_check(s, "sol_irradiance_moments", IRRADIANCE, points, n, config ? &cfg : nullptr, out, out, &go)) || !go || (rc = query_device_check())) return rc;
-  return irradiance_sh_staged(s, points, keys, n, cfg, out, true);
+  return gather_host(s, points, keys, n, config, out, sizeof(SolMoments),
+                     [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_irradiance_moments", SOL_KIND_IRRADIANCE, points, n, c, out, out, go); },
+                     [&](auto... a) { return sol_irradiance_each_launch(s, a..., true); });
 }
 
 int sol_irradiance_rays(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* rays_out_dev,
                         void* keys_out_dev) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = radiance_check(s, "sol_irradiance_rays", IRRADIANCE_RAYS, points_dev, n, config ? &cfg : nullptr, rays_out_dev, keys_out_dev, &go)) || !go ||
-      (rc = query_device_check()))
-    return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  // (no search: neither the scene's device mirror nor any scratch is needed - the generator and the point are all there is)
-  RadianceParams P{};
-  P.n_rays = (uint32_t)n;  // (n == 2^31 fits; the grid is n / 256 blocks)
-  P.first_sample = cfg.first_sample;
-  P.end_sample = cfg.first_sample + 1u;
-  P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
-  P.key_base = cfg.key_base;
-  P.first_draw = cfg.first_draw;
-  P.mode = cfg.reserved;
-  HIP_TRY(sol_launch_irradiance_rays(P, points_dev, keys_dev, rays_out_dev, keys_out_dev, s->stream));
-  return SOL_OK;
+  return sol_gather_entry(
+      s, config,
+      [&](const SolRadianceConfig* c, bool* go) { return radiance_check(s, "sol_irradiance_rays", SOL_KIND_IRRADIANCE_RAYS, points_dev, n, c, rays_out_dev, keys_out_dev, go); },
+      [&](const SolRadianceConfig& cfg) -> int {
+        // (no search: neither the scene's device mirror nor any scratch is needed - the generator and the point are all there is)
+        RadianceParams P{};
+        P.n_rays = (uint32_t)n;  // (n == 2^31 fits; the grid is n / 256 blocks)
+        P.first_sample = cfg.first_sample;
+        P.end_sample = cfg.first_sample + 1u;
+        P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
+        P.key_base = cfg.key_base;
+        P.first_draw = cfg.first_draw;
+        P.mode = cfg.reserved;
+        HIP_TRY(sol_launch_irradiance_rays(P, points_dev, keys_dev, rays_out_dev, keys_out_dev, s->stream));
+        return SOL_OK;
+      });
 }
 
 int sol_camera_ray_keys(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1, uint32_t sample, uint64_t seed, void* keys_dev) {
   int rc;
   if (!s || !keys_dev) return sol_fail(SOL_EINVAL, "sol_camera_ray_keys: null %s", !s ? "scene" : "key pointer");
-  if ((rc = query_device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   if ((rc = camera_rect_check(s, "sol_camera_ray_keys", x0, y0, x1, y1))) return rc;
   HIP_TRY(hipSetDevice(s->device));
   if ((rc = sol_scene_to_device(s))) return rc;
@@ -822,107 +627,44 @@ int sol_camera_ray_keys(SolScene* s, uint32_t x0, uint32_t y0, uint32_t x1, uint
 
 // ---- visibility gathers (include/solstrale_hip.h; kernels: sol_visibility.hip) ----
 namespace {
-static_assert(sizeof(SolVisibility) == 2 * sizeof(SolRadiance), "a SolVisibility row is two dwordx4: two rows of the radiance queries' buffers");
-
 // What both routes refuse; nothing here needs a device, and nothing in front of n == 0 reads the handle. *go = false: nothing to do.
 int visibility_check(const SolScene* s, const char* fn, int mode, const void* points, size_t n, const SolRadianceConfig* cfg, const void* out, bool* go) {
   *go = false;
   if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if (const int rc = query_mode_check(fn, mode)) return rc;
-  if (const int rc = radiance_config_check(fn, IRRADIANCE, n, cfg)) return rc;
+  if (const int rc = sol_query_mode_check(fn, mode)) return rc;
+  if (const int rc = sol_radiance_config_check(fn, SOL_KIND_IRRADIANCE, n, cfg)) return rc;
   if (n == 0) return SOL_OK;
-  if (const int rc = query_medium_check(s, fn)) return rc;
+  if (const int rc = sol_query_medium_check(s, fn)) return rc;
   if (!points || !out) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !points ? "point" : "output");
   *go = true;
   return SOL_OK;
 }
 
-// n <= 2^31 points (and keys, or null) in device memory, n SolVisibility out, on the scene's stream: radiance_launch's plan with this family's
-// kernels. One chunk: one launch writes the answers. More: the chunk rows go through the radiance queries' partial buffer, two of its rows
-// each, under the same bound - the call is split over points (answers are per point) and over windows of chunks (the resolve kernel carries
-// a point's sums from one window to the next in `out`: the same additions in the same order).
+// n <= 2^31 points (and keys, or null) in device memory, n SolVisibility out. Chunk sums, two rows each.
 int visibility_launch(SolScene* s, int mode, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev) {
-  int rc;
-  if ((rc = sol_scene_to_device(s))) return rc;
   const bool any = mode == SOL_QUERY_OCCLUDED;
-  const int bpc = sol_visibility_blocks_per_cu(any, s->strict_triangles);
-  const bool may_spill = s->tree.depth > (uint32_t)SOL_LDS_STACK;
-  if ((rc = s->rad_work.reserve(s->stream, 1))) return rc;
-  const uint32_t total_chunks = (uint32_t)(((uint64_t)cfg.samples + SOL_CHUNK - 1) / SOL_CHUNK);
-  const size_t max_rows = std::max<size_t>(64, std::min<size_t>(s->rad_partial_max_rows, (size_t)1 << 31) / 2);  // in visibility rows
-  const size_t win_chunks = std::min<size_t>(total_chunks, max_rows / 64);
-  const size_t slice_points = total_chunks == 1 ? n : std::max<size_t>(64, max_rows / win_chunks / 64 * 64);
-  for (size_t at = 0; at < n; at += slice_points) {
-    const size_t k = std::min(slice_points, n - at);
-    RadianceParams P{};
-    P.n_rays = (uint32_t)k;
-    P.n_groups = (uint32_t)((k + 63) / 64);
-    P.end_sample = cfg.first_sample + cfg.samples;
-    P.seed_lo = (uint32_t)cfg.seed; P.seed_hi = (uint32_t)(cfg.seed >> 32);
-    P.key_base = key_base + (uint32_t)at;
-    P.first_draw = cfg.first_draw;
-    P.switch_below = s->switch_below;
-    P.direct = total_chunks == 1 ? 1u : 0u;
-    P.mode = cfg.reserved;
-    const char* points_at = (const char*)points_dev + at * sizeof(SolRay);
-    const char* keys_at = keys_dev ? (const char*)keys_dev + at * sizeof(SolRayKey) : nullptr;
-    char* out_at = (char*)out_dev + at * sizeof(SolVisibility);
-    if (!P.direct && (rc = s->rad_partial.reserve(s->stream, (size_t)P.n_groups * 64 * win_chunks * 2))) return rc;
-    for (size_t c0 = 0; c0 < total_chunks; c0 += win_chunks) {
-      P.n_chunks = (uint32_t)std::min<size_t>(win_chunks, total_chunks - c0);
-      P.first_sample = cfg.first_sample + (uint32_t)c0 * SOL_CHUNK;
-      const uint64_t items = (uint64_t)P.n_chunks * P.n_groups * 64u;  // (<= 2^31: far below the headroom of the 32-bit work counter, SOL_MAX_ITEMS)
-      P.n_items = (uint32_t)items;
-      // the grid and the spill tail of THIS launch
-      uint32_t grid;
-      if ((rc = sol_launch_plan(s, bpc, items, SOL_LDS_STACK, s->tree.depth, s->rad_spill, &grid))) return rc;
-      P.total_threads = grid * SOL_WG;
-      HIP_TRY(hipMemsetAsync(s->rad_work.get(), 0, sizeof(uint32_t), s->stream));
-      HIP_TRY(sol_launch_visibility(s->mirror.dev.get(), P, any, may_spill, s->strict_triangles, points_at, keys_at, out_at, s->rad_partial.get(), s->rad_work.get(),
-                                    s->rad_spill.get(), grid, s->stream));
-      if (!P.direct) HIP_TRY(sol_launch_visibility_resolve(P, points_at, s->rad_partial.get(), out_at, cfg.samples, c0 != 0, s->stream));
-    }
-  }
-  return SOL_OK;
-}
-
-// The host route: radiance_staged's buffers, the answers' staging grown to the two rows of a SolVisibility.
-int visibility_staged(SolScene* s, int mode, const SolRay* points, const SolRayKey* keys, size_t n, const SolRadianceConfig& cfg, SolVisibility* out) {
-  int rc;
-  HIP_TRY(hipSetDevice(s->device));
-  const size_t cap = std::min(n, RADIANCE_STAGE_RAYS);
-  if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap * 2))) return rc;
-  for (size_t at = 0; at < n; at += cap) {  // (answers are per point: the split changes nothing)
-    const size_t k = std::min(cap, n - at);
-    HIP_TRY(hipMemcpyAsync(s->rad_in.get(), points + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-    if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
-    if ((rc = visibility_launch(s, mode, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, s->rad_out.get()))) return rc;
-    HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolVisibility), hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-  }
-  return SOL_OK;
+  const SolGatherPlan plan{sol_visibility_blocks_per_cu(any, s->strict_triangles), 2u, 0u, sizeof(SolVisibility), cfg.reserved};
+  return sol_gather_launch(s, plan, points_dev, keys_dev, n, cfg, key_base, out_dev, [&](const SolGatherWindow& w) -> int {
+    HIP_TRY(sol_launch_visibility(s->mirror.dev.get(), w.P, any, w.may_spill, s->strict_triangles, w.points, w.keys, w.out, s->rad_partial.get(), s->rad_work.get(),
+                                  s->rad_spill.get(), w.grid, s->stream));
+    if (!w.P.direct) HIP_TRY(sol_launch_visibility_resolve(w.P, w.points, s->rad_partial.get(), w.out, cfg.samples, !w.first, s->stream));
+    return SOL_OK;
+  });
 }
 }  // namespace
 
 extern "C" {
 
 int sol_visibility_dev(SolScene* s, int mode, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, void* out_dev) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = visibility_check(s, "sol_visibility_dev", mode, points_dev, n, config ? &cfg : nullptr, out_dev, &go)) || !go || (rc = query_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  return visibility_launch(s, mode, points_dev, keys_dev, n, cfg, cfg.key_base, out_dev);
+  return gather_dev(s, points_dev, keys_dev, n, config, out_dev,
+                    [&](const SolRadianceConfig* c, bool* go) { return visibility_check(s, "sol_visibility_dev", mode, points_dev, n, c, out_dev, go); },
+                    [&](auto... a) { return visibility_launch(s, mode, a...); });
 }
 
 int sol_visibility(SolScene* s, int mode, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, SolVisibility* out) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if (config) cfg = radiance_config_of(*config);
-  if ((rc = visibility_check(s, "sol_visibility", mode, points, n, config ? &cfg : nullptr, out, &go)) || !go || (rc = query_device_check())) return rc;
-  return visibility_staged(s, mode, points, keys, n, cfg, out);
+  return gather_host(s, points, keys, n, config, out, sizeof(SolVisibility),
+                     [&](const SolRadianceConfig* c, bool* go) { return visibility_check(s, "sol_visibility", mode, points, n, c, out, go); },
+                     [&](auto... a) { return visibility_launch(s, mode, a...); });
 }
 
 }  // extern "C"

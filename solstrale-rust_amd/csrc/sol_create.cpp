@@ -347,8 +347,7 @@ static int world_tree_check(const SolSceneDesc* d, int use_sah, SolTreeCheck* ou
   DeviceSplitInfo split;
   std::vector<DTri> dev_tris;
   if (use_sah < 0) {  // the tree sol_build.hip builds on the GPU, checked like the host-built ones
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
+    if (const int rc = sol_device_check()) return rc;
     HIP_TRY(hipSetDevice(0));
     dev_tris = cast_triangles(*d);
     SolSplitOptions sp = split_options(ovr, nullptr);
@@ -731,7 +730,7 @@ static int check_lights(const SolSceneDesc* d, HostRecords& r) {
 // 7. the device: the handle, its stream, the properties
 static int open_device(int device, ScenePtr& scene, std::chrono::steady_clock::time_point& t_upload0) {
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
+  if (const int rc = sol_device_check(&ndev)) return rc;
   if (device < 0 || device >= ndev) return sol_fail(SOL_EDEVICE, "device %d out of range (%d devices)", device, ndev);
   HIP_TRY(hipSetDevice(device));
   SolScene* s = new SolScene();

@@ -1,28 +1,22 @@
 // sol_gather_adaptive.cpp -- sol_irradiance_adaptive and sol_radiance_rescale (include/solstrale_hip.h): an irradiance-moments gather
 // in rounds over the points still active (kernels: sol_gather_adaptive.hip; the stop rule: sol_gather_adaptive.h). Round 0 is sol_irradiance_moments's
 // launch over the caller's own points, written into the caller's rows; a later round is the same launch over the compact rows the handle owns, with
-// the projection carrying the rows' sums on (sol_irradiance_moments_launch, sol_api.cpp), followed by the write-back to the caller's rows. After
+// the projection carrying the rows' sums on (sol_irradiance_each_launch, sol_gather.cpp), followed by the write-back to the caller's rows. After
 // every round: judge, scan, one read-back of four counters, and - while rows go on - the scatter. Every refusal is decided before the device is
 // looked for.
 #include <cmath>
 
-#include "sol_scene.h"
+#include "sol_gather.h"
 
 namespace {
-constexpr size_t STAGE_ROWS = (size_t)1 << 20;  // the host routes stage at most this many rows at a time
+constexpr size_t RESCALE_STAGE_ROWS = (size_t)1 << 20;  // sol_radiance_rescale's host route stages at most this many rows at a time
 
-int device_check() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
-  return SOL_OK;
-}
-
-// In the header's order. *go = false: nothing to do (n == 0). *cfg: the gather's configuration as the launches take it.
-int adaptive_check(const SolScene* s, const char* fn, const void* points, size_t n, const SolIrradianceConfig* config, const SolGatherAdaptive* a, const void* out,
-                   const SolGatherAdaptiveStats* stats, SolRadianceConfig* cfg, bool* go) {
+// In the header's order. *go = false: nothing to do (n == 0).
+int adaptive_check(const SolScene* s, const char* fn, const void* points, size_t n, const SolRadianceConfig* cfg, const SolGatherAdaptive* a, const void* out,
+                   const SolGatherAdaptiveStats* stats, bool* go) {
   *go = false;
   if (!s) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if (const int rc = sol_gather_config_check(fn, n, config, cfg)) return rc;
+  if (const int rc = sol_radiance_config_check(fn, SOL_KIND_IRRADIANCE, n, cfg)) return rc;
   if (!a) return sol_fail(SOL_EINVAL, "%s: null adaptive configuration", fn);
   if (a->size != sizeof(SolGatherAdaptive)) return sol_fail(SOL_EINVAL, "%s: SolGatherAdaptive.size is %u, not %zu", fn, a->size, sizeof(SolGatherAdaptive));
   if (a->reserved != 0u) return sol_fail(SOL_EINVAL, "%s: SolGatherAdaptive.reserved must be 0", fn);
@@ -62,7 +56,7 @@ int adaptive_part(SolScene* s, const void* points, const void* keys, size_t n, c
 
   SolRadianceConfig round_cfg = cfg;
   round_cfg.samples = (uint32_t)std::min<uint64_t>(a.round, max_samples);
-  if ((rc = sol_irradiance_moments_launch(s, points, keys, n, round_cfg, key_base, out, false, 0))) return rc;
+  if ((rc = sol_irradiance_each_launch(s, points, keys, n, round_cfg, key_base, out, true))) return rc;
   uint32_t n_active = (uint32_t)n, rounds = 0;
   for (uint64_t k = 0;; ++k) {
     const uint32_t count = (uint32_t)std::min<uint64_t>((k + 1) * a.round, max_samples);  // what every active row holds now
@@ -86,7 +80,7 @@ int adaptive_part(SolScene* s, const void* points, const void* keys, size_t n, c
     const uint64_t done = (k + 1) * a.round;  // (< max_samples: rows went on)
     round_cfg.first_sample = cfg.first_sample + (uint32_t)done;
     round_cfg.samples = (uint32_t)std::min<uint64_t>(a.round, max_samples - done);
-    if ((rc = sol_irradiance_moments_launch(s, s->ga_points.get(), s->ga_keys.get(), n_active, round_cfg, 0u, s->ga_totals.get(), true, (uint32_t)done + round_cfg.samples)))
+    if ((rc = sol_irradiance_each_launch(s, s->ga_points.get(), s->ga_keys.get(), n_active, round_cfg, 0u, s->ga_totals.get(), true, true, (uint32_t)done + round_cfg.samples)))
       return rc;
     HIP_TRY(sol_launch_gather_writeback(n_active, index_out, s->ga_totals.get(), out, s->stream));
   }
@@ -110,13 +104,20 @@ int adaptive_launch(SolScene* s, const void* points, const void* keys, size_t n,
   return SOL_OK;
 }
 
-void stats_of(const Tally& t, SolGatherAdaptiveStats* stats) {
-  if (!stats) return;
+// Both routes: the checks, the device, `run` with the tally of its rounds, and - also when there was nothing to do - the statistics.
+template <typename Run>
+int adaptive_entry(SolScene* s, const char* fn, const void* points, size_t n, const SolIrradianceConfig* config, const SolGatherAdaptive* a, const void* out,
+                   SolGatherAdaptiveStats* stats, Run&& run) {
+  Tally t;
+  const int rc = sol_gather_entry(s, config, [&](const SolRadianceConfig* c, bool* go) { return adaptive_check(s, fn, points, n, c, a, out, stats, go); },
+                                  [&](const SolRadianceConfig& cfg) { return run(cfg, t); });
+  if (rc != SOL_OK || !stats) return rc;
   stats->rounds = t.rounds;
   stats->paths = t.paths;
   stats->rows_valid = t.valid;
   stats->rows_converged = t.converged;
   stats->rows_capped = t.capped;
+  return SOL_OK;
 }
 
 int rescale_check(bool have_scene, const char* fn, const void* rows, size_t n, uint32_t target, const void* out) {
@@ -131,48 +132,22 @@ extern "C" {
 
 int sol_irradiance_adaptive_dev(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolIrradianceConfig* config, const SolGatherAdaptive* adaptive,
                                 void* moments_out_dev, SolGatherAdaptiveStats* stats) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if ((rc = adaptive_check(s, "sol_irradiance_adaptive_dev", points_dev, n, config, adaptive, moments_out_dev, stats, &cfg, &go))) return rc;
-  Tally tally;
-  if (go) {
-    if ((rc = device_check())) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    if ((rc = adaptive_launch(s, points_dev, keys_dev, n, cfg, cfg.key_base, *adaptive, moments_out_dev, tally))) return rc;
-  }
-  stats_of(tally, stats);
-  return SOL_OK;
+  return adaptive_entry(s, "sol_irradiance_adaptive_dev", points_dev, n, config, adaptive, moments_out_dev, stats, [&](const SolRadianceConfig& cfg, Tally& tally) {
+    return adaptive_launch(s, points_dev, keys_dev, n, cfg, cfg.key_base, *adaptive, moments_out_dev, tally);
+  });
 }
 
 int sol_irradiance_adaptive(SolScene* s, const SolRay* points, const SolRayKey* keys, size_t n, const SolIrradianceConfig* config, const SolGatherAdaptive* adaptive,
                             SolMoments* out, SolGatherAdaptiveStats* stats) {
-  int rc;
-  bool go;
-  SolRadianceConfig cfg{};
-  if ((rc = adaptive_check(s, "sol_irradiance_adaptive", points, n, config, adaptive, out, stats, &cfg, &go))) return rc;
-  Tally tally;
-  if (go) {
-    if ((rc = device_check())) return rc;
-    HIP_TRY(hipSetDevice(s->device));
-    const size_t cap = std::min(n, STAGE_ROWS);
-    if ((rc = s->rad_in.reserve(s->stream, cap)) || (rc = s->rad_keys.reserve(s->stream, cap)) || (rc = s->rad_out.reserve(s->stream, cap * 2))) return rc;
-    for (size_t at = 0; at < n; at += cap) {  // (answers are per point: the split changes nothing)
-      const size_t k = std::min(cap, n - at);
-      HIP_TRY(hipMemcpyAsync(s->rad_in.get(), points + at, k * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-      if (keys) HIP_TRY(hipMemcpyAsync(s->rad_keys.get(), keys + at, k * sizeof(SolRayKey), hipMemcpyHostToDevice, s->stream));
-      if ((rc = adaptive_launch(s, s->rad_in.get(), keys ? s->rad_keys.get() : nullptr, k, cfg, cfg.key_base + (uint32_t)at, *adaptive, s->rad_out.get(), tally))) return rc;
-      HIP_TRY(hipMemcpyAsync(out + at, s->rad_out.get(), k * sizeof(SolMoments), hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-  }
-  stats_of(tally, stats);
-  return SOL_OK;
+  return adaptive_entry(s, "sol_irradiance_adaptive", points, n, config, adaptive, out, stats, [&](const SolRadianceConfig& cfg, Tally& tally) {
+    return sol_gather_stage(s, points, keys, n, SOL_GATHER_STAGE_POINTS, out, sizeof(SolMoments), cfg.key_base,
+                            [&](const void* p, const void* k, size_t m, uint32_t key_base, void* o) { return adaptive_launch(s, p, k, m, cfg, key_base, *adaptive, o, tally); });
+  });
 }
 
 int sol_radiance_rescale_dev(SolScene* s, const void* rows_dev, size_t n, uint32_t target_samples, void* out_dev) {
   int rc;
-  if ((rc = rescale_check(s != nullptr, "sol_radiance_rescale_dev", rows_dev, n, target_samples, out_dev)) || n == 0 || (rc = device_check())) return rc;
+  if ((rc = rescale_check(s != nullptr, "sol_radiance_rescale_dev", rows_dev, n, target_samples, out_dev)) || n == 0 || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(sol_launch_radiance_rescale(rows_dev, n, target_samples, out_dev, s->stream));
   return SOL_OK;
@@ -180,9 +155,9 @@ int sol_radiance_rescale_dev(SolScene* s, const void* rows_dev, size_t n, uint32
 
 int sol_radiance_rescale(SolScene* s, const SolRadiance* rows, size_t n, uint32_t target_samples, SolRadiance* out) {
   int rc;
-  if ((rc = rescale_check(s != nullptr, "sol_radiance_rescale", rows, n, target_samples, out)) || n == 0 || (rc = device_check())) return rc;
+  if ((rc = rescale_check(s != nullptr, "sol_radiance_rescale", rows, n, target_samples, out)) || n == 0 || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
-  const size_t cap = std::min(n, STAGE_ROWS);
+  const size_t cap = std::min(n, RESCALE_STAGE_ROWS);
   if ((rc = s->lm_stage.reserve(s->stream, cap * sizeof(SolRadiance)))) return rc;
   for (size_t at = 0; at < n; at += cap) {
     const size_t k = std::min(cap, n - at);

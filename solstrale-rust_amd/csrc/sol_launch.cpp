@@ -226,8 +226,7 @@ int sol_eval(int device, uint32_t fn, const float* in, uint32_t n, uint32_t in_s
   if (in_stride < row_in[fn] || out_stride < row_out[fn])
     return sol_fail(SOL_EINVAL, "sol_eval: function %u reads %u and writes %u floats per row (strides %u / %u)", fn, row_in[fn], row_out[fn], in_stride, out_stride);
   if ((uint64_t)n * std::max(in_stride, out_stride) > (1ull << 32)) return sol_fail(SOL_EINVAL, "sol_eval: more than 2^32 floats");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
+  if (const int rc = sol_device_check()) return rc;
   HIP_TRY(hipSetDevice(device));
   DevPtr<float> din, dout;
   const size_t ib = (size_t)n * in_stride * sizeof(float), ob = (size_t)n * out_stride * sizeof(float);

@@ -11,11 +11,6 @@ namespace {
 constexpr size_t LM_MAX_TRIANGLES = ((size_t)1 << 31) - 2;
 constexpr size_t LM_CTR_WORDS = 16;  // the two list counters, padded so that the owner words stay 64-byte aligned
 
-int device_check() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
-  return SOL_OK;
-}
 int atlas_check(const char* fn, uint32_t width, uint32_t height) {
   if (width == 0 || height == 0 || width > SOL_LIGHTMAP_MAX_SIZE || height > SOL_LIGHTMAP_MAX_SIZE)
     return sol_fail(SOL_EINVAL, "%s: an atlas of %u x %u texels (1 .. %u each way)", fn, width, height, SOL_LIGHTMAP_MAX_SIZE);
@@ -80,11 +75,6 @@ int dilate_launch(SolScene* s, const void* texels, uint32_t width, uint32_t heig
   return SOL_OK;
 }
 
-// the host routes' staging: consecutive arrays in SolScene::lm_stage, each 256-byte aligned
-struct Stage {
-  size_t total = 0;
-  size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; }
-};
 }  // namespace
 
 extern "C" {
@@ -92,7 +82,7 @@ extern "C" {
 int sol_lightmap_points_dev(SolScene* s, const void* vertices_dev, const void* normals_dev, const void* uvs_dev, size_t n_triangles,
                             const SolLightmapConfig* config, void* points_out_dev, void* texels_out_dev) {
   int rc;
-  if ((rc = points_check(s, "sol_lightmap_points_dev", vertices_dev, uvs_dev, n_triangles, config, points_out_dev, texels_out_dev)) || (rc = device_check()))
+  if ((rc = points_check(s, "sol_lightmap_points_dev", vertices_dev, uvs_dev, n_triangles, config, points_out_dev, texels_out_dev)) || (rc = sol_device_check()))
     return rc;
   HIP_TRY(hipSetDevice(s->device));
   return points_launch(s, vertices_dev, normals_dev, uvs_dev, n_triangles, *config, points_out_dev, texels_out_dev);
@@ -101,10 +91,10 @@ int sol_lightmap_points_dev(SolScene* s, const void* vertices_dev, const void* n
 int sol_lightmap_points(SolScene* s, const float* vertices, const float* normals, const float* uvs, size_t n_triangles, const SolLightmapConfig* config,
                         SolRay* points_out, SolTexel* texels_out) {
   int rc;
-  if ((rc = points_check(s, "sol_lightmap_points", vertices, uvs, n_triangles, config, points_out, texels_out)) || (rc = device_check())) return rc;
+  if ((rc = points_check(s, "sol_lightmap_points", vertices, uvs, n_triangles, config, points_out, texels_out)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t n = n_triangles, wh = (size_t)config->width * config->height;
-  Stage st;
+  SolStage st;
   const size_t at_v = st.add(n * 9 * sizeof(float)), at_n = st.add(normals ? n * 9 * sizeof(float) : 0), at_uv = st.add(n * 6 * sizeof(float));
   const size_t at_p = st.add(wh * sizeof(SolRay)), at_t = st.add(wh * sizeof(SolTexel));
   if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
@@ -124,7 +114,7 @@ int sol_lightmap_points(SolScene* s, const float* vertices, const float* normals
 int sol_lightmap_dilate_dev(SolScene* s, const void* texels_dev, uint32_t width, uint32_t height, const void* values_dev, uint32_t channels,
                             uint32_t stride_bytes, uint32_t passes, void* out_dev, void* pass_of_out_dev) {
   int rc;
-  if ((rc = dilate_check(s, "sol_lightmap_dilate_dev", texels_dev, width, height, values_dev, channels, stride_bytes, passes, out_dev)) || (rc = device_check()))
+  if ((rc = dilate_check(s, "sol_lightmap_dilate_dev", texels_dev, width, height, values_dev, channels, stride_bytes, passes, out_dev)) || (rc = sol_device_check()))
     return rc;
   HIP_TRY(hipSetDevice(s->device));
   return dilate_launch(s, texels_dev, width, height, values_dev, channels, stride_bytes, passes, out_dev, pass_of_out_dev);
@@ -133,10 +123,10 @@ int sol_lightmap_dilate_dev(SolScene* s, const void* texels_dev, uint32_t width,
 int sol_lightmap_dilate(SolScene* s, const SolTexel* texels, uint32_t width, uint32_t height, const void* values, uint32_t channels, uint32_t stride_bytes,
                         uint32_t passes, void* out, uint8_t* pass_of_out) {
   int rc;
-  if ((rc = dilate_check(s, "sol_lightmap_dilate", texels, width, height, values, channels, stride_bytes, passes, out)) || (rc = device_check())) return rc;
+  if ((rc = dilate_check(s, "sol_lightmap_dilate", texels, width, height, values, channels, stride_bytes, passes, out)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t wh = (size_t)width * height;
-  Stage st;
+  SolStage st;
   const size_t at_t = st.add(wh * sizeof(SolTexel)), at_v = st.add(wh * stride_bytes), at_o = st.add(wh * stride_bytes), at_p = st.add(wh);
   if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
   char* base = s->lm_stage.get();

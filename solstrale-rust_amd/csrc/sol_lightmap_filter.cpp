@@ -7,12 +7,6 @@
 #include "sol_scene.h"
 
 namespace {
-int device_check() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
-  return SOL_OK;
-}
-
 int filter_check(bool have_scene, const char* fn, const SolLightmapFilterConfig* c, const void* points, const void* texels, const void* values, const void* out) {
   if (!have_scene || !c) return sol_fail(SOL_EINVAL, "%s: null %s", fn, !have_scene ? "scene" : "configuration");
   if (c->size != sizeof(SolLightmapFilterConfig))
@@ -49,10 +43,6 @@ int filter_launch(SolScene* s, const SolLightmapFilterConfig& c, const void* poi
   return SOL_OK;
 }
 
-struct Stage {
-  size_t total = 0;
-  size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; }
-};
 }  // namespace
 
 extern "C" {
@@ -60,17 +50,17 @@ extern "C" {
 int sol_lightmap_filter_dev(SolScene* s, const SolLightmapFilterConfig* config, const void* points_dev, const void* texels_dev, const void* values_dev,
                             void* out_dev) {
   int rc;
-  if ((rc = filter_check(s != nullptr, "sol_lightmap_filter_dev", config, points_dev, texels_dev, values_dev, out_dev)) || (rc = device_check())) return rc;
+  if ((rc = filter_check(s != nullptr, "sol_lightmap_filter_dev", config, points_dev, texels_dev, values_dev, out_dev)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   return filter_launch(s, *config, points_dev, texels_dev, values_dev, out_dev);
 }
 
 int sol_lightmap_filter(SolScene* s, const SolLightmapFilterConfig* config, const SolRay* points, const SolTexel* texels, const void* values, void* out) {
   int rc;
-  if ((rc = filter_check(s != nullptr, "sol_lightmap_filter", config, points, texels, values, out)) || (rc = device_check())) return rc;
+  if ((rc = filter_check(s != nullptr, "sol_lightmap_filter", config, points, texels, values, out)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t wh = (size_t)config->width * config->height, row = config->stride_bytes;
-  Stage st;
+  SolStage st;
   const size_t at_p = st.add(wh * sizeof(SolRay)), at_t = st.add(wh * sizeof(SolTexel)), at_v = st.add(wh * row), at_o = st.add(wh * row);
   if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
   char* base = s->lm_stage.get();

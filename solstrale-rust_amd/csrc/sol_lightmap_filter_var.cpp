@@ -8,12 +8,6 @@
 #include "sol_scene.h"
 
 namespace {
-int device_check() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
-  return SOL_OK;
-}
-
 int filter_var_check(bool have_scene, const char* fn, const SolLightmapFilterVarConfig* c, const void* points, const void* texels, const void* moments,
                      const void* out, const void* variance_out) {
   if (!have_scene || !c) return sol_fail(SOL_EINVAL, "%s: null %s", fn, !have_scene ? "scene" : "configuration");
@@ -54,10 +48,6 @@ int filter_var_launch(SolScene* s, const SolLightmapFilterVarConfig& c, const vo
   return SOL_OK;
 }
 
-struct Stage {
-  size_t total = 0;
-  size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; }
-};
 }  // namespace
 
 extern "C" {
@@ -66,7 +56,7 @@ int sol_lightmap_filter_var_dev(SolScene* s, const SolLightmapFilterVarConfig* c
                                 void* out_dev, void* variance_out_dev) {
   int rc;
   if ((rc = filter_var_check(s != nullptr, "sol_lightmap_filter_var_dev", config, points_dev, texels_dev, moments_dev, out_dev, variance_out_dev)) ||
-      (rc = device_check()))
+      (rc = sol_device_check()))
     return rc;
   HIP_TRY(hipSetDevice(s->device));
   return filter_var_launch(s, *config, points_dev, texels_dev, moments_dev, out_dev, variance_out_dev);
@@ -75,10 +65,10 @@ int sol_lightmap_filter_var_dev(SolScene* s, const SolLightmapFilterVarConfig* c
 int sol_lightmap_filter_var(SolScene* s, const SolLightmapFilterVarConfig* config, const SolRay* points, const SolTexel* texels, const SolMoments* moments,
                             SolRadiance* out, float* variance_out) {
   int rc;
-  if ((rc = filter_var_check(s != nullptr, "sol_lightmap_filter_var", config, points, texels, moments, out, variance_out)) || (rc = device_check())) return rc;
+  if ((rc = filter_var_check(s != nullptr, "sol_lightmap_filter_var", config, points, texels, moments, out, variance_out)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t wh = (size_t)config->width * config->height;
-  Stage st;
+  SolStage st;
   const size_t at_p = st.add(wh * sizeof(SolRay)), at_t = st.add(wh * sizeof(SolTexel)), at_m = st.add(wh * sizeof(SolMoments));
   const size_t at_o = st.add(wh * sizeof(SolRadiance)), at_v = st.add(variance_out ? wh * 16 : 0);
   if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;

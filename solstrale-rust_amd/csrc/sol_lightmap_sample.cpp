@@ -10,12 +10,6 @@ namespace {
 constexpr size_t LS_MAX_TRIANGLES = ((size_t)1 << 31) - 2;
 constexpr size_t LS_MAX_ROWS = (size_t)1 << 31;
 
-int device_check() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
-  return SOL_OK;
-}
-
 int coords_check(bool have_scene, const char* fn, const void* hits, size_t n, const void* table, size_t n_dfs, const void* out) {
   if (!have_scene) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
   if (n > LS_MAX_ROWS) return sol_fail(SOL_EINVAL, "%s: %zu hits in one call (at most 2^31)", fn, n);
@@ -52,11 +46,6 @@ int sample_check(bool have_scene, const char* fn, const SolLightmapSampleConfig*
   return SOL_OK;
 }
 
-// the host routes' staging: consecutive arrays in SolScene::lm_stage, each 256-byte aligned
-struct Stage {
-  size_t total = 0;
-  size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; }
-};
 }  // namespace
 
 extern "C" {
@@ -65,7 +54,7 @@ int sol_lightmap_coords_dev(SolScene* s, const void* hits_dev, size_t n, const v
   int rc;
   if ((rc = coords_check(s != nullptr, "sol_lightmap_coords_dev", hits_dev, n, triangle_of_dfs_dev, n_dfs, coords_out_dev))) return rc;
   if (n == 0) return SOL_OK;
-  if ((rc = device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(sol_launch_lightmap_coords(hits_dev, (uint32_t)n, triangle_of_dfs_dev, (uint32_t)n_dfs, coords_out_dev, s->stream));
   return SOL_OK;
@@ -75,9 +64,9 @@ int sol_lightmap_coords(SolScene* s, const SolRayHit* hits, size_t n, const uint
   int rc;
   if ((rc = coords_check(s != nullptr, "sol_lightmap_coords", hits, n, triangle_of_dfs, n_dfs, coords_out))) return rc;
   if (n == 0) return SOL_OK;
-  if ((rc = device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
-  Stage st;
+  SolStage st;
   const size_t at_h = st.add(n * sizeof(SolRayHit)), at_t = st.add(n_dfs * sizeof(uint32_t)), at_o = st.add(n * sizeof(SolTexel));
   if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
   char* base = s->lm_stage.get();
@@ -97,7 +86,7 @@ int sol_lightmap_sample_dev(SolScene* s, const SolLightmapSampleConfig* config, 
                          out_dev)))
     return rc;
   if (n == 0) return SOL_OK;
-  if ((rc = device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(sol_launch_lightmap_sample(*config, (uint32_t)n_triangles, uvs_dev, texels_dev, pass_of_dev, values_dev, vertices_dev, points_dev, coords_dev,
                                      (uint32_t)n, out_dev, s->stream));
@@ -109,10 +98,10 @@ int sol_lightmap_sample(SolScene* s, const SolLightmapSampleConfig* config, cons
   int rc;
   if ((rc = sample_check(s != nullptr, "sol_lightmap_sample", config, uvs, n_triangles, texels, values, vertices, points, coords, n, out))) return rc;
   if (n == 0) return SOL_OK;
-  if ((rc = device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t wh = (size_t)config->width * config->height, row = config->stride_bytes, out_row = ((size_t)config->channels + 1) * 4, nt = n_triangles;
-  Stage st;
+  SolStage st;
   const size_t at_uv = st.add(nt * 6 * sizeof(float)), at_t = st.add(wh * sizeof(SolTexel)), at_pass = st.add(pass_of ? wh : 0), at_v = st.add(wh * row);
   const size_t at_vx = st.add(vertices ? nt * 9 * sizeof(float) : 0), at_p = st.add(points ? wh * sizeof(SolRay) : 0), at_c = st.add(n * sizeof(SolTexel));
   const size_t at_o = st.add(n * out_row);

@@ -12,6 +12,7 @@
 //   sol_lightmap.cpp sol_lightmap_points / sol_lightmap_dilate: lightmap UVs rasterised into gather points, chart borders dilated (sol_lightmap.hip)
 //   sol_lightmap_filter.cpp sol_lightmap_filter: chart-aware a-trous filtering of a baked atlas (sol_lightmap_filter.hip)
 //   sol_lightmap_filter_var.cpp sol_lightmap_filter_var: the same under the guidance of the per-texel variance sol_irradiance_moments gathers (sol_lightmap_filter_var.hip)
+//   sol_gather.h/.cpp what the radiance queries and the gather families share: configuration checks, entry shape, slice / window launch plan, staged host route
 //   sol_gather_adaptive.cpp sol_irradiance_adaptive / sol_radiance_rescale: rounds of an irradiance-moments gather over the points still active (sol_gather_adaptive.hip)
 //   sol_volume.cpp  sol_volume_points / sol_volume_build / sol_volume_sample: a probe grid laid out, packed and sampled (sol_volume.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
@@ -107,6 +108,13 @@ struct SolSceneMirror {
   }
 };
 #define SOL_MAX_ITEMS 0xFF000000ull
+// SOL_EDEVICE "no HIP device available" unless there is one (sol_api.cpp); *n_devices: how many.
+int sol_device_check(int* n_devices = nullptr);
+// The staging of a host route: consecutive arrays in one buffer, each 256-byte aligned. add: the offset of the next one.
+struct SolStage {
+  size_t total = 0;
+  size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; }
+};
 
 // Developer overrides: environment variables for experiments and A/B runs, parsed by sol_dev_overrides() - the
 // only getenv site of the library - once per sol_scene_create / sol_world_tree_check; nothing on the launch path reads the environment.
@@ -306,11 +314,12 @@ struct SolScene {
   // the spill area of the query kernel's own grid. None of them is the render launch's.
   DevBuf<SolRay> query_in; DevBuf<SolRayHit> query_out;
   DevBuf<uint32_t> query_spill;
-  // Radiance queries (sol_radiance.hip): their own work counter, partial buffer (chunk sums, 16 bytes per (chunk, ray); grown on
-  // demand up to a bound), spill tail and host-route staging (rays, keys, answers; rad_cap rays each). None of them is the render launch's.
-  // The SH irradiance queries share all of it: a row of rad_partial is then the colour of one (sample, point), under the same
-  // bound but never below 1024 rows, and rad_out holds seven rows per staged point. So do the visibility gathers (sol_visibility.hip, DESIGN.md
-  // 22): a chunk's row takes two rows of rad_partial, a staged answer two of rad_out.
+  // Radiance queries (sol_radiance.hip) and every gather family built on them (sol_gather.h): their own work counter, partial buffer
+  // (rows of 16 bytes, grown on demand up to the bound), spill tail and host-route staging (rays or points, keys, answers). None of them is the
+  // render launch's. rad_partial has two uses. Chunk sums (radiance, irradiance; visibility): one row - visibility: two - per (chunk, point).
+  // Per sample (SH, moments; depth): one row - depth: a word, four to a row - per (sample, point), under the same bound counted in those values
+  // but never below one group of 64 points over one chunk. rad_out holds whole rows per staged point: 1, 7 (SolSh9), 2 (SolMoments, SolVisibility)
+  // or res x res (SolOctTexel).
   DevBuf<uint32_t> rad_work;
   DevBuf<SolRadiance> rad_partial;
   size_t rad_partial_max_rows = (size_t)1 << 24;  // the bound: 256 MiB of chunk sums (SOL_RADIANCE_ROWS)
@@ -334,8 +343,7 @@ struct SolScene {
   // measured alternative (SOL_VOLUME_SAMPLE=loadall).
   DevBuf<char> vol_stage;
   bool vol_load_all = false;
-  // Directional distance moments (sol_depth.hip) share the radiance queries' buffers: a row of rad_partial holds the words of four
-  // (sample, point) pairs under the same bound counted in words, rad_out res x res rows per staged point; build and sample stage through vol_stage.
+  // Directional distance moments (sol_depth.hip): the gather runs through rad_*, build and sample stage through vol_stage.
   // depth_project_plain: the projection kernel's measured alternative (SOL_DEPTH_PROJECT=plain).
   bool depth_project_plain = false;
   // Adaptive irradiance gathers (sol_gather_adaptive.hip). The rounds run through the irradiance queries' buffers above; these are
@@ -371,16 +379,7 @@ inline int sol_scene_to_device(SolScene* s) { return s->mirror.upload(s->stream,
 // grid x SOL_WG x (stack_need - lds_depth) words, 16 when the searches fit the kernel's LDS stack.
 int sol_launch_plan(SolScene* s, int blocks_per_cu, uint64_t items, uint32_t lds_depth, uint32_t stack_need, DevBuf<uint32_t>& spill, uint32_t* grid);
 int sol_set_partition(SolScene* s, int rank, int world);
-// What sol_depth.cpp shares with the calls it extends. sol_gather_config_check (sol_api.cpp): the SolIrradianceConfig and n as sol_irradiance judge
-// them, in its order and words; *cfg is the configuration as the launches take it. sol_query_medium_check (sol_api.cpp): sol_query's refusal of a
-// constant medium. sol_volume_grid_check (sol_volume.cpp): what every volume call refuses about the scene pointer and the grid, in the header's order.
-int sol_gather_config_check(const char* fn, size_t n, const SolIrradianceConfig* config, SolRadianceConfig* cfg);
-int sol_query_medium_check(const SolScene* s, const char* fn);
-// What sol_gather_adaptive.cpp shares with sol_irradiance_moments (sol_api.cpp): its launches over n <= 2^31 points (and keys, or null) in device
-// memory, n SolMoments out, on the scene's stream. carry: the projection adds onto what `out` holds from the first window on - the rows' sums of
-// earlier rounds -, and writes total_samples as the rows' count instead of cfg.samples.
-int sol_irradiance_moments_launch(SolScene* s, const void* points_dev, const void* keys_dev, size_t n, const SolRadianceConfig& cfg, uint32_t key_base, void* out_dev,
-                                  bool carry, uint32_t total_samples);
+// What every volume call refuses about the scene pointer and the grid, in the header's order (sol_volume.cpp; sol_depth.cpp shares it).
 int sol_volume_grid_check(bool have_scene, const char* fn, const SolVolumeGrid* g);
 
 // One launch of sol_render_impl (sol_launch.cpp): what differs between its callers, and nothing else - the handle supplies what is not per launch

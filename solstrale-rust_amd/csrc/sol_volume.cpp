@@ -9,12 +9,6 @@
 namespace {
 constexpr size_t VOL_MAX_POINTS = (size_t)1 << 31;
 
-int device_check() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return sol_fail(SOL_EDEVICE, "no HIP device available");
-  return SOL_OK;
-}
-
 // what all three calls refuse, in the header's order
 int grid_check(bool have_scene, const char* fn, const SolVolumeGrid* g) {
   if (!have_scene || !g) return sol_fail(SOL_EINVAL, "%s: null %s", fn, !have_scene ? "scene" : "grid");
@@ -56,18 +50,13 @@ int sol_volume_grid_check(bool have_scene, const char* fn, const SolVolumeGrid* 
 namespace {
 size_t probes_of(const SolVolumeGrid& g) { return (size_t)g.nx * g.ny * g.nz; }
 
-// the host routes' staging: consecutive arrays in SolScene::vol_stage, each 256-byte aligned
-struct Stage {
-  size_t total = 0;
-  size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; }
-};
 }  // namespace
 
 extern "C" {
 
 int sol_volume_points_dev(SolScene* s, const SolVolumeGrid* grid, float tmin, float tmax, void* points_out_dev) {
   int rc;
-  if ((rc = points_check(s != nullptr, "sol_volume_points_dev", grid, tmin, tmax, points_out_dev)) || (rc = device_check())) return rc;
+  if ((rc = points_check(s != nullptr, "sol_volume_points_dev", grid, tmin, tmax, points_out_dev)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(sol_launch_volume_points(*grid, tmin, tmax, points_out_dev, s->stream));
   return SOL_OK;
@@ -75,7 +64,7 @@ int sol_volume_points_dev(SolScene* s, const SolVolumeGrid* grid, float tmin, fl
 
 int sol_volume_points(SolScene* s, const SolVolumeGrid* grid, float tmin, float tmax, SolRay* points_out) {
   int rc;
-  if ((rc = points_check(s != nullptr, "sol_volume_points", grid, tmin, tmax, points_out)) || (rc = device_check())) return rc;
+  if ((rc = points_check(s != nullptr, "sol_volume_points", grid, tmin, tmax, points_out)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t bytes = probes_of(*grid) * sizeof(SolRay);
   if ((rc = s->vol_stage.reserve(s->stream, bytes))) return rc;
@@ -87,7 +76,7 @@ int sol_volume_points(SolScene* s, const SolVolumeGrid* grid, float tmin, float 
 
 int sol_volume_build_dev(SolScene* s, const SolVolumeGrid* grid, const void* sh_dev, const void* visibility_dev, float radius, void* probes_out_dev) {
   int rc;
-  if ((rc = build_check(s != nullptr, "sol_volume_build_dev", grid, sh_dev, probes_out_dev)) || (rc = device_check())) return rc;
+  if ((rc = build_check(s != nullptr, "sol_volume_build_dev", grid, sh_dev, probes_out_dev)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(sol_launch_volume_build((uint32_t)probes_of(*grid), sh_dev, visibility_dev, radius, probes_out_dev, s->stream));
   return SOL_OK;
@@ -95,10 +84,10 @@ int sol_volume_build_dev(SolScene* s, const SolVolumeGrid* grid, const void* sh_
 
 int sol_volume_build(SolScene* s, const SolVolumeGrid* grid, const SolSh9* sh, const SolVisibility* visibility, float radius, SolProbe* probes_out) {
   int rc;
-  if ((rc = build_check(s != nullptr, "sol_volume_build", grid, sh, probes_out)) || (rc = device_check())) return rc;
+  if ((rc = build_check(s != nullptr, "sol_volume_build", grid, sh, probes_out)) || (rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t n = probes_of(*grid);
-  Stage st;
+  SolStage st;
   const size_t at_sh = st.add(n * sizeof(SolSh9)), at_vis = st.add(visibility ? n * sizeof(SolVisibility) : 0), at_out = st.add(n * sizeof(SolProbe));
   if ((rc = s->vol_stage.reserve(s->stream, st.total))) return rc;
   char* base = s->vol_stage.get();
@@ -114,7 +103,7 @@ int sol_volume_sample_dev(SolScene* s, const SolVolumeGrid* grid, const void* pr
   int rc;
   if ((rc = sample_check(s != nullptr, "sol_volume_sample_dev", grid, probes_dev, points_dev, n, out_dev))) return rc;
   if (n == 0) return SOL_OK;
-  if ((rc = device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   HIP_TRY(sol_launch_volume_sample(*grid, s->vol_load_all, probes_dev, points_dev, (uint32_t)n, out_dev, s->stream));
   return SOL_OK;
@@ -124,10 +113,10 @@ int sol_volume_sample(SolScene* s, const SolVolumeGrid* grid, const SolProbe* pr
   int rc;
   if ((rc = sample_check(s != nullptr, "sol_volume_sample", grid, probes, points, n, out))) return rc;
   if (n == 0) return SOL_OK;
-  if ((rc = device_check())) return rc;
+  if ((rc = sol_device_check())) return rc;
   HIP_TRY(hipSetDevice(s->device));
   const size_t np = probes_of(*grid);
-  Stage st;
+  SolStage st;
   const size_t at_probes = st.add(np * sizeof(SolProbe)), at_points = st.add(n * sizeof(SolRay)), at_out = st.add(n * sizeof(SolRadiance));
   if ((rc = s->vol_stage.reserve(s->stream, st.total))) return rc;
   char* base = s->vol_stage.get();

@@ -278,18 +278,25 @@ def test_a_normal_whose_squared_length_underflows_is_counted_nowhere_and_the_cal
 # ---- 6. the splits --------------------------------------------------------------------------------------------------------------------------
 def test_a_bounded_partial_buffer_gives_the_default_bound_s_bits(monkeypatch):
     """SOL_RADIANCE_ROWS = 128 is 64 visibility rows: 300 points x 80 samples (five chunks) run as five slices of 64 points, each in five
-    windows of one chunk carried on by the resolve kernel."""
+    windows of one chunk carried on by the resolve kernel. SOL_RADIANCE_ROWS = 256 is 128 rows: 40 samples (three chunks, the last one short)
+    run in slices of 64 points, each in a window of two chunks and one of the short chunk alone."""
     sc = _cornell()
     calls = [dict(mode="cosine", distances=True), dict(mode="sphere", distances=False)]
     with DeviceScene(sc) as ds:
         points = hit_points(sc, ds, 300)
         points[::2, 7] = 150.0
         want = [ds.visibility(points, samples=80, first_sample=3, seed=SEED, key_base=40, **kw) for kw in calls]
+        want40 = [ds.visibility(points, samples=40, first_sample=3, seed=SEED, key_base=40, **kw) for kw in calls]
         assert 0 < want[0]["hits"].sum() < 80 * 300 and (want[0]["t_sum"] > 0).any()
+        assert 0 < want40[0]["hits"].sum() < 40 * 300 and (want40[0]["t_sum"] > 0).any()
     monkeypatch.setenv("SOL_RADIANCE_ROWS", "128")
     with DeviceScene(sc) as ds:
         for kw, w in zip(calls, want):
             assert_rows_equal(ds.visibility(points, samples=80, first_sample=3, seed=SEED, key_base=40, **kw), w, kw)
+    monkeypatch.setenv("SOL_RADIANCE_ROWS", "256")
+    with DeviceScene(sc) as ds:
+        for kw, w in zip(calls, want40):
+            assert_rows_equal(ds.visibility(points, samples=40, first_sample=3, seed=SEED, key_base=40, **kw), w, (40, kw))
 
 
 # ---- 7. routes ------------------------------------------------------------------------------------------------------------------------------

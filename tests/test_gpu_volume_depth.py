@@ -187,7 +187,9 @@ def test_a_normal_whose_squared_length_underflows_adds_nothing_and_the_call_retu
 @pytest.mark.parametrize("project", ["wave", "plain"])
 def test_a_bounded_partial_buffer_and_both_projection_kernels_give_the_default_s_bits(project, monkeypatch):
     """SOL_RADIANCE_ROWS = 128 words is less than one group of points over one chunk: 300 points x 80 samples (five chunks) run as five slices of 64
-    points, each in five windows of one chunk which the projection kernel carries on in `out`."""
+    points, each in five windows of one chunk which the projection kernel carries on in `out`. SOL_RADIANCE_ROWS = 2048 words is two such units
+    (wave projection only): 40 samples (three chunks, the last one short) run in slices of 64 points, each in a window of two chunks and one of
+    the short chunk alone."""
     sc = _cornell()
     calls = [dict(res=4, sharpness_log2=5, mode="sphere"), dict(res=8, sharpness_log2=6, mode="cosine"), dict(res=16, sharpness_log2=0, mode="sphere")]
     with DeviceScene(sc) as ds:
@@ -195,12 +197,19 @@ def test_a_bounded_partial_buffer_and_both_projection_kernels_give_the_default_s
         pts[::2, 7] = 150.0
         want = [ds.visibility_oct(pts, samples=80, first_sample=3, seed=SEED, key_base=40, **kw) for kw in calls]
         assert all((w[..., 2] > 0).any() and (w[..., 1] > 0).any() for w in want)
+        if project == "wave":
+            want40 = ds.visibility_oct(pts, samples=40, first_sample=3, seed=SEED, key_base=40, **calls[1])
+            assert (want40[..., 2] > 0).any() and (want40[..., 1] > 0).any()
     monkeypatch.setenv("SOL_RADIANCE_ROWS", "128")
     if project == "plain":
         monkeypatch.setenv("SOL_DEPTH_PROJECT", "plain")
     with DeviceScene(sc) as ds:
         for kw, w in zip(calls, want):
             assert_maps_equal(ds.visibility_oct(pts, samples=80, first_sample=3, seed=SEED, key_base=40, **kw), w, (project, kw))
+    if project == "wave":
+        monkeypatch.setenv("SOL_RADIANCE_ROWS", "2048")
+        with DeviceScene(sc) as ds:
+            assert_maps_equal(ds.visibility_oct(pts, samples=40, first_sample=3, seed=SEED, key_base=40, **calls[1]), want40, (project, 40, calls[1]))
 
 
 def test_device_tensors_host_arrays_and_another_stream_give_the_same_bytes(cornell_case):
