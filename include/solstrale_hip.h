@@ -1311,6 +1311,71 @@ int sol_lightmap_sample(SolScene* scene, const SolLightmapSampleConfig* config, 
                         const uint8_t* pass_of, const void* values, const float* vertices, const SolRay* points, const SolTexel* coords, size_t n,
                         void* out);
 
+/* ---- directional lightmaps: an atlas of SolSh9 rows shaded at the caller's normals (EXTENSION, not in the reference) ----------
+ * sol_lightmap_points -> sol_irradiance_sh -> sol_lightmap_filter -> sol_lightmap_dilate bake an atlas of nine SH terms per channel;
+ * sol_lightmap_sh looks it up at surface rows as sol_lightmap_sample does and evaluates the irradiance E(n) at a normal per row - a normal-mapped
+ * surface lit from a baked atlas, on device memory. sol_lightmap_normals gives the surface's own normals for rows that have none. Nothing is
+ * traced and the scene is never read: a scene with a constant medium is served. All arithmetic is fp32, every operation rounded once, no fused
+ * multiply-add, `/` and sqrtf correctly rounded, every clamp a comparison, finite(x) = the exponent field is not all ones;
+ * csrc/sol_lightmap_sh.h is the rule as code and tests/lightmap_sh_ref.py its restatement in numpy.
+ *   Lookup.   Surface row, row validity, atlas coordinates, taps, liveness, chart guard and nearest mode are sol_lightmap_sample's above, word for
+ *             word, with channels fixed at 27 and a value row of stride_bytes (>= 112, a multiple of 16) that starts with a SolSh9's c[9][3]: a tap
+ *             is live only when all 27 of its value words are finite. Word 27 of a row (SolSh9.samples) never enters a value and is never judged.
+ *             L[w] = sum / wsum, sum = ((0 + (w_a * x_a)) + (w_b * x_b)) .. and wsum = ((0 + w_a) + w_b) .. over the live taps in tap order,
+ *             w = 3k + channel; with SOL_LIGHTMAP_SH_NEAREST the one tap's words are copied. count = the number of live taps (0..4), 0 unless
+ *             wsum > 0.
+ *   Evaluation. n = the row of `normals` (x, y, z, unused) as it comes; it is NOT normalised. Y_k(n) is the basis of sol_irradiance_sh above
+ *             (csrc/sol_sh.h), B_k = A_k * Y_k one product with A = the fp32 roundings of pi (k = 0), 2 pi / 3 (k = 1..3), pi / 4 (k = 4..8) - the
+ *             cosine lobe's zonal factors. Per channel t_k = B_k * L[3k + channel], E = ((0 + t_0) + t_1) .. + t_8 in k order, then
+ *             E = E * scale, then with SOL_LIGHTMAP_SH_CLAMP E = E > 0 ? E : 0 (NaN becomes 0). The answer is a SolRadiance (E_r, E_g, E_b,
+ *             count). `scale` is the caller's: 4 pi / samples for a SPHERE-mode sol_irradiance_sh bake whose rows are sums.
+ *   Zeros.    Four zero words for an invalid row; when no tap is live or wsum is not > 0; when a word of n is not finite; when
+ *             ((n.x * n.x) + (n.y * n.y)) + (n.z * n.z) is not a finite, non-zero, non-subnormal number.
+ *   Coefficients. With SOL_LIGHTMAP_SH_COEFFICIENTS no normal is read (normals may be NULL) and no scale is applied (it is not looked at): the
+ *             answer is 28 words a row - the 27 L[w], then count - bit for bit what sol_lightmap_sample answers with channels = 27 over the same
+ *             arguments.
+ *   Normals.  sol_lightmap_normals writes n rows (nx, ny, nz, 0) for n surface rows by sol_lightmap_points' rule: b0 = (1 - b1) - b2;
+ *             g = cross(v1 - v0, v2 - v0), each component (a * b) - (c * d); with vertex normals m = ((n0 * b0) + (n1 * b1)) + (n2 * b2) per
+ *             component replaces g when ((m.x * m.x) + (m.y * m.y)) + (m.z * m.z) is finite, non-zero and not subnormal; the vector is divided,
+ *             component by component, by the sqrtf of its squared length. Four zero words: flags == 0, triangle == SOL_TEXEL_NONE or
+ *             >= n_triangles, b1 or b2 not finite; one of the nine vertex words, or of the nine normal words where given, not finite; a squared
+ *             length of the vector that would be normalised that is not finite, zero or subnormal.
+ * Neutral as the queries are: no accumulator, plane, counter or statistic is touched; calls are ordered by the handle's stream.
+ * SOL_EINVAL (sol_last_error names the call and the reason), before the device is looked for and in this order. sol_lightmap_sh: a null scene; a
+ * null configuration; a wrong size; reserved != 0; unknown flags; CLAMP together with COEFFICIENTS; width or height of 0 or above 16384; a stride
+ * below 112 or no multiple of 16; a chart_radius that is NaN or not > 0; exactly one of vertices / points given; a finite chart_radius with
+ * neither; a scale that is not finite (unless COEFFICIENTS); n_triangles > 2^31 - 2; n > 2^31; a null UV (with n_triangles > 0), texel, value or
+ * coordinate pointer; a null normals pointer (unless COEFFICIENTS); a null output pointer; out == values, coords or normals.
+ * sol_lightmap_normals: a null scene; n_triangles > 2^31 - 2; n > 2^31; with n_triangles > 0 a null vertex pointer; a null coords or output
+ * pointer; out == coords. Then n == 0 succeeds and writes nothing. SOL_EDEVICE without a GPU comes after all of these. There is no host mirror
+ * (DESIGN.md 15). */
+#define SOL_LIGHTMAP_SH_NEAREST 1u
+#define SOL_LIGHTMAP_SH_COEFFICIENTS 2u
+#define SOL_LIGHTMAP_SH_CLAMP 4u
+/* 32 bytes: size 0, width 4, height 8, stride_bytes 12, flags 16, chart_radius 20, scale 24, reserved 28 */
+typedef struct SolLightmapShConfig {
+  uint32_t size, width, height, stride_bytes, flags; /* size = sizeof(SolLightmapShConfig); flags: SOL_LIGHTMAP_SH_* */
+  float chart_radius, scale;                         /* a world length, > 0; +inf: no chart guard. scale: finite, the caller's factor on E */
+  uint32_t reserved;                                 /* zero */
+} SolLightmapShConfig;
+/* Device pointers (the atlas arguments of sol_lightmap_sample_dev; n SolTexel surface rows and n rows of four floats (x, y, z, unused) in; n
+ * SolRadiance out, or n rows of 28 words with COEFFICIENTS; values, normals, coords, texels, points and out 16-byte aligned), on the scene's
+ * stream, asynchronous. */
+int sol_lightmap_sh_dev(SolScene* scene, const SolLightmapShConfig* config, const void* uvs_dev, size_t n_triangles, const void* texels_dev,
+                        const void* pass_of_dev, const void* values_dev, const void* vertices_dev, const void* points_dev, const void* coords_dev,
+                        const void* normals_dev, size_t n, void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_sh(SolScene* scene, const SolLightmapShConfig* config, const float* uvs, size_t n_triangles, const SolTexel* texels,
+                    const uint8_t* pass_of, const void* values, const float* vertices, const SolRay* points, const SolTexel* coords,
+                    const float* normals, size_t n, void* out);
+/* Device pointers (n SolTexel surface rows; n_triangles x 9 floats; as many vertex-normal floats or NULL; n rows of four floats out; coords and
+ * out 16-byte aligned), on the scene's stream, asynchronous. */
+int sol_lightmap_normals_dev(SolScene* scene, const void* coords_dev, size_t n, const void* vertices_dev, const void* vertex_normals_dev,
+                             size_t n_triangles, void* normals_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_normals(SolScene* scene, const SolTexel* coords, size_t n, const float* vertices, const float* vertex_normals, size_t n_triangles,
+                         float* normals_out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

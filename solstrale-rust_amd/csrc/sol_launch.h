@@ -163,6 +163,15 @@ struct SolLightmapSampleConfig;
 hipError_t sol_launch_lightmap_sample(const SolLightmapSampleConfig& c, uint32_t n_triangles, const void* uvs, const void* texels, const void* pass_of,
                                       const void* values, const void* vertices, const void* points, const void* coords, uint32_t n, void* out,
                                       hipStream_t stream);
+// ---- sol_lightmap_sh.hip: directional lightmaps. sh: n surface rows and n normal rows (x, y, z, unused; null in coefficient mode)
+// in, n SolRadiance out - or, with SOL_LIGHTMAP_SH_COEFFICIENTS, n rows of 28 words; the atlas arguments are sol_launch_lightmap_sample's with
+// rows of 27 coefficients. normals: n surface rows in, n rows (nx, ny, nz, 0) out; vertex_normals or null ----
+struct SolLightmapShConfig;
+hipError_t sol_launch_lightmap_sh(const SolLightmapShConfig& c, uint32_t n_triangles, const void* uvs, const void* texels, const void* pass_of,
+                                  const void* values, const void* vertices, const void* points, const void* coords, const void* normals, uint32_t n,
+                                  void* out, hipStream_t stream);
+hipError_t sol_launch_lightmap_normals(const void* coords, uint32_t n, const void* vertices, const void* vertex_normals, uint32_t n_triangles, void* out,
+                                       hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

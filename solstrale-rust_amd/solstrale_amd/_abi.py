@@ -274,6 +274,17 @@ class SolLightmapSampleConfig(C.Structure):
 SOL_LIGHTMAP_SAMPLE_NEAREST, SOL_LIGHTMAP_TABLE_ROTATION_SHIFT, SOL_LIGHTMAP_TABLE_TRIANGLE_MASK = 1, 30, 0x3FFFFFFF
 
 
+class SolLightmapShConfig(C.Structure):
+    """EXTENSION: the configuration of sol_lightmap_sh: size = sizeof, W x H texels, the stride of the SolSh9 rows (>= 112, a
+    multiple of 16), flags (SOL_LIGHTMAP_SH_*), the radius of the chart guard (> 0; +inf: off), the caller's factor on E, reserved = 0. 32 bytes.
+    Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("stride_bytes", C.c_uint32), ("flags", C.c_uint32),
+                ("chart_radius", C.c_float), ("scale", C.c_float), ("reserved", C.c_uint32)]
+
+
+SOL_LIGHTMAP_SH_NEAREST, SOL_LIGHTMAP_SH_COEFFICIENTS, SOL_LIGHTMAP_SH_CLAMP = 1, 2, 4
+
+
 class SolLightmapFilterConfig(C.Structure):
     """EXTENSION: the configuration of sol_lightmap_filter: size = sizeof, W x H texels, 1..8 passes, the normal factor's exponent as a
     power of two (0..7), the rows' channels and stride, the widths of the distance, plane and value factors (>= 1e-6 or +inf), the scale a value is
@@ -493,6 +504,11 @@ def load_hip():
                                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_lightmap_sample", C.c_int, [P, C.POINTER(SolLightmapSampleConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    for name in ("sol_lightmap_sh_dev", "sol_lightmap_sh"):
+        _sig(lib, name, C.c_int, [P, C.POINTER(SolLightmapShConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_lightmap_normals_dev", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_lightmap_normals", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -541,6 +557,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_irradiance_moments_dev", "sol_irradiance_moments", "sol_lightmap_filter_var_dev", "sol_lightmap_filter_var",
                "sol_irradiance_adaptive_dev", "sol_irradiance_adaptive", "sol_radiance_rescale_dev", "sol_radiance_rescale",
                "sol_lightmap_coords_dev", "sol_lightmap_coords", "sol_lightmap_sample_dev", "sol_lightmap_sample",
+               "sol_lightmap_sh_dev", "sol_lightmap_sh", "sol_lightmap_normals_dev", "sol_lightmap_normals",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

@@ -1076,6 +1076,113 @@ class DeviceScene:
         out = self.lightmap_sample(values, coords, uvs, texels, width, height, **sample_args)
         return out.reshape(h, w, -1)
 
+    # ---- directional lightmaps (EXTENSION) ----
+    def _device_pointer(self, name, x, dtype, shape):
+        """The address of a device tensor argument (None: none), after its dtype, layout, device and shape (None: any extent) are checked."""
+        if x is None:
+            return None
+        if (not hasattr(x, "data_ptr") or x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or x.device.index != self.device
+                or len(shape) != x.dim() or any(s is not None and s != d for s, d in zip(shape, x.shape))):
+            raise ValueError(f"{name}: a contiguous {dtype} tensor of shape {list(shape)} on the scene's device")
+        return C.c_void_p(x.data_ptr())
+
+    def lightmap_sh(self, values, coords, normals, uvs, texels, width, height, scale=1.0, pass_of=None, nearest=False, chart_radius=None, vertices=None,
+                    points=None, clamp=False, coefficients=False):
+        """sol_lightmap_sh: the baked atlas `values` of SolSh9 rows (`width * height` rows of 28 words or more, a multiple of 4: what
+        irradiance_sh, lightmap_filter and lightmap_dilate(channels=27) returned) looked up at the surface rows `coords` exactly as
+        lightmap_sample(channels=27) does, and evaluated as irradiance at `normals` [n, 4] (x, y, z, unused; taken as they come, not normalised):
+        E = scale * sum_k A_k Y_k(n) L_k per channel, with clamp=True no less than 0. scale: 4 pi / samples for an irradiance_sh(mode="sphere")
+        bake. Returns [n, 4] float32 rows (E_r, E_g, E_b, the bits of the number of live taps); a row without a live tap or with a normal that is
+        not finite, zero or subnormal in length is zero. coefficients=True: no normals (None), no scale - the [n, 28] rows lightmap_sample
+        (channels=27) answers, from the eight-lanes-to-a-row kernel. Host arrays go the host route, device tensors the device route, decided by
+        `values`."""
+        width, height = int(width), int(height)
+        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
+        flags = ((_abi.SOL_LIGHTMAP_SH_NEAREST if nearest else 0) | (_abi.SOL_LIGHTMAP_SH_COEFFICIENTS if coefficients else 0)
+                 | (_abi.SOL_LIGHTMAP_SH_CLAMP if clamp else 0))
+        cfg = _abi.SolLightmapShConfig(size=C.sizeof(_abi.SolLightmapShConfig), width=width, height=height, stride_bytes=4 * k, flags=flags,
+                                       chart_radius=float("inf") if chart_radius is None else float(chart_radius), scale=float(scale))
+        out_words = 28 if coefficients else 4
+        wh = width * height
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
+            def host(x, dtype=None):
+                return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
+            v, u, vx, p, nr = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32), host(normals, np.float32)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
+            po = host(pass_of, np.uint8)
+            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
+                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or (vx is not None and vx.shape != (u.shape[0], 3, 3))
+                    or (p is not None and p.shape != (wh, 8)) or (nr is not None and nr.shape != (c.shape[0], 4))):
+                raise ValueError("values: [width * height, k] float32 rows; texels, coords: LIGHTMAP_TEXEL_DTYPE rows; normals: [n, 4]; uvs: [n, 3, 2]; "
+                                 "pass_of: width * height bytes; vertices: [n, 3, 3]; points: [width * height, 8]")
+            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
+            self._chk(self.lib.sol_lightmap_sh(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
+                                               None if po is None else po.ctypes.data, v.ctypes.data, None if vx is None else vx.ctypes.data,
+                                               None if p is None else p.ctypes.data, c.ctypes.data, None if nr is None else nr.ctypes.data, c.shape[0],
+                                               out.ctypes.data))
+            return out
+        import torch
+        dev = self._device_pointer
+        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
+        n = int(coords.shape[0])
+        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
+                dev("values", values, torch.float32, (wh, None)), dev("vertices", vertices, torch.float32, (n_tri, 3, 3)),
+                dev("points", points, torch.float32, (wh, 8)), dev("coords", coords, torch.int32, (None, 4)), dev("normals", normals, torch.float32, (n, 4)), n)
+        out = torch.empty((n, out_words), dtype=torch.float32, device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_sh_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def lightmap_normals(self, coords, vertices, normals=None):
+        """sol_lightmap_normals: the unit normals of the surface rows `coords` by lightmap_points' rule - the triangle's geometric normal, or with
+        per-vertex `normals` [n_triangles, 3, 3] their interpolation where it has a length - as [n, 4] float32 rows (nx, ny, nz, 0): what
+        lightmap_sh takes. An invalid row, a triangle with a word that is not finite and a vector without length answer zeros. A
+        LIGHTMAP_TEXEL_DTYPE array goes the host route, an [n, 4] int32 device tensor the device route."""
+        if isinstance(coords, np.ndarray) or not hasattr(coords, "data_ptr"):  # the host route
+            c = np.ascontiguousarray(coords)
+            v = np.ascontiguousarray(vertices.cpu().numpy() if hasattr(vertices, "data_ptr") else vertices, dtype=np.float32)
+            nr = None if normals is None else np.ascontiguousarray(normals.cpu().numpy() if hasattr(normals, "data_ptr") else normals, dtype=np.float32)
+            if c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1 or v.ndim != 3 or v.shape[1:] != (3, 3) or (nr is not None and nr.shape != v.shape):
+                raise ValueError("coords: LIGHTMAP_TEXEL_DTYPE rows; vertices, normals: [n_triangles, 3, 3]")
+            out = np.zeros((c.shape[0], 4), dtype=np.float32)
+            self._chk(self.lib.sol_lightmap_normals(self.h, c.ctypes.data, c.shape[0], v.ctypes.data if len(v) else None,
+                                                    None if nr is None or not len(v) else nr.ctypes.data, v.shape[0], out.ctypes.data))
+            return out
+        import torch
+        n_tri = int(vertices.shape[0]) if hasattr(vertices, "shape") and len(vertices.shape) == 3 else 0
+        dev = self._device_pointer
+        d_coords, d_vertices = dev("coords", coords, torch.int32, (None, 4)), dev("vertices", vertices, torch.float32, (None, 3, 3))
+        d_normals = dev("normals", normals, torch.float32, (n_tri, 3, 3))
+        out = torch.empty((int(coords.shape[0]), 4), dtype=torch.float32, device=coords.device)
+        torch.cuda.current_stream(coords.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_normals_dev(self.h, d_coords, int(coords.shape[0]), d_vertices if n_tri else None, d_normals if n_tri else None, n_tri,
+                                                    C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def lightmap_view_sh(self, values, uvs, texels, width, height, triangle_of_dfs, vertices, x0, y0, x1, y1, scale, sample=0, seed=0, vertex_normals=None,
+                         perturb=None, **sh_args):
+        """A directional bake seen from the scene's camera: camera_rays -> closest_hits -> lightmap_coords -> lightmap_normals -> lightmap_sh over
+        the pixels [x0, x1) x [y0, y1), all on device memory. vertices [n_triangles, 3, 3] (and vertex_normals) give the surface's normals;
+        `perturb`, an [h, w, 4] float32 device tensor of the caller's own normals, replaces them - the normal-mapped case. Returns an [h, w, 4]
+        float32 device tensor (E_r, E_g, E_b, count), or [h, w, 28] with coefficients=True; a pixel that misses, or hits something without
+        lightmap, is zero with count 0."""
+        rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
+        h, w = int(rays.shape[0]), int(rays.shape[1])
+        coords = self.lightmap_coords(self.closest_hits(rays.reshape(-1, 8)), triangle_of_dfs)
+        if sh_args.get("coefficients"):
+            normals = None
+        elif perturb is not None:
+            if tuple(perturb.shape) != (h, w, 4):
+                raise ValueError(f"perturb: an [{h}, {w}, 4] float32 device tensor")
+            normals = perturb.reshape(-1, 4)
+        else:
+            normals = self.lightmap_normals(coords, vertices, vertex_normals)
+        out = self.lightmap_sh(values, coords, normals, uvs, texels, width, height, scale=scale, **sh_args)
+        return out.reshape(h, w, -1)
+
     # ---- irradiance volumes (EXTENSION; DESIGN.md 24) ----
     @staticmethod
     def _volume_rows(grid):
