@@ -1376,6 +1376,102 @@ int sol_lightmap_normals_dev(SolScene* scene, const void* coords_dev, size_t n, 
 int sol_lightmap_normals(SolScene* scene, const SolTexel* coords, size_t n, const float* vertices, const float* vertex_normals, size_t n_triangles,
                          float* normals_out);
 
+/* ---- lightmap mip chains: coverage-aware levels, trilinear lookups, the level of detail of a hit (EXTENSION, not in the reference) --
+ * sol_lightmap_mips reduces a baked atlas to a chain of coarser levels without mixing uncovered or non-finite texels in; sol_lightmap_sample_lod
+ * looks the atlas and its chain up trilinearly at a level of detail per row; sol_lightmap_lod gives that level for the hits of a camera. Nothing is
+ * traced and the scene is never read: a scene with a constant medium is served. All arithmetic is fp32, every operation rounded once, no fused
+ * multiply-add, `/` and sqrtf correctly rounded, every clamp a comparison, finite(x) = the exponent field is not all ones;
+ * csrc/sol_lightmap_mips.h is the rule as code and tests/lightmap_mips_ref.py its restatement in numpy.
+ *   Layout.   Level 0 is the caller's atlas: W x H rows of stride_bytes whose leading `channels` words (1..32) are floats, sol_lightmap_dilate's
+ *             limits. W_l = (W_{l-1} + 1) / 2 and H_l likewise - a ceiling, so no source texel is dropped; 1 stays 1. Texel (i, j) of level l
+ *             stands for the level-0 square [i 2^l, (i + 1) 2^l) x [j 2^l, (j + 1) 2^l). `levels` counts level 0: 1 .. the count at which both
+ *             sizes reach 1 (at most SOL_LIGHTMAP_MAX_LEVELS), 0 meaning that count. The chain holds levels 1 .. levels - 1, packed in this order
+ *             in one buffer of rows of level 0's stride: level l starts at row sum_{k=1}^{l-1} W_k H_k. The cover plane holds one byte per chain
+ *             row at the same row index: 0 covered, 255 not - pass_of's convention, so (level l's rows, level l's cover, W_l, H_l) can be handed
+ *             to sol_lightmap_sample as (values, pass_of, width, height). Level 0 is not copied. sol_lightmap_mip_layout answers, from the
+ *             arguments alone and without a device, the count in force, every level's size and first row (entry 0: level 0's size and 0; the
+ *             entries from the count on: 0) and the chain's rows; each out pointer may be NULL, each array has SOL_LIGHTMAP_MAX_LEVELS entries.
+ *   Live.     A level-0 texel is live by sol_lightmap_sample's words: covered - pass_of != 255 where the plane is given, else
+ *             texels[].triangle != SOL_TEXEL_NONE - and finite in all `channels` words. A chain texel is live when its cover byte is 0.
+ *   Reduction. Texel (i, j) of level l + 1 looks at (2i, 2j), (2i + 1, 2j), (2i, 2j + 1), (2i + 1, 2j + 1) of level l, in this order. The taps
+ *             inside level l and live count c. With c > 0 each channel is ((0 + x_a) + x_b ..) / (float)c over the live taps in tap order, and the
+ *             words of the row behind `channels` are those of the first live tap (a SolRadiance atlas of one sample count keeps it). The cover
+ *             byte is 0 if every channel came out finite; else - a sum overflowed - the whole row is zero and the byte 255. With c == 0: a zero
+ *             row, byte 255. A level depends on the level below only: how the kernels split the levels among them changes no bit.
+ *   Lookup.   sol_lightmap_sample_lod takes sol_lightmap_sample's arguments, the chain's two buffers, `levels` (in the configuration) and one
+ *             float per row. lambda = lod[i], 0 unless lod[i] > 0 (NaN reads as 0), levels - 1 when at least that; l0 = floorf(lambda),
+ *             f = lambda - l0. One level's lookup is sol_lightmap_sample's bilinear rule over that level: u, v as there;
+ *             x = ((u * (float)W) * 2^-l) - 0.5f, y likewise, 2^-l an exact constant; the range test x >= -1 && x < (float)W_l (and y) and
+ *             the inside test of a tap run against the level's own size; taps, weights, coverage (the level's cover byte, != 255) and
+ *             finiteness as at level 0; sum / wsum over the live taps in tap order with their count n_l, nothing when wsum is not > 0. The chart
+ *             guard applies at level 0 only: a coarser texel has no point row. With f == 0 the answer is level l0's, count n_l0. Otherwise both
+ *             l0 and l0 + 1 are looked up: if both have wsum > 0 each channel is (a * (1 - f)) + (b * f), 1 - f rounded once, count
+ *             n_a + n_b; if one has, that one's answer and count; if neither, channels + 1 zero words. An invalid surface row answers zeros.
+ *             With lod <= 0 or levels == 1 the answer is sol_lightmap_sample's, word for word; there is no nearest mode. For an atlas whose
+ *             sizes are powers of two and an integral lod = l the answer is sol_lightmap_sample's over level l with its cover as pass_of, at
+ *             every level with W_l = W 2^-l and H_l = H 2^-l - all of them for a square atlas -, on rows whose u W and v H are zero or normal.
+ *   Level of detail. sol_lightmap_lod takes per row the SolRay, the SolRayHit and the surface row sol_lightmap_coords made of it, the mesh's
+ *             vertices and uvs, the atlas size, `spread` - the angle in radians between the rays of neighbouring pixels - and `bias`. With
+ *             N = cross(v1 - v0, v2 - v0), nn = |N|^2, dd = |D|^2, dn = D . N (dot and squared length ((x x) + (y y)) + (z z), a cross
+ *             component (a b) - (c d)): c2 = (dn * dn) / (dd * nn), taken as 1/64 unless c2 >= 1/64 (a cosine floor of 1/8); a = the absolute
+ *             value of (bx - ax) * (cy - ay) - (by - ay) * (cx - ax) over the corners (u * (float)W, v * (float)H) (sol_lightmap_points'
+ *             doubled texel-space area); r = spread * t; q = ((r * r) * (a / sqrtf(nn))) / c2 - the squared number of texels along the
+ *             footprint's major axis: the isotropic filter would rather blur than alias. lambda = bias, plus 0.5f * plog2(q) when q > 1, and the
+ *             answer is lambda if lambda > 0, else 0. plog2(q) = (float)((int)(bits >> 23) - 127) + (float)(bits & 0x7FFFFF) * 2^-23 is the
+ *             piecewise-linear logarithm of q's bits: exact at powers of two, monotone, continuous. The answer is 0 for a row that is not a hit
+ *             (status != SOL_RAY_HIT) or has flags == 0; triangle == SOL_TEXEL_NONE or >= n_triangles; t not finite or not > 0; an origin or
+ *             direction word of the ray not finite (tmin and tmax are not looked at); one of the triangle's 15 words not finite; a texel-space
+ *             area that is zero or not finite; nn zero, subnormal or not finite.
+ *   Charts.   There are no chart ids: a coarse level mixes charts that lie closer than its texel. The caller bounds `levels` by the atlas's
+ *             gutter, as engines do (a gutter of g texels serves levels up to log2(g) + 1).
+ * Neutral as the queries are: no accumulator, plane, counter or statistic is touched; calls are ordered by the handle's stream.
+ * SOL_EINVAL (sol_last_error names the call and the reason), before the device is looked for and in this order. sol_lightmap_mip_layout: width
+ * or height of 0 or above 16384; levels above the full count. sol_lightmap_mips: a null scene; width or height of 0 or above 16384; channels
+ * outside 1..32; a stride that is no multiple of 4 or below 4 x channels; levels above the full count; a null texel or value pointer; with more
+ * than one level a null chain or cover output; mips_out == values, texels or cover_out; cover_out == values, texels or pass_of. Then one level
+ * succeeds and writes nothing. sol_lightmap_sample_lod: a null scene or configuration; a wrong size; reserved != 0; any flag
+ * (SOL_LIGHTMAP_SAMPLE_NEAREST is an unknown flag here); width or height of 0 or above 16384; channels outside 1..32; a stride that is no multiple
+ * of 4 or below 4 x channels; a chart_radius that is NaN or not > 0; exactly one of vertices / points given; a finite chart_radius with neither;
+ * levels above the full count; n_triangles > 2^31 - 2; n > 2^31; a null UV (with n_triangles > 0), texel, value, coordinate, lod or output
+ * pointer; with more than one level a null chain or cover pointer; out == values, coords, lods or mips. sol_lightmap_lod: a null scene; width or
+ * height of 0 or above 16384; a spread that is not finite or not > 0; a bias that is not finite; n_triangles > 2^31 - 2; n > 2^31; with
+ * n_triangles > 0 a null vertex or UV pointer; a null ray, hit, coordinate or output pointer; out == rays, hits or coords. Then n == 0 succeeds
+ * and writes nothing. SOL_EDEVICE without a GPU comes after all of these. There is no host mirror. */
+#define SOL_LIGHTMAP_MAX_LEVELS 15u
+/* 40 bytes: size 0, width 4, height 8, channels 12, stride_bytes 16, flags 20, chart_radius 24, levels 28, reserved 32 */
+typedef struct SolLightmapLodConfig {
+  uint32_t size, width, height, channels, stride_bytes, flags; /* size = sizeof(SolLightmapLodConfig); flags: zero */
+  float chart_radius;                                          /* a world length, > 0; +inf: no chart guard */
+  uint32_t levels;                                             /* level 0 counted; 0: all */
+  uint32_t reserved[2];                                        /* zero */
+} SolLightmapLodConfig;
+/* No device, no handle: the layout rule. */
+int sol_lightmap_mip_layout(uint32_t width, uint32_t height, uint32_t levels, uint32_t* levels_out, uint32_t* widths, uint32_t* heights,
+                            uint64_t* row_offsets, uint64_t* total_rows);
+/* Device pointers (W x H SolTexel, 16-byte aligned; W x H bytes or NULL; W x H rows of stride_bytes, 4-byte aligned; the chain's rows and as
+ * many bytes out - rows whose stride and addresses are multiples of 16 move as 16-byte words), on the scene's stream, asynchronous. */
+int sol_lightmap_mips_dev(SolScene* scene, const void* texels_dev, const void* pass_of_dev, uint32_t width, uint32_t height, const void* values_dev,
+                          uint32_t channels, uint32_t stride_bytes, uint32_t levels, void* mips_out_dev, void* cover_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_mips(SolScene* scene, const SolTexel* texels, const uint8_t* pass_of, uint32_t width, uint32_t height, const void* values,
+                      uint32_t channels, uint32_t stride_bytes, uint32_t levels, void* mips_out, uint8_t* cover_out);
+/* Device pointers (the arguments of sol_lightmap_sample_dev; the chain's rows and cover bytes, or NULL with one level; n floats of lod; n rows of
+ * channels + 1 words out), on the scene's stream, asynchronous. */
+int sol_lightmap_sample_lod_dev(SolScene* scene, const SolLightmapLodConfig* config, const void* uvs_dev, size_t n_triangles, const void* texels_dev,
+                                const void* pass_of_dev, const void* values_dev, const void* mips_dev, const void* cover_dev, const void* vertices_dev,
+                                const void* points_dev, const void* coords_dev, const void* lods_dev, size_t n, void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_sample_lod(SolScene* scene, const SolLightmapLodConfig* config, const float* uvs, size_t n_triangles, const SolTexel* texels,
+                            const uint8_t* pass_of, const void* values, const void* mips, const uint8_t* cover, const float* vertices,
+                            const SolRay* points, const SolTexel* coords, const float* lods, size_t n, void* out);
+/* Device pointers (n SolRay, n SolRayHit, n SolTexel surface rows, 16-byte aligned; n_triangles x 9 and x 6 floats; n floats out), on the scene's
+ * stream, asynchronous. */
+int sol_lightmap_lod_dev(SolScene* scene, const void* rays_dev, const void* hits_dev, const void* coords_dev, size_t n, const void* vertices_dev,
+                         const void* uvs_dev, size_t n_triangles, uint32_t width, uint32_t height, float spread, float bias, void* lods_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_lod(SolScene* scene, const SolRay* rays, const SolRayHit* hits, const SolTexel* coords, size_t n, const float* vertices,
+                     const float* uvs, size_t n_triangles, uint32_t width, uint32_t height, float spread, float bias, float* lods_out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

@@ -172,6 +172,45 @@ hipError_t sol_launch_lightmap_sh(const SolLightmapShConfig& c, uint32_t n_trian
                                   void* out, hipStream_t stream);
 hipError_t sol_launch_lightmap_normals(const void* coords, uint32_t n, const void* vertices, const void* vertex_normals, uint32_t n_triangles, void* out,
                                        hipStream_t stream);
+// ---- sol_lightmap_mips.hip: lightmap mip chains. The layout is the one rule of host and device: level 0 is the caller's W x H
+// atlas, W_l = (W_{l-1} + 1) / 2 and H_l likewise, the chain holds levels 1 .. levels - 1 packed in this order with level 0's stride, the cover
+// plane one byte per chain row ----
+#define SOL_LMM_MAX_LEVELS 15u  // 16384 = 2^14: levels 0 .. 14
+struct LmmLayout {
+  uint32_t levels, full;  // the count in force (1 .. full); the count at which both sizes reach 1
+  uint32_t w[SOL_LMM_MAX_LEVELS], h[SOL_LMM_MAX_LEVELS];
+  uint64_t at[SOL_LMM_MAX_LEVELS];  // the first row of level l in the chain (at[0] = 0: level 0 is not in the chain)
+  uint64_t rows;                    // the rows of the chain: levels 1 .. levels - 1
+};
+// levels: 0 = all; a count above the full one is clamped here - the entry points refuse it first
+inline LmmLayout lmm_layout(uint32_t W, uint32_t H, uint32_t levels) {
+  LmmLayout L;
+  uint32_t w = W, h = H, full = 1u;
+  while ((w > 1u || h > 1u) && full < SOL_LMM_MAX_LEVELS) { w = (w + 1u) / 2u; h = (h + 1u) / 2u; ++full; }
+  L.full = full;
+  L.levels = (levels == 0u || levels > full) ? full : levels;
+  L.rows = 0;
+  w = W; h = H;
+  for (uint32_t l = 0; l < SOL_LMM_MAX_LEVELS; ++l) {
+    L.w[l] = w; L.h[l] = h;
+    L.at[l] = l >= 1u ? L.rows : 0;
+    if (l >= 1u && l < L.levels) L.rows += (uint64_t)w * h;
+    w = (w + 1u) / 2u; h = (h + 1u) / 2u;
+  }
+  return L;
+}
+// mips: levels 1 .. L.levels - 1 from level 0 (texels, pass_of or null, values) into `mips` and `cover`. tail: the levels from the first one whose
+// source is at most 64 x 64 are made by one workgroup through LDS where the rows fit (the same words); else a launch per level.
+hipError_t sol_launch_lightmap_mips(const LmmLayout& L, uint32_t channels, uint32_t stride_words, bool tail, const void* texels, const void* pass_of,
+                                    const void* values, void* mips, void* cover, hipStream_t stream);
+// sample_lod: sol_launch_lightmap_sample's arguments, the chain, one float of lod per row
+struct SolLightmapLodConfig;
+hipError_t sol_launch_lightmap_sample_lod(const SolLightmapLodConfig& c, const LmmLayout& L, uint32_t n_triangles, const void* uvs, const void* texels,
+                                          const void* pass_of, const void* values, const void* mips, const void* cover, const void* vertices,
+                                          const void* points, const void* coords, const void* lods, uint32_t n, void* out, hipStream_t stream);
+// lod: n SolRay, n SolRayHit, n surface rows in, n floats out
+hipError_t sol_launch_lightmap_lod(const void* rays, const void* hits, const void* coords, uint32_t n, const void* vertices, const void* uvs,
+                                   uint32_t n_triangles, uint32_t W, uint32_t H, float spread, float bias, void* out, hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

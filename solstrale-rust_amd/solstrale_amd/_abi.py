@@ -285,6 +285,17 @@ class SolLightmapShConfig(C.Structure):
 SOL_LIGHTMAP_SH_NEAREST, SOL_LIGHTMAP_SH_COEFFICIENTS, SOL_LIGHTMAP_SH_CLAMP = 1, 2, 4
 
 
+class SolLightmapLodConfig(C.Structure):
+    """EXTENSION: the configuration of sol_lightmap_sample_lod: size = sizeof, W x H texels, the rows' channels and stride, flags = 0,
+    the radius of the chart guard (> 0; +inf: off), the levels of the chain with level 0 counted (0: all), reserved = 0. 40 bytes. Not in
+    ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("stride_bytes", C.c_uint32),
+                ("flags", C.c_uint32), ("chart_radius", C.c_float), ("levels", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+SOL_LIGHTMAP_MAX_LEVELS = 15
+
+
 class SolLightmapFilterConfig(C.Structure):
     """EXTENSION: the configuration of sol_lightmap_filter: size = sizeof, W x H texels, 1..8 passes, the normal factor's exponent as a
     power of two (0..7), the rows' channels and stride, the widths of the distance, plane and value factors (>= 1e-6 or +inf), the scale a value is
@@ -509,6 +520,16 @@ def load_hip():
                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_lightmap_normals_dev", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
     _sig(lib, "sol_lightmap_normals", C.c_int, [P, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    _sig(lib, "sol_lightmap_mip_layout", C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+    for name in ("sol_lightmap_mips_dev", "sol_lightmap_mips"):
+        _sig(lib, name, C.c_int, [P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])
+    for name in ("sol_lightmap_sample_lod_dev", "sol_lightmap_sample_lod"):
+        _sig(lib, name, C.c_int, [P, C.POINTER(SolLightmapLodConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
+    for name in ("sol_lightmap_lod_dev", "sol_lightmap_lod"):
+        _sig(lib, name, C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_float,
+                                  C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -558,6 +579,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_irradiance_adaptive_dev", "sol_irradiance_adaptive", "sol_radiance_rescale_dev", "sol_radiance_rescale",
                "sol_lightmap_coords_dev", "sol_lightmap_coords", "sol_lightmap_sample_dev", "sol_lightmap_sample",
                "sol_lightmap_sh_dev", "sol_lightmap_sh", "sol_lightmap_normals_dev", "sol_lightmap_normals",
+               "sol_lightmap_mip_layout", "sol_lightmap_mips_dev", "sol_lightmap_mips", "sol_lightmap_sample_lod_dev", "sol_lightmap_sample_lod",
+               "sol_lightmap_lod_dev", "sol_lightmap_lod",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

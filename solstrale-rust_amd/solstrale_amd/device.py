@@ -1,6 +1,7 @@
 """Thin Python handle over the device C ABI (libsolstrale_hip.so). No compute happens in Python and there is no
 fallback: every call goes to the HIP library and raises if it fails (e.g. SOL_EDEVICE without a GPU)."""
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -190,6 +191,33 @@ def lightmap_mesh(description, first, count):
     V = np.stack([v0, v0 + a, v0 + b], axis=1).astype(np.float32)
     T = np.stack([field("uv0", np.float32, 2), field("uv1", np.float32, 2), field("uv2", np.float32, 2)], axis=1)
     return np.ascontiguousarray(V), np.ascontiguousarray(T)
+
+
+def lightmap_mip_layout(width, height, levels=None):
+    """The layout of a lightmap mip chain (sol_lightmap_mip_layout's rule) as a dict: `levels` - the count in force, level 0 counted
+    (None or 0: all) -, `widths`, `heights` and `offsets` per level - W_l = (W_{l-1} + 1) // 2; offsets[l] is the first row of level l >= 1 in the
+    chain, offsets[0] = 0: level 0 is the caller's atlas and not in the chain - and `rows`, the rows of the chain and the bytes of its cover
+    plane."""
+    width, height = int(width), int(height)
+    if not (0 < width <= _abi.SOL_LIGHTMAP_MAX_SIZE and 0 < height <= _abi.SOL_LIGHTMAP_MAX_SIZE):
+        raise ValueError(f"an atlas of {width} x {height} texels (1 .. {_abi.SOL_LIGHTMAP_MAX_SIZE} each way)")
+    sizes = [(width, height)]
+    while sizes[-1] != (1, 1):
+        sizes.append(((sizes[-1][0] + 1) // 2, (sizes[-1][1] + 1) // 2))
+    n = len(sizes) if not levels else int(levels)
+    if not 1 <= n <= len(sizes):
+        raise ValueError(f"{levels} levels (an atlas of {width} x {height} texels has {len(sizes)})")
+    offsets, rows = [0], 0
+    for w, h in sizes[1:n]:
+        offsets.append(rows)
+        rows += w * h
+    return {"levels": n, "widths": [w for w, _ in sizes[:n]], "heights": [h for _, h in sizes[:n]], "offsets": offsets, "rows": rows}
+
+
+def pixel_spread(vertical_fov_degrees, height):
+    """The angle in radians between the rays of vertically neighbouring pixels at the centre of a pinhole image of `height` rows: what
+    DeviceScene.lightmap_lod takes as `spread`."""
+    return 2.0 * math.tan(math.radians(float(vertical_fov_degrees)) / 2.0) / float(height)
 
 
 def lightmap_texels_to_numpy(rows):
@@ -1181,6 +1209,138 @@ class DeviceScene:
         else:
             normals = self.lightmap_normals(coords, vertices, vertex_normals)
         out = self.lightmap_sh(values, coords, normals, uvs, texels, width, height, scale=scale, **sh_args)
+        return out.reshape(h, w, -1)
+
+    # ---- lightmap mip chains (EXTENSION) ----
+    def lightmap_mips(self, values, texels, width, height, channels=3, pass_of=None, levels=None):
+        """sol_lightmap_mips: the mip chain of the baked atlas `values` (`width * height` rows whose leading `channels` 32-bit words are floats).
+        A texel of a coarser level is the mean of the live ones among its four sources - covered (pass_of != 255 where lightmap_dilate's plane is
+        given, else owned in `texels`) and finite -, so nothing uncovered bleeds in. Returns (mips, cover): the rows of levels 1 .. levels - 1
+        packed as lightmap_mip_layout says, with the stride of `values`, and one byte per row, 0 covered, 255 not - a level's slice of both can be
+        handed to lightmap_sample as (values, pass_of). levels: level 0 counted, None: all. Host arrays go the host route, device tensors the
+        device route, decided by `values`."""
+        width, height, channels = int(width), int(height), int(channels)
+        lay = lightmap_mip_layout(width, height, levels)
+        wh, rows = width * height, lay["rows"]
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
+            v = np.ascontiguousarray(values, dtype=np.float32)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            po = None if pass_of is None else np.ascontiguousarray(pass_of.cpu().numpy() if hasattr(pass_of, "data_ptr") else pass_of, dtype=np.uint8)
+            if v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or (po is not None and po.size != wh):
+                raise ValueError("values: [width * height, k] float32 rows; texels: width * height LIGHTMAP_TEXEL_DTYPE rows; pass_of: width * height bytes")
+            mips, cover = np.zeros((rows, v.shape[1]), dtype=np.float32), np.zeros(rows, dtype=np.uint8)
+            self._chk(self.lib.sol_lightmap_mips(self.h, t.ctypes.data, None if po is None else po.ctypes.data, width, height, v.ctypes.data, channels,
+                                                 v.shape[1] * 4, lay["levels"], mips.ctypes.data if rows else None, cover.ctypes.data if rows else None))
+            return mips, cover
+        import torch
+        dev = self._device_pointer
+        d_values, d_texels = dev("values", values, torch.float32, (wh, None)), dev("texels", texels, torch.int32, (wh, 4))
+        d_pass = dev("pass_of", pass_of, torch.uint8, (height, width))
+        mips = torch.empty((rows, int(values.shape[1])), dtype=torch.float32, device=values.device)
+        cover = torch.empty((rows,), dtype=torch.uint8, device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()  # (the values may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_mips_dev(self.h, d_texels, d_pass, width, height, d_values, channels, int(values.shape[1]) * 4, lay["levels"],
+                                                 C.c_void_p(mips.data_ptr()) if rows else None, C.c_void_p(cover.data_ptr()) if rows else None))
+        self.sync()
+        return mips, cover
+
+    def lightmap_sample_lod(self, values, mips, cover, lods, coords, uvs, texels, width, height, channels=3, pass_of=None, levels=None, chart_radius=None,
+                            vertices=None, points=None):
+        """sol_lightmap_sample_lod: lightmap_sample's bilinear lookup made trilinear over the chain lightmap_mips returned. lods: one float per row
+        of `coords` - at most 0 (or NaN): level 0 alone, the answer of lightmap_sample word for word; at least levels - 1: the last level alone;
+        between two levels both are looked up and mixed by the fraction, and a level without a live tap leaves the answer to the other. The chart
+        guard (chart_radius, vertices, points) acts at level 0 only. Returns [n, channels + 1] float32 rows - the channels, then the bits of the
+        number of taps that contributed over both levels (0 .. 8). Host arrays go the host route, device tensors the device route, decided by
+        `values`."""
+        width, height, channels = int(width), int(height), int(channels)
+        lay = lightmap_mip_layout(width, height, levels)
+        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
+        cfg = _abi.SolLightmapLodConfig(size=C.sizeof(_abi.SolLightmapLodConfig), width=width, height=height, channels=channels, stride_bytes=4 * k, flags=0,
+                                        chart_radius=float("inf") if chart_radius is None else float(chart_radius), levels=lay["levels"])
+        out_words = channels + 1 if 1 <= channels <= 32 else 1
+        wh, rows = width * height, lay["rows"]
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
+            def host(x, dtype=None):
+                return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
+            v, u, vx, p = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32)
+            m, cv, ld, po = host(mips, np.float32), host(cover, np.uint8), host(lods, np.float32), host(pass_of, np.uint8)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
+            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
+                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or (vx is not None and vx.shape != (u.shape[0], 3, 3))
+                    or (p is not None and p.shape != (wh, 8)) or ld.shape != (c.shape[0],)
+                    or (rows and (m is None or cv is None or m.shape != (rows, v.shape[1]) or cv.shape != (rows,)))):
+                raise ValueError("values: [width * height, k] float32 rows; mips: [rows, k] and cover: [rows] as lightmap_mip_layout says; lods: [n]; texels, "
+                                 "coords: LIGHTMAP_TEXEL_DTYPE rows; uvs: [n, 3, 2]; pass_of: width * height bytes; vertices: [n, 3, 3]; points: "
+                                 "[width * height, 8]")
+            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
+            self._chk(self.lib.sol_lightmap_sample_lod(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
+                                                       None if po is None else po.ctypes.data, v.ctypes.data, m.ctypes.data if rows else None,
+                                                       cv.ctypes.data if rows else None, None if vx is None else vx.ctypes.data,
+                                                       None if p is None else p.ctypes.data, c.ctypes.data, ld.ctypes.data, c.shape[0], out.ctypes.data))
+            return out
+        import torch
+        dev = self._device_pointer
+        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
+        n = int(coords.shape[0])
+        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
+                dev("values", values, torch.float32, (wh, None)), dev("mips", mips, torch.float32, (rows, k)) if rows else None,
+                dev("cover", cover, torch.uint8, (rows,)) if rows else None, dev("vertices", vertices, torch.float32, (n_tri, 3, 3)),
+                dev("points", points, torch.float32, (wh, 8)), dev("coords", coords, torch.int32, (None, 4)), dev("lods", lods, torch.float32, (n,)), n)
+        out = torch.empty((n, out_words), dtype=torch.float32, device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_sample_lod_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def lightmap_lod(self, rays, hits, coords, vertices, uvs, width, height, spread, bias=0.0):
+        """sol_lightmap_lod: the level of detail of each hit - half the piecewise-linear log2 of the squared number of texels under a pixel along
+        its footprint's major axis, plus `bias`, no less than 0. rays [n, 8], hits (closest_hits' rows) and coords (lightmap_coords' rows) belong
+        together row by row; vertices [n_triangles, 3, 3] and uvs [n_triangles, 3, 2] are the lightmap mesh; spread: the angle in radians between
+        the rays of neighbouring pixels (pixel_spread). A miss, an invalid row and a degenerate triangle answer 0. Returns [n] float32: what
+        lightmap_sample_lod takes. Host arrays go the host route, device tensors the device route, decided by `rays`."""
+        width, height = int(width), int(height)
+        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route
+            r = np.ascontiguousarray(rays, dtype=np.float32)
+            h = np.ascontiguousarray(self.hits_to_numpy(hits) if hasattr(hits, "data_ptr") else hits)
+            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
+            v = np.ascontiguousarray(vertices.cpu().numpy() if hasattr(vertices, "data_ptr") else vertices, dtype=np.float32)
+            u = np.ascontiguousarray(uvs.cpu().numpy() if hasattr(uvs, "data_ptr") else uvs, dtype=np.float32)
+            if (r.ndim != 2 or r.shape[1] != 8 or h.dtype != self.RAY_HIT_DTYPE or h.shape != (r.shape[0],) or c.dtype != LIGHTMAP_TEXEL_DTYPE
+                    or c.shape != (r.shape[0],) or v.ndim != 3 or v.shape[1:] != (3, 3) or u.shape != (v.shape[0], 3, 2)):
+                raise ValueError("rays: [n, 8] float32; hits: n RAY_HIT_DTYPE rows; coords: n LIGHTMAP_TEXEL_DTYPE rows; vertices: [t, 3, 3]; uvs: [t, 3, 2]")
+            out = np.zeros(r.shape[0], dtype=np.float32)
+            self._chk(self.lib.sol_lightmap_lod(self.h, r.ctypes.data, h.ctypes.data, c.ctypes.data, r.shape[0], v.ctypes.data if len(v) else None,
+                                                u.ctypes.data if len(v) else None, v.shape[0], width, height, float(spread), float(bias), out.ctypes.data))
+            return out
+        import torch
+        dev = self._device_pointer
+        n = int(rays.shape[0])
+        n_tri = int(vertices.shape[0]) if hasattr(vertices, "shape") and len(vertices.shape) == 3 else 0
+        d_rays, d_hits, d_coords = dev("rays", rays, torch.float32, (n, 8)), dev("hits", hits, torch.int32, (n, 8)), dev("coords", coords, torch.int32, (n, 4))
+        d_vertices, d_uvs = dev("vertices", vertices, torch.float32, (n_tri, 3, 3)), dev("uvs", uvs, torch.float32, (n_tri, 3, 2))
+        out = torch.empty((n,), dtype=torch.float32, device=rays.device)
+        torch.cuda.current_stream(rays.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_lod_dev(self.h, d_rays, d_hits, d_coords, n, d_vertices if n_tri else None, d_uvs if n_tri else None, n_tri, width, height,
+                                                float(spread), float(bias), C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def lightmap_view_lod(self, values, mips, cover, uvs, texels, width, height, triangle_of_dfs, vertices, x0, y0, x1, y1, spread, bias=0.0, sample=0, seed=0,
+                          **sample_args):
+        """The bake seen from the scene's camera without aliasing: camera_rays -> closest_hits -> lightmap_coords -> lightmap_lod ->
+        lightmap_sample_lod over the pixels [x0, x1) x [y0, y1), all on device memory. spread: pixel_spread of the camera; sample_args: what
+        lightmap_sample_lod takes by name (channels, pass_of, levels, chart_radius, points; `vertices` serves the guard too). Returns an
+        [h, w, channels + 1] float32 device tensor; a pixel that misses, or hits something without lightmap, is zero with count 0."""
+        rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
+        h, w = int(rays.shape[0]), int(rays.shape[1])
+        rays = rays.reshape(-1, 8)
+        hits = self.closest_hits(rays)
+        coords = self.lightmap_coords(hits, triangle_of_dfs)
+        lods = self.lightmap_lod(rays, hits, coords, vertices, uvs, width, height, spread, bias)
+        if sample_args.get("points") is not None:
+            sample_args = {**sample_args, "vertices": vertices}
+        out = self.lightmap_sample_lod(values, mips, cover, lods, coords, uvs, texels, width, height, **sample_args)
         return out.reshape(h, w, -1)
 
     # ---- irradiance volumes (EXTENSION; DESIGN.md 24) ----
