@@ -1472,6 +1472,91 @@ int sol_lightmap_lod_dev(SolScene* scene, const void* rays_dev, const void* hits
 int sol_lightmap_lod(SolScene* scene, const SolRay* rays, const SolRayHit* hits, const SolTexel* coords, size_t n, const float* vertices,
                      const float* uvs, size_t n_triangles, uint32_t width, uint32_t height, float spread, float bias, float* lods_out);
 
+/* ---- lightmap charts: UV islands labelled, kept apart in dilation and lookups (EXTENSION, not in the reference) -----------------
+ * A chart is a set of triangles connected through shared edges. sol_lightmap_charts labels them on the device; sol_lightmap_dilate_charts is
+ * sol_lightmap_dilate that never averages across charts and says which chart each texel belongs to; sol_lightmap_sample_charts is
+ * sol_lightmap_sample that refuses the taps of another chart by id, dilated taps included; sol_lightmap_chart_levels answers how many mip levels
+ * an atlas can have before two charts meet in one level. Nothing is traced and the scene is never read: a scene with a constant medium is
+ * served. All arithmetic is fp32, every operation rounded once, no fused multiply-add, `/` correctly rounded, finite(x) = the exponent field is
+ * not all ones; csrc/sol_lightmap_charts.h is the rule as code and tests/lightmap_charts_ref.py its restatement in numpy.
+ *   Labels.   uvs: n_triangles x 6 floats; vertices: n_triangles x 9 floats or NULL (the meshes are not indexed: connectivity is found from the
+ *             values). A triangle is skipped when one of its UV words - with vertices, also one of its vertex words - is not finite: it gets
+ *             SOL_CHART_NONE and joins nothing. Edge e (0, 1, 2) of a triangle joins its corners e and (e + 1) % 3; an end point is (u, v), with
+ *             vertices (u, v, x, y, z); words are compared as numbers (-0 == +0: every word is x + 0.0f before its bits are looked at). Two live
+ *             triangles are connected when the unordered pair of end points of an edge of one equals that of an edge of the other; a shared
+ *             corner alone connects nothing; an edge shared by three or more triangles connects them all. A chart is a connected component; its
+ *             id is the rank of its lowest triangle index among all charts' lowest indices: ids are dense, 0 .. n_charts - 1, in mesh order, and
+ *             do not depend on the schedule. chart_of_triangle_out: n_triangles words; n_charts_out: one word (a device word for the _dev form).
+ *   Dilation. sol_lightmap_dilate's arguments, chart_of_triangle / n_triangles in, and a chart plane (W x H words) out; the plane and pass_of
+ *             are mandatory outputs. A texel is owned when texels[].triangle < n_triangles and that triangle's chart is not SOL_CHART_NONE: its
+ *             row is copied whole, its plane word is its chart, its pass_of 0. Any other texel counts as uncovered. Pass k: a texel uncovered at
+ *             the pass's start with at least one covered neighbour among its eight joins chart c, the chart held by the most of those covered
+ *             neighbours - on a tie the lowest id; per channel its value is (0 + x + x ..) / (float)count over the covered neighbours of chart c
+ *             only, in sol_lightmap_dilate's neighbour order; the rest of its row is zero, its plane word c, its pass_of k. Never filled: a
+ *             zero row, plane SOL_CHART_NONE, pass_of 255. When every owned texel is of one chart, out and pass_of are sol_lightmap_dilate's.
+ *   Lookup.   sol_lightmap_sample's arguments without vertices and points (chart_radius must be +inf), with chart_of_triangle and the chart
+ *             plane. A row is invalid - channels + 1 zero words - under sol_lightmap_sample's rule, and also when
+ *             chart_of_triangle[row.triangle] == SOL_CHART_NONE. A tap is live when it is live by sol_lightmap_sample's rule (inside, covered,
+ *             finite) and plane[tap] == chart_of_triangle[row.triangle]. Sums, renormalisation, nearest mode and the count word are unchanged.
+ *   Levels.   A chart plane (W x H words) and pass_of or NULL. A texel is live when its plane word is not SOL_CHART_NONE and, with pass_of
+ *             given, pass_of != 255; the word 0xFFFFFFFE is reserved (MIXED below). Levels are sol_lightmap_mip_layout's. A level-l texel
+ *             (l >= 1) reduces its four sources (2i, 2j) .. (2i + 1, 2j + 1) that lie inside level l - 1: NONE when none is live; their chart
+ *             when all live ones agree; MIXED otherwise, or when a source is MIXED. mixed_texels[l] counts level l's MIXED texels;
+ *             mixed_windows[l] counts its windows (i, j), (i + 1, j), (i, j + 1), (i + 1, j + 1) - a bilinear footprint; 0 <= i < max(W_l - 1, 1),
+ *             0 <= j < max(H_l - 1, 1), texels outside the level and NONE ignored - that hold two different charts or a MIXED texel.
+ *             levels = 1 + the number of consecutive levels from 1 on with both counts zero: the value to hand to sol_lightmap_mips. Both count
+ *             arrays have SOL_LIGHTMAP_MAX_LEVELS entries; entry 0 is zero and so is every entry from the full count of levels on. Level 0 is
+ *             not judged: charts may abut there, and level 0 has guards.
+ * Neutral as the queries are: no accumulator, plane, counter or statistic is touched; calls are ordered by the handle's stream.
+ * SOL_LIGHTMAP_CHARTS=collide (read at every call) masks the edge hash of the labelling to 4 bits - the measured and tested worst case of the
+ * match; the labels do not change.
+ * SOL_EINVAL (sol_last_error names the call and the reason), before the device is looked for and in this order. sol_lightmap_charts: a null
+ * scene; n_triangles > SOL_LIGHTMAP_CHARTS_MAX_TRIANGLES; with n_triangles > 0 a null UV or label output pointer; a null n_charts pointer. Then
+ * the host form with n_triangles == 0 writes 0 charts and succeeds. sol_lightmap_dilate_charts: a null scene; a null texel, value, output,
+ * pass_of or plane pointer; width or height of 0 or above 16384; channels outside 1..32; a stride that is no multiple of 4 or below
+ * 4 x channels; passes above 254; out == values; a null chart_of_triangle with n_triangles > 0; n_triangles >
+ * SOL_LIGHTMAP_CHARTS_MAX_TRIANGLES. sol_lightmap_sample_charts: a null scene or configuration; a wrong size; reserved != 0; unknown flag bits;
+ * width or height of 0 or above 16384; channels outside 1..32; a stride that is no multiple of 4 or below 4 x channels; a chart_radius that is
+ * not +inf; n_triangles > SOL_LIGHTMAP_CHARTS_MAX_TRIANGLES; n > 2^31; a null UV or chart_of_triangle pointer (with n_triangles > 0), a null
+ * texel, value, plane, coordinate or output pointer; out == values or coords. Then n == 0 succeeds and writes nothing.
+ * sol_lightmap_chart_levels: a null scene; width or height of 0 or above 16384; a null plane, levels, mixed_texels or mixed_windows pointer.
+ * Then the host form with a 1 x 1 plane answers one level and zero counts. SOL_EDEVICE without a GPU comes after all of these. There is no host
+ * mirror. */
+#define SOL_CHART_NONE 0xFFFFFFFFu
+#define SOL_LIGHTMAP_CHARTS_MAX_TRIANGLES (1u << 30)
+/* Device pointers (n_triangles x 6 floats; n_triangles x 9 floats or NULL; n_triangles words and one word out), on the scene's stream,
+ * asynchronous. */
+int sol_lightmap_charts_dev(SolScene* scene, const void* uvs_dev, const void* vertices_dev, size_t n_triangles, void* chart_of_triangle_out_dev,
+                            void* n_charts_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_charts(SolScene* scene, const float* uvs, const float* vertices, size_t n_triangles, uint32_t* chart_of_triangle_out,
+                        uint32_t* n_charts_out);
+/* Device pointers (the arguments of sol_lightmap_dilate_dev; n_triangles words; W x H bytes and W x H words out), on the scene's stream,
+ * asynchronous. */
+int sol_lightmap_dilate_charts_dev(SolScene* scene, const void* texels_dev, uint32_t width, uint32_t height, const void* values_dev, uint32_t channels,
+                                   uint32_t stride_bytes, uint32_t passes, const void* chart_of_triangle_dev, size_t n_triangles, void* out_dev,
+                                   void* pass_of_out_dev, void* chart_plane_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_dilate_charts(SolScene* scene, const SolTexel* texels, uint32_t width, uint32_t height, const void* values, uint32_t channels,
+                               uint32_t stride_bytes, uint32_t passes, const uint32_t* chart_of_triangle, size_t n_triangles, void* out,
+                               uint8_t* pass_of_out, uint32_t* chart_plane_out);
+/* Device pointers (the arguments of sol_lightmap_sample_dev without the guard arrays; n_triangles words; W x H words), on the scene's stream,
+ * asynchronous. */
+int sol_lightmap_sample_charts_dev(SolScene* scene, const SolLightmapSampleConfig* config, const void* uvs_dev, size_t n_triangles,
+                                   const void* texels_dev, const void* pass_of_dev, const void* values_dev, const void* chart_of_triangle_dev,
+                                   const void* chart_plane_dev, const void* coords_dev, size_t n, void* out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_sample_charts(SolScene* scene, const SolLightmapSampleConfig* config, const float* uvs, size_t n_triangles, const SolTexel* texels,
+                               const uint8_t* pass_of, const void* values, const uint32_t* chart_of_triangle, const uint32_t* chart_plane,
+                               const SolTexel* coords, size_t n, void* out);
+/* Device pointers (W x H words; W x H bytes or NULL; one word and two arrays of SOL_LIGHTMAP_MAX_LEVELS words out), on the scene's stream,
+ * asynchronous. */
+int sol_lightmap_chart_levels_dev(SolScene* scene, const void* chart_plane_dev, const void* pass_of_dev, uint32_t width, uint32_t height,
+                                  void* levels_out_dev, void* mixed_texels_out_dev, void* mixed_windows_out_dev);
+/* Host arrays, staged through a buffer the handle owns; blocks. */
+int sol_lightmap_chart_levels(SolScene* scene, const uint32_t* chart_plane, const uint8_t* pass_of, uint32_t width, uint32_t height,
+                              uint32_t* levels_out, uint32_t* mixed_texels_out, uint32_t* mixed_windows_out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

@@ -211,6 +211,31 @@ hipError_t sol_launch_lightmap_sample_lod(const SolLightmapLodConfig& c, const L
 // lod: n SolRay, n SolRayHit, n surface rows in, n floats out
 hipError_t sol_launch_lightmap_lod(const void* rays, const void* hits, const void* coords, uint32_t n, const void* vertices, const void* uvs,
                                    uint32_t n_triangles, uint32_t W, uint32_t H, float spread, float bias, void* out, hipStream_t stream);
+// ---- sol_lightmap_charts.hip: lightmap charts. charts: n triangles (uvs, vertices or null) labelled into chart_of (n words) and
+// *n_charts; collide: the hash masked to 4 bits (the same labels). The scratch of a labelling is sized once, by the entry point, and handed to the
+// launch: offsets in words of keys, keys2 (two each per edge), vals, order (one per edge), parent, root, flag, rank (one per triangle), then
+// rocPRIM's own, 256-byte aligned; `words` in all, 8-byte aligned ----
+struct LcScratch {
+  size_t keys, keys2, vals, order, parent, root, flag, rank, tmp, words;
+  size_t sort_bytes, scan_bytes;
+};
+hipError_t sol_lightmap_charts_scratch(uint32_t n, LcScratch& S);
+hipError_t sol_launch_lightmap_charts(const void* uvs, const void* vertices, uint32_t n, bool collide, const LcScratch& S, uint32_t* scratch, void* chart_of,
+                                      void* n_charts, hipStream_t stream);
+// dilate_charts: as the dilation's two launches, with the labels in and the chart plane beside `out`; the plane is written in place (a pass reads
+// the words of texels covered before it and writes those of texels that were not)
+hipError_t sol_launch_lightmap_dilate_charts_begin(const void* texels, uint32_t n_texels, const void* values, uint32_t stride_words, const void* chart_of,
+                                                   uint32_t n_triangles, void* out, uint8_t* cover, void* plane, hipStream_t stream);
+hipError_t sol_launch_lightmap_dilate_charts_pass(uint32_t W, uint32_t H, uint32_t channels, uint32_t stride_words, uint32_t pass, void* out,
+                                                  const uint8_t* cover_in, uint8_t* cover_out, void* plane, hipStream_t stream);
+// sample_charts: sol_launch_lightmap_sample's arguments without the guard arrays, the labels and the plane
+hipError_t sol_launch_lightmap_sample_charts(const SolLightmapSampleConfig& c, uint32_t n_triangles, const void* uvs, const void* texels, const void* pass_of,
+                                             const void* values, const void* chart_of, const void* plane, const void* coords, uint32_t n, void* out,
+                                             hipStream_t stream);
+// chart_levels: the plane reduced level by level into `scratch` (L.rows words, L = lmm_layout(W, H, 0)); the two count arrays (SOL_LMM_MAX_LEVELS
+// words each) are zeroed here, counted into, and *levels written last
+hipError_t sol_launch_lightmap_chart_levels(const LmmLayout& L, const void* plane, const void* pass_of, uint32_t* scratch, void* levels, void* mixed_texels,
+                                            void* mixed_windows, hipStream_t stream);
 // ---- sol_camera.hip: the background-block proof of a camera move. flags: one byte per 8x8 block, row-major ----
 struct SolProofCamera;
 hipError_t sol_launch_background_proof(const DWide* wides, uint32_t n_wide, uint32_t emin, const SolProofCamera& cam, uint8_t* flags, hipStream_t stream);

@@ -530,6 +530,16 @@ def load_hip():
     for name in ("sol_lightmap_lod_dev", "sol_lightmap_lod"):
         _sig(lib, name, C.c_int, [P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_float,
                                   C.c_float, C.c_void_p])
+    for name in ("sol_lightmap_charts_dev", "sol_lightmap_charts"):
+        _sig(lib, name, C.c_int, [P, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p])
+    for name in ("sol_lightmap_dilate_charts_dev", "sol_lightmap_dilate_charts"):
+        _sig(lib, name, C.c_int, [P, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                  C.c_void_p, C.c_void_p])
+    for name in ("sol_lightmap_sample_charts_dev", "sol_lightmap_sample_charts"):
+        _sig(lib, name, C.c_int, [P, C.POINTER(SolLightmapSampleConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p])
+    for name in ("sol_lightmap_chart_levels_dev", "sol_lightmap_chart_levels"):
+        _sig(lib, name, C.c_int, [P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -581,6 +591,8 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_lightmap_sh_dev", "sol_lightmap_sh", "sol_lightmap_normals_dev", "sol_lightmap_normals",
                "sol_lightmap_mip_layout", "sol_lightmap_mips_dev", "sol_lightmap_mips", "sol_lightmap_sample_lod_dev", "sol_lightmap_sample_lod",
                "sol_lightmap_lod_dev", "sol_lightmap_lod",
+               "sol_lightmap_charts_dev", "sol_lightmap_charts", "sol_lightmap_dilate_charts_dev", "sol_lightmap_dilate_charts",
+               "sol_lightmap_sample_charts_dev", "sol_lightmap_sample_charts", "sol_lightmap_chart_levels_dev", "sol_lightmap_chart_levels",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

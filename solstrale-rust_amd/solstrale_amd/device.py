@@ -193,6 +193,9 @@ def lightmap_mesh(description, first, count):
     return np.ascontiguousarray(V), np.ascontiguousarray(T)
 
 
+CHART_NONE = 0xFFFFFFFF  # SOL_CHART_NONE: a triangle or texel without chart (DeviceScene.lightmap_charts)
+
+
 def lightmap_mip_layout(width, height, levels=None):
     """The layout of a lightmap mip chain (sol_lightmap_mip_layout's rule) as a dict: `levels` - the count in force, level 0 counted
     (None or 0: all) -, `widths`, `heights` and `offsets` per level - W_l = (W_{l-1} + 1) // 2; offsets[l] is the first row of level l >= 1 in the
@@ -1341,6 +1344,153 @@ class DeviceScene:
         if sample_args.get("points") is not None:
             sample_args = {**sample_args, "vertices": vertices}
         out = self.lightmap_sample_lod(values, mips, cover, lods, coords, uvs, texels, width, height, **sample_args)
+        return out.reshape(h, w, -1)
+
+    # ---- lightmap charts (EXTENSION) ----
+    @staticmethod
+    def _host_array(x, dtype=None):
+        return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
+
+    @classmethod
+    def _host_words(cls, name, x):
+        """A host array (or device tensor) of chart labels as contiguous uint32 words: uint32 as it is, int32 reinterpreted; anything else is refused."""
+        a = cls._host_array(x)
+        if a.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)):
+            raise ValueError(f"{name}: 32-bit words (a uint32 or int32 array, or an int32 tensor), not {a.dtype}")
+        return a.view(np.uint32).reshape(-1)
+
+    def lightmap_charts(self, uvs, vertices=None):
+        """sol_lightmap_charts: the UV islands of a mesh. uvs [n, 3, 2] float32 and, optionally, vertices [n, 3, 3]: two triangles are connected
+        when they have an edge in common - the unordered pair of its end points, (u, v) or with vertices (u, v, x, y, z), equal as numbers. Returns
+        (chart_of_triangle [n] - dense ids in mesh order, CHART_NONE for a triangle with a word that is not finite -, n_charts). Host arrays go
+        the host route and return a uint32 array; device tensors the device route and return an int32 tensor holding the same words."""
+        if isinstance(uvs, np.ndarray) or not hasattr(uvs, "data_ptr"):  # the host route
+            u, vx = self._host_array(uvs, np.float32), self._host_array(vertices, np.float32)
+            if u.ndim != 3 or u.shape[1:] != (3, 2) or (vx is not None and vx.shape != (u.shape[0], 3, 3)):
+                raise ValueError("uvs: [n, 3, 2] float32; vertices: [n, 3, 3] float32 or None")
+            n = u.shape[0]
+            chart_of, n_charts = np.zeros(n, dtype=np.uint32), C.c_uint32(0)
+            self._chk(self.lib.sol_lightmap_charts(self.h, u.ctypes.data if n else None, vx.ctypes.data if (vx is not None and n) else None, n,
+                                                   chart_of.ctypes.data if n else None, C.addressof(n_charts)))
+            return chart_of, int(n_charts.value)
+        import torch
+        d_uvs = self._device_pointer("uvs", uvs, torch.float32, (None, 3, 2))
+        n = int(uvs.shape[0])
+        d_vertices = self._device_pointer("vertices", vertices, torch.float32, (n, 3, 3))
+        chart_of = torch.empty((n,), dtype=torch.int32, device=uvs.device)
+        n_charts = torch.zeros((1,), dtype=torch.int32, device=uvs.device)
+        torch.cuda.current_stream(uvs.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
+        self._chk(self.lib.sol_lightmap_charts_dev(self.h, d_uvs if n else None, d_vertices if n else None, n, C.c_void_p(chart_of.data_ptr()) if n else None,
+                                                   C.c_void_p(n_charts.data_ptr())))
+        self.sync()
+        return chart_of, int(n_charts.item())
+
+    def lightmap_dilate_charts(self, values, texels, chart_of_triangle, width, height, passes=1, channels=3):
+        """sol_lightmap_dilate_charts: lightmap_dilate that never averages across charts. chart_of_triangle: what lightmap_charts returned. A
+        texel is owned when its triangle has a chart; a texel filled in a pass joins the chart most of its covered neighbours hold (the lowest
+        id on a tie) and takes the mean of the neighbours of that chart only. Returns (out, pass_of [height, width] uint8, chart_plane
+        [height, width] - the chart of every texel, CHART_NONE where nothing reached). Host arrays go the host route, device tensors the device
+        route, decided by `values`."""
+        width, height = int(width), int(height)
+        wh = width * height
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
+            v = np.ascontiguousarray(values, dtype=np.float32)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            ch = self._host_words("chart_of_triangle", chart_of_triangle) if chart_of_triangle is not None else np.zeros(0, dtype=np.uint32)
+            if v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,):
+                raise ValueError("values: [width * height, k] float32 rows; texels: width * height LIGHTMAP_TEXEL_DTYPE rows")
+            out, pass_of, plane = np.zeros_like(v), np.zeros((height, width), dtype=np.uint8), np.zeros((height, width), dtype=np.uint32)
+            self._chk(self.lib.sol_lightmap_dilate_charts(self.h, t.ctypes.data, width, height, v.ctypes.data, int(channels), v.shape[1] * 4, int(passes),
+                                                          ch.ctypes.data if len(ch) else None, len(ch), out.ctypes.data, pass_of.ctypes.data, plane.ctypes.data))
+            return out, pass_of, plane
+        import torch
+        d_values = self._device_pointer("values", values, torch.float32, (wh, None))
+        d_texels = self._device_pointer("texels", texels, torch.int32, (wh, 4))
+        d_chart = self._device_pointer("chart_of_triangle", chart_of_triangle, torch.int32, (None,))
+        n_tri = int(chart_of_triangle.shape[0])
+        out = torch.empty_like(values)
+        pass_of = torch.empty((height, width), dtype=torch.uint8, device=values.device)
+        plane = torch.empty((height, width), dtype=torch.int32, device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()
+        self._chk(self.lib.sol_lightmap_dilate_charts_dev(self.h, d_texels, width, height, d_values, int(channels), int(values.shape[1]) * 4, int(passes),
+                                                          d_chart if n_tri else None, n_tri, C.c_void_p(out.data_ptr()), C.c_void_p(pass_of.data_ptr()),
+                                                          C.c_void_p(plane.data_ptr())))
+        self.sync()
+        return out, pass_of, plane
+
+    def lightmap_sample_charts(self, values, coords, uvs, texels, chart_of_triangle, chart_plane, width, height, channels=3, pass_of=None, nearest=False):
+        """sol_lightmap_sample_charts: lightmap_sample guarded by chart id. chart_of_triangle: what lightmap_charts returned; chart_plane (and
+        pass_of): what lightmap_dilate_charts returned. A tap contributes when it is inside, covered and finite and its plane word is the chart of
+        the row's triangle - a dilated tap of a neighbouring chart included; a row whose triangle has no chart answers zeros. Returns
+        [n, channels + 1] float32 rows as lightmap_sample does. Host arrays go the host route, device tensors the device route, decided by `values`."""
+        width, height, channels = int(width), int(height), int(channels)
+        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
+        cfg = _abi.SolLightmapSampleConfig(size=C.sizeof(_abi.SolLightmapSampleConfig), width=width, height=height, channels=channels, stride_bytes=4 * k,
+                                           flags=_abi.SOL_LIGHTMAP_SAMPLE_NEAREST if nearest else 0, chart_radius=float("inf"))
+        out_words = channels + 1 if 1 <= channels <= 32 else 1
+        wh = width * height
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
+            v, u, po = self._host_array(values, np.float32), self._host_array(uvs, np.float32), self._host_array(pass_of, np.uint8)
+            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
+            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
+            ch, pl = self._host_words("chart_of_triangle", chart_of_triangle), self._host_words("chart_plane", chart_plane)
+            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
+                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or ch.shape != (u.shape[0],) or pl.shape != (wh,)):
+                raise ValueError("values: [width * height, k] float32 rows; texels, coords: LIGHTMAP_TEXEL_DTYPE rows; uvs: [n, 3, 2]; pass_of: width * height "
+                                 "bytes; chart_of_triangle: n words; chart_plane: width * height words")
+            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
+            self._chk(self.lib.sol_lightmap_sample_charts(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
+                                                          None if po is None else po.ctypes.data, v.ctypes.data, ch.ctypes.data if len(ch) else None,
+                                                          pl.ctypes.data, c.ctypes.data, c.shape[0], out.ctypes.data))
+            return out
+        import torch
+        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
+        dev = self._device_pointer
+        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
+                dev("values", values, torch.float32, (wh, None)), dev("chart_of_triangle", chart_of_triangle, torch.int32, (n_tri,)),
+                dev("chart_plane", chart_plane, torch.int32, (height, width)), dev("coords", coords, torch.int32, (None, 4)), int(coords.shape[0]))
+        out = torch.empty((int(coords.shape[0]), out_words), dtype=torch.float32, device=values.device)
+        torch.cuda.current_stream(values.device).synchronize()
+        self._chk(self.lib.sol_lightmap_sample_charts_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
+        self.sync()
+        return out
+
+    def lightmap_chart_levels(self, chart_plane, width, height, pass_of=None):
+        """sol_lightmap_chart_levels: how many mip levels the atlas can have before two charts meet in one level - the `levels` to hand to
+        lightmap_mips. chart_plane [height, width]: what lightmap_dilate_charts returned; pass_of: its plane, or None (every texel with a chart
+        counts). Returns (levels, mixed_texels [15], mixed_windows [15]): per level l >= 1 the texels that hold two charts and the 2 x 2 windows -
+        a bilinear footprint - that do. A host array goes the host route, a device tensor the device route."""
+        width, height = int(width), int(height)
+        if isinstance(chart_plane, np.ndarray) or not hasattr(chart_plane, "data_ptr"):  # the host route
+            pl, po = self._host_words("chart_plane", chart_plane), self._host_array(pass_of, np.uint8)
+            if pl.shape != (width * height,) or (po is not None and po.size != width * height):
+                raise ValueError("chart_plane: width * height 32-bit words; pass_of: width * height bytes")
+            levels = C.c_uint32(0)
+            mixed_texels, mixed_windows = np.zeros(_abi.SOL_LIGHTMAP_MAX_LEVELS, dtype=np.uint32), np.zeros(_abi.SOL_LIGHTMAP_MAX_LEVELS, dtype=np.uint32)
+            self._chk(self.lib.sol_lightmap_chart_levels(self.h, pl.ctypes.data, None if po is None else po.ctypes.data, width, height, C.addressof(levels),
+                                                         mixed_texels.ctypes.data, mixed_windows.ctypes.data))
+            return int(levels.value), mixed_texels, mixed_windows
+        import torch
+        d_plane = self._device_pointer("chart_plane", chart_plane, torch.int32, (height, width))
+        d_pass = self._device_pointer("pass_of", pass_of, torch.uint8, (height, width))
+        answer = torch.zeros((1 + 2 * _abi.SOL_LIGHTMAP_MAX_LEVELS,), dtype=torch.int32, device=chart_plane.device)
+        torch.cuda.current_stream(chart_plane.device).synchronize()
+        base = answer.data_ptr()
+        self._chk(self.lib.sol_lightmap_chart_levels_dev(self.h, d_plane, d_pass, width, height, C.c_void_p(base), C.c_void_p(base + 4),
+                                                         C.c_void_p(base + 4 + 4 * _abi.SOL_LIGHTMAP_MAX_LEVELS)))
+        self.sync()
+        words = answer.cpu().numpy().view(np.uint32)
+        return int(words[0]), words[1:1 + _abi.SOL_LIGHTMAP_MAX_LEVELS].copy(), words[1 + _abi.SOL_LIGHTMAP_MAX_LEVELS:].copy()
+
+    def lightmap_view_charts(self, values, uvs, texels, chart_of_triangle, chart_plane, width, height, triangle_of_dfs, x0, y0, x1, y1, sample=0, seed=0,
+                             **sample_args):
+        """The bake seen from the scene's camera with the charts kept apart: camera_rays -> closest_hits -> lightmap_coords ->
+        lightmap_sample_charts over the pixels [x0, x1) x [y0, y1), all on device memory. sample_args: what lightmap_sample_charts takes by name
+        (channels, pass_of, nearest). Returns an [h, w, channels + 1] float32 device tensor."""
+        rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
+        h, w = int(rays.shape[0]), int(rays.shape[1])
+        coords = self.lightmap_coords(self.closest_hits(rays.reshape(-1, 8)), triangle_of_dfs)
+        out = self.lightmap_sample_charts(values, coords, uvs, texels, chart_of_triangle, chart_plane, width, height, **sample_args)
         return out.reshape(h, w, -1)
 
     # ---- irradiance volumes (EXTENSION; DESIGN.md 24) ----
