@@ -1,7 +1,8 @@
 """The growth orders of a handle's device buffers that random call sequences reach only by luck: every scratch buffer and table of a handle is
 a DevBuf (csrc/sol_scene.h) that is freed and allocated again when a call needs more than it holds. Each case drives one long-lived handle through
 such an order and compares it bit for bit with a fresh handle that made only the last call: a buffer that grew must hold nothing of its past, and
-one that did not must still be large enough."""
+one that did not must still be large enough.
+The scratch of the queries, gathers, lightmap and volume calls, shared between families, is under the same rule in tests/test_gpu_scratch_reuse.py."""
 import numpy as np
 import pytest
 

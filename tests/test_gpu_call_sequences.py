@@ -1,5 +1,8 @@
-"""Random call sequences against a live handle (the companion of tests/test_desc_mutations.py on the other side of sol_scene_create): every
-entry point that takes a `SolScene*` is called in seeded random order with arguments from pools that hold the legal values, the edges
+"""Random call sequences against a live handle (the companion of tests/test_desc_mutations.py on the other side of sol_scene_create): the
+entry points of the render path that take a `SolScene*` - partition, options, renders, auxiliary planes, reads, post-processing, statistics,
+diagnostics, the accumulator and the communicator calls a single rank can make; the ray queries, gathers, lightmap, volume and move calls that
+came later are the subject of tests/test_gpu_call_sequences_ext.py, and tests/test_call_sequence_coverage.py checks that the two files together
+leave no entry point out - are called in seeded random order with arguments from pools that hold the legal values, the edges
 (0, 15 / 16 / 17 samples, rank = world - 1, more ranks than blocks) and the illegal ones (null pointers, rank >= world, unknown options, a
 NaN bloom kernel, sample ranges that wrap 32 bits, struct sizes of 0 and 2^32 - 1). Contract (SURVEY 8b "Errors"): every call
 returns a code - never an abort, a fault or a hang - and whatever the sequence did, the handle afterwards renders the frame a fresh handle
