@@ -676,7 +676,20 @@ const char* sol_last_error(void);
  *                       stops early where it may).
  * n == 0 succeeds and does nothing. SOL_EINVAL: n above 2^31, an unknown mode, a null pointer, a scene with a constant medium (its hits are
  * random draws keyed by a path; a query has none). SOL_EDEVICE without a GPU. A query touches neither the accumulator, the auxiliary planes,
- * the partition nor an adaptive session, and works for any rank / world (the scene is replicated). */
+ * the partition nor an adaptive session, and works for any rank / world (the scene is replicated).
+ *   Origins.  The fp32 contract's margins are sized by the scene, not by the ray: boxes are padded by S * 2^-20 and a sphere's hit point may
+ *             lie S * 2^-21 outside the sphere's own box (rules 1 and 2), where S is the largest |coordinate|, cast to float, of
+ *             the world's bounding box (the bbox of the description's root) and of the camera origin of the description the handle was
+ *             CREATED from (sol_scene_set_camera does not change S; sol_scene_set_triangles / _set_primitives take the moved boxes). A ray
+ *             from origin o carries a rounding error of about |o| * 2^-23 in its hit points and slab parameters. While every coordinate of
+ *             the origin stays within 4 * S, the answers are the contract's: the same for every world tree, equal to the float oracle's,
+ *             and every hit that the reference's f64 arithmetic finds clear of a primitive's edge is found (measured clean up to 16 * S,
+ *             one rung of 4 kept as margin: profiles/far_origins.txt, tests/test_far_origins.py, tests/test_gpu_far_origins.py). Beyond
+ *             that every origin that is finite stays VALID, the calls return and each ray is answered SOL_RAY_HIT with a finite t in
+ *             [tmin, tmax] and an existing primitive, or SOL_RAY_MISS; but hits may be lost - first at the poles of spheres seen along an
+ *             axis (64 * S), then on flat primitives (quads, axis-aligned triangles) whose boxes are flat (256 * S in the float oracle,
+ *             4096 * S on the device, whose quantised boxes are fatter) -, and from 4096 * S on the answer may depend on the world tree.
+ *             A caller with such rays moves the origin along the ray to within 4 * S and shifts tmin, tmax and the returned t by that step. */
 typedef struct SolRay { float ox, oy, oz, tmin, dx, dy, dz, tmax; } SolRay;        /* 32 bytes; 16-byte aligned in device memory */
 typedef struct SolRayHit { float t, u, v; uint32_t status, kind, dfs_index, material, reserved; } SolRayHit; /* 32 bytes */
 enum { SOL_QUERY_CLOSEST = 0, SOL_QUERY_OCCLUDED = 1 };
@@ -731,7 +744,10 @@ int sol_camera_ray_keys(SolScene* scene, uint32_t x0, uint32_t y0, uint32_t x1, 
  * is the multi-rank image gather; hence the name.)
  *   Points.   A point is a SolRay row read as (position xyz, tmin, normal xyz, tmax), valid by the ray queries' rule exactly as it stands: every
  *             word finite (tmax may be +inf), the normal not zero, 0 <= tmin <= tmax. The normal need not be unit length (its squared length
- *             must be a finite, normal fp32 number). An invalid point answers (0, 0, 0, samples = 0), decided before any search.
+ *             must be a finite, normal fp32 number). An invalid point answers (0, 0, 0, samples = 0), decided before any search. A position is
+ *             the origin of the rays gathered from it: the origin envelope of the ray queries (SolRay, "Origins": every coordinate within
+ *             4 * S for the contract's answers; beyond it proper answers, with hits that may be lost) holds for positions as it stands, in
+ *             every gather that takes such rows (sol_irradiance*, sol_visibility*, sol_volume_points' probes).
  *   Paths.    For a valid point i, each sample s in [first_sample, first_sample + samples) is one path: the RNG stream of (seed, key, s) with
  *             its counter set to first_draw, (key, first_draw) by sol_radiance's rules (the point's SolRayKey or, with keys == NULL,
  *             (key_base + i wrapping, the configuration's first_draw)). The direction is drawn from that generator:
@@ -1575,6 +1591,11 @@ int sol_lightmap_chart_levels(SolScene* scene, const uint32_t* chart_plane, cons
  *   Work order: the creation probe's block costs describe the old view and are dropped - launches run in plain chunk-major order, background
  *          blocks last; the fine tail and the balanced partition keep what creation measured. SOL_CAMERA_REPROBE runs creation's 4-spp cost
  *          probe again for the new camera (a no-op where creation ran none; SOL_EINVAL while world > 1). Images do not depend on it either.
+ *   Far cameras: the handle keeps the box pad of its creation (S of the creation description: SolRay, "Origins"), a fresh handle would take the
+ *          new camera's origin into S. The byte identity above is tested for cameras beside the scene and was MEASURED to hold on
+ *          one scene up to 256 * S along two axes (profiles/far_origins.txt); what is promised for a camera further than 4 * S (creation's S)
+ *          from the origin is the origin envelope's second half: proper frames and answers, in which hits may be lost. A caller that
+ *          moves that far creates a new handle.
  * SOL_EINVAL, before the device is touched: a null scene or camera, a size below 8 or above 4096, unknown flag bits, a non-zero reserved field.
  * SOL_EDEVICE: runtime errors; the handle is then as it was, or has the new camera and no background table - never the new camera with the
  * old table. With sol_kernel_timing on, sol_last_kernel_ms after a call without SOL_CAMERA_REPROBE is the proof kernel's duration. */

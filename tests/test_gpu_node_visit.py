@@ -14,6 +14,7 @@ import pytest
 
 import orc
 import parity_util as pu
+from far_rays import host_triangle_hits
 from solstrale_amd import CameraConfig, DeviceScene, PathTracingShader, RenderConfig, SceneBuilder, _abi, world_tree_check
 
 pytestmark = pytest.mark.gpu
@@ -88,51 +89,6 @@ def oracle_hits(sc, rays):
         if lib.orc_closest_hit(sc.desc_ptr, orc.ORC_F32, o, d, C.byref(tt), C.byref(mm)):
             status[i], t[i], mat[i] = HIT, np.float32(tt.value), mm.value
     return status, t, mat
-
-
-def host_triangle_hits(sc, rays):
-    """The closest triangle hit of every ray by the fp32 contract, evaluated here over all triangles: (t, dfs_index, u, v); t = inf: none.
-    Records: rotated to start at the vertex opposite the longest edge (solstrale_hip.h, sol_triangle_rotation / sol_triangle_rotated), in
-    double, then rounded to float. Test: Moller-Trumbore in the operation order of tri_test, sums left to right, one IEEE division; among
-    equal t the LAST triangle in depth-first order wins."""
-    d = sc.desc
-    n = d.n_triangles
-    v0, e1, e2, dfs = np.empty((n, 3)), np.empty((n, 3)), np.empty((n, 3)), np.empty(n, np.uint32)
-    for i in range(n):
-        s = d.triangles[i]
-        p, a, b = np.array(s.v0[:]), np.array(s.v0v1[:]), np.array(s.v0v2[:])
-        c = b - a
-        l01, l02, l12 = (a * a).sum(), (b * b).sum(), (c * c).sum()
-        k, best = 0, l12
-        if l02 > best:
-            best, k = l02, 1
-        if l01 > best:
-            k = 2
-        v0[i], e1[i], e2[i] = [(p, a, b), (p + a, b - a, -a), (p + b, -b, a - b)][k]
-        dfs[i] = s.dfs_index
-    v0, e1, e2 = v0.astype(F), e1.astype(F), e2.astype(F)
-    ox, oy, oz = (rays[:, k].astype(F)[:, None] for k in (0, 1, 2))
-    dx, dy, dz = (rays[:, k].astype(F)[:, None] for k in (4, 5, 6))
-    col = lambda m: (m[None, :, 0], m[None, :, 1], m[None, :, 2])
-    (ax, ay, az), (bx, by, bz), (vx, vy, vz) = col(e1), col(e2), col(v0)
-    dot = lambda x0, y0, z0, x1, y1, z1: (x0 * x1 + y0 * y1) + z0 * z1
-    with np.errstate(all="ignore"):
-        px, py, pz = dy * bz - dz * by, dz * bx - dx * bz, dx * by - dy * bx  # cross3(d, e2)
-        det = dot(ax, ay, az, px, py, pz)
-        inv = F(1.0) / det
-        tx, ty, tz = ox - vx, oy - vy, oz - vz
-        qx, qy, qz = ty * az - tz * ay, tz * ax - tx * az, tx * ay - ty * ax  # cross3(t_vec, e1)
-        u = dot(tx, ty, tz, px, py, pz) * inv
-        v = dot(dx, dy, dz, qx, qy, qz) * inv
-        t = dot(bx, by, bz, qx, qy, qz) * inv
-        assert u.dtype == F and t.dtype == F
-        ok = ~(np.abs(det) < F(1e-8)) & (u >= 0) & (u <= 1) & ~((v < 0) | (u + v > F(1.0))) & (t >= F(0.001))
-    t = np.where(ok, t, F(np.inf))
-    tbest = t.min(axis=1)
-    tie = (t == tbest[:, None]) & ok
-    win = np.where(tie, dfs[None, :].astype(np.int64), -1).argmax(axis=1)
-    r = np.arange(len(rays))
-    return tbest, dfs[win], u[r, win], v[r, win]
 
 
 def test_tree_has_inner_levels_and_partly_filled_nodes():
