@@ -1,14 +1,15 @@
 // sol_depth.cpp -- sol_visibility_oct, sol_volume_build_depth and sol_volume_sample_depth (include/solstrale_hip.h): the directional
 // distance moments of an irradiance volume (kernels: sol_depth.hip; the rule: sol_depth.h). The gather is a visibility gather: it shares the
 // radiance queries' scratch and staging (SolScene::rad_*) and their launch plan; build and sample trace nothing and stage through
-// SolScene::vol_stage. Every refusal is decided before the device is looked for.
+// SolScene::vol_stage (SolStaged, sol_stage.h). Every refusal is decided before the device is looked for.
 #include <algorithm>
 #include <cmath>
 
+#include "sol_bake_checks.h"
 #include "sol_gather.h"
+#include "sol_stage.h"
 
 namespace {
-constexpr size_t DEPTH_MAX_POINTS = (size_t)1 << 31;
 constexpr size_t DEPTH_STAGE_TEXELS = (size_t)1 << 24;  // the gather's host route stages at most this many SolOctTexel rows at a time (256 MiB)
 
 int oct_config_check(const char* fn, const SolOctConfig* c) {
@@ -42,7 +43,7 @@ int sample_check(bool have_scene, const char* fn, const SolVolumeGrid* g, const 
                  const void* out) {
   if (const int rc = sol_volume_grid_check(have_scene, fn, g)) return rc;
   if (const int rc = oct_config_check(fn, c)) return rc;
-  if (n > DEPTH_MAX_POINTS) return sol_fail(SOL_EINVAL, "%s: %zu points in one call (at most 2^31)", fn, n);
+  if (const int rc = sol_rows_check(fn, n, "points")) return rc;
   if (n > 0 && (!probes || !depth || !points || !out))
     return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !probes ? "probe" : !depth ? "depth" : !points ? "point" : "output");
   return SOL_OK;
@@ -60,6 +61,15 @@ int gather_launch(SolScene* s, const void* points_dev, const void* keys_dev, siz
                                      s->stream));
     return SOL_OK;
   });
+}
+
+int build_launch(SolScene* s, size_t n_texels, const void* oct, float radius, void* depth) {
+  HIP_TRY(sol_launch_depth_build((uint64_t)n_texels, oct, radius, depth, s->stream));
+  return SOL_OK;
+}
+int sample_launch(SolScene* s, const SolVolumeGrid& g, const void* probes, const void* depth, uint32_t res, const void* points, size_t n, void* out) {
+  HIP_TRY(sol_launch_volume_sample_depth(g, probes, depth, res, points, (uint32_t)n, out, s->stream));
+  return SOL_OK;
 }
 }  // namespace
 
@@ -85,59 +95,39 @@ int sol_visibility_oct(SolScene* s, const SolRay* points, const SolRayKey* keys,
 
 int sol_volume_build_depth_dev(SolScene* s, const SolVolumeGrid* grid, const void* oct_dev, const SolOctConfig* oct, float radius, void* depth_out_dev) {
   int rc;
-  if ((rc = build_check(s != nullptr, "sol_volume_build_depth_dev", grid, oct_dev, oct, radius, depth_out_dev)) || (rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_depth_build((uint64_t)probes_of(*grid) * oct->res * oct->res, oct_dev, radius, depth_out_dev, s->stream));
-  return SOL_OK;
+  if ((rc = build_check(s != nullptr, "sol_volume_build_depth_dev", grid, oct_dev, oct, radius, depth_out_dev)) || (rc = sol_device_enter(s))) return rc;
+  return build_launch(s, probes_of(*grid) * oct->res * oct->res, oct_dev, radius, depth_out_dev);
 }
 
 int sol_volume_build_depth(SolScene* s, const SolVolumeGrid* grid, const SolOctTexel* oct_rows, const SolOctConfig* oct, float radius, SolDepthTexel* depth_out) {
   int rc;
-  if ((rc = build_check(s != nullptr, "sol_volume_build_depth", grid, oct_rows, oct, radius, depth_out)) || (rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = build_check(s != nullptr, "sol_volume_build_depth", grid, oct_rows, oct, radius, depth_out)) || (rc = sol_device_enter(s))) return rc;
   const size_t n = probes_of(*grid) * oct->res * oct->res;
-  SolStage st;
-  const size_t at_in = st.add(n * sizeof(SolOctTexel)), at_out = st.add(n * sizeof(SolDepthTexel));
-  if ((rc = s->vol_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->vol_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_in, oct_rows, n * sizeof(SolOctTexel), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(sol_launch_depth_build((uint64_t)n, base + at_in, radius, base + at_out, s->stream));
-  HIP_TRY(hipMemcpyAsync(depth_out, base + at_out, n * sizeof(SolDepthTexel), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->vol_stage);
+  const int oc = st.in(oct_rows, n * sizeof(SolOctTexel)), o = st.out(depth_out, n * sizeof(SolDepthTexel));
+  if ((rc = st.upload()) || (rc = build_launch(s, n, st[oc], radius, st[o]))) return rc;
+  return st.finish();
 }
 
 int sol_volume_sample_depth_dev(SolScene* s, const SolVolumeGrid* grid, const void* probes_dev, const void* depth_dev, const SolOctConfig* oct, const void* points_dev,
                                 size_t n, void* out_dev) {
   int rc;
-  if ((rc = sample_check(s != nullptr, "sol_volume_sample_depth_dev", grid, probes_dev, depth_dev, oct, points_dev, n, out_dev))) return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_volume_sample_depth(*grid, probes_dev, depth_dev, oct->res, points_dev, (uint32_t)n, out_dev, s->stream));
-  return SOL_OK;
+  if ((rc = sample_check(s != nullptr, "sol_volume_sample_depth_dev", grid, probes_dev, depth_dev, oct, points_dev, n, out_dev)) || n == 0 ||
+      (rc = sol_device_enter(s)))
+    return rc;
+  return sample_launch(s, *grid, probes_dev, depth_dev, oct->res, points_dev, n, out_dev);
 }
 
 int sol_volume_sample_depth(SolScene* s, const SolVolumeGrid* grid, const SolProbe* probes, const SolDepthTexel* depth, const SolOctConfig* oct, const SolRay* points,
                             size_t n, SolRadiance* out) {
   int rc;
-  if ((rc = sample_check(s != nullptr, "sol_volume_sample_depth", grid, probes, depth, oct, points, n, out))) return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = sample_check(s != nullptr, "sol_volume_sample_depth", grid, probes, depth, oct, points, n, out)) || n == 0 || (rc = sol_device_enter(s))) return rc;
   const size_t np = probes_of(*grid), nt = np * oct->res * oct->res;
-  SolStage st;
-  const size_t at_probes = st.add(np * sizeof(SolProbe)), at_depth = st.add(nt * sizeof(SolDepthTexel)), at_points = st.add(n * sizeof(SolRay)),
-               at_out = st.add(n * sizeof(SolRadiance));
-  if ((rc = s->vol_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->vol_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_probes, probes, np * sizeof(SolProbe), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_depth, depth, nt * sizeof(SolDepthTexel), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_points, points, n * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(sol_launch_volume_sample_depth(*grid, base + at_probes, base + at_depth, oct->res, base + at_points, (uint32_t)n, base + at_out, s->stream));
-  HIP_TRY(hipMemcpyAsync(out, base + at_out, n * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->vol_stage);
+  const int pr = st.in(probes, np * sizeof(SolProbe)), d = st.in(depth, nt * sizeof(SolDepthTexel)), p = st.in(points, n * sizeof(SolRay));
+  const int o = st.out(out, n * sizeof(SolRadiance));
+  if ((rc = st.upload()) || (rc = sample_launch(s, *grid, st[pr], st[d], oct->res, st[p], n, st[o]))) return rc;
+  return st.finish();
 }
 
 }  // extern "C"

@@ -33,8 +33,7 @@ int sol_gather_entry(SolScene* s, const Config* config, Check&& check, Run&& run
   const SolRadianceConfig* cfg = sol_gather_config(config, as);
   bool go = false;
   int rc;
-  if ((rc = check(cfg, &go)) || !go || (rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = check(cfg, &go)) || !go || (rc = sol_device_enter(s))) return rc;
   return run(*cfg);
 }
 

@@ -1,35 +1,24 @@
 // sol_lightmap_charts.cpp -- sol_lightmap_charts, sol_lightmap_dilate_charts, sol_lightmap_sample_charts and sol_lightmap_chart_levels
 // (include/solstrale_hip.h): UV islands labelled on the device, the dilation and the lookup that keep them apart, and the count of
 // mip levels before two of them meet (kernels: sol_lightmap_charts.hip; the rule: sol_lightmap_charts.h). The handle supplies the device, the
-// stream, the scratch (SolScene::lm_owner) and the staging of the host routes (SolScene::lm_stage); the scene itself is not read: nothing is
-// traced. Every refusal is decided before the device is looked for, from the arguments alone - the checks below are not given the handle's
-// contents, only whether there is one.
+// stream, the scratch (SolScene::lm_owner) and the staging of the host routes (SolScene::lm_stage through SolStaged, sol_stage.h); the scene
+// itself is not read: nothing is traced. Every refusal is decided before the device is looked for, from the arguments alone - the checks below
+// (their shared sentences: sol_bake_checks.h; the 2^30 triangles are this family's own) are not given the handle's contents, only whether there
+// is one.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
-#include "sol_scene.h"
+#include "sol_bake_checks.h"
+#include "sol_stage.h"
 
 namespace {
 constexpr size_t LC_MAX_TRIANGLES = SOL_LIGHTMAP_CHARTS_MAX_TRIANGLES;
-constexpr size_t LC_MAX_ROWS = (size_t)1 << 31;
 
 // SOL_LIGHTMAP_CHARTS=collide: the edge hash masked to 4 bits, the tested worst case of the match (the same labels)
 bool charts_collide() {
   const char* e = std::getenv("SOL_LIGHTMAP_CHARTS");
   return e && std::strcmp(e, "collide") == 0;
-}
-
-int atlas_check(const char* fn, uint32_t width, uint32_t height) {
-  if (width == 0 || height == 0 || width > SOL_LIGHTMAP_MAX_SIZE || height > SOL_LIGHTMAP_MAX_SIZE)
-    return sol_fail(SOL_EINVAL, "%s: an atlas of %u x %u texels (1 .. %u each way)", fn, width, height, SOL_LIGHTMAP_MAX_SIZE);
-  return SOL_OK;
-}
-int rows_check(const char* fn, uint32_t channels, uint32_t stride_bytes) {
-  if (channels == 0 || channels > 32) return sol_fail(SOL_EINVAL, "%s: %u channels (1 .. 32)", fn, channels);
-  if (stride_bytes % 4 != 0 || stride_bytes / 4 < channels)
-    return sol_fail(SOL_EINVAL, "%s: a stride of %u bytes (a multiple of 4, at least 4 x %u channels)", fn, stride_bytes, channels);
-  return SOL_OK;
 }
 
 int charts_check(bool have_scene, const char* fn, const void* uvs, size_t n, const void* chart_of, const void* n_charts) {
@@ -40,13 +29,25 @@ int charts_check(bool have_scene, const char* fn, const void* uvs, size_t n, con
   return SOL_OK;
 }
 
+// The labelling over n triangles; its scratch is sized here. (n == 0, the device route only: the launch writes *n_charts = 0.)
+int charts_launch(SolScene* s, const void* uvs, const void* vertices, size_t n_triangles, void* chart_of, void* n_charts) {
+  int rc;
+  const uint32_t n = (uint32_t)n_triangles;
+  LcScratch S{};
+  S.words = 1;
+  if (n) HIP_TRY(sol_lightmap_charts_scratch(n, S));
+  if ((rc = s->lm_owner.reserve(s->stream, S.words))) return rc;
+  HIP_TRY(sol_launch_lightmap_charts(uvs, vertices, n, charts_collide(), S, s->lm_owner.get(), chart_of, n_charts, s->stream));
+  return SOL_OK;
+}
+
 int dilate_check(bool have_scene, const char* fn, const void* texels, uint32_t width, uint32_t height, const void* values, uint32_t channels,
                  uint32_t stride_bytes, uint32_t passes, const void* chart_of, size_t n_triangles, const void* out, const void* pass_of, const void* plane) {
   int rc;
   if (!have_scene) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
   if (!texels || !values || !out || !pass_of || !plane)
     return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !texels ? "texel" : !values ? "value" : !out ? "output" : !pass_of ? "pass_of output" : "plane output");
-  if ((rc = atlas_check(fn, width, height)) || (rc = rows_check(fn, channels, stride_bytes))) return rc;
+  if ((rc = sol_atlas_check(fn, width, height)) || (rc = sol_channels_check(fn, channels, stride_bytes))) return rc;
   if (passes > 254) return sol_fail(SOL_EINVAL, "%s: %u passes (at most 254)", fn, passes);
   if (out == values) return sol_fail(SOL_EINVAL, "%s: out may not be values", fn);
   if (n_triangles > 0 && !chart_of) return sol_fail(SOL_EINVAL, "%s: null chart_of_triangle pointer", fn);
@@ -72,15 +73,12 @@ int sample_check(bool have_scene, const char* fn, const SolLightmapSampleConfig*
                  const void* chart_of, const void* plane, const void* coords, size_t n, const void* out) {
   int rc;
   if (!have_scene || !c) return sol_fail(SOL_EINVAL, "%s: null %s", fn, !have_scene ? "scene" : "configuration");
-  if (c->size != sizeof(SolLightmapSampleConfig))
-    return sol_fail(SOL_EINVAL, "%s: SolLightmapSampleConfig.size %u (expected %zu)", fn, c->size, sizeof(SolLightmapSampleConfig));
-  if (c->reserved) return sol_fail(SOL_EINVAL, "%s: SolLightmapSampleConfig.reserved must be 0", fn);
-  if (c->flags & ~SOL_LIGHTMAP_SAMPLE_NEAREST) return sol_fail(SOL_EINVAL, "%s: SolLightmapSampleConfig.flags 0x%x: unknown bits", fn, c->flags);
-  if ((rc = atlas_check(fn, c->width, c->height)) || (rc = rows_check(fn, c->channels, c->stride_bytes))) return rc;
+  if ((rc = sol_config_head_check(fn, "SolLightmapSampleConfig", *c, c->flags, SOL_LIGHTMAP_SAMPLE_NEAREST))) return rc;
+  if ((rc = sol_atlas_check(fn, c->width, c->height)) || (rc = sol_channels_check(fn, c->channels, c->stride_bytes))) return rc;
   if (!(std::isinf(c->chart_radius) && c->chart_radius > 0.0f))
     return sol_fail(SOL_EINVAL, "%s: chart_radius %g (+inf: the guard is the chart id)", fn, (double)c->chart_radius);
   if (n_triangles > LC_MAX_TRIANGLES) return sol_fail(SOL_EINVAL, "%s: %zu triangles in one call (at most 2^30)", fn, n_triangles);
-  if (n > LC_MAX_ROWS) return sol_fail(SOL_EINVAL, "%s: %zu rows in one call (at most 2^31)", fn, n);
+  if ((rc = sol_rows_check(fn, n, "rows"))) return rc;
   if ((n_triangles > 0 && (!uvs || !chart_of)) || !texels || !values || !plane || !coords || !out)
     return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn,
                     (n_triangles > 0 && !uvs)        ? "UV"
@@ -94,13 +92,27 @@ int sample_check(bool have_scene, const char* fn, const SolLightmapSampleConfig*
   return SOL_OK;
 }
 
+int sample_launch(SolScene* s, const SolLightmapSampleConfig& c, const void* uvs, size_t n_triangles, const void* texels, const void* pass_of, const void* values,
+                  const void* chart_of, const void* plane, const void* coords, size_t n, void* out) {
+  HIP_TRY(sol_launch_lightmap_sample_charts(c, (uint32_t)n_triangles, uvs, texels, pass_of, values, chart_of, plane, coords, (uint32_t)n, out, s->stream));
+  return SOL_OK;
+}
+
 int levels_check(bool have_scene, const char* fn, const void* plane, uint32_t width, uint32_t height, const void* levels, const void* mixed_texels,
                  const void* mixed_windows) {
   int rc;
   if (!have_scene) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if ((rc = atlas_check(fn, width, height))) return rc;
+  if ((rc = sol_atlas_check(fn, width, height))) return rc;
   if (!plane || !levels || !mixed_texels || !mixed_windows)
     return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !plane ? "plane" : !levels ? "levels" : !mixed_texels ? "mixed_texels" : "mixed_windows");
+  return SOL_OK;
+}
+
+// The plane reduced level by level in the scratch (L = lmm_layout(width, height, 0): L.rows words and a counter).
+int levels_launch(SolScene* s, const LmmLayout& L, const void* plane, const void* pass_of, void* levels, void* mixed_texels, void* mixed_windows) {
+  int rc;
+  if ((rc = s->lm_owner.reserve(s->stream, (size_t)L.rows + 1))) return rc;
+  HIP_TRY(sol_launch_lightmap_chart_levels(L, plane, pass_of, s->lm_owner.get(), levels, mixed_texels, mixed_windows, s->stream));
   return SOL_OK;
 }
 
@@ -111,16 +123,9 @@ extern "C" {
 int sol_lightmap_charts_dev(SolScene* s, const void* uvs_dev, const void* vertices_dev, size_t n_triangles, void* chart_of_triangle_out_dev,
                             void* n_charts_out_dev) {
   int rc;
-  if ((rc = charts_check(s != nullptr, "sol_lightmap_charts_dev", uvs_dev, n_triangles, chart_of_triangle_out_dev, n_charts_out_dev))) return rc;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  const uint32_t n = (uint32_t)n_triangles;
-  LcScratch S{};
-  S.words = 1;
-  if (n) HIP_TRY(sol_lightmap_charts_scratch(n, S));
-  if ((rc = s->lm_owner.reserve(s->stream, S.words))) return rc;
-  HIP_TRY(sol_launch_lightmap_charts(uvs_dev, vertices_dev, n, charts_collide(), S, s->lm_owner.get(), chart_of_triangle_out_dev, n_charts_out_dev, s->stream));
-  return SOL_OK;
+  if ((rc = charts_check(s != nullptr, "sol_lightmap_charts_dev", uvs_dev, n_triangles, chart_of_triangle_out_dev, n_charts_out_dev)) || (rc = sol_device_enter(s)))
+    return rc;
+  return charts_launch(s, uvs_dev, vertices_dev, n_triangles, chart_of_triangle_out_dev, n_charts_out_dev);
 }
 
 int sol_lightmap_charts(SolScene* s, const float* uvs, const float* vertices, size_t n_triangles, uint32_t* chart_of_triangle_out, uint32_t* n_charts_out) {
@@ -130,24 +135,13 @@ int sol_lightmap_charts(SolScene* s, const float* uvs, const float* vertices, si
     *n_charts_out = 0;
     return SOL_OK;
   }
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  const uint32_t n = (uint32_t)n_triangles;
+  if ((rc = sol_device_enter(s))) return rc;
   const size_t nt = n_triangles;
-  LcScratch S{};
-  HIP_TRY(sol_lightmap_charts_scratch(n, S));
-  SolStage st;
-  const size_t at_uv = st.add(nt * 6 * sizeof(float)), at_vx = st.add(vertices ? nt * 9 * sizeof(float) : 0), at_c = st.add(nt * sizeof(uint32_t));
-  const size_t at_n = st.add(sizeof(uint32_t));
-  if ((rc = s->lm_stage.reserve(s->stream, st.total)) || (rc = s->lm_owner.reserve(s->stream, S.words))) return rc;
-  char* base = s->lm_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_uv, uvs, nt * 6 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  if (vertices) HIP_TRY(hipMemcpyAsync(base + at_vx, vertices, nt * 9 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(sol_launch_lightmap_charts(base + at_uv, vertices ? base + at_vx : nullptr, n, charts_collide(), S, s->lm_owner.get(), base + at_c, base + at_n, s->stream));
-  HIP_TRY(hipMemcpyAsync(chart_of_triangle_out, base + at_c, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(n_charts_out, base + at_n, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int uv = st.in(uvs, nt * 6 * sizeof(float)), vx = st.in_opt(vertices, nt * 9 * sizeof(float));
+  const int c = st.out(chart_of_triangle_out, nt * sizeof(uint32_t)), n = st.out(n_charts_out, sizeof(uint32_t));
+  if ((rc = st.upload()) || (rc = charts_launch(s, st[uv], st[vx], nt, st[c], st[n]))) return rc;
+  return st.finish();
 }
 
 int sol_lightmap_dilate_charts_dev(SolScene* s, const void* texels_dev, uint32_t width, uint32_t height, const void* values_dev, uint32_t channels,
@@ -156,9 +150,8 @@ int sol_lightmap_dilate_charts_dev(SolScene* s, const void* texels_dev, uint32_t
   int rc;
   if ((rc = dilate_check(s != nullptr, "sol_lightmap_dilate_charts_dev", texels_dev, width, height, values_dev, channels, stride_bytes, passes,
                          chart_of_triangle_dev, n_triangles, out_dev, pass_of_out_dev, chart_plane_out_dev)) ||
-      (rc = sol_device_check()))
+      (rc = sol_device_enter(s)))
     return rc;
-  HIP_TRY(hipSetDevice(s->device));
   return dilate_launch(s, texels_dev, width, height, values_dev, channels, stride_bytes, passes, chart_of_triangle_dev, n_triangles, out_dev, pass_of_out_dev,
                        chart_plane_out_dev);
 }
@@ -169,25 +162,14 @@ int sol_lightmap_dilate_charts(SolScene* s, const SolTexel* texels, uint32_t wid
   int rc;
   if ((rc = dilate_check(s != nullptr, "sol_lightmap_dilate_charts", texels, width, height, values, channels, stride_bytes, passes, chart_of_triangle,
                          n_triangles, out, pass_of_out, chart_plane_out)) ||
-      (rc = sol_device_check()))
+      (rc = sol_device_enter(s)))
     return rc;
-  HIP_TRY(hipSetDevice(s->device));
   const size_t wh = (size_t)width * height, nt = n_triangles;
-  SolStage st;
-  const size_t at_t = st.add(wh * sizeof(SolTexel)), at_v = st.add(wh * stride_bytes), at_c = st.add(nt * sizeof(uint32_t)), at_o = st.add(wh * stride_bytes);
-  const size_t at_p = st.add(wh), at_pl = st.add(wh * sizeof(uint32_t));
-  if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->lm_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_t, texels, wh * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_v, values, wh * stride_bytes, hipMemcpyHostToDevice, s->stream));
-  if (nt) HIP_TRY(hipMemcpyAsync(base + at_c, chart_of_triangle, nt * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  if ((rc = dilate_launch(s, base + at_t, width, height, base + at_v, channels, stride_bytes, passes, base + at_c, nt, base + at_o, base + at_p, base + at_pl)))
-    return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + at_o, wh * stride_bytes, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(pass_of_out, base + at_p, wh, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(chart_plane_out, base + at_pl, wh * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int t = st.in(texels, wh * sizeof(SolTexel)), v = st.in(values, wh * stride_bytes), c = st.in(chart_of_triangle, nt * sizeof(uint32_t));
+  const int o = st.out(out, wh * stride_bytes), p = st.out(pass_of_out, wh), pl = st.out(chart_plane_out, wh * sizeof(uint32_t));
+  if ((rc = st.upload()) || (rc = dilate_launch(s, st[t], width, height, st[v], channels, stride_bytes, passes, st[c], nt, st[o], st[p], st[pl]))) return rc;
+  return st.finish();
 }
 
 int sol_lightmap_sample_charts_dev(SolScene* s, const SolLightmapSampleConfig* config, const void* uvs_dev, size_t n_triangles, const void* texels_dev,
@@ -195,45 +177,26 @@ int sol_lightmap_sample_charts_dev(SolScene* s, const SolLightmapSampleConfig* c
                                    const void* coords_dev, size_t n, void* out_dev) {
   int rc;
   if ((rc = sample_check(s != nullptr, "sol_lightmap_sample_charts_dev", config, uvs_dev, n_triangles, texels_dev, values_dev, chart_of_triangle_dev,
-                         chart_plane_dev, coords_dev, n, out_dev)))
+                         chart_plane_dev, coords_dev, n, out_dev)) ||
+      n == 0 || (rc = sol_device_enter(s)))
     return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_lightmap_sample_charts(*config, (uint32_t)n_triangles, uvs_dev, texels_dev, pass_of_dev, values_dev, chart_of_triangle_dev, chart_plane_dev,
-                                            coords_dev, (uint32_t)n, out_dev, s->stream));
-  return SOL_OK;
+  return sample_launch(s, *config, uvs_dev, n_triangles, texels_dev, pass_of_dev, values_dev, chart_of_triangle_dev, chart_plane_dev, coords_dev, n, out_dev);
 }
 
 int sol_lightmap_sample_charts(SolScene* s, const SolLightmapSampleConfig* config, const float* uvs, size_t n_triangles, const SolTexel* texels,
                                const uint8_t* pass_of, const void* values, const uint32_t* chart_of_triangle, const uint32_t* chart_plane, const SolTexel* coords,
                                size_t n, void* out) {
   int rc;
-  if ((rc = sample_check(s != nullptr, "sol_lightmap_sample_charts", config, uvs, n_triangles, texels, values, chart_of_triangle, chart_plane, coords, n, out)))
+  if ((rc = sample_check(s != nullptr, "sol_lightmap_sample_charts", config, uvs, n_triangles, texels, values, chart_of_triangle, chart_plane, coords, n, out)) ||
+      n == 0 || (rc = sol_device_enter(s)))
     return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
   const size_t wh = (size_t)config->width * config->height, row = config->stride_bytes, out_row = ((size_t)config->channels + 1) * 4, nt = n_triangles;
-  SolStage st;
-  const size_t at_uv = st.add(nt * 6 * sizeof(float)), at_t = st.add(wh * sizeof(SolTexel)), at_pass = st.add(pass_of ? wh : 0), at_v = st.add(wh * row);
-  const size_t at_ch = st.add(nt * sizeof(uint32_t)), at_pl = st.add(wh * sizeof(uint32_t)), at_c = st.add(n * sizeof(SolTexel)), at_o = st.add(n * out_row);
-  if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->lm_stage.get();
-  if (nt) {
-    HIP_TRY(hipMemcpyAsync(base + at_uv, uvs, nt * 6 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(base + at_ch, chart_of_triangle, nt * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  }
-  HIP_TRY(hipMemcpyAsync(base + at_t, texels, wh * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  if (pass_of) HIP_TRY(hipMemcpyAsync(base + at_pass, pass_of, wh, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_v, values, wh * row, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_pl, chart_plane, wh * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_c, coords, n * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(sol_launch_lightmap_sample_charts(*config, (uint32_t)nt, base + at_uv, base + at_t, pass_of ? base + at_pass : nullptr, base + at_v, base + at_ch,
-                                            base + at_pl, base + at_c, (uint32_t)n, base + at_o, s->stream));
-  HIP_TRY(hipMemcpyAsync(out, base + at_o, n * out_row, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int uv = st.in(uvs, nt * 6 * sizeof(float)), t = st.in(texels, wh * sizeof(SolTexel)), pass = st.in_opt(pass_of, wh), v = st.in(values, wh * row);
+  const int ch = st.in(chart_of_triangle, nt * sizeof(uint32_t)), pl = st.in(chart_plane, wh * sizeof(uint32_t)), c = st.in(coords, n * sizeof(SolTexel));
+  const int o = st.out(out, n * out_row);
+  if ((rc = st.upload()) || (rc = sample_launch(s, *config, st[uv], nt, st[t], st[pass], st[v], st[ch], st[pl], st[c], n, st[o]))) return rc;
+  return st.finish();
 }
 
 int sol_lightmap_chart_levels_dev(SolScene* s, const void* chart_plane_dev, const void* pass_of_dev, uint32_t width, uint32_t height, void* levels_out_dev,
@@ -241,14 +204,9 @@ int sol_lightmap_chart_levels_dev(SolScene* s, const void* chart_plane_dev, cons
   int rc;
   if ((rc = levels_check(s != nullptr, "sol_lightmap_chart_levels_dev", chart_plane_dev, width, height, levels_out_dev, mixed_texels_out_dev,
                          mixed_windows_out_dev)) ||
-      (rc = sol_device_check()))
+      (rc = sol_device_enter(s)))
     return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  const LmmLayout L = lmm_layout(width, height, 0);
-  if ((rc = s->lm_owner.reserve(s->stream, (size_t)L.rows + 1))) return rc;
-  HIP_TRY(sol_launch_lightmap_chart_levels(L, chart_plane_dev, pass_of_dev, s->lm_owner.get(), levels_out_dev, mixed_texels_out_dev, mixed_windows_out_dev,
-                                           s->stream));
-  return SOL_OK;
+  return levels_launch(s, lmm_layout(width, height, 0), chart_plane_dev, pass_of_dev, levels_out_dev, mixed_texels_out_dev, mixed_windows_out_dev);
 }
 
 int sol_lightmap_chart_levels(SolScene* s, const uint32_t* chart_plane, const uint8_t* pass_of, uint32_t width, uint32_t height, uint32_t* levels_out,
@@ -262,21 +220,13 @@ int sol_lightmap_chart_levels(SolScene* s, const uint32_t* chart_plane, const ui
     std::memset(mixed_windows_out, 0, SOL_LIGHTMAP_MAX_LEVELS * sizeof(uint32_t));
     return SOL_OK;
   }
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = sol_device_enter(s))) return rc;
   const size_t wh = (size_t)width * height, counts = SOL_LIGHTMAP_MAX_LEVELS * sizeof(uint32_t);
-  SolStage st;
-  const size_t at_pl = st.add(wh * sizeof(uint32_t)), at_p = st.add(pass_of ? wh : 0), at_l = st.add(sizeof(uint32_t)), at_mt = st.add(counts), at_mw = st.add(counts);
-  if ((rc = s->lm_stage.reserve(s->stream, st.total)) || (rc = s->lm_owner.reserve(s->stream, (size_t)L.rows + 1))) return rc;
-  char* base = s->lm_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_pl, chart_plane, wh * sizeof(uint32_t), hipMemcpyHostToDevice, s->stream));
-  if (pass_of) HIP_TRY(hipMemcpyAsync(base + at_p, pass_of, wh, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(sol_launch_lightmap_chart_levels(L, base + at_pl, pass_of ? base + at_p : nullptr, s->lm_owner.get(), base + at_l, base + at_mt, base + at_mw, s->stream));
-  HIP_TRY(hipMemcpyAsync(levels_out, base + at_l, sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(mixed_texels_out, base + at_mt, counts, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(mixed_windows_out, base + at_mw, counts, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int pl = st.in(chart_plane, wh * sizeof(uint32_t)), p = st.in_opt(pass_of, wh);
+  const int l = st.out(levels_out, sizeof(uint32_t)), mt = st.out(mixed_texels_out, counts), mw = st.out(mixed_windows_out, counts);
+  if ((rc = st.upload()) || (rc = levels_launch(s, L, st[pl], st[p], st[l], st[mt], st[mw]))) return rc;
+  return st.finish();
 }
 
 }  // extern "C"

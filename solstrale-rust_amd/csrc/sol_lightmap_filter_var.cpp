@@ -1,22 +1,20 @@
 // sol_lightmap_filter_var.cpp -- sol_lightmap_filter_var (include/solstrale_hip.h): a baked atlas filtered on the device under the
 // guidance of its own per-texel variance (kernels: sol_lightmap_filter_var.hip; the rule: sol_lightmap_filter_var.h). The handle supplies the
 // device, the stream and the scratch - sol_lightmap_filter's: SolScene::lf_guide, and lf_planes holding the two sides' mean and variance planes
-// (both calls write all they read of them first); lm_stage for the host route -; the scene itself is not read: nothing is traced. Every refusal is
-// decided before the device is looked for, by a function that gets the arguments and not the handle.
+// (both calls write all they read of them first); lm_stage for the host route, laid out by SolStaged (sol_stage.h) -; the scene itself is not
+// read: nothing is traced. Every refusal is decided before the device is looked for (sol_device_enter), by a function that gets the arguments and
+// not the handle; the sentences other families share are sol_bake_checks.h's, their order is this file's.
 #include <cmath>
 
-#include "sol_scene.h"
+#include "sol_bake_checks.h"
+#include "sol_stage.h"
 
 namespace {
 int filter_var_check(bool have_scene, const char* fn, const SolLightmapFilterVarConfig* c, const void* points, const void* texels, const void* moments,
                      const void* out, const void* variance_out) {
   if (!have_scene || !c) return sol_fail(SOL_EINVAL, "%s: null %s", fn, !have_scene ? "scene" : "configuration");
-  if (c->size != sizeof(SolLightmapFilterVarConfig))
-    return sol_fail(SOL_EINVAL, "%s: SolLightmapFilterVarConfig.size %u (expected %zu)", fn, c->size, sizeof(SolLightmapFilterVarConfig));
-  for (uint32_t r : c->reserved)
-    if (r) return sol_fail(SOL_EINVAL, "%s: SolLightmapFilterVarConfig.reserved must be 0", fn);
-  if (c->width == 0 || c->height == 0 || c->width > SOL_LIGHTMAP_MAX_SIZE || c->height > SOL_LIGHTMAP_MAX_SIZE)
-    return sol_fail(SOL_EINVAL, "%s: an atlas of %u x %u texels (1 .. %u each way)", fn, c->width, c->height, SOL_LIGHTMAP_MAX_SIZE);
+  if (const int rc = sol_config_head_check(fn, "SolLightmapFilterVarConfig", *c)) return rc;
+  if (const int rc = sol_atlas_check(fn, c->width, c->height)) return rc;
   if (c->iterations < 1 || c->iterations > 8) return sol_fail(SOL_EINVAL, "%s: %u iterations (1 .. 8)", fn, c->iterations);
   if (c->normal_power_log2 > 7) return sol_fail(SOL_EINVAL, "%s: normal_power_log2 %u (0 .. 7)", fn, c->normal_power_log2);
   const float sigma[3] = {c->sigma_position, c->sigma_plane, c->sigma_value};
@@ -56,31 +54,21 @@ int sol_lightmap_filter_var_dev(SolScene* s, const SolLightmapFilterVarConfig* c
                                 void* out_dev, void* variance_out_dev) {
   int rc;
   if ((rc = filter_var_check(s != nullptr, "sol_lightmap_filter_var_dev", config, points_dev, texels_dev, moments_dev, out_dev, variance_out_dev)) ||
-      (rc = sol_device_check()))
+      (rc = sol_device_enter(s)))
     return rc;
-  HIP_TRY(hipSetDevice(s->device));
   return filter_var_launch(s, *config, points_dev, texels_dev, moments_dev, out_dev, variance_out_dev);
 }
 
 int sol_lightmap_filter_var(SolScene* s, const SolLightmapFilterVarConfig* config, const SolRay* points, const SolTexel* texels, const SolMoments* moments,
                             SolRadiance* out, float* variance_out) {
   int rc;
-  if ((rc = filter_var_check(s != nullptr, "sol_lightmap_filter_var", config, points, texels, moments, out, variance_out)) || (rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = filter_var_check(s != nullptr, "sol_lightmap_filter_var", config, points, texels, moments, out, variance_out)) || (rc = sol_device_enter(s))) return rc;
   const size_t wh = (size_t)config->width * config->height;
-  SolStage st;
-  const size_t at_p = st.add(wh * sizeof(SolRay)), at_t = st.add(wh * sizeof(SolTexel)), at_m = st.add(wh * sizeof(SolMoments));
-  const size_t at_o = st.add(wh * sizeof(SolRadiance)), at_v = st.add(variance_out ? wh * 16 : 0);
-  if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->lm_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_p, points, wh * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_t, texels, wh * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_m, moments, wh * sizeof(SolMoments), hipMemcpyHostToDevice, s->stream));
-  if ((rc = filter_var_launch(s, *config, base + at_p, base + at_t, base + at_m, base + at_o, variance_out ? base + at_v : nullptr))) return rc;
-  HIP_TRY(hipMemcpyAsync(out, base + at_o, wh * sizeof(SolRadiance), hipMemcpyDeviceToHost, s->stream));
-  if (variance_out) HIP_TRY(hipMemcpyAsync(variance_out, base + at_v, wh * 16, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int p = st.in(points, wh * sizeof(SolRay)), t = st.in(texels, wh * sizeof(SolTexel)), m = st.in(moments, wh * sizeof(SolMoments));
+  const int o = st.out(out, wh * sizeof(SolRadiance)), v = st.out_opt(variance_out, wh * 16);  // (no variance plane asked for: none written)
+  if ((rc = st.upload()) || (rc = filter_var_launch(s, *config, st[p], st[t], st[m], st[o], st[v]))) return rc;
+  return st.finish();
 }
 
 }  // extern "C"

@@ -1,31 +1,21 @@
 // sol_lightmap_mips.cpp -- sol_lightmap_mip_layout, sol_lightmap_mips, sol_lightmap_sample_lod and sol_lightmap_lod (include/solstrale_hip.h;
 // DESIGN.md 31): the mip chain of a baked atlas, its trilinear lookup and the level of detail of a hit (kernels: sol_lightmap_mips.hip; the rule:
 // sol_lightmap_mips.h; the layout: lmm_layout of sol_launch.h). The handle supplies the device, the stream and the staging of the host routes
-// (SolScene::lm_stage); the scene itself is not read: nothing is traced. Every refusal is decided before the device is looked for, from the
-// arguments alone - the checks below are not given the handle's contents, only whether there is one.
+// (SolScene::lm_stage through SolStaged, sol_stage.h); the scene itself is not read: nothing is traced. Every refusal is decided before the device
+// is looked for, from the arguments alone - the checks below (their shared sentences: sol_bake_checks.h) are not given the handle's contents, only
+// whether there is one.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
-#include "sol_scene.h"
+#include "sol_bake_checks.h"
+#include "sol_stage.h"
 
 namespace {
-constexpr size_t LMM_MAX_TRIANGLES = ((size_t)1 << 31) - 2;
-constexpr size_t LMM_MAX_ROWS = (size_t)1 << 31;
-
 // SOL_LIGHTMAP_MIPS=levels: a launch per level down to 1 x 1, the measured alternative of the tail kernel (the same words)
 bool mips_tail() {
   const char* e = std::getenv("SOL_LIGHTMAP_MIPS");
   return !(e && std::strcmp(e, "levels") == 0);
-}
-
-int atlas_check(const char* fn, uint32_t width, uint32_t height, uint32_t channels, uint32_t stride_bytes) {
-  if (width == 0 || height == 0 || width > SOL_LIGHTMAP_MAX_SIZE || height > SOL_LIGHTMAP_MAX_SIZE)
-    return sol_fail(SOL_EINVAL, "%s: an atlas of %u x %u texels (1 .. %u each way)", fn, width, height, SOL_LIGHTMAP_MAX_SIZE);
-  if (channels == 0 || channels > 32) return sol_fail(SOL_EINVAL, "%s: %u channels (1 .. 32)", fn, channels);
-  if (stride_bytes % 4 != 0 || stride_bytes / 4 < channels)
-    return sol_fail(SOL_EINVAL, "%s: a stride of %u bytes (a multiple of 4, at least 4 x %u channels)", fn, stride_bytes, channels);
-  return SOL_OK;
 }
 
 int levels_check(const char* fn, uint32_t width, uint32_t height, uint32_t levels) {
@@ -38,7 +28,8 @@ int mips_check(bool have_scene, const char* fn, const void* texels, const void* 
                uint32_t stride_bytes, uint32_t levels, const void* mips, const void* cover) {
   int rc;
   if (!have_scene) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if ((rc = atlas_check(fn, width, height, channels, stride_bytes)) || (rc = levels_check(fn, width, height, levels))) return rc;
+  if ((rc = sol_atlas_check(fn, width, height)) || (rc = sol_channels_check(fn, channels, stride_bytes)) || (rc = levels_check(fn, width, height, levels)))
+    return rc;
   if (!texels || !values) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !texels ? "texel" : "value");
   if (lmm_layout(width, height, levels).levels > 1) {
     if (!mips || !cover) return sol_fail(SOL_EINVAL, "%s: null %s output pointer", fn, !mips ? "chain" : "cover");
@@ -49,30 +40,15 @@ int mips_check(bool have_scene, const char* fn, const void* texels, const void* 
   return SOL_OK;
 }
 
-int lod_config_check(const char* fn, const SolLightmapLodConfig* c) {
-  int rc;
-  if (c->size != sizeof(SolLightmapLodConfig))
-    return sol_fail(SOL_EINVAL, "%s: SolLightmapLodConfig.size %u (expected %zu)", fn, c->size, sizeof(SolLightmapLodConfig));
-  if (c->reserved[0] || c->reserved[1]) return sol_fail(SOL_EINVAL, "%s: SolLightmapLodConfig.reserved must be 0", fn);
-  if (c->flags) return sol_fail(SOL_EINVAL, "%s: SolLightmapLodConfig.flags 0x%x: unknown bits", fn, c->flags);
-  if ((rc = atlas_check(fn, c->width, c->height, c->channels, c->stride_bytes))) return rc;
-  if (!(c->chart_radius > 0.0f)) return sol_fail(SOL_EINVAL, "%s: chart_radius %g (> 0, not NaN; +inf switches the guard off)", fn, (double)c->chart_radius);
-  return SOL_OK;
-}
-
 int sample_lod_check(bool have_scene, const char* fn, const SolLightmapLodConfig* c, const void* uvs, size_t n_triangles, const void* texels, const void* values,
                      const void* mips, const void* cover, const void* vertices, const void* points, const void* coords, const void* lods, size_t n,
                      const void* out) {
   int rc;
   if (!have_scene || !c) return sol_fail(SOL_EINVAL, "%s: null %s", fn, !have_scene ? "scene" : "configuration");
-  if ((rc = lod_config_check(fn, c))) return rc;
-  if ((vertices != nullptr) != (points != nullptr))
-    return sol_fail(SOL_EINVAL, "%s: vertices and points go together (the %s pointer is null)", fn, !vertices ? "vertex" : "point");
-  if (std::isfinite(c->chart_radius) && !vertices)
-    return sol_fail(SOL_EINVAL, "%s: a finite chart_radius needs the guard arrays (vertices and points)", fn);
-  if ((rc = levels_check(fn, c->width, c->height, c->levels))) return rc;
-  if (n_triangles > LMM_MAX_TRIANGLES) return sol_fail(SOL_EINVAL, "%s: %zu triangles in one call (at most 2^31 - 2)", fn, n_triangles);
-  if (n > LMM_MAX_ROWS) return sol_fail(SOL_EINVAL, "%s: %zu rows in one call (at most 2^31)", fn, n);
+  if ((rc = sol_config_head_check(fn, "SolLightmapLodConfig", *c, c->flags, 0))) return rc;
+  if ((rc = sol_atlas_check(fn, c->width, c->height)) || (rc = sol_channels_check(fn, c->channels, c->stride_bytes))) return rc;
+  if ((rc = sol_chart_guard_check(fn, c->chart_radius, vertices, points)) || (rc = levels_check(fn, c->width, c->height, c->levels))) return rc;
+  if ((rc = sol_triangles_check(fn, n_triangles)) || (rc = sol_rows_check(fn, n, "rows"))) return rc;
   if ((n_triangles > 0 && !uvs) || !texels || !values || !coords || !lods || !out)
     return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn,
                     (n_triangles > 0 && !uvs) ? "UV" : !texels ? "texel" : !values ? "value" : !coords ? "coordinate" : !lods ? "lod" : "output");
@@ -85,17 +61,37 @@ int sample_lod_check(bool have_scene, const char* fn, const SolLightmapLodConfig
 
 int lod_check(bool have_scene, const char* fn, const void* rays, const void* hits, const void* coords, size_t n, const void* vertices, const void* uvs,
               size_t n_triangles, uint32_t width, uint32_t height, float spread, float bias, const void* out) {
+  int rc;
   if (!have_scene) return sol_fail(SOL_EINVAL, "%s: null scene", fn);
-  if (width == 0 || height == 0 || width > SOL_LIGHTMAP_MAX_SIZE || height > SOL_LIGHTMAP_MAX_SIZE)
-    return sol_fail(SOL_EINVAL, "%s: an atlas of %u x %u texels (1 .. %u each way)", fn, width, height, SOL_LIGHTMAP_MAX_SIZE);
+  if ((rc = sol_atlas_check(fn, width, height))) return rc;
   if (!(std::isfinite(spread) && spread > 0.0f)) return sol_fail(SOL_EINVAL, "%s: spread %g (finite, > 0)", fn, (double)spread);
   if (!std::isfinite(bias)) return sol_fail(SOL_EINVAL, "%s: bias %g (finite)", fn, (double)bias);
-  if (n_triangles > LMM_MAX_TRIANGLES) return sol_fail(SOL_EINVAL, "%s: %zu triangles in one call (at most 2^31 - 2)", fn, n_triangles);
-  if (n > LMM_MAX_ROWS) return sol_fail(SOL_EINVAL, "%s: %zu rows in one call (at most 2^31)", fn, n);
+  if ((rc = sol_triangles_check(fn, n_triangles)) || (rc = sol_rows_check(fn, n, "rows"))) return rc;
   if (n_triangles > 0 && (!vertices || !uvs)) return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !vertices ? "vertex" : "UV");
   if (!rays || !hits || !coords || !out)
     return sol_fail(SOL_EINVAL, "%s: null %s pointer", fn, !rays ? "ray" : !hits ? "hit" : !coords ? "coordinate" : "output");
   if (out == rays || out == hits || out == coords) return sol_fail(SOL_EINVAL, "%s: out may not be %s", fn, out == rays ? "rays" : out == hits ? "hits" : "coords");
+  return SOL_OK;
+}
+
+// The three launches as both routes of an entry point run them, on the scene's stream.
+int mips_launch(SolScene* s, const LmmLayout& L, uint32_t channels, uint32_t stride_bytes, const void* texels, const void* pass_of, const void* values, void* mips,
+                void* cover) {
+  HIP_TRY(sol_launch_lightmap_mips(L, channels, stride_bytes / 4, mips_tail(), texels, pass_of, values, mips, cover, s->stream));
+  return SOL_OK;
+}
+
+int sample_lod_launch(SolScene* s, const SolLightmapLodConfig& c, const LmmLayout& L, const void* uvs, size_t n_triangles, const void* texels, const void* pass_of,
+                      const void* values, const void* mips, const void* cover, const void* vertices, const void* points, const void* coords, const void* lods,
+                      size_t n, void* out) {
+  HIP_TRY(sol_launch_lightmap_sample_lod(c, L, (uint32_t)n_triangles, uvs, texels, pass_of, values, mips, cover, vertices, points, coords, lods, (uint32_t)n, out,
+                                         s->stream));
+  return SOL_OK;
+}
+
+int lod_launch(SolScene* s, const void* rays, const void* hits, const void* coords, size_t n, const void* vertices, const void* uvs, size_t n_triangles,
+               uint32_t width, uint32_t height, float spread, float bias, void* out) {
+  HIP_TRY(sol_launch_lightmap_lod(rays, hits, coords, (uint32_t)n, vertices, uvs, (uint32_t)n_triangles, width, height, spread, bias, out, s->stream));
   return SOL_OK;
 }
 
@@ -107,9 +103,7 @@ int sol_lightmap_mip_layout(uint32_t width, uint32_t height, uint32_t levels, ui
                             uint64_t* total_rows) {
   int rc;
   const char* fn = "sol_lightmap_mip_layout";
-  if (width == 0 || height == 0 || width > SOL_LIGHTMAP_MAX_SIZE || height > SOL_LIGHTMAP_MAX_SIZE)
-    return sol_fail(SOL_EINVAL, "%s: an atlas of %u x %u texels (1 .. %u each way)", fn, width, height, SOL_LIGHTMAP_MAX_SIZE);
-  if ((rc = levels_check(fn, width, height, levels))) return rc;
+  if ((rc = sol_atlas_check(fn, width, height)) || (rc = levels_check(fn, width, height, levels))) return rc;
   const LmmLayout L = lmm_layout(width, height, levels);
   if (levels_out) *levels_out = L.levels;
   for (uint32_t l = 0; l < SOL_LIGHTMAP_MAX_LEVELS; ++l) {
@@ -129,11 +123,8 @@ int sol_lightmap_mips_dev(SolScene* s, const void* texels_dev, const void* pass_
                        cover_out_dev)))
     return rc;
   const LmmLayout L = lmm_layout(width, height, levels);
-  if (L.levels == 1) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_lightmap_mips(L, channels, stride_bytes / 4, mips_tail(), texels_dev, pass_of_dev, values_dev, mips_out_dev, cover_out_dev, s->stream));
-  return SOL_OK;
+  if (L.levels == 1 || (rc = sol_device_enter(s))) return rc;
+  return mips_launch(s, L, channels, stride_bytes, texels_dev, pass_of_dev, values_dev, mips_out_dev, cover_out_dev);
 }
 
 int sol_lightmap_mips(SolScene* s, const SolTexel* texels, const uint8_t* pass_of, uint32_t width, uint32_t height, const void* values, uint32_t channels,
@@ -141,23 +132,13 @@ int sol_lightmap_mips(SolScene* s, const SolTexel* texels, const uint8_t* pass_o
   int rc;
   if ((rc = mips_check(s != nullptr, "sol_lightmap_mips", texels, pass_of, width, height, values, channels, stride_bytes, levels, mips_out, cover_out))) return rc;
   const LmmLayout L = lmm_layout(width, height, levels);
-  if (L.levels == 1) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  if (L.levels == 1 || (rc = sol_device_enter(s))) return rc;
   const size_t wh = (size_t)width * height, row = stride_bytes;
-  SolStage st;
-  const size_t at_t = st.add(wh * sizeof(SolTexel)), at_p = st.add(pass_of ? wh : 0), at_v = st.add(wh * row), at_m = st.add(L.rows * row), at_c = st.add(L.rows);
-  if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->lm_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_t, texels, wh * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  if (pass_of) HIP_TRY(hipMemcpyAsync(base + at_p, pass_of, wh, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_v, values, wh * row, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(sol_launch_lightmap_mips(L, channels, stride_bytes / 4, mips_tail(), base + at_t, pass_of ? base + at_p : nullptr, base + at_v, base + at_m, base + at_c,
-                                   s->stream));
-  HIP_TRY(hipMemcpyAsync(mips_out, base + at_m, L.rows * row, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipMemcpyAsync(cover_out, base + at_c, L.rows, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int t = st.in(texels, wh * sizeof(SolTexel)), p = st.in_opt(pass_of, wh), v = st.in(values, wh * row);
+  const int m = st.out(mips_out, L.rows * row), c = st.out(cover_out, L.rows);
+  if ((rc = st.upload()) || (rc = mips_launch(s, L, channels, stride_bytes, st[t], st[p], st[v], st[m], st[c]))) return rc;
+  return st.finish();
 }
 
 int sol_lightmap_sample_lod_dev(SolScene* s, const SolLightmapLodConfig* config, const void* uvs_dev, size_t n_triangles, const void* texels_dev,
@@ -165,94 +146,56 @@ int sol_lightmap_sample_lod_dev(SolScene* s, const SolLightmapLodConfig* config,
                                 const void* points_dev, const void* coords_dev, const void* lods_dev, size_t n, void* out_dev) {
   int rc;
   if ((rc = sample_lod_check(s != nullptr, "sol_lightmap_sample_lod_dev", config, uvs_dev, n_triangles, texels_dev, values_dev, mips_dev, cover_dev, vertices_dev,
-                             points_dev, coords_dev, lods_dev, n, out_dev)))
+                             points_dev, coords_dev, lods_dev, n, out_dev)) ||
+      n == 0 || (rc = sol_device_enter(s)))
     return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_lightmap_sample_lod(*config, lmm_layout(config->width, config->height, config->levels), (uint32_t)n_triangles, uvs_dev, texels_dev,
-                                         pass_of_dev, values_dev, mips_dev, cover_dev, vertices_dev, points_dev, coords_dev, lods_dev, (uint32_t)n, out_dev,
-                                         s->stream));
-  return SOL_OK;
+  return sample_lod_launch(s, *config, lmm_layout(config->width, config->height, config->levels), uvs_dev, n_triangles, texels_dev, pass_of_dev, values_dev,
+                           mips_dev, cover_dev, vertices_dev, points_dev, coords_dev, lods_dev, n, out_dev);
 }
 
 int sol_lightmap_sample_lod(SolScene* s, const SolLightmapLodConfig* config, const float* uvs, size_t n_triangles, const SolTexel* texels, const uint8_t* pass_of,
                             const void* values, const void* mips, const uint8_t* cover, const float* vertices, const SolRay* points, const SolTexel* coords,
                             const float* lods, size_t n, void* out) {
   int rc;
-  if ((rc = sample_lod_check(s != nullptr, "sol_lightmap_sample_lod", config, uvs, n_triangles, texels, values, mips, cover, vertices, points, coords, lods, n, out)))
+  if ((rc = sample_lod_check(s != nullptr, "sol_lightmap_sample_lod", config, uvs, n_triangles, texels, values, mips, cover, vertices, points, coords, lods, n,
+                             out)) ||
+      n == 0 || (rc = sol_device_enter(s)))
     return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
   const LmmLayout L = lmm_layout(config->width, config->height, config->levels);
   const size_t wh = (size_t)config->width * config->height, row = config->stride_bytes, out_row = ((size_t)config->channels + 1) * 4, nt = n_triangles;
-  SolStage st;
-  const size_t at_uv = st.add(nt * 6 * sizeof(float)), at_t = st.add(wh * sizeof(SolTexel)), at_pass = st.add(pass_of ? wh : 0), at_v = st.add(wh * row);
-  const size_t at_m = st.add(L.rows * row), at_cv = st.add(L.rows);
-  const size_t at_vx = st.add(vertices ? nt * 9 * sizeof(float) : 0), at_p = st.add(points ? wh * sizeof(SolRay) : 0), at_c = st.add(n * sizeof(SolTexel));
-  const size_t at_l = st.add(n * sizeof(float)), at_o = st.add(n * out_row);
-  if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->lm_stage.get();
-  if (nt) HIP_TRY(hipMemcpyAsync(base + at_uv, uvs, nt * 6 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_t, texels, wh * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  if (pass_of) HIP_TRY(hipMemcpyAsync(base + at_pass, pass_of, wh, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_v, values, wh * row, hipMemcpyHostToDevice, s->stream));
-  if (L.rows) {
-    HIP_TRY(hipMemcpyAsync(base + at_m, mips, L.rows * row, hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(base + at_cv, cover, L.rows, hipMemcpyHostToDevice, s->stream));
-  }
-  if (vertices && nt) HIP_TRY(hipMemcpyAsync(base + at_vx, vertices, nt * 9 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  if (points) HIP_TRY(hipMemcpyAsync(base + at_p, points, wh * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_c, coords, n * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_l, lods, n * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(sol_launch_lightmap_sample_lod(*config, L, (uint32_t)nt, base + at_uv, base + at_t, pass_of ? base + at_pass : nullptr, base + at_v, base + at_m,
-                                         base + at_cv, vertices ? base + at_vx : nullptr, points ? base + at_p : nullptr, base + at_c, base + at_l, (uint32_t)n,
-                                         base + at_o, s->stream));
-  HIP_TRY(hipMemcpyAsync(out, base + at_o, n * out_row, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int uv = st.in(uvs, nt * 6 * sizeof(float)), t = st.in(texels, wh * sizeof(SolTexel)), pass = st.in_opt(pass_of, wh), v = st.in(values, wh * row);
+  const int m = st.in(mips, L.rows * row), cv = st.in(cover, L.rows);  // (one level: no chain, 0 bytes, and still an address)
+  const int vx = st.in_opt(vertices, nt * 9 * sizeof(float)), p = st.in_opt(points, wh * sizeof(SolRay)), c = st.in(coords, n * sizeof(SolTexel));
+  const int l = st.in(lods, n * sizeof(float)), o = st.out(out, n * out_row);
+  if ((rc = st.upload()) ||
+      (rc = sample_lod_launch(s, *config, L, st[uv], nt, st[t], st[pass], st[v], st[m], st[cv], st[vx], st[p], st[c], st[l], n, st[o])))
+    return rc;
+  return st.finish();
 }
 
 int sol_lightmap_lod_dev(SolScene* s, const void* rays_dev, const void* hits_dev, const void* coords_dev, size_t n, const void* vertices_dev, const void* uvs_dev,
                          size_t n_triangles, uint32_t width, uint32_t height, float spread, float bias, void* lods_out_dev) {
   int rc;
   if ((rc = lod_check(s != nullptr, "sol_lightmap_lod_dev", rays_dev, hits_dev, coords_dev, n, vertices_dev, uvs_dev, n_triangles, width, height, spread, bias,
-                      lods_out_dev)))
+                      lods_out_dev)) ||
+      n == 0 || (rc = sol_device_enter(s)))
     return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(sol_launch_lightmap_lod(rays_dev, hits_dev, coords_dev, (uint32_t)n, vertices_dev, uvs_dev, (uint32_t)n_triangles, width, height, spread, bias,
-                                  lods_out_dev, s->stream));
-  return SOL_OK;
+  return lod_launch(s, rays_dev, hits_dev, coords_dev, n, vertices_dev, uvs_dev, n_triangles, width, height, spread, bias, lods_out_dev);
 }
 
 int sol_lightmap_lod(SolScene* s, const SolRay* rays, const SolRayHit* hits, const SolTexel* coords, size_t n, const float* vertices, const float* uvs,
                      size_t n_triangles, uint32_t width, uint32_t height, float spread, float bias, float* lods_out) {
   int rc;
-  if ((rc = lod_check(s != nullptr, "sol_lightmap_lod", rays, hits, coords, n, vertices, uvs, n_triangles, width, height, spread, bias, lods_out))) return rc;
-  if (n == 0) return SOL_OK;
-  if ((rc = sol_device_check())) return rc;
-  HIP_TRY(hipSetDevice(s->device));
+  if ((rc = lod_check(s != nullptr, "sol_lightmap_lod", rays, hits, coords, n, vertices, uvs, n_triangles, width, height, spread, bias, lods_out)) || n == 0 ||
+      (rc = sol_device_enter(s)))
+    return rc;
   const size_t nt = n_triangles;
-  SolStage st;
-  const size_t at_r = st.add(n * sizeof(SolRay)), at_h = st.add(n * sizeof(SolRayHit)), at_c = st.add(n * sizeof(SolTexel));
-  const size_t at_v = st.add(nt * 9 * sizeof(float)), at_uv = st.add(nt * 6 * sizeof(float)), at_o = st.add(n * sizeof(float));
-  if ((rc = s->lm_stage.reserve(s->stream, st.total))) return rc;
-  char* base = s->lm_stage.get();
-  HIP_TRY(hipMemcpyAsync(base + at_r, rays, n * sizeof(SolRay), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_h, hits, n * sizeof(SolRayHit), hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemcpyAsync(base + at_c, coords, n * sizeof(SolTexel), hipMemcpyHostToDevice, s->stream));
-  if (nt) {
-    HIP_TRY(hipMemcpyAsync(base + at_v, vertices, nt * 9 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(hipMemcpyAsync(base + at_uv, uvs, nt * 6 * sizeof(float), hipMemcpyHostToDevice, s->stream));
-  }
-  HIP_TRY(sol_launch_lightmap_lod(base + at_r, base + at_h, base + at_c, (uint32_t)n, base + at_v, base + at_uv, (uint32_t)nt, width, height, spread, bias,
-                                  base + at_o, s->stream));
-  HIP_TRY(hipMemcpyAsync(lods_out, base + at_o, n * sizeof(float), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return SOL_OK;
+  SolStaged st(s->stream, s->lm_stage);
+  const int r = st.in(rays, n * sizeof(SolRay)), h = st.in(hits, n * sizeof(SolRayHit)), c = st.in(coords, n * sizeof(SolTexel));
+  const int v = st.in(vertices, nt * 9 * sizeof(float)), uv = st.in(uvs, nt * 6 * sizeof(float)), o = st.out(lods_out, n * sizeof(float));
+  if ((rc = st.upload()) || (rc = lod_launch(s, st[r], st[h], st[c], n, st[v], st[uv], nt, width, height, spread, bias, st[o]))) return rc;
+  return st.finish();
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 //   sol_lightmap_filter.cpp sol_lightmap_filter: chart-aware a-trous filtering of a baked atlas (sol_lightmap_filter.hip)
 //   sol_lightmap_filter_var.cpp sol_lightmap_filter_var: the same under the guidance of the per-texel variance sol_irradiance_moments gathers (sol_lightmap_filter_var.hip)
 //   sol_gather.h/.cpp what the radiance queries and the gather families share: configuration checks, entry shape, slice / window launch plan, staged host route
+//   sol_stage.h / sol_bake_checks.h what the bake families (lightmaps, volumes, depth moments) share: the staged host route (SolStaged) and the sentences of their refusals
 //   sol_gather_adaptive.cpp sol_irradiance_adaptive / sol_radiance_rescale: rounds of an irradiance-moments gather over the points still active (sol_gather_adaptive.hip)
 //   sol_volume.cpp  sol_volume_points / sol_volume_build / sol_volume_sample: a probe grid laid out, packed and sampled (sol_volume.hip)
 //   sol_post.cpp    un-permute, Nop tone-map, bloom (kernels in sol_aux.hip)
@@ -110,11 +111,6 @@ struct SolSceneMirror {
 #define SOL_MAX_ITEMS 0xFF000000ull
 // SOL_EDEVICE "no HIP device available" unless there is one (sol_api.cpp); *n_devices: how many.
 int sol_device_check(int* n_devices = nullptr);
-// The staging of a host route: consecutive arrays in one buffer, each 256-byte aligned. add: the offset of the next one.
-struct SolStage {
-  size_t total = 0;
-  size_t add(size_t bytes) { const size_t at = total; total += (bytes + 255) / 256 * 256; return at; }
-};
 
 // Developer overrides: environment variables for experiments and A/B runs, parsed by sol_dev_overrides() - the
 // only getenv site of the library - once per sol_scene_create / sol_world_tree_check; nothing on the launch path reads the environment.
@@ -327,7 +323,8 @@ struct SolScene {
   DevBuf<SolRay> rad_in; DevBuf<SolRayKey> rad_keys; DevBuf<SolRadiance> rad_out;
   // Lightmap texel points and dilation (sol_lightmap.hip). lm_owner: the scratch - 16 words of list counters, the W x H owner words
   // of the claim pass, then its two work lists of n_triangles words each; a dilation keeps its two coverage planes (a byte per texel each) in the
-  // same words. lm_stage: what the host routes stage, inputs and outputs. lm_small_max / lm_tiles_max: the claim pass's thresholds (SOL_LIGHTMAP_CLAIM).
+  // same words. lm_stage: what the host routes of every lightmap family stage, inputs and outputs, laid out by SolStaged (sol_stage.h);
+  // sol_radiance_rescale batches through it too. lm_small_max / lm_tiles_max: the claim pass's thresholds (SOL_LIGHTMAP_CLAIM).
   DevBuf<uint32_t> lm_owner;
   DevBuf<char> lm_stage;
   uint32_t lm_small_max = 16, lm_tiles_max = 64;
@@ -339,8 +336,8 @@ struct SolScene {
   // them first.
   DevBuf<float4> lf_guide, lf_planes;
   bool lf_staged = true, lf_fold = false;
-  // Irradiance volumes (sol_volume.hip). vol_stage: what the host routes stage, inputs and outputs. vol_load_all: the sampler's
-  // measured alternative (SOL_VOLUME_SAMPLE=loadall).
+  // Irradiance volumes (sol_volume.hip). vol_stage: what the host routes stage, inputs and outputs, laid out by SolStaged
+  // (sol_stage.h; sol_volume_points: its one array). vol_load_all: the sampler's measured alternative (SOL_VOLUME_SAMPLE=loadall).
   DevBuf<char> vol_stage;
   bool vol_load_all = false;
   // Directional distance moments (sol_depth.hip): the gather runs through rad_*, build and sample stage through vol_stage.
@@ -356,6 +353,12 @@ struct SolScene {
   size_t ga_max_rows = (size_t)1 << 22;
   SolDynamic dyn;  // sol_scene_set_triangles / sol_scene_set_primitives (sol_geometry.cpp)
 };
+// The tail of an entry point's preamble, behind its refusals: the device looked for, then the handle's made current - the first read of the handle.
+inline int sol_device_enter(const SolScene* s) {
+  if (const int rc = sol_device_check()) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  return SOL_OK;
+}
 // The f64 weights w_i = area_i x Y_i of the lights of `d` in list order (sol_lights.hip; host only; sol_light_weights).
 std::vector<double> sol_light_weights_of(const SolSceneDesc* d);
 // Why environment importance sampling cannot run on the scene `d` describes, or "" (sol_envmap.hip; host only).

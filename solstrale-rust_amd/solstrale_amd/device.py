@@ -1062,8 +1062,7 @@ class DeviceScene:
         out_words = channels + 1 if 1 <= channels <= 32 else 1
         wh = width * height
         if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            def host(x, dtype=None):
-                return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
+            host = self._host_array
             v, u, vx, p = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32)
             t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
             c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
@@ -1079,14 +1078,7 @@ class DeviceScene:
                                                    None if p is None else p.ctypes.data, c.ctypes.data, c.shape[0], out.ctypes.data))
             return out
         import torch
-
-        def dev(name, x, dtype, shape):
-            if x is None:
-                return None
-            if (not hasattr(x, "data_ptr") or x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or x.device.index != self.device
-                    or len(shape) != x.dim() or any(s is not None and s != d for s, d in zip(shape, x.shape))):
-                raise ValueError(f"{name}: a contiguous {dtype} tensor of shape {list(shape)} on the scene's device")
-            return C.c_void_p(x.data_ptr())
+        dev = self._device_pointer
         n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
         args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
                 dev("values", values, torch.float32, (wh, None)), dev("vertices", vertices, torch.float32, (n_tri, 3, 3)),
@@ -1136,8 +1128,7 @@ class DeviceScene:
         out_words = 28 if coefficients else 4
         wh = width * height
         if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            def host(x, dtype=None):
-                return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
+            host = self._host_array
             v, u, vx, p, nr = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32), host(normals, np.float32)
             t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
             c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
@@ -1263,8 +1254,7 @@ class DeviceScene:
         out_words = channels + 1 if 1 <= channels <= 32 else 1
         wh, rows = width * height, lay["rows"]
         if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            def host(x, dtype=None):
-                return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
+            host = self._host_array
             v, u, vx, p = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32)
             m, cv, ld, po = host(mips, np.float32), host(cover, np.uint8), host(lods, np.float32), host(pass_of, np.uint8)
             t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)

@@ -178,11 +178,12 @@ def lm_points(name, W, H, conservative, h):
                 lambda ds: ds.lightmap_points(*R(h, V, T), W, H, normals=R(h, N)[0], conservative=conservative), want)
 
 
-def lm_dilate(W, H, channels, passes, h):
+def lm_dilate(W, H, channels, passes, h, pass_of=True):
+    """pass_of=False: the caller asks for no pass_of plane (a null pass_of_out: the rows alone)"""
     A, values = atlas(W, H), values_of(W * H, channels, channels + 1, 7 * W + H)
-    return Step(E("sol_lightmap_dilate", h), f"{W}x{H} channels={channels} passes={passes}",
-                lambda ds: ds.lightmap_dilate(*R(h, values, A.texels), W, H, passes=passes, channels=channels, return_pass_of=True),
-                lambda: lr.lightmap_dilate(values, A.texels, W, H, passes=passes, channels=channels))
+    return Step(E("sol_lightmap_dilate", h), f"{W}x{H} channels={channels} passes={passes}" + ("" if pass_of else " no pass_of"),
+                lambda ds: ds.lightmap_dilate(*R(h, values, A.texels), W, H, passes=passes, channels=channels, return_pass_of=pass_of),
+                lambda: lr.lightmap_dilate(values, A.texels, W, H, passes=passes, channels=channels)[:2 if pass_of else 1])
 
 
 def lm_filter(W, H, channels, iterations, h):
@@ -193,13 +194,14 @@ def lm_filter(W, H, channels, iterations, h):
                 lambda ds: ds.lightmap_filter(*R(h, values, P, T), W, H, **kw), lambda: fr.lightmap_filter(values, P, T, W, H, **kw), nan_for_nan=True)
 
 
-def lm_filter_var(W, H, iterations, h):
+def lm_filter_var(W, H, iterations, h, variance=True):
+    """variance=False: the caller asks for no variance plane (a null variance_out: the filtered rows alone)"""
     P, T, sigma = filter_atlas(W, H)
     M = moments_of(W * H, W)
     kw = dict(sigma_position=sigma, iterations=iterations)
-    return Step(E("sol_lightmap_filter_var", h), f"{W}x{H} iterations={iterations}",
-                lambda ds: ds.lightmap_filter_var(*R(h, M.view(F).reshape(-1, 8), P, T), W, H, return_variance=True, **kw),
-                lambda: fvr.lightmap_filter_var(M, P, T, W, H, **kw), nan_for_nan=True)
+    return Step(E("sol_lightmap_filter_var", h), f"{W}x{H} iterations={iterations}" + ("" if variance else " no variance"),
+                lambda ds: ds.lightmap_filter_var(*R(h, M.view(F).reshape(-1, 8), P, T), W, H, return_variance=variance, **kw),
+                lambda: fvr.lightmap_filter_var(M, P, T, W, H, **kw)[:2 if variance else 1], nan_for_nan=True)
 
 
 class _Floor:
@@ -223,17 +225,21 @@ def floor():
     return _Floor()
 
 
-def lm_coords(n, h):
+def lm_coords(n, h, n_dfs=None):
+    """n_dfs: the table cut to its first so many entries (0: an empty table, a null pointer - every hit is unlisted)"""
     fl = floor()
-    hits = fl.hits[:n]
-    return Step(E("sol_lightmap_coords", h), f"n={n}", lambda ds: ds.lightmap_coords(R(h, hits)[0], fl.table), lambda: sr.lightmap_coords(hits, fl.table))
+    hits, table = fl.hits[:n], fl.table[:n_dfs]
+    return Step(E("sol_lightmap_coords", h), f"n={n}" + ("" if n_dfs is None else f" n_dfs={n_dfs}"), lambda ds: ds.lightmap_coords(R(h, hits)[0], table),
+                lambda: sr.lightmap_coords(hits, table))
 
 
-def lm_lod(n, W, H, h):
+def lm_lod(n, W, H, h, n_triangles=None):
+    """n_triangles: the mesh cut to its first so many triangles (0: no mesh, null pointers - every row answers 0)"""
     fl = floor()
-    rays, hits, coords = fl.rays[:n], fl.hits[:n], fl.coords[:n]
-    return Step(E("sol_lightmap_lod", h), f"n={n} {W}x{H}", lambda ds: ds.lightmap_lod(*R(h, rays, hits, coords, fl.V, fl.T), W, H, fl.spread, 0.25),
-                lambda: mr.lightmap_lod(rays, hits, coords, fl.V, fl.T, W, H, fl.spread, 0.25))
+    rays, hits, coords, V, T = fl.rays[:n], fl.hits[:n], fl.coords[:n], np.ascontiguousarray(fl.V[:n_triangles]), np.ascontiguousarray(fl.T[:n_triangles])
+    return Step(E("sol_lightmap_lod", h), f"n={n} {W}x{H}" + ("" if n_triangles is None else f" n_triangles={n_triangles}"),
+                lambda ds: ds.lightmap_lod(*R(h, rays, hits, coords, V, T), W, H, fl.spread, 0.25),
+                lambda: mr.lightmap_lod(rays, hits, coords, V, T, W, H, fl.spread, 0.25))
 
 
 def lm_sample(W, H, channels, passes, n, nearest, h):
@@ -271,14 +277,17 @@ def lm_mips(W, H, channels, passes, levels, h):
                 lambda: (mips[:nrows], cover[:nrows]))
 
 
-def lm_sample_lod(W, H, channels, passes, n, h):
+def lm_sample_lod(W, H, channels, passes, n, h, radius=None):
+    """radius: the chart guard on - a finite chart_radius with the guard arrays (the mesh's vertices, the atlas's points)"""
     A = atlas(W, H)
     values, pass_of, mips, cover = chain(A, channels, passes)
     levels = lightmap_mip_layout(W, H)["levels"]
     lods, rows = lods_for(257, levels)[:n], A.rows[:n]
-    return Step(E("sol_lightmap_sample_lod", h), f"{W}x{H} channels={channels} passes={passes} n={n}",
-                lambda ds: ds.lightmap_sample_lod(*R(h, values, mips, cover, lods, rows, A.uvs, A.texels), W, H, channels=channels, pass_of=R(h, pass_of)[0]),
-                lambda: mr.lightmap_sample_lod(values, mips, cover, lods, rows, A.uvs, A.texels, W, H, channels=channels, pass_of=pass_of))
+    guard = {} if radius is None else dict(chart_radius=radius, vertices=A.vertices, points=A.points)
+    return Step(E("sol_lightmap_sample_lod", h), f"{W}x{H} channels={channels} passes={passes} n={n}" + ("" if radius is None else f" radius={radius}"),
+                lambda ds: ds.lightmap_sample_lod(*R(h, values, mips, cover, lods, rows, A.uvs, A.texels), W, H, channels=channels, pass_of=R(h, pass_of)[0],
+                                                  **{k: v if k == "chart_radius" else R(h, v)[0] for k, v in guard.items()}),
+                lambda: mr.lightmap_sample_lod(values, mips, cover, lods, rows, A.uvs, A.texels, W, H, channels=channels, pass_of=pass_of, **guard))
 
 
 def lm_charts(name, h):
@@ -344,9 +353,13 @@ def vol_points(counts, h):
     return Step(E("sol_volume_points", h), f"{counts}", lambda ds: ds.volume_points(g, tmin=0.25, tmax=7.5, host=h), lambda: vr.volume_points(g, tmin=0.25, tmax=7.5))
 
 
-def vol_build(counts, h):
+def vol_build(counts, h, visibility=True):
+    """visibility=False: no SolVisibility rows (a null pointer: the probes' distance words by the rule without them)"""
     g = grid_of(counts)
     sh, vis, probes, _ = volume_case(counts)
+    if not visibility:
+        return Step(E("sol_volume_build", h), f"{counts} no visibility", lambda ds: ds.volume_build(g, R(h, sh)[0], None, radius=2.0),
+                    lambda: vr.volume_build(sh, None, radius=2.0))
     return Step(E("sol_volume_build", h), f"{counts}", lambda ds: ds.volume_build(g, *R(h, sh, vis), radius=2.0), lambda: probes)
 
 
@@ -539,6 +552,12 @@ def test_lm_stage_serves_the_host_route_of_every_user_in_turn():
              lm_dilate_charts(130, 67, 27, 4, True),               # 8710 x (16 + 2 x 112 + 1 + 4) bytes
              lm_sample_charts(1, 1, 3, 0, 1, True), lm_chart_levels(130, 67, 4, True), lm_chart_levels(1, 1, 0, True),
              lm_charts("strip", True), lm_points("empty", 1, 1, False, True)]
+    # what a host route stages or leaves out by a null pointer or a zero count, each beside its counterpart, at the smallest shapes that still run the
+    # kernels: no pass_of plane and no variance plane asked for, an empty table and no mesh (a required array of 0 bytes), the chart guard's arrays
+    stage += [lm_dilate(5, 3, 3, 1, True, pass_of=False), lm_dilate(5, 3, 3, 1, True),
+              lm_filter_var(5, 3, 1, True, variance=False),
+              lm_coords(65, True, n_dfs=0), lm_coords(1, True, n_dfs=2), lm_lod(65, 5, 3, True, n_triangles=0), lm_lod(1, 5, 3, True, n_triangles=2),
+              lm_sample_lod(5, 3, 3, 4, 65, True, radius=5.0), lm_sample_lod(5, 3, 3, 4, 1, True)]
     with cornell() as ds:
         run_order(ds, stage)
         run_order(ds, stage[::-1])
@@ -633,7 +652,8 @@ def test_volume_staging_serves_probes_and_depth_maps_in_turn():
                        vol_build_depth(big, 8, True), vol_sample_depth(big, 8, 257, True),                     # 192000 bytes: grows; 64000 more
                        vol_points(one, True), vol_build(one, True), vol_sample_depth(one, 4, 63, True), vol_build(mid, True), vol_sample(big, 64, True),
                        vol_points(mid, False), vol_build(big, False), vol_sample(mid, 257, False), vol_build_depth(big, 4, False),  # (the device routes stage nothing)
-                       vol_sample_depth(big, 8, 1, False), vol_points(big, True)])
+                       vol_sample_depth(big, 8, 1, False), vol_points(big, True),
+                       vol_build(one, True, visibility=False), vol_build(big, True, visibility=False)])               # no visibility rows: none staged, a null pointer
 
 
 def test_query_staging_serves_both_modes_and_routes_in_turn():
