@@ -134,7 +134,7 @@ sol_render_kernel(const DevScene* __restrict__ Sp, const RenderParams P, float* 
     for (;;) {
       const bool act = t.cur != REF_DONE;
       if (!wave_keeps_searching(act, P.switch_below)) break;
-      trav_step_wave<COUNT, MEDIUM, STRICT>(S, t, act, st, p.rng, p.depth, cnt);
+      trav_step_wave<COUNT, MEDIUM, STRICT, false, MEDIUM ? 1 : SOL_PRIM_QUEUE>(S, t, act, st, p.rng, p.depth, cnt);  // (MEDIUM keeps depth 1: sol_trace.h)
     }
 #if SOL_LOOP_PRIO
     __builtin_amdgcn_s_setprio(0);

@@ -250,6 +250,10 @@ DEV bool tri_hit_consistent(const DTri& T, f3 o, f3 d, float t, float u, float v
 //               visit).
 //   prim group  pg = base_prim | hit leaf slots << 24  (leaf kind and lmask: g1, the same node's meta word) - the hit primitives of
 //               the node visited last; they are tested before the search descends further.
+//   (searches stepped with a primitive QUEUE of depth 2, trav_step_wave) a lane holds up to two primitive groups, the older in pg, the younger
+//               in pg2, and keeps visiting nodes while pg2 is free. A node visit overwrites g1, so each group carries its own leaf description:
+//               the upper half of its node's meta word (lmask at bit 6, leaf kind at bit 13) in pd - low half the older group's, high half the
+//               younger's. pg2 holds a group only while pg does: an empty pg means an empty queue, at either depth.
 // `cur` is only the status of such a search: REF_DONE when it is over, 0 while it runs.
 //
 // ConstantMedium::hit (constant_medium.rs:35-79) is two closest-hit searches of the medium's boundary. A world search that reaches
@@ -272,6 +276,7 @@ struct Trav {
   uint32_t cur;
   int sp, sp_base;
   uint32_t g0, g1, pg, oct;  // (7-wide searches only; oct = the ray's octant, sign bits of the direction as x<<2 | y<<1 | z)
+  uint32_t pg2, pd;          // (queue depth 2 only; dead otherwise) the younger primitive group, both groups' leaf descriptions
   Hit h;
   MedSearch m;               // (MEDIUM kernels only; dead otherwise)
   // (STRICT kernels only: scenes with needle triangles) a search that follows a closest hit the consistency rule refused looks only
@@ -279,6 +284,9 @@ struct Trav {
   float bt;
   uint32_t bdfs;
 };
+// Is a 7-wide search over? No primitive group held (at queue depth 2 an empty pg means that pg2 is empty too), no node group, an empty stack.
+// The one text of the test: the primitive part and the end of a medium test ask it.
+DEV bool trav_nothing_left(const Trav& t) { return (t.pg >> 24) == 0u && (t.g0 >> 24) == 0u && t.sp == t.sp_base; }
 
 // Starts a search of `root` over [tmin, tmax]; (bxmin..bzmax) is root's own box, tested first when root is a node
 // (Bvh::hit, bvh.rs:166). WIDE: root is an index into DevScene::wides, else a reference into the 2-wide tree.
@@ -297,6 +305,8 @@ DEV void trav_begin(Trav& t, f3 o, f3 d, float tmin, float tmax, uint32_t root, 
   t.g0 = root | (1u << 24);
   t.g1 = 0u;
   t.pg = 0u;
+  t.pg2 = 0u;
+  t.pd = 0u;
   t.m.phase = 0u;
   t.bt = -__builtin_huge_valf();  // (a search behind a refused hit sets its bound after this call)
   t.bdfs = 0u;
@@ -371,7 +381,8 @@ typedef uint32_t sol_h2;
   }
 // The slab tests of one fetched 7-wide node (h = origin + meta, qa / qb / qc = the six plane arrays) for the ray of search `t`:
 // the search's new node group and primitive group.
-template <bool COUNT>
+// QUEUE = 2: the primitive group goes to the free place of the lane's queue (the caller saw to it that pg2 is free) with its leaf description.
+template <bool COUNT, int QUEUE = 1>
 DEV void wide_node_test(const Stack& st, Trav& t, uint32_t oct, float4 h, uint4 qa, uint4 qb, uint4 qc, sol_v4u kx, sol_v4u ky, sol_v4u kz) {
   const uint32_t wide_emin = st.wide_emin;
   const uint32_t meta = __float_as_uint(h.w);
@@ -438,7 +449,15 @@ DEV void wide_node_test(const Stack& st, Trav& t, uint32_t oct, float4 h, uint4 
   const uint32_t base_prim = __builtin_amdgcn_perm(qc.w, __builtin_amdgcn_perm(qc.y, qb.w, 0x0C0C0703u), 0x0C070100u);
   t.g0 = base_inner | (ih << 24);
   t.g1 = meta;  // (imask, lmask and leaf kind are read from it where they are needed)
-  t.pg = base_prim | ((hits & lmask) << 24);
+  const uint32_t pg = base_prim | ((hits & lmask) << 24);
+  if (QUEUE == 1) {
+    t.pg = pg;
+  } else {
+    const bool first = (t.pg >> 24) == 0u;  // nothing held: the new group is the older one
+    t.pd = first ? meta >> 16 : ((t.pd & 0xFFFFu) | (meta & 0xFFFF0000u));
+    t.pg2 = first ? 0u : pg;
+    t.pg = first ? pg : t.pg;
+  }
 }
 
 // Tests primitive `idx` of kind `kind` against the search's interval [tmin, best t] and keeps it when it is the better hit
@@ -504,14 +523,14 @@ DEV void prim_test(const DevScene& S, Trav& t, const Stack& st, uint32_t kind, u
 // inner mask in 7, the ordered hit bits in 8 (bit p stands for slot p ^ octant: slots 0..6, positions 0..7) - instead of (g0, meta word):
 // half the LDS per level, which is what the pool kernel (sol_pool.hip) pays its path contexts with. A popped group gets its inner mask
 // back in the meta word's place; the other fields of the meta word are read only between a node's test and its primitives, never after a pop.
-template <bool COUNT, bool PACK = false>
+template <bool COUNT, bool PACK = false, int QUEUE = 1>
 DEV void wide_visit(Trav& t, const Stack& st, Counters& cnt) {
   const uint32_t oct = t.oct;
 #if SOL_FETCH_PRIO
   __builtin_amdgcn_s_setprio(SOL_FETCH_PRIO % 10);  // the wave about to fetch goes first: its memory latency starts now
 #endif
   uint32_t g0 = t.g0, g1 = t.g1;
-  if ((g0 >> 24) == 0u) {  // (a running search without pending primitives has a group here or on the stack)
+  if ((g0 >> 24) == 0u) {  // (a running search without pending primitives has a group here or on the stack; one that holds some: the caller's test)
     if (PACK) {
       const uint32_t e = stack_pop(st, t.sp);
       g0 = (e & (SOL_PACK_MAX_NODES - 1u)) | (e & 0xFF000000u);
@@ -547,7 +566,7 @@ DEV void wide_visit(Trav& t, const Stack& st, Counters& cnt) {
   asm volatile("s_setprio %0" ::"n"(SOL_LOOP_PRIO) : "memory");  // (after the loads are issued; asm: the builtin may be moved across them)
 #endif
   if (COUNT) cnt.node_visits++;
-  wide_node_test<COUNT>(st, t, oct, h, qa, qb, qc, kx, ky, kz);
+  wide_node_test<COUNT, QUEUE>(st, t, oct, h, qa, qb, qc, kx, ky, kz);
 }
 
 // One step of a search of the 2-wide DNode tree (the boundary of a constant medium, whose interval includes negative t): visits
@@ -651,7 +670,7 @@ DEV void medium_step(const DevScene& S, Trav& t, const Stack& st, const Rng& rng
     }
   }
   t.m.phase = 0u;  // the world search goes on
-  if ((t.pg >> 24) == 0u && (t.g0 >> 24) == 0u && t.sp == t.sp_base) t.cur = REF_DONE;
+  if (trav_nothing_left(t)) t.cur = REF_DONE;
 }
 
 // One step of a 7-wide world search for a whole WAVE (every lane of the wave that is still in the kernel calls it; `act`: the lane
@@ -660,38 +679,51 @@ DEV void medium_step(const DevScene& S, Trav& t, const Stack& st, const Rng& rng
 // visits per step, while a wave whose lanes are spread over nodes and primitives pays for both parts anyway. The votes on the
 // step's shape (does any lane hold primitives? are they postponed?) are taken by the whole wave once, not inside the divergent
 // region of the searching lanes (MI355X, 64 spp, ms: C3 69.57 -> 68.85, C2 44.0 -> 43.45, C1 10.37 -> 10.30).
-template <bool COUNT, bool MEDIUM, bool STRICT = false, bool PACK = false>
+//
+// QUEUE = 2 (SOL_PRIM_QUEUE; the product render kernel's plain instances): a lane holds up to two primitive groups and keeps visiting nodes
+// while the second place is free, instead of sitting out the node parts until its one group is empty - about 6 of 64 lanes in a node part
+// did. Part 1 runs for a lane whose pg2 is free and which has a node group or a stack entry; part 2 tests one primitive of the OLDER group
+// and moves the younger one up when the older is used up; the vote postpones part 2 while fewer than SOL_PRIM_MIN_Q2 lanes hold a primitive
+// and some lane can visit a node. better() is a total order on (t, dfs): the closest hit does not depend on the order of the tests, a
+// later test only delays a cull, so every frame is the one depth 1 computes. MEDIUM instances start a sub-search from part 2 and sit at
+// the register limit: they keep depth 1, as do the query, radiance, visibility and A/B kernels.
+template <bool COUNT, bool MEDIUM, bool STRICT = false, bool PACK = false, int QUEUE = 1>
 DEV void trav_step_wave(const DevScene& S, Trav& t, bool act, const Stack& st, const Rng& rng, uint32_t depth, Counters& cnt) {
+  static_assert(QUEUE == 1 || (QUEUE == 2 && !MEDIUM && !PACK), "a primitive queue of depth 2: plain two-dword searches only");
   // (MEDIUM) a lane inside a medium test rests its world search: no node visit, no primitive of its group, until the test is over
   const bool world = !MEDIUM || t.m.phase == 0u;
   if (act) {
     phase_tick<COUNT>(cnt, 0);
-    if (world && (t.pg >> 24) == 0u) wide_visit<COUNT, PACK>(t, st, cnt);
+    if (QUEUE == 1) {
+      if (world && (t.pg >> 24) == 0u) wide_visit<COUNT, PACK>(t, st, cnt);
+    } else {  // (a lane that holds nothing has a node group or a stack entry: its search is running)
+      if ((t.pg2 >> 24) == 0u && ((t.pg >> 24) == 0u || (t.g0 >> 24) != 0u || t.sp != t.sp_base)) wide_visit<COUNT, PACK, QUEUE>(t, st, cnt);
+    }
   }
-  const bool has_prim = act && world && (t.pg >> 24) != 0u;
-  const bool has_inner = act && world && !has_prim && ((t.g0 >> 24) != 0u || t.sp != t.sp_base);
+  const bool has_prim = act && world && (t.pg >> 24) != 0u;  // (an empty pg: an empty queue)
+  // can the lane visit a node in the next turn? Its queue has room and it has a node group or a stack entry
+  const bool room = QUEUE == 1 ? !has_prim : (t.pg2 >> 24) == 0u;
+  const bool has_inner = act && world && room && ((t.g0 >> 24) != 0u || t.sp != t.sp_base);
   if (act && world && !has_prim && !has_inner) t.cur = REF_DONE;
   const unsigned long long prim_m = sol_ballot(has_prim);
   bool prims = true;  // does the primitive part run in this turn?
+  constexpr int prim_min = QUEUE == 1 ? SOL_PRIM_MIN : SOL_PRIM_MIN_Q2;  // (1: never wait)
   if (!MEDIUM) {
     if (prim_m == 0ull) return;
-#if SOL_PRIM_MIN > 1
-    // Postponed primitive tests: while fewer than SOL_PRIM_MIN lanes hold primitives and some lane has an inner node to visit
+    // Postponed primitive tests: while fewer than SOL_PRIM_MIN (depth 2: SOL_PRIM_MIN_Q2) lanes hold primitives and some lane has an inner node to visit
     // next turn, the holders wait (a later primitive part then runs with more lanes enabled). Results do not depend on the order
     // of the tests.
-    if (sol_ballot(has_inner) != 0ull && (int)__popcll(prim_m) < SOL_PRIM_MIN) return;
-#endif
+    if (prim_min > 1 && sol_ballot(has_inner) != 0ull && (int)__popcll(prim_m) < prim_min) return;
   } else {  // (the same votes, but part 3 below still has to run)
     prims = prim_m != 0ull;
-#if SOL_PRIM_MIN > 1
-    if (prims && sol_ballot(has_inner) != 0ull && (int)__popcll(prim_m) < SOL_PRIM_MIN) prims = false;
-#endif
+    if (prim_min > 1 && prims && sol_ballot(has_inner) != 0ull && (int)__popcll(prim_m) < prim_min) prims = false;
   }
-  const uint32_t lkind = t.g1 >> 29;  // (no group was popped since this node's test: a lane with pending primitives skips part 1)
+  // (depth 1: no group was popped since this node's test - a lane with pending primitives skips part 1; depth 2: the older group's own description)
+  const uint32_t lkind = QUEUE == 1 ? t.g1 >> 29 : (t.pd >> 13) & 7u;
   if (has_prim && prims) {
     const uint32_t slot = (uint32_t)__builtin_ctz(t.pg >> 24);
     t.pg &= ~(1u << (24u + slot));
-    uint32_t idx = (t.pg & SOL_WIDE_MAX_INDEX) + __popc(__builtin_amdgcn_ubfe(t.g1, 22u, slot));  // lmask bits below `slot`
+    uint32_t idx = (t.pg & SOL_WIDE_MAX_INDEX) + __popc(QUEUE == 1 ? __builtin_amdgcn_ubfe(t.g1, 22u, slot) : __builtin_amdgcn_ubfe(t.pd, 6u, slot));  // lmask bits below `slot`
     // Triangle leaves go straight to their test: through prim_test's chain (leaf kind -> reference kind -> compare tree) every
     // test had nine more vector instructions in front of it (C3 74.8 -> 73.3 ms per 64 spp); the other kinds keep the chain.
     if (lkind == SOL_LEAF_TRIANGLES) {
@@ -706,7 +738,12 @@ DEV void trav_step_wave(const DevScene& S, Trav& t, bool act, const Stack& st, c
       if (MEDIUM && kind == SOL_REF_MEDIUM) medium_begin(S, t, idx);
       else prim_test<COUNT, STRICT ? 1 : 0>(S, t, st, kind, idx, cnt);
     }
-    if ((t.pg >> 24) == 0u && (t.g0 >> 24) == 0u && t.sp == t.sp_base && !(MEDIUM && t.m.phase != 0u)) t.cur = REF_DONE;
+    if (QUEUE == 2 && (t.pg >> 24) == 0u) {  // the older group is used up: the younger one moves up
+      t.pg = t.pg2;
+      t.pg2 = 0u;
+      t.pd >>= 16;
+    }
+    if (trav_nothing_left(t) && !(MEDIUM && t.m.phase != 0u)) t.cur = REF_DONE;
   }
   if (MEDIUM) {  // part 3: one boundary step for every lane inside a medium test (those that began it in this turn included)
     const bool in_medium = act && t.m.phase != 0u;

@@ -28,6 +28,15 @@
                             // MI355X, 1080p x 128 spp, C3 / C2 ms: 1: 199.8 / 128.4, 4: 196.6 / 126.5, 8: 193.1 / 122.5,
                             // 12: 193.0 / 122.6, 16: 199.1 / 129.7, 24: 215.7 / 148.0
 #endif
+#ifndef SOL_PRIM_QUEUE
+#define SOL_PRIM_QUEUE 2    // trav_step_wave in sol_render_kernel's plain instances: primitive groups a lane may hold while it goes on
+                            // visiting nodes (1: it waits until its one group is empty). profiles/prim_queue_ab.txt
+#endif
+#ifndef SOL_PRIM_MIN_Q2
+#define SOL_PRIM_MIN_Q2 12  // SOL_PRIM_MIN of the searches stepped at queue depth 2 (depth 1 keeps its own: the query, radiance, visibility and
+                            // MEDIUM kernels are not touched). MI355X, 1080p x 64 spp, ms, depth 1 / depth 2 with 8 / 10 / 12 / 16:
+                            // C3 58.9 / 57.8 / 57.4 / 57.3 / 58.4, C2 30.2 / 30.8 / 30.4 / 30.1 / 30.8
+#endif
 #ifndef SOL_FETCH_PRIO
 #define SOL_FETCH_PRIO 33        // s_setprio around the loads of a search step (units: node fetch, tens: triangle fetch; 0 off): the wave
                                  // about to fetch issues its addresses and loads ahead of the waves in their arithmetic
