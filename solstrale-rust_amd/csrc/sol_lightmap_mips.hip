@@ -10,14 +10,15 @@
 //   sol_lightmap_mips_tail_kernel   one workgroup of 256 lanes takes a source level of at most 64 x 64 texels all the way to the last level: each
 //                               level is written to the chain and to one of two LDS buffers, the next level reads the LDS copy. Only for rows of
 //                               at most LMM_TAIL_MAX_STRIDE words (the two largest levels and their cover fit 64 KiB of LDS).
-//   sol_lightmap_sample_lod_kernel  a lane per surface row, as sol_lightmap_sample_kernel: the cover bytes of both levels, then the finiteness walk,
-//                               then the sums channel by channel. The channel count is a run-time number: nothing is kept in an array.
+//   sol_lightmap_sample_lod_kernel  a lane per surface row: the steps of sol_lightmap_lookup.h once per level. Its own: the walk of the level
+//                               layout, lml_taps, the cover byte of the levels above 0 and lml_blend.
 //   sol_lightmap_lod_kernel     a thread per row: two dwordx4 of the ray, one of the hit, the surface row, fifteen words of the triangle; one float out.
 // No atomics, no scratch; every store is a vector store.
 #include <hip/hip_runtime.h>
 
 #include "../../include/solstrale_hip.h"
 #include "sol_launch.h"
+#include "sol_lightmap_lookup.h"
 #include "sol_lightmap_mips.h"
 
 #define LMM_WG 256
@@ -194,12 +195,17 @@ struct LmlAtlas {
   uint32_t guard;
   float chart_radius;
 };
-// One level of a row's lookup: the taps, the live ones, their weights. (rows, cover): the level's; level 0 has texels / pass_of instead of cover.
+// One level of a row's lookup: the taps, the covered ones, then the live ones and their weights. rows: the level's.
 struct LmlLevel {
   LsTaps T;
-  uint32_t live, count, W;
-  float w[4], wsum;
+  uint32_t live, W;
+  LsWeights R;
   const float* rows;
+};
+// a tap of a level above 0: its cover byte (level 0 has texels / pass_of instead: LsGuardTest)
+struct LmlCoverTest {
+  const uint8_t* cover;
+  DEV bool operator()(size_t at) const { return ls_covered(true, (uint32_t)ldg_u8(cover + at), 0u); }
 };
 
 __global__ __launch_bounds__(LMM_WG) void sol_lightmap_sample_lod_kernel(LmlAtlas A, const float* __restrict__ uvs, const uint32_t* __restrict__ texels,
@@ -212,34 +218,7 @@ __global__ __launch_bounds__(LMM_WG) void sol_lightmap_sample_lod_kernel(LmlAtla
   if (x >= n) return;
   const sol_v4u row = *(const SOL_AS1 sol_v4u*)(coords + (size_t)x * 4);
   uint32_t* o = out + (size_t)x * (A.channels + 1u);
-  const float b1 = __uint_as_float(row.y), b2 = __uint_as_float(row.z);
-
-  // 1. the row, as sol_lightmap_sample_kernel judges it: nothing of it is an address before it is known to be one
-  bool valid = row.w != 0u && row.x != SOL_LS_NONE && row.x < A.n_triangles && lf_finite(b1) && lf_finite(b2);
-  float uv[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  float px = 0.0f, py = 0.0f, pz = 0.0f;
-  const float b0 = (1.0f - b1) - b2;
-  if (valid) {
-    const SOL_AS1 float* t = (const SOL_AS1 float*)(uvs + (size_t)row.x * 6);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      uv[k] = t[k];
-      valid = valid && lf_finite(uv[k]);
-    }
-    if (A.guard) {
-      const SOL_AS1 float* p = (const SOL_AS1 float*)(vertices + (size_t)row.x * 9);
-      float v[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        v[k] = p[k];
-        valid = valid && lf_finite(v[k]);
-      }
-      px = ls_lerp3(v[0], v[3], v[6], b0, b1, b2);
-      py = ls_lerp3(v[1], v[4], v[7], b0, b1, b2);
-      pz = ls_lerp3(v[2], v[5], v[8], b0, b1, b2);
-    }
-  }
-  const float u = ls_lerp3(uv[0], uv[2], uv[4], b0, b1, b2), v = ls_lerp3(uv[1], uv[3], uv[5], b0, b1, b2);
+  const LsSurface S = ls_surface(row, A.n_triangles, uvs, vertices, A.guard != 0u);  // 1. the row
 
   // 2. the two levels and the fraction
   const float lambda = lml_clamp(((const SOL_AS1 float*)lods)[x], A.levels);
@@ -251,9 +230,9 @@ __global__ __launch_bounds__(LMM_WG) void sol_lightmap_sample_lod_kernel(LmlAtla
   for (uint32_t s = 0; s < 2u; ++s) {
     LmlLevel& Q = L[s];
     Q.T = LsTaps{0, 0, 0.0f, 0.0f, 0u};
-    Q.live = 0u; Q.count = 0u; Q.W = 1u; Q.wsum = 0.0f; Q.rows = values;
+    Q.live = 0u; Q.W = 1u; Q.rows = values;
     const uint32_t l = l0 + s;
-    if (!valid || (s == 1u && !two)) continue;
+    if (!S.valid || (s == 1u && !two)) continue;
     // the level's size and place by the layout rule
     uint32_t Wl = A.W, Hl = A.H;
     size_t at = 0;
@@ -262,76 +241,26 @@ __global__ __launch_bounds__(LMM_WG) void sol_lightmap_sample_lod_kernel(LmlAtla
       if (k < l) at += (size_t)Wl * Hl;
     }
     Q.W = Wl;
-    Q.T = l == 0u ? ls_taps(u, v, A.W, A.H, false) : lml_taps(u, v, A.W, A.H, l, Wl, Hl);
+    Q.T = l == 0u ? ls_taps(S.u, S.v, A.W, A.H, false) : lml_taps(S.u, S.v, A.W, A.H, l, Wl, Hl);
     Q.rows = l == 0u ? values : mips + at * A.stride_words;
     // 3. coverage (and at level 0 the chart guard) of every tap, before any value is fetched
-    const float r2 = A.chart_radius * A.chart_radius;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-      if (k >= Q.T.n) continue;
-      const int i = ls_tap_i(Q.T, k), j = ls_tap_j(Q.T, k);
-      if (!ls_tap_inside(i, j, Wl, Hl)) continue;
-      const size_t tap = (size_t)j * Wl + (size_t)i;
-      if (l == 0u) {
-        sol_v4u tx = {0u, 0u, 0u, 0u};
-        if (!pass_of || A.guard) tx = *(const SOL_AS1 sol_v4u*)(texels + tap * 4);
-        if (!ls_covered(pass_of != nullptr, pass_of ? (uint32_t)ldg_u8(pass_of + tap) : 0u, tx.x)) continue;
-        if (A.guard && tx.w != 0u) {
-          const sol_v4f q = *(const SOL_AS1 sol_v4f*)(points + tap * 8);
-          if (!ls_guard(tx.w, q.x, q.y, q.z, px, py, pz, r2)) continue;
-        }
-      } else {
-        if (!ls_covered(true, (uint32_t)ldg_u8(cover + at + tap), 0u)) continue;
-      }
-      Q.live |= 1u << k;
-    }
+    Q.live = l == 0u ? ls_live_taps(Q.T, Wl, Hl, ls_guard_test(texels, pass_of, points, A.guard != 0u, S, A.chart_radius))
+                     : ls_live_taps(Q.T, Wl, Hl, LmlCoverTest{cover + at});
   }
   // 4. the value words of the covered taps: one that is not finite takes its tap out; then weights, wsum and count
 #pragma unroll
-  for (uint32_t s = 0; s < 2u; ++s) {
-    LmlLevel& Q = L[s];
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-      if (!(Q.live & (1u << k))) continue;
-      const SOL_AS1 float* val = (const SOL_AS1 float*)(Q.rows + ((size_t)ls_tap_j(Q.T, k) * Q.W + (size_t)ls_tap_i(Q.T, k)) * A.stride_words);
-      bool finite = true;
-      for (uint32_t c = 0; c < A.channels; ++c) finite = finite && lf_finite(val[c]);
-      if (!finite) Q.live &= ~(1u << k);
-    }
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-      Q.w[k] = ls_tap_weight(Q.T, k);
-      if (Q.live & (1u << k)) {
-        Q.wsum = Q.wsum + Q.w[k];
-        ++Q.count;
-      }
-    }
-    if (!(Q.wsum > 0.0f)) Q.live = 0u, Q.count = 0u;
-  }
+  for (uint32_t s = 0; s < 2u; ++s) L[s].R = ls_weights(L[s].T, ls_drop_nonfinite(L[s].live, L[s].T, L[s].W, L[s].rows, A.stride_words, A.channels));
   // 5. the answer
-  const bool have_a = L[0].live != 0u, have_b = L[1].live != 0u;
+  const bool have_a = L[0].R.live != 0u, have_b = L[1].R.live != 0u;
   const float g = 1.0f - f;
-  const size_t at_a = ((size_t)L[0].T.j0 * L[0].W + (size_t)L[0].T.i0) * A.stride_words, si_a = A.stride_words, sj_a = (size_t)L[0].W * A.stride_words;
-  const size_t at_b = ((size_t)L[1].T.j0 * L[1].W + (size_t)L[1].T.i0) * A.stride_words, sj_b = (size_t)L[1].W * A.stride_words;
+  const LsAt at_a = ls_at(L[0].T, L[0].W, A.stride_words), at_b = ls_at(L[1].T, L[1].W, A.stride_words);
   for (uint32_t c = 0; c < A.channels; ++c) {
     float a = 0.0f, b = 0.0f;
-    if (have_a) {
-      float sum = 0.0f;
-#pragma unroll
-      for (uint32_t k = 0; k < 4u; ++k)
-        if (L[0].live & (1u << k)) sum = sum + (L[0].w[k] * ((const SOL_AS1 float*)L[0].rows)[at_a + (k & 1u) * si_a + (k >> 1) * sj_a + c]);
-      a = sum / L[0].wsum;
-    }
-    if (have_b) {
-      float sum = 0.0f;
-#pragma unroll
-      for (uint32_t k = 0; k < 4u; ++k)
-        if (L[1].live & (1u << k)) sum = sum + (L[1].w[k] * ((const SOL_AS1 float*)L[1].rows)[at_b + (k & 1u) * si_a + (k >> 1) * sj_b + c]);
-      b = sum / L[1].wsum;
-    }
+    if (have_a) a = ls_bilinear(L[0].R, L[0].rows, at_a, c);
+    if (have_b) b = ls_bilinear(L[1].R, L[1].rows, at_b, c);
     o[c] = (have_a && have_b) ? __float_as_uint(lml_blend(a, b, g, f)) : have_a ? __float_as_uint(a) : have_b ? __float_as_uint(b) : 0u;
   }
-  o[A.channels] = L[0].count + L[1].count;
+  o[A.channels] = L[0].R.count + L[1].R.count;
 }
 
 // ---- the level of detail of a hit ----
@@ -346,7 +275,7 @@ __global__ __launch_bounds__(LMM_WG) void sol_lightmap_lod_kernel(const uint32_t
   const sol_v4u row = *(const SOL_AS1 sol_v4u*)(coords + (size_t)x * 4);
   const float t = __uint_as_float(h0.x);
   float lambda = 0.0f;
-  const bool ok = h0.w == SOL_RAY_HIT && row.w != 0u && row.x != SOL_LS_NONE && row.x < n_triangles && lf_finite(t) && t > 0.0f && lf_finite(r0.x) &&
+  const bool ok = h0.w == SOL_RAY_HIT && ls_row_listed(row, n_triangles) && lf_finite(t) && t > 0.0f && lf_finite(r0.x) &&
                   lf_finite(r0.y) && lf_finite(r0.z) && lf_finite(r1.x) && lf_finite(r1.y) && lf_finite(r1.z);
   if (ok) {
     float uv[6], pos[9];

@@ -1,12 +1,11 @@
 // sol_lightmap_sh.hip -- directional lightmaps: an atlas of SolSh9 rows looked up at surface rows and shaded at the caller's normals, and the
 // normals of surface rows (sol_lightmap_sh, sol_lightmap_normals; sol_lightmap_sh.cpp). The rule is sol_lightmap_sh.h (and, for
-// the lookup, sol_lightmap_sample.h); the kernels only fetch, exchange, call it and store.
+// the lookup, sol_lightmap_sample.h through the shared steps of sol_lightmap_lookup.h); the kernels only fetch, exchange, call it and store.
 //
 //   sol_lightmap_sh_kernel       EIGHT lanes to a surface row, eight rows to a wave. Lane g of an octet owns dwordx4 g of a 112-byte value row
 //                                (g = 0..6: words 0..27; lane 7 owns none), so a tap of a row is ONE contiguous 112-byte fetch by seven
-//                                neighbouring lanes. The row, its UV words and (with the chart guard) its vertex words are read by every lane of
-//                                the octet - one address, one request. Coverage and the chart guard are divided: lane t < 4 decides tap t (the
-//                                coverage byte or the SolTexel, the first dwordx4 of the point row) and a ballot hands all eight lanes the same
+//                                neighbouring lanes. The row (ls_surface) is read by every lane of the octet - one address, one request. The
+//                                tap decision is divided: lane t < 4 decides tap t (ls_tap_live) and a ballot hands all eight lanes the same
 //                                mask. The seven value lanes then fetch the covered taps and judge their own words; a ballot per tap is the AND
 //                                over the octet. Coefficient mode stores the lane's dwordx4 of the answer (seven to a row). Evaluation mode:
 //                                each lane forms t = B_k * L[w] for its words and writes them to LDS as one ds_write_b128 (32 rows x 28 words =
@@ -27,6 +26,7 @@
 
 #include "../../include/solstrale_hip.h"
 #include "sol_launch.h"
+#include "sol_lightmap_lookup.h"
 #include "sol_lightmap_sh.h"
 
 #define LSH_WG 256
@@ -65,49 +65,11 @@ __global__ __launch_bounds__(LSH_WG) void sol_lightmap_sh_kernel(LshAtlas A, con
   // 1. the row (every lane of the octet: one address): nothing of it is an address before it is known to be one
   sol_v4u row = {SOL_LS_NONE, 0u, 0u, 0u};
   if (in_range) row = *(const SOL_AS1 sol_v4u*)(coords + (size_t)x * 4);
-  const float b1 = __uint_as_float(row.y), b2 = __uint_as_float(row.z);
-  bool valid = in_range && row.w != 0u && row.x != SOL_LS_NONE && row.x < A.n_triangles && lf_finite(b1) && lf_finite(b2);
-  float uv[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  float px = 0.0f, py = 0.0f, pz = 0.0f;
-  const float b0 = (1.0f - b1) - b2;
-  if (valid) {
-    const SOL_AS1 float* t = (const SOL_AS1 float*)(uvs + (size_t)row.x * 6);
-#pragma unroll
-    for (int k = 0; k < 6; ++k) {
-      uv[k] = t[k];
-      valid = valid && lf_finite(uv[k]);
-    }
-    if (A.guard) {
-      const SOL_AS1 float* p = (const SOL_AS1 float*)(vertices + (size_t)row.x * 9);
-      float v[9];
-#pragma unroll
-      for (int k = 0; k < 9; ++k) {
-        v[k] = p[k];
-        valid = valid && lf_finite(v[k]);
-      }
-      px = ls_lerp3(v[0], v[3], v[6], b0, b1, b2);
-      py = ls_lerp3(v[1], v[4], v[7], b0, b1, b2);
-      pz = ls_lerp3(v[2], v[5], v[8], b0, b1, b2);
-    }
-  }
-  LsTaps T = {0, 0, 0.0f, 0.0f, 0u};
-  if (valid) T = ls_taps(ls_lerp3(uv[0], uv[2], uv[4], b0, b1, b2), ls_lerp3(uv[1], uv[3], uv[5], b0, b1, b2), A.W, A.H, A.nearest != 0u);
+  const LsSurface S = ls_surface(row, A.n_triangles, uvs, vertices, A.guard != 0u);  // (a row beyond n is SOL_LS_NONE: not valid)
+  const LsTaps T = ls_surface_taps(S, A.W, A.H, A.nearest != 0u);
 
   // 2. coverage and the chart guard: lane t of the octet decides tap t, before any value is fetched
-  bool mine = false;
-  if (g < T.n) {  // (T.n <= 4)
-    const int i = ls_tap_i(T, g), j = ls_tap_j(T, g);
-    if (ls_tap_inside(i, j, A.W, A.H)) {
-      const size_t at = (size_t)j * A.W + (size_t)i;
-      sol_v4u tx = {0u, 0u, 0u, 0u};
-      if (!pass_of || A.guard) tx = *(const SOL_AS1 sol_v4u*)(texels + at * 4);
-      mine = ls_covered(pass_of != nullptr, pass_of ? (uint32_t)ldg_u8(pass_of + at) : 0u, tx.x);
-      if (mine && A.guard && tx.w != 0u) {
-        const sol_v4f q = *(const SOL_AS1 sol_v4f*)(points + at * 8);
-        mine = ls_guard(tx.w, q.x, q.y, q.z, px, py, pz, A.chart_radius * A.chart_radius);
-      }
-    }
-  }
+  const bool mine = ls_tap_live(T, g, A.W, A.H, ls_guard_test(texels, pass_of, points, A.guard != 0u, S, A.chart_radius));
   uint32_t live = (uint32_t)(sol_ballot(mine) >> octet_shift) & 0xFu;  // bit k: tap k; the same in all eight lanes
 
   // 3. the value words of the covered taps, a dwordx4 a lane: one word that is not finite takes its tap out (word 27 is not judged)
@@ -122,30 +84,19 @@ __global__ __launch_bounds__(LSH_WG) void sol_lightmap_sh_kernel(LshAtlas A, con
   }
 
   // 4. the interpolated coefficients of this lane's four words
-  float w[4] = {0.0f, 0.0f, 0.0f, 0.0f}, wsum = 0.0f;
-  uint32_t count = 0u;
-  if (A.nearest) {
-    count = live;
-  } else {
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) {
-      w[k] = ls_tap_weight(T, k);
-      if (live & (1u << k)) {
-        wsum = wsum + w[k];
-        ++count;
-      }
-    }
-    if (!(wsum > 0.0f)) live = 0u, count = 0u;
-  }
+  LsWeights R = {{0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, live, live};  // (nearest: the count is the one tap's bit)
+  if (!A.nearest) R = ls_weights(T, live);
+  live = R.live;
+  const uint32_t count = R.count;
   sol_v4f L = {0.0f, 0.0f, 0.0f, 0.0f};
   if (live) {
     if (A.nearest) {
       L = val[0];  // the one tap's words, copied
     } else {
-      L.x = lsh_word(live, w, val[0].x, val[1].x, val[2].x, val[3].x, wsum);
-      L.y = lsh_word(live, w, val[0].y, val[1].y, val[2].y, val[3].y, wsum);
-      L.z = lsh_word(live, w, val[0].z, val[1].z, val[2].z, val[3].z, wsum);
-      L.w = lsh_word(live, w, val[0].w, val[1].w, val[2].w, val[3].w, wsum);
+      L.x = lsh_word(live, R.w, val[0].x, val[1].x, val[2].x, val[3].x, R.wsum);
+      L.y = lsh_word(live, R.w, val[0].y, val[1].y, val[2].y, val[3].y, R.wsum);
+      L.z = lsh_word(live, R.w, val[0].z, val[1].z, val[2].z, val[3].z, R.wsum);
+      L.w = lsh_word(live, R.w, val[0].w, val[1].w, val[2].w, val[3].w, R.wsum);
     }
   }
 
@@ -191,7 +142,7 @@ __global__ __launch_bounds__(LSH_WG) void sol_lightmap_normals_kernel(const uint
   if (x >= n) return;
   const sol_v4u row = *(const SOL_AS1 sol_v4u*)(coords + (size_t)x * 4);
   const float b1 = __uint_as_float(row.y), b2 = __uint_as_float(row.z);
-  bool valid = row.w != 0u && row.x != SOL_LS_NONE && row.x < n_triangles && lf_finite(b1) && lf_finite(b2);
+  bool valid = ls_row_valid(row, n_triangles);
   f3 unit = {0.0f, 0.0f, 0.0f};
   if (valid) {
     float pos[9], nv[9];
