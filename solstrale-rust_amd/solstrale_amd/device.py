@@ -2,6 +2,7 @@
 fallback: every call goes to the HIP library and raises if it fails (e.g. SOL_EDEVICE without a GPU)."""
 import ctypes as C
 import math
+from collections import namedtuple
 
 import numpy as np
 
@@ -301,6 +302,43 @@ class VolumeGrid:
         return g
 
 
+# A SolRayHit of sol_query and a SolVisibility of sol_visibility; DeviceScene carries both names too.
+RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("status", np.uint32), ("kind", np.uint32),
+                          ("dfs_index", np.uint32), ("material", np.uint32), ("reserved", np.uint32)])
+VISIBILITY_DTYPE = np.dtype([("bent", np.float32, (3,)), ("open", np.uint32), ("t_sum", np.float32), ("t2_sum", np.float32),
+                             ("hits", np.uint32), ("samples", np.uint32)])
+
+# The element layouts of the array arguments and answers of the two-route entry points, written once: name -> (the structured host dtype or
+# None, the host element dtype, the device dtype, what the host route takes besides the structured dtype). A structured array [..] is a device
+# tensor [.., words] of its 32-bit words: LIGHTMAP_TEXEL_DTYPE [n] <-> int32 [n, 4], OCT_TEXEL_DTYPE [n, t] <-> float32 [n, t, 4]. On the host
+# route "cast" takes any numbers and converts them (for a record: its raw rows [.., words]), "reshape" does the same for any shape that holds
+# whole rows, "bits" takes uint32 or int32 and reinterprets them, and None takes the structured dtype alone; a tensor is brought over with
+# .cpu() first and then goes as its raw rows.
+_LAYOUTS = {
+    "f32": (None, np.float32, "float32", "cast"),
+    "f64": (None, np.float64, "float64", "cast"),
+    "u8": (None, np.uint8, "uint8", "cast"),
+    "u32": (None, np.uint32, "int32", "cast"),
+    "words": (None, np.uint32, "int32", "bits"),
+    "texel": (LIGHTMAP_TEXEL_DTYPE, np.int32, "int32", None),
+    "hit": (RAY_HIT_DTYPE, np.int32, "int32", None),
+    "moments": (MOMENTS_DTYPE, np.float32, "float32", "cast"),
+    "visibility": (VISIBILITY_DTYPE, np.float32, "float32", "cast"),
+    "probe": (VOLUME_PROBE_DTYPE, np.float32, "float32", "cast"),
+    "oct": (OCT_TEXEL_DTYPE, np.float32, "float32", "reshape"),
+    "depth": (DEPTH_TEXEL_DTYPE, np.float32, "float32", "reshape"),
+}
+
+# One array argument of a two-route entry point: its name, the caller's value, its layout (a key of _LAYOUTS) and its shape in elements of that
+# layout - an int is an extent, None any extent, a string a symbol that the first argument to carry it binds for the others ("n", "k"). optional:
+# None is taken and passes a null pointer; null_if_empty: so does an array without elements; aligned: a tensor's memory must be 16-byte aligned
+# (the volume kernels move whole 16-byte words); flat: the host route takes any shape with as many elements (a plane as its rows); upload: on the
+# device route a host value is staged as on the host route and copied to the scene's device ("any": so is a tensor that does not fit as it is).
+_Arg = namedtuple("_Arg", "name value layout shape optional null_if_empty aligned flat upload", defaults=(False,) * 5)
+# One answer: np.zeros of the layout's host dtype on the host route, torch.empty of its words on the device route (zero: torch.zeros).
+_Out = namedtuple("_Out", "name layout shape zero null_if_empty", defaults=(False, False))
+
+
 class DeviceScene:
     """sol_scene_create .. sol_scene_destroy"""
 
@@ -593,26 +631,146 @@ class DeviceScene:
         return out
 
     # ---- ray queries (EXTENSION) ----
-    RAY_HIT_DTYPE = np.dtype([("t", np.float32), ("u", np.float32), ("v", np.float32), ("status", np.uint32), ("kind", np.uint32),
-                              ("dfs_index", np.uint32), ("material", np.uint32), ("reserved", np.uint32)])
+    RAY_HIT_DTYPE = RAY_HIT_DTYPE
+
+    # The two routes of an array entry point: sol_x takes host arrays and stages them, sol_x_dev takes device pointers, both in the same positions.
+    @staticmethod
+    def _on_device(x):
+        """The route a value asks for: a tensor (whatever has data_ptr) goes the device route, everything else the host route."""
+        return hasattr(x, "data_ptr")
+
+    @staticmethod
+    def _fit(shape, pattern, dims):
+        """The symbols of `pattern` that `shape` binds beyond `dims`; None where it does not fit."""
+        if len(shape) != len(pattern):
+            return None
+        new = {}
+        for have, want in zip(shape, pattern):
+            if isinstance(want, str):
+                want = dims[want] if want in dims else new.setdefault(want, int(have))
+            if want is not None and want != have:
+                return None
+        return new
+
+    @staticmethod
+    def _wanted(a, device):
+        """What argument `a` has to be, for the refusal."""
+        st, word, dev_dtype, raw = _LAYOUTS[a.layout]
+        rows = a.shape + (() if st is None else (st.itemsize // 4,))
+
+        def text(shape):
+            return "[" + ", ".join("*" if s is None else str(s) for s in shape) + "]"
+        if device:
+            return f"{a.name}: a contiguous {dev_dtype} tensor of shape {text(rows)} on the scene's device"
+        if st is None:
+            return f"{a.name}: {np.dtype(word).name} numbers of shape {text(rows)}" + (", or as many in another shape" if a.flat else "")
+        return f"{a.name}: {a.layout} records of shape {text(a.shape)}" + ("" if raw is None else f", or their raw {np.dtype(word).name} rows {text(rows)}")
+
+    def _host_rows(self, a, dims):
+        """Argument `a` as the host route hands it over: a contiguous array of its layout, its shape checked (its symbols go to `dims`)."""
+        st, word, _, raw = _LAYOUTS[a.layout]
+        x = np.ascontiguousarray(a.value.cpu().numpy() if self._on_device(a.value) else a.value)
+        pattern, fits = a.shape, True
+        if st is not None and raw is None:  # (the structured dtype alone; a tensor holds its raw rows)
+            x = x.view(st).reshape(-1) if self._on_device(a.value) else x
+            fits = x.dtype == st
+        elif raw == "bits" and x.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)):
+            raise ValueError(f"{a.name}: 32-bit words (a uint32 or int32 array, or an int32 tensor), not {x.dtype}")
+        else:  # (the words of the layout: a structured array reinterpreted, anything else converted)
+            record = st is not None and x.dtype == st
+            x = x.view(word) if record or raw == "bits" else np.ascontiguousarray(x.astype(word, copy=False))
+            if st is not None:
+                pattern += (st.itemsize // 4,)
+                if raw == "reshape" and x.size % math.prod(pattern[1:]) == 0:
+                    x = x.reshape((-1,) + pattern[1:])
+                elif record:
+                    x = x.reshape(-1, pattern[-1])
+        if a.flat:
+            x, pattern = x.reshape(-1), (math.prod(pattern),) if len(pattern) > 1 else pattern
+        new = self._fit(x.shape, pattern, dims) if fits else None
+        if new is None:
+            raise ValueError(self._wanted(a, False))
+        dims.update(new)
+        return x
+
+    def _stage(self, args, device):
+        """Makes or checks the arrays of one call (`args`: _Arg, in the order they are checked) and waits for torch's stream when one of them is
+        on the device. Returns (the pointers by name - None: a null pointer -, the extents the symbols stand for, what must live through the call)."""
+        p, dims, keep = {}, {}, []
+        if device:
+            import torch
+        for a in args:
+            st, _, dev_dtype, raw = _LAYOUTS[a.layout]
+            x, staged = a.value, None
+            if x is None:
+                if not a.optional:
+                    raise ValueError(self._wanted(a, device) + ", not None")
+                p[a.name] = None
+                continue
+            if device and self._on_device(x) and x.dtype == getattr(torch, dev_dtype) and x.is_contiguous() and x.is_cuda and x.device.index == self.device:
+                shape, pattern = tuple(x.shape), a.shape + (() if st is None else (st.itemsize // 4,))
+                if raw == "reshape" and shape:  # (a probe's map may come as one row)
+                    shape, pattern = (shape[0], math.prod(shape[1:])), (pattern[0], math.prod(pattern[1:]))
+                new = self._fit(shape, pattern, dims)
+                if new is not None:
+                    if a.aligned and x.data_ptr() % 16:  # (a view that starts inside an allocation: the kernels move whole 16-byte words)
+                        raise ValueError(f"{a.name}: the tensor's memory must be 16-byte aligned")
+                    dims.update(new)
+                    staged = x
+            if staged is None:
+                if device and not (a.upload == "any" or a.upload and not self._on_device(x)):
+                    raise ValueError(self._wanted(a, True))
+                staged = self._host_rows(a, dims)
+                if device:
+                    staged = torch.from_numpy(staged.view(np.int32) if staged.dtype == np.uint32 else staged).to(f"cuda:{self.device}")
+            keep.append(staged)
+            empty = not (staged.numel() if device else staged.size)
+            p[a.name] = None if a.null_if_empty and empty else staged.data_ptr() if device else staged.ctypes.data
+        if device and keep:
+            torch.cuda.current_stream(self.device).synchronize()  # (the tensors may still be in the making on torch's stream: the scene's is another)
+        return p, dims, keep
+
+    def _call(self, entry, args, outs, fn, device=None, dev_suffix="_dev", sync=True):
+        """One call of a two-route entry point. The first argument decides the route (or `device` does); the arrays are made or checked (_stage),
+        the answers `outs` (_Out) allocated, and fn(p, d) - p: the pointers of arguments and answers by name, d: the extents of the symbols - gives
+        the arguments after the handle, the same for sol_x and sol_x_dev. The device route waits for torch's stream before the call and, unless
+        the call blocks by itself (sync=False), for the scene's stream after it. Returns the answers by name."""
+        device = self._on_device(args[0].value) if device is None else device
+        p, d, keep = self._stage(args, device)
+        if device:
+            import torch
+        made = {}
+        for o in outs:
+            st, word, dev_dtype, _ = _LAYOUTS[o.layout]
+            shape = tuple(d[s] if isinstance(s, str) else int(s) for s in o.shape)
+            if device:
+                x = (torch.zeros if o.zero else torch.empty)(shape + (() if st is None else (st.itemsize // 4,)), dtype=getattr(torch, dev_dtype),
+                                                             device=f"cuda:{self.device}")
+            else:
+                x = np.zeros(shape, dtype=st or word)
+            made[o.name] = x
+            p[o.name] = None if o.null_if_empty and not math.prod(shape) else x.data_ptr() if device else x.ctypes.data
+        self._chk(getattr(self.lib, entry + (dev_suffix if device else ""))(self.h, *fn(p, d)))
+        if device and sync:
+            self.sync()
+        return made
+
+    @staticmethod
+    def _split(rows, shape=(3,)):
+        """The host route's [n, k + 1] rows of sums and a count as (sums [n, *shape] float32, counts [n] uint32); the device route's raw rows stay."""
+        if not isinstance(rows, np.ndarray):
+            return rows
+        return np.ascontiguousarray(rows[:, :-1]).reshape((-1,) + shape), np.ascontiguousarray(rows[:, -1]).view(np.uint32)
+
+    @staticmethod
+    def _stride(values):
+        """The bytes of a row of `values` for a config struct; 0 for what is not rows (the checks refuse it)."""
+        return 4 * int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
 
     def _query(self, mode, rays):
-        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: sol_query stages the arrays itself
-            a = np.ascontiguousarray(rays, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError("rays: an [n, 8] float32 array of (origin xyz, tmin, direction xyz, tmax)")
-            out = np.zeros(a.shape[0], dtype=np.uint32 if mode == _abi.SOL_QUERY_OCCLUDED else self.RAY_HIT_DTYPE)
-            self._chk(self.lib.sol_query(self.h, mode, a.ctypes.data, a.shape[0], out.ctypes.data))
-            return out
-        import torch
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
-            raise ValueError("rays: a contiguous [n, 8] float32 tensor on the scene's device")
-        n = int(rays.shape[0])
-        out = torch.empty((n,) if mode == _abi.SOL_QUERY_OCCLUDED else (n, 8), dtype=torch.int32, device=rays.device)
-        torch.cuda.current_stream(rays.device).synchronize()  # (the rays may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_query_dev(self.h, mode, C.c_void_p(rays.data_ptr()), n, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        answer = "u32" if mode == _abi.SOL_QUERY_OCCLUDED else "hit"
+        return self._call("sol_query", [_Arg("rays", rays, "f32", ("n", 8))], [_Out("out", answer, ("n",))],
+                          lambda p, d: (mode, p["rays"], d["n"], p["out"]))["out"]
 
     def closest_hits(self, rays):
         """sol_query, SOL_QUERY_CLOSEST. A numpy [n, 8] float32 array of (origin xyz, tmin, direction xyz, tmax) goes the host route and
@@ -650,48 +808,14 @@ class DeviceScene:
         before and for the scene's stream after the launch."""
         cfg = _abi.SolRadianceConfig(size=C.sizeof(_abi.SolRadianceConfig), samples=int(samples), first_sample=int(first_sample), first_draw=int(first_draw),
                                      seed=int(seed), key_base=int(key_base) & 0xFFFFFFFF)
-        return self._radiance(self.lib.sol_radiance, self.lib.sol_radiance_dev, "rays", "origin xyz, tmin, direction xyz, tmax", rays, keys, cfg)
+        return self._split(self._radiance("sol_radiance", "rays", rays, keys, cfg))
 
-    def _radiance(self, host_fn, dev_fn, what, row, rays, keys, cfg, words=4, raw=False):
-        """The two routes radiance(), irradiance(), irradiance_sh() and visibility() share: `rays` are the [n, 8] rows (`what`: their name in messages,
-        `row`: their words), `words` the 32-bit words of an answer (4: a SolRadiance, returned split into sums and counts; 28: a SolSh9 and 8: a
-        SolVisibility, returned raw)."""
-        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route: the library stages the arrays itself
-            a = np.ascontiguousarray(rays, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError(f"{what}: an [n, 8] float32 array of ({row})")
-            k = None
-            if keys is not None:
-                k = np.ascontiguousarray(keys.cpu().numpy() if hasattr(keys, "data_ptr") else keys).astype(np.uint32, copy=False)
-                if k.shape != (a.shape[0], 2):
-                    raise ValueError(f"keys: an [n, 2] uint32 array of (pixel, first_draw), one row per row of {what}")
-                k = np.ascontiguousarray(k)
-            out = np.zeros((a.shape[0], words), dtype=np.float32)
-            self._chk(host_fn(self.h, a.ctypes.data, None if k is None else k.ctypes.data, a.shape[0], C.byref(cfg), out.ctypes.data))
-            if words != 4 or raw:
-                return out
-            return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
-        import torch
-        n = self._device_rows(what, rays, keys)
-        out = torch.empty((n, words), dtype=torch.float32, device=rays.device)
-        torch.cuda.current_stream(rays.device).synchronize()  # (the rays may still be in the making on torch's stream: the scene's is another)
-        self._chk(dev_fn(self.h, C.c_void_p(rays.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(cfg),
-                         C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
-
-    def _device_rows(self, what, rays, keys):
-        """Checks the device tensors of a radiance or irradiance call; returns n."""
-        import torch
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous() or not rays.is_cuda:
-            raise ValueError(f"{what}: a contiguous [n, 8] float32 tensor on the scene's device")
-        if rays.device.index != self.device:
-            raise ValueError(f"{what}: the tensor is on cuda:{rays.device.index}, the scene on cuda:{self.device}")
-        n = int(rays.shape[0])
-        if keys is not None and (not hasattr(keys, "data_ptr") or keys.dtype != torch.int32 or tuple(keys.shape) != (n, 2) or not keys.is_contiguous()
-                                 or keys.device != rays.device):
-            raise ValueError(f"keys: a contiguous [n, 2] int32 tensor of (pixel, first_draw) on the device of {what}")
-        return n
+    def _radiance(self, entry, what, rays, keys, cfg, words=4, call=lambda *a: a):
+        """The call radiance(), irradiance(), irradiance_sh(), visibility() and their kin share: `rays` are the [n, 8] rows (`what`: their name in
+        messages), `keys` the optional [n, 2] rows of (pixel, first_draw), `words` the 32-bit words of an answer; `call` turns (rays, keys, n, config,
+        out) into the entry point's own arguments. Returns the raw [n, words] float32 rows of either route."""
+        return self._call(entry, [_Arg(what, rays, "f32", ("n", 8)), _Arg("keys", keys, "u32", ("n", 2), optional=True)], [_Out("out", "f32", ("n", words))],
+                          lambda p, d: call(p[what], p["keys"], d["n"], C.byref(cfg), p["out"]))["out"]
 
     # ---- irradiance queries (EXTENSION; DESIGN.md 20) ----
     IRRADIANCE_MODES = {"cosine": _abi.SOL_IRRADIANCE_COSINE, "sphere": _abi.SOL_IRRADIANCE_SPHERE}
@@ -707,31 +831,17 @@ class DeviceScene:
         on the device ("cosine": cosine-weighted about the normal, irradiance = pi * sum / samples; "sphere": uniform, mean radiance = sum /
         samples) and is then radiance()'s path. keys, key_base, first_draw and the two routes with their return shapes are radiance()'s."""
         cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
-        return self._radiance(self.lib.sol_irradiance, self.lib.sol_irradiance_dev, "points", "position xyz, tmin, normal xyz, tmax", points, keys, cfg)
+        return self._split(self._radiance("sol_irradiance", "points", points, keys, cfg))
 
     def irradiance_rays(self, points, sample, seed=0, keys=None, key_base=0, first_draw=0, mode="cosine"):
         """sol_irradiance_rays: the rays sample `sample` of irradiance() starts with and the keys its paths go on from, as ([n, 8] float32, [n, 2]
         int32) device tensors: radiance(rays, samples=1, first_sample=sample, seed=seed, keys=keys) is that sample's contribution, bit for bit.
         points and keys: device tensors as for irradiance(), or host arrays, which are copied to the scene's device first."""
-        import torch
         cfg = self._irradiance_config(1, sample, seed, key_base, first_draw, mode)
-        dev = f"cuda:{self.device}"
-        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):
-            a = np.ascontiguousarray(points, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError("points: an [n, 8] float32 array of (position xyz, tmin, normal xyz, tmax)")
-            points = torch.from_numpy(a).to(dev)
-        if keys is not None and not hasattr(keys, "data_ptr"):
-            k = np.ascontiguousarray(np.ascontiguousarray(keys).astype(np.uint32, copy=False))
-            keys = torch.from_numpy(k.view(np.int32)).to(dev)
-        n = self._device_rows("points", points, keys)
-        rays = torch.empty((n, 8), dtype=torch.float32, device=points.device)
-        keys_out = torch.empty((n, 2), dtype=torch.int32, device=points.device)
-        torch.cuda.current_stream(points.device).synchronize()  # (the points may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_irradiance_rays(self.h, C.c_void_p(points.data_ptr()), C.c_void_p(keys.data_ptr()) if keys is not None else None, n, C.byref(cfg),
-                                               C.c_void_p(rays.data_ptr()), C.c_void_p(keys_out.data_ptr())))
-        self.sync()
-        return rays, keys_out
+        out = self._call("sol_irradiance_rays", [_Arg("points", points, "f32", ("n", 8), upload=True), _Arg("keys", keys, "u32", ("n", 2), optional=True, upload=True)],
+                         [_Out("rays", "f32", ("n", 8)), _Out("keys_out", "u32", ("n", 2))],
+                         lambda p, d: (p["points"], p["keys"], d["n"], C.byref(cfg), p["rays"], p["keys_out"]), device=True, dev_suffix="")
+        return out["rays"], out["keys_out"]
 
     # ---- SH irradiance queries (EXTENSION; DESIGN.md 21) ----
     def irradiance_sh(self, points, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="sphere"):
@@ -742,14 +852,10 @@ class DeviceScene:
         irradiance for any normal; "cosine": pi x sh / samples estimates the cosine-weighted projection about the point's normal. points, keys,
         key_base, first_draw and the waits of the two routes are irradiance()'s."""
         cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
-        rows = self._radiance(self.lib.sol_irradiance_sh, self.lib.sol_irradiance_sh_dev, "points", "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=28)
-        if isinstance(rows, np.ndarray):
-            return np.ascontiguousarray(rows[:, :27]).reshape(-1, 9, 3), np.ascontiguousarray(rows[:, 27]).view(np.uint32)
-        return rows
+        return self._split(self._radiance("sol_irradiance_sh", "points", points, keys, cfg, words=28), (9, 3))
 
     # ---- visibility gathers (EXTENSION; DESIGN.md 22) ----
-    VISIBILITY_DTYPE = np.dtype([("bent", np.float32, (3,)), ("open", np.uint32), ("t_sum", np.float32), ("t2_sum", np.float32),
-                                 ("hits", np.uint32), ("samples", np.uint32)])
+    VISIBILITY_DTYPE = VISIBILITY_DTYPE
 
     def visibility(self, points, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="cosine", distances=False):
         """sol_visibility: how much of the hemisphere ("cosine") or of the sphere ("sphere") is open at the caller's points - rows of (position xyz,
@@ -761,11 +867,8 @@ class DeviceScene:
         (visibility_to_numpy views them as the structured array). points, keys, key_base, first_draw and the waits of the two routes are irradiance()'s."""
         cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
         qmode = _abi.SOL_QUERY_CLOSEST if distances else _abi.SOL_QUERY_OCCLUDED
-        rows = self._radiance(lambda h, *a: self.lib.sol_visibility(h, qmode, *a), lambda h, *a: self.lib.sol_visibility_dev(h, qmode, *a), "points",
-                              "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=8)
-        if isinstance(rows, np.ndarray):
-            return rows.view(self.VISIBILITY_DTYPE).reshape(-1)
-        return rows
+        rows = self._radiance("sol_visibility", "points", points, keys, cfg, words=8, call=lambda *a: (qmode, *a))
+        return rows.view(VISIBILITY_DTYPE).reshape(-1) if isinstance(rows, np.ndarray) else rows
 
     @classmethod
     def visibility_to_numpy(cls, rows):
@@ -783,37 +886,11 @@ class DeviceScene:
         cfg = _abi.SolLightmapConfig(size=C.sizeof(_abi.SolLightmapConfig), width=int(width), height=int(height),
                                      flags=_abi.SOL_LIGHTMAP_CONSERVATIVE if conservative else 0, tmin=float(tmin), tmax=float(tmax))
         wh = int(width) * int(height) if 0 < int(width) <= _abi.SOL_LIGHTMAP_MAX_SIZE and 0 < int(height) <= _abi.SOL_LIGHTMAP_MAX_SIZE else 1
-        arrays = (("vertices", vertices, (3, 3)), ("uvs", uvs, (3, 2)), ("normals", normals, (3, 3)))
-        if isinstance(vertices, np.ndarray) or not hasattr(vertices, "data_ptr"):  # the host route
-            a = []
-            for name, x, tail in arrays:
-                if x is None and name == "normals":
-                    a.append(None)
-                    continue
-                x = np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=np.float32)
-                if x.ndim != 3 or x.shape[1:] != tail or (a and x.shape[0] != a[0].shape[0]):
-                    raise ValueError(f"{name}: a float32 [n, {tail[0]}, {tail[1]}] array, one row per triangle")
-                a.append(x)
-            points = np.zeros((wh, 8), dtype=np.float32)
-            texels = np.zeros(wh, dtype=LIGHTMAP_TEXEL_DTYPE)
-            self._chk(self.lib.sol_lightmap_points(self.h, a[0].ctypes.data, None if a[2] is None else a[2].ctypes.data, a[1].ctypes.data, a[0].shape[0],
-                                                   C.byref(cfg), points.ctypes.data, texels.ctypes.data))
-            return points, texels
-        import torch
-        n = int(vertices.shape[0])
-        for name, x, tail in arrays:
-            if x is None:
-                continue
-            if (not hasattr(x, "data_ptr") or x.dtype != torch.float32 or x.dim() != 3 or tuple(x.shape) != (n,) + tail or not x.is_contiguous() or not x.is_cuda
-                    or x.device.index != self.device):
-                raise ValueError(f"{name}: a contiguous float32 [n, {tail[0]}, {tail[1]}] tensor on the scene's device, one row per triangle")
-        points = torch.empty((wh, 8), dtype=torch.float32, device=vertices.device)
-        texels = torch.empty((wh, 4), dtype=torch.int32, device=vertices.device)
-        torch.cuda.current_stream(vertices.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_points_dev(self.h, C.c_void_p(vertices.data_ptr()), C.c_void_p(normals.data_ptr()) if normals is not None else None,
-                                                   C.c_void_p(uvs.data_ptr()), n, C.byref(cfg), C.c_void_p(points.data_ptr()), C.c_void_p(texels.data_ptr())))
-        self.sync()
-        return points, texels
+        out = self._call("sol_lightmap_points", [_Arg("vertices", vertices, "f32", ("n", 3, 3)), _Arg("uvs", uvs, "f32", ("n", 3, 2)),
+                                                 _Arg("normals", normals, "f32", ("n", 3, 3), optional=True)],
+                         [_Out("points", "f32", (wh, 8)), _Out("texels", "texel", (wh,))],
+                         lambda p, d: (p["vertices"], p["normals"], p["uvs"], d["n"], C.byref(cfg), p["points"], p["texels"]))
+        return out["points"], out["texels"]
 
     def lightmap_dilate(self, values, texels, width, height, passes=1, channels=3, return_pass_of=False):
         """sol_lightmap_dilate: the border dilation that finishes a bake. values: `width * height` rows whose leading `channels` 32-bit words are
@@ -822,31 +899,10 @@ class DeviceScene:
         gets their mean, the rest of its row zero. Host arrays go the host route, device tensors the device route, and the answer has the shape and
         place of `values`. return_pass_of: also the uint8 plane [height, width] of 0 owned, k filled in pass k, 255 never filled."""
         width, height = int(width), int(height)
-        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            v = np.ascontiguousarray(values, dtype=np.float32)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            if v.ndim != 2 or v.shape[0] != width * height or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (width * height,):
-                raise ValueError("values: [width * height, k] float32 rows; texels: width * height LIGHTMAP_TEXEL_DTYPE rows")
-            out = np.zeros_like(v)
-            pass_of = np.zeros((height, width), dtype=np.uint8) if return_pass_of else None
-            self._chk(self.lib.sol_lightmap_dilate(self.h, t.ctypes.data, width, height, v.ctypes.data, int(channels), v.shape[1] * 4, int(passes), out.ctypes.data,
-                                                   None if pass_of is None else pass_of.ctypes.data))
-            return (out, pass_of) if return_pass_of else out
-        import torch
-        if (values.dtype != torch.float32 or values.dim() != 2 or values.shape[0] != width * height or not values.is_contiguous() or not values.is_cuda
-                or values.device.index != self.device):
-            raise ValueError("values: a contiguous [width * height, k] float32 tensor on the scene's device")
-        if (not hasattr(texels, "data_ptr") or texels.dtype != torch.int32 or tuple(texels.shape) != (width * height, 4) or not texels.is_contiguous()
-                or texels.device != values.device):
-            raise ValueError("texels: the contiguous [width * height, 4] int32 tensor lightmap_points returned, on the device of values")
-        out = torch.empty_like(values)
-        pass_of = torch.empty((height, width), dtype=torch.uint8, device=values.device) if return_pass_of else None
-        torch.cuda.current_stream(values.device).synchronize()  # (the values may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_dilate_dev(self.h, C.c_void_p(texels.data_ptr()), width, height, C.c_void_p(values.data_ptr()), int(channels),
-                                                   int(values.shape[1]) * 4, int(passes), C.c_void_p(out.data_ptr()),
-                                                   C.c_void_p(pass_of.data_ptr()) if pass_of is not None else None))
-        self.sync()
-        return (out, pass_of) if return_pass_of else out
+        out = self._call("sol_lightmap_dilate", [_Arg("values", values, "f32", (width * height, "k")), _Arg("texels", texels, "texel", (width * height,))],
+                         [_Out("out", "f32", (width * height, "k"))] + ([_Out("pass_of", "u8", (height, width))] if return_pass_of else []),
+                         lambda p, d: (p["texels"], width, height, p["values"], int(channels), d["k"] * 4, int(passes), p["out"], p.get("pass_of")))
+        return (out["out"], out["pass_of"]) if return_pass_of else out["out"]
 
     # ---- lightmap filtering (EXTENSION; DESIGN.md 26) ----
     def lightmap_filter(self, values, points, texels, width, height, sigma_position, sigma_plane=None, iterations=4, normal_power_log2=5, sigma_value=0.25,
@@ -861,39 +917,14 @@ class DeviceScene:
         steps 1, 2, 4, .. Rows of texels that are not live (no owner, or a word that is not finite) come back as they went in. Host arrays go the
         host route, device tensors the device route, and the answer has the shape and place of `values`."""
         width, height = int(width), int(height)
-        host = isinstance(values, np.ndarray) or not hasattr(values, "data_ptr")
-        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
         cfg = _abi.SolLightmapFilterConfig(size=C.sizeof(_abi.SolLightmapFilterConfig), width=width, height=height, iterations=int(iterations),
-                                           normal_power_log2=int(normal_power_log2), channels=int(channels), stride_bytes=4 * k,
+                                           normal_power_log2=int(normal_power_log2), channels=int(channels), stride_bytes=self._stride(values),
                                            sigma_position=float(sigma_position), sigma_plane=float(sigma_position if sigma_plane is None else sigma_plane),
                                            sigma_value=float(sigma_value), value_scale=float(value_scale))
-        if host:
-            v = np.ascontiguousarray(values, dtype=np.float32)
-            p = np.ascontiguousarray(points.cpu().numpy() if hasattr(points, "data_ptr") else points, dtype=np.float32)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            if (v.ndim != 2 or v.shape[0] != width * height or p.shape != (width * height, 8) or t.dtype != LIGHTMAP_TEXEL_DTYPE
-                    or t.shape != (width * height,)):
-                raise ValueError("values: [width * height, k] float32 rows; points: [width * height, 8] float32 rows; texels: width * height "
-                                 "LIGHTMAP_TEXEL_DTYPE rows")
-            out = np.zeros_like(v)
-            self._chk(self.lib.sol_lightmap_filter(self.h, C.byref(cfg), p.ctypes.data, t.ctypes.data, v.ctypes.data, out.ctypes.data))
-            return out
-        import torch
-        if (values.dtype != torch.float32 or values.dim() != 2 or values.shape[0] != width * height or not values.is_contiguous() or not values.is_cuda
-                or values.device.index != self.device):
-            raise ValueError("values: a contiguous [width * height, k] float32 tensor on the scene's device")
-        if (not hasattr(points, "data_ptr") or points.dtype != torch.float32 or tuple(points.shape) != (width * height, 8) or not points.is_contiguous()
-                or points.device != values.device):
-            raise ValueError("points: the contiguous [width * height, 8] float32 tensor lightmap_points returned, on the device of values")
-        if (not hasattr(texels, "data_ptr") or texels.dtype != torch.int32 or tuple(texels.shape) != (width * height, 4) or not texels.is_contiguous()
-                or texels.device != values.device):
-            raise ValueError("texels: the contiguous [width * height, 4] int32 tensor lightmap_points returned, on the device of values")
-        out = torch.empty_like(values)
-        torch.cuda.current_stream(values.device).synchronize()  # (the values may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_filter_dev(self.h, C.byref(cfg), C.c_void_p(points.data_ptr()), C.c_void_p(texels.data_ptr()),
-                                                   C.c_void_p(values.data_ptr()), C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        wh = width * height
+        args = [_Arg("values", values, "f32", (wh, "k")), _Arg("points", points, "f32", (wh, 8)), _Arg("texels", texels, "texel", (wh,))]
+        return self._call("sol_lightmap_filter", args, [_Out("out", "f32", (wh, "k"))],
+                          lambda p, d: (C.byref(cfg), p["points"], p["texels"], p["values"], p["out"]))["out"]
 
     # ---- irradiance moments and the variance-guided lightmap filter (EXTENSION; DESIGN.md 27) ----
     def irradiance_moments(self, points, samples=1, first_sample=0, seed=0, keys=None, key_base=0, first_draw=0, mode="cosine"):
@@ -904,11 +935,8 @@ class DeviceScene:
         array). moments_mean_variance gives the mean and the variance of the mean. points, keys, key_base, first_draw, the modes and the waits
         of the two routes are irradiance()'s."""
         cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
-        rows = self._radiance(self.lib.sol_irradiance_moments, self.lib.sol_irradiance_moments_dev, "points", "position xyz, tmin, normal xyz, tmax", points, keys,
-                              cfg, words=8)
-        if isinstance(rows, np.ndarray):
-            return rows.view(MOMENTS_DTYPE).reshape(-1)
-        return rows
+        rows = self._radiance("sol_irradiance_moments", "points", points, keys, cfg, words=8)
+        return rows.view(MOMENTS_DTYPE).reshape(-1) if isinstance(rows, np.ndarray) else rows
 
     def lightmap_filter_var(self, moments, points, texels, width, height, sigma_position, sigma_plane=None, iterations=4, normal_power_log2=5, sigma_value=4.0,
                             variance_floor=1e-12, return_variance=False):
@@ -929,37 +957,11 @@ class DeviceScene:
                                               normal_power_log2=int(normal_power_log2), sigma_position=float(sigma_position),
                                               sigma_plane=float(sigma_position if sigma_plane is None else sigma_plane), sigma_value=float(sigma_value),
                                               variance_floor=float(variance_floor))
-        if isinstance(moments, np.ndarray) or not hasattr(moments, "data_ptr"):  # the host route
-            m = np.ascontiguousarray(moments)
-            m = m.view(np.float32).reshape(-1, 8) if m.dtype == MOMENTS_DTYPE else np.ascontiguousarray(m, dtype=np.float32)
-            p = np.ascontiguousarray(points.cpu().numpy() if hasattr(points, "data_ptr") else points, dtype=np.float32)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            if m.shape != (wh, 8) or p.shape != (wh, 8) or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,):
-                raise ValueError("moments: width * height MOMENTS_DTYPE rows (or [width * height, 8] float32); points: [width * height, 8] float32 rows; "
-                                 "texels: width * height LIGHTMAP_TEXEL_DTYPE rows")
-            out = np.zeros((wh, 4), dtype=np.float32)
-            var = np.zeros((wh, 4), dtype=np.float32) if return_variance else None
-            self._chk(self.lib.sol_lightmap_filter_var(self.h, C.byref(cfg), p.ctypes.data, t.ctypes.data, m.ctypes.data, out.ctypes.data,
-                                                       None if var is None else var.ctypes.data))
-            return (out, var) if return_variance else out
-        import torch
-        if (moments.dtype != torch.float32 or tuple(moments.shape) != (wh, 8) or not moments.is_contiguous() or not moments.is_cuda
-                or moments.device.index != self.device):
-            raise ValueError("moments: the contiguous [width * height, 8] float32 tensor irradiance_moments returned, on the scene's device")
-        if (not hasattr(points, "data_ptr") or points.dtype != torch.float32 or tuple(points.shape) != (wh, 8) or not points.is_contiguous()
-                or points.device != moments.device):
-            raise ValueError("points: the contiguous [width * height, 8] float32 tensor lightmap_points returned, on the device of moments")
-        if (not hasattr(texels, "data_ptr") or texels.dtype != torch.int32 or tuple(texels.shape) != (wh, 4) or not texels.is_contiguous()
-                or texels.device != moments.device):
-            raise ValueError("texels: the contiguous [width * height, 4] int32 tensor lightmap_points returned, on the device of moments")
-        out = torch.empty((wh, 4), dtype=torch.float32, device=moments.device)
-        var = torch.empty((wh, 4), dtype=torch.float32, device=moments.device) if return_variance else None
-        torch.cuda.current_stream(moments.device).synchronize()  # (the moments may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_filter_var_dev(self.h, C.byref(cfg), C.c_void_p(points.data_ptr()), C.c_void_p(texels.data_ptr()),
-                                                       C.c_void_p(moments.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                       C.c_void_p(var.data_ptr()) if var is not None else None))
-        self.sync()
-        return (out, var) if return_variance else out
+        out = self._call("sol_lightmap_filter_var", [_Arg("moments", moments, "moments", (wh,)), _Arg("points", points, "f32", (wh, 8)),
+                                                     _Arg("texels", texels, "texel", (wh,))],
+                         [_Out("out", "f32", (wh, 4))] + ([_Out("variance", "f32", (wh, 4))] if return_variance else []),
+                         lambda p, d: (C.byref(cfg), p["points"], p["texels"], p["moments"], p["out"], p.get("variance")))
+        return (out["out"], out["variance"]) if return_variance else out["out"]
 
     # ---- adaptive irradiance gathers (EXTENSION) ----
     def irradiance_adaptive(self, points, max_samples, round=16, min_samples=32, threshold=0.05, floor=0.0, first_sample=0, seed=0, keys=None, key_base=0,
@@ -978,14 +980,8 @@ class DeviceScene:
         ad = _abi.SolGatherAdaptive(size=C.sizeof(_abi.SolGatherAdaptive), round=int(round), min_samples=int(min_samples), threshold=float(threshold),
                                     floor=float(floor))
         stats = _abi.SolGatherAdaptiveStats(size=C.sizeof(_abi.SolGatherAdaptiveStats))
-
-        def host_fn(h, p, k, n, c, out):
-            return self.lib.sol_irradiance_adaptive(h, p, k, n, c, C.byref(ad), out, C.byref(stats))
-
-        def dev_fn(h, p, k, n, c, out):
-            return self.lib.sol_irradiance_adaptive_dev(h, p, k, n, c, C.byref(ad), out, C.byref(stats))
-
-        rows = self._radiance(host_fn, dev_fn, "points", "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=8)
+        rows = self._radiance("sol_irradiance_adaptive", "points", points, keys, cfg, words=8,
+                              call=lambda p, k, n, c, out: (p, k, n, c, C.byref(ad), out, C.byref(stats)))
         if isinstance(rows, np.ndarray):
             rows = rows.view(MOMENTS_DTYPE).reshape(-1)
         if not return_stats:
@@ -999,24 +995,11 @@ class DeviceScene:
         channel with the count target_samples, a row with count 0 is copied. After an adaptive gather the filter's rows carry different counts, and
         lightmap_dilate averages sums: this goes between them. Host arrays go the host route and return an array, device tensors the device route
         and return a new tensor - or, in_place=True, `rows` itself, overwritten (a contiguous float32 array or tensor)."""
-        target = int(target_samples)
-        if isinstance(rows, np.ndarray) or not hasattr(rows, "data_ptr"):
-            a = np.ascontiguousarray(rows, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 4:
-                raise ValueError("rows: an [n, 4] float32 array of (r, g, b sums, the bits of the sample count)")
-            if in_place and a is not rows:
-                raise ValueError("rows: in_place needs the contiguous float32 array itself")
-            out = a if in_place else np.zeros_like(a)
-            self._chk(self.lib.sol_radiance_rescale(self.h, a.ctypes.data, a.shape[0], target, out.ctypes.data))
-            return out
-        import torch
-        if rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 4 or not rows.is_contiguous() or not rows.is_cuda or rows.device.index != self.device:
-            raise ValueError("rows: a contiguous [n, 4] float32 tensor on the scene's device")
-        out = rows if in_place else torch.empty_like(rows)
-        torch.cuda.current_stream(rows.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_radiance_rescale_dev(self.h, C.c_void_p(rows.data_ptr()), int(rows.shape[0]), target, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        if in_place and not self._on_device(rows) and np.ascontiguousarray(rows, dtype=np.float32) is not rows:
+            raise ValueError("rows: in_place needs the contiguous float32 array itself")
+        out = self._call("sol_radiance_rescale", [_Arg("rows", rows, "f32", ("n", 4))], [] if in_place else [_Out("out", "f32", ("n", 4))],
+                         lambda p, d: (p["rows"], d["n"], int(target_samples), p.get("out", p["rows"])))
+        return rows if in_place else out["out"]
 
     # ---- lightmap lookups (EXTENSION; DESIGN.md 29) ----
     def lightmap_coords(self, hits, triangle_of_dfs):
@@ -1025,25 +1008,9 @@ class DeviceScene:
         goes the host route and returns a LIGHTMAP_TEXEL_DTYPE array; the [n, 8] int32 device tensor closest_hits returned goes through
         sol_lightmap_coords_dev and returns an [n, 4] int32 device tensor (lightmap_texels_to_numpy views it). A miss, a sphere, a quad, and a
         triangle the table does not list answer (SOL_TEXEL_NONE, 0, 0, 0)."""
-        table = np.ascontiguousarray(triangle_of_dfs.cpu().numpy() if hasattr(triangle_of_dfs, "data_ptr") else triangle_of_dfs).astype(np.uint32, copy=False).reshape(-1)
-        if isinstance(hits, np.ndarray) or not hasattr(hits, "data_ptr"):  # the host route
-            h = np.ascontiguousarray(hits)
-            if h.dtype != self.RAY_HIT_DTYPE or h.ndim != 1:
-                raise ValueError("hits: a RAY_HIT_DTYPE array, what closest_hits returned")
-            out = np.zeros(h.shape[0], dtype=LIGHTMAP_TEXEL_DTYPE)
-            self._chk(self.lib.sol_lightmap_coords(self.h, h.ctypes.data, h.shape[0], table.ctypes.data if len(table) else None, len(table), out.ctypes.data))
-            return out
-        import torch
-        if hits.dtype != torch.int32 or hits.dim() != 2 or hits.shape[1] != 8 or not hits.is_contiguous() or not hits.is_cuda or hits.device.index != self.device:
-            raise ValueError("hits: the contiguous [n, 8] int32 tensor closest_hits returned, on the scene's device")
-        d_table = (triangle_of_dfs if hasattr(triangle_of_dfs, "data_ptr") and triangle_of_dfs.is_cuda and triangle_of_dfs.dtype == torch.int32
-                   and triangle_of_dfs.is_contiguous() else torch.from_numpy(table.view(np.int32)).to(hits.device))
-        out = torch.empty((int(hits.shape[0]), 4), dtype=torch.int32, device=hits.device)
-        torch.cuda.current_stream(hits.device).synchronize()  # (the hits and the table may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_coords_dev(self.h, C.c_void_p(hits.data_ptr()), int(hits.shape[0]), C.c_void_p(d_table.data_ptr()) if len(table) else None,
-                                                   len(table), C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        table = _Arg("triangle_of_dfs", triangle_of_dfs, "u32", ("entries",), null_if_empty=True, flat=True, upload="any")  # (a host table is copied over)
+        return self._call("sol_lightmap_coords", [_Arg("hits", hits, "hit", ("n",)), table], [_Out("out", "texel", ("n",))],
+                          lambda p, d: (p["hits"], d["n"], p["triangle_of_dfs"], d["entries"], p["out"]))["out"]
 
     def lightmap_sample(self, values, coords, uvs, texels, width, height, channels=3, pass_of=None, nearest=False, chart_radius=None, vertices=None, points=None):
         """sol_lightmap_sample: the baked atlas `values` (`width * height` rows whose leading `channels` 32-bit words are floats: what
@@ -1055,59 +1022,44 @@ class DeviceScene:
         bits of the number of taps that contributed (0: nothing was found, the row is zero). Host arrays go the host route, device tensors the
         device route, decided by `values`."""
         width, height, channels = int(width), int(height), int(channels)
-        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
-        cfg = _abi.SolLightmapSampleConfig(size=C.sizeof(_abi.SolLightmapSampleConfig), width=width, height=height, channels=channels, stride_bytes=4 * k,
-                                           flags=_abi.SOL_LIGHTMAP_SAMPLE_NEAREST if nearest else 0,
+        cfg = _abi.SolLightmapSampleConfig(size=C.sizeof(_abi.SolLightmapSampleConfig), width=width, height=height, channels=channels,
+                                           stride_bytes=self._stride(values), flags=_abi.SOL_LIGHTMAP_SAMPLE_NEAREST if nearest else 0,
                                            chart_radius=float("inf") if chart_radius is None else float(chart_radius))
         out_words = channels + 1 if 1 <= channels <= 32 else 1
-        wh = width * height
-        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            host = self._host_array
-            v, u, vx, p = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
-            po = host(pass_of, np.uint8)
-            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
-                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or (vx is not None and vx.shape != (u.shape[0], 3, 3))
-                    or (p is not None and p.shape != (wh, 8))):
-                raise ValueError("values: [width * height, k] float32 rows; texels, coords: LIGHTMAP_TEXEL_DTYPE rows; uvs: [n, 3, 2]; pass_of: width * height "
-                                 "bytes; vertices: [n, 3, 3]; points: [width * height, 8]")
-            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
-            self._chk(self.lib.sol_lightmap_sample(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
-                                                   None if po is None else po.ctypes.data, v.ctypes.data, None if vx is None else vx.ctypes.data,
-                                                   None if p is None else p.ctypes.data, c.ctypes.data, c.shape[0], out.ctypes.data))
-            return out
-        import torch
-        dev = self._device_pointer
-        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
-        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
-                dev("values", values, torch.float32, (wh, None)), dev("vertices", vertices, torch.float32, (n_tri, 3, 3)),
-                dev("points", points, torch.float32, (wh, 8)), dev("coords", coords, torch.int32, (None, 4)), int(coords.shape[0]))
-        out = torch.empty((int(coords.shape[0]), out_words), dtype=torch.float32, device=values.device)
-        torch.cuda.current_stream(values.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_sample_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        args = self._atlas_args(uvs, texels, pass_of, values, width, height) + self._guard_args(vertices, points, coords, width * height)
+        return self._call("sol_lightmap_sample", args, [_Out("out", "f32", ("n", out_words))],
+                          lambda p, d: (C.byref(cfg), p["uvs"], d["n_triangles"], p["texels"], p["pass_of"], p["values"], p["vertices"], p["points"], p["coords"],
+                                        d["n"], p["out"]), device=self._on_device(values))["out"]
 
     def lightmap_view(self, values, uvs, texels, width, height, triangle_of_dfs, x0, y0, x1, y1, sample=0, seed=0, **sample_args):
         """The bake seen from the scene's camera: camera_rays -> closest_hits -> lightmap_coords -> lightmap_sample over the pixels [x0, x1) x
         [y0, y1), all on device memory (values, uvs, texels and what sample_args names are device tensors). Returns an [h, w, channels + 1]
         float32 device tensor; a pixel that misses, or hits something without lightmap, is zero with count 0."""
+        _, _, coords, h, w = self._view_coords(triangle_of_dfs, x0, y0, x1, y1, sample, seed)
+        return self.lightmap_sample(values, coords, uvs, texels, width, height, **sample_args).reshape(h, w, -1)
+
+    def _view_coords(self, triangle_of_dfs, x0, y0, x1, y1, sample, seed):
+        """The first steps of every view, camera_rays -> closest_hits -> lightmap_coords over the pixels [x0, x1) x [y0, y1): (rays [h * w, 8], hits,
+        coords, h, w), device tensors."""
         rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
         h, w = int(rays.shape[0]), int(rays.shape[1])
-        coords = self.lightmap_coords(self.closest_hits(rays.reshape(-1, 8)), triangle_of_dfs)
-        out = self.lightmap_sample(values, coords, uvs, texels, width, height, **sample_args)
-        return out.reshape(h, w, -1)
+        rays = rays.reshape(-1, 8)
+        hits = self.closest_hits(rays)
+        return rays, hits, self.lightmap_coords(hits, triangle_of_dfs), h, w
 
     # ---- directional lightmaps (EXTENSION; DESIGN.md 30) ----
-    def _device_pointer(self, name, x, dtype, shape):
-        """The address of a device tensor argument (None: none), after its dtype, layout, device and shape (None: any extent) are checked."""
-        if x is None:
-            return None
-        if (not hasattr(x, "data_ptr") or x.dtype != dtype or not x.is_contiguous() or not x.is_cuda or x.device.index != self.device
-                or len(shape) != x.dim() or any(s is not None and s != d for s, d in zip(shape, x.shape))):
-            raise ValueError(f"{name}: a contiguous {dtype} tensor of shape {list(shape)} on the scene's device")
-        return C.c_void_p(x.data_ptr())
+    @staticmethod
+    def _atlas_args(uvs, texels, pass_of, values, width, height):
+        """What every lookup takes of the atlas: the lightmap UVs (they bind n_triangles), lightmap_points' texels, lightmap_dilate's plane or None, and
+        the atlas itself (it binds k, the words of a row)."""
+        return [_Arg("uvs", uvs, "f32", ("n_triangles", 3, 2), null_if_empty=True), _Arg("texels", texels, "texel", (width * height,)),
+                _Arg("pass_of", pass_of, "u8", (height, width), optional=True, flat=True), _Arg("values", values, "f32", (width * height, "k"))]
+
+    @staticmethod
+    def _guard_args(vertices, points, coords, wh):
+        """The chart guard's two optional arrays and the surface rows (they bind n) of a lookup."""
+        return [_Arg("vertices", vertices, "f32", ("n_triangles", 3, 3), optional=True), _Arg("points", points, "f32", (wh, 8), optional=True),
+                _Arg("coords", coords, "texel", ("n",))]
 
     def lightmap_sh(self, values, coords, normals, uvs, texels, width, height, scale=1.0, pass_of=None, nearest=False, chart_radius=None, vertices=None,
                     points=None, clamp=False, coefficients=False):
@@ -1120,69 +1072,25 @@ class DeviceScene:
         (channels=27) answers, from the eight-lanes-to-a-row kernel. Host arrays go the host route, device tensors the device route, decided by
         `values`."""
         width, height = int(width), int(height)
-        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
         flags = ((_abi.SOL_LIGHTMAP_SH_NEAREST if nearest else 0) | (_abi.SOL_LIGHTMAP_SH_COEFFICIENTS if coefficients else 0)
                  | (_abi.SOL_LIGHTMAP_SH_CLAMP if clamp else 0))
-        cfg = _abi.SolLightmapShConfig(size=C.sizeof(_abi.SolLightmapShConfig), width=width, height=height, stride_bytes=4 * k, flags=flags,
+        cfg = _abi.SolLightmapShConfig(size=C.sizeof(_abi.SolLightmapShConfig), width=width, height=height, stride_bytes=self._stride(values), flags=flags,
                                        chart_radius=float("inf") if chart_radius is None else float(chart_radius), scale=float(scale))
-        out_words = 28 if coefficients else 4
-        wh = width * height
-        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            host = self._host_array
-            v, u, vx, p, nr = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32), host(normals, np.float32)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
-            po = host(pass_of, np.uint8)
-            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
-                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or (vx is not None and vx.shape != (u.shape[0], 3, 3))
-                    or (p is not None and p.shape != (wh, 8)) or (nr is not None and nr.shape != (c.shape[0], 4))):
-                raise ValueError("values: [width * height, k] float32 rows; texels, coords: LIGHTMAP_TEXEL_DTYPE rows; normals: [n, 4]; uvs: [n, 3, 2]; "
-                                 "pass_of: width * height bytes; vertices: [n, 3, 3]; points: [width * height, 8]")
-            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
-            self._chk(self.lib.sol_lightmap_sh(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
-                                               None if po is None else po.ctypes.data, v.ctypes.data, None if vx is None else vx.ctypes.data,
-                                               None if p is None else p.ctypes.data, c.ctypes.data, None if nr is None else nr.ctypes.data, c.shape[0],
-                                               out.ctypes.data))
-            return out
-        import torch
-        dev = self._device_pointer
-        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
-        n = int(coords.shape[0])
-        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
-                dev("values", values, torch.float32, (wh, None)), dev("vertices", vertices, torch.float32, (n_tri, 3, 3)),
-                dev("points", points, torch.float32, (wh, 8)), dev("coords", coords, torch.int32, (None, 4)), dev("normals", normals, torch.float32, (n, 4)), n)
-        out = torch.empty((n, out_words), dtype=torch.float32, device=values.device)
-        torch.cuda.current_stream(values.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_sh_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        args = (self._atlas_args(uvs, texels, pass_of, values, width, height) + self._guard_args(vertices, points, coords, width * height)
+                + [_Arg("normals", normals, "f32", ("n", 4), optional=True)])
+        return self._call("sol_lightmap_sh", args, [_Out("out", "f32", ("n", 28 if coefficients else 4))],
+                          lambda p, d: (C.byref(cfg), p["uvs"], d["n_triangles"], p["texels"], p["pass_of"], p["values"], p["vertices"], p["points"], p["coords"],
+                                        p["normals"], d["n"], p["out"]), device=self._on_device(values))["out"]
 
     def lightmap_normals(self, coords, vertices, normals=None):
         """sol_lightmap_normals: the unit normals of the surface rows `coords` by lightmap_points' rule - the triangle's geometric normal, or with
         per-vertex `normals` [n_triangles, 3, 3] their interpolation where it has a length - as [n, 4] float32 rows (nx, ny, nz, 0): what
         lightmap_sh takes. An invalid row, a triangle with a word that is not finite and a vector without length answer zeros. A
         LIGHTMAP_TEXEL_DTYPE array goes the host route, an [n, 4] int32 device tensor the device route."""
-        if isinstance(coords, np.ndarray) or not hasattr(coords, "data_ptr"):  # the host route
-            c = np.ascontiguousarray(coords)
-            v = np.ascontiguousarray(vertices.cpu().numpy() if hasattr(vertices, "data_ptr") else vertices, dtype=np.float32)
-            nr = None if normals is None else np.ascontiguousarray(normals.cpu().numpy() if hasattr(normals, "data_ptr") else normals, dtype=np.float32)
-            if c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1 or v.ndim != 3 or v.shape[1:] != (3, 3) or (nr is not None and nr.shape != v.shape):
-                raise ValueError("coords: LIGHTMAP_TEXEL_DTYPE rows; vertices, normals: [n_triangles, 3, 3]")
-            out = np.zeros((c.shape[0], 4), dtype=np.float32)
-            self._chk(self.lib.sol_lightmap_normals(self.h, c.ctypes.data, c.shape[0], v.ctypes.data if len(v) else None,
-                                                    None if nr is None or not len(v) else nr.ctypes.data, v.shape[0], out.ctypes.data))
-            return out
-        import torch
-        n_tri = int(vertices.shape[0]) if hasattr(vertices, "shape") and len(vertices.shape) == 3 else 0
-        dev = self._device_pointer
-        d_coords, d_vertices = dev("coords", coords, torch.int32, (None, 4)), dev("vertices", vertices, torch.float32, (None, 3, 3))
-        d_normals = dev("normals", normals, torch.float32, (n_tri, 3, 3))
-        out = torch.empty((int(coords.shape[0]), 4), dtype=torch.float32, device=coords.device)
-        torch.cuda.current_stream(coords.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_normals_dev(self.h, d_coords, int(coords.shape[0]), d_vertices if n_tri else None, d_normals if n_tri else None, n_tri,
-                                                    C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        return self._call("sol_lightmap_normals", [_Arg("coords", coords, "texel", ("n",)), _Arg("vertices", vertices, "f32", ("n_triangles", 3, 3), null_if_empty=True),
+                                                   _Arg("normals", normals, "f32", ("n_triangles", 3, 3), optional=True, null_if_empty=True)],
+                          [_Out("out", "f32", ("n", 4))],
+                          lambda p, d: (p["coords"], d["n"], p["vertices"], p["normals"], d["n_triangles"], p["out"]))["out"]
 
     def lightmap_view_sh(self, values, uvs, texels, width, height, triangle_of_dfs, vertices, x0, y0, x1, y1, scale, sample=0, seed=0, vertex_normals=None,
                          perturb=None, **sh_args):
@@ -1191,9 +1099,7 @@ class DeviceScene:
         `perturb`, an [h, w, 4] float32 device tensor of the caller's own normals, replaces them - the normal-mapped case. Returns an [h, w, 4]
         float32 device tensor (E_r, E_g, E_b, count), or [h, w, 28] with coefficients=True; a pixel that misses, or hits something without
         lightmap, is zero with count 0."""
-        rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
-        h, w = int(rays.shape[0]), int(rays.shape[1])
-        coords = self.lightmap_coords(self.closest_hits(rays.reshape(-1, 8)), triangle_of_dfs)
+        _, _, coords, h, w = self._view_coords(triangle_of_dfs, x0, y0, x1, y1, sample, seed)
         if sh_args.get("coefficients"):
             normals = None
         elif perturb is not None:
@@ -1216,27 +1122,11 @@ class DeviceScene:
         width, height, channels = int(width), int(height), int(channels)
         lay = lightmap_mip_layout(width, height, levels)
         wh, rows = width * height, lay["rows"]
-        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            v = np.ascontiguousarray(values, dtype=np.float32)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            po = None if pass_of is None else np.ascontiguousarray(pass_of.cpu().numpy() if hasattr(pass_of, "data_ptr") else pass_of, dtype=np.uint8)
-            if v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or (po is not None and po.size != wh):
-                raise ValueError("values: [width * height, k] float32 rows; texels: width * height LIGHTMAP_TEXEL_DTYPE rows; pass_of: width * height bytes")
-            mips, cover = np.zeros((rows, v.shape[1]), dtype=np.float32), np.zeros(rows, dtype=np.uint8)
-            self._chk(self.lib.sol_lightmap_mips(self.h, t.ctypes.data, None if po is None else po.ctypes.data, width, height, v.ctypes.data, channels,
-                                                 v.shape[1] * 4, lay["levels"], mips.ctypes.data if rows else None, cover.ctypes.data if rows else None))
-            return mips, cover
-        import torch
-        dev = self._device_pointer
-        d_values, d_texels = dev("values", values, torch.float32, (wh, None)), dev("texels", texels, torch.int32, (wh, 4))
-        d_pass = dev("pass_of", pass_of, torch.uint8, (height, width))
-        mips = torch.empty((rows, int(values.shape[1])), dtype=torch.float32, device=values.device)
-        cover = torch.empty((rows,), dtype=torch.uint8, device=values.device)
-        torch.cuda.current_stream(values.device).synchronize()  # (the values may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_mips_dev(self.h, d_texels, d_pass, width, height, d_values, channels, int(values.shape[1]) * 4, lay["levels"],
-                                                 C.c_void_p(mips.data_ptr()) if rows else None, C.c_void_p(cover.data_ptr()) if rows else None))
-        self.sync()
-        return mips, cover
+        out = self._call("sol_lightmap_mips", [_Arg("values", values, "f32", (wh, "k")), _Arg("texels", texels, "texel", (wh,)),
+                                               _Arg("pass_of", pass_of, "u8", (height, width), optional=True, flat=True)],
+                         [_Out("mips", "f32", (rows, "k"), null_if_empty=True), _Out("cover", "u8", (rows,), null_if_empty=True)],
+                         lambda p, d: (p["texels"], p["pass_of"], width, height, p["values"], channels, d["k"] * 4, lay["levels"], p["mips"], p["cover"]))
+        return out["mips"], out["cover"]
 
     def lightmap_sample_lod(self, values, mips, cover, lods, coords, uvs, texels, width, height, channels=3, pass_of=None, levels=None, chart_radius=None,
                             vertices=None, points=None):
@@ -1248,43 +1138,16 @@ class DeviceScene:
         `values`."""
         width, height, channels = int(width), int(height), int(channels)
         lay = lightmap_mip_layout(width, height, levels)
-        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
-        cfg = _abi.SolLightmapLodConfig(size=C.sizeof(_abi.SolLightmapLodConfig), width=width, height=height, channels=channels, stride_bytes=4 * k, flags=0,
-                                        chart_radius=float("inf") if chart_radius is None else float(chart_radius), levels=lay["levels"])
+        cfg = _abi.SolLightmapLodConfig(size=C.sizeof(_abi.SolLightmapLodConfig), width=width, height=height, channels=channels, stride_bytes=self._stride(values),
+                                        flags=0, chart_radius=float("inf") if chart_radius is None else float(chart_radius), levels=lay["levels"])
         out_words = channels + 1 if 1 <= channels <= 32 else 1
-        wh, rows = width * height, lay["rows"]
-        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            host = self._host_array
-            v, u, vx, p = host(values, np.float32), host(uvs, np.float32), host(vertices, np.float32), host(points, np.float32)
-            m, cv, ld, po = host(mips, np.float32), host(cover, np.uint8), host(lods, np.float32), host(pass_of, np.uint8)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
-            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
-                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or (vx is not None and vx.shape != (u.shape[0], 3, 3))
-                    or (p is not None and p.shape != (wh, 8)) or ld.shape != (c.shape[0],)
-                    or (rows and (m is None or cv is None or m.shape != (rows, v.shape[1]) or cv.shape != (rows,)))):
-                raise ValueError("values: [width * height, k] float32 rows; mips: [rows, k] and cover: [rows] as lightmap_mip_layout says; lods: [n]; texels, "
-                                 "coords: LIGHTMAP_TEXEL_DTYPE rows; uvs: [n, 3, 2]; pass_of: width * height bytes; vertices: [n, 3, 3]; points: "
-                                 "[width * height, 8]")
-            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
-            self._chk(self.lib.sol_lightmap_sample_lod(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
-                                                       None if po is None else po.ctypes.data, v.ctypes.data, m.ctypes.data if rows else None,
-                                                       cv.ctypes.data if rows else None, None if vx is None else vx.ctypes.data,
-                                                       None if p is None else p.ctypes.data, c.ctypes.data, ld.ctypes.data, c.shape[0], out.ctypes.data))
-            return out
-        import torch
-        dev = self._device_pointer
-        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
-        n = int(coords.shape[0])
-        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
-                dev("values", values, torch.float32, (wh, None)), dev("mips", mips, torch.float32, (rows, k)) if rows else None,
-                dev("cover", cover, torch.uint8, (rows,)) if rows else None, dev("vertices", vertices, torch.float32, (n_tri, 3, 3)),
-                dev("points", points, torch.float32, (wh, 8)), dev("coords", coords, torch.int32, (None, 4)), dev("lods", lods, torch.float32, (n,)), n)
-        out = torch.empty((n, out_words), dtype=torch.float32, device=values.device)
-        torch.cuda.current_stream(values.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_sample_lod_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        rows = lay["rows"]  # (a chain of level 0 alone has no rows: mips and cover are not looked at and go as null pointers)
+        args = (self._atlas_args(uvs, texels, pass_of, values, width, height)
+                + [_Arg("mips", mips if rows else None, "f32", (rows, "k"), optional=not rows), _Arg("cover", cover if rows else None, "u8", (rows,), optional=not rows)]
+                + self._guard_args(vertices, points, coords, width * height) + [_Arg("lods", lods, "f32", ("n",))])
+        return self._call("sol_lightmap_sample_lod", args, [_Out("out", "f32", ("n", out_words))],
+                          lambda p, d: (C.byref(cfg), p["uvs"], d["n_triangles"], p["texels"], p["pass_of"], p["values"], p["mips"], p["cover"], p["vertices"],
+                                        p["points"], p["coords"], p["lods"], d["n"], p["out"]), device=self._on_device(values))["out"]
 
     def lightmap_lod(self, rays, hits, coords, vertices, uvs, width, height, spread, bias=0.0):
         """sol_lightmap_lod: the level of detail of each hit - half the piecewise-linear log2 of the squared number of texels under a pixel along
@@ -1292,32 +1155,11 @@ class DeviceScene:
         together row by row; vertices [n_triangles, 3, 3] and uvs [n_triangles, 3, 2] are the lightmap mesh; spread: the angle in radians between
         the rays of neighbouring pixels (pixel_spread). A miss, an invalid row and a degenerate triangle answer 0. Returns [n] float32: what
         lightmap_sample_lod takes. Host arrays go the host route, device tensors the device route, decided by `rays`."""
-        width, height = int(width), int(height)
-        if isinstance(rays, np.ndarray) or not hasattr(rays, "data_ptr"):  # the host route
-            r = np.ascontiguousarray(rays, dtype=np.float32)
-            h = np.ascontiguousarray(self.hits_to_numpy(hits) if hasattr(hits, "data_ptr") else hits)
-            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
-            v = np.ascontiguousarray(vertices.cpu().numpy() if hasattr(vertices, "data_ptr") else vertices, dtype=np.float32)
-            u = np.ascontiguousarray(uvs.cpu().numpy() if hasattr(uvs, "data_ptr") else uvs, dtype=np.float32)
-            if (r.ndim != 2 or r.shape[1] != 8 or h.dtype != self.RAY_HIT_DTYPE or h.shape != (r.shape[0],) or c.dtype != LIGHTMAP_TEXEL_DTYPE
-                    or c.shape != (r.shape[0],) or v.ndim != 3 or v.shape[1:] != (3, 3) or u.shape != (v.shape[0], 3, 2)):
-                raise ValueError("rays: [n, 8] float32; hits: n RAY_HIT_DTYPE rows; coords: n LIGHTMAP_TEXEL_DTYPE rows; vertices: [t, 3, 3]; uvs: [t, 3, 2]")
-            out = np.zeros(r.shape[0], dtype=np.float32)
-            self._chk(self.lib.sol_lightmap_lod(self.h, r.ctypes.data, h.ctypes.data, c.ctypes.data, r.shape[0], v.ctypes.data if len(v) else None,
-                                                u.ctypes.data if len(v) else None, v.shape[0], width, height, float(spread), float(bias), out.ctypes.data))
-            return out
-        import torch
-        dev = self._device_pointer
-        n = int(rays.shape[0])
-        n_tri = int(vertices.shape[0]) if hasattr(vertices, "shape") and len(vertices.shape) == 3 else 0
-        d_rays, d_hits, d_coords = dev("rays", rays, torch.float32, (n, 8)), dev("hits", hits, torch.int32, (n, 8)), dev("coords", coords, torch.int32, (n, 4))
-        d_vertices, d_uvs = dev("vertices", vertices, torch.float32, (n_tri, 3, 3)), dev("uvs", uvs, torch.float32, (n_tri, 3, 2))
-        out = torch.empty((n,), dtype=torch.float32, device=rays.device)
-        torch.cuda.current_stream(rays.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_lod_dev(self.h, d_rays, d_hits, d_coords, n, d_vertices if n_tri else None, d_uvs if n_tri else None, n_tri, width, height,
-                                                float(spread), float(bias), C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        args = [_Arg("rays", rays, "f32", ("n", 8)), _Arg("hits", hits, "hit", ("n",)), _Arg("coords", coords, "texel", ("n",)),
+                _Arg("vertices", vertices, "f32", ("n_triangles", 3, 3), null_if_empty=True), _Arg("uvs", uvs, "f32", ("n_triangles", 3, 2), null_if_empty=True)]
+        return self._call("sol_lightmap_lod", args, [_Out("out", "f32", ("n",))],
+                          lambda p, d: (p["rays"], p["hits"], p["coords"], d["n"], p["vertices"], p["uvs"], d["n_triangles"], int(width), int(height), float(spread),
+                                        float(bias), p["out"]))["out"]
 
     def lightmap_view_lod(self, values, mips, cover, uvs, texels, width, height, triangle_of_dfs, vertices, x0, y0, x1, y1, spread, bias=0.0, sample=0, seed=0,
                           **sample_args):
@@ -1325,11 +1167,7 @@ class DeviceScene:
         lightmap_sample_lod over the pixels [x0, x1) x [y0, y1), all on device memory. spread: pixel_spread of the camera; sample_args: what
         lightmap_sample_lod takes by name (channels, pass_of, levels, chart_radius, points; `vertices` serves the guard too). Returns an
         [h, w, channels + 1] float32 device tensor; a pixel that misses, or hits something without lightmap, is zero with count 0."""
-        rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
-        h, w = int(rays.shape[0]), int(rays.shape[1])
-        rays = rays.reshape(-1, 8)
-        hits = self.closest_hits(rays)
-        coords = self.lightmap_coords(hits, triangle_of_dfs)
+        rays, hits, coords, h, w = self._view_coords(triangle_of_dfs, x0, y0, x1, y1, sample, seed)
         lods = self.lightmap_lod(rays, hits, coords, vertices, uvs, width, height, spread, bias)
         if sample_args.get("points") is not None:
             sample_args = {**sample_args, "vertices": vertices}
@@ -1337,43 +1175,16 @@ class DeviceScene:
         return out.reshape(h, w, -1)
 
     # ---- lightmap charts (EXTENSION) ----
-    @staticmethod
-    def _host_array(x, dtype=None):
-        return None if x is None else np.ascontiguousarray(x.cpu().numpy() if hasattr(x, "data_ptr") else x, dtype=dtype)
-
-    @classmethod
-    def _host_words(cls, name, x):
-        """A host array (or device tensor) of chart labels as contiguous uint32 words: uint32 as it is, int32 reinterpreted; anything else is refused."""
-        a = cls._host_array(x)
-        if a.dtype not in (np.dtype(np.uint32), np.dtype(np.int32)):
-            raise ValueError(f"{name}: 32-bit words (a uint32 or int32 array, or an int32 tensor), not {a.dtype}")
-        return a.view(np.uint32).reshape(-1)
-
     def lightmap_charts(self, uvs, vertices=None):
         """sol_lightmap_charts: the UV islands of a mesh. uvs [n, 3, 2] float32 and, optionally, vertices [n, 3, 3]: two triangles are connected
         when they have an edge in common - the unordered pair of its end points, (u, v) or with vertices (u, v, x, y, z), equal as numbers. Returns
         (chart_of_triangle [n] - dense ids in mesh order, CHART_NONE for a triangle with a word that is not finite -, n_charts). Host arrays go
         the host route and return a uint32 array; device tensors the device route and return an int32 tensor holding the same words."""
-        if isinstance(uvs, np.ndarray) or not hasattr(uvs, "data_ptr"):  # the host route
-            u, vx = self._host_array(uvs, np.float32), self._host_array(vertices, np.float32)
-            if u.ndim != 3 or u.shape[1:] != (3, 2) or (vx is not None and vx.shape != (u.shape[0], 3, 3)):
-                raise ValueError("uvs: [n, 3, 2] float32; vertices: [n, 3, 3] float32 or None")
-            n = u.shape[0]
-            chart_of, n_charts = np.zeros(n, dtype=np.uint32), C.c_uint32(0)
-            self._chk(self.lib.sol_lightmap_charts(self.h, u.ctypes.data if n else None, vx.ctypes.data if (vx is not None and n) else None, n,
-                                                   chart_of.ctypes.data if n else None, C.addressof(n_charts)))
-            return chart_of, int(n_charts.value)
-        import torch
-        d_uvs = self._device_pointer("uvs", uvs, torch.float32, (None, 3, 2))
-        n = int(uvs.shape[0])
-        d_vertices = self._device_pointer("vertices", vertices, torch.float32, (n, 3, 3))
-        chart_of = torch.empty((n,), dtype=torch.int32, device=uvs.device)
-        n_charts = torch.zeros((1,), dtype=torch.int32, device=uvs.device)
-        torch.cuda.current_stream(uvs.device).synchronize()  # (the arrays may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_lightmap_charts_dev(self.h, d_uvs if n else None, d_vertices if n else None, n, C.c_void_p(chart_of.data_ptr()) if n else None,
-                                                   C.c_void_p(n_charts.data_ptr())))
-        self.sync()
-        return chart_of, int(n_charts.item())
+        out = self._call("sol_lightmap_charts", [_Arg("uvs", uvs, "f32", ("n", 3, 2), null_if_empty=True),
+                                                 _Arg("vertices", vertices, "f32", ("n", 3, 3), optional=True, null_if_empty=True)],
+                         [_Out("chart_of", "u32", ("n",), null_if_empty=True), _Out("n_charts", "u32", (1,), zero=True)],
+                         lambda p, d: (p["uvs"], p["vertices"], d["n"], p["chart_of"], p["n_charts"]))
+        return out["chart_of"], int(out["n_charts"][0])
 
     def lightmap_dilate_charts(self, values, texels, chart_of_triangle, width, height, passes=1, channels=3):
         """sol_lightmap_dilate_charts: lightmap_dilate that never averages across charts. chart_of_triangle: what lightmap_charts returned. A
@@ -1383,30 +1194,13 @@ class DeviceScene:
         route, decided by `values`."""
         width, height = int(width), int(height)
         wh = width * height
-        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            v = np.ascontiguousarray(values, dtype=np.float32)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            ch = self._host_words("chart_of_triangle", chart_of_triangle) if chart_of_triangle is not None else np.zeros(0, dtype=np.uint32)
-            if v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,):
-                raise ValueError("values: [width * height, k] float32 rows; texels: width * height LIGHTMAP_TEXEL_DTYPE rows")
-            out, pass_of, plane = np.zeros_like(v), np.zeros((height, width), dtype=np.uint8), np.zeros((height, width), dtype=np.uint32)
-            self._chk(self.lib.sol_lightmap_dilate_charts(self.h, t.ctypes.data, width, height, v.ctypes.data, int(channels), v.shape[1] * 4, int(passes),
-                                                          ch.ctypes.data if len(ch) else None, len(ch), out.ctypes.data, pass_of.ctypes.data, plane.ctypes.data))
-            return out, pass_of, plane
-        import torch
-        d_values = self._device_pointer("values", values, torch.float32, (wh, None))
-        d_texels = self._device_pointer("texels", texels, torch.int32, (wh, 4))
-        d_chart = self._device_pointer("chart_of_triangle", chart_of_triangle, torch.int32, (None,))
-        n_tri = int(chart_of_triangle.shape[0])
-        out = torch.empty_like(values)
-        pass_of = torch.empty((height, width), dtype=torch.uint8, device=values.device)
-        plane = torch.empty((height, width), dtype=torch.int32, device=values.device)
-        torch.cuda.current_stream(values.device).synchronize()
-        self._chk(self.lib.sol_lightmap_dilate_charts_dev(self.h, d_texels, width, height, d_values, int(channels), int(values.shape[1]) * 4, int(passes),
-                                                          d_chart if n_tri else None, n_tri, C.c_void_p(out.data_ptr()), C.c_void_p(pass_of.data_ptr()),
-                                                          C.c_void_p(plane.data_ptr())))
-        self.sync()
-        return out, pass_of, plane
+        out = self._call("sol_lightmap_dilate_charts", [_Arg("values", values, "f32", (wh, "k")), _Arg("texels", texels, "texel", (wh,)),
+                                                        _Arg("chart_of_triangle", chart_of_triangle, "words", ("n_triangles",), optional=True, null_if_empty=True,
+                                                             flat=True)],
+                         [_Out("out", "f32", (wh, "k")), _Out("pass_of", "u8", (height, width)), _Out("chart_plane", "words", (height, width))],
+                         lambda p, d: (p["texels"], width, height, p["values"], int(channels), d["k"] * 4, int(passes), p["chart_of_triangle"],
+                                       d.get("n_triangles", 0), p["out"], p["pass_of"], p["chart_plane"]))
+        return out["out"], out["pass_of"], out["chart_plane"]
 
     def lightmap_sample_charts(self, values, coords, uvs, texels, chart_of_triangle, chart_plane, width, height, channels=3, pass_of=None, nearest=False):
         """sol_lightmap_sample_charts: lightmap_sample guarded by chart id. chart_of_triangle: what lightmap_charts returned; chart_plane (and
@@ -1414,72 +1208,35 @@ class DeviceScene:
         the row's triangle - a dilated tap of a neighbouring chart included; a row whose triangle has no chart answers zeros. Returns
         [n, channels + 1] float32 rows as lightmap_sample does. Host arrays go the host route, device tensors the device route, decided by `values`."""
         width, height, channels = int(width), int(height), int(channels)
-        k = int(values.shape[1]) if getattr(values, "ndim", 0) == 2 else 0
-        cfg = _abi.SolLightmapSampleConfig(size=C.sizeof(_abi.SolLightmapSampleConfig), width=width, height=height, channels=channels, stride_bytes=4 * k,
-                                           flags=_abi.SOL_LIGHTMAP_SAMPLE_NEAREST if nearest else 0, chart_radius=float("inf"))
+        cfg = _abi.SolLightmapSampleConfig(size=C.sizeof(_abi.SolLightmapSampleConfig), width=width, height=height, channels=channels,
+                                           stride_bytes=self._stride(values), flags=_abi.SOL_LIGHTMAP_SAMPLE_NEAREST if nearest else 0, chart_radius=float("inf"))
         out_words = channels + 1 if 1 <= channels <= 32 else 1
-        wh = width * height
-        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):  # the host route
-            v, u, po = self._host_array(values, np.float32), self._host_array(uvs, np.float32), self._host_array(pass_of, np.uint8)
-            t = np.ascontiguousarray(lightmap_texels_to_numpy(texels) if hasattr(texels, "data_ptr") else texels)
-            c = np.ascontiguousarray(lightmap_texels_to_numpy(coords) if hasattr(coords, "data_ptr") else coords)
-            ch, pl = self._host_words("chart_of_triangle", chart_of_triangle), self._host_words("chart_plane", chart_plane)
-            if (v.ndim != 2 or v.shape[0] != wh or t.dtype != LIGHTMAP_TEXEL_DTYPE or t.shape != (wh,) or c.dtype != LIGHTMAP_TEXEL_DTYPE or c.ndim != 1
-                    or u.ndim != 3 or u.shape[1:] != (3, 2) or (po is not None and po.size != wh) or ch.shape != (u.shape[0],) or pl.shape != (wh,)):
-                raise ValueError("values: [width * height, k] float32 rows; texels, coords: LIGHTMAP_TEXEL_DTYPE rows; uvs: [n, 3, 2]; pass_of: width * height "
-                                 "bytes; chart_of_triangle: n words; chart_plane: width * height words")
-            out = np.zeros((c.shape[0], out_words), dtype=np.float32)
-            self._chk(self.lib.sol_lightmap_sample_charts(self.h, C.byref(cfg), u.ctypes.data if len(u) else None, u.shape[0], t.ctypes.data,
-                                                          None if po is None else po.ctypes.data, v.ctypes.data, ch.ctypes.data if len(ch) else None,
-                                                          pl.ctypes.data, c.ctypes.data, c.shape[0], out.ctypes.data))
-            return out
-        import torch
-        n_tri = int(uvs.shape[0]) if hasattr(uvs, "shape") and len(uvs.shape) == 3 else 0
-        dev = self._device_pointer
-        args = (dev("uvs", uvs, torch.float32, (None, 3, 2)), n_tri, dev("texels", texels, torch.int32, (wh, 4)), dev("pass_of", pass_of, torch.uint8, (height, width)),
-                dev("values", values, torch.float32, (wh, None)), dev("chart_of_triangle", chart_of_triangle, torch.int32, (n_tri,)),
-                dev("chart_plane", chart_plane, torch.int32, (height, width)), dev("coords", coords, torch.int32, (None, 4)), int(coords.shape[0]))
-        out = torch.empty((int(coords.shape[0]), out_words), dtype=torch.float32, device=values.device)
-        torch.cuda.current_stream(values.device).synchronize()
-        self._chk(self.lib.sol_lightmap_sample_charts_dev(self.h, C.byref(cfg), *args, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        args = (self._atlas_args(uvs, texels, pass_of, values, width, height)
+                + [_Arg("chart_of_triangle", chart_of_triangle, "words", ("n_triangles",), null_if_empty=True, flat=True),
+                   _Arg("chart_plane", chart_plane, "words", (height, width), flat=True), _Arg("coords", coords, "texel", ("n",))])
+        return self._call("sol_lightmap_sample_charts", args, [_Out("out", "f32", ("n", out_words))],
+                          lambda p, d: (C.byref(cfg), p["uvs"], d["n_triangles"], p["texels"], p["pass_of"], p["values"], p["chart_of_triangle"], p["chart_plane"],
+                                        p["coords"], d["n"], p["out"]), device=self._on_device(values))["out"]
 
     def lightmap_chart_levels(self, chart_plane, width, height, pass_of=None):
         """sol_lightmap_chart_levels: how many mip levels the atlas can have before two charts meet in one level - the `levels` to hand to
         lightmap_mips. chart_plane [height, width]: what lightmap_dilate_charts returned; pass_of: its plane, or None (every texel with a chart
         counts). Returns (levels, mixed_texels [15], mixed_windows [15]): per level l >= 1 the texels that hold two charts and the 2 x 2 windows -
         a bilinear footprint - that do. A host array goes the host route, a device tensor the device route."""
-        width, height = int(width), int(height)
-        if isinstance(chart_plane, np.ndarray) or not hasattr(chart_plane, "data_ptr"):  # the host route
-            pl, po = self._host_words("chart_plane", chart_plane), self._host_array(pass_of, np.uint8)
-            if pl.shape != (width * height,) or (po is not None and po.size != width * height):
-                raise ValueError("chart_plane: width * height 32-bit words; pass_of: width * height bytes")
-            levels = C.c_uint32(0)
-            mixed_texels, mixed_windows = np.zeros(_abi.SOL_LIGHTMAP_MAX_LEVELS, dtype=np.uint32), np.zeros(_abi.SOL_LIGHTMAP_MAX_LEVELS, dtype=np.uint32)
-            self._chk(self.lib.sol_lightmap_chart_levels(self.h, pl.ctypes.data, None if po is None else po.ctypes.data, width, height, C.addressof(levels),
-                                                         mixed_texels.ctypes.data, mixed_windows.ctypes.data))
-            return int(levels.value), mixed_texels, mixed_windows
-        import torch
-        d_plane = self._device_pointer("chart_plane", chart_plane, torch.int32, (height, width))
-        d_pass = self._device_pointer("pass_of", pass_of, torch.uint8, (height, width))
-        answer = torch.zeros((1 + 2 * _abi.SOL_LIGHTMAP_MAX_LEVELS,), dtype=torch.int32, device=chart_plane.device)
-        torch.cuda.current_stream(chart_plane.device).synchronize()
-        base = answer.data_ptr()
-        self._chk(self.lib.sol_lightmap_chart_levels_dev(self.h, d_plane, d_pass, width, height, C.c_void_p(base), C.c_void_p(base + 4),
-                                                         C.c_void_p(base + 4 + 4 * _abi.SOL_LIGHTMAP_MAX_LEVELS)))
-        self.sync()
-        words = answer.cpu().numpy().view(np.uint32)
-        return int(words[0]), words[1:1 + _abi.SOL_LIGHTMAP_MAX_LEVELS].copy(), words[1 + _abi.SOL_LIGHTMAP_MAX_LEVELS:].copy()
+        width, height, levels = int(width), int(height), _abi.SOL_LIGHTMAP_MAX_LEVELS
+        words = self._call("sol_lightmap_chart_levels", [_Arg("chart_plane", chart_plane, "words", (height, width), flat=True),
+                                                         _Arg("pass_of", pass_of, "u8", (height, width), optional=True, flat=True)],
+                           [_Out("answer", "u32", (1 + 2 * levels,), zero=True)],  # (the count, then the two rows of counts per level)
+                           lambda p, d: (p["chart_plane"], p["pass_of"], width, height, p["answer"], p["answer"] + 4, p["answer"] + 4 + 4 * levels))["answer"]
+        words = words if isinstance(words, np.ndarray) else words.cpu().numpy().view(np.uint32)
+        return int(words[0]), words[1:1 + levels].copy(), words[1 + levels:].copy()
 
     def lightmap_view_charts(self, values, uvs, texels, chart_of_triangle, chart_plane, width, height, triangle_of_dfs, x0, y0, x1, y1, sample=0, seed=0,
                              **sample_args):
         """The bake seen from the scene's camera with the charts kept apart: camera_rays -> closest_hits -> lightmap_coords ->
         lightmap_sample_charts over the pixels [x0, x1) x [y0, y1), all on device memory. sample_args: what lightmap_sample_charts takes by name
         (channels, pass_of, nearest). Returns an [h, w, channels + 1] float32 device tensor."""
-        rays = self.camera_rays(x0, y0, x1, y1, sample, seed)
-        h, w = int(rays.shape[0]), int(rays.shape[1])
-        coords = self.lightmap_coords(self.closest_hits(rays.reshape(-1, 8)), triangle_of_dfs)
+        _, _, coords, h, w = self._view_coords(triangle_of_dfs, x0, y0, x1, y1, sample, seed)
         out = self.lightmap_sample_charts(values, coords, uvs, texels, chart_of_triangle, chart_plane, width, height, **sample_args)
         return out.reshape(h, w, -1)
 
@@ -1489,30 +1246,14 @@ class DeviceScene:
         """The rows to allocate for `grid`; 1 for a grid the library refuses."""
         return grid.n_probes if all(c > 0 for c in grid.counts) and grid.n_probes <= _abi.SOL_VOLUME_MAX_PROBES else 1
 
-    def _volume_tensor(self, name, x, rows, words):
-        import torch
-        if (not hasattr(x, "data_ptr") or x.dtype != torch.float32 or x.dim() != 2 or (rows is not None and x.shape[0] != rows) or x.shape[1] != words
-                or not x.is_contiguous() or not x.is_cuda or x.device.index != self.device):
-            raise ValueError(f"{name}: a contiguous [{'n' if rows is None else rows}, {words}] float32 tensor on the scene's device")
-        if x.data_ptr() % 16:  # (a view that starts inside an allocation: the kernels move whole 16-byte words)
-            raise ValueError(f"{name}: the tensor's memory must be 16-byte aligned")
-        return C.c_void_p(x.data_ptr())
-
     def volume_points(self, grid, tmin=1e-3, tmax=float("inf"), host=False):
         """sol_volume_points: the rows (position, tmin, (0, 0, 1), tmax) of the probes of `grid` (a VolumeGrid), probe (i, j, k) in row (k * ny + j) *
         nx + i - what irradiance_sh(mode="sphere") and visibility(distances=True) take, with every position on the bits the one volume_sample
         measures from. Returns an [nx * ny * nz, 8] float32 tensor on the scene's device (sol_volume_points_dev), with host=True a numpy array
         (the host route)."""
-        rec, rows = grid.record(), self._volume_rows(grid)
-        if host:
-            out = np.zeros((rows, 8), dtype=np.float32)
-            self._chk(self.lib.sol_volume_points(self.h, C.byref(rec), float(tmin), float(tmax), out.ctypes.data))
-            return out
-        import torch
-        out = torch.empty((rows, 8), dtype=torch.float32, device=f"cuda:{self.device}")
-        self._chk(self.lib.sol_volume_points_dev(self.h, C.byref(rec), float(tmin), float(tmax), C.c_void_p(out.data_ptr())))
-        self.sync()  # (the scene's stream is not torch's)
-        return out
+        rec = grid.record()
+        return self._call("sol_volume_points", [], [_Out("out", "f32", (self._volume_rows(grid), 8))],
+                          lambda p, d: (C.byref(rec), float(tmin), float(tmax), p["out"]), device=not host)["out"]
 
     def volume_build(self, grid, sh, visibility=None, radius=None):
         """sol_volume_build: one SolProbe per probe of `grid` from what irradiance_sh(volume_points(grid), mode="sphere") answered - the sums must be
@@ -1523,35 +1264,14 @@ class DeviceScene:
         or raw [n, 8] rows; returns a VOLUME_PROBE_DTYPE array. Device route: the [n, 28] and [n, 8] float32 tensors of the gathers, without a
         copy; returns the raw [n, 32] float32 device tensor (volume_probes_to_numpy views it)."""
         rec, rows = grid.record(), self._volume_rows(grid)
-        radius = 0.0 if radius is None else float(radius)
-        if isinstance(sh, (tuple, list, np.ndarray)):  # the host route
-            if isinstance(sh, (tuple, list)):
-                sums, counts = sh
-                a = np.concatenate([np.ascontiguousarray(sums, dtype=np.float32).reshape(-1, 27),
-                                    np.ascontiguousarray(counts).astype(np.uint32, copy=False).view(np.float32).reshape(-1, 1)], axis=1)
-            else:
-                a = np.ascontiguousarray(sh, dtype=np.float32)
-            a = np.ascontiguousarray(a)
-            if a.shape != (rows, 28):
-                raise ValueError("sh: the (sums [n, 9, 3], counts [n]) irradiance_sh returned, or raw [n, 28] float32 rows, one per probe of the grid")
-            v = None
-            if visibility is not None:
-                v = self.visibility_to_numpy(visibility) if hasattr(visibility, "data_ptr") else np.ascontiguousarray(visibility)
-                v = v.view(np.float32).reshape(-1, 8) if v.dtype == self.VISIBILITY_DTYPE else np.ascontiguousarray(v, dtype=np.float32)
-                if v.shape != (rows, 8):
-                    raise ValueError("visibility: a VISIBILITY_DTYPE array or raw [n, 8] float32 rows, one per probe of the grid")
-                v = np.ascontiguousarray(v)
-            out = np.zeros(rows, dtype=VOLUME_PROBE_DTYPE)
-            self._chk(self.lib.sol_volume_build(self.h, C.byref(rec), a.ctypes.data, None if v is None else v.ctypes.data, radius, out.ctypes.data))
-            return out
-        import torch
-        p_sh = self._volume_tensor("sh", sh, rows, 28)
-        p_vis = None if visibility is None else self._volume_tensor("visibility", visibility, rows, 8)
-        out = torch.empty((rows, 32), dtype=torch.float32, device=sh.device)
-        torch.cuda.current_stream(sh.device).synchronize()  # (the sums may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_volume_build_dev(self.h, C.byref(rec), p_sh, p_vis, radius, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        if isinstance(sh, (tuple, list)):  # (irradiance_sh's pair: the raw rows again)
+            sums, counts = sh
+            sh = np.concatenate([np.ascontiguousarray(sums, dtype=np.float32).reshape(-1, 27),
+                                 np.ascontiguousarray(counts).astype(np.uint32, copy=False).view(np.float32).reshape(-1, 1)], axis=1)
+        return self._call("sol_volume_build", [_Arg("sh", sh, "f32", (rows, 28), aligned=True),
+                                               _Arg("visibility", visibility, "visibility", (rows,), optional=True, aligned=True)],
+                          [_Out("out", "probe", (rows,))],
+                          lambda p, d: (C.byref(rec), p["sh"], p["visibility"], 0.0 if radius is None else float(radius), p["out"]))["out"]
 
     def volume_sample(self, grid, probes, points, depth=None, res=8):
         """sol_volume_sample: the irradiance at the caller's points - rows of (position xyz, tmin, normal xyz, tmax), irradiance()'s rows; tmin and
@@ -1562,30 +1282,16 @@ class DeviceScene:
         rows, which lightmap_dilate takes as they are. depth (sol_volume_sample_depth): the probes' res x res depth maps as
         volume_build_depth returned them (a DEPTH_TEXEL_DTYPE array, raw [n_probes, res * res, 2] float32 rows, or that device tensor) - the
         Chebyshev weight then reads mean and mean2 from a probe's map in the direction of the point instead of the probe's two isotropic words."""
-        if depth is not None:
-            return self._volume_sample_depth(grid, probes, points, depth, res)
         rec, rows = grid.record(), self._volume_rows(grid)
-        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):  # the host route
-            a = np.ascontiguousarray(points, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError("points: an [n, 8] float32 array of (position xyz, tmin, normal xyz, tmax)")
-            p = volume_probes_to_numpy(probes) if hasattr(probes, "data_ptr") else np.ascontiguousarray(probes)
-            p = p.view(np.float32).reshape(-1, 32) if p.dtype == VOLUME_PROBE_DTYPE else np.ascontiguousarray(p, dtype=np.float32)
-            if p.shape != (rows, 32):
-                raise ValueError("probes: a VOLUME_PROBE_DTYPE array or raw [n, 32] float32 rows, one per probe of the grid")
-            p = np.ascontiguousarray(p)
-            out = np.zeros((a.shape[0], 4), dtype=np.float32)
-            self._chk(self.lib.sol_volume_sample(self.h, C.byref(rec), p.ctypes.data, a.ctypes.data, a.shape[0], out.ctypes.data))
-            return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
-        import torch
-        p_points = self._volume_tensor("points", points, None, 8)
-        p_probes = self._volume_tensor("probes", probes, rows, 32)
-        n = int(points.shape[0])
-        out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
-        torch.cuda.current_stream(points.device).synchronize()  # (the points may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_volume_sample_dev(self.h, C.byref(rec), p_probes, p_points, n, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        args = [_Arg("points", points, "f32", ("n", 8), aligned=True), _Arg("probes", probes, "probe", (rows,), aligned=True)]
+        if depth is None:
+            out = self._call("sol_volume_sample", args, [_Out("out", "f32", ("n", 4))], lambda p, d: (C.byref(rec), p["probes"], p["points"], d["n"], p["out"]))
+        else:
+            oct_cfg = self._oct_config(res)
+            args.append(_Arg("depth", depth, "depth", (rows, self._oct_texels(res)), aligned=True))
+            out = self._call("sol_volume_sample_depth", args, [_Out("out", "f32", ("n", 4))],
+                             lambda p, d: (C.byref(rec), p["probes"], p["depth"], C.byref(oct_cfg), p["points"], d["n"], p["out"]))
+        return self._split(out["out"])
 
     # ---- directional distance moments: octahedral maps (EXTENSION; DESIGN.md 25) ----
     @staticmethod
@@ -1605,9 +1311,8 @@ class DeviceScene:
         route. points, keys, key_base, first_draw and the waits of the two routes are irradiance()'s."""
         cfg = self._irradiance_config(samples, first_sample, seed, key_base, first_draw, mode)
         oct_cfg, texels = self._oct_config(res, sharpness_log2), self._oct_texels(res)
-        rows = self._radiance(lambda h, p, k, n, c, o: self.lib.sol_visibility_oct(h, p, k, n, c, C.byref(oct_cfg), o),
-                              lambda h, p, k, n, c, o: self.lib.sol_visibility_oct_dev(h, p, k, n, c, C.byref(oct_cfg), o), "points",
-                              "position xyz, tmin, normal xyz, tmax", points, keys, cfg, words=4 * texels, raw=True)
+        rows = self._radiance("sol_visibility_oct", "points", points, keys, cfg, words=4 * texels,
+                              call=lambda p, k, n, c, out: (p, k, n, c, C.byref(oct_cfg), out))
         return rows.reshape(-1, texels, 4)
 
     def volume_build_depth(self, grid, oct, radius, res=8, sharpness_log2=5):
@@ -1616,51 +1321,8 @@ class DeviceScene:
         [n_probes, res * res, 2] float32, a numpy array for a host array (DEPTH_TEXEL_DTYPE views it) and a device tensor for a device tensor."""
         rec, rows = grid.record(), self._volume_rows(grid)
         oct_cfg, texels = self._oct_config(res, sharpness_log2), self._oct_texels(res)
-        if isinstance(oct, np.ndarray) or not hasattr(oct, "data_ptr"):  # the host route
-            a = np.ascontiguousarray(oct)
-            a = np.ascontiguousarray(a.view(np.float32) if a.dtype == OCT_TEXEL_DTYPE else a.astype(np.float32, copy=False)).reshape(-1, texels, 4)
-            if a.shape[0] != rows:
-                raise ValueError("oct: [n_probes, res * res, 4] float32 rows as visibility_oct returned them, one map per probe of the grid")
-            out = np.zeros((rows, texels, 2), dtype=np.float32)
-            self._chk(self.lib.sol_volume_build_depth(self.h, C.byref(rec), a.ctypes.data, C.byref(oct_cfg), float(radius), out.ctypes.data))
-            return out
-        import torch
-        p_oct = self._volume_tensor("oct", oct.reshape(oct.shape[0], -1), rows, texels * 4)
-        out = torch.empty((rows, texels, 2), dtype=torch.float32, device=oct.device)
-        torch.cuda.current_stream(oct.device).synchronize()  # (the sums may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_volume_build_depth_dev(self.h, C.byref(rec), p_oct, C.byref(oct_cfg), float(radius), C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
-
-    def _volume_sample_depth(self, grid, probes, points, depth, res):
-        rec, rows = grid.record(), self._volume_rows(grid)
-        oct_cfg, texels = self._oct_config(res), self._oct_texels(res)
-        if isinstance(points, np.ndarray) or not hasattr(points, "data_ptr"):  # the host route
-            a = np.ascontiguousarray(points, dtype=np.float32)
-            if a.ndim != 2 or a.shape[1] != 8:
-                raise ValueError("points: an [n, 8] float32 array of (position xyz, tmin, normal xyz, tmax)")
-            p = volume_probes_to_numpy(probes) if hasattr(probes, "data_ptr") else np.ascontiguousarray(probes)
-            p = p.view(np.float32).reshape(-1, 32) if p.dtype == VOLUME_PROBE_DTYPE else np.ascontiguousarray(p, dtype=np.float32)
-            if p.shape != (rows, 32):
-                raise ValueError("probes: a VOLUME_PROBE_DTYPE array or raw [n, 32] float32 rows, one per probe of the grid")
-            d = np.ascontiguousarray(depth.cpu().numpy() if hasattr(depth, "data_ptr") else depth)
-            d = np.ascontiguousarray(d.view(np.float32) if d.dtype == DEPTH_TEXEL_DTYPE else d.astype(np.float32, copy=False)).reshape(-1, texels, 2)
-            if d.shape[0] != rows:
-                raise ValueError("depth: [n_probes, res * res, 2] float32 rows as volume_build_depth returned them, one map per probe of the grid")
-            out = np.zeros((a.shape[0], 4), dtype=np.float32)
-            self._chk(self.lib.sol_volume_sample_depth(self.h, C.byref(rec), np.ascontiguousarray(p).ctypes.data, d.ctypes.data, C.byref(oct_cfg), a.ctypes.data,
-                                                       a.shape[0], out.ctypes.data))
-            return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3]).view(np.uint32)
-        import torch
-        p_points = self._volume_tensor("points", points, None, 8)
-        p_probes = self._volume_tensor("probes", probes, rows, 32)
-        p_depth = self._volume_tensor("depth", depth.reshape(depth.shape[0], -1) if hasattr(depth, "data_ptr") else depth, rows, texels * 2)
-        n = int(points.shape[0])
-        out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
-        torch.cuda.current_stream(points.device).synchronize()  # (the points may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_volume_sample_depth_dev(self.h, C.byref(rec), p_probes, p_depth, C.byref(oct_cfg), p_points, n, C.c_void_p(out.data_ptr())))
-        self.sync()
-        return out
+        return self._call("sol_volume_build_depth", [_Arg("oct", oct, "oct", (rows, texels), aligned=True)], [_Out("out", "f32", (rows, texels, 2))],
+                          lambda p, d: (C.byref(rec), p["oct"], C.byref(oct_cfg), float(radius), p["out"]))["out"]
 
     def camera_ray_keys(self, x0, y0, x1, y1, sample, seed):
         """sol_camera_ray_keys: (pixel, first_draw) of the camera rays of pixels [x0, x1) x [y0, y1) for (sample, seed) as an [h, w, 2] int32 device
@@ -1700,19 +1362,8 @@ class DeviceScene:
         device goes through sol_scene_set_triangles_dev without a copy. Clears the sums and the auxiliary planes, ends an adaptive session; blocks."""
         upd = _abi.SolGeometryUpdate(size=C.sizeof(_abi.SolGeometryUpdate),
                                      flags=(0 if background_proof else _abi.SOL_GEOM_NO_BACKGROUND_PROOF) | (_abi.SOL_GEOM_REPROBE if reprobe else 0))
-        if isinstance(vertices, np.ndarray) or not hasattr(vertices, "data_ptr"):
-            a = np.ascontiguousarray(vertices, dtype=np.float64)
-            if a.ndim != 3 or a.shape[1:] != (3, 3):
-                raise ValueError("vertices: a float64 [n, 3, 3] array of (v0, v1, v2)")
-            self._chk(self.lib.sol_scene_set_triangles(self.h, a.ctypes.data, a.shape[0], C.byref(upd)))
-            return
-        import torch
-        if vertices.dtype != torch.float64 or vertices.dim() != 3 or tuple(vertices.shape[1:]) != (3, 3) or not vertices.is_contiguous() or not vertices.is_cuda:
-            raise ValueError("vertices: a contiguous float64 [n, 3, 3] tensor on the scene's device")
-        if vertices.device.index != self.device:
-            raise ValueError(f"vertices: the tensor is on cuda:{vertices.device.index}, the scene on cuda:{self.device}")
-        torch.cuda.current_stream(vertices.device).synchronize()  # (the vertices may still be in the making on torch's stream: the scene's is another)
-        self._chk(self.lib.sol_scene_set_triangles_dev(self.h, C.c_void_p(vertices.data_ptr()), int(vertices.shape[0]), C.byref(upd)))
+        self._call("sol_scene_set_triangles", [_Arg("vertices", vertices, "f64", ("n", 3, 3))], [], lambda p, d: (p["vertices"], d["n"], C.byref(upd)),
+                   sync=False)  # (the move blocks by itself)
 
     def set_triangles_ms(self):
         """sol_scene_set_triangles_ms: device-event ms of the last timed move: upload, records, refit, rest."""
@@ -1747,30 +1398,17 @@ class DeviceScene:
         given = {k: v for k, v in given.items() if v[0] is not None}
         if not given:
             raise ValueError("set_primitives: at least one of triangles, spheres, quads")
-        on_device = [not isinstance(a, np.ndarray) and hasattr(a, "data_ptr") for a, _ in given.values()]
+        on_device = [self._on_device(a) for a, _ in given.values()]
         if any(on_device) and not all(on_device):
             raise ValueError("set_primitives: host arrays and device tensors in one call (give all kinds the same way)")
         ps = _abi.SolPrimitiveSet(size=C.sizeof(_abi.SolPrimitiveSet), flags=_abi.SOL_PRIMS_DEVICE if on_device[0] else 0)
         keep = []
         for name, (a, shape) in given.items():
-            what = f"{name}: a contiguous float64 [n, {', '.join(map(str, shape))}] " + ("tensor on the scene's device" if on_device[0] else "array")
-            if on_device[0]:
-                import torch
-                if a.dtype != torch.float64 or a.dim() != 1 + len(shape) or tuple(a.shape[1:]) != shape or not a.is_contiguous() or not a.is_cuda:
-                    raise ValueError(what)
-                if a.device.index != self.device:
-                    raise ValueError(f"{name}: the tensor is on cuda:{a.device.index}, the scene on cuda:{self.device}")
-                torch.cuda.current_stream(a.device).synchronize()  # (the rows may still be in the making on torch's stream: the scene's is another)
-                ptr = a.data_ptr()
-            else:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                if a.ndim != 1 + len(shape) or a.shape[1:] != shape:
-                    raise ValueError(what)
-                ptr = a.ctypes.data
-            keep.append(a)
+            p, d, staged = self._stage([_Arg(name, a, "f64", ("n",) + shape)], on_device[0])
+            keep += staged
             # (an empty array's pointer may be null: the kind is given all the same)
-            setattr(ps, name, C.c_void_p(ptr or 16))
-            setattr(ps, "n_" + name, int(a.shape[0]))
+            setattr(ps, name, C.c_void_p(p[name] or 16))
+            setattr(ps, "n_" + name, d["n"])
         self._chk(self.lib.sol_scene_set_primitives(self.h, C.byref(ps), C.byref(upd)))
 
     SPHERE_DTYPE = np.dtype([("c", np.float32, 3), ("radius", np.float32), ("dfs", np.uint32), ("mat", np.int32), ("pad", np.uint32, 2)])
