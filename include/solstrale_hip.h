@@ -1573,6 +1573,73 @@ int sol_lightmap_chart_levels_dev(SolScene* scene, const void* chart_plane_dev, 
 int sol_lightmap_chart_levels(SolScene* scene, const uint32_t* chart_plane, const uint8_t* pass_of, uint32_t width, uint32_t height,
                               uint32_t* levels_out, uint32_t* mixed_texels_out, uint32_t* mixed_windows_out);
 
+/* ---- lightmap unwrap: box-projected charts packed into an atlas (EXTENSION, not in the reference) ---------------------------
+ * The first link of the lightmap chain: vertices -> (uvs, chart_of_triangle, result). uvs is the [n, 3, 2] array every other lightmap call
+ * takes, chart_of_triangle what sol_lightmap_dilate_charts and sol_lightmap_sample_charts take. Deterministic: the words depend on the arguments
+ * alone, whatever the schedule. fp32 with one rounding per operation, `/` and sqrtf correctly rounded; tests/lightmap_unwrap_ref.py restates
+ * the rule in numpy float32 and the device equals it word for word. The rule, operation by operation (csrc/sol_lightmap_unwrap.h):
+ *   Triangle.   Live when its nine words are finite and n = cross(v1 - v0, v2 - v0) has a dot(n, n) = (nx nx + ny ny) + nz nz that is finite,
+ *               not zero and not subnormal (sol_lightmap_points' rule). Its class is (a, s): a the index of the largest |n_k|, the lowest on a
+ *               tie, s the sign of n_a. Its unit normal is n / sqrt(dot(n, n)), a division per component. A dead triangle gets SOL_CHART_NONE
+ *               and six +0 UV words; sol_lightmap_points lets it claim nothing.
+ *   Charts.     Two live triangles are joined when they share an edge (the canonical end point words of sol_lightmap_charts over the positions
+ *               alone, equal word for word; the hash decides nothing), have the same class, and (ux_a ux_b + uy_a uy_b) + uz_a uz_b >=
+ *               crease_cos. With crease_cos = -1 the class alone decides. Every pair of triangles on one edge is judged. Charts are the
+ *               connected components, ids dense and in mesh order: a chart's id is the rank of its lowest triangle.
+ *   Projection. A corner projects to the coordinates ((a + 1) % 3, (a + 2) % 3) of its position, each (p * texels_per_unit) + 0.0f.
+ *   Extent.     Per chart and axis the minimum lo and maximum hi over its corners, f = floor(lo), e = (floor(hi) + 1) - f. The content
+ *               rectangle is e + 2 texels: the e whole texels the corners span and a guard texel on each side, which a conservative claim of
+ *               a corner on a whole texel line may take. An e outside 1 .. 32765 (a chart no atlas holds) is reported as content 32767.
+ *   Packing.    A chart's rectangle is its content plus `gutter` each way (the gutter to the right and above). Rectangles are sorted by height
+ *               descending, then width descending, then chart id ascending, and walked in that order by the greedy shelf rule: a rectangle
+ *               joins the current shelf at x while x + w <= width, otherwise it opens the next shelf at x = 0 above the one it leaves; a shelf
+ *               is as high as its first rectangle. The walk stops once the shelves' height passes SOL_LIGHTMAP_MAX_SIZE.
+ *   UVs.        u = ((x - f_x) + (float)(rect_x + 1)) / (float)width, v = ((y - f_y) + (float)(rect_y + 1)) / (float)height. Corners that
+ *               share a position inside a chart get identical words.
+ *   Result.     n_charts; live_triangles; used_width, the widest shelf; used_height, the shelves' height; overflow - bit 0: a rectangle is
+ *               wider than the atlas, bit 1: used_height > height; content_texels, the sum of the content rectangles (fill ratio:
+ *               content_texels / (width x used_height)). On overflow the call still returns SOL_OK: every UV word is +0, every label
+ *               SOL_CHART_NONE, and the result carries the sizes, so that a caller can choose another density.
+ * Density is that of the projection: a tilted face gets up to sqrt(3) fewer texels along one direction. Self-overlap is NOT detected: the join
+ * rule keeps a chart one-to-one in projection locally (a fold flips the class), but a connected surface that passes over itself along its axis,
+ * such as a spiral ramp, lands on itself in the atlas. A larger crease_cos cuts such charts apart.
+ * No scene: nothing is traced, no handle is read. Both routes allocate their scratch for the call and free it after waiting for the stream:
+ * BOTH BLOCK, the device route too. SOL_LIGHTMAP_UNWRAP=collide (read at every call) masks the edge hash to 4 bits, the tested worst case of the
+ * match; the words do not change. SOL_LIGHTMAP_UNWRAP=stages times the stages (sol_lightmap_unwrap_stage_ms).
+ * SOL_EINVAL (sol_last_error names the call and the reason), before the device is looked for and in this order: a null configuration; a wrong
+ * size; reserved != 0; unknown flag bits; width or height of 0 or above 16384; gutter above 64; a texels_per_unit that is not finite and > 0; a
+ * crease_cos outside [-1, 1]; n_triangles > SOL_LIGHTMAP_CHARTS_MAX_TRIANGLES; with n_triangles > 0 a null vertex, UV output or label output
+ * pointer; a null result pointer. Then the host form with n_triangles == 0 writes a zero result and succeeds. SOL_EDEVICE without a GPU comes
+ * after all of these. */
+#define SOL_UNWRAP_MAX_GUTTER 64u
+#define SOL_UNWRAP_OVERFLOW_WIDTH 1u  /* SolUnwrapResult.overflow: a chart with its gutter is wider than the atlas */
+#define SOL_UNWRAP_OVERFLOW_HEIGHT 2u /* used_height > height */
+typedef struct SolUnwrapConfig {
+  uint32_t size;          /* sizeof(SolUnwrapConfig) */
+  uint32_t width, height; /* the atlas in texels; height is the most the packing may use */
+  uint32_t gutter;        /* texels between the contents of two charts, 0 .. 64 */
+  float texels_per_unit;  /* finite, > 0 */
+  float crease_cos;       /* -1 .. 1; -1: the class rule alone decides */
+  uint32_t flags;         /* none yet */
+  uint32_t reserved;
+} SolUnwrapConfig;
+typedef struct SolUnwrapResult {
+  uint32_t n_charts, live_triangles;
+  uint32_t used_width, used_height;
+  uint32_t overflow, reserved;
+  uint64_t content_texels;
+} SolUnwrapResult;
+/* Host arrays (n_triangles x 9 floats in; n_triangles x 6 floats, n_triangles words and one result out); blocks. */
+int sol_lightmap_unwrap(int device, const SolUnwrapConfig* config, const float* vertices, size_t n_triangles, float* uvs_out,
+                        uint32_t* chart_of_triangle_out, SolUnwrapResult* result_out);
+/* Device pointers of `device`, launched on hip_stream (a hipStream_t, NULL: the default stream); blocks until the stream has finished. */
+int sol_lightmap_unwrap_dev(int device, void* hip_stream, const SolUnwrapConfig* config, const void* vertices_dev, size_t n_triangles,
+                            void* uvs_out_dev, void* chart_of_triangle_out_dev, void* result_out_dev);
+/* Measurement: with SOL_LIGHTMAP_UNWRAP=stages in the environment a call records device events around its stages; this copies the calling
+ * thread's last such call as 8 floats of milliseconds - normals and hash, sort, unions and ids, extents, rectangles and their sort, pack, write,
+ * and all of them (launches only: the scratch is allocated before the first event and freed after the last). Zeros before any. */
+int sol_lightmap_unwrap_stage_ms(float* stage_ms_out);
+
 /* ---- a new camera for a live scene (EXTENSION, not in the reference) -------------------------------------------------------
  * A handle owns what is expensive and does not depend on the camera: the world tree, the records and textures, the light tree, the environment
  * tables. sol_scene_set_camera looks at the same scene from another viewpoint without building any of it again. After it returns SOL_OK every

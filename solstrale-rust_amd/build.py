@@ -32,10 +32,11 @@ HIP_SRC = ["csrc/sol_render.hip", "csrc/sol_aux.hip", "csrc/sol_build.hip", "csr
            "csrc/sol_lightmap_sample.hip", "csrc/sol_lightmap_sample.cpp",
            "csrc/sol_lightmap_sh.hip", "csrc/sol_lightmap_sh.cpp",
            "csrc/sol_lightmap_mips.hip", "csrc/sol_lightmap_mips.cpp",
-           "csrc/sol_lightmap_charts.hip", "csrc/sol_lightmap_charts.cpp"]
+           "csrc/sol_lightmap_charts.hip", "csrc/sol_lightmap_charts.cpp",
+           "csrc/sol_lightmap_unwrap.hip", "csrc/sol_lightmap_unwrap.cpp"]
 HIP_HDR = ["csrc/sol_types.h", "csrc/sol_math.h", "csrc/sol_trace.h", "csrc/sol_shade.h", "csrc/sol_path.h", "csrc/sol_launch.h",
            "csrc/sol_tree.h", "csrc/sol_build.h", "csrc/sol_scene.h", "csrc/sol_camera.h", "csrc/sol_triangle.h", "csrc/sol_primitive.h", "csrc/sol_geometry.h", "csrc/sol_quant.h", "csrc/sol_wide.h", "csrc/sol_proof.h", "csrc/sol_ray.h", "csrc/sol_wave.h",
-           "csrc/sol_sh.h", "csrc/sol_radiance_body.h", "csrc/sol_lightmap.h", "csrc/sol_lightmap_filter.h", "csrc/sol_lightmap_filter_var.h", "csrc/sol_gather.h", "csrc/sol_stage.h", "csrc/sol_bake_checks.h", "csrc/sol_gather_adaptive.h", "csrc/sol_volume.h", "csrc/sol_depth.h", "csrc/sol_lightmap_sample.h", "csrc/sol_lightmap_lookup.h", "csrc/sol_lightmap_sh.h", "csrc/sol_lightmap_mips.h", "csrc/sol_lightmap_charts.h", "../include/solstrale_hip.h"]
+           "csrc/sol_sh.h", "csrc/sol_radiance_body.h", "csrc/sol_lightmap.h", "csrc/sol_lightmap_filter.h", "csrc/sol_lightmap_filter_var.h", "csrc/sol_gather.h", "csrc/sol_stage.h", "csrc/sol_bake_checks.h", "csrc/sol_gather_adaptive.h", "csrc/sol_volume.h", "csrc/sol_depth.h", "csrc/sol_lightmap_sample.h", "csrc/sol_lightmap_lookup.h", "csrc/sol_lightmap_sh.h", "csrc/sol_lightmap_mips.h", "csrc/sol_lightmap_charts.h", "csrc/sol_lightmap_unwrap.h", "../include/solstrale_hip.h"]
 HOST_SRC = ["host/solstrale_host.cpp", "host/solstrale_obj.cpp", "host/solstrale_host_c.cpp"]
 HOST_DEPS = HOST_SRC + ["host/solstrale.hpp", "../include/solstrale_hip.h", "../include/solstrale_host.h"]
 EXAMPLES = ["examples/profiling.cpp"]  # native programs over the C++ host mirror (the reference's src/bin/profiling.rs); no Python, no torch

@@ -222,6 +222,24 @@ struct LcScratch {
 hipError_t sol_lightmap_charts_scratch(uint32_t n, LcScratch& S);
 hipError_t sol_launch_lightmap_charts(const void* uvs, const void* vertices, uint32_t n, bool collide, const LcScratch& S, uint32_t* scratch, void* chart_of,
                                       void* n_charts, hipStream_t stream);
+// chart_ids: the tail of the labelling, which the unwrap shares - parent (a union-find over n triangles, in the scratch) flattened, the roots
+// flagged and ranked; chart_of holds SOL_LC_NONE for a dead triangle going in, the dense ids coming out
+hipError_t sol_launch_lightmap_chart_ids(uint32_t n, const LcScratch& S, uint32_t* scratch, void* chart_of, void* n_charts, hipStream_t stream);
+// ---- sol_lightmap_unwrap.hip: the lightmap unwrap. The scratch of a call is sized once, by the entry point: a labelling's (C),
+// then offsets in words of the triangles' normals and classes (four per triangle), the counters, the shelves' two tables and rocPRIM's own for
+// the second sort and the prefix sum. The rectangles' arrays live in the words of C the labelling is done with (keys .. order) ----
+struct LuScratch {
+  LcScratch C;
+  size_t nrm, misc, shelf_first, shelf_y, tmp, words;
+  size_t sort_bytes, scan_bytes;
+};
+struct SolUnwrapConfig;
+// stages: null, or SOL_LU_STAGES + 1 events recorded around the stages - normals and hash, sort, unions and ids, extents, rectangles and their
+// sort, pack, write (not for n == 0)
+#define SOL_LU_STAGES 7
+hipError_t sol_lightmap_unwrap_scratch(uint32_t n, LuScratch& S);
+hipError_t sol_launch_lightmap_unwrap(const SolUnwrapConfig& c, const void* vertices, uint32_t n, bool collide, const LuScratch& S, uint32_t* scratch,
+                                      void* uvs, void* chart_of, void* result, hipStream_t stream, hipEvent_t* stages);
 // dilate_charts: as the dilation's two launches, with the labels in and the chart plane beside `out`; the plane is written in place (a pass reads
 // the words of texels covered before it and writes those of texels that were not)
 hipError_t sol_launch_lightmap_dilate_charts_begin(const void* texels, uint32_t n_texels, const void* values, uint32_t stride_words, const void* chart_of,

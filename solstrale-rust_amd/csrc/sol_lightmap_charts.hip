@@ -320,8 +320,7 @@ hipError_t sol_launch_lightmap_charts(const void* uvs, const void* vertices, uin
   const uint32_t E = n * 3u;
   uint64_t* keys = (uint64_t*)(scratch + S.keys);
   uint64_t* keys2 = (uint64_t*)(scratch + S.keys2);
-  uint32_t *vals = scratch + S.vals, *order = scratch + S.order, *parent = scratch + S.parent, *root = scratch + S.root, *flag = scratch + S.flag,
-           *rank = scratch + S.rank;
+  uint32_t *vals = scratch + S.vals, *order = scratch + S.order, *parent = scratch + S.parent;
   void* tmp = scratch + S.tmp;
   hipLaunchKernelGGL(sol_lightmap_charts_hash_kernel, dim3(lc_blocks(n)), dim3(LC_WG), 0, stream, (const float*)uvs, (const float*)vertices, n,
                      collide ? 0xFull : ~0ull, keys, vals, parent, (uint32_t*)chart_of);
@@ -330,10 +329,17 @@ hipError_t sol_launch_lightmap_charts(const void* uvs, const void* vertices, uin
   if ((e = rocprim::radix_sort_pairs(tmp, bytes, keys, keys2, vals, order, (size_t)E, 0, collide ? 4 : 64, stream)) != hipSuccess) return e;
   hipLaunchKernelGGL(sol_lightmap_charts_match_kernel, dim3(lc_blocks(E)), dim3(LC_WG), 0, stream, (const float*)uvs, (const float*)vertices, E,
                      (const uint64_t*)keys2, (const uint32_t*)order, (const uint32_t*)chart_of, parent);
+  return sol_launch_lightmap_chart_ids(n, S, scratch, chart_of, n_charts, stream);
+}
+
+hipError_t sol_launch_lightmap_chart_ids(uint32_t n, const LcScratch& S, uint32_t* scratch, void* chart_of, void* n_charts, hipStream_t stream) {
+  hipError_t e;
+  uint32_t *parent = scratch + S.parent, *root = scratch + S.root, *flag = scratch + S.flag, *rank = scratch + S.rank;
+  void* tmp = scratch + S.tmp;
   hipLaunchKernelGGL(sol_lightmap_charts_flatten_kernel, dim3(lc_blocks(n)), dim3(LC_WG), 0, stream, n, (const uint32_t*)parent, (const uint32_t*)chart_of, root,
                      flag);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  bytes = S.scan_bytes;
+  size_t bytes = S.scan_bytes;
   if ((e = rocprim::exclusive_scan(tmp, bytes, flag, rank, 0u, (size_t)n, rocprim::plus<uint32_t>(), stream)) != hipSuccess) return e;
   hipLaunchKernelGGL(sol_lightmap_charts_ids_kernel, dim3(lc_blocks(n)), dim3(LC_WG), 0, stream, n, (const uint32_t*)root, (const uint32_t*)flag,
                      (const uint32_t*)rank, (uint32_t*)chart_of, (uint32_t*)n_charts);

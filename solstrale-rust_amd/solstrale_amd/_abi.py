@@ -274,6 +274,23 @@ class SolLightmapSampleConfig(C.Structure):
 SOL_LIGHTMAP_SAMPLE_NEAREST, SOL_LIGHTMAP_TABLE_ROTATION_SHIFT, SOL_LIGHTMAP_TABLE_TRIANGLE_MASK = 1, 30, 0x3FFFFFFF
 
 
+class SolUnwrapConfig(C.Structure):
+    """EXTENSION: the configuration of sol_lightmap_unwrap: size = sizeof, the atlas W x H in texels, the gutter (0 .. 64), the
+    density, the crease cosine (-1 .. 1), flags = 0, reserved = 0. 32 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("size", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("gutter", C.c_uint32), ("texels_per_unit", C.c_float),
+                ("crease_cos", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SolUnwrapResult(C.Structure):
+    """EXTENSION: what sol_lightmap_unwrap reports: charts, live triangles, the atlas the packing used, the overflow bits
+    (SOL_UNWRAP_OVERFLOW_WIDTH, _HEIGHT) and the sum of the content rectangles. 32 bytes. Not in ABI_STRUCTS."""
+    _fields_ = [("n_charts", C.c_uint32), ("live_triangles", C.c_uint32), ("used_width", C.c_uint32), ("used_height", C.c_uint32),
+                ("overflow", C.c_uint32), ("reserved", C.c_uint32), ("content_texels", C.c_uint64)]
+
+
+SOL_UNWRAP_MAX_GUTTER, SOL_UNWRAP_OVERFLOW_WIDTH, SOL_UNWRAP_OVERFLOW_HEIGHT = 64, 1, 2
+
+
 class SolLightmapShConfig(C.Structure):
     """EXTENSION: the configuration of sol_lightmap_sh: size = sizeof, W x H texels, the stride of the SolSh9 rows (>= 112, a
     multiple of 16), flags (SOL_LIGHTMAP_SH_*), the radius of the chart guard (> 0; +inf: off), the caller's factor on E, reserved = 0. 32 bytes.
@@ -540,6 +557,10 @@ def load_hip():
                                   C.c_void_p, C.c_size_t, C.c_void_p])
     for name in ("sol_lightmap_chart_levels_dev", "sol_lightmap_chart_levels"):
         _sig(lib, name, C.c_int, [P, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_unwrap", C.c_int, [C.c_int, C.POINTER(SolUnwrapConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p])
+    _sig(lib, "sol_lightmap_unwrap_stage_ms", C.c_int, [C.POINTER(C.c_float)])
+    _sig(lib, "sol_lightmap_unwrap_dev", C.c_int, [C.c_int, C.c_void_p, C.POINTER(SolUnwrapConfig), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p])
     _sig(lib, "sol_volume_points_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_points", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_float, C.c_float, C.c_void_p])
     _sig(lib, "sol_volume_build_dev", C.c_int, [P, C.POINTER(SolVolumeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p])
@@ -593,6 +614,7 @@ HIP_SYMBOLS = ["sol_device_count", "sol_scene_create", "sol_scene_destroy", "sol
                "sol_lightmap_lod_dev", "sol_lightmap_lod",
                "sol_lightmap_charts_dev", "sol_lightmap_charts", "sol_lightmap_dilate_charts_dev", "sol_lightmap_dilate_charts",
                "sol_lightmap_sample_charts_dev", "sol_lightmap_sample_charts", "sol_lightmap_chart_levels_dev", "sol_lightmap_chart_levels",
+               "sol_lightmap_unwrap_dev", "sol_lightmap_unwrap", "sol_lightmap_unwrap_stage_ms",
                "sol_volume_points_dev", "sol_volume_points", "sol_volume_build_dev", "sol_volume_build", "sol_volume_sample_dev", "sol_volume_sample",
                "sol_visibility_oct_dev", "sol_visibility_oct", "sol_volume_build_depth_dev", "sol_volume_build_depth", "sol_volume_sample_depth_dev",
                "sol_volume_sample_depth"]

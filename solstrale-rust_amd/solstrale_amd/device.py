@@ -1468,3 +1468,82 @@ class DeviceScene:
         st = _abi.SolStats()
         self._chk(self.lib.sol_stats(self.h, C.byref(st)))
         return st.as_dict()
+
+
+# ---- lightmap unwrap (EXTENSION): no scene, so no DeviceScene ----
+class _DeviceCalls(DeviceScene):
+    """The two-route call path (DeviceScene._stage and _call) for entry points that take a device index where the others take a
+    handle: the index stands in the handle's place, and there is nothing to create or destroy."""
+
+    def __init__(self, device):
+        self.lib = _abi.load_hip()
+        self.device = int(device)
+        self.h = int(device)
+
+    def close(self):
+        pass
+
+
+UnwrapResult = namedtuple("UnwrapResult", "n_charts live_triangles used_width used_height overflow content_texels")
+UnwrapFit = namedtuple("UnwrapFit", "uvs chart_of_triangle result texels_per_unit overflow_at")
+UNWRAP_OVERFLOW_WIDTH, UNWRAP_OVERFLOW_HEIGHT = _abi.SOL_UNWRAP_OVERFLOW_WIDTH, _abi.SOL_UNWRAP_OVERFLOW_HEIGHT
+
+
+def lightmap_unwrap(vertices, width, height, texels_per_unit, gutter=2, crease_cos=-1.0, device=0):
+    """sol_lightmap_unwrap: lightmap UVs for a mesh. vertices [n, 3, 3] float32. Charts are the connected pieces of the mesh whose triangles face
+    the same way along the same dominant axis (and, across an edge, whose unit normals have a dot product >= crease_cos); each is projected
+    along that axis at texels_per_unit and the charts are packed by the greedy shelf rule into a width x height atlas with `gutter` texels
+    between them. Returns (uvs [n, 3, 2] float32, chart_of_triangle [n], result): what lightmap_points, lightmap_dilate_charts and
+    lightmap_sample_charts take. When result.overflow is not 0 - bit 0: a chart is wider than the atlas, bit 1: used_height > height - the UVs
+    are zero and the labels CHART_NONE; the sizes are still reported (lightmap_unwrap_fit looks for a density that fits). Self-overlapping
+    charts (a spiral ramp) are not detected: raise crease_cos to cut them. Host arrays go the host route; device tensors of `device` the device
+    route, on torch's current stream, and return tensors (the labels as int32 words). Both routes block."""
+    calls = _DeviceCalls(device)
+    on_device = calls._on_device(vertices)
+    cfg = _abi.SolUnwrapConfig(size=C.sizeof(_abi.SolUnwrapConfig), width=int(width), height=int(height), gutter=int(gutter),
+                               texels_per_unit=float(texels_per_unit), crease_cos=float(crease_cos))
+    stream = ()
+    if on_device:
+        import torch
+        stream = (C.c_void_p(torch.cuda.current_stream(calls.device).cuda_stream),)
+    out = calls._call("sol_lightmap_unwrap", [_Arg("vertices", vertices, "f32", ("n", 3, 3), null_if_empty=True)],
+                      [_Out("uvs", "f32", ("n", 3, 2), null_if_empty=True), _Out("chart_of", "u32", ("n",), null_if_empty=True),
+                       _Out("result", "u32", (8,), zero=True)],
+                      lambda p, d: stream + (C.byref(cfg), p["vertices"], d["n"], p["uvs"], p["chart_of"], p["result"]), device=on_device, sync=False)
+    words = (out["result"].cpu().numpy() if on_device else out["result"]).view(np.uint32)
+    result = UnwrapResult(*(int(w) for w in words[:5]), int(words[6]) | (int(words[7]) << 32))
+    return out["uvs"], out["chart_of"], result
+
+
+def lightmap_unwrap_fit(vertices, width, height, gutter=2, crease_cos=-1.0, device=0, steps=16):
+    """The densest lightmap_unwrap that fits: texels_per_unit is doubled from one texel over the mesh's largest extent until the unwrap
+    overflows, then bisected `steps` times between the last density that fit and the first that did not. Returns UnwrapFit(uvs,
+    chart_of_triangle, result, texels_per_unit, overflow_at): the densest probe that fit and the least density probed that overflowed - one
+    bisection step denser. No device code of its own: every probe is one lightmap_unwrap. The defaults (gutter,
+    steps, the starting density) are not tuned. Raises ValueError when even the starting density overflows (more charts than the atlas has
+    room for at any density)."""
+    v = vertices.detach().cpu().numpy() if DeviceScene._on_device(vertices) else np.asarray(vertices, dtype=np.float32)
+    v = v.reshape(-1, 3)
+    v = v[np.isfinite(v).all(axis=1)]
+    extent = float((v.max(axis=0) - v.min(axis=0)).max()) if len(v) else 0.0
+    lo = 1.0 / extent if extent > 0 else 1.0
+
+    def probe(t):
+        return lightmap_unwrap(vertices, width, height, t, gutter=gutter, crease_cos=crease_cos, device=device)
+    best = probe(lo)
+    if best[2].overflow:
+        raise ValueError(f"lightmap_unwrap_fit: {best[2].n_charts} charts overflow a {width} x {height} atlas at every density")
+    hi = lo * 2.0
+    for _ in range(64):  # (2^64 times the starting density: no atlas holds that)
+        out = probe(hi)
+        if out[2].overflow:
+            break
+        best, lo, hi = out, hi, hi * 2.0
+    for _ in range(int(steps)):
+        mid = 0.5 * (lo + hi)
+        out = probe(mid)
+        if out[2].overflow:
+            hi = mid
+        else:
+            best, lo = out, mid
+    return UnwrapFit(*best, lo, hi)
